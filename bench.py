@@ -9,13 +9,18 @@ the host) against a resident 1M-point map.  Inputs are resident in HBM before th
 f-1/f-2).  Every step restarts from the same predicted prior, so all steps do the
 same work and produce the same pose.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 For N > 1 the driver launches it under torch.distributed.run (one rank per GPU); a plain `python bench.py --gpus N` starts
 the N ranks itself (self_launch).  The path shards
 by independent scan streams (config 5): no data-path collective, weak scaling; torch.distributed is
 used only for the barrier and the max-over-ranks time.
 
-Rank 0 prints ONE JSON line (see the contract in the task description) with these extra objects:
+A plain run sets up, runs W warm-up steps, times K steps and prints ONE JSON line from rank 0: `value` (scans/s), `ms_per_step`
+(one timed step), `config`, `host_us_per_step`.  --dump-outputs DIR writes what the last timed step computed -- the registered
+state `state_x` [26], its covariance `state_P` [23, 23] and the pose covariance `pose_cov` [6, 6], float64 -- as DIR/<name>.npy
+(ranks > 0: DIR/<name>_rank<r>.npy).  The inputs are synthetic with fixed seeds, identical from run to run.
+
+--full adds every other figure to the same line (the --no-* options leave some of them out):
   roofline      dominant kernel = the one-launch measurement pass (k-NN fast path + in-kernel widening + plane fit +
                 residual / Jacobian + H^T H reduction, `knn5_kernel<2, 8, true, false>`): ALGORITHMIC bytes per launch / its mean
                 launch duration from HIP events attached to the dispatch during the timed region, vs 8 TB/s HBM; `stage`
@@ -24,6 +29,7 @@ Rank 0 prints ONE JSON line (see the contract in the task description) with thes
   end_to_end    the same scan from a host cloud: filters + time sort + upload + deskew + update + map insert
   cpu_baseline  the CPU oracle (a restatement of the reference algorithm, "port") timed on this box's
                 host cores on the same scan / map, N = 1 only
+  and value_regions, update_layouts, with_map_insert, concurrent_streams (see main()).
 """
 from __future__ import annotations
 
@@ -572,6 +578,11 @@ def main():
     ap.add_argument("--with-insert", action="store_true",
                     help="time the step WITH the path exit (transform + map insert) over six steps instead of the default two "
                          "(first insertion + one repeat), for a steadier 'repeat' figure")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline figure: roofline (+ hbm_regime, crowded), "
+                         "cpu_baseline, end_to_end, value_regions, update_layouts, with_map_insert, concurrent_streams")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (state_x, state_P, pose_cov; float64) as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -696,10 +707,17 @@ def main():
     n_passes = loc.hip.pass_count() - passes0
     n_fused_passes = loc.hip.fused_pass_count() - fused0
     hp = loc.host_profile()
+    # what the last timed step handed its caller: the registered state and its covariances (every step starts from the same prior)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = "" if rank == 0 else "_rank%d" % rank
+        for name, arr in (("state_x", loc.get_x()), ("state_P", loc.get_P()), ("pose_cov", loc.pose_cov())):
+            np.save(os.path.join(args.dump_outputs, name + sfx + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    # Everything below up to the result line, other than the reproducibility checks, runs with --full only.
     # The spread of the timed region: the same K-step region nine more times, untimed by events (timing level 0), right after `value`'s
     # (the driver's 20 steps last 3 ms; one region is a thin sample)
     value_regions = None
-    if rank == 0:
+    if rank == 0 and args.full:
         loc.hip.set_timing(0)
         regs = []
         for _ in range(9):
@@ -721,7 +739,7 @@ def main():
     # The update's two layouts on THIS host, the same K steps each (informational; `value` above is the layout the library chose by
     # its launch round-trip measurement): the chain queued at once and the host loop over single passes
     modes = None
-    if rank == 0:
+    if rank == 0 and args.full:
         um = loc.hip.update_mode()
         modes = {"chosen": "chain" if um["chained"] else "host_loop", "launch_round_trip_us": um["launch_rtt_us"]}
         for name, mode in (("chain", 2), ("host_loop", 1)):
@@ -740,7 +758,7 @@ def main():
             step()
     dense = None
     kernel_us_per_step = None
-    if int(os.environ.get('FLIMO_BENCH_TIMING', '1')) == 1:
+    if args.full and int(os.environ.get('FLIMO_BENCH_TIMING', '1')) == 1:
         loc.hip.set_timing_stride(1)
         # (the series as rounds 3-5 ran it, each pass's events read right behind it: the host's reading leaves the GPU idle half
         # of the time, and on some boxes its clocks follow -- kept as a second figure, never the one the roofline uses)
@@ -779,7 +797,7 @@ def main():
     # the k-NN STAGE on its own (fast path + widening, no fit): the same registration with the pass split into separate dispatches
     # (A/B switch), every pass timed -- what the fused launch's k-NN part costs when rocprofv3 / HIP events can see it
     knn_stage = None
-    if int(os.environ.get('FLIMO_BENCH_TIMING', '1')) == 1 and os.environ.get('FLIMO_FUSE', '1') != '0':
+    if args.full and int(os.environ.get('FLIMO_BENCH_TIMING', '1')) == 1 and os.environ.get('FLIMO_FUSE', '1') != '0':
         loc.hip.set_path_switches(fuse=0)
         for _ in range(2):
             step()
@@ -801,7 +819,7 @@ def main():
     # own map and resident scan, each driven by its own host thread (SURVEY 8 e / BASELINE configs[4] on a single GPU).  One stream is
     # a chain of dependent round trips that leaves most of the chip idle; streams overlap.
     concurrent = None
-    if rank == 0 and world == 1 and args.streams > 1:
+    if args.full and rank == 0 and world == 1 and args.streams > 1:
         import threading
         from fast_limo_amd import synth
         S, K = args.streams, max(50, min(args.steps * 4, 300))
@@ -839,7 +857,7 @@ def main():
     # beside `value`, never as `value`.  The first insertion stores the scan's new points; repeating the same scan is
     # then mostly rejected by the reference's down-sampling rule, so both are shown.  Runs after the timed region.
     with_insert = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # two steps by default (the scan's first insertion and one repeat: 8 more k-NN launches next to the 200+ of the timed
         # region, so the profiler's per-kernel average stays the benchmark's); --with-insert runs six for a steadier repeat figure
         t_ins = []
@@ -858,7 +876,7 @@ def main():
     # deskew, update, device-resident map insert on the Mapper's worker thread), sweep after sweep, reported beside `value`.
     # "tied": the stamps of a spinning sensor (all rings of a column share one stamp), "unique": every point its own stamp.
     end_to_end = None
-    if rank == 0 and not args.no_end_to_end:
+    if rank == 0 and args.full and not args.no_end_to_end:
         from fast_limo_amd import synth
         st, w, a = imu
         i = loc._imu_cursor
@@ -1004,115 +1022,114 @@ def main():
                                                            if pipe_found else "host loop over single passes (this host's launch round trip is short, or FLIMO_HOST_UPDATE=1)")),
                        "chains_run": chain["chains"], "chains_handed_back_early": chain["handed_back"], "chains_declined": chain["declined"],
                        "host_loop_passes_found_waiting": pipe_found, "host_loop_passes_queued_for_nothing": pipe_wasted},
-            "update_layouts": modes,
             "host_us_per_step": {"deskew_call": 1e6 * hp["deskew_s"] / args.steps, "update": 1e6 * hp["update_s"] / args.steps,
                                  "in_match_reduce": 1e6 * hp["match_reduce_s"] / args.steps},
-            "with_map_insert": with_insert,
-            "end_to_end": end_to_end,
-            "concurrent_streams": concurrent,
         }
-        cb, E, x_o = (None, None, None)
-        if world == 1 and not args.no_cpu_baseline:
-            cb, E, x_o = cpu_baseline(args)
-            out["cpu_baseline"] = cb
-            dpos = float(np.abs(x_ref[0:3] - x_o[0:3]).max())
-            drot = float(2.0 * np.abs(x_ref[3:6] - x_o[3:6]).max())
-            out["pose_err_vs_cpu"] = {"pos_m": dpos, "rot_rad": drot, "tolerance": 1e-4}
-        Eq = E if E else E_FALLBACK
-        if not E and (args.rings, args.azimuths, args.map_points, args.box) != (64, 1024, 1000000, 100.0):
-            Eq = None                      # the constant only describes configs[1]
-        bytes_per_query = (16.0 + 16.0 * Eq + NBR_BYTES) if Eq else None
-        qpl = tot["queries"] / tot["passes"] if tot["passes"] else float(scan.shape[0])      # queries per launch (every point of the scan is a query here)
-        us = lambda ms, n: (1e3 * ms / n) if n else None
-        in_region_us = us(split["fused_ms"], split["fused_n"])      # sparse samples inside the timed region (each perturbs the wall time)
-        one_us = dense["one_launch_pass_us"] if (dense and dense.get("one_launch_pass_us")) else in_region_us
-        # ^ mean duration of the one-launch pass from HIP events on its dispatch: the dense series (every pass of 12 steps timed,
-        #   right after the timed region, events read after the series) when it ran -- a timed dispatch issued once in 30 passes
-        #   runs cold and reads ~10 % long
-        sep = {"knn": us(split["knn_ms"], split["separate_n"]), "widen": us(split["widen_ms"], split["separate_n"]),
-               "fit_reduce": us(split["fit_ms"], split["separate_n"])} if split["separate_n"] else None
-        if one_us:
-            kernel, dur_us, n_timed = "knn5_kernel<2, 8, true, false>: the whole measurement pass in one launch (k-NN fast path + in-kernel widening + plane fit + residual/Jacobian + H^T H reduction)", one_us, (dense["one_launch_passes_timed"] if (dense and dense.get("one_launch_pass_us")) else split["fused_n"])
-        else:                              # developer switches (FLIMO_FUSE=0 ...): the k-NN dispatch alone
-            kernel, dur_us, n_timed = "knn5_kernel<2, 8, false, false>: k-NN dispatch (separate widening / fit dispatches)", us(tot["knn_ms"], tot["passes"]), tot["passes"]
-        achieved = bytes_per_query * qpl / (dur_us * 1e-6) / 1e9 if (dur_us and bytes_per_query) else None
-        traffic = pmc_traffic(qpl)
-        out["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                           "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBPS) if achieved else None, "traffic": traffic,
-                           "hbm_utilisation_measured": (traffic / (dur_us * 1e-6) / 1e9 / HBM_PEAK_GBPS) if (traffic and dur_us) else None,
-                           "bytes_per_query": bytes_per_query, "E_evals_per_query": Eq,
-                           "queries_per_launch": qpl, "mean_launch_us": dur_us, "timed_launches": n_timed,
-                           "kernel_in_timed_region": ("knn5_chain_kernel<2, 8, true, false>: the same device function queued AHEAD of its pose (pipelined host loop): its "
-                                                      "event duration includes the wait for the pose, so `mean_launch_us` is taken from the dense series right after the "
-                                                      "region, where every pass is launched when its pose is known (knn5_kernel<2, 8, true, false>)"
-                                                      if pipe_found else "knn5_kernel<2, 8, true, false> (passes launched when their pose is known)"),
-                           "reproduce": "rocprofv3 --kernel-trace --stats of `FLIMO_PIPELINE=0 python3 bench.py --streams 0`: profiles/r06/bench_r06_prof_nopipeline_kernel_stats.csv, "
-                                        "row knn5_kernel<2, 8, true, false>",
-                           "step": {"value_regions": value_regions, "kernel_us_per_step": kernel_us_per_step,
-                                    "step_minus_kernels_us": ((1e3 * 1e3 * elapsed / args.steps) - kernel_us_per_step["total"]) if kernel_us_per_step else None,
-                                    "note": "value_regions: the timed K-step region and nine more right behind it (min / median / max of scans/s); "
-                                            "kernel_us_per_step: every launch of 12 steps timed by HIP events on its dispatch"},
-                           "note": "achieved = ALGORITHMIC k-NN bytes (16 B query + 16 B x E candidate points of the reference's own traversal + 32 B neighbour "
-                                   "record) per launch / launch duration; the launch also does the plane fit, the residual / Jacobian rows and the "
-                                   "reduction, which add no algorithmic bytes (the five neighbours were just read).  `traffic` / "
-                                   "`hbm_utilisation_measured` are the HBM-side bytes from PMC counters: the 1M-point map lives in L2 / Infinity Cache",
-                           "stage": {"one_launch_pass_us_sampled_inside_timed_region": in_region_us, "one_launch_passes_timed": split["fused_n"],
-                                     "separate_dispatch_pass_us": sep, "separate_dispatch_passes_timed": split["separate_n"],
-                                     "passes_in_one_launch": n_fused_passes, "passes_total": n_passes,
-                                     "dense_after_timed_region": dense,
-                                     "note": "separate-dispatch passes (the first pass of the poor prior) are three launches: k-NN, widening of the "
-                                             "worklist, fit + reduction"}}
-        if concurrent and bytes_per_query:
-            # the chip's aggregate k-NN rate with S streams in flight: algorithmic bytes of all their passes / wall time
-            ppstep = n_passes / max(args.steps, 1)
-            agg = concurrent["scans_per_s_aggregate"] * ppstep * bytes_per_query * qpl / 1e9
-            concurrent["knn_algorithmic_GBps_aggregate"] = agg
-            concurrent["knn_algorithmic_frac_of_hbm_peak"] = agg / HBM_PEAK_GBPS
-        if knn_stage and bytes_per_query:
-            st_us = knn_stage["knn_us"] + knn_stage["widen_us"]
-            out["roofline"]["knn_stage_separate_dispatches"] = dict(
-                knn_stage, stage_us_per_pass=st_us, achieved=bytes_per_query * qpl / (st_us * 1e-6) / 1e9,
-                frac=bytes_per_query * qpl / (st_us * 1e-6) / 1e9 / HBM_PEAK_GBPS,
-                note="A/B series after the timed region with the pass split into dispatches: k-NN (fast path + in-kernel widening; the "
-                     "first pass of the poor prior hands its clustered stragglers to the widening dispatch) + widening, mean per pass "
-                     "over all 4 pass positions; same algorithmic bytes")
-        loc.close()
-        loc = None
-        if world == 1 and not args.no_hbm_regime:
-            out["roofline"]["hbm_regime"] = hbm_regime_leg(local_rank % n_dev, args.hbm_steps, with_oracle=not args.no_cpu_baseline)
-        if rank == 0 and world == 1 and not args.no_crowded:
-            out["roofline"]["crowded"] = crowded_leg(local_rank % n_dev, args.rings, args.azimuths, args.map_points, args.box)
-        # the figures a reader of a trimmed record wants, as plain scalars of `config` / `roofline` (nested objects may be dropped)
-        flat = out["config"]
-        if value_regions:
-            flat["scans_per_s_long_region"] = value_regions.get("scans_per_s_region_of_%d_steps" % value_regions["long_region_steps"])
-            flat["scans_per_s_median_of_regions"] = value_regions["scans_per_s_median"]
-        if end_to_end:
-            if end_to_end.get("first_sweeps_into_a_static_map"):
-                flat["pcie_inclusive_ms_per_sweep_first_sweeps_into_a_static_map"] = end_to_end["first_sweeps_into_a_static_map"]["ms_per_sweep"]
-            for key, src in (("tied", end_to_end.get("tied_stamps")), ("unique", end_to_end.get("unique_stamps")),
-                             ("shipped", end_to_end.get("shipped_config")), ("shipped_tied", end_to_end.get("shipped_config_tied"))):
-                if not src:
-                    continue
-                flat["pcie_inclusive_ms_per_sweep_%s" % key] = src.get("ms_per_sweep")
-                flat["pcie_inclusive_ms_per_sweep_%s_sustained" % key] = src.get("ms_per_sweep_sustained")
-                if "speedup_vs_cpu_oracle" in src:
-                    flat["speedup_vs_cpu_oracle_%s" % key] = src["speedup_vs_cpu_oracle"]
-        rf = out["roofline"]
-        ks = rf.get("knn_stage_separate_dispatches")
-        if ks and bytes_per_query:
-            rf["knn_kernel_alone_us"] = ks["knn_us"]
-            rf["knn_kernel_alone_frac"] = bytes_per_query * qpl / (ks["knn_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
-            rf["knn_stage_frac"] = ks["frac"]
-        hb = rf.get("hbm_regime")
-        if hb:
-            rf["hbm_regime_ms_per_step"] = hb.get("ms_per_step")
-            rf["hbm_regime_frac"] = hb.get("frac")
-            rf["hbm_regime_widen_us"] = (hb.get("separate_dispatch_pass_us") or {}).get("widen")
-            rf["hbm_regime_insert_ms_repeat"] = (hb.get("map_insert_ms") or {}).get("repeat")
-            rf["hbm_regime_insert_ms_first"] = (hb.get("map_insert_ms") or {}).get("first")
-        if kernel_us_per_step:
-            rf["kernel_us_per_step"] = kernel_us_per_step["total"]
+        if args.full:
+            out.update({"update_layouts": modes, "with_map_insert": with_insert, "end_to_end": end_to_end,
+                        "concurrent_streams": concurrent})
+            cb, E, x_o = (None, None, None)
+            if world == 1 and not args.no_cpu_baseline:
+                cb, E, x_o = cpu_baseline(args)
+                out["cpu_baseline"] = cb
+                dpos = float(np.abs(x_ref[0:3] - x_o[0:3]).max())
+                drot = float(2.0 * np.abs(x_ref[3:6] - x_o[3:6]).max())
+                out["pose_err_vs_cpu"] = {"pos_m": dpos, "rot_rad": drot, "tolerance": 1e-4}
+            Eq = E if E else E_FALLBACK
+            if not E and (args.rings, args.azimuths, args.map_points, args.box) != (64, 1024, 1000000, 100.0):
+                Eq = None                      # the constant only describes configs[1]
+            bytes_per_query = (16.0 + 16.0 * Eq + NBR_BYTES) if Eq else None
+            qpl = tot["queries"] / tot["passes"] if tot["passes"] else float(scan.shape[0])      # queries per launch (every point of the scan is a query here)
+            us = lambda ms, n: (1e3 * ms / n) if n else None
+            in_region_us = us(split["fused_ms"], split["fused_n"])      # sparse samples inside the timed region (each perturbs the wall time)
+            one_us = dense["one_launch_pass_us"] if (dense and dense.get("one_launch_pass_us")) else in_region_us
+            # ^ mean duration of the one-launch pass from HIP events on its dispatch: the dense series (every pass of 12 steps timed,
+            #   right after the timed region, events read after the series) when it ran -- a timed dispatch issued once in 30 passes
+            #   runs cold and reads ~10 % long
+            sep = {"knn": us(split["knn_ms"], split["separate_n"]), "widen": us(split["widen_ms"], split["separate_n"]),
+                   "fit_reduce": us(split["fit_ms"], split["separate_n"])} if split["separate_n"] else None
+            if one_us:
+                kernel, dur_us, n_timed = "knn5_kernel<2, 8, true, false>: the whole measurement pass in one launch (k-NN fast path + in-kernel widening + plane fit + residual/Jacobian + H^T H reduction)", one_us, (dense["one_launch_passes_timed"] if (dense and dense.get("one_launch_pass_us")) else split["fused_n"])
+            else:                              # developer switches (FLIMO_FUSE=0 ...): the k-NN dispatch alone
+                kernel, dur_us, n_timed = "knn5_kernel<2, 8, false, false>: k-NN dispatch (separate widening / fit dispatches)", us(tot["knn_ms"], tot["passes"]), tot["passes"]
+            achieved = bytes_per_query * qpl / (dur_us * 1e-6) / 1e9 if (dur_us and bytes_per_query) else None
+            traffic = pmc_traffic(qpl)
+            out["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                               "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBPS) if achieved else None, "traffic": traffic,
+                               "hbm_utilisation_measured": (traffic / (dur_us * 1e-6) / 1e9 / HBM_PEAK_GBPS) if (traffic and dur_us) else None,
+                               "bytes_per_query": bytes_per_query, "E_evals_per_query": Eq,
+                               "queries_per_launch": qpl, "mean_launch_us": dur_us, "timed_launches": n_timed,
+                               "kernel_in_timed_region": ("knn5_chain_kernel<2, 8, true, false>: the same device function queued AHEAD of its pose (pipelined host loop): its "
+                                                          "event duration includes the wait for the pose, so `mean_launch_us` is taken from the dense series right after the "
+                                                          "region, where every pass is launched when its pose is known (knn5_kernel<2, 8, true, false>)"
+                                                          if pipe_found else "knn5_kernel<2, 8, true, false> (passes launched when their pose is known)"),
+                               "reproduce": "rocprofv3 --kernel-trace --stats of `FLIMO_PIPELINE=0 python3 bench.py --full --streams 0`: profiles/r06/bench_r06_prof_nopipeline_kernel_stats.csv, "
+                                            "row knn5_kernel<2, 8, true, false>",
+                               "step": {"value_regions": value_regions, "kernel_us_per_step": kernel_us_per_step,
+                                        "step_minus_kernels_us": ((1e3 * 1e3 * elapsed / args.steps) - kernel_us_per_step["total"]) if kernel_us_per_step else None,
+                                        "note": "value_regions: the timed K-step region and nine more right behind it (min / median / max of scans/s); "
+                                                "kernel_us_per_step: every launch of 12 steps timed by HIP events on its dispatch"},
+                               "note": "achieved = ALGORITHMIC k-NN bytes (16 B query + 16 B x E candidate points of the reference's own traversal + 32 B neighbour "
+                                       "record) per launch / launch duration; the launch also does the plane fit, the residual / Jacobian rows and the "
+                                       "reduction, which add no algorithmic bytes (the five neighbours were just read).  `traffic` / "
+                                       "`hbm_utilisation_measured` are the HBM-side bytes from PMC counters: the 1M-point map lives in L2 / Infinity Cache",
+                               "stage": {"one_launch_pass_us_sampled_inside_timed_region": in_region_us, "one_launch_passes_timed": split["fused_n"],
+                                         "separate_dispatch_pass_us": sep, "separate_dispatch_passes_timed": split["separate_n"],
+                                         "passes_in_one_launch": n_fused_passes, "passes_total": n_passes,
+                                         "dense_after_timed_region": dense,
+                                         "note": "separate-dispatch passes (the first pass of the poor prior) are three launches: k-NN, widening of the "
+                                                 "worklist, fit + reduction"}}
+            if concurrent and bytes_per_query:
+                # the chip's aggregate k-NN rate with S streams in flight: algorithmic bytes of all their passes / wall time
+                ppstep = n_passes / max(args.steps, 1)
+                agg = concurrent["scans_per_s_aggregate"] * ppstep * bytes_per_query * qpl / 1e9
+                concurrent["knn_algorithmic_GBps_aggregate"] = agg
+                concurrent["knn_algorithmic_frac_of_hbm_peak"] = agg / HBM_PEAK_GBPS
+            if knn_stage and bytes_per_query:
+                st_us = knn_stage["knn_us"] + knn_stage["widen_us"]
+                out["roofline"]["knn_stage_separate_dispatches"] = dict(
+                    knn_stage, stage_us_per_pass=st_us, achieved=bytes_per_query * qpl / (st_us * 1e-6) / 1e9,
+                    frac=bytes_per_query * qpl / (st_us * 1e-6) / 1e9 / HBM_PEAK_GBPS,
+                    note="A/B series after the timed region with the pass split into dispatches: k-NN (fast path + in-kernel widening; the "
+                         "first pass of the poor prior hands its clustered stragglers to the widening dispatch) + widening, mean per pass "
+                         "over all 4 pass positions; same algorithmic bytes")
+            loc.close()
+            loc = None
+            if world == 1 and not args.no_hbm_regime:
+                out["roofline"]["hbm_regime"] = hbm_regime_leg(local_rank % n_dev, args.hbm_steps, with_oracle=not args.no_cpu_baseline)
+            if rank == 0 and world == 1 and not args.no_crowded:
+                out["roofline"]["crowded"] = crowded_leg(local_rank % n_dev, args.rings, args.azimuths, args.map_points, args.box)
+            # the figures a reader of a trimmed record wants, as plain scalars of `config` / `roofline` (nested objects may be dropped)
+            flat = out["config"]
+            if value_regions:
+                flat["scans_per_s_long_region"] = value_regions.get("scans_per_s_region_of_%d_steps" % value_regions["long_region_steps"])
+                flat["scans_per_s_median_of_regions"] = value_regions["scans_per_s_median"]
+            if end_to_end:
+                if end_to_end.get("first_sweeps_into_a_static_map"):
+                    flat["pcie_inclusive_ms_per_sweep_first_sweeps_into_a_static_map"] = end_to_end["first_sweeps_into_a_static_map"]["ms_per_sweep"]
+                for key, src in (("tied", end_to_end.get("tied_stamps")), ("unique", end_to_end.get("unique_stamps")),
+                                 ("shipped", end_to_end.get("shipped_config")), ("shipped_tied", end_to_end.get("shipped_config_tied"))):
+                    if not src:
+                        continue
+                    flat["pcie_inclusive_ms_per_sweep_%s" % key] = src.get("ms_per_sweep")
+                    flat["pcie_inclusive_ms_per_sweep_%s_sustained" % key] = src.get("ms_per_sweep_sustained")
+                    if "speedup_vs_cpu_oracle" in src:
+                        flat["speedup_vs_cpu_oracle_%s" % key] = src["speedup_vs_cpu_oracle"]
+            rf = out["roofline"]
+            ks = rf.get("knn_stage_separate_dispatches")
+            if ks and bytes_per_query:
+                rf["knn_kernel_alone_us"] = ks["knn_us"]
+                rf["knn_kernel_alone_frac"] = bytes_per_query * qpl / (ks["knn_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
+                rf["knn_stage_frac"] = ks["frac"]
+            hb = rf.get("hbm_regime")
+            if hb:
+                rf["hbm_regime_ms_per_step"] = hb.get("ms_per_step")
+                rf["hbm_regime_frac"] = hb.get("frac")
+                rf["hbm_regime_widen_us"] = (hb.get("separate_dispatch_pass_us") or {}).get("widen")
+                rf["hbm_regime_insert_ms_repeat"] = (hb.get("map_insert_ms") or {}).get("repeat")
+                rf["hbm_regime_insert_ms_first"] = (hb.get("map_insert_ms") or {}).get("first")
+            if kernel_us_per_step:
+                rf["kernel_us_per_step"] = kernel_us_per_step["total"]
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if loc is not None:
         loc.close()

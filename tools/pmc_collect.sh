@@ -6,7 +6,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/pmc_$tag
 rm -rf $out
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $out -- python3 $root/bench.py --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+timeout 300 rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $out -- python3 $root/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 cd $root
 python3 - "$out" <<'PY'
 import csv, glob, sys, os

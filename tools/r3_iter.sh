@@ -1,13 +1,14 @@
 #!/bin/bash
 # round 3 iteration: GPU suite (stop at first failure) + default bench summary
 root=${GRAFT_REPO_ROOT:-$(pwd)}
-cd $root; mkdir -p gpurun_out
-timeout 1200 python -m pytest tests -m gpu -x -q $PYTEST_ARGS > gpurun_out/r3_pytest.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed|Error|error|assert" gpurun_out/r3_pytest.log | tail -15
-timeout 600 python bench.py --steps 50 --warmup 5 $BENCH_ARGS 2> gpurun_out/r3_bench.err > gpurun_out/r3_bench.json; echo "bench rc=$?"; tail -3 gpurun_out/r3_bench.err
-python - <<'PY'
-import json
+out=${FLIMO_DEV_OUT:-dev_out}
+cd $root; mkdir -p $out
+timeout 1200 python -m pytest tests -m gpu -x -q $PYTEST_ARGS > $out/r3_pytest.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed|Error|error|assert" $out/r3_pytest.log | tail -15
+timeout 600 python bench.py --full --steps 50 --warmup 5 $BENCH_ARGS 2> $out/r3_bench.err > $out/r3_bench.json; echo "bench rc=$?"; tail -3 $out/r3_bench.err
+python - $out <<'PY'
+import json, sys
 try:
-    d=json.load(open('gpurun_out/r3_bench.json'))
+    d=json.load(open(sys.argv[1] + '/r3_bench.json'))
 except Exception as e:
     print("no bench json", e); raise SystemExit
 r=d['roofline']; print('value',d['value'],'ms',d['ms_per_step'],'frac',r['frac'],'us',r['mean_launch_us'], 'bitrepro', d['config']['steps_bit_reproducible'])

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Developer tool: GPU timeline of ONE sweep of the end-to-end leg (front end, passes, map insert) from a rocprofv3 kernel trace.
 
-  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tl -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline \
+  rocprofv3 --kernel-trace --output-format csv -d <trace dir> -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline \
       --no-hbm-regime --streams 0
-  python3 tools/sweep_timeline.py gpurun_out/tl
+  python3 tools/sweep_timeline.py <trace dir>
 
 Prints every kernel between the last two launches of the anchor kernel (default: bbox_finite_kernel = start of a map insert):
 start offset, duration, idle gap before it."""
