@@ -79,7 +79,7 @@ HIP_SYMBOLS = [
     "flimo_map_points", "flimo_knn", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
-    "flimo_scan_to_world", "flimo_scan_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
+    "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
     "flimo_set_timing", "flimo_set_timing_stride", "flimo_set_timing_deferred", "flimo_pass_count", "flimo_fused_pass_count", "flimo_tie_stats", "flimo_map_index_bytes", "flimo_fine_stats", "flimo_map_grid_selfcheck", "flimo_set_debug_records", "flimo_last_kernel_ms",
     "flimo_last_candidates_per_query", "flimo_last_widen_count", "flimo_last_stragglers", "flimo_stragglers_by_pass", "flimo_timing_totals", "flimo_timing_split", "flimo_set_path_switches", "flimo_set_wait_timeout_ms", "flimo_insert_rule_replay", "flimo_plane_fit5_host", "flimo_plane_eval5_host", "flimo_calculate_H_host",
     "flimo_update_chain", "flimo_chain_stats", "flimo_set_update_mode", "flimo_update_mode", "flimo_scan_adopt", "flimo_set_pass_pipeline", "flimo_pass_pipeline_end", "flimo_pass_pipeline_last", "flimo_pass_pipeline_stats",
@@ -132,6 +132,7 @@ def load_hip():
     L.flimo_match_fetch_H.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.flimo_scan_to_world.argtypes = [vp, f64p, C.c_void_p, C.c_size_t]
     L.flimo_scan_clouds.argtypes = [vp, f64p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.flimo_scan_debug_clouds.argtypes = [vp, f64p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.flimo_upload_stage.argtypes = [vp, C.c_size_t, C.POINTER(C.c_void_p)]
     L.flimo_map_add_scan.argtypes = [vp, f64p, C.c_double]
     L.flimo_set_timing.argtypes = [vp, C.c_int]
@@ -357,6 +358,15 @@ class HipCtx:
             return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
         rec = lambda p: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value, 4))[:, :3].copy()
         return rec(b), rec(w)
+
+    def scan_debug_clouds(self, x26):
+        """(deskewed_scan, final_raw_scan) x y z w records of the last deskew (flimo_scan_debug_clouds): (n, 4) float32 copies."""
+        d, f, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        self._chk(self._L.flimo_scan_debug_clouds(self._h, np.ascontiguousarray(x26, dtype=np.float64), C.byref(d), C.byref(f), C.byref(n)))
+        if n.value == 0:
+            return np.zeros((0, 4), np.float32), np.zeros((0, 4), np.float32)
+        rec = lambda p: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value, 4)).copy()
+        return rec(d), rec(f)
 
     def map_add_scan(self, x26, stamp=0.0):
         self._chk(self._L.flimo_map_add_scan(self._h, np.ascontiguousarray(x26, dtype=np.float64), float(stamp)))

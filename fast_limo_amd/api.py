@@ -44,7 +44,7 @@ HOST_SYMBOLS = [
     "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_last_sweep_tied", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
-    "flimo_loc_get_final_scan", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
+    "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
     "flimo_eskf_update_fixed", "flimo_eskf_predict", "flimo_host_eigen_solver6", "flimo_host_plane", "flimo_host_state_update", "flimo_host_time_order",
 ]
 
@@ -164,6 +164,8 @@ def load_host():
     L.flimo_loc_get_pc2match.argtypes = [vp, C.c_void_p, C.c_size_t]
     L.flimo_loc_get_final_scan.restype = C.c_size_t
     L.flimo_loc_get_final_scan.argtypes = [vp, C.c_void_p, C.c_size_t]
+    L.flimo_loc_get_debug_cloud.restype = C.c_size_t
+    L.flimo_loc_get_debug_cloud.argtypes = [vp, C.c_int, C.c_void_p, C.c_size_t]
     L.flimo_loc_get_stage_times.restype = None
     L.flimo_loc_get_stage_times.argtypes = [vp, f64p]
     L.flimo_loc_get_pose_cov.restype = None
@@ -328,6 +330,26 @@ class Localizer:
     def final_scan(self, out=None):
         """xyz of get_pointcloud() (world frame); `out` as for pc2match."""
         return self._cloud(self._L.flimo_loc_get_final_scan, out)
+
+    def orig_scan(self):
+        """get_orig_pointcloud(): the filtered sweep (LiDAR frame) as POINT_DTYPE records; empty unless cfg.debug."""
+        return self._debug_cloud(0)
+
+    def deskewed_scan(self):
+        """get_deskewed_pointcloud(): the sweep in time order, deskewed into the world frame (POINT_DTYPE); empty unless cfg.debug."""
+        return self._debug_cloud(1)
+
+    def final_raw_scan(self):
+        """get_finalraw_pointcloud(): the un-voxelised deskewed sweep in the world frame of the corrected pose (POINT_DTYPE); empty
+        unless cfg.debug."""
+        return self._debug_cloud(2)
+
+    def _debug_cloud(self, which):
+        n = int(self._L.flimo_loc_get_debug_cloud(self._h, which, None, 0))
+        out = np.zeros(n, POINT_DTYPE)
+        if n:
+            self._L.flimo_loc_get_debug_cloud(self._h, which, out.ctypes.data, n)
+        return out
 
     def _cloud(self, getter, out):
         n = int(getter(self._h, None, 0))

@@ -99,6 +99,7 @@ struct flimo_ctx {
   DeskewArgs deskew_args{};
   size_t deskew_n = 0;
   bool deskew_pending = false;
+  bool deskew_kept = false;        // deskew_args / deskew_n still describe the resident raw sweep (flimo_scan_debug_clouds)
   // per pass
   Rec16* d_recs = nullptr;
   RecDbg* d_dbg = nullptr;
@@ -128,6 +129,9 @@ struct flimo_ctx {
   // staging
   void* h_stage = nullptr;         // pinned
   void* h_clouds = nullptr;        // pinned: the two clouds of flimo_scan_clouds
+  void* h_dbg_clouds = nullptr;    // pinned: the two clouds of flimo_scan_debug_clouds
+  float4* d_dbg_clouds = nullptr;  // their device side, [deskewed | final raw]
+  size_t dbg_clouds_cap = 0, dbg_clouds_dcap = 0;   // bytes of h_dbg_clouds, points of each half of d_dbg_clouds
   void (*overlap_fn)(void*) = nullptr;   // flimo_match_reduce_overlap: host work of the caller to run while the pass is in flight
   void* overlap_arg = nullptr;
   size_t clouds_cap = 0;
@@ -271,16 +275,18 @@ static int fail(flimo_ctx* c, int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(c, FLIMO_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
-static int ensure_stage(flimo_ctx* c, size_t bytes) {
-  if (bytes <= c->stage_cap) return FLIMO_OK;
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  c->h_stage = nullptr;
-  c->stage_cap = 0;
-  size_t cap = bytes + bytes / 4 + 4096;
-  HIPCHK(c, hipHostMalloc(&c->h_stage, cap, hipHostMallocDefault));
-  c->stage_cap = cap;
+// Grows a pinned host buffer of the context (cap: its size in bytes) to hold `bytes`; the old contents are not kept.
+static int ensure_pinned(flimo_ctx* c, void*& buf, size_t& cap, size_t bytes) {
+  if (bytes <= cap) return FLIMO_OK;
+  if (buf) (void)hipHostFree(buf);
+  buf = nullptr;
+  cap = 0;
+  const size_t ncap = bytes + bytes / 4 + 4096;
+  HIPCHK(c, hipHostMalloc(&buf, ncap, hipHostMallocDefault));
+  cap = ncap;
   return FLIMO_OK;
 }
+static int ensure_stage(flimo_ctx* c, size_t bytes) { return ensure_pinned(c, c->h_stage, c->stage_cap, bytes); }
 
 template <typename T>
 static int ensure_dev(flimo_ctx* c, T*& p, size_t& cap, size_t need, bool keep, size_t keep_n) {
@@ -494,7 +500,7 @@ extern "C" void flimo_ctx_destroy(flimo_ctx* c) {
   (void)hipFree(c->d_scan_sorted); (void)hipFree(c->d_nbr); (void)hipFree(c->d_wl); (void)hipFree(c->d_wl_count);
   (void)hipFree(c->d_fit_partials); (void)hipFree(c->d_raw_sorted); (void)hipFree(c->d_t_sorted);
   (void)hipFree(c->d_scan); (void)hipFree(c->d_scan_raw); (void)hipFree(c->d_scan_world); (void)hipFree(c->d_scan_t);
-  (void)hipFree(c->d_frames); (void)hipFree(c->d_recs); (void)hipFree(c->d_dbg);
+  (void)hipFree(c->d_frames); (void)hipFree(c->d_recs); (void)hipFree(c->d_dbg); (void)hipFree(c->d_dbg_clouds);
   (void)hipFree(c->d_fine_tmp); (void)hipFree(c->d_fine_pts); 
   (void)hipFree(c->d_fine_count); (void)hipFree(c->d_crowd_list); (void)hipFree(c->d_crowd_count); (void)hipFree(c->d_crowd_bits);
   (void)hipFree(c->d_tkey[0]); (void)hipFree(c->d_tkey[1]); (void)hipFree(c->d_tperm); (void)hipFree(c->d_t_tmp);
@@ -511,6 +517,7 @@ extern "C" void flimo_ctx_destroy(flimo_ctx* c) {
   if (c->h_chain_log) (void)hipHostFree(c->h_chain_log);
   if (c->chain_ev_made) for (int i = 0; i < CH_MAX_PASSES; i++) for (int k = 0; k < 8; k++) (void)hipEventDestroy(c->chain_ev[i][k]);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
+  if (c->h_dbg_clouds) (void)hipHostFree(c->h_dbg_clouds);
   if (c->h_clouds) (void)hipHostFree(c->h_clouds);
   for (int k = 0; k < 2; k++) if (c->h_frames[k]) (void)hipHostFree(c->h_frames[k]);
   map_scratch_free(c->scratch);
@@ -1140,6 +1147,7 @@ static int ensure_scan(flimo_ctx* c, size_t n) {
   c->d_scan = a; c->d_scan_raw = b; c->d_scan_world = w; c->d_scan_t = t;
   c->scan_cap = cap;
   c->scan_n = 0; c->sorted_n = 0; c->raw_n = 0; c->prev.valid = 0;
+  c->deskew_kept = false;
   return FLIMO_OK;
 }
 
@@ -1184,6 +1192,7 @@ extern "C" int flimo_scan_set(flimo_ctx* c, const float* xyz, size_t n, size_t s
   if (n > 0x7fff0000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan too large");
   ctx_enter(c);
   c->deskew_pending = false;                 // the scan it belonged to is replaced
+  c->deskew_kept = false;
   int rc = ensure_scan(c, n);
   if (rc) return rc;
   if (n) {
@@ -1244,6 +1253,7 @@ extern "C" int flimo_raw_scan_set(flimo_ctx* c, const float* xyz, size_t n, size
   if (n > 0 && (!xyz || !t || stride_bytes < 12)) return fail(c, FLIMO_ERR_INVALID, "bad xyz/t/stride");
   ctx_enter(c);
   c->deskew_pending = false;                 // a deskew never run belonged to the scan this one replaces
+  c->deskew_kept = false;
   int rc = ensure_scan(c, n);
   if (rc) return rc;
   if (n) {
@@ -1284,6 +1294,7 @@ extern "C" int flimo_raw_scan_filter_order_set(flimo_ctx* c, const void* points3
   if (n > 0x7fff0000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan too large");
   *n_kept = 0; *last_stamp = 0.0; *nan_stamp = 0; *tied = 0;
   c->deskew_pending = false;                 // a deskew never run belonged to the scan this one replaces
+  c->deskew_kept = false;
   ctx_enter(c);
   int rc = ensure_scan(c, n);
   if (rc) return rc;
@@ -1433,6 +1444,8 @@ extern "C" int flimo_scan_adopt(flimo_ctx* dst, flimo_ctx* src) {
   ctx_enter(dst);
   const size_t m = src->raw_n;
   dst->deskew_pending = false;
+  dst->deskew_kept = false;
+  src->deskew_kept = false;                         // its raw sweep moves to dst
   { const int rc = ensure_scan(dst, m); if (rc) return rc; }
   dst->raw_n = 0; dst->order_n = 0; dst->resident_t_offset = 0.0; dst->raw_time_ordered = false;
   if (m == 0) return FLIMO_OK;
@@ -1480,6 +1493,7 @@ extern "C" int flimo_deskew_resident_offset(flimo_ctx* c, const flimo_frame* fra
   static_assert(sizeof(flimo_frame) == 112, "flimo_frame layout");
   if (dev_frame_size() != sizeof(flimo_frame)) return fail(c, FLIMO_ERR_INVALID, "frame layout mismatch");
   const size_t n = c->raw_n;
+  c->deskew_kept = false;
   if (n == 0) { c->scan_n = 0; c->sorted_n = 0; c->prev.valid = 0; return FLIMO_OK; }
   const size_t fbytes = nf * sizeof(flimo_frame);
   const size_t total = fbytes + 32 * sizeof(float);
@@ -1503,6 +1517,7 @@ extern "C" int flimo_deskew_resident_offset(flimo_ctx* c, const flimo_frame* fra
                                 t_offset, c->d_scan_sorted, c->d_scan, 1, (int)(total / 4)};
     c->deskew_n = n;
     c->deskew_pending = true;
+    c->deskew_kept = true;
     c->scan_n = n; c->sorted_n = n; c->prev.valid = 0;
     return FLIMO_OK;
   }
@@ -1541,6 +1556,7 @@ extern "C" int flimo_deskew_resident_offset(flimo_ctx* c, const flimo_frame* fra
                               t_offset, c->d_scan_sorted, c->d_scan, 1, 0};
   c->deskew_n = n;
   c->deskew_pending = true;
+  c->deskew_kept = true;
   c->async_deskews++;
   c->scan_n = n; c->sorted_n = n; c->prev.valid = 0;
   return FLIMO_OK;
@@ -2639,13 +2655,7 @@ extern "C" int flimo_scan_clouds(flimo_ctx* c, const double x26[26], const float
   if (c->scan_n == 0) return FLIMO_OK;
   ctx_enter(c);
   const size_t bytes = c->scan_n * sizeof(float4);
-  if (2 * bytes > c->clouds_cap) {
-    if (c->h_clouds) (void)hipHostFree(c->h_clouds);
-    c->h_clouds = nullptr; c->clouds_cap = 0;
-    const size_t cap = 2 * bytes + bytes / 2 + 4096;
-    HIPCHK(c, hipHostMalloc(&c->h_clouds, cap, hipHostMallocDefault));
-    c->clouds_cap = cap;
-  }
+  { const int rcp = ensure_pinned(c, c->h_clouds, c->clouds_cap, 2 * bytes); if (rcp) return rcp; }
   PoseMats P;
   pose_from_x26(x26, P);
   { const int rcf = flush_deskew(c); if (rcf) return rcf; }
@@ -2656,6 +2666,33 @@ extern "C" int flimo_scan_clouds(flimo_ctx* c, const double x26[26], const float
   HIPCHK(c, hipStreamSynchronize(c->stream));
   *body = (const float*)c->h_clouds;
   *world = (const float*)((const char*)c->h_clouds + bytes);
+  return FLIMO_OK;
+}
+
+// config.debug clouds of the last deskew (Localizer.cpp:373-374,848-850), recomputed from the resident raw sweep by one launch:
+// deskewed_scan (world frame, each point with its own IMU pose) and final_raw_scan (the un-voxelised body-frame sweep moved by x26),
+// both in the order of the raw sweep's original indices.  Nothing when the resident scan did not come from a deskew.
+extern "C" int flimo_scan_debug_clouds(flimo_ctx* c, const double x26[26], const float** deskewed_world, const float** final_raw,
+                                       size_t* n) {
+  if (!c || !x26 || !deskewed_world || !final_raw || !n) return FLIMO_ERR_INVALID;
+  *deskewed_world = *final_raw = nullptr;
+  *n = 0;
+  if (!c->deskew_kept || c->deskew_n == 0) return FLIMO_OK;
+  ctx_enter(c);
+  const size_t m = c->deskew_n;
+  const size_t bytes = m * sizeof(float4);
+  { const int rcp = ensure_pinned(c, c->h_dbg_clouds, c->dbg_clouds_cap, 2 * bytes); if (rcp) return rcp; }
+  { const int rcd = ensure_dev(c, c->d_dbg_clouds, c->dbg_clouds_dcap, 2 * m, false, 0); if (rcd) return rcd; }
+  PoseMats P;
+  pose_from_x26(x26, P);
+  if (!launch_deskew_debug(c->stream, c->deskew_args, (int)m, P, c->d_dbg_clouds, c->d_dbg_clouds + m))
+    return fail(c, FLIMO_ERR_INVALID, "flimo_scan_debug_clouds: staged IMU frames larger than the kernel takes");
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(c->h_dbg_clouds, c->d_dbg_clouds, 2 * bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *deskewed_world = (const float*)c->h_dbg_clouds;
+  *final_raw = (const float*)((const char*)c->h_dbg_clouds + bytes);
+  *n = m;
   return FLIMO_OK;
 }
 

@@ -98,6 +98,9 @@ void launch_rtt_probe(hipStream_t st, void* out_granule, unsigned long long tag)
 void launch_deskew(hipStream_t st, const float4* in, const double* t, int n, const void* frames, int nf,
                    const float* mats32, float4* out_sorted, float4* out_orig, double t_offset = 0.0);   // stamp of point k = t[k] + t_offset
 void launch_transform(hipStream_t st, const float4* in, int n, const PoseMats& P, float4* out);
+// config.debug clouds of the deskew `dk` (n points): deskewed_scan (world frame) and final_raw_scan (moved by P.RT), each at the raw
+// point's original index.  false: the staged frames are larger than the kernel takes.
+bool launch_deskew_debug(hipStream_t st, const DeskewArgs& dk, int n, const PoseMats& P, float4* out_world, float4* out_final);
 size_t dev_frame_size();
 
 // flimo_map.hip

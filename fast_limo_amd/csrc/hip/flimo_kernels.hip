@@ -11,6 +11,7 @@
 //   cap_kernel        MAX_NUM_MATCHES "first M matches" rule (Localizer.cpp:539)
 //   deskew_kernel     Localizer::deskewPointCloud loop (Localizer.cpp:822-843)
 //   transform_kernel  pcl::transformPointCloud(pc2match, state.get_RT()) (Localizer.cpp:361)
+//   deskew_debug_kernel  the config.debug clouds deskewed_scan / final_raw_scan (Localizer.cpp:373-374,848-850)
 //
 // The map is a uniform grid (flimo_types.h: GridView).  A query visits the 3x3x3 block of cells
 // around it as 9 contiguous point ranges (x-adjacent cells are adjacent in memory), keeps a
@@ -688,9 +689,9 @@ FLIMO_DEV void quat_to_rot(float qx, float qy, float qz, float qw, float (&R)[9]
   R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.f - (txx + tyy);
 }
 
-// One point: p = raw LiDAR-frame point (w = original index), tk = its absolute stamp; returns the point in the body frame at the
-// scan's end (w unchanged).  The per-pass k-NN kernel of a scan's FIRST pass calls it too (the deskew rides on that launch).
-__device__ __forceinline__ float4 deskew_point(const float4 p, const double tk, const DevFrame* __restrict__ frames, int nf,
+// One point: p = raw LiDAR-frame point, tk = its absolute stamp; returns T * [p, 1], the point deskewed into the world frame with
+// its own IMU pose (Localizer.cpp:827-832), the 4th component as the reference carries it.
+__device__ __forceinline__ float4 deskew_world(const float4 p, const double tk, const DevFrame* __restrict__ frames, int nf,
                                                const float* __restrict__ mats /* [0..15] lidar2baselink_T, [16..31] last_state.get_RT_inv() */) {
   // binary_search_tailored (Algorithms.hpp:25-38)
   int low = 0, high = nf - 1;
@@ -803,11 +804,23 @@ __device__ __forceinline__ float4 deskew_point(const float4 p, const double tk, 
   float wy_ = ((T[4] * p.x + T[5] * p.y) + T[6] * p.z) + T[7] * 1.f;
   float wz_ = ((T[8] * p.x + T[9] * p.y) + T[10] * p.z) + T[11] * 1.f;
   float ww_ = ((T[12] * p.x + T[13] * p.y) + T[14] * p.z) + T[15] * 1.f;
+  return make_float4(wx_, wy_, wz_, ww_);
+}
+
+// The world-frame point into the body frame at the scan's end: last_state.get_RT_inv() * world (Localizer.cpp:835); w = `w`.
+__device__ __forceinline__ float4 deskew_body(const float4 wp, const float* __restrict__ mats, float w) {
   const float* Li = mats + 16;
-  const float ox_ = ((Li[0] * wx_ + Li[1] * wy_) + Li[2] * wz_) + Li[3] * ww_;
-  const float oy_ = ((Li[4] * wx_ + Li[5] * wy_) + Li[6] * wz_) + Li[7] * ww_;
-  const float oz_ = ((Li[8] * wx_ + Li[9] * wy_) + Li[10] * wz_) + Li[11] * ww_;
-  return make_float4(ox_, oy_, oz_, p.w);
+  const float ox_ = ((Li[0] * wp.x + Li[1] * wp.y) + Li[2] * wp.z) + Li[3] * wp.w;
+  const float oy_ = ((Li[4] * wp.x + Li[5] * wp.y) + Li[6] * wp.z) + Li[7] * wp.w;
+  const float oz_ = ((Li[8] * wp.x + Li[9] * wp.y) + Li[10] * wp.z) + Li[11] * wp.w;
+  return make_float4(ox_, oy_, oz_, w);
+}
+
+// One point: p = raw LiDAR-frame point (w = original index), tk = its absolute stamp; returns the point in the body frame at the
+// scan's end (w unchanged).  The per-pass k-NN kernel of a scan's FIRST pass calls it too (the deskew rides on that launch).
+__device__ __forceinline__ float4 deskew_point(const float4 p, const double tk, const DevFrame* __restrict__ frames, int nf,
+                                               const float* __restrict__ mats) {
+  return deskew_body(deskew_world(p, tk, frames, nf, mats), mats, p.w);
 }
 
 __global__ __launch_bounds__(256) void deskew_kernel(const float4* __restrict__ in, const double* __restrict__ t,
@@ -2806,6 +2819,42 @@ __global__ __launch_bounds__(256) void transform_kernel(const float4* __restrict
   out[k] = make_float4(x, y, z, p.w);
 }
 
+// config.debug clouds of the last deskew (Localizer.cpp:822-836,848-850 and :373-374), recomputed from the resident raw sweep: for
+// each raw point the world-frame point of deskew_world (deskewed_scan) and its body-frame point moved by the corrected pose with
+// transform_kernel's arithmetic (final_raw_scan), both stored at the point's original index (w), as deskew_kernel stores out_orig.
+// The frames are read as the pass that deskewed read them: staged (host stores into fine-grained memory), past the caches into
+// shared memory.
+constexpr int DEBUG_STAGE_WORDS = 2048;             // the largest staged frames + matrices (flimo_capi.hip: FRAMES_FG_SLOT / 4)
+__global__ __launch_bounds__(256) void deskew_debug_kernel(const DeskewArgs dk, int n, PoseMats P, float4* __restrict__ out_world,
+                                                           float4* __restrict__ out_final) {
+  __shared__ double s_frames[DEBUG_STAGE_WORDS / 2];
+  const DevFrame* frames = static_cast<const DevFrame*>(dk.frames);
+  const float* mats = dk.mats;
+  if (dk.stage_words > 0) {                                     // (launch-uniform)
+    unsigned int* dst = reinterpret_cast<unsigned int*>(s_frames);
+    const unsigned int* src = reinterpret_cast<const unsigned int*>(dk.frames);
+    for (int i = (int)threadIdx.x; i < dk.stage_words; i += 256)
+      dst[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __syncthreads();
+    frames = reinterpret_cast<const DevFrame*>(dst);
+    mats = reinterpret_cast<const float*>(dst) + (dk.mats - static_cast<const float*>(dk.frames));
+  }
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const float4 p = dk.raw[k];
+  const unsigned int o = __float_as_uint(p.w);
+  if (o >= (unsigned int)n) return;
+  const float4 wp = deskew_world(p, dk.t[k] + dk.t_offset, frames, dk.nf, mats);
+  const float4 b = deskew_body(wp, mats, 1.0f);
+  const float* M = P.RT;
+  const float x = M[0] * b.x + (M[1] * b.y + (M[2] * b.z + M[3]));
+  const float y = M[4] * b.x + (M[5] * b.y + (M[6] * b.z + M[7]));
+  const float z = M[8] * b.x + (M[9] * b.y + (M[10] * b.z + M[11]));
+  const float w = M[12] * b.x + (M[13] * b.y + (M[14] * b.z + M[15]));
+  out_world[o] = wp;
+  out_final[o] = make_float4(x, y, z, w);
+}
+
 // ------------------------------------------------------------------------------------------
 // host-callable launchers
 // ------------------------------------------------------------------------------------------
@@ -2995,6 +3044,14 @@ void launch_deskew(hipStream_t st, const float4* in, const double* t, int n, con
   if (blocks == 0) return;
   hipLaunchKernelGGL(deskew_kernel, dim3(blocks), dim3(256), 0, st, in, t, n, (const DevFrame*)frames, nf, mats32,
                      out_sorted, out_orig, t_offset);
+}
+
+bool launch_deskew_debug(hipStream_t st, const DeskewArgs& dk, int n, const PoseMats& P, float4* out_world, float4* out_final) {
+  if (dk.stage_words > DEBUG_STAGE_WORDS) return false;
+  const int blocks = (n + 255) / 256;
+  if (blocks == 0) return true;
+  hipLaunchKernelGGL(deskew_debug_kernel, dim3(blocks), dim3(256), 0, st, dk, n, P, out_world, out_final);
+  return true;
 }
 
 void launch_transform(hipStream_t st, const float4* in, int n, const PoseMats& P, float4* out) {

@@ -232,6 +232,17 @@ static size_t copy_cloud(const pcl::PointCloud<PointType>& pc, float* out, size_
 }
 size_t flimo_loc_get_pc2match(flimo_loc* L, float* out, size_t cap) { return copy_cloud(*L->loc->get_pc2match_pointcloud(), out, cap); }
 size_t flimo_loc_get_final_scan(flimo_loc* L, float* out, size_t cap) { return copy_cloud(*L->loc->get_pointcloud(), out, cap); }
+size_t flimo_loc_get_debug_cloud(flimo_loc* L, int which, void* out, size_t cap) {
+  pcl::PointCloud<PointType>::ConstPtr pc;
+  if (which == 0) pc = L->loc->get_orig_pointcloud();
+  else if (which == 1) pc = L->loc->get_deskewed_pointcloud();
+  else if (which == 2) pc = L->loc->get_finalraw_pointcloud();
+  else return (size_t)-1;
+  if (!pc) return 0;
+  const size_t n = pc->points.size() < cap ? pc->points.size() : cap;
+  if (out && n) std::memcpy(out, pc->points.data(), n * sizeof(PointType));
+  return pc->points.size();
+}
 void flimo_loc_get_stage_times(flimo_loc* L, double t[4]) { L->loc->get_stage_times(t); }
 void flimo_loc_get_pose_cov(flimo_loc* L, double cov36[36]) {
   std::vector<double> c = L->loc->getPoseCovariance();

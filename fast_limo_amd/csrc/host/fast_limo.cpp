@@ -1207,7 +1207,8 @@ pcl::PointCloud<PointType>::Ptr Localizer::deskewPointCloud(pcl::PointCloud<Poin
   if (prof)
     fprintf(stderr, "[flimo deskew] time sort + gather %.0f us, frames/times %.0f us, upload + Morton sort %.0f us, deskew call %.0f us (n = %zu)\n",
             (tp1 - tp0) * 1e6, (tp2 - tp1) * 1e6, (tp3 - tp2) * 1e6, (tp4 - tp3) * 1e6, n);
-  if (download_clouds && arrival_order_) {
+  dbg_sweep_ = config.debug ? sorted : nullptr;                    // (debugClouds, after the update)
+  if ((download_clouds || config.debug) && arrival_order_) {
     // the GPU is busy with the deskew (and has the sweep): now the permutation of the reference's sort, for the host clouds
     const std::vector<PointType>& P = sorted->points;
     if (sensor == SensorType::OUSTER) {
@@ -1223,18 +1224,22 @@ pcl::PointCloud<PointType>::Ptr Localizer::deskewPointCloud(pcl::PointCloud<Poin
       for (size_t i = 0; i < n; i++) k[i] = P[i].timestamp;
       time_order(k.data(), 2, n, desc, false, lazy_order_);
     }
-    std::vector<float> xyz(n * 3);
-    size_t m = 0;
-    flimo_scan_get(c, xyz.data(), n, &m);
-    auto out = fast_limo::make_shared<pcl::PointCloud<PointType>>();
-    out->points.resize(n);
-    for (size_t k = 0; k < n; k++) {
-      const size_t j = lazy_order_[k];                 // position k of pc2match = arrival index j
-      PointType p = P[j];
-      p.x = xyz[3 * j]; p.y = xyz[3 * j + 1]; p.z = xyz[3 * j + 2];
-      out->points[k] = p;
+    if (download_clouds) {
+      std::vector<float> xyz(n * 3);
+      size_t m = 0;
+      flimo_scan_get(c, xyz.data(), n, &m);
+      auto out = fast_limo::make_shared<pcl::PointCloud<PointType>>();
+      out->points.resize(n);
+      for (size_t k = 0; k < n; k++) {
+        const size_t j = lazy_order_[k];               // position k of pc2match = arrival index j
+        PointType p = P[j];
+        p.x = xyz[3 * j]; p.y = xyz[3 * j + 1]; p.z = xyz[3 * j + 2];
+        out->points[k] = p;
+      }
+      pc2match = out;
+    } else {
+      pc2match = sorted;
     }
-    pc2match = out;
   } else if (download_clouds) {
     std::vector<float> xyz(n * 3);
     size_t m = 0;
@@ -1544,40 +1549,84 @@ void Localizer::releaseRawCloud() {
 
 // The device's side of the clouds: deskewed points (body frame), the same in the world frame, and -- a sweep the device put into
 // time order -- that order.  Called right after the last pass, before the map insert is handed to the Mapper's thread.
-void Localizer::downloadClouds(const double x26[26]) {
+void Localizer::downloadClouds(const double x26[26], bool registered) {
   flimo_ctx* c = map_->ctx();
   if (!c) return;
   // resident pc2match (the deskewed points, or the voxel centroids) and its world-frame image: one round trip, no repacking
   size_t n_dev = 0, got = 0;
-  if (flimo_scan_clouds(c, x26, &mat_body4_, &mat_world4_, &n_dev) != FLIMO_OK) return;
-  mat_n_dev_ = n_dev;
-  if (dev_time_ordered_) {
+  if (registered) {
+    if (flimo_scan_clouds(c, x26, &mat_body4_, &mat_world4_, &n_dev) != FLIMO_OK) return;
+    mat_n_dev_ = n_dev;
+  }
+  // config.debug: deskewed_scan and final_raw_scan, recomputed from the raw sweep by one launch (Localizer.cpp:373-374,848-850)
+  mat_n_dbg_ = 0;
+  if (config.debug && flimo_scan_debug_clouds(c, x26, &mat_dbg4_[0], &mat_dbg4_[1], &mat_n_dbg_) != FLIMO_OK) mat_n_dbg_ = 0;
+  mat_dbg_final_ = registered;
+  if (dev_time_ordered_ && (registered || mat_n_dbg_)) {
     size_t m = 0;
     flimo_ctx* oc = order_ctx_ ? order_ctx_ : c;                    // the context that ran the input stage keeps the time order
     flimo_raw_scan_order(oc, nullptr, 0, &m);
     prep_order_.resize(m);
     flimo_raw_scan_order(oc, prep_order_.data(), m, &got);
   }
-  mat_downloaded_ = true;
+  mat_downloaded_ = registered;
+}
+
+// The config.debug clouds of a sweep that was deskewed (Localizer.cpp:373-374,848-850): deskewed_scan, and for a registered sweep
+// final_raw_scan moved by the corrected pose x26.  Device front end: downloaded here, put together with the other clouds in
+// materializeClouds.  Host front end: the sweep as uploaded (dbg_sweep_, in time order or -- lazy_order_ -- arrival order) supplies
+// intensity and stamps.  As in the reference, deskewed_scan is a new cloud each sweep; final_raw_scan is overwritten in place.
+void Localizer::debugClouds(const double x26[26], bool registered) {
+  if (!config.debug) return;
+  if (dev_front_end_) { downloadClouds(x26, registered); return; }
+  flimo_ctx* c = map_->ctx();
+  const pcl::PointCloud<PointType>::Ptr S = dbg_sweep_;
+  dbg_sweep_.reset();
+  const float* dw = nullptr;
+  const float* fr = nullptr;
+  size_t n = 0;
+  if (!c || !S || flimo_scan_debug_clouds(c, x26, &dw, &fr, &n) != FLIMO_OK || n == 0) return;
+  if (n != S->points.size()) {
+    std::cout << "FAST_LIMO::WARNING: the debug clouds have " << n << " points, the sweep " << S->points.size() << ": not filled\n";
+    return;
+  }
+  const bool perm = lazy_order_.size() == n;                        // the device holds the sweep in arrival order
+  auto ds = fast_limo::make_shared<pcl::PointCloud<PointType>>();
+  ds->points.resize(n);
+  if (registered) final_raw_scan->points.resize(n);
+  for (size_t k = 0; k < n; k++) {
+    const size_t j = perm ? lazy_order_[k] : k;
+    PointType p = S->points[j];
+    p.x = dw[4 * j]; p.y = dw[4 * j + 1]; p.z = dw[4 * j + 2]; p.data_w = dw[4 * j + 3];
+    ds->points[k] = p;
+    if (registered) {
+      p.x = fr[4 * j]; p.y = fr[4 * j + 1]; p.z = fr[4 * j + 2]; p.data_w = fr[4 * j + 3];
+      final_raw_scan->points[k] = p;
+    }
+  }
+  deskewed_scan = ds;
 }
 
 void Localizer::materializeClouds(size_t n_raw) {
   static const bool prof = std::getenv("FLIMO_PROF_CLOUDS") != nullptr;     // developer timing of the stages
   const double tp0 = prof ? now_s() : 0.0;
+  const size_t n_dbg = mat_n_dbg_;                                  // config.debug clouds downloaded for this sweep (downloadClouds)
+  mat_n_dbg_ = 0;
   if (!prep_started_) return;
   helpers_->wait();
   prep_started_ = false;
   pcl::PointCloud<PointType>::Ptr input_pc = prep_input_;
   prep_input_.reset();
   const size_t m = input_pc->points.size();
-  if (last_status_ != 0 || m == 0 || !mat_downloaded_) { pc2match = fast_limo::make_shared<pcl::PointCloud<PointType>>(); return; }
+  bool main = last_status_ == 0 && m > 0 && mat_downloaded_;        // pc2match and final_scan: a registered sweep
+  if (!main) pc2match = fast_limo::make_shared<pcl::PointCloud<PointType>>();
   mat_downloaded_ = false;
   const double tp1 = prof ? now_s() : 0.0;
   // pc2match position -> index in input_pc
   const std::vector<uint32_t>& order = prep_order_;
-  if (!dev_voxel_ && order.size() != m) {
+  if (main && !dev_voxel_ && order.size() != m) {
     std::cout << "FAST_LIMO::WARNING: device and host input filters disagree (" << order.size() << " vs " << m << " points)\n";
-    return;
+    main = false;
   }
   const size_t n_dev = mat_n_dev_;
   const float* body = mat_body4_;
@@ -1585,51 +1634,90 @@ void Localizer::materializeClouds(size_t n_raw) {
   // Without the voxel grid the device's kept set must BE the host's: a different count (a filter decided differently at a boundary:
   // atan2f of the FoV filter on another libm, a NaN rule) would pair every later point with the wrong device point -- and in the
   // arrival-order layout index the pinned buffers beyond their n_dev valid records.  Refused, loudly, instead.
-  if (!dev_voxel_ && n_dev != m) {
+  if (main && !dev_voxel_ && n_dev != m) {
     std::cout << "FAST_LIMO::WARNING: device and host input filters kept different sets (" << n_dev << " vs " << m
               << " points): no clouds for this sweep\n";
     pc2match = fast_limo::make_shared<pcl::PointCloud<PointType>>();
     final_scan = fast_limo::make_shared<pcl::PointCloud<PointType>>();
-    return;
+    main = false;
   }
+  // The debug clouds hold every kept point of the deskew (never the voxel centroids, never the MAX_NUM_PC2MATCH prefix), in the
+  // same order as pc2match without the voxel grid: the device's kept set must be the host's here too.
+  bool dbg = n_dbg > 0;
+  if (dbg && (n_dbg != m || order.size() != m)) {
+    std::cout << "FAST_LIMO::WARNING: device and host input filters kept different sets (" << n_dbg << " vs " << m
+              << " points): no debug clouds for this sweep\n";
+    dbg = false;
+  }
+  const bool dfin = dbg && mat_dbg_final_;                          // final_raw_scan: a registered sweep only
+  if (!main && !dbg) return;
   // (the storage of the last sweep's clouds is taken over when the caller has let go of them: no fresh pages to fault in)
-  if (pc2match == mat_pm_) pc2match.reset();
-  if (final_scan == mat_fs_) final_scan.reset();
-  pcl::PointCloud<PointType>::Ptr pm = (mat_pm_ && mat_pm_.use_count() == 1) ? mat_pm_ : fast_limo::make_shared<pcl::PointCloud<PointType>>();
-  pcl::PointCloud<PointType>::Ptr fs = (mat_fs_ && mat_fs_.use_count() == 1) ? mat_fs_ : fast_limo::make_shared<pcl::PointCloud<PointType>>();
-  pm->points.resize(n_dev);
-  fs->points.resize(n_dev);
-  PointType* pmp = pm->points.data();
-  PointType* fsp = fs->points.data();
+  pcl::PointCloud<PointType>::Ptr pm, fs;
+  if (main) {
+    if (pc2match == mat_pm_) pc2match.reset();
+    if (final_scan == mat_fs_) final_scan.reset();
+    pm = (mat_pm_ && mat_pm_.use_count() == 1) ? mat_pm_ : fast_limo::make_shared<pcl::PointCloud<PointType>>();
+    fs = (mat_fs_ && mat_fs_.use_count() == 1) ? mat_fs_ : fast_limo::make_shared<pcl::PointCloud<PointType>>();
+    pm->points.resize(n_dev);
+    fs->points.resize(n_dev);
+  }
+  pcl::PointCloud<PointType>::Ptr ds;                              // deskewed_scan: a new cloud each sweep (Localizer.cpp:848-850)
+  if (dbg) {
+    ds = fast_limo::make_shared<pcl::PointCloud<PointType>>();
+    ds->points.resize(m);
+  }
+  if (dfin) final_raw_scan->points.resize(m);                      // final_raw_scan: overwritten in place (Localizer.cpp:373-374)
+  PointType* pmp = main ? pm->points.data() : nullptr;
+  PointType* fsp = main ? fs->points.data() : nullptr;
+  PointType* dsp = dbg ? ds->points.data() : nullptr;
+  PointType* frp = dfin ? final_raw_scan->points.data() : nullptr;
+  const float* dw = mat_dbg4_[0];
+  const float* dr = mat_dbg4_[1];
   const PointType* in = input_pc->points.data();
   const bool vox = dev_voxel_, ordered = dev_time_ordered_;
-  const size_t n_out = vox ? n_dev : std::min(n_dev, m);
+  const bool rows = main && !vox;                                  // pc2match / final_scan are rows of the sweep too
+  const size_t n_main = !main ? 0 : (vox ? n_dev : std::min(n_dev, m));
+  const size_t n_out = std::max(n_main, dbg ? m : (size_t)0);
   auto assemble = [=, &order](size_t k0, size_t k1) {
-    if (vox) {
-      for (size_t k = k0; k < k1; k++) {
+    if (main && vox) {
+      for (size_t k = k0; k < std::min(k1, n_main); k++) {
         PointType p{};
         p.x = body[4 * k]; p.y = body[4 * k + 1]; p.z = body[4 * k + 2];
         pmp[k] = p;
         p.x = world[4 * k]; p.y = world[4 * k + 1]; p.z = world[4 * k + 2];
         fsp[k] = p;
       }
-      return;
     }
+    if (!rows && !dbg) return;
+    k1 = std::min(k1, rows ? n_main : m);
     // device order: its time order (position k = input_pc[order[k]]) or arrival order (position j = input_pc[j], shown at rank k)
     for (size_t k = k0; k < k1; k++) {
       const size_t src = order[k];
       const size_t dev = ordered ? k : src;
-      if (src >= m || dev >= n_dev) continue;                       // (cannot happen after the count check above; never index past the buffers)
-      if (k + 24 < k1) {                                           // the sweep's time order is a scattered walk over three arrays
+      if (src >= m || (rows && dev >= n_dev) || (dbg && dev >= n_dbg)) continue;   // (cannot happen after the count checks above)
+      if (k + 24 < k1) {                                           // the sweep's time order is a scattered walk over the arrays
         const size_t nsrc = order[k + 24];
         __builtin_prefetch(&in[nsrc]);
-        if (!ordered) { __builtin_prefetch(&body[4 * nsrc]); __builtin_prefetch(&world[4 * nsrc]); }
+        if (!ordered) {
+          if (rows) { __builtin_prefetch(&body[4 * nsrc]); __builtin_prefetch(&world[4 * nsrc]); }
+          if (dbg) { __builtin_prefetch(&dw[4 * nsrc]); if (dfin) __builtin_prefetch(&dr[4 * nsrc]); }
+        }
       }
       PointType p = in[src];
-      p.x = body[4 * dev]; p.y = body[4 * dev + 1]; p.z = body[4 * dev + 2];
-      pmp[k] = p;
-      p.x = world[4 * dev]; p.y = world[4 * dev + 1]; p.z = world[4 * dev + 2];
-      fsp[k] = p;
+      if (rows) {
+        p.x = body[4 * dev]; p.y = body[4 * dev + 1]; p.z = body[4 * dev + 2];
+        pmp[k] = p;
+        p.x = world[4 * dev]; p.y = world[4 * dev + 1]; p.z = world[4 * dev + 2];
+        fsp[k] = p;
+      }
+      if (dbg) {                                                   // x, y, z and the 4th component as the device computed them
+        p.x = dw[4 * dev]; p.y = dw[4 * dev + 1]; p.z = dw[4 * dev + 2]; p.data_w = dw[4 * dev + 3];
+        dsp[k] = p;
+        if (dfin) {
+          p.x = dr[4 * dev]; p.y = dr[4 * dev + 1]; p.z = dr[4 * dev + 2]; p.data_w = dr[4 * dev + 3];
+          frp[k] = p;
+        }
+      }
     }
   };
   // four slices: three helpers and this thread (small clouds: not worth waking anybody)
@@ -1638,10 +1726,13 @@ void Localizer::materializeClouds(size_t n_raw) {
   for (int w = 1; w < parts; w++) helpers_->run(w - 1, [=] { assemble(std::min(n_out, w * per), std::min(n_out, (w + 1) * per)); });
   assemble(0, std::min(n_out, per));
   if (parts > 1) helpers_->wait();
-  mat_pm_.reset(); mat_fs_.reset();
-  pc2match = pm;
-  final_scan = fs;
-  mat_pm_ = pm; mat_fs_ = fs;
+  if (main) {
+    mat_pm_.reset(); mat_fs_.reset();
+    pc2match = pm;
+    final_scan = fs;
+    mat_pm_ = pm; mat_fs_ = fs;
+  }
+  if (dbg) deskewed_scan = ds;
   if (prof)
     fprintf(stderr, "[flimo clouds] wait for the host filters / order %.0f us, assembly %.0f us (%zu -> %zu points, %zu resident)\n",
             (tp1 - tp0) * 1e6, (now_s() - tp1) * 1e6, n_raw, m, n_dev);
@@ -1767,7 +1858,10 @@ void Localizer::finishUpdate(bool ok, double t0, double t1, double t2) {
       // A pass of the update failed on the GPU (the reference's Mapper::match cannot, Mapper.cpp:59-86).  The filter is back at the
       // propagated state and covariance; the scan is not inserted into the map at an unmeasured pose; the caller sees status -4 and
       // the reference's own line for a scan that produced no update (Localizer.cpp:379-380).  The next sweep registers normally.
+      double xp[26];
+      ikfom_->get_x().to_flat(xp);
       mtx_ikfom.unlock();
+      debugClouds(xp, false);                                      // deskewed_scan was set before the update (Localizer.cpp:848-850)
       std::cout << "-------------- FAST_LIMO::NULL ITERATION --------------\n";
       last_status_ = -4;
       stage_t_[0] = t1 - t0; stage_t_[1] = t2 - t1; stage_t_[2] = now_s() - t2; stage_t_[3] = 0.0;
@@ -1800,9 +1894,17 @@ void Localizer::finishUpdate(bool ok, double t0, double t1, double t2) {
       }
     }
     if (dev_front_end_ && (download_clouds || config.debug)) downloadClouds(x26);   // before the insert takes the context
+    else debugClouds(x26, true);
     if (add_to_map) map_->add_scan(x26, scan_stamp);               // returns at once; the insert overlaps the next scan's host work
     t4 = now_s();
   } else {
+    if (ok && c) {                                                 // a deskewed sweep of at most one point (Localizer.cpp:848-850)
+      double xp[26];
+      mtx_ikfom.lock();
+      ikfom_->get_x().to_flat(xp);
+      mtx_ikfom.unlock();
+      debugClouds(xp, false);
+    }
     std::cout << "-------------- FAST_LIMO::NULL ITERATION --------------\n";
     last_status_ = 1;
   }

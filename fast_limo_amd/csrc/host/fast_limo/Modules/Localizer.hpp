@@ -138,6 +138,12 @@ class fast_limo::Localizer {
   bool dev_voxel_ = false;
   const float* mat_body4_ = nullptr;          // the downloaded clouds (float4 records in the context's pinned memory)
   const float* mat_world4_ = nullptr;
+  // config.debug: deskewed_scan / final_raw_scan records of the sweep's deskew (flimo_scan_debug_clouds), in the device's order of
+  // the raw sweep; mat_n_dbg_ = 0: none downloaded for this sweep.  final_raw_scan only for a registered sweep (mat_dbg_final_).
+  const float* mat_dbg4_[2] = {nullptr, nullptr};
+  size_t mat_n_dbg_ = 0;
+  bool mat_dbg_final_ = false;
+  pcl::PointCloud<PointType>::Ptr dbg_sweep_;   // host path: the sweep in the order the device holds it (its non-xyz fields)
   // Materialization in three steps: the host-only part (input filters on the host copy, debug copy, host time order) runs on a
   // helper thread beside the GPU's front end and passes; the downloads follow the last pass (before the map insert is handed to
   // the Mapper's thread, which then owns the context); the two clouds are assembled by the helpers and the caller's thread.
@@ -152,7 +158,8 @@ class fast_limo::Localizer {
   void compactRaw(pcl::PointCloud<PointType>::Ptr& raw_pc);
   void startCloudPrep(pcl::PointCloud<PointType>::Ptr& raw_pc);
   void startCloudPrep(PointType* raw_points, size_t n_raw);
-  void downloadClouds(const double x26[26]);
+  void downloadClouds(const double x26[26], bool registered = true);
+  void debugClouds(const double x26[26], bool registered);   // config.debug clouds of a deskewed sweep (both front ends)
   pcl::PointCloud<PointType>::Ptr mat_pm_, mat_fs_;   // the clouds it handed out last (their storage is reused once the caller let go)
   size_t arrival_last_ = 0;             // index of the point the reference's sort would put last
   float rs_l2b_[16];

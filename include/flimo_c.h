@@ -270,6 +270,14 @@ int flimo_scan_to_world(flimo_ctx* ctx, const double x26[26], float* world_xyz_o
  * Localizer.cpp:361-371) in ONE round trip: packed float4 records (x, y, z, unused) in pinned memory owned by the context, valid
  * until the next flimo_scan_clouds on it.  *n = points in each. */
 int flimo_scan_clouds(flimo_ctx* ctx, const double x26[26], const float** body_xyzw, const float** world_xyzw, size_t* n);
+/* The two clouds Localizer::updatePointCloud keeps under config.debug, for the last deskew of the resident raw sweep:
+ * deskewed_scan (each point deskewed into the world frame with its own IMU pose, Localizer.cpp:848-850) and final_raw_scan (the
+ * un-voxelised deskewed sweep moved by pose x26, Localizer.cpp:373-374).  Packed float4 records (x, y, z, w: the 4th component the
+ * reference's arithmetic leaves, 1 for rigid matrices), both in the order of flimo_scan_clouds' arrays before the voxel grid and
+ * any MAX_NUM_PC2MATCH cut (all points of the deskew), in pinned memory owned by the context, valid until the next call; one round
+ * trip.  *n = 0 (no launch) when the resident scan did not come from a deskew (flimo_scan_set, a new raw sweep, a hand-over). */
+int flimo_scan_debug_clouds(flimo_ctx* ctx, const double x26_final[26], const float** deskewed_world_xyzw,
+                            const float** final_raw_xyzw, size_t* n);
 int flimo_map_add_scan(flimo_ctx* ctx, const double x26[26], double stamp);
 
 /* Wall-clock bound (milliseconds, default 2000) of the wait for a pass's result inside flimo_match_reduce: the reference's

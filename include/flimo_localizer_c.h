@@ -100,6 +100,11 @@ int    flimo_loc_num_passes(flimo_loc* L);
 void   flimo_loc_get_pass(flimo_loc* L, int i, int* M, double* HTH, double* HTh, double* dx, double* x_after);
 size_t flimo_loc_get_pc2match(flimo_loc* L, float* xyz_out, size_t cap);
 size_t flimo_loc_get_final_scan(flimo_loc* L, float* xyz_out, size_t cap);
+/* The clouds Localizer keeps under config.debug (flimo_loc_cfg.debug), as full 32-byte PointType records: which = 0
+ * get_orig_pointcloud() (the filtered sweep, LiDAR frame), 1 get_deskewed_pointcloud() (the sweep in time order, each point
+ * deskewed into the world frame), 2 get_finalraw_pointcloud() (the un-voxelised deskewed sweep in the world frame of the corrected
+ * pose).  Copies min(n, cap) records to points32_out (may be NULL when cap = 0) and returns n; (size_t)-1 for another `which`. */
+size_t flimo_loc_get_debug_cloud(flimo_loc* L, int which, void* points32_out, size_t cap);
 void   flimo_loc_get_stage_times(flimo_loc* L, double t[4]);
 void   flimo_loc_get_pose_cov(flimo_loc* L, double cov36[36]);       /* getPoseCovariance */
 /* host-side profile of register_resident: seconds in deskew call, whole update, flimo_match_reduce; passes */
