@@ -75,7 +75,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -113,6 +113,8 @@ def load_hip():
     L.flimo_map_config.argtypes = [vp, C.POINTER(MapCfg)]
     L.flimo_map_add.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.c_double]
     L.flimo_map_clear.argtypes = [vp]
+    L.flimo_map_crop_box.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.flimo_map_crop_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.flimo_map_size.restype = C.c_size_t
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
@@ -229,6 +231,20 @@ class HipCtx:
 
     def map_clear(self):
         self._chk(self._L.flimo_map_clear(self._h))
+
+    def map_crop_box(self, lo, hi) -> int:
+        """Forget the stored points outside [lo, hi] (inclusive); the map is then clear() + initialize(kept points, in insertion
+        order).  Returns the number of points removed."""
+        lo = np.ascontiguousarray(lo, dtype=np.float32).reshape(3)
+        hi = np.ascontiguousarray(hi, dtype=np.float32).reshape(3)
+        removed = C.c_size_t(0)
+        self._chk(self._L.flimo_map_crop_box(self._h, lo.ctypes.data, hi.ctypes.data, C.byref(removed)))
+        return int(removed.value)
+
+    def map_crop_stats(self):
+        o = (C.c_uint64 * 2)()
+        self._chk(self._L.flimo_map_crop_stats(self._h, o))
+        return dict(crops=int(o[0]), points_removed=int(o[1]))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

@@ -41,7 +41,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_last_sweep_tied", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_last_sweep_tied", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -131,6 +131,10 @@ def load_host():
     L.flimo_loc_set_gpu_filters.argtypes = [vp, C.c_int]
     L.flimo_loc_set_exact_tied_order.restype = None
     L.flimo_loc_set_exact_tied_order.argtypes = [vp, C.c_int]
+    L.flimo_loc_set_local_map.restype = None
+    L.flimo_loc_set_local_map.argtypes = [vp, f32p, C.c_float]
+    L.flimo_local_map_rule.restype = C.c_int
+    L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
     L.flimo_loc_last_sweep_tied.argtypes = [vp]
     L.flimo_loc_set_propagation_wait.restype = None
@@ -304,6 +308,12 @@ class Localizer:
         device's stable order (flimo_localizer_c.h)."""
         self._L.flimo_loc_set_exact_tied_order(self._h, int(on))
 
+    def set_local_map(self, half_extent, recentre_dist):
+        """A local map (default off): after a sweep's insert, once the position has moved more than ``recentre_dist`` (per-axis
+        maximum) from the box centre, the map is cropped to position +- ``half_extent``.  A non-positive or non-finite extent
+        switches it off."""
+        self._L.flimo_loc_set_local_map(self._h, np.ascontiguousarray(half_extent, dtype=np.float32).reshape(3), float(recentre_dist))
+
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))
 
@@ -390,6 +400,27 @@ class Localizer:
         def call(_keep=(x, P)):
             return fn(h, xp, pp)
         return call
+
+
+class LocalMapRule:
+    """The local-map policy's rule (flimo_local_map_rule) with its state: ``step(p)`` returns (lo, hi) when the map is to be cropped
+    now, None when not; ``off`` is True when the arguments switch the policy off."""
+
+    def __init__(self, half_extent, recentre_dist):
+        self._L = load_host()
+        self.half = np.ascontiguousarray(half_extent, dtype=np.float32).reshape(3)
+        self.recentre = float(recentre_dist)
+        self.centre = np.zeros(3, np.float64)
+        self.have = C.c_int(0)
+        self.off = False
+
+    def step(self, p):
+        lo = np.zeros(3, np.float32)
+        hi = np.zeros(3, np.float32)
+        rc = self._L.flimo_local_map_rule(np.ascontiguousarray(p, dtype=np.float64).reshape(3), self.half, self.recentre, self.centre,
+                                          C.byref(self.have), lo, hi)
+        self.off = rc < 0
+        return (lo, hi) if rc == 1 else None
 
 
 def eskf_update_fixed(x26, P, H, h, max_iters=3, limits=None, R=0.001, D=5.0):

@@ -49,6 +49,7 @@ struct flimo_ctx {
   bool force_full = false;         // the next index update lays the grid out afresh (cell size changed)
   bool full_rebuild = false;       // FLIMO_FULL_REBUILD=1: sort the whole map on every insert (A/B of the merge)
   uint64_t grid_merges = 0, grid_builds = 0, grid_regrids = 0, index_overflows = 0, pool_grows = 0;
+  uint64_t crops = 0, crop_removed = 0;   // flimo_map_crop_box: calls that removed points, points removed so far
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
@@ -956,7 +957,8 @@ static int map_append_host(flimo_ctx* c, const float4* pts, size_t n) {
 
 // Octree::update for a batch that already lives on the device (m points, NaNs allowed): the device
 // book decides keep / drop, the kept points are appended in batch order, the grid is rebuilt.
-static int map_add_device(flimo_ctx* c, const float4* d_pts, size_t m, double stamp) {
+// (known_bb: the exact box of the batch's finite points when the caller has it already -- a crop's compaction leaves it)
+static int map_add_device(flimo_ctx* c, const float4* d_pts, size_t m, double stamp, const float* known_bb = nullptr) {
   if (m == 0) return FLIMO_OK;
   if (c->map_n + m > 0x7fff0000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map would exceed 2^31 points");
   static const bool prof = getenv("FLIMO_PROF_INSERT") != nullptr;     // developer timing of the insert stages
@@ -964,7 +966,8 @@ static int map_add_device(flimo_ctx* c, const float4* d_pts, size_t m, double st
   const double t0 = prof ? now() : 0.0;
   float bb[6];
   bool any = false;
-  HIPCHK(c, batch_bbox(c->stream, d_pts, m, c->scratch, bb, &any));
+  if (known_bb) { memcpy(bb, known_bb, sizeof(bb)); any = true; }
+  else HIPCHK(c, batch_bbox(c->stream, d_pts, m, c->scratch, bb, &any));
   const double t1 = prof ? now() : 0.0;
   double t2 = t1, t3 = t1;
   if (any) {
@@ -1038,6 +1041,66 @@ extern "C" int flimo_map_add(flimo_ctx* c, const float* xyz, size_t n, size_t st
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_batch, st, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
   return map_add_device(c, c->d_batch, n, stamp);
+}
+
+// Forgetting: the stored points inside [lo, hi] stay, in insertion order; from then on the map is what flimo_map_clear +
+// flimo_map_add(kept points, one batch) gives -- Octree::clear() + initialize(kept) (Objects/Octree.hpp:186-189, 282-298).
+//  1. one compaction launch (map_crop_compact) reads d_map_raw once and writes the kept points, in order, into a transient
+//     buffer; kept count and the kept points' box come back in the mail words;
+//  2. nothing removed: the call ends there -- book, index and every counter but the crop's own are untouched;
+//  3. otherwise the book is released and built from the kept points by the first batch's path (GBook::init, which writes d_map_raw
+//     itself), the index tables are released and laid out afresh over the kept points' box (the full layout of rebuild_grid;
+//     the cells' origin is set anew), crowded-cell list and second level follow.  Everything a pass kept from the sweep before
+//     that names map positions goes: the pruning bound, the neighbour records behind flimo_match_fetch, a pass queued ahead.
+// d_map_raw, pt_leaf and d_map_sorted keep their capacity: the next adds re-use the freed tail.  The book's per-batch scratch
+// (sized by the kept count for this one call) and the transient buffer are released before the call returns.
+extern "C" int flimo_map_crop_box(flimo_ctx* c, const float lo[3], const float hi[3], size_t* removed) {
+  if (removed) *removed = 0;
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!lo || !hi) return fail(c, FLIMO_ERR_INVALID, "crop box: null bounds");
+  for (int a = 0; a < 3; a++)
+    if (!(lo[a] <= hi[a])) return fail(c, FLIMO_ERR_INVALID, "crop box: lo <= hi must hold on every axis (no NaN)");
+  if (c->map_n == 0) return FLIMO_OK;
+  ctx_enter(c);
+  const size_t n_old = c->map_n;
+  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
+  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  size_t kept = 0;
+  float bb[6];
+  HIPCHK(c, map_crop_compact(c->stream, c->d_map_raw, n_old, lo, hi, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
+  if (kept > n_old) return fail(c, FLIMO_ERR_HIP, "crop box: compaction reported %zu of %zu points", kept, n_old);
+  if (kept == n_old) return FLIMO_OK;
+  // ---- clear() ... ----
+  HIPCHK(c, c->gbook.finish(c->stream, c->scratch));
+  const double last_time = c->map_last_time;
+  const bool had_center = c->have_fine_center;
+  (void)flimo_map_clear(c);
+  c->map_last_time = last_time;                      // (a crop is no insert)
+  c->gbook.release();                                // the nodes of the forgotten regions go with the rest
+  index_free(c->idx);
+  index_free(c->fine_idx);
+  (void)hipFree(c->d_crowd_bits);
+  c->d_crowd_bits = nullptr; c->crowd_bits_cap = 0;
+  c->crowd_cells.clear(); c->crowd_listed = 0;
+  c->last_nq = 0; c->recs_valid = c->dbg_valid = false;      // the last pass's records name positions of the old arrays
+  c->crops++;
+  c->crop_removed += n_old - kept;
+  if (removed) *removed = n_old - kept;
+  if (kept == 0) return FLIMO_OK;
+  // ---- ... + initialize(kept) ----
+  c->have_fine_center = had_center;                  // (the sensor is where it was: the second level stays around it)
+  const int rc = map_add_device(c, kept_pts.p, kept, last_time, bb);
+  c->gbook.release_batch_scratch();
+  if (rc) return rc;
+  if (c->map_n != kept) return fail(c, FLIMO_ERR_HIP, "crop box: %zu of the %zu kept points were stored", c->map_n, kept);
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_crop_stats(const flimo_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return FLIMO_ERR_INVALID;
+  out[0] = c->crops; out[1] = c->crop_removed;
+  return FLIMO_OK;
 }
 
 extern "C" int flimo_map_points(flimo_ctx* c, float* out, size_t cap, size_t* n) {

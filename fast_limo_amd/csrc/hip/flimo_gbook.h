@@ -61,6 +61,7 @@ struct GBook {
   hipError_t update(hipStream_t st, const float4* batch, int m, const float bb[6], float4* map_raw, int map_n, int* kept_out,
                     MapBuildScratch& S);
   void release();
+  void release_batch_scratch();   // the per-batch buffers (about 40 bytes per point of the largest batch so far); the next batch sizes them anew
   hipError_t reserve_nodes(hipStream_t st, size_t want);
 };
 

@@ -493,6 +493,14 @@ void GBook::release() {
   *this = GBook();
 }
 
+void GBook::release_batch_scratch() {
+  (void)hipFree(keep); (void)hipFree(assign); (void)hipFree(new_index); (void)hipFree(items); (void)hipFree(cursor);
+  (void)hipFree(flags); (void)hipFree(rank); (void)hipFree(lists); (void)hipFree(tmp); (void)hipFree(big_items);
+  keep = nullptr; assign = nullptr; new_index = nullptr; items = nullptr; cursor = nullptr; flags = nullptr; rank = nullptr;
+  lists = nullptr; tmp = nullptr; big_items = nullptr;
+  batch_cap = lists_cap = big_cap = 0;
+}
+
 hipError_t GBook::import_host(hipStream_t st, const std::vector<float>& c4, const std::vector<int>& child, const std::vector<int>& cnt,
                               int root_id, const float4* map_raw, int map_n, float min_half_, bool downsample_) {
   min_half = min_half_;

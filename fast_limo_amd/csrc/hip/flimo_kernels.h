@@ -126,9 +126,12 @@ struct MapBuildScratch {
   unsigned int filt_epoch = 0, filt_ticket_base = 0;
   unsigned long long* filt_mail_host = nullptr;   // mapped: four {value, launch number} granules (extreme key, kept count, NaN mark; tied stamps)
   unsigned long long* filt_mail_dev = nullptr;
+  // the ordered compaction of a crop (map_crop_compact): per tile {state, count}, then the tile ticket and the kept count
+  unsigned long long* crop_desc = nullptr;
+  size_t crop_tiles_cap = 0;
 };
 // slots of the mail words
-enum MailSlot { MAIL_BOOK = 0 /* 6 */, MAIL_BOOK_END = 8 /* 2 */, MAIL_CROWD = 12, MAIL_BOXCOUNT = 13, MAIL_BBOX = 16 /* 6 */, MAIL_VOXEL = 24 /* 4 */, MAIL_TILES = 28 /* build: tiles, overflow; merge: tiles, overflow */, MAIL_ROWS = 32 /* an insert found the point array full */,
+enum MailSlot { MAIL_BOOK = 0 /* 6 */, MAIL_BOOK_END = 8 /* 2 */, MAIL_CROWD = 12, MAIL_BOXCOUNT = 13, MAIL_BBOX = 16 /* 6 */, MAIL_VOXEL = 24 /* 4 */, MAIL_TILES = 28 /* build: tiles, overflow; merge: tiles, overflow */, MAIL_ROWS = 32 /* an insert found the point array full */, MAIL_CROP = 36 /* kept count of a crop */,
                 MAIL_TAG = 62 /* number of the last mail_words, written behind its words */, MAIL_WORDS = 64 };
 struct MailPart { const void* src; int n; int dst; };
 // queues ONE small kernel that copies up to 6 runs of words into the mail slots; `rearm_bbox`: S.bbox is reset to the empty box
@@ -137,6 +140,11 @@ hipError_t mail_words(hipStream_t st, MapBuildScratch& S, const MailPart* parts,
                       int zero_n = 0);
 hipError_t ensure_mail(MapBuildScratch& S);
 hipError_t mail_wait(hipStream_t st, MapBuildScratch& S);   // the words of the last mail_words are in S.mail_host (spins on their tag)
+// Forgetting (flimo_map_crop_box): the points of in[0 .. n) inside [lo, hi] (inclusive, float32 compares) go to out[0 ..) in their
+// order, w = new index -- one launch that reads the map once and writes the kept part once (`blocks` workgroups take tiles by
+// ticket); *kept and the kept points' box bb (untouched when nothing is kept) come back through the mail words.  Ends synchronised.
+hipError_t map_crop_compact(hipStream_t st, const float4* in, size_t n, const float lo[3], const float hi[3], float4* out, int blocks,
+                            MapBuildScratch& S, size_t* kept, float bb[6]);
 
 // min/max of n float4 points (NaN-free) -> host bbox[6]
 hipError_t map_bbox(hipStream_t st, const float4* pts, size_t n, MapBuildScratch& S, float bbox_host[6]);

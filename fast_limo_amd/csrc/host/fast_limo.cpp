@@ -280,6 +280,12 @@ void Mapper::run_insert(const double x26[26], double stamp) {
   if (rc != FLIMO_OK) std::cout << "FAST_LIMO::map insert failed: " << flimo_last_error(ctx_) << "\n";
   insert_seconds_ = now_s() - t0;
 }
+void Mapper::run_crop(const float lo[3], const float hi[3]) {
+  size_t removed = 0;
+  const int rc = flimo_map_crop_box(ctx_, lo, hi, &removed);
+  if (rc != FLIMO_OK) std::cout << "FAST_LIMO::map crop failed: " << flimo_last_error(ctx_) << "\n";
+  crop_removed_ = removed;
+}
 void Mapper::worker_main() {
   std::unique_lock<std::mutex> lk(wm_);
   for (;;) {
@@ -292,9 +298,17 @@ void Mapper::worker_main() {
     }
     wcv_.wait(lk, [this] { return busy_.load() || quit_.load(); });
     if (quit_) return;
-    lk.unlock();
-    run_insert(job_x_, job_stamp_);                 // the only user of ctx_ while busy_ is set
-    lk.lock();
+    // an insert, then the crop that follows it -- also one that was asked for while the insert ran (crop_box)
+    while (job_insert_ || job_crop_) {
+      const bool ins = job_insert_, crop = !ins && job_crop_;
+      float lo[3], hi[3];
+      if (ins) job_insert_ = false;
+      if (crop) { job_crop_ = false; std::memcpy(lo, job_lo_, sizeof(lo)); std::memcpy(hi, job_hi_, sizeof(hi)); }
+      lk.unlock();
+      if (ins) run_insert(job_x_, job_stamp_);      // the only user of ctx_ while busy_ is set
+      else run_crop(lo, hi);
+      lk.lock();
+    }
     busy_ = false;
     wcv_.notify_all();
   }
@@ -309,7 +323,26 @@ void Mapper::add_scan(const double x26[26], double stamp) {
     std::lock_guard<std::mutex> lk(wm_);
     std::memcpy(job_x_, x26, sizeof(job_x_));
     job_stamp_ = stamp;
+    job_insert_ = true;
     busy_ = true;
+  }
+  wcv_.notify_all();
+}
+void Mapper::crop_box(const float lo[3], const float hi[3]) {
+  if (!ctx_) return;
+  if (!async_ || !worker_.joinable()) { sync(); run_crop(lo, hi); return; }
+  for (;;) {
+    {
+      std::lock_guard<std::mutex> lk(wm_);
+      if (!job_crop_) {                            // behind whatever the worker is doing now; it looks again before it goes idle
+        std::memcpy(job_lo_, lo, sizeof(job_lo_));
+        std::memcpy(job_hi_, hi, sizeof(job_hi_));
+        job_crop_ = true;
+        busy_ = true;
+        break;
+      }
+    }
+    sync();                                         // (a second crop before the first one ran: one after the other)
   }
   wcv_.notify_all();
 }
@@ -460,6 +493,37 @@ class Helpers {
 // ---------------------------------------------------------------------------------------------
 // Localizer
 // ---------------------------------------------------------------------------------------------
+int Localizer::local_map_rule(const double p[3], const float half_extent[3], float recentre_dist, double centre[3], int* have_centre,
+                              float lo[3], float hi[3]) {
+  if (!p || !half_extent || !centre || !have_centre || !lo || !hi) return -1;
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(half_extent[a]) || !(half_extent[a] > 0.f)) return -1;
+  if (!std::isfinite(recentre_dist)) return -1;
+  if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return 0;      // (no position to centre a box on)
+  if (*have_centre) {
+    double d = 0.0;                                  // per-axis maximum: the box is axis-aligned, so is the distance to its centre
+    for (int a = 0; a < 3; a++) d = std::max(d, std::fabs(p[a] - centre[a]));
+    if (!(d > (double)recentre_dist)) return 0;
+  }
+  for (int a = 0; a < 3; a++) {
+    centre[a] = p[a];
+    lo[a] = (float)(centre[a] - (double)half_extent[a]);
+    hi[a] = (float)(centre[a] + (double)half_extent[a]);
+  }
+  *have_centre = 1;
+  return 1;
+}
+void Localizer::set_local_map(const float half_extent[3], float recentre_dist) {
+  double c[3] = {0.0, 0.0, 0.0}, p0[3] = {0.0, 0.0, 0.0};
+  int have = 0;
+  float lo[3], hi[3];
+  local_map_on_ = half_extent && local_map_rule(p0, half_extent, recentre_dist, c, &have, lo, hi) >= 0;
+  local_have_centre_ = 0;                            // the next inserted sweep sets the centre
+  if (!local_map_on_) return;
+  for (int a = 0; a < 3; a++) local_half_[a] = half_extent[a];
+  local_recentre_ = recentre_dist;
+}
+
 Localizer::Localizer() : Localizer(&Mapper::getInstance()) { own_map_ = false; }
 Localizer::Localizer(Mapper* map)
     : map_(map), own_map_(false), ikfom_(new Esekf()), sensor(SensorType::UNKNOWN), scan_stamp(0.0),
@@ -1896,6 +1960,11 @@ void Localizer::finishUpdate(bool ok, double t0, double t1, double t2) {
     if (dev_front_end_ && (download_clouds || config.debug)) downloadClouds(x26);   // before the insert takes the context
     else debugClouds(x26, true);
     if (add_to_map) map_->add_scan(x26, scan_stamp);               // returns at once; the insert overlaps the next scan's host work
+    if (add_to_map && local_map_on_) {                             // local map: forget what lies outside the box around the sensor
+      float lo[3], hi[3];
+      if (local_map_rule(x26, local_half_, local_recentre_, local_centre_, &local_have_centre_, lo, hi) == 1)
+        map_->crop_box(lo, hi);                                    // behind the insert, on its worker: nothing waits here
+    }
     t4 = now_s();
   } else {
     if (ok && c) {                                                 // a deskewed sweep of at most one point (Localizer.cpp:848-850)

@@ -81,6 +81,15 @@ class fast_limo::Localizer {
                                         // GPU; true: the order std::partial_sort_copy leaves them in (Localizer.cpp:789-790), reproduced move
                                         // for move by the host front end (bit-exact centroids and cap membership, 1.5 ms per 64k sweep)
   bool last_sweep_tied() const { return dev_tied_; }      // the last sweep of the device front end had equal stamps
+  // A local map (off by default; the reference has no counterpart -- its octree only grows): after the map insert of a registered
+  // sweep at position p, if no centre is set yet or max_a |p[a] - centre[a]| > recentre_dist, then centre = p and the map is
+  // cropped to float(centre +- half_extent) (Mapper::crop_box, behind the insert).  half_extent[a] <= 0 on any axis, or a
+  // non-finite argument, switches the policy off.  Size the box as sensor range + MAX_DIST_PLANE + recentre_dist.
+  void set_local_map(const float half_extent[3], float recentre_dist);
+  // The rule itself, as a pure function (flimo_local_map_rule): 1 = crop now to [lo, hi] (centre / have_centre updated), 0 = not
+  // now, -1 = these arguments switch the policy off (nothing is touched).
+  static int local_map_rule(const double p[3], const float half_extent[3], float recentre_dist, double centre[3], int* have_centre,
+                            float lo[3], float hi[3]);
 
   static Localizer& getInstance() {
     static Localizer* loc = new Localizer();
@@ -104,6 +113,10 @@ class fast_limo::Localizer {
 
   Mapper* map_;
   bool own_map_;
+  bool local_map_on_ = false;           // set_local_map
+  float local_half_[3] = {0.f, 0.f, 0.f}, local_recentre_ = 0.f;
+  double local_centre_[3] = {0.0, 0.0, 0.0};
+  int local_have_centre_ = 0;
   flimo_host::Esekf* ikfom_;
   std::unique_ptr<flimo_chain_io> chain_io_;          // arguments / results of flimo_update_chain (20 kB: kept, not on the stack)
   std::mutex mtx_ikfom, mtx_prop;

@@ -47,7 +47,12 @@ class fast_limo::Mapper {
   // the GPU: returns at once, the insert runs on the worker thread and overlaps the host-side preparation (filters,
   // time sort) of the next scan.  FLIMO_SYNC_INSERT=1 (or set_async(false)) makes it synchronous.
   void add_scan(const double x26[26], double stamp);
-  void sync();                                  // wait for a running insert (no-op when idle)
+  // A local map: forget the stored points outside [lo, hi] (flimo_map_crop_box; the reference's octree has no erase).  With
+  // asynchronous inserts the crop runs on the same worker thread, BEHIND an insert that is running or queued: the sweep that
+  // asked for it does not wait.  sync() waits for it like for an insert.
+  void crop_box(const float lo[3], const float hi[3]);
+  size_t last_crop_removed() { sync(); return crop_removed_; }   // points the last crop_box removed
+  void sync();                                  // wait for a running insert or crop (no-op when idle)
   void set_async(bool on) { sync(); async_ = on; }
   double last_insert_seconds() { sync(); return insert_seconds_; }
   double last_handoff_time() const { return handoff_time_; }      // developer timing
@@ -73,11 +78,15 @@ class fast_limo::Mapper {
   std::mutex wm_;
   std::condition_variable wcv_;
   std::atomic<bool> busy_{false}, quit_{false};   // written under wm_, also polled without it (short spins before the condition-variable waits)
+  bool job_insert_ = false, job_crop_ = false;    // what the worker's next round holds (both under wm_)
   double job_x_[26];
   double job_stamp_ = 0.0;
+  float job_lo_[3] = {0, 0, 0}, job_hi_[3] = {0, 0, 0};
+  size_t crop_removed_ = 0;
   double handoff_time_ = 0.0;
   double insert_seconds_ = 0.0;
   void run_insert(const double x26[26], double stamp);
+  void run_crop(const float lo[3], const float hi[3]);
   void worker_main();
   Mapper(const Mapper&) = delete;
   Mapper& operator=(const Mapper&) = delete;

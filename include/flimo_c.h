@@ -86,6 +86,14 @@ int flimo_map_config(flimo_ctx* ctx, const flimo_map_cfg* cfg);
  * dropped (Octree::processPoints, Objects/Octree.hpp:243-244). */
 int flimo_map_add(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes, double stamp);
 int flimo_map_clear(flimo_ctx* ctx);
+/* A local map (no counterpart in the reference, whose octree has no erase): keeps the stored points inside [lo, hi] (inclusive,
+ * per axis, float32 compares), in insertion order; afterwards the map is the reference octree's clear() + initialize(kept)
+ * (Objects/Octree.hpp:186-189, 282-298): insertion indices are renumbered (a kept point's new index is its rank among the kept
+ * ones), the down-sampling memory of the kept region starts afresh, the k-NN index is laid out over the kept points' box.
+ * *removed (may be NULL) receives how many points went.  A crop that removes nothing changes nothing; one that removes everything
+ * leaves the map as flimo_map_clear does, except flimo_map_last_time, which a crop never touches.  FLIMO_ERR_INVALID for a NULL /
+ * NaN / lo > hi box.  Same calling rules as flimo_map_add: no pass of this context in flight. */
+int flimo_map_crop_box(flimo_ctx* ctx, const float lo[3], const float hi[3], size_t* removed);
 size_t flimo_map_size(const flimo_ctx* ctx);
 double flimo_map_last_time(const flimo_ctx* ctx);
 /* copies the stored points (insertion order: what neighbour indices refer to) as packed xyz; *n receives the total count

@@ -61,6 +61,8 @@ double flimo_last_candidates_per_query(const flimo_ctx* ctx);
  * where the maintained index differs (by meaning: a row's points in order, a row's position at every column) -- 0 by construction.
  * stats = {inserts in place, full layouts} so far. */
 int flimo_map_grid_selfcheck(flimo_ctx* ctx, uint64_t* mismatches, uint64_t stats[2]);
+/* flimo_map_crop_box so far: out[0] = calls that removed points (each one full layout), out[1] = points removed */
+int flimo_map_crop_stats(const flimo_ctx* ctx, uint64_t out[2]);
 
 /* out[0] = GPU ms of the algebra launches timed so far (timing level 1), out[1] = their number,
  * out[2] = chains run, out[3] = chains that came back before the final iteration, out[4] = chains declined */

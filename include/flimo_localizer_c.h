@@ -65,6 +65,17 @@ void   flimo_loc_set_gpu_filters(flimo_loc* L, int on);
  * points a cap cuts off; on = the order std::partial_sort_copy leaves them in (Localizer.cpp:789-790), reproduced move for move
  * by the host front end (bit-exact against the reference's library call, 1.5 ms per 64k-point sweep). */
 void   flimo_loc_set_exact_tied_order(flimo_loc* L, int on);
+/* A local map, default off (the reference has no counterpart: its octree has no erase and only grows).  After the map insert of a
+ * registered sweep at position p (the state's position), if no centre is set yet or max_a |p[a] - centre[a]| > recentre_dist,
+ * then centre = p and the map is cropped to float(centre +- half_extent) (flimo_map_crop_box), on the insert's worker thread behind
+ * the insert: the sweep does not wait for it.  half_extent[a] <= 0 on any axis, or a non-finite argument, switches the policy off.
+ * Size the box as sensor range + MAX_DIST_PLANE + recentre_dist. */
+void   flimo_loc_set_local_map(flimo_loc* L, const float half_extent[3], float recentre_dist);
+/* The rule above as a pure host function.  centre / have_centre: the policy's state (in / out; *have_centre = 0 before the first
+ * sweep).  Returns 1 when the map is to be cropped now -- centre = p, lo / hi = float(centre -+ half_extent) --, 0 when not (nothing
+ * written), -1 when the arguments switch the policy off (nothing written). */
+int    flimo_local_map_rule(const double p[3], const float half_extent[3], float recentre_dist, double centre[3], int* have_centre,
+                            float lo[3], float hi[3]);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
