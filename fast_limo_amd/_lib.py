@@ -82,7 +82,7 @@ HIP_SYMBOLS = [
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
     "flimo_set_timing", "flimo_set_timing_stride", "flimo_set_timing_deferred", "flimo_pass_count", "flimo_fused_pass_count", "flimo_tie_stats", "flimo_map_index_bytes", "flimo_fine_stats", "flimo_map_grid_selfcheck", "flimo_set_debug_records", "flimo_last_kernel_ms",
     "flimo_last_candidates_per_query", "flimo_last_widen_count", "flimo_last_stragglers", "flimo_stragglers_by_pass", "flimo_timing_totals", "flimo_timing_split", "flimo_set_path_switches", "flimo_set_wait_timeout_ms", "flimo_insert_rule_replay", "flimo_plane_fit5_host", "flimo_plane_eval5_host", "flimo_calculate_H_host",
-    "flimo_update_chain", "flimo_chain_stats", "flimo_set_update_mode", "flimo_update_mode", "flimo_scan_adopt", "flimo_set_pass_pipeline", "flimo_pass_pipeline_end", "flimo_pass_pipeline_last", "flimo_pass_pipeline_stats",
+    "flimo_update_chain", "flimo_chain_stats", "flimo_set_update_mode", "flimo_update_mode", "flimo_scan_adopt", "flimo_set_pass_pipeline", "flimo_pass_pipeline_end", "flimo_pass_pipeline_last", "flimo_pass_pipeline_stats", "flimo_device_large_bar",
 ]
 
 _hip = None
@@ -515,6 +515,17 @@ class HipCtx:
 
     def last_candidates_per_query(self) -> float:
         return float(self._L.flimo_last_candidates_per_query(self._h))
+
+
+def device_large_bar(device: int = 0) -> bool:
+    """The hardware's side of the pipelined host loop (flimo_device_large_bar): the device maps its memory for the host."""
+    v = C.c_int(0)
+    fn = load_hip().flimo_device_large_bar
+    fn.argtypes = [C.c_int, C.POINTER(C.c_int)]
+    rc = fn(int(device), C.byref(v))
+    if rc != 0:
+        raise FlimoError(f"flimo_device_large_bar({device}) failed: {_ERRS.get(rc, rc)}")
+    return bool(v.value)
 
 
 def default_match_cfg(**kw) -> MatchCfg:

@@ -231,10 +231,11 @@ struct flimo_ctx {
     uint64_t grid_version = 0;
     unsigned int end_code = 0;
     double t_launch = 0.0;
+    float prev_RT[16] = {0};   // the bound's reference pose the launch was given (a kernel argument)
   } pre;
   bool pipeline = false;                 // flimo_set_pass_pipeline (FLIMO_PIPELINE=0/1 presets it and wins)
   bool pipeline_env = false;
-  ChainHead* d_pipe_head = nullptr;      // fine-grained device memory (host-writable); nullptr: not available on this system
+  PipeHead* d_pipe_head = nullptr;       // fine-grained device memory (host-writable); nullptr: not available on this system
   unsigned int pipe_tag = 0;
   bool pipe_last_hint = false;           // flimo_pass_pipeline_last: the next pass is its update's last -- nothing is queued behind it
   unsigned long long pipe_published = 0, pipe_cancelled = 0;   // statistics
@@ -242,6 +243,7 @@ struct flimo_ctx {
   bool row_slack = true;                  // FLIMO_ROW_SLACK=0: a full layout packs the rows (A/B of the room behind every row)
   bool test_tight_array = false;          // FLIMO_TEST_TIGHT_ARRAY (tests): the cell-sorted array gets 4096 points of room instead of twice the map
   int test_publish_delay_ms = 0;         // FLIMO_TEST_PUBLISH_DELAY_MS (tests): a sleep between the age check of a waiting pass and the publish
+  int test_publish_split_ms = 0;         // FLIMO_TEST_PUBLISH_SPLIT_MS (tests): a sleep between the two halves of the published head
   PrevPass prev_before{};                // `prev` as the pass in flight was given it (a pass that has to be launched a second time)
   // Which way the iterated update runs: the chain costs about 11 us per pass on top of the pass's kernels whatever the host (the
   // algebra launch and two dispatch boundaries); the host loop costs this host's launch -> result round trip + 2-3 us of algebra --
@@ -328,6 +330,7 @@ static int ensure_dev(flimo_ctx* c, T*& p, size_t& cap, size_t need, bool keep, 
 //   FLIMO_TEST_TIGHT_ARRAY=1      (tests) the cell-sorted point array has room for 4096 more points only: inserts find it full and the
 //                                 map is laid out afresh (the path a long drive takes when the array fills up)
 //   FLIMO_TEST_PUBLISH_DELAY_MS   (tests) a sleep between the age check of a waiting pass and the publish of its pose
+//   FLIMO_TEST_PUBLISH_SPLIT_MS   (tests) a sleep between the two halves of that publish (a waiting pass starts on a complete head only)
 //   FLIMO_PROF_PASS / FLIMO_PROF_INSERT   host-side timing prints (stderr)
 // (csrc/host: FLIMO_REFERENCE_SOLVE=1 literal two-inverse gain, FLIMO_NO_FRONT_CTX=1 input stage on the main context,
 //  FLIMO_PROF_DESKEW / FLIMO_PROF_CLOUDS timing prints; bench.py: FLIMO_BENCH_*.)
@@ -346,30 +349,32 @@ static void load_dev_switches(flimo_ctx* c) {
   if (env_int("FLIMO_HOST_UPDATE", v)) c->update_mode = v != 0 ? 1 : 2;
   if (env_int("FLIMO_PIPELINE", v)) { c->pipeline = v != 0; c->pipeline_env = true; }
   if (env_int("FLIMO_TEST_PUBLISH_DELAY_MS", v) && v > 0) c->test_publish_delay_ms = v;
+  if (env_int("FLIMO_TEST_PUBLISH_SPLIT_MS", v) && v > 0) c->test_publish_split_ms = v;
   if (env_int("FLIMO_TEST_TIGHT_ARRAY", v)) c->test_tight_array = v != 0;
   if (env_int("FLIMO_ROW_SLACK", v)) c->row_slack = v != 0;
   if (env_int("FLIMO_TAIL_MAX", v) && v > 0) c->tail_max_env = v;
 }
 
-// Does the GPU see what the HOST stores into this allocation?  The host writes a pattern into the head's epoch word (a plain store
-// through the BAR, as publish_prelaunch does), a one-thread kernel reads the word past the caches and hands it back in a granule
-// of mapped host memory; twice, with different patterns.  A mapping that is missing altogether would fault at the first store --
-// the large-BAR attribute is what stands for its presence (hipPointerGetAttributes reports such memory as plain device memory);
-// FLIMO_NO_BAR=1 switches the path off on a system where that is not enough.
-static bool host_store_probe(flimo_ctx* c, ChainHead* head) {
+// Does the GPU see what the HOST stores into this allocation?  The host writes a pattern into the head's first and last granule (a
+// plain eight-byte store through the BAR, as publish_prelaunch does), a one-thread kernel reads the granule's tag word past the
+// caches and hands it back in a granule of mapped host memory.  A mapping that is missing altogether would fault at the first
+// store -- the large-BAR attribute is what stands for its presence (hipPointerGetAttributes reports such memory as plain device
+// memory); FLIMO_NO_BAR=1 switches the path off on a system where that is not enough.
+static bool host_store_probe(flimo_ctx* c, PipeHead* head) {
   volatile unsigned long long* tagp = reinterpret_cast<volatile unsigned long long*>(c->h_chain_res) + 1;
   for (unsigned int round = 0; round < 2; round++) {
     const unsigned int pattern = 0x5a17c0deu ^ (round * 0x01010101u);
-    __atomic_store_n(&head->epoch, pattern, __ATOMIC_RELEASE);
+    volatile unsigned long long* g = &head->gran[round == 0 ? 0 : PH_GRANULES - 1];
+    *g = ((unsigned long long)pattern << 32) | (unsigned long long)round;
     _mm_sfence();
     const unsigned long long tag = 0x7200000000000000ull + round;
-    launch_word_probe(c->stream, &head->epoch, c->d_chain_res, tag);
+    launch_word_probe(c->stream, reinterpret_cast<unsigned int*>(const_cast<unsigned long long*>(g)) + 1, c->d_chain_res, tag);
     if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (*tagp != tag) return false;
     const double seen = c->h_chain_res[0];
     if ((unsigned int)llround(seen) != pattern) return false;
+    *g = 0ull;
   }
-  __atomic_store_n(&head->epoch, 0u, __ATOMIC_RELEASE);
   _mm_sfence();
   memset(c->h_chain_res, 0, 2 * sizeof(double));
   return true;
@@ -455,9 +460,9 @@ extern "C" int flimo_ctx_create(int device, flimo_ctx** out) {
     int large_bar = 0;
     (void)hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device);      // (host stores into device memory need the whole of it behind the BAR)
     if (getenv("FLIMO_NO_BAR") != nullptr) large_bar = 0;      // (stands in for a system that does not map device memory for the host)
-    if (large_bar && hipExtMallocWithFlags(&p, sizeof(ChainHead), hipDeviceMallocFinegrained) == hipSuccess && p &&
-        hipMemset(p, 0, sizeof(ChainHead)) == hipSuccess && hipDeviceSynchronize() == hipSuccess && host_store_probe(c, static_cast<ChainHead*>(p))) {
-      c->d_pipe_head = static_cast<ChainHead*>(p);
+    if (large_bar && hipExtMallocWithFlags(&p, sizeof(PipeHead), hipDeviceMallocFinegrained) == hipSuccess && p &&
+        hipMemset(p, 0, sizeof(PipeHead)) == hipSuccess && hipDeviceSynchronize() == hipSuccess && host_store_probe(c, static_cast<PipeHead*>(p))) {
+      c->d_pipe_head = static_cast<PipeHead*>(p);
       void* q = nullptr;
       if (hipExtMallocWithFlags(&q, 2 * FRAMES_FG_SLOT, hipDeviceMallocFinegrained) == hipSuccess && q)
         c->d_frames_fg = static_cast<char*>(q);
@@ -1760,12 +1765,13 @@ static inline bool same_match_cfg(const flimo_match_cfg& a, const flimo_match_cf
 }
 // ---- pipelined host loop: the pass queued ahead of the algebra --------------------------------------------------------------
 static inline double wall_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// the waiting pass is told to leave (its workgroups poll head.epoch); cheap: one posted store when there is one, nothing otherwise
+// the waiting pass is told to leave (its workgroups poll the head's granules: granule 0's tag); cheap: one posted store when there
+// is one, nothing otherwise
 static inline void cancel_prelaunch(flimo_ctx* c) {
   if (!c->pre.active) return;
   c->pre.active = false;
   c->pipe_cancelled++;
-  __atomic_store_n(&c->d_pipe_head->epoch, c->pre.end_code, __ATOMIC_RELEASE);
+  *reinterpret_cast<volatile unsigned long long*>(&c->d_pipe_head->gran[0]) = (unsigned long long)c->pre.end_code << 32;
   _mm_sfence();
 }
 // every entry point that queues work on the context's stream passes here first: nothing may line up behind a pass that waits
@@ -1773,23 +1779,21 @@ static inline void ctx_enter(flimo_ctx* c) {
   (void)hipSetDevice(c->device);
   cancel_prelaunch(c);
 }
-// the constants of the waiting pass: pose, the last pass's pose (its pruning bound's reference), then -- behind a store fence --
-// the word its workgroups poll
-static inline void publish_prelaunch(flimo_ctx* c, const PoseMats& P, const float prev_RT[16], unsigned long long seq) {
-  ChainHead h;
-  memset(&h, 0, sizeof(h));
-  h.pose = P;
-  memcpy(h.prev_RT, prev_RT, sizeof(h.prev_RT));
-  h.status = 0;
-  // (everything but the epoch word, in 8-byte stores; then the epoch)
-  const size_t words8 = offsetof(ChainHead, status) / 8;
-  static_assert(offsetof(ChainHead, status) % 8 == 0 && offsetof(ChainHead, epoch) == offsetof(ChainHead, status) + 4, "ChainHead layout");
-  volatile unsigned long long* dst = reinterpret_cast<volatile unsigned long long*>(c->d_pipe_head);
-  const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&h);
-  for (size_t i = 0; i < words8; i++) dst[i] = src[i];
-  __atomic_store_n(&c->d_pipe_head->status, 0, __ATOMIC_RELAXED);
-  _mm_sfence();
-  __atomic_store_n(&c->d_pipe_head->epoch, ch_epoch_of(seq), __ATOMIC_RELEASE);
+// the constants of the waiting pass: PH_GRANULES eight-byte stores {word, epoch} (PipeHead, flimo_chain.h) -- no order among them is
+// needed, the pass starts when it has seen every one (its bound's reference pose went with the launch)
+static inline void publish_prelaunch(flimo_ctx* c, const PoseMats& P, unsigned long long seq) {
+  unsigned int w[PH_GRANULES] = {0u};
+  const unsigned int* src = reinterpret_cast<const unsigned int*>(&P);
+  for (int i = 0; i < PH_WORDS; i++) w[i] = src[i < 36 ? (i / 12) * 16 + i % 12 : i + 12];
+  const unsigned long long tag = (unsigned long long)ch_epoch_of(seq) << 32;
+  volatile unsigned long long* dst = c->d_pipe_head->gran;
+  for (int i = 0; i < PH_GRANULES; i++) {
+    if (i == PH_GRANULES / 2 && c->test_publish_split_ms > 0) {
+      _mm_sfence();
+      std::this_thread::sleep_for(std::chrono::milliseconds(c->test_publish_split_ms));
+    }
+    dst[i] = tag | (unsigned long long)w[i];
+  }
   _mm_sfence();
   c->pre.active = false;
   c->pipe_published++;
@@ -1943,7 +1947,8 @@ static int pass_plan(flimo_ctx* c, const double x26[26], const flimo_match_cfg* 
   bool use_pre = c->pre.active && !pl.general_k && c->prev.valid && c->pre.nq == nq && c->pre.seq == c->pass_seq + 1 &&
                  same_match_cfg(c->pre.cfg, *cfg) && c->pre.grid_version == pl.grid_version && !c->deskew_pending &&
                  !(nq < c->sorted_n || (c->sorted_n < c->scan_n && nq > c->sorted_n)) && c->pre.n_all == (int)c->sorted_n &&
-                 !c->debug_recs && !(cfg->MAX_NUM_MATCHES >= 0 && (size_t)cfg->MAX_NUM_MATCHES < nq);
+                 !c->debug_recs && !(cfg->MAX_NUM_MATCHES >= 0 && (size_t)cfg->MAX_NUM_MATCHES < nq) &&
+                 memcmp(c->pre.prev_RT, c->prev.RT, sizeof(c->pre.prev_RT)) == 0;      // (its bound's reference pose went with the launch)
   if (use_pre && !(wall_s() - c->pre.t_launch < 0.25e-3 * (double)CH_POLL_MS)) { use_pre = false; c->pipe_aged++; }      // (this call's, but too old)
   if (!use_pre) cancel_prelaunch(c);
   pre_guard.decided = true;
@@ -2088,7 +2093,7 @@ static int pass_launch(flimo_ctx* c, PassPlan& pl) {
   const unsigned long long seq = pl.seq;
   const int tlev = pl.tlev;
   if (pl.use_pre) {
-    publish_prelaunch(c, P, c->prev.RT, seq);
+    publish_prelaunch(c, P, seq);
     c->fused_passes++;
   } else if (pl.after_fine) {
     launch_knn5_fine(c->stream, c->fine, c->d_scan_sorted, n_all, P, c->d_nbr, c->prev, c->fine_qlo, c->fine_qhi, &pl.tl, seq);
@@ -2158,13 +2163,15 @@ static int pass_launch(flimo_ctx* c, PassPlan& pl) {
       ChainCtl pc{};
       pc.end_code = 0x80000000u | (++c->pipe_tag & 0x7fffffffu);
       PrevPass pv = c->prev;
-      pv.valid = 1;                                            // (its reference pose comes from the head)
+      pv.valid = 1;                                            // (pv.RT, this pass's pose, is the bound's reference the launch will use:
+                                                               //  a kernel argument, compared again before the publish -- pass_plan)
       launch_match_fused(c->stream, c->grid, c->d_scan_sorted, n_all, P, mp, c->d_nbr, c->d_wl, c->d_wl_count, nullptr, pv,
                          c->live_idx, c->d_fit2_partials, c->d_granules_host, c->d_ticket, nseq, nullptr, nullptr, &tln, 0, nullptr,
-                         c->d_pipe_head, &pc, pl.bookp, ch_epoch_of(nseq));
+                         nullptr, &pc, pl.bookp, ch_epoch_of(nseq), c->d_pipe_head);
       HIPCHK(c, hipGetLastError());
       c->pre.active = true; c->pre.seq = nseq; c->pre.nq = nq; c->pre.n_all = n_all; c->pre.pos = npos; c->pre.cfg = *cfg;
       c->pre.grid_version = pl.grid_version; c->pre.end_code = pc.end_code; c->pre.t_launch = wall_s();
+      memcpy(c->pre.prev_RT, pv.RT, sizeof(c->pre.prev_RT));
     }
   }
   return FLIMO_OK;
@@ -2389,6 +2396,13 @@ extern "C" int flimo_pass_pipeline_stats(const flimo_ctx* c, unsigned long long 
   out[0] = c->pipe_published; out[1] = c->pipe_cancelled; out[2] = c->pipe_aged; out[3] = c->pipe_left;
   return FLIMO_OK;
 }
+extern "C" int flimo_device_large_bar(int device, int* large_bar) {
+  if (!large_bar) return FLIMO_ERR_INVALID;
+  int v = 0;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeIsLargeBar, device) != hipSuccess) { (void)hipGetLastError(); return FLIMO_ERR_HIP; }
+  *large_bar = v;
+  return FLIMO_OK;
+}
 extern "C" int flimo_update_mode(const flimo_ctx* c, int* chained, double* launch_rtt_us) {
   if (!c) return FLIMO_ERR_INVALID;
   if (chained) *chained = c->host_update ? 0 : 1;
@@ -2492,20 +2506,18 @@ extern "C" int flimo_update_chain(flimo_ctx* c, const flimo_match_cfg* cfg, flim
     pv.valid = prev_valid ? 1 : 0;            // (pass 0: the context's own bound, if any; later passes: RT comes from the device filter)
     TieList tl{};                                // (ties are settled inside the reducing launches: nothing is listed)
     tl.count_next = c->d_tie_count + ((seq + 1) & 1);
-    unsigned int wait_epoch = 0u;                 // (the algebra launch queued before this pass has stored its constants)
     if (after_fine) {
-      launch_knn5_fine(c->stream, c->fine, c->d_scan_sorted, n_all, P0, c->d_nbr, pv, c->fine_qlo, c->fine_qhi, &tl, seq, ch, wait_epoch, ctl.end_code);
-      wait_epoch = 0u;
+      launch_knn5_fine(c->stream, c->fine, c->d_scan_sorted, n_all, P0, c->d_nbr, pv, c->fine_qlo, c->fine_qhi, &tl, seq, ch);
       c->fine_passes++;
     }
     const DeskewArgs* dk = i == 0 ? dkp : nullptr;
     if (fused) {
       launch_match_fused(c->stream, c->grid, c->d_scan_sorted, n_all, P0, mp, c->d_nbr, c->d_wl, c->d_wl_count, nullptr, pv, c->live_idx,
                          c->d_fit2_partials, c->d_chain_gran, c->d_ticket, seq, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, &tl,
-                         after_fine ? 1 : 0, dk, ch, &ctl, bookp, wait_epoch);
+                         after_fine ? 1 : 0, dk, ch, &ctl, bookp);      // (the algebra launch queued before this pass has stored its constants)
     } else {
       launch_knn5(c->stream, 2, c->grid, c->d_scan_sorted, n_all, P0, mp.max_ring, c->d_nbr, c->d_wl, c->d_wl_count, nullptr, pv, 0,
-                  ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, nullptr, &tl, after_fine ? 1 : 0, seq, dk, ch, wait_epoch, ctl.end_code);
+                  ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, nullptr, &tl, after_fine ? 1 : 0, seq, dk, ch);
       {
         launch_widen(c->stream, c->grid, c->d_scan_sorted, P0, mp.max_ring, c->d_nbr, c->d_wl, c->d_wl_count, nullptr, ev ? ev[6] : nullptr, ev ? ev[7] : nullptr, &tl, ch);
         launch_fit2(c->stream, c->grid, c->d_scan_sorted, n_all, c->d_nbr, P0, mp, c->live_idx, c->d_fit2_partials, c->d_chain_gran,

@@ -26,11 +26,26 @@ struct ChainHead {
   PoseMats pose;           // float32 constants of the NEXT pass (State casts, get_RT / get_RT_inv / get_extr_RT_inv, calculate_H's rotations)
   float prev_RT[16];       // body -> world of the pass just completed: the next pass's pruning bound is relative to it
   int status;              // 0: the chain goes on; 2: handed back to the host filter
-  unsigned int epoch;      // pipelined host loop: number (low 32 bits) of the pass these constants are FOR -- written last, behind them
-  unsigned int decision;   // a launch that waits for `epoch`: workgroup 0's verdict when the wait runs out (chain_enter, flimo_kernels.hip); written by the device only
   int pad;
 };
 static_assert(sizeof(ChainHead) % 4 == 0 && sizeof(ChainHead) / 4 <= 128, "a pass workgroup reads the head with one load per thread");
+
+// The head of a pass that the pipelined host loop queued ahead of its pose (flimo_capi.hip: publish_prelaunch): fine-grained device
+// memory the HOST stores into.  The constants travel as eight-byte granules {word (low half), epoch (high half)}: data and "go" in one
+// -- a waiting workgroup's look is one wave-wide load, lane i reads granule i (chain_enter, flimo_kernels.hip), and an eight-byte
+// aligned store is the only unit either side relies on.  The words: rows 0 .. 2 of PoseMats' three 4 x 4 matrices (their last rows
+// are 0 0 0 1 by construction, flimo_pose.h), then its two 3 x 3 ones; granules PH_WORDS .. PH_GRANULES - 1 carry the tag alone.
+// The epoch is the number of the pass the constants are FOR (ch_epoch_of); granule 0's tag doubles as the word that tells a waiting
+// launch to leave (ChainCtl::end_code, top bit set).  prev_RT of such a pass is known when it is queued: a kernel argument.
+constexpr int PH_GRANULES = 64;
+constexpr int PH_WORDS = 3 * 12 + 9 + 9;
+struct PipeHead {
+  unsigned long long gran[PH_GRANULES];
+  unsigned int decision;   // workgroup 0's verdict when the wait runs out (chain_enter); written by the device only
+  unsigned int pad[15];
+};
+static_assert(PH_WORDS <= PH_GRANULES && sizeof(PoseMats) == (PH_WORDS + 12) * 4, "every live word of PoseMats has its granule");
+struct PrevRT { float v[16]; };
 
 // The prior of a scan's update, written by the host into mapped memory before the chain is enqueued (copied to the device filter
 // by the first pass's extra workgroup, beside the pass).  The measurement-independent half of iteration -1 (x == x_prop: no
@@ -71,7 +86,7 @@ struct ChainCtl {
   double2* res;                // mapped host memory: CH_RES result granules {value, tag}
   double2* log;                // mapped host memory: per-pass log (or nullptr)
   unsigned long long tag;      // tag of this scan's chain
-  unsigned int end_code;       // a pass queued ahead of its pose (pipelined host loop): head.epoch takes this value (top bit set) when it is told to leave
+  unsigned int end_code;       // a pass queued ahead of its pose (pipelined host loop): the tag of PipeHead's granule 0 takes this value (top bit set) when it is told to leave
 };
 
 // Results: 16-byte granules {value, tag} in mapped host memory (data and "ready" travel together, like a pass's sums)
@@ -90,7 +105,7 @@ size_t chain_state_size();
 void launch_ieskf(hipStream_t st, const ChainCtl& ch, unsigned long long seq, const float* used_RT_host_or_null,
                   hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 void launch_ieskf_extra(hipStream_t st, const ChainCtl& ch, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);   // developer tool
-// head.epoch of the pass numbered seq: never zero (zero means "do not wait"), top bit clear (set: an end code)
+// PipeHead's epoch of the pass numbered seq: never zero (zero means "do not wait"), top bit clear (set: an end code)
 __host__ __device__ inline unsigned int ch_epoch_of(unsigned long long seq) { return (unsigned int)(seq & 0x3fffffffull) | 0x40000000u; }
 constexpr int CH_POLL_MS = 50;           // a pass's workgroups give up waiting for their constants after this long (status FAILED)
 

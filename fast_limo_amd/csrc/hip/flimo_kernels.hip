@@ -276,8 +276,17 @@ __shared__ unsigned long long s_trace_lds[2][8];
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                         \
     if (threadIdx.x == 0) s_trace_lds[k][slot] = wall_clock64();                                        \
   } while (0)
+// ... by another thread than 0 (only its own wave drains its memory operations)
+#define TRACE_LANE(k, slot, tid)                                                                        \
+  do {                                                                                                  \
+    if (threadIdx.x == (tid)) {                                                                         \
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                       \
+      s_trace_lds[k][slot] = wall_clock64();                                                            \
+    }                                                                                                   \
+  } while (0)
 #define TRACE_FLUSH()                                                                                   \
   do {                                                                                                  \
+    __syncthreads();                                                                                    \
     if (threadIdx.x == 0 && blockIdx.x < 16384)                                                         \
       for (int k_ = 0; k_ < 2; k_++) for (int s_ = 0; s_ < 8; s_++) g_trace[k_][blockIdx.x * 8 + s_] = s_trace_lds[k_][s_]; \
   } while (0)
@@ -288,6 +297,7 @@ __shared__ unsigned long long s_trace_lds[2][8];
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_trace[k][blockIdx.x * 8 + (slot)] = wall_clock64();  \
   } while (0)
 #define TRACE_FLUSH() do {} while (0)
+#define TRACE_LANE(k, slot, tid) do {} while (0)
 #endif
 extern "C" int flimo_trace_read(int k, unsigned long long* out, size_t n) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), n * sizeof(unsigned long long), (size_t)k * 16384 * 8 * sizeof(unsigned long long),
@@ -296,6 +306,7 @@ extern "C" int flimo_trace_read(int k, unsigned long long* out, size_t n) {
 #else
 #define TRACE(k, slot) do {} while (0)
 #define TRACE_FLUSH() do {} while (0)
+#define TRACE_LANE(k, slot, tid) do {} while (0)
 #endif
 
 FLIMO_DEV u64 make_key(float d, uint32_t idx) { return ((u64)__float_as_uint(d) << 32) | (u64)idx; }
@@ -1435,63 +1446,82 @@ __global__ __launch_bounds__(256) KNN_WPE void knn5_kernel(GridView G, const flo
     reinterpret_cast<uint32_t*>(&s_pose)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&P)[threadIdx.x];
   knn5_pass<L, SLOTS, FUSE, FINE>(G, s_dir, &dr, scan_sorted, n, s_pose, max_ring, nbr, wl, wl_count, cand_total, prev.RT, prev.valid, prev.probe_min, tail, fa);
 }
-// How a launch of a chained pass gets the filter's head: a copy in the workgroup's shared memory (one word per thread), which the pass
-// reads its constants from.  wait_epoch == 0: the head was stored by an earlier launch on this stream (the algebra as a launch of
-// its own; a later launch of a pass whose first one waited): plain loads.  Otherwise a resident workgroup publishes it while this
-// launch is already placed: one thread polls head.epoch in device memory (s_sleep between looks, bounded by the wall clock), then
-// the workgroup reads the head past the caches.  nullptr: the chain has ended (or the wait ran out): leave.
-__device__ __forceinline__ const ChainHead* chain_enter(const ChainHead* __restrict__ H, unsigned int wait_epoch, unsigned int end_code) {
+// How a launch of a chained pass gets the filter's head: a copy in the workgroup's shared memory, which the pass reads its constants
+// from.  pipe == nullptr: the head was stored by an earlier launch on this stream (the algebra as a launch of its own): plain loads,
+// one word per thread.  Otherwise the launch was queued ahead of its pose (pipelined host loop) and the HOST publishes the constants
+// while the launch is already placed: PH_GRANULES eight-byte granules {word, epoch} in device memory (PipeHead, flimo_chain.h).
+// "Go" and the data are ONE round trip: every look of the workgroup's first wave is one wave-wide 8-byte load past the caches, lane i
+// reads granule i, and when all tags carry the awaited epoch the constants are in registers already -- they go to shared memory
+// behind the one barrier (s_sleep between looks, bounded by the wall clock).  The bound's reference pose, known when the launch
+// was queued, comes as a kernel argument.  nullptr: the chain has ended (or the wait ran out): leave.
+__device__ __forceinline__ const ChainHead* chain_enter(const ChainHead* __restrict__ H, const PipeHead* __restrict__ pipe, const PrevRT& prt,
+                                                        unsigned int wait_epoch, unsigned int end_code) {
   constexpr int NW = (int)(sizeof(ChainHead) / 4);
   __shared__ unsigned int s_head[NW];
   __shared__ int s_go;
-  if (wait_epoch != 0u) {
-    if (threadIdx.x == 0) {
+  if (pipe != nullptr) {
+    const int tid = (int)threadIdx.x;
+    if (tid < 64) {
       const unsigned long long t0 = wall_clock64();
       int go = 0;
-      // (the algebra takes a few microseconds from the moment the last pass delivered: hundreds of workgroups looking at one word
+      unsigned long long gv = 0ull;
+      // (the algebra takes a few microseconds from the moment the last pass delivered: hundreds of workgroups looking at the head
       //  every 60 ns would stand in its way -- a first look, a nap of 1.5 us (the host's algebra of a pipelined loop takes two),
       //  then a look every quarter of a microsecond)
-      // Whether the launch runs or leaves is ONE decision for all of its workgroups.  Every workgroup looks at the host's word and
-      // goes the moment it sees its constants published (no atomics, nothing between the publish and the start); only workgroup 0
+      // Whether the launch runs or leaves is ONE decision for all of its workgroups.  Every workgroup looks at the host's granules and
+      // goes the moment it sees ALL of them published (no atomics, nothing between the publish and the start); only workgroup 0
       // may declare the wait over, and it does so in two steps through the head's decision word: "pending", a grace period longer
-      // than a store takes to become visible, then -- after another look at the host's word -- "leave", or "go" when the publish
-      // arrived in between.  A workgroup that finds "pending" waits for the verdict; one that finds "leave" leaves even if it
-      // also sees the publish (the host reads the same word and launches the pass again).  So a host thread descheduled around its
-      // publish can no longer leave half a launch running and half of it gone (tickets never completed, sums that cannot come).
+      // than a store takes to become visible, then -- after another look at the host's granules -- "leave", or "go" when the publish
+      // was complete in between.  A workgroup that finds "pending" waits for the verdict; one that finds "leave" leaves even if it
+      // also sees the publish (the host reads the same word and launches the pass again); one that finds "go" keeps looking until
+      // it holds the complete head itself.  So a host thread descheduled around its publish can no longer leave half a launch
+      // running and half of it gone (tickets never completed, sums that cannot come).
       // The word holds the wait's own number: go = number, pending = number | bit 31, leave = number without bit 30 | bit 31.
-      unsigned int* dec = const_cast<unsigned int*>(&H->decision);
+      // The host tells a launch to leave through granule 0's tag (end_code: top bit set, never an epoch).
+      unsigned int* dec = const_cast<unsigned int*>(&pipe->decision);
       const unsigned int v_go = wait_epoch, v_pend = wait_epoch | 0x80000000u, v_no = (wait_epoch & 0x3fffffffu) | 0x80000000u;
       for (int look = 0;; look++) {
         const unsigned int d = __hip_atomic_load(dec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const unsigned int e = __hip_atomic_load(&H->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (written by the HOST)
+        gv = __hip_atomic_load(&pipe->gran[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);                 // (written by the HOST)
+        const unsigned int e = (unsigned int)(gv >> 32);
+        const bool all = __ballot(e == wait_epoch) == ~0ull;
+        const unsigned int e0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)e);
         if (d == v_no) break;
         if (d == v_pend) { __builtin_amdgcn_s_sleep(8); continue; }
-        if (e == wait_epoch || d == v_go) { go = 1; break; }
-        if (e == end_code) break;                              // (told to leave by the host: every workgroup reads the same)
+        if (all) { go = 1; break; }
+        if (e0 == end_code) break;                             // (told to leave by the host: every workgroup reads the same)
         const unsigned long long waited = wall_clock64() - t0;                                                // 100 MHz
-        if (blockIdx.x == 0 && waited > (unsigned long long)CH_POLL_MS * 100000ull) {
-          __hip_atomic_store(dec, v_pend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (blockIdx.x == 0 && d != v_go && waited > (unsigned long long)CH_POLL_MS * 100000ull) {
+          if (tid == 0) __hip_atomic_store(dec, v_pend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           for (int nap = 0; nap < 4; nap++) __builtin_amdgcn_s_sleep(127);                                   // >= 10 us
-          const unsigned int e2 = __hip_atomic_load(&H->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          go = e2 == wait_epoch ? 1 : 0;
-          __hip_atomic_store(dec, go ? v_go : v_no, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          gv = __hip_atomic_load(&pipe->gran[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          go = __ballot((unsigned int)(gv >> 32) == wait_epoch) == ~0ull ? 1 : 0;
+          if (tid == 0) __hip_atomic_store(dec, go ? v_go : v_no, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           break;
         }
         if (waited > 4ull * (unsigned long long)CH_POLL_MS * 100000ull) break;      // (backstop: workgroup 0 decides long before)
         if (look == 0) __builtin_amdgcn_s_sleep(48);
         else __builtin_amdgcn_s_sleep(8);
       }
-      s_go = go;
+      // granule i -> word of the head: rows 0 .. 2 of the three 4 x 4 matrices (12 words each), then the two 3 x 3 ones
+      if (go && tid < PH_WORDS) s_head[tid < 36 ? (tid / 12) * 16 + tid % 12 : tid + 12] = (unsigned int)gv;
+      if (tid == 0) s_go = go;
+    } else if (tid < 64 + 12) {
+      // the matrices' last rows are 0 0 0 1 by construction (flimo_pose.h): not transported
+      const int k = tid - 64;
+      s_head[(k / 4) * 16 + 12 + k % 4] = __float_as_uint(k % 4 == 3 ? 1.f : 0.f);
+    } else if (tid >= 128 && tid < 128 + 16) {
+      s_head[offsetof(ChainHead, prev_RT) / 4 + (tid - 128)] = __float_as_uint(prt.v[tid - 128]);
+    } else if (tid >= 192 && tid < 192 + NW - (int)(offsetof(ChainHead, status) / 4)) {
+      s_head[offsetof(ChainHead, status) / 4 + (tid - 192)] = 0u;      // status 0: the chain goes on
     }
     __syncthreads();
     if (!s_go) return nullptr;
-    if ((int)threadIdx.x < NW)
-      s_head[threadIdx.x] = __hip_atomic_load(reinterpret_cast<const unsigned int*>(H) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   } else {
     if ((int)threadIdx.x < NW) s_head[threadIdx.x] = reinterpret_cast<const unsigned int*>(H)[threadIdx.x];
+    __syncthreads();
   }
-  __syncthreads();
   const ChainHead* Lh = reinterpret_cast<const ChainHead*>(s_head);
   return Lh->status != 0 ? nullptr : Lh;
 }
@@ -1502,7 +1532,7 @@ __global__ __launch_bounds__(256) KNN_WPE void knn5_chain_kernel(GridView G, con
                                                    const ChainHead* __restrict__ H, int max_ring, NbrRec* __restrict__ nbr,
                                                    int* __restrict__ wl, int* __restrict__ wl_count,
                                                    unsigned long long* __restrict__ cand_total, int prev_valid, unsigned probe_min, int tail,
-                                                   FuseArgs fa, unsigned int wait_epoch) {
+                                                   FuseArgs fa, unsigned int wait_epoch, const PipeHead* __restrict__ pipe, PrevRT prt) {
   // (the directory of the map's index is copied while the launch may still be waiting for its pose: the map does not change
   //  between the passes of a scan)
   __shared__ __align__(16) uint16_t s_dir[GRID_DIR_MAX];
@@ -1510,7 +1540,7 @@ __global__ __launch_bounds__(256) KNN_WPE void knn5_chain_kernel(GridView G, con
     const DirRegs dr = grid_dir_fetch(G);
     grid_dir_store(s_dir, dr);
   }
-  const ChainHead* Lh = chain_enter(H, wait_epoch, fa.ch.end_code);
+  const ChainHead* Lh = chain_enter(H, pipe, prt, wait_epoch, fa.ch.end_code);
   if (!Lh) return;
   knn5_pass<L, SLOTS, FUSE, FINE>(G, s_dir, nullptr, scan_sorted, n, Lh->pose, max_ring, nbr, wl, wl_count, cand_total, Lh->prev_RT, prev_valid, probe_min, tail, fa);
 }
@@ -1939,6 +1969,29 @@ FLIMO_DEV void fit_row(const GridView& G, const PoseMats& P, const MatchParams& 
   v[13] = 1.f;
 }
 
+// The launch's two counters, published in slot 0 of the granules (the host waits for these two first) by the one lane of the launch
+// that loaded them (fit_reduce_publish): granule FIT_LIVE = queries of this pass that needed more than their 3x3x3 block, granule
+// FIT_LIVE + 1 = queries whose five hinge on an exact distance tie (the host then runs tie_kernel and the fit again).  Then
+// everything launch-wide is re-armed (behind the loads).
+__device__ __forceinline__ void publish_counters(int n_wl, unsigned int n_tie, double2* __restrict__ out_granules,
+                                                 unsigned int* __restrict__ ticket, int* __restrict__ wl_count, unsigned long long seq,
+                                                 const TieList& tl) {
+  typedef double v2d_t __attribute__((ext_vector_type(2)));
+  // (s_nop 1 after every such store: the two wait states of the VMEM-store-data hazard on gfx940+, which the compiler cannot insert
+  //  for inline assembly -- the next VALU write of g's registers could otherwise reach the store)
+  v2d_t g;
+  g.x = (double)n_wl;
+  g.y = __longlong_as_double((long long)seq);
+  double2* o = out_granules + FIT_LIVE;
+  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(o), "v"(g) : "memory");
+  g.x = (double)n_tie;
+  o = out_granules + FIT_LIVE + 1;
+  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(o), "v"(g) : "memory");
+  __hip_atomic_store(ticket + FIT_GROUPS, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(wl_count, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tl.count_next) __hip_atomic_store(tl.count_next, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Block-wide part of a pass: the wave's ROWS rows X = [H | h | valid] -> D = X^T X on the f64 matrix core (4 rows per MFMA),
 // the 91 sums the filter reads -> per-block partial (written through) -> ticket -> the last block of each of the FIT_GROUPS
 // groups adds its group's partials in block order (two halves, fixed order: bit-reproducible) and publishes 16-byte
@@ -1990,11 +2043,19 @@ __device__ __forceinline__ void fit_reduce_publish(const float (&v)[16], bool ow
   if (*s_last) {
     // Launch-wide ticket (slot FIT_GROUPS): the group whose last block arrives here LAST knows that every block of EVERY group has
     // taken its group ticket, i.e. finished its k-NN / tail phase (in the one-launch pass the groups run concurrently: the last
-    // block of group 0 alone cannot know that).  Only that block reads the two counters of the pass and re-arms them.  Taken now,
-    // so that the round trip overlaps the loads of the group's partials.
-    bool launch_last = false;
-    if (threadIdx.x == 0)
-      launch_last = __hip_atomic_fetch_add(ticket + FIT_GROUPS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)FIT_GROUPS - 1u;
+    // block of group 0 alone cannot know that).  Only that block reads the two counters of the pass and re-arms them.  The ticket
+    // and the counters are the work of a lane that owns no slice of the gather (thread 255): the ticket is taken now, so that its
+    // round trip overlaps the loads of the group's partials; the counters' loads go out right behind the gather's wait (the ticket
+    // is back by then), both at once, and are on their way while the sums are added and published -- the host, which waits for
+    // the counters' granules first, no longer gets them one (with a tie list two) load round trips behind the sums.
+    // (the ticket's VALUE is first looked at behind the gather: a comparison here would make the wave wait for the atomic's return
+    //  before it issues its share of the gather -- the round trip the early ticket is there to hide)
+    //  (and the address is handed over in a vector register: for an address it knows to be the same in every lane the compiler
+    //  adds up the wave's increments itself and broadcasts the returned value at once, which is the same wait)
+    unsigned int launch_ticket = 0xffffffffu;
+    unsigned int* launch_slot = ticket + FIT_GROUPS;
+    asm volatile("" : "+v"(launch_slot));
+    if (threadIdx.x == 255) launch_ticket = __hip_atomic_fetch_add(launch_slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // Five slices of the group's block list x 48 column PAIRS: 16-byte loads, a slice's thirteen (at 64 blocks per group) in flight
     // at once -- one round trip, where round 5's 32 eight-byte loads per thread went out in two to three batches behind their
     // address arithmetic (1.5 us of the launch's tail).  Agent-scope loads (sc1) read past this XCD's L2.  Fixed slices, fixed
@@ -2007,21 +2068,41 @@ __device__ __forceinline__ void fit_reduce_publish(const float (&v)[16], bool ow
       const double* base = partials + (size_t)group * FIT_LIVE_PAD + 2 * c2;
       const size_t stride = (size_t)FIT_GROUPS * FIT_LIVE_PAD;
       for (int k = k0; k < k1; k += 16) {
-        v2d_t w[16];
+        // (the sixteen loads and their wait are ONE statement with early-clobber outputs: the compiler sees registers that are
+        //  written when the statement ends, so it can neither move nor spill one while its data is in flight)
+        const double* q[16];
 #pragma unroll
-        for (int u = 0; u < 16; u++) {
-          const double* q = base + (size_t)min(k + u, k1 - 1) * stride;      // (dead slots read the slice's last partial again)
-          asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(w[u]) : "v"(q));
-        }
-        asm volatile("s_waitcnt vmcnt(0)"
-                     : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]), "+v"(w[8]), "+v"(w[9]),
-                       "+v"(w[10]), "+v"(w[11]), "+v"(w[12]), "+v"(w[13]), "+v"(w[14]), "+v"(w[15]));
+        for (int u = 0; u < 16; u++) q[u] = base + (size_t)min(k + u, k1 - 1) * stride;      // (dead slots read the slice's last partial again)
+        v2d_t w[16];
+        asm volatile(
+            "global_load_dwordx4 %0, %16, off sc1\n\tglobal_load_dwordx4 %1, %17, off sc1\n\t"
+            "global_load_dwordx4 %2, %18, off sc1\n\tglobal_load_dwordx4 %3, %19, off sc1\n\t"
+            "global_load_dwordx4 %4, %20, off sc1\n\tglobal_load_dwordx4 %5, %21, off sc1\n\t"
+            "global_load_dwordx4 %6, %22, off sc1\n\tglobal_load_dwordx4 %7, %23, off sc1\n\t"
+            "global_load_dwordx4 %8, %24, off sc1\n\tglobal_load_dwordx4 %9, %25, off sc1\n\t"
+            "global_load_dwordx4 %10, %26, off sc1\n\tglobal_load_dwordx4 %11, %27, off sc1\n\t"
+            "global_load_dwordx4 %12, %28, off sc1\n\tglobal_load_dwordx4 %13, %29, off sc1\n\t"
+            "global_load_dwordx4 %14, %30, off sc1\n\tglobal_load_dwordx4 %15, %31, off sc1\n\t"
+            "s_waitcnt vmcnt(0)"
+            : "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3]), "=&v"(w[4]), "=&v"(w[5]), "=&v"(w[6]), "=&v"(w[7]), "=&v"(w[8]),
+              "=&v"(w[9]), "=&v"(w[10]), "=&v"(w[11]), "=&v"(w[12]), "=&v"(w[13]), "=&v"(w[14]), "=&v"(w[15])
+            : "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[3]), "v"(q[4]), "v"(q[5]), "v"(q[6]), "v"(q[7]), "v"(q[8]), "v"(q[9]), "v"(q[10]),
+              "v"(q[11]), "v"(q[12]), "v"(q[13]), "v"(q[14]), "v"(q[15])
+            : "memory");
 #pragma unroll
         for (int u = 0; u < 16; u += 2) {
           if (k + u < k1) a0 += w[u];
           if (k + u + 1 < k1) a1 += w[u + 1];
         }
       }
+    }
+    asm volatile("" : "+v"(launch_ticket));                    // (keeps the comparison below behind the gather's statement)
+    const bool launch_last = launch_ticket == (unsigned int)FIT_GROUPS - 1u;
+    int n_wl = 0;
+    unsigned int n_tie = 0u;
+    if (launch_last) {
+      n_wl = __hip_atomic_load(wl_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tl.count) n_tie = __hip_atomic_load(tl.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();                                               // sa0 .. sa2 are free (every thread read its block sums above)
     if (sl < 5) {
@@ -2041,25 +2122,10 @@ __device__ __forceinline__ void fit_reduce_publish(const float (&v)[16], bool ow
       double2* o = out_granules + (size_t)group * FIT_LIVE_PAD + threadIdx.x;
       asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(o), "v"(g) : "memory");
     }
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(ticket + group, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next pass
-      if (launch_last) {
-        // the launch's two counters, published in slot 0 whichever group this is (the host waits for these two granules first):
-        // granule FIT_LIVE = queries of this pass that needed more than their 3x3x3 block, granule FIT_LIVE + 1 = queries whose five
-        // hinge on an exact distance tie (the host then runs tie_kernel and the fit again).  Then everything is re-armed.
-        v2d_t g;
-        g.x = (double)__hip_atomic_load(wl_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        g.y = __longlong_as_double((long long)seq);
-        double2* o = out_granules + FIT_LIVE;
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(o), "v"(g) : "memory");
-        g.x = tl.count ? (double)__hip_atomic_load(tl.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-        o = out_granules + FIT_LIVE + 1;
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(o), "v"(g) : "memory");
-        __hip_atomic_store(ticket + FIT_GROUPS, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(wl_count, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tl.count_next) __hip_atomic_store(tl.count_next, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    if (threadIdx.x == 0) __hip_atomic_store(ticket + group, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next pass
+    asm volatile("" : "+v"(n_wl), "+v"(n_tie));              // (the loaded values are first looked at here, behind the barriers)
+    if (launch_last) publish_counters(n_wl, n_tie, out_granules, ticket, wl_count, seq, tl);      // (its wave publishes no sum: nobody waits behind these loads)
+    if (launch_last) TRACE_LANE(1, 2, 255);                    // (developer stamp: the counters' granules stored and acknowledged)
     TRACE(1, 7);
   }
 }
@@ -2865,15 +2931,17 @@ static void launch_knn5_L(hipStream_t st, const GridView& G, const float4* scan_
                           int max_ring, void* nbr, int* wl, int* wl_count, unsigned long long* cand, const PrevPass& prev,
                           int tail, hipEvent_t e0, hipEvent_t e1, const FuseArgs* fuse, const TieList* tlp, int after_fine = 0,
                           unsigned long long seq = 0ull, const DeskewArgs* dk = nullptr, const ChainHead* chain = nullptr,
-                          unsigned int wait_epoch = 0u, unsigned int end_code = 0u) {
+                          unsigned int wait_epoch = 0u, unsigned int end_code = 0u, const PipeHead* pipe = nullptr) {
   const int qpb = 256 / L;
+  PrevRT prt;                                                  // (a pass queued ahead of its pose: its bound's reference pose is known now)
+  for (int i = 0; i < 16; i++) prt.v[i] = prev.RT[i];
   const int blocks = round_up8((n + qpb - 1) / qpb);
   constexpr int slots = 8;          // candidate loads in flight per lane
   if constexpr (L == 2) {
     if (fuse) {      // the whole pass in one launch (blocks is a multiple of 8 = FIT_GROUPS; a chained pass has one workgroup more)
       const int grid = fused_blocks(n) + (fuse->ch.S ? 1 : 0);
-      if (chain)
-        hipExtLaunchKernelGGL((knn5_chain_kernel<2, 8, true>), dim3(grid), dim3(256), 0, st, e0, e1, 0, G, scan_sorted, n, chain, max_ring, (NbrRec*)nbr, wl, wl_count, cand, prev.valid, prev.probe_min, 1, *fuse, wait_epoch);
+      if (chain || pipe)
+        hipExtLaunchKernelGGL((knn5_chain_kernel<2, 8, true>), dim3(grid), dim3(256), 0, st, e0, e1, 0, G, scan_sorted, n, chain, max_ring, (NbrRec*)nbr, wl, wl_count, cand, prev.valid, prev.probe_min, 1, *fuse, wait_epoch, pipe, prt);
       else
       hipExtLaunchKernelGGL((knn5_kernel<2, 8, true>), dim3(grid), dim3(256), 0, st, e0, e1, 0, G, scan_sorted, n, P, max_ring, (NbrRec*)nbr, wl, wl_count, cand, prev, 1, *fuse);
       return;
@@ -2888,8 +2956,8 @@ static void launch_knn5_L(hipStream_t st, const GridView& G, const float4* scan_
   // e0 / e1 (optional) are attached to the dispatch itself: they read the kernel's own begin / end
   // timestamps, without the extra barrier packets of hipEventRecord
   if constexpr (L == 2) {
-    if (chain) {
-      hipExtLaunchKernelGGL((knn5_chain_kernel<2, 8, false>), dim3(blocks), dim3(256), 0, st, e0, e1, 0, G, scan_sorted, n, chain, max_ring, (NbrRec*)nbr, wl, wl_count, cand, prev.valid, prev.probe_min, tail, nofuse, wait_epoch);
+    if (chain || pipe) {
+      hipExtLaunchKernelGGL((knn5_chain_kernel<2, 8, false>), dim3(blocks), dim3(256), 0, st, e0, e1, 0, G, scan_sorted, n, chain, max_ring, (NbrRec*)nbr, wl, wl_count, cand, prev.valid, prev.probe_min, tail, nofuse, wait_epoch, pipe, prt);
       return;
     }
   }
@@ -2899,10 +2967,10 @@ static void launch_knn5_L(hipStream_t st, const GridView& G, const float4* scan_
 void launch_knn5(hipStream_t st, int lanes_per_query, const GridView& G, const float4* scan_sorted, int n,
                  const PoseMats& P, int max_ring, void* nbr, int* wl, int* wl_count, unsigned long long* cand,
                  const PrevPass& prev, int tail, hipEvent_t e0, hipEvent_t e1, const FuseArgs* fuse, const TieList* tlp, int after_fine,
-                 unsigned long long seq, const DeskewArgs* dk, const ChainHead* chain, unsigned int wait_epoch, unsigned int end_code) {
+                 unsigned long long seq, const DeskewArgs* dk, const ChainHead* chain) {
   if (n <= 0) return;
   if (max_ring < 2 || max_ring > TAIL_MAX_RING) tail = 0;
-  if (chain) { launch_knn5_L<2>(st, G, scan_sorted, n, P, max_ring, nbr, wl, wl_count, cand, prev, tail, e0, e1, fuse, tlp, after_fine, seq, dk, chain, wait_epoch, end_code); return; }   // (two lanes per query only)
+  if (chain) { launch_knn5_L<2>(st, G, scan_sorted, n, P, max_ring, nbr, wl, wl_count, cand, prev, tail, e0, e1, fuse, tlp, after_fine, seq, dk, chain); return; }   // (two lanes per query only)
   // (two lanes per query: the other lane counts of rounds 1-4 were A/B variants nothing selected)
   (void)lanes_per_query;
   launch_knn5_L<2>(st, G, scan_sorted, n, P, max_ring, nbr, wl, wl_count, cand, prev, tail, e0, e1, fuse, tlp, after_fine, seq, dk);
@@ -2965,11 +3033,9 @@ int fused_blocks(int n) { return round_up8((int)((((long long)n << fused_spread(
 // fine pre-pass over the second-level grid (crowded regions): settles the queries whose five are proven inside their fine 3x3x3
 // block; their records get flag 4, which the main launch of the same pass (fine_mode 1) takes over
 void launch_knn5_fine(hipStream_t st, const GridView& Gf, const float4* scan_sorted, int n, const PoseMats& P, void* nbr,
-                      const PrevPass& prev, const int qlo[3], const int qhi[3], const TieList* tlp, unsigned long long seq, const ChainHead* chain,
-                      unsigned int wait_epoch, unsigned int end_code) {
+                      const PrevPass& prev, const int qlo[3], const int qhi[3], const TieList* tlp, unsigned long long seq, const ChainHead* chain) {
   if (n <= 0) return;
   FuseArgs fa{};
-  fa.ch.end_code = end_code;
   fa.fine_mode = 2;
   fa.seq = seq;
   for (int a = 0; a < 3; a++) { fa.qlo[a] = qlo[a]; fa.qhi[a] = qhi[a]; }
@@ -2977,7 +3043,7 @@ void launch_knn5_fine(hipStream_t st, const GridView& Gf, const float4* scan_sor
   PrevPass pv = prev;
   if (chain) {
     hipLaunchKernelGGL((knn5_chain_kernel<2, 8, false, true>), dim3(round_up8((n + 127) / 128)), dim3(256), 0, st, Gf, scan_sorted, n, chain, 1,
-                       (NbrRec*)nbr, (int*)nullptr, (int*)nullptr, (unsigned long long*)nullptr, pv.valid, pv.probe_min, 0, fa, wait_epoch);
+                       (NbrRec*)nbr, (int*)nullptr, (int*)nullptr, (unsigned long long*)nullptr, pv.valid, pv.probe_min, 0, fa, 0u, (const PipeHead*)nullptr, PrevRT{});
     return;
   }
   hipLaunchKernelGGL((knn5_kernel<2, 8, false, true>), dim3(round_up8((n + 127) / 128)), dim3(256), 0, st, Gf, scan_sorted, n, P, 1,
@@ -2987,8 +3053,9 @@ void launch_match_fused(hipStream_t st, const GridView& G, const float4* scan_so
                         void* nbr, int* wl, int* wl_count, unsigned long long* cand, const PrevPass& prev,
                         const unsigned char* live_idx, double* partials, void* out_granules, unsigned int* ticket,
                         unsigned long long seq, hipEvent_t e0, hipEvent_t e1, const TieList* tlp, int after_fine, const DeskewArgs* dk,
-                        const ChainHead* chain, const ChainCtl* ctl, const BookView* bookp, unsigned int wait_epoch) {
+                        const ChainHead* chain, const ChainCtl* ctl, const BookView* bookp, unsigned int wait_epoch, const PipeHead* pipe) {
   if (n <= 0) return;
+  if ((pipe != nullptr) != (wait_epoch != 0u)) return;      // (a wait needs the head it waits on: the caller's hipGetLastError finds no launch)
   FuseArgs fa{};
   if (ctl) fa.ch = *ctl;
   if (bookp) fa.book = *bookp;
@@ -3000,7 +3067,7 @@ void launch_match_fused(hipStream_t st, const GridView& G, const float4* scan_so
   for (int i = 0; i < FIT_LIVE_PAD; i++) fa.idx.raw[i] = i < FIT_LIVE ? live_idx[i] : 0;
   fa.partials = partials; fa.granules = (double2*)out_granules; fa.ticket = ticket; fa.seq = seq;
   fa.spread = fused_spread(n);
-  launch_knn5_L<2>(st, G, scan_sorted, n, P, mp.max_ring, nbr, wl, wl_count, cand, prev, 1, e0, e1, &fa, nullptr, 0, 0ull, nullptr, chain, wait_epoch, fa.ch.end_code);
+  launch_knn5_L<2>(st, G, scan_sorted, n, P, mp.max_ring, nbr, wl, wl_count, cand, prev, 1, e0, e1, &fa, nullptr, 0, 0ull, nullptr, chain, wait_epoch, fa.ch.end_code, pipe);
 }
 
 size_t nbr_rec_size() { return sizeof(NbrRec); }

@@ -77,6 +77,9 @@ int flimo_map_index_bytes(const flimo_ctx* ctx, uint64_t out[6]);
  * whose waiting launch was found too old to publish to (told to leave, launched the usual way), passes whose launch had left as a
  * whole before the publish reached it (launched again)} */
 int flimo_pass_pipeline_stats(const flimo_ctx* ctx, unsigned long long out[4]);
+/* the hardware's side of the pipelined host loop: *large_bar = 1 when the device maps the whole of its memory for the host
+ * (hipDeviceAttributeIsLargeBar), whatever a context then made of it -- a context on such a device queues passes ahead */
+int flimo_device_large_bar(int device, int* large_bar);
 
 /* ---- host-side evaluation, no GPU (round 6: out of the boundary header): what the host C++ mirror's Plane / calculate_H objects and
  * the CPU tests call ----
