@@ -41,6 +41,7 @@ class Frame(C.Structure):
 
 
 CHAIN_MAX_PASSES = 12
+RADIUS_SORTED = 1      # FLIMO_RADIUS_SORTED
 
 
 class FilterCfg(C.Structure):
@@ -76,7 +77,7 @@ FRAME_DTYPE = np.dtype([
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
     "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
+    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
@@ -121,6 +122,9 @@ def load_hip():
     L.flimo_map_last_time.argtypes = [vp]
     L.flimo_map_points.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.flimo_knn.argtypes = [vp, f32p, C.c_size_t, C.c_int, i32p, f32p, i32p]
+    L.flimo_radius_search.argtypes = [vp, f32p, C.c_size_t, C.c_float, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.POINTER(C.c_uint64)]
+    L.flimo_radius_candidates.argtypes = [vp, f32p, C.c_size_t, C.c_float, C.c_void_p]
     L.flimo_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.flimo_scan_size.restype = C.c_size_t
     L.flimo_scan_size.argtypes = [vp]
@@ -264,6 +268,39 @@ class HipCtx:
         cnt = np.empty((nq,), np.int32)
         self._chk(self._L.flimo_knn(self._h, q.reshape(-1), nq, k, idx.reshape(-1), sqd.reshape(-1), cnt))
         return idx, sqd, cnt
+
+    def radius_count(self, q, radius):
+        """Results per query of ``radius_search`` (count only: nothing but the offsets comes back)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        off = np.zeros(q.shape[0] + 1, np.uint64)
+        self._chk(self._L.flimo_radius_search(self._h, q.reshape(-1), q.shape[0], float(radius), 0, off.ctypes.data, None, None, None, 0, None))
+        return np.diff(off).astype(np.int64)
+
+    def radius_candidates(self, q, radius):
+        """Stored points each query's walk loads and tests at this radius (flimo_radius_candidates, include/flimo_dev.h)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        cand = np.zeros(q.shape[0], np.uint64)
+        self._chk(self._L.flimo_radius_candidates(self._h, q.reshape(-1), q.shape[0], float(radius), cand.ctypes.data))
+        return cand
+
+    def radius_search(self, q, radius, sorted=False, want_xyz=False):
+        """flimo_radius_search (Octree::radiusSearch for a batch): the stored points with squared float32 distance < radius * radius.
+        Returns (offsets [nq + 1], idx, sqd[, xyz]) in CSR form; idx = insertion indices (rows of ``map_points()``).  Unsorted: an
+        order that only a change of the map changes; ``sorted``: ascending by (distance bits, index)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        nq = q.shape[0]
+        off = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        # count, then size the arrays, then fill
+        self._chk(self._L.flimo_radius_search(self._h, q.reshape(-1), nq, float(radius), 0, off.ctypes.data, None, None, None, 0, C.byref(total)))
+        n = int(total.value)
+        idx = np.empty(n, np.int32)
+        sqd = np.empty(n, np.float32)
+        xyz = np.empty((n, 3), np.float32) if want_xyz else None
+        if n > 0:
+            self._chk(self._L.flimo_radius_search(self._h, q.reshape(-1), nq, float(radius), RADIUS_SORTED if sorted else 0, off.ctypes.data,
+                                                  idx.ctypes.data, sqd.ctypes.data, xyz.ctypes.data if want_xyz else None, n, C.byref(total)))
+        return (off, idx, sqd, xyz) if want_xyz else (off, idx, sqd)
 
     # ---- scan ----
     def scan_set(self, xyz):

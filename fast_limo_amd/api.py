@@ -41,7 +41,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_last_sweep_tied", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_map_radius_search", "flimo_loc_last_sweep_tied", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -133,6 +133,8 @@ def load_host():
     L.flimo_loc_set_exact_tied_order.argtypes = [vp, C.c_int]
     L.flimo_loc_set_local_map.restype = None
     L.flimo_loc_set_local_map.argtypes = [vp, f32p, C.c_float]
+    L.flimo_loc_map_radius_search.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.POINTER(C.c_uint64)]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -313,6 +315,28 @@ class Localizer:
         maximum) from the box centre, the map is cropped to position +- ``half_extent``.  A non-positive or non-finite extent
         switches it off."""
         self._L.flimo_loc_set_local_map(self._h, np.ascontiguousarray(half_extent, dtype=np.float32).reshape(3), float(recentre_dist))
+
+    def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
+        """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,
+        as ``HipCtx.radius_search``.  Waits for an insert or a crop still running behind the last sweep; changes nothing."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        nq = q.shape[0]
+        off = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        fn = self._L.flimo_loc_map_radius_search
+        rc = fn(self._h, q.ctypes.data, nq, float(radius), 0, off.ctypes.data, None, None, None, 0, C.byref(total))
+        if rc != 0:
+            raise FlimoError(f"flimo_loc_map_radius_search failed ({rc})")
+        n = int(total.value)
+        idx = np.empty(n, np.int32)
+        sqd = np.empty(n, np.float32)
+        xyz = np.empty((n, 3), np.float32) if want_xyz else None
+        if n > 0:
+            rc = fn(self._h, q.ctypes.data, nq, float(radius), 1 if sorted else 0, off.ctypes.data, idx.ctypes.data, sqd.ctypes.data,
+                    xyz.ctypes.data if want_xyz else None, n, C.byref(total))
+            if rc != 0:
+                raise FlimoError(f"flimo_loc_map_radius_search failed ({rc})")
+        return (off, idx, sqd, xyz) if want_xyz else (off, idx, sqd)
 
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))

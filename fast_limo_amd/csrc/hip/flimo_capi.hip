@@ -1163,6 +1163,100 @@ extern "C" int flimo_knn(flimo_ctx* c, const float* q, size_t nq, int k, int32_t
   return FLIMO_OK;
 }
 
+// ---- radius search (Octree::radiusSearch, Objects/Octree.hpp:453-523) ---------------------------
+// kernels and the meaning of the call: flimo_radius.hip.  count -> 64-bit exclusive sum -> offsets to the host (total, the cap
+// decision) -> result scratch -> fill (the same walk) -> sorted: segmented sort of (distance bits, insertion index) keys -> copies
+// back; one wait at the end of each half.
+extern "C" int flimo_radius_search(flimo_ctx* c, const float* q, size_t nq, float radius, unsigned flags, uint64_t* offsets,
+                                   int32_t* idx, float* sqd, float* xyz, size_t cap, uint64_t* total) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!offsets || (nq > 0 && !q)) return fail(c, FLIMO_ERR_INVALID, "radius search: null queries / offsets");
+  if (!(radius >= 0.f) || std::isinf(radius)) return fail(c, FLIMO_ERR_INVALID, "radius search: the radius must be finite and >= 0");
+  if (flags & ~FLIMO_RADIUS_SORTED) return fail(c, FLIMO_ERR_INVALID, "radius search: unknown flag bits 0x%x", flags & ~FLIMO_RADIUS_SORTED);
+  if (nq > 0x7fff0000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "radius search: too many queries");
+  if (total) *total = 0;
+  offsets[0] = 0;
+  if (nq == 0) return FLIMO_OK;
+  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  if (!c->grid_valid) {                       // Octree::radiusSearch with root_ == nullptr returns nothing (Octree.hpp:459)
+    for (size_t i = 0; i <= nq; i++) offsets[i] = 0;
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  // scratch of this call, released on every exit path
+  struct Scratch {
+    float* q = nullptr; uint32_t* cnt = nullptr; unsigned long long* off = nullptr; void* tmp = nullptr;
+    int32_t* idx = nullptr; float* sqd = nullptr; float* xyz = nullptr; unsigned long long *keys = nullptr, *keys2 = nullptr;
+    ~Scratch() {
+      (void)hipFree(q); (void)hipFree(cnt); (void)hipFree(off); (void)hipFree(tmp); (void)hipFree(idx); (void)hipFree(sqd); (void)hipFree(xyz);
+      (void)hipFree(keys); (void)hipFree(keys2);
+    }
+  } d;
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "offsets are copied as they are");
+  HIPCHK(c, hipMalloc(&d.q, nq * 3 * sizeof(float)));
+  HIPCHK(c, hipMalloc(&d.cnt, (nq + 1) * sizeof(uint32_t)));
+  HIPCHK(c, hipMalloc(&d.off, (nq + 1) * sizeof(unsigned long long)));
+  size_t scan_bytes = 0;
+  HIPCHK(c, radius_offsets(c->stream, nullptr, scan_bytes, d.cnt, d.off, nq));
+  HIPCHK(c, hipMalloc(&d.tmp, scan_bytes + 16));
+  HIPCHK(c, hipMemcpyAsync(d.q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(d.cnt + nq, 0, sizeof(uint32_t), c->stream));
+  HIPCHK(c, launch_radius_count(c->stream, c->grid, d.q, (int)nq, radius, d.cnt, nullptr));
+  HIPCHK(c, radius_offsets(c->stream, d.tmp, scan_bytes, d.cnt, d.off, nq));
+  HIPCHK(c, hipMemcpyAsync(offsets, d.off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t n = offsets[nq];
+  if (total) *total = n;
+  if (!idx && !sqd && !xyz) return FLIMO_OK;      // count only
+  if (n > 0x7fffffffull) return fail(c, FLIMO_ERR_TOO_LARGE, "radius search: %llu results (the limit is 2^31 - 1)", (unsigned long long)n);
+  if (n > cap) return fail(c, FLIMO_ERR_TOO_LARGE, "radius search: %llu results, room for %zu", (unsigned long long)n, cap);
+  if (n == 0) return FLIMO_OK;
+  if (idx) HIPCHK(c, hipMalloc(&d.idx, n * sizeof(int32_t)));
+  if (sqd) HIPCHK(c, hipMalloc(&d.sqd, n * sizeof(float)));
+  if (xyz) HIPCHK(c, hipMalloc(&d.xyz, n * 3 * sizeof(float)));
+  if (flags & FLIMO_RADIUS_SORTED) {
+    HIPCHK(c, hipMalloc(&d.keys, n * sizeof(unsigned long long)));
+    HIPCHK(c, hipMalloc(&d.keys2, n * sizeof(unsigned long long)));
+    size_t sort_bytes = 0;
+    HIPCHK(c, radius_sort_segments(c->stream, nullptr, sort_bytes, d.keys, d.keys2, (size_t)n, nq, d.off));
+    (void)hipFree(d.tmp); d.tmp = nullptr;
+    HIPCHK(c, hipMalloc(&d.tmp, sort_bytes + 16));
+    HIPCHK(c, launch_radius_fill(c->stream, c->grid, d.q, (int)nq, radius, d.off, nullptr, nullptr, nullptr, d.keys));
+    HIPCHK(c, radius_sort_segments(c->stream, d.tmp, sort_bytes, d.keys, d.keys2, (size_t)n, nq, d.off));
+    HIPCHK(c, launch_radius_unpack(c->stream, d.keys2, (size_t)n, c->d_map_raw, d.idx, d.sqd, d.xyz));
+  } else {
+    HIPCHK(c, launch_radius_fill(c->stream, c->grid, d.q, (int)nq, radius, d.off, d.idx, d.sqd, d.xyz, nullptr));
+  }
+  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d.idx, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (sqd) HIPCHK(c, hipMemcpyAsync(sqd, d.sqd, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, d.xyz, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return FLIMO_OK;
+}
+
+extern "C" int flimo_radius_candidates(flimo_ctx* c, const float* q, size_t nq, float radius, uint64_t* cand) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (nq > 0 && (!q || !cand)) return fail(c, FLIMO_ERR_INVALID, "radius candidates: null queries / output");
+  if (!(radius >= 0.f) || std::isinf(radius)) return fail(c, FLIMO_ERR_INVALID, "radius candidates: the radius must be finite and >= 0");
+  if (nq > 0x7fff0000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "radius candidates: too many queries");
+  if (nq == 0) return FLIMO_OK;
+  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  if (!c->grid_valid) { for (size_t i = 0; i < nq; i++) cand[i] = 0; return FLIMO_OK; }
+  ctx_enter(c);
+  struct Scratch {
+    float* q = nullptr; uint32_t* cnt = nullptr; unsigned long long* cand = nullptr;
+    ~Scratch() { (void)hipFree(q); (void)hipFree(cnt); (void)hipFree(cand); }
+  } d;
+  HIPCHK(c, hipMalloc(&d.q, nq * 3 * sizeof(float)));
+  HIPCHK(c, hipMalloc(&d.cnt, nq * sizeof(uint32_t)));
+  HIPCHK(c, hipMalloc(&d.cand, nq * sizeof(unsigned long long)));
+  HIPCHK(c, hipMemcpyAsync(d.q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_radius_count(c->stream, c->grid, d.q, (int)nq, radius, d.cnt, d.cand));
+  HIPCHK(c, hipMemcpyAsync(cand, d.cand, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return FLIMO_OK;
+}
+
 // ---- scan -------------------------------------------------------------------------------------
 // the Morton-ordered raw sweep (deskew's input) has a capacity of its own: flimo_scan_adopt exchanges it between two contexts
 static int ensure_raw_sorted(flimo_ctx* c, size_t n) {

@@ -233,4 +233,22 @@ hipError_t voxel_grid(hipStream_t st, const float4* in, size_t n, float leaf, fl
                       MapBuildScratch& S);
 void map_scratch_free(MapBuildScratch& S);
 
+// flimo_radius.hip -- Octree::radiusSearch (Octree.hpp:453-523): the stored points with sqdist3(q, p) < radius * radius, per query.
+// Count and fill are ONE walk (same rows, same candidates, same order); lanes per query and the kind of walk (rows of the ball's
+// box, or the directory's tiles for a box of many rows) follow from the radius and the grid alone (radius_plan).
+void radius_plan(const GridView& G, float radius, int& lanes, bool& tiles);
+// cnt[q] = results of query q; cand (optional): candidates examined per query
+hipError_t launch_radius_count(hipStream_t st, const GridView& G, const float* q, int nq, float radius, uint32_t* cnt, unsigned long long* cand);
+// offsets[0 .. nq] = exclusive sum of cnt[0 .. nq] (cnt[nq] = 0 set by the caller); tmp == nullptr: tmp_bytes only
+hipError_t radius_offsets(hipStream_t st, void* tmp, size_t& tmp_bytes, uint32_t* cnt, unsigned long long* offsets, size_t nq);
+// results of query q at offsets[q] ..: insertion index, squared distance, xyz (each optional), or -- keys non-null -- the 64-bit
+// keys (distance bits << 32 | insertion index) of the sorted form
+hipError_t launch_radius_fill(hipStream_t st, const GridView& G, const float* q, int nq, float radius, const unsigned long long* offsets,
+                              int32_t* idx, float* sqd, float* xyz, unsigned long long* keys);
+// every segment of the keys ascending (tmp == nullptr: tmp_bytes only), and the keys taken apart (xyz gathered from the map in
+// insertion order)
+hipError_t radius_sort_segments(hipStream_t st, void* tmp, size_t& tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+                                size_t total, size_t nq, const unsigned long long* offsets);
+hipError_t launch_radius_unpack(hipStream_t st, const unsigned long long* keys, size_t n, const float4* map_raw, int32_t* idx, float* sqd, float* xyz);
+
 }  // namespace flimo

@@ -215,6 +215,18 @@ int flimo_local_map_rule(const double p[3], const float half_extent[3], float re
                          float lo[3], float hi[3]) {
   return fast_limo::Localizer::local_map_rule(p, half_extent, recentre_dist, centre, have_centre, lo, hi);
 }
+int flimo_loc_map_radius_search(flimo_loc* L, const float* q_xyz, size_t nq, float radius, unsigned flags, uint64_t* offsets, int32_t* idx,
+                                float* sqd, float* xyz, size_t cap, uint64_t* total) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
+  if (!c) {                          // no map yet: Octree::radiusSearch with root_ == nullptr
+    if (!offsets || (nq > 0 && !q_xyz)) return FLIMO_ERR_INVALID;
+    for (size_t i = 0; i <= nq; i++) offsets[i] = 0;
+    if (total) *total = 0;
+    return FLIMO_OK;
+  }
+  return flimo_radius_search(c, q_xyz, nq, radius, flags, offsets, idx, sqd, xyz, cap, total);
+}
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
 // the map insert that ends a scan runs on the Mapper's worker thread (Mapper::add_scan): wait for it / switch it off

@@ -382,6 +382,44 @@ bool Mapper::exists() { sync(); return ctx_ && flimo_map_size(ctx_) > 0; }
 int Mapper::size() { sync(); return ctx_ ? (int)flimo_map_size(ctx_) : 0; }
 double Mapper::last_time() { sync(); return ctx_ ? flimo_map_last_time(ctx_) : -1.0; }
 
+// Octree::radiusSearch over the GPU map: count -> size the arrays -> fill (an insert or a crop on the worker thread ends first)
+int Mapper::radiusSearch(const float* q_xyz, size_t nq, float radius, bool sorted, std::vector<uint64_t>& offsets, std::vector<int32_t>& idx,
+                         std::vector<float>& sqd, std::vector<float>* xyz) {
+  sync();
+  offsets.assign(nq + 1, 0);
+  idx.clear(); sqd.clear();
+  if (xyz) xyz->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  uint64_t total = 0;
+  int rc = flimo_radius_search(ctx_, q_xyz, nq, radius, 0u, offsets.data(), nullptr, nullptr, nullptr, 0, &total);
+  if (rc != FLIMO_OK || total == 0) return rc;
+  idx.resize(total); sqd.resize(total);
+  if (xyz) xyz->resize(3 * total);
+  return flimo_radius_search(ctx_, q_xyz, nq, radius, sorted ? FLIMO_RADIUS_SORTED : 0u, offsets.data(), idx.data(), sqd.data(),
+                             xyz ? xyz->data() : nullptr, (size_t)total, &total);
+}
+void Mapper::radiusSearch(const PointType& query, float radius, std::vector<PointType>& neighbors, std::vector<float>& distances) {
+  if (!exists()) return;                       // Octree.hpp:459: root_ == nullptr leaves the outputs as they are
+  neighbors.clear();                           // Octree.hpp:461-462
+  distances.clear();
+  const float q[3] = {query.x, query.y, query.z};
+  std::vector<uint64_t> off;
+  std::vector<int32_t> idx;
+  std::vector<float> xyz;
+  const int rc = radiusSearch(q, 1, radius, true, off, idx, distances, &xyz);
+  if (rc != FLIMO_OK) {
+    std::cout << "FAST_LIMO::Mapper::radiusSearch failed: " << flimo_last_error(ctx_) << "\n";
+    distances.clear();
+    return;
+  }
+  neighbors.resize(distances.size());
+  for (size_t i = 0; i < distances.size(); i++) {      // (only the coordinates: Octree.hpp:470-474)
+    PointType p{};
+    p.x = xyz[3 * i]; p.y = xyz[3 * i + 1]; p.z = xyz[3 * i + 2];
+    neighbors[i] = p;
+  }
+}
+
 void Mapper::add(pcl::PointCloud<PointType>::Ptr& pc, double time) {   // Mapper.cpp:88-96
   if (!pc || pc->points.size() < 1) return;
   sync();

@@ -8,6 +8,8 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+#include <vector>
+#include <cstdint>
 #include "fast_limo/Common.hpp"
 #include "fast_limo/Objects/Match.hpp"
 #include "fast_limo/Objects/State.hpp"
@@ -52,6 +54,15 @@ class fast_limo::Mapper {
   // asked for it does not wait.  sync() waits for it like for an insert.
   void crop_box(const float lo[3], const float hi[3]);
   size_t last_crop_removed() { sync(); return crop_removed_; }   // points the last crop_box removed
+  // octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the GPU map (flimo_radius_search).  The reference's Mapper hides
+  // its octree, so this is an addition: the stored points with (p - query).squaredNorm() < radius * radius (strict, float32), in
+  // ascending order of (distance, insertion index) -- the reference's traversal order is not reproduced.  As the template
+  // (Octree.hpp:453-477): outputs untouched when the map is empty, cleared otherwise; only x, y, z of a neighbour are set.
+  void radiusSearch(const PointType& query, float radius, std::vector<PointType>& neighbors, std::vector<float>& distances);
+  // ... for a batch of packed xyz queries, CSR form: results of query i are [offsets[i], offsets[i + 1]) of idx (insertion
+  // indices) / sqd / xyz (optional, packed).  sorted = false: an order only a change of the map changes.  Returns a FLIMO_* code.
+  int radiusSearch(const float* q_xyz, size_t nq, float radius, bool sorted, std::vector<uint64_t>& offsets, std::vector<int32_t>& idx,
+                   std::vector<float>& sqd, std::vector<float>* xyz = nullptr);
   void sync();                                  // wait for a running insert or crop (no-op when idle)
   void set_async(bool on) { sync(); async_ = on; }
   double last_insert_seconds() { sync(); return insert_seconds_; }

@@ -108,6 +108,30 @@ int flimo_map_points(flimo_ctx* ctx, float* xyz_out, size_t cap, size_t* n);
  * empty space in between. */
 int flimo_knn(flimo_ctx* ctx, const float* q_xyz, size_t nq, int k, int32_t* idx, float* sqd, int32_t* cnt);
 
+/* ---- exact radius search: replaces octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) for a batch ----
+ * For every query q the call returns exactly the stored points p with
+ *     sqdist3(q, p) < radius * radius     (strict; all float32: dx*dx + (dy*dy + dz*dz) uncontracted, the reference's
+ *                                          (p - query).squaredNorm(); radius * radius one float32 product, Octree.hpp:467)
+ * each with its insertion index (what flimo_knn returns, what flimo_map_points is ordered by), that squared distance and,
+ * optionally, its xyz.
+ *  - The reference takes every point of an octant whose farthest corner lies inside the ball without testing the point
+ *    (Octree.hpp:485-503).  In exact arithmetic that is the same set; in float32 it could differ by a rounding.  A restatement of
+ *    that traversal (tests/radius_ref) agrees with the plain predicate on every query checked; the contract here is the predicate.
+ *  - The reference's order within a query is its tree's traversal order; it is not reproduced.  Default: unspecified, but the same
+ *    for two calls on an unchanged map.  FLIMO_RADIUS_SORTED: ascending by (squared-distance bits, insertion index) -- unique.
+ * Output in CSR form, host memory: the results of query i are [offsets[i], offsets[i + 1]) of idx / sqd / xyz ([..][3]);
+ * *total = offsets[nq].  offsets ([nq + 1]) is required; idx, sqd, xyz and total may each be NULL.  All three of idx, sqd, xyz
+ * NULL: count only (no fill launch, no result scratch).  cap = results the non-NULL arrays can hold: total > cap returns
+ * FLIMO_ERR_TOO_LARGE with offsets and *total valid and the arrays untouched (call again with room); so does a total above
+ * 2^31 - 1, whatever cap (a count-only call has no such limit).  FLIMO_ERR_INVALID: NULL ctx / q_xyz (nq > 0) / offsets, a
+ * radius that is NaN, infinite or negative, unknown flag bits.  radius == 0: every query is empty (nothing is < 0); a query with
+ * a NaN coordinate is empty; an empty map (Octree.hpp:459) gives all offsets 0; nq == 0 gives offsets[0] = 0.  The cost follows
+ * the points and the index tiles the ball meets, not its volume: a ball of kilometres over a sparse map skips the tiles that do
+ * not exist.  Calling rules as flimo_knn. */
+#define FLIMO_RADIUS_SORTED 1u
+int flimo_radius_search(flimo_ctx* ctx, const float* q_xyz, size_t nq, float radius, unsigned flags, uint64_t* offsets /* [nq + 1] */,
+                        int32_t* idx, float* sqd, float* xyz /* [..][3] */, size_t cap, uint64_t* total);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

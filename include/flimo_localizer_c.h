@@ -76,6 +76,11 @@ void   flimo_loc_set_local_map(flimo_loc* L, const float half_extent[3], float r
  * written), -1 when the arguments switch the policy off (nothing written). */
 int    flimo_local_map_rule(const double p[3], const float half_extent[3], float recentre_dist, double centre[3], int* have_centre,
                             float lo[3], float hi[3]);
+/* octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the Localizer's map: flimo_radius_search (include/flimo_c.h: same
+ * arguments, same results, same error codes) on the map's context, after an insert or a crop still running behind the last sweep
+ * has ended.  A Localizer that has no map yet answers like an empty one (all offsets 0). */
+int    flimo_loc_map_radius_search(flimo_loc* L, const float* q_xyz, size_t nq, float radius, unsigned flags, uint64_t* offsets,
+                                   int32_t* idx, float* sqd, float* xyz, size_t cap, uint64_t* total);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
