@@ -77,7 +77,7 @@ FRAME_DTYPE = np.dtype([
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
     "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
+    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
@@ -125,6 +125,8 @@ def load_hip():
     L.flimo_radius_search.argtypes = [vp, f32p, C.c_size_t, C.c_float, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.POINTER(C.c_uint64)]
     L.flimo_radius_candidates.argtypes = [vp, f32p, C.c_size_t, C.c_float, C.c_void_p]
+    L.flimo_knn_k.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_knn_k_candidates.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p]
     L.flimo_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.flimo_scan_size.restype = C.c_size_t
     L.flimo_scan_size.argtypes = [vp]
@@ -268,6 +270,30 @@ class HipCtx:
         cnt = np.empty((nq,), np.int32)
         self._chk(self._L.flimo_knn(self._h, q.reshape(-1), nq, k, idx.reshape(-1), sqd.reshape(-1), cnt))
         return idx, sqd, cnt
+
+    def knn_k(self, q, k, max_dist=float("inf"), want_xyz=False):
+        """flimo_knn_k (Octree::knn for any k up to 64, with a distance gate): per query the first ``k`` stored points in the order
+        (float32 squared-distance bits, insertion index) among those with squared distance < max_dist * max_dist (``inf``: no gate).
+        Returns (idx [nq, k], sqd [nq, k], cnt [nq][, xyz [nq, k, 3]]); idx = insertion indices (rows of ``map_points()``), slots
+        beyond cnt are idx -1, sqd 0, xyz 0."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        nq, kk = q.shape[0], max(int(k), 1)
+        idx = np.empty((nq, kk), np.int32)
+        sqd = np.empty((nq, kk), np.float32)
+        cnt = np.empty((nq,), np.int32)
+        xyz = np.empty((nq, kk, 3), np.float32) if want_xyz else None
+        # (an array of no element may have no address; the call wants its pointers non-null)
+        ptr = lambda a: a.ctypes.data if a.size else C.addressof(C.c_double())
+        self._chk(self._L.flimo_knn_k(self._h, q.ctypes.data if nq else None, nq, int(k), float(max_dist), ptr(idx), ptr(sqd),
+                                      ptr(xyz) if want_xyz else None, ptr(cnt)))
+        return (idx, sqd, cnt, xyz) if want_xyz else (idx, sqd, cnt)
+
+    def knn_k_candidates(self, q, k, max_dist=float("inf")):
+        """Stored points each query's search loads and tests (flimo_knn_k_candidates, include/flimo_dev.h)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        cand = np.zeros(q.shape[0], np.uint64)
+        self._chk(self._L.flimo_knn_k_candidates(self._h, q.ctypes.data, q.shape[0], int(k), float(max_dist), cand.ctypes.data))
+        return cand
 
     def radius_count(self, q, radius):
         """Results per query of ``radius_search`` (count only: nothing but the offsets comes back)."""

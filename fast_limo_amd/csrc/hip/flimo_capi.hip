@@ -1257,6 +1257,56 @@ extern "C" int flimo_radius_candidates(flimo_ctx* c, const float* q, size_t nq, 
   return FLIMO_OK;
 }
 
+// ---- k-NN for k up to FLIMO_KNN_MAX_K with a distance gate (Octree::knn, Objects/Octree.hpp:526-555) -------------
+// kernels and the meaning of the call: flimo_knn_k.hip.  One block-search launch, one launch that finishes what it could not prove
+// over the directory's tiles, the copies back, one wait.  cand (developer counter, flimo_dev.h): the result arrays may then be NULL.
+static int knn_k_run(flimo_ctx* c, const float* q, size_t nq, int k, float max_dist, int32_t* idx, float* sqd, float* xyz, int32_t* cnt,
+                     uint64_t* cand) {
+  static_assert(FLIMO_KNN_MAX_K == KNNK_MAX_K, "the header's limit is the kernels'");
+  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "knn_k: max_dist must be >= 0 or INFINITY");
+  if (k < 1 || k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "knn_k: k must be in 1..%d", FLIMO_KNN_MAX_K);
+  if ((unsigned long long)nq * (unsigned long long)k >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "knn_k: nq * k must be below 2^31");
+  if (nq == 0) return FLIMO_OK;
+  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  if (!c->grid_valid) {                       // Octree::knn with root_ == nullptr returns nothing
+    for (size_t i = 0; i < nq; i++) { if (cnt) cnt[i] = 0; if (cand) cand[i] = 0; }
+    for (size_t i = 0; i < nq * (size_t)k; i++) { if (idx) idx[i] = -1; if (sqd) sqd[i] = 0.f; }
+    if (xyz) for (size_t i = 0; i < nq * (size_t)k * 3; i++) xyz[i] = 0.f;
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  // scratch of this call, released on every exit path
+  struct Scratch {
+    float* q = nullptr; int32_t* idx = nullptr; float* sqd = nullptr; float* xyz = nullptr; int32_t* cnt = nullptr; unsigned long long* cand = nullptr;
+    ~Scratch() { (void)hipFree(q); (void)hipFree(idx); (void)hipFree(sqd); (void)hipFree(xyz); (void)hipFree(cnt); (void)hipFree(cand); }
+  } d;
+  HIPCHK(c, hipMalloc(&d.q, nq * 3 * sizeof(float)));
+  HIPCHK(c, hipMalloc(&d.idx, nq * k * sizeof(int32_t)));
+  HIPCHK(c, hipMalloc(&d.sqd, nq * k * sizeof(float)));
+  if (xyz) HIPCHK(c, hipMalloc(&d.xyz, nq * k * 3 * sizeof(float)));
+  HIPCHK(c, hipMalloc(&d.cnt, nq * sizeof(int32_t)));
+  if (cand) HIPCHK(c, hipMalloc(&d.cand, nq * sizeof(unsigned long long)));
+  HIPCHK(c, hipMemcpyAsync(d.q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_knn_k(c->stream, c->grid, c->d_map_raw, d.q, (int)nq, k, max_dist, d.idx, d.sqd, d.xyz, d.cnt, d.cand));
+  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d.idx, nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (sqd) HIPCHK(c, hipMemcpyAsync(sqd, d.sqd, nq * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, d.xyz, nq * k * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (cnt) HIPCHK(c, hipMemcpyAsync(cnt, d.cnt, nq * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (cand) HIPCHK(c, hipMemcpyAsync(cand, d.cand, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return FLIMO_OK;
+}
+extern "C" int flimo_knn_k(flimo_ctx* c, const float* q, size_t nq, int k, float max_dist, int32_t* idx, float* sqd, float* xyz, int32_t* cnt) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if ((nq > 0 && !q) || !idx || !sqd || !cnt) return fail(c, FLIMO_ERR_INVALID, "knn_k: null queries / idx / sqd / cnt");
+  return knn_k_run(c, q, nq, k, max_dist, idx, sqd, xyz, cnt, nullptr);
+}
+extern "C" int flimo_knn_k_candidates(flimo_ctx* c, const float* q, size_t nq, int k, float max_dist, uint64_t* cand) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (nq > 0 && (!q || !cand)) return fail(c, FLIMO_ERR_INVALID, "knn_k candidates: null queries / output");
+  return knn_k_run(c, q, nq, k, max_dist, nullptr, nullptr, nullptr, nullptr, cand);
+}
+
 // ---- scan -------------------------------------------------------------------------------------
 // the Morton-ordered raw sweep (deskew's input) has a capacity of its own: flimo_scan_adopt exchanges it between two contexts
 static int ensure_raw_sorted(flimo_ctx* c, size_t n) {

@@ -251,4 +251,15 @@ hipError_t radius_sort_segments(hipStream_t st, void* tmp, size_t& tmp_bytes, co
                                 size_t total, size_t nq, const unsigned long long* offsets);
 hipError_t launch_radius_unpack(hipStream_t st, const unsigned long long* keys, size_t n, const float4* map_raw, int32_t* idx, float* sqd, float* xyz);
 
+// flimo_knn_k.hip -- Octree::knn (Octree.hpp:526-555) for k up to KNNK_MAX_K with a distance gate: per query the first k stored points
+// in the order (float32 squared-distance bits, insertion index) among those with sqdist3(q, p) < max_dist * max_dist (INFINITY: no
+// gate).  The running k-best is a list distributed over the lanes that serve the query (knnk_plan lanes, chosen from k); a block
+// search near the map, then a best-first walk over the directory's tiles for what it could not prove.  idx / sqd: [nq][k], padded
+// with -1 / 0; xyz (optional): [nq][k][3], gathered from map_raw (the map in insertion order); cnt: [nq]; cand (optional): stored
+// points each query's walk loaded and tested.
+constexpr int KNNK_MAX_K = 64;
+int knnk_plan(int k);
+hipError_t launch_knn_k(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, int nq, int k, float max_dist, int32_t* idx,
+                        float* sqd, float* xyz, int32_t* cnt, unsigned long long* cand);
+
 }  // namespace flimo

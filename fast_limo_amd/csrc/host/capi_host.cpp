@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <cmath>
 #include <memory>
 #include "../../../include/flimo_localizer_c.h"
 #include "fast_limo/Modules/Localizer.hpp"
@@ -226,6 +227,20 @@ int flimo_loc_map_radius_search(flimo_loc* L, const float* q_xyz, size_t nq, flo
     return FLIMO_OK;
   }
   return flimo_radius_search(c, q_xyz, nq, radius, flags, offsets, idx, sqd, xyz, cap, total);
+}
+int flimo_loc_map_knn(flimo_loc* L, const float* q_xyz, size_t nq, int k, float max_dist, int32_t* idx, float* sqd, float* xyz, int32_t* cnt) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
+  if (!c) {                          // no map yet: Octree::knn with root_ == nullptr
+    if ((nq > 0 && !q_xyz) || !idx || !sqd || !cnt || std::isnan(max_dist) || max_dist < 0.f) return FLIMO_ERR_INVALID;
+    if (k < 1 || k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
+    if ((unsigned long long)nq * (unsigned long long)k >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
+    for (size_t i = 0; i < nq; i++) cnt[i] = 0;
+    for (size_t i = 0; i < nq * (size_t)k; i++) { idx[i] = -1; sqd[i] = 0.f; }
+    if (xyz) for (size_t i = 0; i < nq * (size_t)k * 3; i++) xyz[i] = 0.f;
+    return FLIMO_OK;
+  }
+  return flimo_knn_k(c, q_xyz, nq, k, max_dist, idx, sqd, xyz, cnt);
 }
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }

@@ -13,6 +13,7 @@
 #include <emmintrin.h>
 #endif
 #include <cstring>
+#include <cmath>
 #include <functional>
 #include <iostream>
 #include <memory>
@@ -414,6 +415,43 @@ void Mapper::radiusSearch(const PointType& query, float radius, std::vector<Poin
   }
   neighbors.resize(distances.size());
   for (size_t i = 0; i < distances.size(); i++) {      // (only the coordinates: Octree.hpp:470-474)
+    PointType p{};
+    p.x = xyz[3 * i]; p.y = xyz[3 * i + 1]; p.z = xyz[3 * i + 2];
+    neighbors[i] = p;
+  }
+}
+
+// Octree::knn over the GPU map for k up to FLIMO_KNN_MAX_K (an insert or a crop on the worker thread ends first)
+int Mapper::knn(const float* q_xyz, size_t nq, int k, float max_dist, std::vector<int32_t>& idx, std::vector<float>& sqd, std::vector<int32_t>& cnt,
+                std::vector<float>* xyz) {
+  sync();
+  idx.clear(); sqd.clear(); cnt.clear();
+  if (xyz) xyz->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (k < 1 || k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
+  idx.assign(nq * (size_t)k, -1); sqd.assign(nq * (size_t)k, 0.f); cnt.assign(nq, 0);
+  if (xyz) xyz->assign(nq * (size_t)k * 3, 0.f);
+  // (vectors of no element may hand out a null pointer, which the call rejects)
+  int32_t none_i = 0; float none_f = 0.f;
+  return flimo_knn_k(ctx_, q_xyz, nq, k, max_dist, nq ? idx.data() : &none_i, nq ? sqd.data() : &none_f, (xyz && nq) ? xyz->data() : nullptr,
+                     nq ? cnt.data() : &none_i);
+}
+void Mapper::knn(const PointType& query, int k, std::vector<PointType>& neighbors, std::vector<float>& distances) {
+  if (!exists()) return;                       // Octree.hpp:532: root_ == nullptr leaves the outputs as they are
+  neighbors.clear();                           // Octree.hpp:535-536
+  distances.clear();
+  const float q[3] = {query.x, query.y, query.z};
+  std::vector<int32_t> idx, cnt;
+  std::vector<float> sqd, xyz;
+  const int rc = knn(q, 1, k, INFINITY, idx, sqd, cnt, &xyz);
+  if (rc != FLIMO_OK) {
+    std::cout << "FAST_LIMO::Mapper::knn failed: " << flimo_last_error(ctx_) << "\n";
+    return;
+  }
+  const size_t n = (size_t)cnt[0];
+  neighbors.resize(n);
+  distances.assign(sqd.begin(), sqd.begin() + n);
+  for (size_t i = 0; i < n; i++) {             // (only the coordinates)
     PointType p{};
     p.x = xyz[3 * i]; p.y = xyz[3 * i + 1]; p.z = xyz[3 * i + 2];
     neighbors[i] = p;

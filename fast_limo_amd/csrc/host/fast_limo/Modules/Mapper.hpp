@@ -63,6 +63,15 @@ class fast_limo::Mapper {
   // indices) / sqd / xyz (optional, packed).  sorted = false: an order only a change of the map changes.  Returns a FLIMO_* code.
   int radiusSearch(const float* q_xyz, size_t nq, float radius, bool sorted, std::vector<uint64_t>& offsets, std::vector<int32_t>& idx,
                    std::vector<float>& sqd, std::vector<float>* xyz = nullptr);
+  // octree::Octree::knn (Objects/Octree.hpp:526-555) over the GPU map for any k up to FLIMO_KNN_MAX_K (flimo_knn_k): the k nearest
+  // stored points in ascending order of (distance, insertion index) -- among exactly tied distances the reference's first-met
+  // choice is not reproduced.  As the template: outputs untouched when the map is empty, cleared otherwise; only x, y, z of a
+  // neighbour are set; distances are squared.
+  void knn(const PointType& query, int k, std::vector<PointType>& neighbors, std::vector<float>& distances);
+  // ... for a batch of packed xyz queries, with a distance gate (INFINITY: none; finite: only points with squared distance
+  // < max_dist * max_dist): idx / sqd [nq][k] (-1 / 0 beyond cnt[q]), cnt [nq], xyz (optional) [nq][k][3].  Returns a FLIMO_* code.
+  int knn(const float* q_xyz, size_t nq, int k, float max_dist, std::vector<int32_t>& idx, std::vector<float>& sqd, std::vector<int32_t>& cnt,
+          std::vector<float>* xyz = nullptr);
   void sync();                                  // wait for a running insert or crop (no-op when idle)
   void set_async(bool on) { sync(); async_ = on; }
   double last_insert_seconds() { sync(); return insert_seconds_; }

@@ -132,6 +132,32 @@ int flimo_knn(flimo_ctx* ctx, const float* q_xyz, size_t nq, int k, int32_t* idx
 int flimo_radius_search(flimo_ctx* ctx, const float* q_xyz, size_t nq, float radius, unsigned flags, uint64_t* offsets /* [nq + 1] */,
                         int32_t* idx, float* sqd, float* xyz /* [..][3] */, size_t cap, uint64_t* total);
 
+/* ---- exact k-NN for any k up to FLIMO_KNN_MAX_K, with a distance gate: octree::Octree::knn (Objects/Octree.hpp:526-555), which
+ *      takes any k, and -- with a finite gate -- the max_nn form of a radius search (PCL's radiusSearch(p, r, idx, d, max_nn)) ----
+ * Order the stored points of a query by the key (float32 squared-distance bits, insertion index), ascending.  The distance is
+ * sqdist3: dx*dx + (dy*dy + dz*dz), uncontracted, float32 (distances are non-negative floats, so bit order is value order); the
+ * index is what flimo_knn, flimo_radius_search and flimo_map_points use.  That is a total order, unique, and independent of where a
+ * point lies in the map's internal arrays.
+ *  - max_dist == INFINITY: no gate.  The result is the first min(k, map size) points of that order.
+ *  - a finite max_dist >= 0 admits only points with sqd < max_dist * max_dist (strict; the square one float32 product: exactly
+ *    flimo_radius_search's predicate).  The result is then, entry for entry, the first k results of
+ *    flimo_radius_search(.., max_dist, FLIMO_RADIUS_SORTED).  max_dist == 0: every query is empty.
+ * Outputs, host memory: cnt[q] = number of results of query q; idx [nq][k], sqd [nq][k] and (optional, may be NULL) xyz [nq][k][3]
+ * hold them in that order; the slots beyond cnt[q] are idx = -1, sqd = 0, xyz = 0.  idx, sqd and cnt are required.
+ * Difference from flimo_knn: for k <= 5 sqd is bit-equal to flimo_knn's; idx may differ only where candidates tie exactly in
+ * distance -- flimo_knn keeps the reference's first-met choice among them (the registration depends on it), this call its own
+ * unique order.
+ * A query with a NaN coordinate gives cnt 0; an empty map gives all cnt 0 (Octree::knn with root_ == nullptr); nq == 0 returns
+ * FLIMO_OK.  FLIMO_ERR_INVALID: NULL ctx / q_xyz (nq > 0) / idx / sqd / cnt, max_dist NaN or negative.  FLIMO_ERR_UNSUPPORTED: k
+ * outside 1 .. FLIMO_KNN_MAX_K.  FLIMO_ERR_TOO_LARGE: nq * k >= 2^31.
+ * Calling rules as flimo_knn, and like it the call answers from anywhere at bounded cost: a few rings of cells near the map, then
+ * a best-first walk over the index's existing tiles (nearest first, until the next one is farther than the k-th best or the
+ * gate); a query kilometres from every point, or in the empty middle of a sparse map, costs a look at the tile directory and the
+ * nearest tiles.  With a finite gate the search also stops at the gate. */
+#define FLIMO_KNN_MAX_K 64
+int flimo_knn_k(flimo_ctx* ctx, const float* q_xyz, size_t nq, int k, float max_dist, int32_t* idx /* [nq][k] */,
+                float* sqd /* [nq][k] */, float* xyz /* [nq][k][3], may be NULL */, int32_t* cnt /* [nq] */);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

@@ -66,6 +66,9 @@ int flimo_map_crop_stats(const flimo_ctx* ctx, uint64_t out[2]);
 /* flimo_radius_search's walk, counted: cand[i] = stored points query i's walk loads and tests at this radius (what the count and
  * the fill launch each read, 16 bytes apiece); cand: host, [nq].  Arguments as flimo_radius_search. */
 int flimo_radius_candidates(flimo_ctx* ctx, const float* q_xyz, size_t nq, float radius, uint64_t* cand);
+/* flimo_knn_k's walk, counted: cand[i] = stored points query i's search loads and tests (16 bytes apiece), the block search and --
+ * where it ran -- the walk over the tiles together; cand: host, [nq].  Arguments as flimo_knn_k. */
+int flimo_knn_k_candidates(flimo_ctx* ctx, const float* q_xyz, size_t nq, int k, float max_dist, uint64_t* cand);
 
 /* out[0] = GPU ms of the algebra launches timed so far (timing level 1), out[1] = their number,
  * out[2] = chains run, out[3] = chains that came back before the final iteration, out[4] = chains declined */

@@ -81,6 +81,11 @@ int    flimo_local_map_rule(const double p[3], const float half_extent[3], float
  * has ended.  A Localizer that has no map yet answers like an empty one (all offsets 0). */
 int    flimo_loc_map_radius_search(flimo_loc* L, const float* q_xyz, size_t nq, float radius, unsigned flags, uint64_t* offsets,
                                    int32_t* idx, float* sqd, float* xyz, size_t cap, uint64_t* total);
+/* octree::Octree::knn (Objects/Octree.hpp:526-555) for k up to FLIMO_KNN_MAX_K with a distance gate over the Localizer's map:
+ * flimo_knn_k (include/flimo_c.h: same arguments, same results, same error codes) on the map's context, after an insert or a crop
+ * still running behind the last sweep has ended.  A Localizer that has no map yet answers like an empty one (all cnt 0). */
+int    flimo_loc_map_knn(flimo_loc* L, const float* q_xyz, size_t nq, int k, float max_dist, int32_t* idx, float* sqd, float* xyz,
+                         int32_t* cnt);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
