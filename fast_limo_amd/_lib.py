@@ -77,7 +77,7 @@ FRAME_DTYPE = np.dtype([
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
     "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
+    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
@@ -87,6 +87,24 @@ HIP_SYMBOLS = [
 ]
 
 _hip = None
+
+
+def normals_call(call, nq, k, max_dist, min_pts, viewpoint, want):
+    """The output arrays of flimo_map_normals / flimo_map_normals_range and the call's common arguments (``call`` takes them: k,
+    max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig); shared with ``api.Localizer``."""
+    unknown = set(want) - {"centroid", "cov", "eig"}
+    if unknown:
+        raise ValueError(f"normals: unknown outputs {sorted(unknown)}")
+    out = {"normal": np.empty((nq, 4), np.float32), "cnt": np.empty((nq,), np.int32)}
+    for name, w in (("centroid", 3), ("cov", 6), ("eig", 6)):
+        if name in want:
+            out[name] = np.empty((nq, w), np.float64)
+    vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float32).reshape(3)
+    # (an array of no element may have no address; the call wants its pointers non-null)
+    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(C.c_double()))
+    call(int(k), float(max_dist), int(min_pts), None if vp is None else vp.ctypes.data, ptr(out["normal"]), ptr(out["cnt"]),
+         ptr(out.get("centroid")), ptr(out.get("cov")), ptr(out.get("eig")))
+    return out
 
 
 def hip_lib_path() -> str:
@@ -127,6 +145,11 @@ def load_hip():
     L.flimo_radius_candidates.argtypes = [vp, f32p, C.c_size_t, C.c_float, C.c_void_p]
     L.flimo_knn_k.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_knn_k_candidates.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p]
+    L.flimo_map_normals.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]
+    L.flimo_map_normals_range.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+    L.flimo_set_normals_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.flimo_scan_size.restype = C.c_size_t
     L.flimo_scan_size.argtypes = [vp]
@@ -287,6 +310,26 @@ class HipCtx:
         self._chk(self._L.flimo_knn_k(self._h, q.ctypes.data if nq else None, nq, int(k), float(max_dist), ptr(idx), ptr(sqd),
                                       ptr(xyz) if want_xyz else None, ptr(cnt)))
         return (idx, sqd, cnt, xyz) if want_xyz else (idx, sqd, cnt)
+
+    def normals(self, q, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
+        """flimo_map_normals: plane normal and curvature of the neighbourhood ``knn_k(q, k, max_dist)`` of every query, computed on
+        the GPU in float64 (mean and covariance of p - q, divided by n; Jacobi eigen-decomposition).  Returns a dict: ``normal``
+        [nq, 4] float32 (nx ny nz curvature), ``cnt`` [nq], and of ``want`` ``centroid`` [nq, 3], ``cov`` [nq, 6] (xx xy xz yy yz zz),
+        ``eig`` [nq, 6] (l0 <= l1 <= l2, the float64 normal).  ``viewpoint``: the normals face it; None: the component of largest
+        magnitude is positive.  Fewer than max(3, min_pts) neighbours: NaN."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        return normals_call(lambda *a: self._chk(self._L.flimo_map_normals(self._h, q.ctypes.data if q.shape[0] else None, q.shape[0], *a)),
+                            q.shape[0], k, max_dist, min_pts, viewpoint, want)
+
+    def normals_range(self, first, n, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
+        """flimo_map_normals_range: ``normals`` of the stored points first .. first + n - 1 themselves (rows of ``map_points()``);
+        nothing is uploaded, the bits are those of ``normals(map_points()[first:first + n], ...)``."""
+        return normals_call(lambda *a: self._chk(self._L.flimo_map_normals_range(self._h, int(first), int(n), *a)),
+                            int(n), k, max_dist, min_pts, viewpoint, want)
+
+    def set_normals_chunk(self, n):
+        """Queries per launch of ``normals`` / ``normals_range`` (flimo_set_normals_chunk; 0: the default of 2^20)."""
+        self._chk(self._L.flimo_set_normals_chunk(self._h, int(n)))
 
     def knn_k_candidates(self, q, k, max_dist=float("inf")):
         """Stored points each query's search loads and tests (flimo_knn_k_candidates, include/flimo_dev.h)."""

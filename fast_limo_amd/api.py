@@ -41,7 +41,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_map_radius_search", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -136,6 +136,10 @@ def load_host():
     L.flimo_loc_map_radius_search.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.POINTER(C.c_uint64)]
     L.flimo_loc_map_knn.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_map_normals.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+    L.flimo_loc_map_normals_range.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -354,6 +358,23 @@ class Localizer:
         if rc != 0:
             raise FlimoError(f"flimo_loc_map_knn failed ({rc})")
         return (idx, sqd, cnt, xyz) if want_xyz else (idx, sqd, cnt)
+
+    def _normals_chk(self, rc):
+        if rc != 0:
+            raise FlimoError(f"flimo_loc_map_normals failed ({rc})")
+
+    def map_normals(self, q, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
+        """Plane normals, curvature and covariances of the map's k-NN neighbourhoods (flimo_loc_map_normals): the dict of
+        ``HipCtx.normals``.  Waits for an insert or a crop still running behind the last sweep; changes nothing."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        return _lib.normals_call(lambda *a: self._normals_chk(self._L.flimo_loc_map_normals(self._h, q.ctypes.data if q.shape[0] else None,
+                                                                                            q.shape[0], *a)),
+                                 q.shape[0], k, max_dist, min_pts, viewpoint, want)
+
+    def map_normals_range(self, first, n, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
+        """... of the stored points first .. first + n - 1 themselves (flimo_loc_map_normals_range), as ``HipCtx.normals_range``."""
+        return _lib.normals_call(lambda *a: self._normals_chk(self._L.flimo_loc_map_normals_range(self._h, int(first), int(n), *a)),
+                                 int(n), k, max_dist, min_pts, viewpoint, want)
 
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))

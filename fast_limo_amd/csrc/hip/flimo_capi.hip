@@ -15,6 +15,7 @@
 #include <array>
 #include <vector>
 #include <algorithm>
+#include <limits>
 #include <immintrin.h>
 #include "../../../include/flimo_c.h"
 #include "../../../include/flimo_dev.h"
@@ -52,6 +53,7 @@ struct flimo_ctx {
   uint64_t crops = 0, crop_removed = 0;   // flimo_map_crop_box: calls that removed points, points removed so far
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
+  size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
   IndexTables idx;                 // the index of the main grid (GridView, flimo_types.h): tiles, directory, escapes, xstart
   GridView grid{};
@@ -1305,6 +1307,83 @@ extern "C" int flimo_knn_k_candidates(flimo_ctx* c, const float* q, size_t nq, i
   if (!c) return FLIMO_ERR_INVALID;
   if (nq > 0 && (!q || !cand)) return fail(c, FLIMO_ERR_INVALID, "knn_k candidates: null queries / output");
   return knn_k_run(c, q, nq, k, max_dist, nullptr, nullptr, nullptr, nullptr, cand);
+}
+
+// ---- normals and covariances of k-NN neighbourhoods (PCL's NormalEstimation over the map) -------------------------
+// kernels: flimo_knn_k.hip (flimo_knn_k's search, finished in registers).  Chunks of c->normals_chunk queries: per chunk the
+// queries go up (q != NULL; the range form reads them from the map), three launches (block search, walk over the tiles, the
+// eigen-decomposition), the results come back; device scratch is the chunk's, whatever nq, and nothing of nq * k entries exists.
+static int normals_run(flimo_ctx* c, const float* q, size_t first, size_t nq, int k, float max_dist, int min_pts, const float* viewpoint,
+                       float* normal, int32_t* cnt, double* centroid, double* cov, double* eig) {
+  if (!normal || !cnt) return fail(c, FLIMO_ERR_INVALID, "map normals: null normal / cnt");
+  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "map normals: max_dist must be >= 0 or INFINITY");
+  if (viewpoint && (std::isnan(viewpoint[0]) || std::isnan(viewpoint[1]) || std::isnan(viewpoint[2])))
+    return fail(c, FLIMO_ERR_INVALID, "map normals: NaN viewpoint");
+  if (k < 1 || k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map normals: k must be in 1..%d", FLIMO_KNN_MAX_K);
+  if (nq >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map normals: the number of queries must be below 2^31");
+  if (nq == 0) return FLIMO_OK;
+  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  if (!c->grid_valid) {                       // an empty map: no neighbours anywhere
+    const float fn = std::numeric_limits<float>::quiet_NaN();
+    const double dn = std::numeric_limits<double>::quiet_NaN();
+    for (size_t i = 0; i < nq; i++) cnt[i] = 0;
+    for (size_t i = 0; i < nq * 4; i++) normal[i] = fn;
+    if (centroid) for (size_t i = 0; i < nq * 3; i++) centroid[i] = dn;
+    if (cov) for (size_t i = 0; i < nq * 6; i++) cov[i] = dn;
+    if (eig) for (size_t i = 0; i < nq * 6; i++) eig[i] = dn;
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  // scratch of this call, released on every exit path
+  struct Scratch {
+    float* q = nullptr; float4* normal = nullptr; int32_t* cnt = nullptr; double *centroid = nullptr, *cov = nullptr, *eig = nullptr;
+    double* mom = nullptr; uint2* work = nullptr; unsigned* nwork = nullptr;
+    ~Scratch() {
+      (void)hipFree(q); (void)hipFree(normal); (void)hipFree(cnt); (void)hipFree(centroid); (void)hipFree(cov); (void)hipFree(eig);
+      (void)hipFree(mom); (void)hipFree(work); (void)hipFree(nwork);
+    }
+  } d;
+  const size_t m = std::min(nq, std::max<size_t>(c->normals_chunk, 1));
+  if (q) HIPCHK(c, hipMalloc(&d.q, m * 3 * sizeof(float)));
+  HIPCHK(c, hipMalloc(&d.normal, m * sizeof(float4)));
+  HIPCHK(c, hipMalloc(&d.cnt, m * sizeof(int32_t)));
+  if (centroid) HIPCHK(c, hipMalloc(&d.centroid, m * 3 * sizeof(double)));
+  if (cov) HIPCHK(c, hipMalloc(&d.cov, m * 6 * sizeof(double)));
+  if (eig) HIPCHK(c, hipMalloc(&d.eig, m * 6 * sizeof(double)));
+  HIPCHK(c, hipMalloc(&d.mom, m * 9 * sizeof(double)));
+  HIPCHK(c, hipMalloc(&d.work, m * sizeof(uint2)));
+  HIPCHK(c, hipMalloc(&d.nwork, sizeof(unsigned)));
+  for (size_t a = 0; a < nq; a += m) {
+    const size_t n = std::min(m, nq - a);
+    if (q) HIPCHK(c, hipMemcpyAsync(d.q, q + 3 * a, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_knn_k_normals(c->stream, c->grid, c->d_map_raw, d.q, (unsigned)(first + a), (int)n, k, max_dist, min_pts, viewpoint, d.normal,
+                                   d.cnt, d.centroid, d.cov, d.eig, d.mom, d.work, d.nwork));
+    HIPCHK(c, hipMemcpyAsync(normal + 4 * a, d.normal, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt + a, d.cnt, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (centroid) HIPCHK(c, hipMemcpyAsync(centroid + 3 * a, d.centroid, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (cov) HIPCHK(c, hipMemcpyAsync(cov + 6 * a, d.cov, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (eig) HIPCHK(c, hipMemcpyAsync(eig + 6 * a, d.eig, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    // (the next chunk's upload overwrites d.q; the copies above read host memory the caller owns: one wait per chunk)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_normals(flimo_ctx* c, const float* q, size_t nq, int k, float max_dist, int min_pts, const float viewpoint[3], float* normal,
+                                 int32_t* cnt, double* centroid, double* cov, double* eig) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (nq > 0 && !q) return fail(c, FLIMO_ERR_INVALID, "map normals: null queries");
+  return normals_run(c, nq ? q : nullptr, 0, nq, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
+}
+extern "C" int flimo_map_normals_range(flimo_ctx* c, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3],
+                                       float* normal, int32_t* cnt, double* centroid, double* cov, double* eig) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (first > c->map_n || n > c->map_n - first) return fail(c, FLIMO_ERR_INVALID, "map normals: the range [%zu, %zu + %zu) ends beyond the map's %zu points", first, first, n, c->map_n);
+  return normals_run(c, nullptr, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
+}
+extern "C" int flimo_set_normals_chunk(flimo_ctx* c, size_t n) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->normals_chunk = n ? n : (size_t)1 << 20;
+  return FLIMO_OK;
 }
 
 // ---- scan -------------------------------------------------------------------------------------

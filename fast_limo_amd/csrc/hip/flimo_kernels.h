@@ -261,5 +261,13 @@ constexpr int KNNK_MAX_K = 64;
 int knnk_plan(int k);
 hipError_t launch_knn_k(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, int nq, int k, float max_dist, int32_t* idx,
                         float* sqd, float* xyz, int32_t* cnt, unsigned long long* cand);
+// The same search, every query finished on the device into the plane normal of its neighbourhood (flimo_map_normals, flimo_c.h):
+// mean and covariance of r = p - q in float64, a Jacobi eigen-decomposition, the orientation rule.  q == nullptr: query i is the
+// stored point first + i.  normal / cnt: [nq]; centroid [nq][3], cov [nq][6], eig [nq][6]: optional.  Scratch: mom ([nq][9], the
+// moments between the searches and the launch that decomposes them), work ([nq]) and nwork (one counter): the queries left to the
+// walk over the tiles.
+hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, unsigned first, int nq, int k,
+                                float max_dist, int min_pts, const float* viewpoint, float4* normal, int32_t* cnt, double* centroid, double* cov,
+                                double* eig, double* mom, uint2* work, unsigned* nwork);
 
 }  // namespace flimo

@@ -327,6 +327,337 @@ __global__ __launch_bounds__(KK_BLOCK) void knnk_far_kernel(GridView G, const fl
   }
 }
 
+// ---- the two searches once more as device functions, for kernels that end a query differently (below).  knnk_kernel and
+//      knnk_far_kernel above stay as they are: inlining these into them changes their register allocation (92 -> 100 VGPRs, five
+//      waves per SIMD -> four); the text is the same, statement for statement. ----
+// The block search of one query by the L lanes of its group (every lane of the wave calls it; a group without a query passes
+// live = false): `mine` ends as this lane's entry of the k-best list.  Returns whether the list is proven exact; if not, the tiles'
+// walk (knnk_tile_walk) has to finish the query.
+template <int L>
+__device__ __forceinline__ bool knnk_block_search(const GridView& G, bool live, float gx, float gy, float gz, int lane, int k, float r2,
+                                                  kk_u64 gate_key, kk_u64& mine, unsigned long long& cand) {
+  const int sub = lane & (L - 1);
+  const int maxdim = grid_maxdim(G);
+  KnnkGeo g;
+  const bool valid = knnk_geo(G, maxdim, live ? gx : NAN, gy, gz, g);
+  const float edge = fminf(fminf(fminf(g.rx, 1.f - g.rx), fminf(g.ry, 1.f - g.ry)), fminf(g.rz, 1.f - g.rz));
+  mine = gate_key;
+  bool done = !valid || gate_key == 0ull, proven = true;      // NaN query / a gate of 0: empty, and that is exact
+  // first ring that can reach the grid at all
+  int r_prev = -1, r = 1;
+  if (!done) {
+    const int ox_ = g.cx < 0 ? -g.cx : (g.cx >= G.nx ? g.cx - G.nx + 1 : 0);
+    const int oy_ = g.cy < 0 ? -g.cy : (g.cy >= G.ny ? g.cy - G.ny + 1 : 0);
+    const int oz_ = g.cz < 0 ? -g.cz : (g.cz >= G.nz ? g.cz - G.nz + 1 : 0);
+    r = max(1, max(ox_, max(oy_, oz_)));
+    if (r > KK_FAR_RING) { done = true; proven = false; }
+  }
+  float bound = r2;                          // min(gate, k-th distance so far) [m^2]: no point farther than it can enter the list
+  while (__any(!done)) {
+    // ---- the block of ring r, of which the block of ring r_prev has been walked: rows clipped to the grid; an inner row has a
+    //      part on either side of the old block (two jobs), an outer row is one job ----
+    const int y0 = max(g.cy - r, 0), y1 = min(g.cy + r, G.ny - 1), z0 = max(g.cz - r, 0), z1 = min(g.cz + r, G.nz - 1);
+    const int nyb = max(y1 - y0 + 1, 0), nzb = max(z1 - z0 + 1, 0);
+    const int sides = r_prev >= 0 ? 2 : 1;
+    const int njobs = done ? 0 : nyb * nzb * sides;
+    float bnd2 = kk_ball(G, bound);
+    for (int jb = 0; __any(jb < njobs); jb += L) {
+      const int j = jb + sub;
+      uint32_t lo = 0, len = 0;
+      if (j < njobs) {
+        const int row = sides == 2 ? j >> 1 : j, side = sides == 2 ? j & 1 : 0;
+        const int yy = y0 + row % nyb, zz = z0 + row / nyb;
+        const bool inner = r_prev >= 0 && abs(yy - g.cy) <= r_prev && abs(zz - g.cz) <= r_prev;
+        int x0 = g.cx - r, x1 = g.cx + r;
+        if (inner) { if (side == 0) x1 = g.cx - r_prev - 1; else x0 = g.cx + r_prev + 1; }
+        else if (side == 1) x1 = x0 - 1;
+        x0 = max(x0, 0); x1 = min(x1, G.nx - 1);
+        if (x0 <= x1) knnk_row(G, g, bnd2, yy, zz, x0, x1, lo, len);
+      }
+      knnk_round<L>(G, gx, gy, gz, lane, k, lo, len, mine, cand);
+      // the ball shrinks with the k-th best
+      const float dk = kk_key_dist(__shfl(mine, k - 1, L));
+      if (dk < bound) { bound = dk; bnd2 = kk_ball(G, bound); }
+    }
+    if (!done) {
+      // ---- exactness: every point not visited is at least rg away (knn_search) ----
+      const float rg = ((float)r + edge - g.margin) * G.cell;
+      const bool covers = (g.cx - r <= 0) && (g.cx + r >= G.nx - 1) && (g.cy - r <= 0) && (g.cy + r >= G.ny - 1) && (g.cz - r <= 0) &&
+                          (g.cz + r >= G.nz - 1);
+      if (covers || (rg > 0.f && bound <= rg * rg * (1.f - 1.0e-6f))) {
+        done = true;
+      } else {
+        // next ring: straight to the one that proves exactness once a bound is known, else double
+        int rn = 2 * r;
+        if (bound < 3.0e38f) {
+          const float need = fl_sqrt(bound) * G.inv_cell * (1.f + 4.0e-6f) - edge + g.margin;
+          rn = max(r + 1, (int)ceilf(fminf(need, 1.0e9f)));
+        }
+        if (rn > KK_FAR_RING) { done = true; proven = false; }
+        r_prev = r;
+        r = rn;
+      }
+    }
+  }
+  return proven;
+}
+
+// (the walk of one query by one wave: `bound` [m^2] is the first bound, `mine` ends as this lane's entry of the list)
+__device__ __forceinline__ void knnk_tile_walk(const GridView& G, int maxdim, int ndir, int cells_per_xtile, float gx, float gy, float gz, int lane,
+                                               int k, float bound, kk_u64 gate_key, kk_u64& mine, unsigned long long& cand) {
+  KnnkGeo g;
+  (void)knnk_geo(G, maxdim, gx, gy, gz, g);                    // (a NaN query never comes here)
+  float bnd2 = kk_ball(G, bound);
+  mine = gate_key;
+  float last_d = -1.f;
+  int last_i = -1;
+  for (;;) {
+    // ---- the nearest tile not visited yet: (distance, directory index) in ascending order ----
+    float best_d = INFINITY;
+    int best_i = INT_MAX;
+    for (int i = lane; i < ndir; i += 64) {
+      if (G.dir[i] == 0) continue;
+      const int tx = i % G.ntx, tyz = i / G.ntx, ty_ = tyz % G.nty, tz_ = tyz / G.nty;
+      const float x0 = (float)(tx * cells_per_xtile), x1 = (float)((tx + 1) * cells_per_xtile);
+      const float y0 = (float)((ty_ << G.ty) - GRID_PAD), y1 = (float)(((ty_ + 1) << G.ty) - GRID_PAD);
+      const float z0 = (float)((tz_ << G.tz) - GRID_PAD), z1 = (float)(((tz_ + 1) << G.tz) - GRID_PAD);
+      const float ax = fmaxf(fmaxf(x0 - g.qcx, g.qcx - x1) - g.margin, 0.f), ay = fmaxf(fmaxf(y0 - g.qcy, g.qcy - y1) - g.margin, 0.f),
+                  az = fmaxf(fmaxf(z0 - g.qcz, g.qcz - z1) - g.margin, 0.f);
+      const float d = (ax * ax + ay * ay + az * az) * (1.f - 1.0e-6f);
+      const bool after = d > last_d || (d == last_d && i > last_i);
+      if (after && (d < best_d || (d == best_d && i < best_i))) { best_d = d; best_i = i; }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float od = __shfl_xor(best_d, o, 64);
+      const int oi = __shfl_xor(best_i, o, 64);
+      if (od < best_d || (od == best_d && oi < best_i)) { best_d = od; best_i = oi; }
+    }
+    if (best_i == INT_MAX) break;                              // every tile has been visited
+    if (best_d > bnd2) break;                                  // no point of it -- or of any later one -- lies within the bound
+    last_d = best_d; last_i = best_i;
+    // ---- its rows, one per lane and round ----
+    const int tx = best_i % G.ntx, tyz = best_i / G.ntx, ty_ = tyz % G.nty, tz_ = tyz / G.nty;
+    const int xt0 = tx * cells_per_xtile, xt1 = min((tx + 1) * cells_per_xtile, G.nx) - 1;
+    const int nrows = 1 << (G.ty + G.tz);
+    for (int jb = 0; jb < nrows; jb += 64) {
+      const int j = jb + lane;
+      const int yy = (ty_ << G.ty) + (j & ((1 << G.ty) - 1)) - GRID_PAD, zz = (tz_ << G.tz) + (j >> G.ty) - GRID_PAD;
+      uint32_t lo = 0, len = 0;
+      if (j < nrows && yy >= 0 && yy < G.ny && zz >= 0 && zz < G.nz && xt0 <= xt1) knnk_row(G, g, bnd2, yy, zz, xt0, xt1, lo, len);
+      if (!__any(len != 0u)) continue;
+      knnk_round<64>(G, gx, gy, gz, lane, k, lo, len, mine, cand);
+      const float dk = kk_key_dist(__shfl(mine, k - 1, 64));
+      if (dk < bound) { bound = dk; bnd2 = kk_ball(G, bound); }
+    }
+  }
+}
+
+// ---- normals and covariances of the k-NN neighbourhoods (flimo_map_normals) ---------------------------------------------------
+// The same search; instead of knnk_store the group finishes its query in registers.  Lane `sub` holds slot sub of the list; it
+// loads that stored point and forms r = (double)p - (double)q (exact).  Every sum is a butterfly over the 64 SLOTS of a list,
+// slots beyond cnt holding +0.0: a 16-lane group runs the four levels it has and adds the +0.0 of the two it lacks, so the bits
+// depend on the list alone -- not on which kernel finished the query, nor on how many lanes served it.  Mean (divided by n), then
+// the sums of the six products centred on it (two passes, the values stay in registers): 72 bytes per query go to the chunk's
+// scratch, the neighbour list goes nowhere.  A third launch, one THREAD per query, divides by n and runs a cyclic Jacobi on the
+// 3 x 3 until the off-diagonal is exactly 0 (measured: run by the search kernel's lanes, each on the same numbers, the float64
+// divisions and square roots of the rotations added 70 % to the search's time -- profiles/normals/README.md).
+template <int L>
+__device__ __forceinline__ double kk_slot_sum(double v) {
+#pragma unroll
+  for (int o = 1; o < L; o <<= 1) v = v + __shfl_xor(v, o, L);
+#pragma unroll
+  for (int o = L; o < 64; o <<= 1) v = v + 0.0;      // (the empty upper slots of a 64-slot list: also turns a sum of -0.0 into the wave's +0.0)
+  return v;
+}
+
+// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3: app, aqq, apq its 2 x 2; arp, arq the third row's entries of those
+// columns; v*p, v*q columns p and q of the accumulated eigenvectors (Rutishauser's update: apq becomes exactly 0)
+__device__ __forceinline__ void kk_jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
+                                              double& v1p, double& v1q, double& v2p, double& v2q) {
+  if (apq == 0.0) return;
+  const double g = fabs(apq);
+  if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) { apq = 0.0; return; }      // below the diagonal's last bit
+  const double h = aqq - app;
+  double t;
+  if (fabs(h) + g == fabs(h)) {
+    t = apq / h;
+  } else {
+    const double theta = 0.5 * h / apq;
+    t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+    if (theta < 0.0) t = -t;
+  }
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+  const double hh = t * apq;
+  app = app - hh; aqq = aqq + hh; apq = 0.0;
+  double a = arp, b = arq;
+  arp = a - s * (b + a * tau); arq = b + s * (a - b * tau);
+  a = v0p; b = v0q; v0p = a - s * (b + a * tau); v0q = b + s * (a - b * tau);
+  a = v1p; b = v1q; v1p = a - s * (b + a * tau); v1q = b + s * (a - b * tau);
+  a = v2p; b = v2q; v2p = a - s * (b + a * tau); v2q = b + s * (a - b * tau);
+}
+
+constexpr int KK_JACOBI_SWEEPS = 12;
+__device__ __forceinline__ void kk_swap_if(bool c, double& a, double& b) { const double x = c ? b : a, y = c ? a : b; a = x; b = y; }
+
+struct NormalsOut {
+  float4* normal;        // [n] nx ny nz curvature
+  int32_t* cnt;          // [n]
+  double* centroid;      // [n][3] or null
+  double* cov;           // [n][6] or null: xx xy xz yy yz zz
+  double* eig;           // [n][6] or null: l0 <= l1 <= l2, the unit normal
+};
+struct NormalsArgs {
+  const float* qxyz;     // the chunk's queries, or null: query i is stored point first + i
+  unsigned first;
+  int nq, k, need;       // need: neighbours below which a query's results are NaN
+  float r2;
+  kk_u64 gate_key;
+  float vx, vy, vz;      // the viewpoint
+  int has_vp;
+};
+
+__device__ __forceinline__ void knnk_query(const NormalsArgs& A, const float4* __restrict__ map_raw, int q, float& gx, float& gy, float& gz) {
+  if (A.qxyz) { gx = A.qxyz[3 * q]; gy = A.qxyz[3 * q + 1]; gz = A.qxyz[3 * q + 2]; }
+  else { const float4 p = map_raw[(size_t)A.first + (size_t)q]; gx = p.x; gy = p.y; gz = p.z; }
+}
+
+// the group's end of a query whose list is exact: cnt, and the record {mean of r (3), sums of the centred products (6)}
+constexpr int KK_MOM = 9;
+template <int L>
+__device__ __forceinline__ void knnk_moments(const NormalsArgs& A, int lane, int q, bool live, kk_u64 mine, float gx, float gy, float gz,
+                                             const float4* __restrict__ map_raw, int32_t* __restrict__ cnt, double* __restrict__ mom) {
+  const int sub = lane & (L - 1);
+  const bool has = live && sub < A.k && mine < A.gate_key;
+  const unsigned long long bal = __ballot(has);
+  const int c = L == 64 ? __popcll(bal) : __popc(kk_group_mask<L>(bal, lane));
+  const double qx = (double)gx, qy = (double)gy, qz = (double)gz;
+  double rx = 0.0, ry = 0.0, rz = 0.0;
+  if (has) {
+    const float4 p = map_raw[(uint32_t)mine];
+    rx = (double)p.x - qx; ry = (double)p.y - qy; rz = (double)p.z - qz;
+  }
+  const double n = (double)c;
+  const double mx = kk_slot_sum<L>(rx) / n, my = kk_slot_sum<L>(ry) / n, mz = kk_slot_sum<L>(rz) / n;      // (c == 0: NaN, not used)
+  const double dx = has ? rx - mx : 0.0, dy = has ? ry - my : 0.0, dz = has ? rz - mz : 0.0;
+  const double s00 = kk_slot_sum<L>(has ? dx * dx : 0.0), s01 = kk_slot_sum<L>(has ? dx * dy : 0.0), s02 = kk_slot_sum<L>(has ? dx * dz : 0.0),
+               s11 = kk_slot_sum<L>(has ? dy * dy : 0.0), s12 = kk_slot_sum<L>(has ? dy * dz : 0.0), s22 = kk_slot_sum<L>(has ? dz * dz : 0.0);
+  if (live && sub == 0) {
+    cnt[q] = c;
+    double* M = mom + (size_t)KK_MOM * (size_t)q;
+    M[0] = mx; M[1] = my; M[2] = mz; M[3] = s00; M[4] = s01; M[5] = s02; M[6] = s11; M[7] = s12; M[8] = s22;
+  }
+}
+
+// One thread per query, after both searches: covariance = sums / n, the eigen-decomposition, the orientation, the outputs.  (In
+// the search kernels the 64 lanes of a wave would each run this on the same numbers: a wave's time for one query instead of 64.)
+__global__ __launch_bounds__(KK_BLOCK) void knnk_normals_finish_kernel(NormalsArgs A, const float4* __restrict__ map_raw, const double* __restrict__ mom,
+                                                                       NormalsOut O) {
+  const size_t gq = (size_t)blockIdx.x * KK_BLOCK + threadIdx.x;
+  if (gq >= (size_t)A.nq) return;
+  const int q = (int)gq;
+  float gx, gy, gz;
+  knnk_query(A, map_raw, q, gx, gy, gz);
+  const double qx = (double)gx, qy = (double)gy, qz = (double)gz;
+  const int c = O.cnt[q];
+  const bool enough = c >= A.need;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double* M = mom + (size_t)KK_MOM * (size_t)q;
+  const double n = (double)c;
+  double mx = 0.0, my = 0.0, mz = 0.0, a00 = 1.0, a01 = 0.0, a02 = 0.0, a11 = 1.0, a12 = 0.0, a22 = 1.0;      // (too few: nothing to rotate)
+  if (enough) {
+    mx = M[0]; my = M[1]; mz = M[2];
+    a00 = M[3] / n; a01 = M[4] / n; a02 = M[5] / n; a11 = M[6] / n; a12 = M[7] / n; a22 = M[8] / n;
+  }
+  if (O.centroid) {
+    O.centroid[3 * (size_t)q] = enough ? qx + mx : nan; O.centroid[3 * (size_t)q + 1] = enough ? qy + my : nan; O.centroid[3 * (size_t)q + 2] = enough ? qz + mz : nan;
+  }
+  if (O.cov) {
+    double* C = O.cov + 6 * (size_t)q;
+    C[0] = enough ? a00 : nan; C[1] = enough ? a01 : nan; C[2] = enough ? a02 : nan; C[3] = enough ? a11 : nan; C[4] = enough ? a12 : nan; C[5] = enough ? a22 : nan;
+  }
+  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+  for (int sweep = 0; sweep < KK_JACOBI_SWEEPS; sweep++) {
+    if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
+    kk_jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+    kk_jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+    kk_jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+  }
+  // ascending eigenvalues; on a tie the lower column first.  Only the smallest one's vector is kept.
+  double l0 = a00, l1 = a11, l2 = a22;
+  const bool s01 = l1 < l0;
+  kk_swap_if(s01, l0, l1); kk_swap_if(s01, v00, v01); kk_swap_if(s01, v10, v11); kk_swap_if(s01, v20, v21);
+  const bool s12 = l2 < l1;
+  kk_swap_if(s12, l1, l2); kk_swap_if(s12, v01, v02); kk_swap_if(s12, v11, v12); kk_swap_if(s12, v21, v22);
+  const bool t01 = l1 < l0;
+  kk_swap_if(t01, l0, l1); kk_swap_if(t01, v00, v01); kk_swap_if(t01, v10, v11); kk_swap_if(t01, v20, v21);
+  double nx = v00, ny = v10, nz = v20;
+  bool flip;
+  if (A.has_vp) {
+    flip = nx * ((double)A.vx - qx) + ny * ((double)A.vy - qy) + nz * ((double)A.vz - qz) < 0.0;
+  } else {
+    const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+    const double big = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
+    flip = big < 0.0;
+  }
+  if (flip) { nx = -nx; ny = -ny; nz = -nz; }
+  const double tr = l0 + l1 + l2;
+  const double curv = tr == 0.0 ? 0.0 : l0 / tr;
+  const float fn = __int_as_float(0x7fc00000);
+  O.normal[q] = enough ? make_float4((float)nx, (float)ny, (float)nz, (float)curv) : make_float4(fn, fn, fn, fn);
+  if (O.eig) {
+    double* E = O.eig + 6 * (size_t)q;
+    E[0] = enough ? l0 : nan; E[1] = enough ? l1 : nan; E[2] = enough ? l2 : nan; E[3] = enough ? nx : nan; E[4] = enough ? ny : nan; E[5] = enough ? nz : nan;
+  }
+}
+
+// knnk_kernel's search with that end.  A query the block search cannot prove goes to the worklist (its number, its first bound):
+// one atomicAdd of its leading lane on `nwork`.
+template <int L>
+__global__ __launch_bounds__(KK_BLOCK) void knnk_normals_kernel(GridView G, NormalsArgs A, const float4* __restrict__ map_raw, int32_t* __restrict__ cnt,
+                                                                double* __restrict__ mom, uint2* __restrict__ work, unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63;
+  const int sub = lane & (L - 1);
+  const size_t gq = ((size_t)blockIdx.x * KK_BLOCK + threadIdx.x) / (unsigned)L;
+  const bool live = gq < (size_t)A.nq;
+  const int q = live ? (int)gq : 0;
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  if (live) knnk_query(A, map_raw, q, gx, gy, gz);
+  kk_u64 mine;
+  unsigned long long cand = 0;
+  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, A.k, A.r2, A.gate_key, mine, cand);
+  if (!proven) {
+    // (the list's k-th distance, when there is one, bounds the true one: knnk_far_kernel's first bound)
+    const kk_u64 kth = __shfl(mine, A.k - 1, L);
+    if (live && sub == 0) {
+      const unsigned at = atomicAdd(nwork, 1u);
+      work[at] = make_uint2((unsigned)q, __float_as_uint(kth < A.gate_key ? kk_key_dist(kth) : A.r2));
+    }
+  }
+  knnk_moments<L>(A, lane, q, live && proven, mine, gx, gy, gz, map_raw, cnt, mom);
+}
+
+// the worklist's queries, one wave per entry: knnk_far_kernel's walk, the same end
+__global__ __launch_bounds__(KK_BLOCK, 5) void knnk_normals_far_kernel(GridView G, NormalsArgs A, const float4* __restrict__ map_raw,
+                                                                       int32_t* __restrict__ cnt, double* __restrict__ mom,
+                                                                       const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int maxdim = grid_maxdim(G);
+  const int ndir = G.ntx * G.nty * G.ntz;
+  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
+  const unsigned n = min(*nwork, (unsigned)A.nq);
+  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < n; w += gridDim.x * (KK_BLOCK / 64)) {
+    const uint2 e = work[w];
+    const int q = (int)min(e.x, (unsigned)(A.nq - 1));
+    float gx, gy, gz;
+    knnk_query(A, map_raw, q, gx, gy, gz);
+    kk_u64 mine;
+    unsigned long long cand = 0;
+    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, gx, gy, gz, lane, A.k, __uint_as_float(e.y), A.gate_key, mine, cand);
+    knnk_moments<64>(A, lane, q, true, mine, gx, gy, gz, map_raw, cnt, mom);
+  }
+}
+
 // lanes per query from k: a list of k keys needs k lanes
 int knnk_plan(int k) { return k <= 16 ? 16 : 64; }
 
@@ -344,6 +675,32 @@ hipError_t launch_knn_k(hipStream_t st, const GridView& G, const float4* map_raw
   else hipLaunchKernelGGL((knnk_kernel<64>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, q, nq, k, r2, gate_key, map_raw, idx, sqd, xyz, cnt, cand);
   const unsigned far_blocks = (unsigned)std::min<size_t>(4096, ((size_t)nq + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
   hipLaunchKernelGGL(knnk_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, q, nq, k, r2, gate_key, map_raw, idx, sqd, xyz, cnt, cand);
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, unsigned first, int nq, int k,
+                                float max_dist, int min_pts, const float* viewpoint, float4* normal, int32_t* cnt, double* centroid, double* cov,
+                                double* eig, double* mom, uint2* work, unsigned* nwork) {
+  if (nq <= 0) return hipSuccess;
+  if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
+  NormalsArgs A;
+  A.qxyz = q; A.first = first; A.nq = nq; A.k = k; A.need = std::max(3, min_pts);
+  A.r2 = max_dist * max_dist;
+  uint32_t r2_bits;
+  memcpy(&r2_bits, &A.r2, sizeof r2_bits);
+  A.gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
+  A.has_vp = viewpoint != nullptr;
+  A.vx = viewpoint ? viewpoint[0] : 0.f; A.vy = viewpoint ? viewpoint[1] : 0.f; A.vz = viewpoint ? viewpoint[2] : 0.f;
+  const NormalsOut O{normal, cnt, centroid, cov, eig};
+  hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  const int L = knnk_plan(k);
+  const unsigned blocks = (unsigned)(((size_t)nq * L + KK_BLOCK - 1) / KK_BLOCK);
+  if (L == 16) hipLaunchKernelGGL((knnk_normals_kernel<16>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
+  else hipLaunchKernelGGL((knnk_normals_kernel<64>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
+  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, ((size_t)nq + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
+  hipLaunchKernelGGL(knnk_normals_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
+  hipLaunchKernelGGL(knnk_normals_finish_kernel, dim3((unsigned)(((size_t)nq + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, A, map_raw, mom, O);
   return hipGetLastError();
 }
 

@@ -242,6 +242,40 @@ int flimo_loc_map_knn(flimo_loc* L, const float* q_xyz, size_t nq, int k, float 
   }
   return flimo_knn_k(c, q_xyz, nq, k, max_dist, idx, sqd, xyz, cnt);
 }
+// no map yet: the answer of an empty one, after flimo_map_normals' own argument checks
+static int normals_of_no_map(size_t nq, int k, float max_dist, const float* viewpoint, float* normal, int32_t* cnt, double* centroid, double* cov,
+                             double* eig) {
+  if (!normal || !cnt || std::isnan(max_dist) || max_dist < 0.f) return FLIMO_ERR_INVALID;
+  if (viewpoint && (std::isnan(viewpoint[0]) || std::isnan(viewpoint[1]) || std::isnan(viewpoint[2]))) return FLIMO_ERR_INVALID;
+  if (k < 1 || k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
+  if (nq >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
+  for (size_t i = 0; i < nq; i++) cnt[i] = 0;
+  for (size_t i = 0; i < nq * 4; i++) normal[i] = NAN;
+  if (centroid) for (size_t i = 0; i < nq * 3; i++) centroid[i] = (double)NAN;
+  if (cov) for (size_t i = 0; i < nq * 6; i++) cov[i] = (double)NAN;
+  if (eig) for (size_t i = 0; i < nq * 6; i++) eig[i] = (double)NAN;
+  return FLIMO_OK;
+}
+int flimo_loc_map_normals(flimo_loc* L, const float* q_xyz, size_t nq, int k, float max_dist, int min_pts, const float viewpoint[3], float* normal,
+                          int32_t* cnt, double* centroid, double* cov, double* eig) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
+  if (!c) {
+    if (nq > 0 && !q_xyz) return FLIMO_ERR_INVALID;
+    return normals_of_no_map(nq, k, max_dist, viewpoint, normal, cnt, centroid, cov, eig);
+  }
+  return flimo_map_normals(c, q_xyz, nq, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
+}
+int flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3], float* normal,
+                                int32_t* cnt, double* centroid, double* cov, double* eig) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();
+  if (!c) {
+    if (first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (beyond the size of a map of no points)
+    return normals_of_no_map(0, k, max_dist, viewpoint, normal, cnt, centroid, cov, eig);
+  }
+  return flimo_map_normals_range(c, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
+}
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
 // the map insert that ends a scan runs on the Mapper's worker thread (Mapper::add_scan): wait for it / switch it off

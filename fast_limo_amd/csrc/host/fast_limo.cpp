@@ -458,6 +458,42 @@ void Mapper::knn(const PointType& query, int k, std::vector<PointType>& neighbor
   }
 }
 
+// normals of the map's neighbourhoods (an insert or a crop on the worker thread ends first); q_xyz == nullptr: the range form
+int Mapper::normals_run(const float* q_xyz, size_t first, size_t nq, int k, float max_dist, int min_pts, const float* viewpoint,
+                        std::vector<float>& normal, std::vector<int32_t>& cnt, std::vector<double>* centroid, std::vector<double>* cov,
+                        std::vector<double>* eig) {
+  sync();
+  normal.clear(); cnt.clear();
+  if (centroid) centroid->clear();
+  if (cov) cov->clear();
+  if (eig) eig->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (k < 1 || k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
+  normal.assign(nq * 4, NAN); cnt.assign(nq, 0);
+  if (centroid) centroid->assign(nq * 3, (double)NAN);
+  if (cov) cov->assign(nq * 6, (double)NAN);
+  if (eig) eig->assign(nq * 6, (double)NAN);
+  // (vectors of no element may hand out a null pointer, which the call rejects)
+  int32_t none_i = 0; float none_f = 0.f;
+  float* np = nq ? normal.data() : &none_f;
+  int32_t* cp = nq ? cnt.data() : &none_i;
+  double* ce = (centroid && nq) ? centroid->data() : nullptr;
+  double* co = (cov && nq) ? cov->data() : nullptr;
+  double* ei = (eig && nq) ? eig->data() : nullptr;
+  if (q_xyz) return flimo_map_normals(ctx_, q_xyz, nq, k, max_dist, min_pts, viewpoint, np, cp, ce, co, ei);
+  return flimo_map_normals_range(ctx_, first, nq, k, max_dist, min_pts, viewpoint, np, cp, ce, co, ei);
+}
+int Mapper::normals(const float* q_xyz, size_t nq, int k, float max_dist, int min_pts, const float* viewpoint, std::vector<float>& normal,
+                    std::vector<int32_t>& cnt, std::vector<double>* centroid, std::vector<double>* cov, std::vector<double>* eig) {
+  if (!q_xyz && nq > 0) return FLIMO_ERR_INVALID;
+  const float none[3] = {0.f, 0.f, 0.f};
+  return normals_run(q_xyz ? q_xyz : none, 0, nq, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
+}
+int Mapper::normals_range(size_t first, size_t n, int k, float max_dist, int min_pts, const float* viewpoint, std::vector<float>& normal,
+                          std::vector<int32_t>& cnt, std::vector<double>* centroid, std::vector<double>* cov, std::vector<double>* eig) {
+  return normals_run(nullptr, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
+}
+
 void Mapper::add(pcl::PointCloud<PointType>::Ptr& pc, double time) {   // Mapper.cpp:88-96
   if (!pc || pc->points.size() < 1) return;
   sync();

@@ -72,6 +72,17 @@ class fast_limo::Mapper {
   // < max_dist * max_dist): idx / sqd [nq][k] (-1 / 0 beyond cnt[q]), cnt [nq], xyz (optional) [nq][k][3].  Returns a FLIMO_* code.
   int knn(const float* q_xyz, size_t nq, int k, float max_dist, std::vector<int32_t>& idx, std::vector<float>& sqd, std::vector<int32_t>& cnt,
           std::vector<float>* xyz = nullptr);
+  // Plane normals and covariances of the map's k-NN neighbourhoods (flimo_map_normals: what pcl::NormalEstimation computes), the
+  // neighbour lists never leaving the GPU.  normal [nq][4] = nx ny nz curvature, cnt [nq]; centroid [nq][3], cov [nq][6] (xx xy xz
+  // yy yz zz) and eig [nq][6] (ascending eigenvalues, the float64 normal) are filled where a vector is given.  viewpoint (may be
+  // null): the normals face it.  A query with fewer than max(3, min_pts) neighbours has NaN results.  Returns a FLIMO_* code.
+  int normals(const float* q_xyz, size_t nq, int k, float max_dist, int min_pts, const float* viewpoint, std::vector<float>& normal,
+              std::vector<int32_t>& cnt, std::vector<double>* centroid = nullptr, std::vector<double>* cov = nullptr,
+              std::vector<double>* eig = nullptr);
+  // ... of the stored points first .. first + n - 1 themselves (insertion order), nothing uploaded (flimo_map_normals_range)
+  int normals_range(size_t first, size_t n, int k, float max_dist, int min_pts, const float* viewpoint, std::vector<float>& normal,
+                    std::vector<int32_t>& cnt, std::vector<double>* centroid = nullptr, std::vector<double>* cov = nullptr,
+                    std::vector<double>* eig = nullptr);
   void sync();                                  // wait for a running insert or crop (no-op when idle)
   void set_async(bool on) { sync(); async_ = on; }
   double last_insert_seconds() { sync(); return insert_seconds_; }
@@ -89,6 +100,9 @@ class fast_limo::Mapper {
   int num_threads_;
   flimo_ctx* ctx_;
   flimo_ctx* front_;            // the input stage's context (front_ctx())
+  int normals_run(const float* q_xyz, size_t first, size_t nq, int k, float max_dist, int min_pts, const float* viewpoint,
+                  std::vector<float>& normal, std::vector<int32_t>& cnt, std::vector<double>* centroid, std::vector<double>* cov,
+                  std::vector<double>* eig);
   int device_;
   float cell_size_;
   std::string err_;

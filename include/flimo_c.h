@@ -158,6 +158,38 @@ int flimo_radius_search(flimo_ctx* ctx, const float* q_xyz, size_t nq, float rad
 int flimo_knn_k(flimo_ctx* ctx, const float* q_xyz, size_t nq, int k, float max_dist, int32_t* idx /* [nq][k] */,
                 float* sqd /* [nq][k] */, float* xyz /* [nq][k][3], may be NULL */, int32_t* cnt /* [nq] */);
 
+/* ---- plane normals and covariances of the map's k-NN neighbourhoods: what pcl::NormalEstimation computes (the reference's ROS
+ *      side links PCL), over the resident map and without the neighbour lists ever leaving the GPU ----
+ * The neighbourhood of query i is exactly flimo_knn_k(q_i, k, max_dist): same predicate, same unique order, same cnt.  With its
+ * n = cnt[i] points p_j, all in float64:
+ *     r_j = (double)p_j - (double)q          (exact: the precision does not depend on how far the map lies from the origin)
+ *     m   = sum r_j / n                      centroid = (double)q + m
+ *     C   = sum (r_j - m)(r_j - m)^T / n     (divided by n, as pcl::computeMeanAndCovarianceMatrix)
+ *     l0 <= l1 <= l2 the eigenvalues of C; the normal is the unit eigenvector of l0 (equal eigenvalues: the lower axis of the
+ *     decomposition first); curvature = l0 / (l0 + l1 + l2), 0 when that sum is 0 (PCL's rule).
+ * Orientation: with a viewpoint the normal is flipped so that n . (viewpoint - q) >= 0 (pcl::flipNormalTowardsViewpoint); with
+ * viewpoint == NULL its component of largest magnitude is made positive (equal magnitudes: the lowest axis decides).
+ * Outputs, host memory: normal [nq][4] = nx ny nz curvature, the float32 roundings of the float64 values; cnt [nq]; optional
+ * (each may be NULL) centroid [nq][3], cov [nq][6] = xx xy xz yy yz zz, eig [nq][6] = l0 l1 l2 and the float64 normal.
+ * cnt[i] < max(3, min_pts): normal, centroid, cov and eig of query i are NaN; cnt[i] is still reported.  A query with a NaN
+ * coordinate gives cnt 0; an empty map gives cnt 0 everywhere and FLIMO_OK; nq == 0 returns FLIMO_OK.
+ * A query's results depend on its neighbour list alone: every sum is taken in one fixed shape over the list's slots, so the same
+ * bits come out whatever path of the search finished the query, whatever the map's cell size, however the call is cut into
+ * chunks, and in the range form below.
+ * FLIMO_ERR_INVALID: NULL ctx / q_xyz (nq > 0) / normal / cnt, max_dist NaN or negative, a NaN viewpoint.  FLIMO_ERR_UNSUPPORTED:
+ * k outside 1 .. FLIMO_KNN_MAX_K.  flimo_knn_k's nq * k < 2^31 does not apply (nothing of that size exists): the only bound is
+ * nq < 2^31 (FLIMO_ERR_TOO_LARGE).  The outputs are untouched on an error.  Calling rules and cost as flimo_knn_k; device memory
+ * is taken per chunk of 2^20 queries, not per call. */
+int flimo_map_normals(flimo_ctx* ctx, const float* q_xyz, size_t nq, int k, float max_dist, int min_pts,
+                      const float viewpoint[3] /* may be NULL */, float* normal /* [nq][4]: nx ny nz curvature */, int32_t* cnt /* [nq] */,
+                      double* centroid /* [nq][3], may be NULL */, double* cov /* [nq][6] xx xy xz yy yz zz, may be NULL */,
+                      double* eig /* [nq][6]: l0 <= l1 <= l2, then the float64 unit normal; may be NULL */);
+/* The same with query i = stored point first + i (insertion index: flimo_map_points' order): nothing is uploaded, and the point is
+ * its own first neighbour (distance 0), as in PCL when the search surface is the input.  Bit for bit flimo_map_normals on those
+ * points.  FLIMO_ERR_INVALID also for first + n beyond flimo_map_size. */
+int flimo_map_normals_range(flimo_ctx* ctx, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3],
+                            float* normal, int32_t* cnt, double* centroid, double* cov, double* eig);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

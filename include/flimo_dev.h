@@ -69,6 +69,9 @@ int flimo_radius_candidates(flimo_ctx* ctx, const float* q_xyz, size_t nq, float
 /* flimo_knn_k's walk, counted: cand[i] = stored points query i's search loads and tests (16 bytes apiece), the block search and --
  * where it ran -- the walk over the tiles together; cand: host, [nq].  Arguments as flimo_knn_k. */
 int flimo_knn_k_candidates(flimo_ctx* ctx, const float* q_xyz, size_t nq, int k, float max_dist, uint64_t* cand);
+/* flimo_map_normals / flimo_map_normals_range work in chunks of n queries (default 2^20; 0 restores it): the chunk bounds the call's
+ * device scratch.  The results do not depend on it (tests, A/B). */
+int flimo_set_normals_chunk(flimo_ctx* ctx, size_t n);
 
 /* out[0] = GPU ms of the algebra launches timed so far (timing level 1), out[1] = their number,
  * out[2] = chains run, out[3] = chains that came back before the final iteration, out[4] = chains declined */

@@ -86,6 +86,14 @@ int    flimo_loc_map_radius_search(flimo_loc* L, const float* q_xyz, size_t nq, 
  * still running behind the last sweep has ended.  A Localizer that has no map yet answers like an empty one (all cnt 0). */
 int    flimo_loc_map_knn(flimo_loc* L, const float* q_xyz, size_t nq, int k, float max_dist, int32_t* idx, float* sqd, float* xyz,
                          int32_t* cnt);
+/* Plane normals and covariances of the map's k-NN neighbourhoods over the Localizer's map: flimo_map_normals and
+ * flimo_map_normals_range (include/flimo_c.h: same arguments, same results, same error codes) on the map's context, after an insert
+ * or a crop still running behind the last sweep has ended.  A Localizer that has no map yet answers like an empty one (all cnt 0,
+ * NaN results; a range other than first = 0, n = 0 lies beyond it). */
+int    flimo_loc_map_normals(flimo_loc* L, const float* q_xyz, size_t nq, int k, float max_dist, int min_pts, const float viewpoint[3],
+                             float* normal, int32_t* cnt, double* centroid, double* cov, double* eig);
+int    flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3],
+                                   float* normal, int32_t* cnt, double* centroid, double* cov, double* eig);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
