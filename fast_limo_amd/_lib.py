@@ -81,7 +81,7 @@ HIP_SYMBOLS = [
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
-    "flimo_set_timing", "flimo_set_timing_stride", "flimo_set_timing_deferred", "flimo_pass_count", "flimo_fused_pass_count", "flimo_tie_stats", "flimo_map_index_bytes", "flimo_fine_stats", "flimo_map_grid_selfcheck", "flimo_set_debug_records", "flimo_last_kernel_ms",
+    "flimo_set_timing", "flimo_set_timing_stride", "flimo_set_timing_deferred", "flimo_pass_count", "flimo_fused_pass_count", "flimo_tie_stats", "flimo_map_index_bytes", "flimo_map_index_layout", "flimo_fine_stats", "flimo_map_grid_selfcheck", "flimo_set_debug_records", "flimo_last_kernel_ms",
     "flimo_last_candidates_per_query", "flimo_last_widen_count", "flimo_last_stragglers", "flimo_stragglers_by_pass", "flimo_timing_totals", "flimo_timing_split", "flimo_set_path_switches", "flimo_set_wait_timeout_ms", "flimo_insert_rule_replay", "flimo_plane_fit5_host", "flimo_plane_eval5_host", "flimo_calculate_H_host",
     "flimo_update_chain", "flimo_chain_stats", "flimo_set_update_mode", "flimo_update_mode", "flimo_scan_adopt", "flimo_set_pass_pipeline", "flimo_pass_pipeline_end", "flimo_pass_pipeline_last", "flimo_pass_pipeline_stats", "flimo_device_large_bar",
 ]
@@ -175,6 +175,7 @@ def load_hip():
     L.flimo_tie_stats.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.flimo_fine_stats.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.flimo_map_index_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.flimo_map_index_layout.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
     L.flimo_fused_pass_count.restype = C.c_ulonglong
     L.flimo_fused_pass_count.argtypes = [vp]
     L.flimo_map_grid_selfcheck.restype = C.c_int
@@ -524,6 +525,20 @@ class HipCtx:
         self._chk(self._L.flimo_map_index_bytes(self._h, o))
         return dict(points=int(o[0]), index=int(o[1]), second_level=int(o[2]), tiles=int(o[3]), tile_pool_relayouts=int(o[4]),
                     sorted_array_allocated=int(o[5]))
+
+    def map_index_layout(self, level=0):
+        """flimo_map_index_layout (include/flimo_dev.h): the layout of the main grid's index (``level`` 0) or of the second level's
+        (1) as it was made.  ``valid`` False: that level has no index now (nothing else is in the dict then).  Drains the stream."""
+        o = (C.c_double * 28)()
+        self._chk(self._L.flimo_map_index_layout(self._h, int(level), o))
+        if not o[19]:
+            return dict(valid=False)
+        ints = ("xs", "six", "siy", "siz", "nx", "ny", "nz", "ts", "ty", "tz", "ntx", "nty", "ntz", "escape_slots", "escape_slots_taken")
+        d = dict(valid=True, ox=np.float32(o[0]), oy=np.float32(o[1]), oz=np.float32(o[2]), cell=np.float32(o[3]), points=int(o[20]))
+        d.update((name, int(o[4 + i])) for i, name in enumerate(ints))
+        if level == 1:
+            d.update(qlo=tuple(int(o[21 + a]) for a in range(3)), qhi=tuple(int(o[24 + a]) for a in range(3)))
+        return d
 
     def fused_pass_count(self) -> int:
         return int(self._L.flimo_fused_pass_count(self._h))

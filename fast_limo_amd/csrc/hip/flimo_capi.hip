@@ -755,14 +755,14 @@ static int rebuild_grid(flimo_ctx* c) {
   const float* bb = c->bb;    // tracked on the host while points are appended (no reduction kernel)
   if (c->sorted_follows) {
     // the raw buffer grew (by a quarter each time): the cell-sorted copy moves into a larger array as it is -- its rows stay where
-    // they are -- and the escape pool grows with it; nothing is sorted
+    // they are -- and the escape pool grows with it (index_escape_words); nothing is sorted
     c->sorted_follows = false;
     if (c->d_map_sorted && c->grid_valid && !c->test_tight_array) {
       const size_t ncap = std::min<size_t>(3 * c->map_cap + 65536, 0x7fffffffull);
       float4* np = nullptr;
       HIPCHK(c, hipMalloc(&np, ncap * sizeof(float4)));
       HIPCHK(c, hipMemcpyAsync(np, c->d_map_sorted, std::min(ncap, c->sorted_cap) * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-      const size_t ovf_words = (c->map_cap / 16 + 64) * 8;
+      const size_t ovf_words = index_escape_words(c->map_cap);      // (a pool a layout has grown beyond that is kept as it is)
       uint32_t* no = nullptr;
       if (ovf_words > c->idx.ovf_cap) {
         HIPCHK(c, hipMalloc(&no, ovf_words * sizeof(uint32_t)));
@@ -1904,6 +1904,29 @@ extern "C" int flimo_map_index_bytes(const flimo_ctx* c, uint64_t out[6]) {
   out[2] = c->fine_valid ? (uint64_t)c->fine.n_pts * sizeof(float4) + tables(c->fine, c->fine_idx) : 0ull;
   out[3] = c->grid_valid ? c->idx.tiles_used : 0ull;
   out[4] = c->index_overflows;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_index_layout(flimo_ctx* c, int level, double out[28]) {
+  if (!c || !out || level < 0 || level > 1) return FLIMO_ERR_INVALID;
+  for (int i = 0; i < 28; i++) out[i] = 0.0;
+  const bool valid = level == 0 ? c->grid_valid : c->fine_valid;
+  out[19] = valid ? 1.0 : 0.0;
+  if (!valid) return FLIMO_OK;
+  const GridView& g = level == 0 ? c->grid : c->fine;
+  const IndexTables& T = level == 0 ? c->idx : c->fine_idx;
+  out[0] = g.ox; out[1] = g.oy; out[2] = g.oz; out[3] = g.cell; out[4] = g.xs;
+  out[5] = g.six; out[6] = g.siy; out[7] = g.siz; out[8] = g.nx; out[9] = g.ny; out[10] = g.nz;
+  out[11] = g.ts; out[12] = g.ty; out[13] = g.tz; out[14] = g.ntx; out[15] = g.nty; out[16] = g.ntz;
+  out[17] = (double)(T.ovf_cap / 8);
+  // the escape slots taken so far: counted on the device.  NOT a passive getter: the context is entered and the stream drained
+  // for the read -- the owner's thread only.
+  uint32_t taken = 0;
+  ctx_enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (T.counters) HIPCHK(c, hipMemcpy(&taken, T.counters + 2, sizeof(taken), hipMemcpyDeviceToHost));
+  out[18] = taken;
+  out[20] = g.n_pts;
+  if (level == 1) for (int a = 0; a < 3; a++) { out[21 + a] = c->fine_qlo[a]; out[24 + a] = c->fine_qhi[a]; }
   return FLIMO_OK;
 }
 extern "C" int flimo_tie_stats(flimo_ctx* c, unsigned long long out[2]) {

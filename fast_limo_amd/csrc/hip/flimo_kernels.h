@@ -134,7 +134,7 @@ struct MapBuildScratch {
   size_t crop_tiles_cap = 0;
 };
 // slots of the mail words
-enum MailSlot { MAIL_BOOK = 0 /* 6 */, MAIL_BOOK_END = 8 /* 2 */, MAIL_CROWD = 12, MAIL_BOXCOUNT = 13, MAIL_BBOX = 16 /* 6 */, MAIL_VOXEL = 24 /* 4 */, MAIL_TILES = 28 /* build: tiles, overflow; merge: tiles, overflow */, MAIL_ROWS = 32 /* an insert found the point array full */, MAIL_CROP = 36 /* kept count of a crop */,
+enum MailSlot { MAIL_BOOK = 0 /* 6 */, MAIL_BOOK_END = 8 /* 2 */, MAIL_CROWD = 12, MAIL_BOXCOUNT = 13, MAIL_BBOX = 16 /* 6 */, MAIL_VOXEL = 24 /* 4 */, MAIL_TILES = 28 /* build: tiles, overflow; merge: tiles, overflow */, MAIL_ROWS = 32 /* an insert found the point array or the escape pool full */, MAIL_ESCAPES = 33 /* escape slots a full layout asked for */, MAIL_CROP = 36 /* kept count of a crop */,
                 MAIL_TAG = 62 /* number of the last mail_words, written behind its words */, MAIL_WORDS = 64 };
 struct MailPart { const void* src; int n; int dst; };
 // queues ONE small kernel that copies up to 6 runs of words into the mail slots; `rearm_bbox`: S.bbox is reset to the empty box
@@ -158,8 +158,14 @@ hipError_t sort_scan(hipStream_t st, const float4* in, size_t n, float4* out, Ma
 // the same layout without re-ordering (out[i] = (xyz, w = i)): for a sweep a voxel filter re-orders anyway
 hipError_t index_scan(hipStream_t st, const float4* in, size_t n, float4* out, const double* t_in, double* t_out);
 // The index of a grid (GridView, flimo_types.h) as the host owns it: the pool of tiles (tile 0: all zero), the directory, the
-// escape pool (one slot per 16 points of the point buffer's capacity is always enough) and xstart.  map_build_grid sizes and
-// (re)allocates all of it; map_merge_grid takes tiles from the pool's room and reports when it ran out (index_merge_overflow).
+// escape pool and xstart.  map_build_grid sizes and (re)allocates all of it; map_merge_grid takes tiles and escape slots from the
+// pools' room and reports when one ran out (index_merge_overflow).
+// The escape pool starts at one slot per 16 points of the point buffer's capacity (index_escape_words: 2 bytes per point).  That is
+// what a map needs whose crowded columns lie anywhere; the worst case is twice that (16 points in the first column of an x-tile
+// take two slots: the segment's own entry and the closing entry of the tile to its left).  A full layout counts the slots it
+// asks for and, when the pool was too small, grows it to that count plus a quarter and writes its entries again: it never ends
+// with an entry unwritten.  A pool grown that way is kept when the point buffer grows (the larger of the two sizes holds).
+constexpr size_t index_escape_words(size_t pts_cap) { return (pts_cap / 16 + 64) * 8; }
 struct IndexTables {
   uint2* tiles = nullptr; size_t tiles_cap_entries = 0;
   uint32_t cap_tiles = 0, tiles_used = 0;                 // tiles of the current shape the pool holds / numbers taken at the last build
@@ -180,7 +186,8 @@ void index_free(IndexTables& T);
 // Sorts `pts_in` by (z, y, fine x column) into the rows of `pts_out` (room for out_cap points) and builds the index (ends with the
 // stream waited for once: the pool is sized by the number of tiles the points need).  slack: the rows keep room behind their last
 // point (a map that receives inserts) as far as out_cap allows; otherwise they are packed.  pts_cap: capacity of the point buffer
-// the index is for (sizes the escape pool).
+// the index is for (the escape pool's first size; a layout that needs more slots grows the pool and writes its entries again, so
+// success means every escape is recorded).  Ends with the stream waited for.
 // geo: the grid's geometry (origin, cell, extents, column factor, cell shifts; its table pointers are not looked at).
 hipError_t map_build_grid(hipStream_t st, const float4* pts_in, size_t n, float4* pts_out, size_t out_cap, bool slack, IndexTables& T, size_t pts_cap,
                           const GridView& geo, MapBuildScratch& S);

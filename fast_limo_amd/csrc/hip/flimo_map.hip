@@ -231,7 +231,7 @@ __device__ __forceinline__ uint32_t wave_lower_bound_k(const ckey_t* __restrict_
 }
 // geometry of the index as the builders need it
 struct TabGeo { int nxs, ny, nz, ts, ty, tz, ntx, nty, ntz; };
-struct SegTab { uint2* tiles; const uint16_t* dir; uint32_t* ovf; uint32_t* ovf_count; uint32_t ovf_cap; uint32_t* xstart; TabGeo g; uint32_t* full_mail; };      // full_mail: word of mapped host memory that says "lay the index out afresh" (an insert), or null
+struct SegTab { uint2* tiles; const uint16_t* dir; uint32_t* ovf; uint32_t* ovf_count; uint32_t ovf_cap; uint32_t* xstart; TabGeo g; uint32_t* full_mail; };      // full_mail: word of mapped host memory that says "lay the index out afresh" (an insert), or null (a full layout: it reads ovf_count itself)
 __device__ __forceinline__ uint32_t tab_dir_index(const TabGeo& g, uint32_t py, uint32_t pz, uint32_t sg) {
   return ((pz >> g.tz) * (uint32_t)g.nty + (py >> g.ty)) * (uint32_t)g.ntx + (sg >> g.ts);
 }
@@ -353,13 +353,18 @@ __device__ __forceinline__ void row_entries(const SegTab& T, uint32_t py, uint32
       if (!big) { *dst = make_uint2(pre, nib); return; }
       const uint2 old = *dst;
       const uint32_t slot_o = ((int)old.x < 0) ? old.y : atomicAdd(T.ovf_count, 1u);
-      if (slot_o < T.ovf_cap) {            // (the pool holds one slot per 16 points of the point buffer's capacity -- 2 bytes per point; a segment at a tile's edge takes two, its own entry and the left tile's closing one, and moved rows never hand slots back: when it does run out, the insert says so below)
+      // (the pool starts at one slot per 16 points of the point buffer's capacity -- 2 bytes per point; a segment at a tile's edge
+      //  takes two, its own entry and the left tile's closing one, and moved rows never hand slots back.  The counter goes on
+      //  counting when the pool is exhausted: it says how many slots this layout needs.  A full layout reads it, grows the pool
+      //  and writes its entries again (map_build_grid), so it never ends with an entry unwritten; an insert leaves the entry
+      //  stale and says so below -- acceptable only because the full layout the host answers with is complete by that rule)
+      if (slot_o < T.ovf_cap) {
         uint32_t a = 0u;
 #pragma unroll
         for (int k = 0; k < 8; k++) { T.ovf[(size_t)slot_o * 8u + k] = a; a += s_cnt[i * 8 + k]; }
         *dst = make_uint2(pre | 0x80000000u, slot_o);
       } else if (T.full_mail) {
-        *T.full_mail = 1u;                 // out of escape slots: the entry stays stale -- the host lays the index out afresh before anything reads it
+        *T.full_mail = 1u;                 // out of escape slots: the host lays the index out afresh before anything reads it
       }
     };
 #pragma unroll
@@ -499,7 +504,7 @@ hipError_t map_build_grid(hipStream_t st, const float4* pts_in, size_t n, float4
   }
   {
     size_t slots = T.ovf_cap;
-    if ((e = grow(T.ovf, slots, (pts_cap / 16 + 64) * 8, 0)) != hipSuccess) return e;
+    if ((e = grow(T.ovf, slots, index_escape_words(pts_cap), 0)) != hipSuccess) return e;
     T.ovf_cap = slots;
     if ((e = grow(T.xstart, T.xstart_cap, grid_xstart_size(ny, nz, shape.ntx), grid_xstart_size(ny, nz, shape.ntx) / 2)) != hipSuccess) return e;
   }
@@ -558,16 +563,34 @@ hipError_t map_build_grid(hipStream_t st, const float4* pts_in, size_t n, float4
   T.cap_tiles = (uint32_t)std::min<size_t>(std::min<size_t>(T.tiles_cap_entries, ((size_t)1 << 32) - 1) / te, 65536);
   if ((e = hipMemsetAsync(T.tiles, 0, (size_t)T.cap_tiles * te * sizeof(uint2), st)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(T.xstart, 0, grid_xstart_size(ny, nz, shape.ntx) * sizeof(uint32_t), st)) != hipSuccess) return e;
-  const SegTab tab{T.tiles, T.dir, T.ovf, T.counters + 2, (uint32_t)(T.ovf_cap / 8), T.xstart, g, nullptr};
   {
     size_t rc = T.rowcap_cap;
     if ((e = grow(T.rowcap, rc, ((size_t)ny + 2 * GRID_PAD) * ((size_t)nz + 2 * GRID_PAD), ((size_t)ny + 2 * GRID_PAD) * ((size_t)nz + 2 * GRID_PAD) / 2)) != hipSuccess) return e;
     T.rowcap_cap = rc;
   }
   if ((e = hipMemsetAsync(T.rowcap, 0, ((size_t)ny + 2 * GRID_PAD) * ((size_t)nz + 2 * GRID_PAD) * sizeof(uint32_t), st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(rows_build_kernel, dim3((unsigned)nrows), dim3(256), 0, st, tab, T.rowcap, T.tail, S.ck_out, row_lo, room, T.rowoff, (uint32_t)nrows);
+  // the entries.  An escape that finds the pool exhausted writes nothing, but the counter goes on counting: it comes back with the
+  // number of slots this layout needs.  More than the pool holds (crowded columns right behind tile boundaries take two slots per
+  // 16 points): the pool grows to that count and a quarter for the inserts that follow, the tiles are cleared and the entries are
+  // written again -- the sort and the points' places stand.  The count depends on the points alone, so the second round fits.
+  for (int round = 0;; round++) {
+    const SegTab tab{T.tiles, T.dir, T.ovf, T.counters + 2, (uint32_t)std::min<size_t>(T.ovf_cap / 8, 0xffffffffull), T.xstart, g, nullptr};
+    hipLaunchKernelGGL(rows_build_kernel, dim3((unsigned)nrows), dim3(256), 0, st, tab, T.rowcap, T.tail, S.ck_out, row_lo, room, T.rowoff, (uint32_t)nrows);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const MailPart part{T.counters + 2, 1, MAIL_ESCAPES};
+    if ((e = mail_words(st, S, &part, 1)) != hipSuccess) return e;
+    if ((e = mail_wait(st, S)) != hipSuccess) return e;          // (everything queued before the words has completed)
+    const size_t asked = S.mail_host[MAIL_ESCAPES];
+    if (asked <= T.ovf_cap / 8) break;
+    if (round > 0) return hipErrorOutOfMemory;                     // (cannot happen: the same points ask for the same slots)
+    size_t words = T.ovf_cap;
+    if ((e = grow(T.ovf, words, (asked + asked / 4 + 64) * 8, 0)) != hipSuccess) { T.ovf_cap = 0; return e; }
+    T.ovf_cap = words;
+    if ((e = hipMemsetAsync(T.tiles, 0, (size_t)T.cap_tiles * te * sizeof(uint2), st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(T.counters + 2, 0, sizeof(uint32_t), st)) != hipSuccess) return e;
+  }
   T.tiles_used = (uint32_t)ntiles;
-  return hipGetLastError();
+  return hipSuccess;
 }
 
 // ---- incremental update of the cell-sorted map ------------------------------------------------

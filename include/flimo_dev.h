@@ -82,6 +82,17 @@ int flimo_chain_stats(flimo_ctx* ctx, double out[5], int reset);
  * the tile pool too small and had the index laid out afresh, out[5] = the cell-sorted array AS ALLOCATED (three times the raw
  * buffer's capacity: its rows keep room behind their last point, so that an insert touches only the rows it adds to) */
 int flimo_map_index_bytes(const flimo_ctx* ctx, uint64_t out[6]);
+/* The layout of the map's index as it was actually made (tests place points by it instead of deriving it again): level 0 = the
+ * main grid, 1 = the second level over crowded regions.  out[0..2] = ox oy oz (origin of the cells), [3] = cell edge, [4] = xs (fine x
+ * columns per cell); [5..7] = six siy siz (the grid's corner in cells of the origin's lattice), [8..10] = nx ny nz; [11..13] = ts ty
+ * tz (log2 of a tile's extent in segments of 8 columns / rows / layers), [14..16] = ntx nty ntz (directory extent); [17] = capacity
+ * of the escape pool in slots (a slot: the eight cumulative counts of a segment with a column of more than 15 points), [18] = slots
+ * taken since the last full layout; [19] = 1 when that level's index is valid (everything else is 0 when it is not), [20] = points
+ * it holds; level 1 only: [21..23] / [24..26] = lowest / highest fine cell per axis of a query the second level may settle.
+ * A point p lies in column floor(((p.x - ox) * (1 / cell)) * xs) - six * xs of row (floor((p.y - oy) * (1 / cell)) - siy,
+ * floor((p.z - oz) * (1 / cell)) - siz), all in float32.  [18] is read from the device behind a wait for the context's stream:
+ * the owner's thread only. */
+int flimo_map_index_layout(flimo_ctx* ctx, int level, double out[28]);
 /* pipelined host loop (flimo_set_pass_pipeline): {passes that found their launch waiting, queued passes nobody asked for, passes
  * whose waiting launch was found too old to publish to (told to leave, launched the usual way), passes whose launch had left as a
  * whole before the publish reached it (launched again)} */
