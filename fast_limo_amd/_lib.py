@@ -405,7 +405,7 @@ class HipCtx:
                 setattr(fc, k, v)
         rec = np.ascontiguousarray(records)
         n = rec.shape[0]
-        assert rec.dtype.itemsize * (rec.size // max(n, 1)) == (16 if (time_order & 4) else 32)
+        assert n == 0 or rec.dtype.itemsize * (rec.size // n) == (16 if (time_order & 4) else 32)
         kept, last, nan, tied = C.c_size_t(0), C.c_double(0), C.c_int(0), C.c_int(0)
         self._chk(self._L.flimo_raw_scan_filter_order_set(self._h, rec.ctypes.data, n, C.byref(fc), int(time_order), C.byref(kept),
                                                           C.byref(last), C.byref(nan), C.byref(tied)))

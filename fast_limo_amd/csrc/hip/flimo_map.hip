@@ -1352,8 +1352,9 @@ hipError_t filter_raw_scan(hipStream_t st, const void* raw32_dev, size_t n, cons
     if ((e = hipMalloc(&S.filt_desc, (2 * cap + 1) * sizeof(unsigned long long))) != hipSuccess) return e;
     if ((e = hipMemsetAsync(S.filt_desc, 0, (2 * cap + 1) * sizeof(unsigned long long), st)) != hipSuccess) return e;   // launch number 0: never valid
     S.filt_tiles_cap = cap;
-    S.filt_epoch = 0;
     S.filt_ticket_base = 0;
+    // (the launch number goes on counting: the new words carry 0, which no launch has, and the host's mail granules still carry
+    //  the tags of the launches before -- a count that started again would meet its own old tag there and read a stale result)
   }
   if (!S.filt_mail_host) {
     if ((e = hipHostMalloc((void**)&S.filt_mail_host, 8 * sizeof(unsigned long long), hipHostMallocMapped)) != hipSuccess) return e;
@@ -1519,15 +1520,33 @@ __global__ __launch_bounds__(256) void bbox_finite_kernel(const float4* __restri
 __global__ __launch_bounds__(256) void voxelkey_kernel(const float4* __restrict__ pts, size_t n, float inv, const unsigned* __restrict__ box,
                                                        uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ flags) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned b0 = box[0];
   int mb0 = 0, mb1 = 0, mb2 = 0, mul1 = 1, mul2 = 1;
-  bool bad = b0 == 0xffffffffu;
+  // no finite point: the box is as the reduction found it armed or left it -- min above max (its blocks fold in FLT_MAX / -FLT_MAX,
+  // so the words are not the arming values any more)
+  bool bad = box[0] > box[3];
   if (!bad) {
-    mb0 = (int)floorf(o2f(box[0]) * inv); mb1 = (int)floorf(o2f(box[1]) * inv); mb2 = (int)floorf(o2f(box[2]) * inv);
-    const int d0 = (int)floorf(o2f(box[3]) * inv) - mb0 + 1, d1 = (int)floorf(o2f(box[4]) * inv) - mb1 + 1, d2 = (int)floorf(o2f(box[5]) * inv) - mb2 + 1;
-    const long long cells = (long long)d0 * d1 * d2;
+    // The lattice in 64-bit, as PCL forms dx, dy, dz (int64): one axis of more than 2^31 cells must not wrap into a small or
+    // negative count.  A floor that does not fit an int (|x * inv| >= 2^31: PCL's own static_cast<int> is undefined there) passes
+    // through as well.  Each factor is in 1 .. 2^32, so the product is tested factor by factor.
+    float fl[3], fh[3];
+    bool fits = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      fl[a] = floorf(o2f(box[a]) * inv); fh[a] = floorf(o2f(box[3 + a]) * inv);
+      fits = fits && (fabsf(fl[a]) < 2147483648.0f) && (fabsf(fh[a]) < 2147483648.0f);
+    }
+    long long d0 = 1, d1 = 1, cells = 2147483648ll;
+    if (fits) {
+      mb0 = (int)fl[0]; mb1 = (int)fl[1]; mb2 = (int)fl[2];
+      d0 = (long long)fh[0] - (long long)fl[0] + 1;
+      d1 = (long long)fh[1] - (long long)fl[1] + 1;
+      const long long d2 = (long long)fh[2] - (long long)fl[2] + 1;
+      cells = d0;
+      if (cells <= 2147483647ll) cells *= d1;
+      if (cells <= 2147483647ll) cells *= d2;
+    }
     if (cells > 2147483647ll) { bad = true; if (i == 0) flags[1] = 1u; }
-    mul1 = d0; mul2 = d0 * d1;
+    else { mul1 = (int)d0; mul2 = (int)(d0 * d1); }
   } else if (i == 0) {
     flags[0] = 1u;
   }

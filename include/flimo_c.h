@@ -197,7 +197,11 @@ size_t flimo_scan_size(const flimo_ctx* ctx);
 int flimo_scan_get(flimo_ctx* ctx, float* xyz_out, size_t cap, size_t* n);
 
 /* ---- voxel-grid filter on the resident scan: replaces pcl::VoxelGrid in Localizer::updatePointCloud
- *      (Modules/Localizer.cpp:313-321): centroid per occupied voxel, ascending voxel index ---- */
+ *      (Modules/Localizer.cpp:313-321): centroid per occupied voxel, ascending voxel index.  Non-finite points are skipped; a scan
+ *      with no finite point becomes empty.  The lattice is formed in 64-bit, as PCL forms it: floor(min / leaf) and floor(max / leaf)
+ *      per axis, their difference + 1 and the product of the three counts as int64.  A product above INT_MAX -- one axis alone may
+ *      exceed it -- leaves the scan as it is, non-finite points included (PCL warns "leaf size is too small" and returns its input).
+ *      So does a floor that does not fit an int, |x / leaf| >= 2^31: PCL casts it to int, which is undefined there. ---- */
 int flimo_scan_voxel_filter(flimo_ctx* ctx, float leaf_size, size_t* n_out);
 
 /* ---- deskew: replaces the OpenMP loop of Localizer::deskewPointCloud

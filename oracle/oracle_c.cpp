@@ -83,6 +83,37 @@ void oracle_state_update(float s[25], double time, double t) {
   s[7] = X.v.x; s[8] = X.v.y; s[9] = X.v.z;
 }
 
+void oracle_deskew_points(const float* xyz, const double* t, size_t n, const void* frames, size_t nf, const float L2B[16],
+                          const double last_x26[26], float* out_body, float* out_world) {
+  std::vector<State> fr(nf);
+  for (size_t k = 0; k < nf; k++) {
+    const char* rec = (const char*)frames + k * 112;
+    float f[27];
+    memcpy(f, rec, sizeof(f));
+    State& X = fr[k];
+    X.p = V3f(f[0], f[1], f[2]);
+    X.q = Quatf(f[6], f[3], f[4], f[5]);
+    X.v = V3f(f[7], f[8], f[9]);
+    X.g = V3f(f[10], f[11], f[12]);
+    X.w = V3f(f[13], f[14], f[15]);
+    X.a = V3f(f[16], f[17], f[18]);
+    X.bgyro = V3f(f[19], f[20], f[21]);
+    X.baccel = V3f(f[22], f[23], f[24]);
+    memcpy(&X.time, rec + 104, sizeof(double));
+  }
+  M4f T;
+  for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) T.m[i][j] = L2B[i * 4 + j];
+  StateIkfom s;
+  s.from_flat(last_x26);
+  const M4f last_inv = State(s).get_RT_inv();
+  for (size_t k = 0; k < n; k++) {
+    V4f pw, p2;
+    deskew_point(fr, T, last_inv, xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2], t[k], pw, p2);
+    out_body[3 * k] = p2.v[0]; out_body[3 * k + 1] = p2.v[1]; out_body[3 * k + 2] = p2.v[2];
+    if (out_world) for (int c = 0; c < 4; c++) out_world[4 * k + c] = pw.v[c];
+  }
+}
+
 void* oracle_octree_create(float min_extent, int downsample) {
   Octree* t = new Octree();
   t->setMinExtent(min_extent);

@@ -56,6 +56,14 @@ typedef struct oracle_match_rec {
  * from `time` to `t`; writes p, q, v back */
 void   oracle_state_update(float s[25], double time, double t);
 
+/* The loop body of Localizer::deskewPointCloud (Localizer.cpp:825-839) for n points given the IMU frames: xyz n x 3 (LiDAR frame),
+ * t[n] absolute stamps, frames nf records of 112 bytes in flimo_frame's layout (include/flimo_c.h: p3 q4(xyzw) v3 g3 w3 a3 bg3 ba3
+ * as 27 floats, 4 bytes of padding, double time), sorted by time; lidar2baselink_T row-major 4x4; last_x26 the filter state whose
+ * State(..).get_RT_inv() takes the world-frame point to the body frame at the scan's end.  out_body n x 3; out_world (may be NULL)
+ * n x 4, the world-frame point with the 4th component the arithmetic leaves. */
+void   oracle_deskew_points(const float* xyz, const double* t, size_t n, const void* frames, size_t nf,
+                            const float lidar2baselink_T[16], const double last_x26[26], float* out_body, float* out_world);
+
 /* ---- octree (reference Objects/Octree.hpp) ---- */
 void*  oracle_octree_create(float min_extent, int downsample);
 void   oracle_octree_destroy(void* t);

@@ -237,6 +237,24 @@ def voxel_grid(xyz, leaf):
     return out[:n]
 
 
+def deskew_points(xyz, t, frames, L2B, last_x26):
+    """The loop body of Localizer::deskewPointCloud for points with given stamps and IMU frames (oracle_deskew_points): ``frames``
+    an array of 112-byte records in flimo_frame's layout.  Returns (body [n, 3], world [n, 4])."""
+    xyz = _f32(xyz).reshape(-1, 3)
+    t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+    frames = np.ascontiguousarray(frames)
+    assert frames.dtype.itemsize == 112 and t.shape[0] == xyz.shape[0] and frames.shape[0] >= 1
+    n = xyz.shape[0]
+    body = np.empty((max(n, 1), 3), np.float32)
+    world = np.empty((max(n, 1), 4), np.float32)
+    L = lib()
+    L.oracle_deskew_points.restype = None
+    L.oracle_deskew_points.argtypes = [f32p, f64p, C.c_size_t, C.c_void_p, C.c_size_t, f32p, f64p, f32p, f32p]
+    L.oracle_deskew_points(xyz, t, n, frames.ctypes.data, frames.shape[0], _f32(L2B).reshape(16),
+                           np.ascontiguousarray(last_x26, dtype=np.float64), body, world)
+    return body[:n], world[:n]
+
+
 def state_update(s25, time, t):
     """State::update on a flat state (p3 q4(xyzw) v3 g3 w3 a3 bg3 ba3); returns the updated copy."""
     s = np.ascontiguousarray(s25, dtype=np.float32).copy()

@@ -183,14 +183,22 @@ inline std::vector<Pt> voxel_grid(const std::vector<Pt>& in, float leaf) {
     mn[0] = std::min(mn[0], p.x); mn[1] = std::min(mn[1], p.y); mn[2] = std::min(mn[2], p.z);
     mx[0] = std::max(mx[0], p.x); mx[1] = std::max(mx[1], p.y); mx[2] = std::max(mx[2], p.z);
   }
-  int min_b[3], max_b[3], div_b[3];
+  if (mn[0] > mx[0]) return out;                      // no finite point: nothing to bin (the box is still at its initial values)
+  // The lattice in 64-bit, as PCL forms dx, dy, dz (int64) before its "leaf size is too small" test: an axis of more than 2^31
+  // cells, or a product beyond INT_MAX, returns the input unchanged.  A floor that does not fit an int (|x * inv| >= 2^31) is
+  // undefined in PCL itself (its min_b_ / max_b_ are static_cast<int>): passed through as well.
+  long long lo_b[3], div64[3];
   for (int a = 0; a < 3; a++) {
-    min_b[a] = (int)std::floor(mn[a] * inv);
-    max_b[a] = (int)std::floor(mx[a] * inv);
-    div_b[a] = max_b[a] - min_b[a] + 1;
+    const float fl = std::floor(mn[a] * inv), fh = std::floor(mx[a] * inv);
+    if (!(std::fabs(fl) < 2147483648.0f) || !(std::fabs(fh) < 2147483648.0f)) return in;
+    lo_b[a] = (long long)fl;
+    div64[a] = (long long)fh - lo_b[a] + 1;
   }
-  const long long cells = (long long)div_b[0] * div_b[1] * div_b[2];
+  long long cells = div64[0];                          // (each factor is in 1 .. 2^32: the product is tested factor by factor)
+  for (int a = 1; a < 3 && cells <= (long long)INT_MAX; a++) cells *= div64[a];
   if (cells > (long long)INT_MAX) return in;          // PCL warns and returns the input unchanged
+  int min_b[3], div_b[3];
+  for (int a = 0; a < 3; a++) { min_b[a] = (int)lo_b[a]; div_b[a] = (int)div64[a]; }
   const int mul1 = div_b[0], mul2 = div_b[0] * div_b[1];
   std::vector<std::pair<int, int>> iv;
   iv.reserve(in.size());
@@ -374,6 +382,19 @@ inline int binary_search_tailored(const std::vector<State>& v, double t) {
   }
   if (high < 0) return 0;
   return high;
+}
+
+// One point of the loop of Localizer::deskewPointCloud (Localizer.cpp:825-839): the frame of its stamp, State::update to that stamp,
+// pw = (X0.get_RT() * lidar2baselink_T) * [x y z 1] (world frame, all four components), p2 = last_state.get_RT_inv() * pw.
+inline void deskew_point(const std::vector<State>& frames, const M4f& lidar2baselink_T, const M4f& last_inv, float x, float y, float z,
+                         double tk, V4f& pw, V4f& p2) {
+  int i_f = binary_search_tailored(frames, tk);
+  State X0 = frames[i_f];
+  X0.update(tk);
+  M4f T = mul(X0.get_RT(), lidar2baselink_T);
+  V4f pt(x, y, z, 1.f);
+  pw = mul(T, pt);
+  p2 = mul(last_inv, pw);
 }
 
 struct Localizer {
@@ -617,13 +638,8 @@ struct Localizer {
 #pragma omp parallel for num_threads(nt)
     for (long long k = 0; k < (long long)sorted.size(); k++) {
       double tk = extract(sorted[k]) + offset;
-      int i_f = binary_search_tailored(frames, tk);
-      State X0 = frames[i_f];
-      X0.update(tk);
-      M4f T = mul(X0.get_RT(), lidar2baselink_T);
-      V4f pt(sorted[k].x, sorted[k].y, sorted[k].z, 1.f);
-      V4f pw = mul(T, pt);
-      V4f p2 = mul(last_inv, pw);
+      V4f pw, p2;
+      deskew_point(frames, lidar2baselink_T, last_inv, sorted[k].x, sorted[k].y, sorted[k].z, tk, pw, p2);
       Pt o = sorted[k];
       o.x = p2.v[0]; o.y = p2.v[1]; o.z = p2.v[2];
       out[k] = o;

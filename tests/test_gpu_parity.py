@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from common import CAPS, cfg1_scene, drive_two_scans, pose_delta, sort_rows
+from front_end_common import filter_cfg, filter_reference
 from fast_limo_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -454,9 +455,9 @@ def test_sensor_time_formats_and_input_filters_match_oracle(built, oracle, senso
 def test_gpu_input_filters_and_stamps_match_oracle(built, oracle, sensor, eos):
     """The pre-update pipeline on the GPU (flimo_raw_scan_filter_set): NaN removal, negative crop box,
     every-n-th survivor, min distance and the per-sensor point stamps, for a sweep that stays in arrival order (no host clouds
-    requested).  The deskewed resident scan must be the oracle's pc2match as a set of points (bit for bit where the body does
-    not turn, 2e-6 m with rotation: device sinf / cosf), with the same count; the host-filter path of the product must give the
-    identical resident scan and pose."""
+    requested).  The deskewed resident scan must be the oracle's pc2match as a set of points, bit for bit (the body turns: the
+    device evaluates sinf / cosf as the host's libm does, flimo_math.h libm_sincosf), with the same count; the host-filter path of
+    the product must give the identical resident scan and pose."""
     from fast_limo_amd import api
     code = {"OUSTER": 0, "VELODYNE": 1, "HESAI": 2, "LIVOX": 3}[sensor]
     mp, scan5, imu = cfg1_scene(n_scan=6000)
@@ -506,7 +507,7 @@ def test_gpu_input_filters_and_stamps_match_oracle(built, oracle, sensor, eos):
     po = Lo.pc2match()
     dev, hst = res["device"], res["host"]
     assert dev[0].shape == po.shape and 800 < po.shape[0] < 2600
-    np.testing.assert_allclose(sort_rows(dev[0]), sort_rows(po), rtol=0, atol=2e-6)       # same kept points, same stamps
+    np.testing.assert_array_equal(sort_rows(dev[0]), sort_rows(po))                       # same kept points, same stamps
     np.testing.assert_array_equal(dev[0], hst[0])                                        # device filters == host filters, same order
     np.testing.assert_array_equal(dev[1], hst[1])
     assert dev[2] == hst[2] == Lo.map_size()
@@ -581,16 +582,10 @@ def test_c_abi_input_stage_records_hand_over_and_time_order(built, oracle):
     rec16[:, 3] = rel
     cfg = dict(crop_active=1, crop_min=(-2.0, -2.0, -2.0), crop_max=(2.0, 2.0, 2.0), dist_active=1, min_dist=5.0, rate_active=1,
                rate_value=3, time_kind=1, end_of_sweep=0, sweep_ref_time=10.0)
-    # numpy restatement of the filters
-    finite = np.isfinite(xyz).all(axis=1)
-    inside = ((xyz > -2.0) & (xyz < 2.0)).all(axis=1)
-    alive = finite & ~inside
-    rank = np.cumsum(alive) - 1
-    keep = alive & (rank % 3 == 0)
-    with np.errstate(invalid="ignore"):
-        keep &= np.sqrt(xyz[:, 0] * xyz[:, 0] + (xyz[:, 1] * xyz[:, 1] + xyz[:, 2] * xyz[:, 2])) > np.float32(5.0)
-    kept_xyz, kept_t = xyz[keep], rel[keep]
-    order_ref = np.argsort(kept_t, kind="stable")
+    # numpy restatement of the filters and the time sort (tests/front_end_common.py)
+    ref = filter_reference(xyz, rel, filter_cfg(**cfg))
+    keep, kept_xyz, kept_t, order_ref = ref["keep"], ref["xyz"], rel[ref["keep"]], ref["order"]
+    assert 0 < ref["n_kept"] < n // 3 and ref["tied"] == 0
     frames = np.zeros(24, _lib.FRAME_DTYPE)
     frames["q"][:, 3] = 1.0
     frames["g"][:, 2] = -9.81
