@@ -77,7 +77,7 @@ FRAME_DTYPE = np.dtype([
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
     "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_size", "flimo_scan_get",
+    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
@@ -105,6 +105,21 @@ def normals_call(call, nq, k, max_dist, min_pts, viewpoint, want):
     call(int(k), float(max_dist), int(min_pts), None if vp is None else vp.ctypes.data, ptr(out["normal"]), ptr(out["cnt"]),
          ptr(out.get("centroid")), ptr(out.get("cov")), ptr(out.get("eig")))
     return out
+
+
+def fitness_call(call, x26s, n, max_dist, want_nn):
+    """The output arrays of flimo_scan_fitness / flimo_loc_scan_fitness and the call's arguments (``call`` takes them: x26, np,
+    max_dist, inliers, sum_sqd, nn_sqd, nn_idx); ``n``: the size of the resident scan.  Shared with ``api.Localizer``."""
+    x = np.ascontiguousarray(x26s, dtype=np.float64).reshape(-1, 26)
+    m = x.shape[0]
+    inliers = np.zeros(m, np.int32)
+    sum_sqd = np.zeros(m, np.float64)
+    nn_sqd = np.full((m, n), -1, np.float32) if want_nn else None
+    nn_idx = np.full((m, n), -1, np.int32) if want_nn else None
+    # (an array of no element may have no address; the call wants its required pointers non-null)
+    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(C.c_double()))
+    call(x.ctypes.data if m else None, m, float(max_dist), ptr(inliers), ptr(sum_sqd), ptr(nn_sqd), ptr(nn_idx))
+    return (inliers, sum_sqd, nn_sqd, nn_idx) if want_nn else (inliers, sum_sqd)
 
 
 def hip_lib_path() -> str:
@@ -150,6 +165,8 @@ def load_hip():
     L.flimo_map_normals_range.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
     L.flimo_set_normals_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_scan_fitness.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_set_fitness_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.flimo_scan_size.restype = C.c_size_t
     L.flimo_scan_size.argtypes = [vp]
@@ -388,6 +405,17 @@ class HipCtx:
         m = C.c_size_t(0)
         self._chk(self._L.flimo_scan_get(self._h, out.ctypes.data, n, C.byref(m)))
         return out[:n]
+
+    def scan_fitness(self, x26s, max_dist=float("inf"), want_nn=False):
+        """flimo_scan_fitness: how well the resident scan fits the map at each pose of ``x26s`` [np, 26] (only pos and rot are read).
+        Per pose the nearest stored point of every scan point moved by it (``scan_to_world`` + ``knn_k(k=1, max_dist)``, on the GPU):
+        returns (inliers [np] int32: points that have one within the gate, sum_sqd [np] float64: the sum of their squared distances
+        [, nn_sqd [np, n] float32: the distance or -1, nn_idx [np, n]: the stored point's insertion index or -1])."""
+        return fitness_call(lambda *a: self._chk(self._L.flimo_scan_fitness(self._h, *a)), x26s, self.scan_size(), max_dist, want_nn)
+
+    def set_fitness_chunk(self, pairs):
+        """(pose, point) pairs per chunk of ``scan_fitness`` (flimo_set_fitness_chunk; 0: the default of 2^22)."""
+        self._chk(self._L.flimo_set_fitness_chunk(self._h, int(pairs)))
 
     def scan_voxel_filter(self, leaf: float) -> int:
         n = C.c_size_t(0)

@@ -41,7 +41,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -140,6 +140,7 @@ def load_host():
                                         C.c_void_p, C.c_void_p]
     L.flimo_loc_map_normals_range.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_scan_fitness.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -376,6 +377,17 @@ class Localizer:
         return _lib.normals_call(lambda *a: self._normals_chk(self._L.flimo_loc_map_normals_range(self._h, int(first), int(n), *a)),
                                  int(n), k, max_dist, min_pts, viewpoint, want)
 
+    def _fitness_chk(self, rc):
+        if rc != 0:
+            raise FlimoError(f"flimo_loc_scan_fitness failed ({rc})")
+
+    def scan_fitness(self, x26s, max_dist=float("inf"), want_nn=False):
+        """How well the scan of the last sweep (``pc2match()``, resident on the GPU) fits the map at each pose of ``x26s`` [np, 26]
+        (flimo_loc_scan_fitness): ``(inliers, sum_sqd[, nn_sqd, nn_idx])`` as ``HipCtx.scan_fitness``.  Waits for an insert or a crop
+        still running behind the last sweep; changes nothing."""
+        n = self.hip.scan_size()      # (the scan resident in the map's context; 0 when there is no map yet)
+        return _lib.fitness_call(lambda *a: self._fitness_chk(self._L.flimo_loc_scan_fitness(self._h, *a)), x26s, n, max_dist, want_nn)
+
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))
 
@@ -483,6 +495,13 @@ class LocalMapRule:
                                           C.byref(self.have), lo, hi)
         self.off = rc < 0
         return (lo, hi) if rc == 1 else None
+
+
+def fitness_cost(inliers, sum_sqd, n, max_dist):
+    """The truncated least-squares cost of pose hypotheses from ``scan_fitness``' two numbers: every scan point pays its squared
+    distance to the map, one without a neighbour inside the gate pays the gate's: sum_sqd + (n - inliers) * max_dist^2 (float64).
+    It is the one number that ranks hypotheses with different inlier counts; the lowest wins."""
+    return np.asarray(sum_sqd, np.float64) + (float(n) - np.asarray(inliers, np.float64)) * (float(max_dist) * float(max_dist))
 
 
 def eskf_update_fixed(x26, P, H, h, max_iters=3, limits=None, R=0.001, D=5.0):

@@ -54,6 +54,7 @@ struct flimo_ctx {
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
+  size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
   IndexTables idx;                 // the index of the main grid (GridView, flimo_types.h): tiles, directory, escapes, xstart
   GridView grid{};
@@ -2966,6 +2967,76 @@ extern "C" int flimo_scan_to_world(flimo_ctx* c, const double x26[26], float* ou
   HIPCHK(c, hipGetLastError());
   if (out && cap) return download_xyz(c, c->d_scan_world, std::min(cap, c->scan_n), out);
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return FLIMO_OK;
+}
+
+// ---- fitness of the resident scan under pose hypotheses (pcl::Registration::getFitnessScore over the map) ----------
+// kernels: flimo_knn_k.hip.  Chunks of whole poses, c->fitness_chunk (pose, point) pairs at most unless one pose alone has more:
+// per chunk the poses' matrices go up (pose_from_x26 on the host, as flimo_scan_to_world forms them), three launches (block search,
+// walk over the tiles, the reduction per pose), two numbers per pose -- and the slots, where asked for -- come back; device scratch
+// is the chunk's, whatever np.  Reads d_scan only: d_scan_world and the pass's buffers are left alone.
+extern "C" int flimo_scan_fitness(flimo_ctx* c, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
+                                  int32_t* nn_idx) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if ((np > 0 && !x26) || !inliers || !sum_sqd) return fail(c, FLIMO_ERR_INVALID, "scan fitness: null poses / inliers / sum_sqd");
+  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "scan fitness: max_dist must be >= 0 or INFINITY");
+  if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan fitness: the number of poses must be below 2^31");
+  for (size_t j = 0; j < np; j++)
+    for (int t = 0; t < 7; t++)
+      if (!std::isfinite(x26[26 * j + t])) return fail(c, FLIMO_ERR_INVALID, "scan fitness: pose %zu has a non-finite position or rotation", j);
+  if (np == 0) return FLIMO_OK;
+  const size_t n = c->scan_n;
+  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  if (n == 0 || !c->grid_valid || max_dist == 0.f) {      // an empty scan or map, a gate that admits nothing: every query is empty
+    for (size_t j = 0; j < np; j++) { inliers[j] = 0; sum_sqd[j] = 0.0; }
+    if (nn_sqd) for (size_t i = 0; i < np * n; i++) nn_sqd[i] = -1.f;
+    if (nn_idx) for (size_t i = 0; i < np * n; i++) nn_idx[i] = -1;
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  { const int rcf = flush_deskew(c); if (rcf) return rcf; }
+  // scratch of this call, released on every exit path
+  struct Scratch {
+    float* poses = nullptr; float* sqd = nullptr; int32_t* idx = nullptr; uint2* work = nullptr; unsigned* nwork = nullptr;
+    int32_t* inliers = nullptr; double* sum = nullptr;
+    ~Scratch() {
+      (void)hipFree(poses); (void)hipFree(sqd); (void)hipFree(idx); (void)hipFree(work); (void)hipFree(nwork); (void)hipFree(inliers);
+      (void)hipFree(sum);
+    }
+  } d;
+  // poses per chunk: whole poses, at least one; the kernels' pair numbers are 32-bit and a search launch has the poses as its grid's y
+  const size_t pairs_max = std::min<size_t>(std::max<size_t>(c->fitness_chunk, 1), (size_t)1 << 28);
+  const size_t m = std::min(np, std::min<size_t>(std::max<size_t>(pairs_max / n, 1), FIT_MAX_POSES));
+  HIPCHK(c, hipMalloc(&d.poses, m * 12 * sizeof(float)));
+  HIPCHK(c, hipMalloc(&d.sqd, m * n * sizeof(float)));
+  if (nn_idx) HIPCHK(c, hipMalloc(&d.idx, m * n * sizeof(int32_t)));
+  HIPCHK(c, hipMalloc(&d.work, m * n * sizeof(uint2)));
+  HIPCHK(c, hipMalloc(&d.nwork, sizeof(unsigned)));
+  HIPCHK(c, hipMalloc(&d.inliers, m * sizeof(int32_t)));
+  HIPCHK(c, hipMalloc(&d.sum, m * sizeof(double)));
+  std::vector<float> rt(m * 12);
+  for (size_t a = 0; a < np; a += m) {
+    const size_t k = std::min(m, np - a);
+    for (size_t j = 0; j < k; j++) {
+      PoseMats P;
+      pose_from_x26(x26 + 26 * (a + j), P);
+      memcpy(&rt[12 * j], P.RT, 12 * sizeof(float));
+    }
+    HIPCHK(c, hipMemcpyAsync(d.poses, rt.data(), k * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_scan_fitness(c->stream, c->grid, c->d_scan, (unsigned)n, d.poses, (unsigned)k, max_dist, d.sqd, d.idx, d.work, d.nwork,
+                                  d.inliers, d.sum));
+    HIPCHK(c, hipMemcpyAsync(inliers + a, d.inliers, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sum_sqd + a, d.sum, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (nn_sqd) HIPCHK(c, hipMemcpyAsync(nn_sqd + a * n, d.sqd, k * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nn_idx) HIPCHK(c, hipMemcpyAsync(nn_idx + a * n, d.idx, k * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    // (the next chunk's poses overwrite rt and d.poses: one wait per chunk)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return FLIMO_OK;
+}
+extern "C" int flimo_set_fitness_chunk(flimo_ctx* c, size_t pairs) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->fitness_chunk = pairs ? pairs : (size_t)1 << 22;
   return FLIMO_OK;
 }
 

@@ -276,5 +276,13 @@ hipError_t launch_knn_k(hipStream_t st, const GridView& G, const float4* map_raw
 hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, unsigned first, int nq, int k,
                                 float max_dist, int min_pts, const float* viewpoint, float4* normal, int32_t* cnt, double* centroid, double* cov,
                                 double* eig, double* mom, uint2* work, unsigned* nwork);
+// The same search with k = 1 for every (pose, point of the resident scan) pair of a chunk of poses (flimo_scan_fitness, flimo_c.h):
+// the world point is transform_kernel's, from poses [np][12] (the upper three rows of PoseMats::RT).  sqd [np][n]: the nearest
+// stored point's squared distance, -1 for an empty query; idx [np][n] (optional): its insertion index, -1; inliers / sum_sqd [np]:
+// the slots that hold a distance and their float64 sum in one fixed shape.  n * np <= 2^31, np <= FIT_MAX_POSES.  Scratch: work
+// ([np * n]), nwork.
+constexpr unsigned FIT_MAX_POSES = 65535;
+hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* scan, unsigned n, const float* poses, unsigned np, float max_dist,
+                               float* sqd, int32_t* idx, uint2* work, unsigned* nwork, int32_t* inliers, double* sum_sqd);
 
 }  // namespace flimo

@@ -658,6 +658,110 @@ __global__ __launch_bounds__(KK_BLOCK, 5) void knnk_normals_far_kernel(GridView 
   }
 }
 
+// ---- fitness of the resident scan under pose hypotheses (flimo_scan_fitness) ----------------------------------------------------
+// One query per (pose, scan point) pair: the world point is transform_kernel's (flimo_kernels.hip) float32
+// c0*x + (c1*y + (c2*z + c3)) from the pose's RT, the search is the one above with k = 1 and the gate.  A workgroup serves
+// FIT_QPB consecutive scan points of ONE pose, so the 12 floats of its RT are uniform over the wave.  The nearest key of a pair goes
+// into the pair's slot (sqd, -1.0f when the query is empty; the insertion index beside it when asked for): by the group when the
+// block search proves it, by the walk over the tiles otherwise (worklist, as knnk_normals_kernel).  A third launch, one workgroup
+// per pose, counts and sums the pose's n slots in ONE shape: thread t adds slots t, t + FIT_RED, ... in float64, then a tree over
+// the FIT_RED partials in shared memory.  No atomics on floating-point values: the bits of a pose's sum depend on its slots alone.
+constexpr int FIT_L = 8;                        // lanes per query: a list of one key; measured against 16 (profiles/scan_fitness/README.md)
+constexpr int FIT_QPB = KK_BLOCK / FIT_L;       // queries per workgroup
+constexpr int FIT_RED = 256;                    // threads of the reduction's workgroup
+constexpr unsigned FIT_MAX_GRID_X = 1u << 20;   // a search launch's grid is (workgroups of a pose, poses); a pose of more workgroups takes several launches
+
+struct FitArgs {
+  const float4* scan;    // the resident scan (body frame), [n]
+  const float* poses;    // the chunk's poses: [np][12], the upper three rows of RT (pose_from_x26)
+  unsigned n, np;        // points of the scan, poses of the chunk: n * np <= 2^31, np < 2^16 (the grid's y)
+  unsigned b0;           // the search launch's first workgroup of a pose
+  float r2;
+  kk_u64 gate_key;
+};
+
+__device__ __forceinline__ void fit_world(const FitArgs& A, unsigned pose, unsigned i, float& x, float& y, float& z) {
+  const float4 p = A.scan[i];
+  const float* M = A.poses + 12 * (size_t)pose;
+  x = M[0] * p.x + (M[1] * p.y + (M[2] * p.z + M[3]));
+  y = M[4] * p.x + (M[5] * p.y + (M[6] * p.z + M[7]));
+  z = M[8] * p.x + (M[9] * p.y + (M[10] * p.z + M[11]));
+}
+__device__ __forceinline__ void fit_store(size_t at, bool has, kk_u64 key, float* __restrict__ sqd, int32_t* __restrict__ idx) {
+  sqd[at] = has ? kk_key_dist(key) : -1.f;
+  if (idx) idx[at] = has ? (int32_t)(uint32_t)key : -1;
+}
+
+template <int L>
+__global__ __launch_bounds__(KK_BLOCK) void fit_search_kernel(GridView G, FitArgs A, float* __restrict__ sqd, int32_t* __restrict__ idx,
+                                                              uint2* __restrict__ work, unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63;
+  const int sub = lane & (L - 1);
+  const unsigned pose = blockIdx.y;
+  const size_t gi = ((size_t)A.b0 + blockIdx.x) * (KK_BLOCK / L) + threadIdx.x / (unsigned)L;
+  const bool live = gi < (size_t)A.n;
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  if (live) fit_world(A, pose, (unsigned)gi, gx, gy, gz);
+  kk_u64 mine;
+  unsigned long long cand = 0;
+  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, 1, A.r2, A.gate_key, mine, cand);
+  if (live && sub == 0) {      // (k = 1: the group's first lane holds the list)
+    const size_t at = (size_t)pose * (size_t)A.n + gi;
+    if (!proven) {
+      // (the candidate's distance, when there is one, bounds the true one: the walk's first bound)
+      const unsigned w = atomicAdd(nwork, 1u);
+      work[w] = make_uint2((unsigned)at, __float_as_uint(mine < A.gate_key ? kk_key_dist(mine) : A.r2));
+    }
+    fit_store(at, proven && mine < A.gate_key, mine, sqd, idx);
+  }
+}
+
+// the worklist's pairs, one wave per entry: knnk_far_kernel's walk, the same slot
+__global__ __launch_bounds__(KK_BLOCK, 5) void fit_far_kernel(GridView G, FitArgs A, float* __restrict__ sqd, int32_t* __restrict__ idx,
+                                                              const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int maxdim = grid_maxdim(G);
+  const int ndir = G.ntx * G.nty * G.ntz;
+  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
+  const size_t pairs = (size_t)A.n * (size_t)A.np;
+  const unsigned nw = (unsigned)min((size_t)*nwork, pairs);
+  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < nw; w += gridDim.x * (KK_BLOCK / 64)) {
+    const uint2 e = work[w];
+    const size_t at = min((size_t)e.x, pairs - 1);
+    float gx, gy, gz;
+    fit_world(A, (unsigned)(at / A.n), (unsigned)(at % A.n), gx, gy, gz);
+    kk_u64 mine;
+    unsigned long long cand = 0;
+    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, gx, gy, gz, lane, 1, __uint_as_float(e.y), A.gate_key, mine, cand);
+    if (lane == 0) fit_store(at, mine < A.gate_key, mine, sqd, idx);
+  }
+}
+
+// One workgroup per pose over its n slots: the number of slots that hold a distance and their float64 sum, in one fixed shape.
+__global__ __launch_bounds__(FIT_RED) void fit_reduce_kernel(const float* __restrict__ sqd, unsigned n, int32_t* __restrict__ inliers,
+                                                             double* __restrict__ sum_sqd) {
+  __shared__ double s_sum[FIT_RED];
+  __shared__ int s_cnt[FIT_RED];
+  const float* s = sqd + (size_t)blockIdx.x * (size_t)n;
+  double acc = 0.0;
+  int c = 0;
+  for (unsigned i = threadIdx.x; i < n; i += FIT_RED) {
+    const float v = s[i];
+    if (v >= 0.f) { acc = acc + (double)v; c++; }      // (an empty slot holds -1)
+  }
+  s_sum[threadIdx.x] = acc;
+  s_cnt[threadIdx.x] = c;
+  __syncthreads();
+  for (int o = FIT_RED / 2; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      s_sum[threadIdx.x] = s_sum[threadIdx.x] + s_sum[threadIdx.x + o];
+      s_cnt[threadIdx.x] += s_cnt[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { inliers[blockIdx.x] = s_cnt[0]; sum_sqd[blockIdx.x] = s_sum[0]; }
+}
+
 // lanes per query from k: a list of k keys needs k lanes
 int knnk_plan(int k) { return k <= 16 ? 16 : 64; }
 
@@ -701,6 +805,28 @@ hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4*
   const unsigned far_blocks = (unsigned)std::min<size_t>(4096, ((size_t)nq + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
   hipLaunchKernelGGL(knnk_normals_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
   hipLaunchKernelGGL(knnk_normals_finish_kernel, dim3((unsigned)(((size_t)nq + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, A, map_raw, mom, O);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* scan, unsigned n, const float* poses, unsigned np, float max_dist,
+                               float* sqd, int32_t* idx, uint2* work, unsigned* nwork, int32_t* inliers, double* sum_sqd) {
+  if (n == 0 || np == 0) return hipSuccess;
+  if ((unsigned long long)n * np > 0x80000000ull || np > FIT_MAX_POSES) return hipErrorInvalidValue;
+  FitArgs A;
+  A.scan = scan; A.poses = poses; A.n = n; A.np = np; A.b0 = 0;
+  A.r2 = max_dist * max_dist;                // one float32 product, as launch_knn_k's
+  uint32_t r2_bits;
+  memcpy(&r2_bits, &A.r2, sizeof r2_bits);
+  A.gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
+  hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  const size_t pairs = (size_t)n * np;
+  const unsigned bpp = (unsigned)(((size_t)n + FIT_QPB - 1) / FIT_QPB);      // workgroups per pose
+  for (; A.b0 < bpp; A.b0 += FIT_MAX_GRID_X)
+    hipLaunchKernelGGL((fit_search_kernel<FIT_L>), dim3(std::min(bpp - A.b0, FIT_MAX_GRID_X), np), dim3(KK_BLOCK), 0, st, G, A, sqd, idx, work, nwork);
+  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, (pairs + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
+  hipLaunchKernelGGL(fit_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, sqd, idx, work, nwork);
+  hipLaunchKernelGGL(fit_reduce_kernel, dim3(np), dim3(FIT_RED), 0, st, sqd, n, inliers, sum_sqd);
   return hipGetLastError();
 }
 

@@ -276,6 +276,21 @@ int flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, flo
   }
   return flimo_map_normals_range(c, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
 }
+int flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
+                           int32_t* nn_idx) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
+  if (!c) {                          // no map yet, and no resident scan: flimo_scan_fitness' own argument checks, then nothing per point
+    if ((np > 0 && !x26) || !inliers || !sum_sqd || std::isnan(max_dist) || max_dist < 0.f) return FLIMO_ERR_INVALID;
+    if (np >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
+    for (size_t j = 0; j < np; j++)
+      for (int t = 0; t < 7; t++)
+        if (!std::isfinite(x26[26 * j + t])) return FLIMO_ERR_INVALID;
+    for (size_t j = 0; j < np; j++) { inliers[j] = 0; sum_sqd[j] = 0.0; }
+    return FLIMO_OK;
+  }
+  return flimo_scan_fitness(c, x26, np, max_dist, inliers, sum_sqd, nn_sqd, nn_idx);
+}
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
 // the map insert that ends a scan runs on the Mapper's worker thread (Mapper::add_scan): wait for it / switch it off

@@ -494,6 +494,26 @@ int Mapper::normals_range(size_t first, size_t n, int k, float max_dist, int min
   return normals_run(nullptr, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
 }
 
+// fitness of the resident scan at pose hypotheses (an insert or a crop on the worker thread ends first)
+int Mapper::fitness(const double* x26, size_t np, float max_dist, std::vector<int32_t>& inliers, std::vector<double>& sum_sqd,
+                    std::vector<float>* nn_sqd, std::vector<int32_t>* nn_idx) {
+  sync();
+  inliers.clear(); sum_sqd.clear();
+  if (nn_sqd) nn_sqd->clear();
+  if (nn_idx) nn_idx->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (!x26 && np > 0) return FLIMO_ERR_INVALID;
+  if (np >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
+  const size_t n = flimo_scan_size(ctx_);
+  inliers.assign(np, 0); sum_sqd.assign(np, 0.0);
+  if (nn_sqd) nn_sqd->assign(np * n, -1.f);
+  if (nn_idx) nn_idx->assign(np * n, -1);
+  // (vectors of no element may hand out a null pointer, which the call rejects)
+  int32_t none_i = 0; double none_d = 0.0;
+  return flimo_scan_fitness(ctx_, x26, np, max_dist, np ? inliers.data() : &none_i, np ? sum_sqd.data() : &none_d,
+                            (nn_sqd && np && n) ? nn_sqd->data() : nullptr, (nn_idx && np && n) ? nn_idx->data() : nullptr);
+}
+
 void Mapper::add(pcl::PointCloud<PointType>::Ptr& pc, double time) {   // Mapper.cpp:88-96
   if (!pc || pc->points.size() < 1) return;
   sync();

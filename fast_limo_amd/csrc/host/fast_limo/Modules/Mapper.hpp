@@ -83,6 +83,13 @@ class fast_limo::Mapper {
   int normals_range(size_t first, size_t n, int k, float max_dist, int min_pts, const float* viewpoint, std::vector<float>& normal,
                     std::vector<int32_t>& cnt, std::vector<double>* centroid = nullptr, std::vector<double>* cov = nullptr,
                     std::vector<double>* eig = nullptr);
+  // How well the scan resident in this Mapper's context -- after Localizer::updatePointCloud: pc2match -- fits the map at each of np
+  // pose hypotheses x26 [np][26] (flimo_scan_fitness: what pcl::Registration::getFitnessScore computes for one pose).  inliers [np]:
+  // scan points whose nearest stored point is closer than max_dist (INFINITY: no gate); sum_sqd [np]: the float64 sum of their
+  // squared distances; nn_sqd / nn_idx [np][scan size] (optional): that distance (-1: none) and the stored point's insertion index.
+  // Returns a FLIMO_* code.
+  int fitness(const double* x26, size_t np, float max_dist, std::vector<int32_t>& inliers, std::vector<double>& sum_sqd,
+              std::vector<float>* nn_sqd = nullptr, std::vector<int32_t>* nn_idx = nullptr);
   void sync();                                  // wait for a running insert or crop (no-op when idle)
   void set_async(bool on) { sync(); async_ = on; }
   double last_insert_seconds() { sync(); return insert_seconds_; }

@@ -360,6 +360,33 @@ int flimo_match_fetch_H(flimo_ctx* ctx, double* H, double* h, size_t cap_rows, s
 /* ---- path exit: pcl::transformPointCloud(pc2match, state.get_RT()) + Mapper::add
  *      (Modules/Localizer.cpp:361-377).  world_xyz_out may be NULL. ---- */
 int flimo_scan_to_world(flimo_ctx* ctx, const double x26[26], float* world_xyz_out, size_t cap);
+/* ---- how well the resident scan fits the map at each of np pose hypotheses: what pcl::Registration::getFitnessScore computes
+ *      for one pose (nearest stored point of every transformed scan point, gated), for a batch of poses and without the world
+ *      points or the neighbours ever leaving the GPU ----
+ * x26 [np][26]: the poses; only pos (x26[j][0..2]) and rot (x26[j][3..6]) of a pose are read.  n = flimo_scan_size(ctx).
+ * w(j, i), the world point of resident scan point i under pose j, is the reference's s.get_RT() * bl4_point (Modules/Mapper.cpp:72)
+ * in float32: exactly point i of flimo_scan_to_world(ctx, x26[j], ..) -- the matrix of that call, the same
+ * c0*x + (c1*y + (c2*z + c3)), uncontracted --, i in the order of flimo_scan_get / flimo_scan_to_world.
+ * The neighbour of w(j, i) is exactly flimo_knn_k(w, k = 1, max_dist): same predicate (strict sqd < max_dist * max_dist, the
+ * square one float32 product; INFINITY: no gate), same unique order (float32 squared-distance bits, insertion index).
+ * Outputs, host memory:
+ *  - nn_sqd [np][n] (may be NULL): that squared distance, -1.0f when the query is empty (gated out, a NaN coordinate in w, an empty
+ *    map); nn_idx [np][n] (may be NULL): the insertion index, or -1.  Both bit-equal to flimo_knn_k.
+ *  - inliers [np]: the number of non-empty queries of pose j, exact.
+ *  - sum_sqd [np]: the float64 sum of their float32 sqd, taken in ONE fixed shape over the scan's slots (no floating-point
+ *    atomics): its bits depend on the scan, the map's points and pose j alone -- not on np, the other poses, how the call is cut
+ *    into chunks, the map's cell size or which path of the search finished a query -- and do not differ between two calls.
+ * The mean squared distance (sum_sqd / inliers: getFitnessScore's number) and any robust cost are the caller's arithmetic.
+ * FLIMO_OK with all inliers / sum_sqd 0 and all nn_sqd / nn_idx -1 for an empty map, an empty scan and max_dist == 0; np == 0
+ * returns FLIMO_OK and touches nothing.  FLIMO_ERR_INVALID: NULL ctx / x26 (np > 0) / inliers / sum_sqd, max_dist NaN or negative, a
+ * non-finite value among x26[j][0..6] of any pose.  FLIMO_ERR_TOO_LARGE: np >= 2^31; there is no limit on np * n.  The outputs are
+ * untouched on an error.
+ * A scan whose deskew still rides on the next launch is deskewed first (as flimo_scan_to_world does).  The call changes neither the
+ * resident scan nor the map nor the bits of a later pass.  Calling rules and cost as flimo_knn_k (no pass in flight; a pose that
+ * throws the scan kilometres from the map costs a look at the tile directory per point); device memory is taken per chunk of 2^22
+ * (pose, point) pairs -- whole poses --, not per call. */
+int flimo_scan_fitness(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t np, float max_dist, int32_t* inliers /* [np] */,
+                       double* sum_sqd /* [np] */, float* nn_sqd /* [np][n], may be NULL */, int32_t* nn_idx /* [np][n], may be NULL */);
 /* Both clouds the caller of Localizer::updatePointCloud may ask for (pc2match: body frame; final_scan: world frame of pose x26,
  * Localizer.cpp:361-371) in ONE round trip: packed float4 records (x, y, z, unused) in pinned memory owned by the context, valid
  * until the next flimo_scan_clouds on it.  *n = points in each. */

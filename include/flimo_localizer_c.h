@@ -94,6 +94,12 @@ int    flimo_loc_map_normals(flimo_loc* L, const float* q_xyz, size_t nq, int k,
                              float* normal, int32_t* cnt, double* centroid, double* cov, double* eig);
 int    flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3],
                                    float* normal, int32_t* cnt, double* centroid, double* cov, double* eig);
+/* How well the scan resident in the map's context -- after updatePointCloud: pc2match -- fits the Localizer's map at each of np pose
+ * hypotheses: flimo_scan_fitness (include/flimo_c.h: same arguments, same results, same error codes; n = the size of pc2match) on
+ * the map's context, after an insert or a crop still running behind the last sweep has ended.  A Localizer that has no map yet
+ * answers like an empty scan (all inliers and sums 0; nn_sqd / nn_idx have no element). */
+int    flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
+                              int32_t* nn_idx);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
