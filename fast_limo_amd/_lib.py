@@ -77,7 +77,7 @@ FRAME_DTYPE = np.dtype([
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
     "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_size", "flimo_scan_get",
+    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
@@ -120,6 +120,23 @@ def fitness_call(call, x26s, n, max_dist, want_nn):
     ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(C.c_double()))
     call(x.ctypes.data if m else None, m, float(max_dist), ptr(inliers), ptr(sum_sqd), ptr(nn_sqd), ptr(nn_idx))
     return (inliers, sum_sqd, nn_sqd, nn_idx) if want_nn else (inliers, sum_sqd)
+
+
+def linearize_call(call, x26s, n, k, max_dist, min_pts, max_curv, want_rows):
+    """The output arrays of flimo_scan_linearize / flimo_loc_scan_linearize and the call's arguments (``call`` takes them: x26, np, k,
+    max_dist, min_pts, max_curv, valid, H, g, cost, rows, pair_cnt); ``n``: the size of the resident scan.  Shared with
+    ``api.Localizer``.  Returns a dict: valid [np] int32, H [np, 21], g [np, 6], cost [np][, rows [np, n, 7], pair_cnt [np, n]]."""
+    x = np.ascontiguousarray(x26s, dtype=np.float64).reshape(-1, 26)
+    m = x.shape[0]
+    out = {"valid": np.zeros(m, np.int32), "H": np.zeros((m, 21)), "g": np.zeros((m, 6)), "cost": np.zeros(m)}
+    if want_rows:
+        out["rows"] = np.full((m, n, 7), np.nan)
+        out["pair_cnt"] = np.zeros((m, n), np.int32)
+    # (an array of no element may have no address; the call wants its required pointers non-null)
+    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(C.c_double()))
+    call(x.ctypes.data if m else None, m, int(k), float(max_dist), int(min_pts), float(max_curv), ptr(out["valid"]), ptr(out["H"]), ptr(out["g"]),
+         ptr(out["cost"]), ptr(out.get("rows")), ptr(out.get("pair_cnt")))
+    return out
 
 
 def hip_lib_path() -> str:
@@ -167,6 +184,9 @@ def load_hip():
     L.flimo_set_normals_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_scan_fitness.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_set_fitness_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_scan_linearize.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_set_linearize_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.flimo_scan_size.restype = C.c_size_t
     L.flimo_scan_size.argtypes = [vp]
@@ -416,6 +436,19 @@ class HipCtx:
     def set_fitness_chunk(self, pairs):
         """(pose, point) pairs per chunk of ``scan_fitness`` (flimo_set_fitness_chunk; 0: the default of 2^22)."""
         self._chk(self._L.flimo_set_fitness_chunk(self._h, int(pairs)))
+
+    def scan_linearize(self, x26s, k, max_dist, min_pts=3, max_curv=float("inf"), want_rows=False):
+        """flimo_scan_linearize: the point-to-plane normal equations of the resident scan against the map at each pose of ``x26s``
+        [np, 26] (only pos and rot are read).  Per pose and scan point the plane of ``normals(scan_to_world(x26), k, max_dist,
+        min_pts)``, gated by ``max_curv``; returns a dict: valid [np] int32, H [np, 21] (upper triangle, row-major), g [np, 6],
+        cost [np][, rows [np, n, 7]: J0..J5, d per pair, NaN when invalid; pair_cnt [np, n]].  The step solves H xi = -g
+        (``api.scan_align`` iterates it)."""
+        return linearize_call(lambda *a: self._chk(self._L.flimo_scan_linearize(self._h, *a)), x26s, self.scan_size(), k, max_dist, min_pts,
+                              max_curv, want_rows)
+
+    def set_linearize_chunk(self, pairs):
+        """(pose, point) pairs per chunk of ``scan_linearize`` (flimo_set_linearize_chunk; 0: the default of 2^20)."""
+        self._chk(self._L.flimo_set_linearize_chunk(self._h, int(pairs)))
 
     def scan_voxel_filter(self, leaf: float) -> int:
         n = C.c_size_t(0)

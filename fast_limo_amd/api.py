@@ -6,6 +6,7 @@ there is no Python compute path.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import numpy as np
 
@@ -41,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -141,6 +142,8 @@ def load_host():
     L.flimo_loc_map_normals_range.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_scan_fitness.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_scan_linearize.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -388,6 +391,18 @@ class Localizer:
         n = self.hip.scan_size()      # (the scan resident in the map's context; 0 when there is no map yet)
         return _lib.fitness_call(lambda *a: self._fitness_chk(self._L.flimo_loc_scan_fitness(self._h, *a)), x26s, n, max_dist, want_nn)
 
+    def _linearize_chk(self, rc):
+        if rc != 0:
+            raise FlimoError(f"flimo_loc_scan_linearize failed ({rc})")
+
+    def scan_linearize(self, x26s, k, max_dist, min_pts=3, max_curv=float("inf"), want_rows=False):
+        """The point-to-plane normal equations of the scan of the last sweep against the map at each pose of ``x26s`` [np, 26]
+        (flimo_loc_scan_linearize): the dict of ``HipCtx.scan_linearize``.  Waits for an insert or a crop still running behind the
+        last sweep; changes nothing."""
+        n = self.hip.scan_size()      # (the scan resident in the map's context; 0 when there is no map yet)
+        return _lib.linearize_call(lambda *a: self._linearize_chk(self._L.flimo_loc_scan_linearize(self._h, *a)), x26s, n, k, max_dist, min_pts,
+                                   max_curv, want_rows)
+
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))
 
@@ -502,6 +517,79 @@ def fitness_cost(inliers, sum_sqd, n, max_dist):
     distance to the map, one without a neighbour inside the gate pays the gate's: sum_sqd + (n - inliers) * max_dist^2 (float64).
     It is the one number that ranks hypotheses with different inlier counts; the lowest wins."""
     return np.asarray(sum_sqd, np.float64) + (float(n) - np.asarray(inliers, np.float64)) * (float(max_dist) * float(max_dist))
+
+
+ALIGN_RUNNING, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2      # scan_align's status per pose: ran every iteration / too few valid pairs / H not positive definite
+
+
+def sym6(H21):
+    """[.., 21] upper triangles (row-major 00, 01 .. 05, 11 .. 55) -> the symmetric [.., 6, 6] matrices."""
+    H21 = np.asarray(H21, np.float64)
+    iu = np.triu_indices(6)
+    M = np.zeros(H21.shape[:-1] + (6, 6))
+    M[..., iu[0], iu[1]] = H21
+    M[..., iu[1], iu[0]] = H21
+    return M
+
+
+def pose_retract(x26, xi):
+    """The body-frame update of scan_linearize's perturbation on one state vector, in float64: t += R(q) drho, q <- q (x) Exp(dphi),
+    renormalised (q = x26[3:7] as x y z w).  Everything else is copied through."""
+    x = np.array(x26, np.float64)
+    qx, qy, qz, qw = x[3:7] / np.linalg.norm(x[3:7])
+    R = np.array([[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw)],
+                  [2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw)],
+                  [2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)]])
+    x[0:3] += R @ np.asarray(xi[0:3], np.float64)
+    phi = np.asarray(xi[3:6], np.float64)
+    th = float(np.linalg.norm(phi))
+    half = 0.5 * th
+    s = 0.5 - th * th / 48.0 if th < 1e-6 else math.sin(half) / th      # sin(th / 2) / th
+    dx, dy, dz, dw = s * phi[0], s * phi[1], s * phi[2], math.cos(half)
+    q = np.array([qw * dx + qx * dw + qy * dz - qz * dy, qw * dy - qx * dz + qy * dw + qz * dx, qw * dz + qx * dy - qy * dx + qz * dw,
+                  qw * dw - qx * dx - qy * dy - qz * dz])
+    x[3:7] = q / np.linalg.norm(q)
+    return x
+
+
+def scan_align(obj, x26s, k=5, max_dist=1.0, min_pts=3, max_curv=0.05, iters=10, min_valid=30, linearize=None):
+    """Refine pose hypotheses of the resident scan against the map by point-to-plane Gauss-Newton: the GPU linearises
+    (``scan_linearize`` of ``obj``, a ``HipCtx`` or a ``Localizer``; or ``linearize(x26s)`` when given: any callable that returns
+    that dict), the host solves.  Per iteration ONE call for all poses still running, a Cholesky factorisation of every 6 x 6
+    system, H xi = -g, and ``pose_retract``.  A pose with fewer than ``min_valid`` valid pairs, or whose H is not positive definite,
+    stops where it is.  The loop ends by the iteration count alone: neighbour sets may flip from one pass to the next, so a step
+    norm need not fall below a tolerance.  Returns a dict: x26 [np, 26] (refined; all other entries copied through), valid and cost
+    [np] of each pose's LAST linearisation (at the pose before its last step), iters [np] (steps taken), status [np]
+    (ALIGN_RUNNING / ALIGN_FEW / ALIGN_SINGULAR)."""
+    if linearize is None:
+        linearize = lambda x: obj.scan_linearize(x, k, max_dist, min_pts, max_curv)
+    x = np.array(np.asarray(x26s, np.float64).reshape(-1, 26))
+    m = x.shape[0]
+    valid, cost = np.zeros(m, np.int32), np.zeros(m)
+    steps, status = np.zeros(m, np.int32), np.full(m, ALIGN_RUNNING, np.int32)
+    for _ in range(int(iters)):
+        run = np.nonzero(status == ALIGN_RUNNING)[0]
+        if run.size == 0:
+            break
+        lin = linearize(x[run])
+        valid[run], cost[run] = lin["valid"], lin["cost"]
+        H, g = sym6(lin["H"]), np.asarray(lin["g"], np.float64)
+        for a, j in enumerate(run):
+            if valid[j] < min_valid:
+                status[j] = ALIGN_FEW
+                continue
+            try:
+                Lc = np.linalg.cholesky(H[a])
+            except np.linalg.LinAlgError:
+                status[j] = ALIGN_SINGULAR
+                continue
+            xi = -np.linalg.solve(Lc.T, np.linalg.solve(Lc, g[a]))
+            if not np.all(np.isfinite(xi)):
+                status[j] = ALIGN_SINGULAR
+                continue
+            x[j] = pose_retract(x[j], xi)
+            steps[j] += 1
+    return dict(x26=x, valid=valid, cost=cost, iters=steps, status=status)
 
 
 def eskf_update_fixed(x26, P, H, h, max_iters=3, limits=None, R=0.001, D=5.0):

@@ -54,6 +54,7 @@ struct flimo_ctx {
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
+  size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
   IndexTables idx;                 // the index of the main grid (GridView, flimo_types.h): tiles, directory, escapes, xstart
@@ -3037,6 +3038,91 @@ extern "C" int flimo_scan_fitness(flimo_ctx* c, const double* x26, size_t np, fl
 extern "C" int flimo_set_fitness_chunk(flimo_ctx* c, size_t pairs) {
   if (!c) return FLIMO_ERR_INVALID;
   c->fitness_chunk = pairs ? pairs : (size_t)1 << 22;
+  return FLIMO_OK;
+}
+
+// ---- point-to-plane normal equations of the resident scan under pose hypotheses: one linearisation of a registration ----------
+// kernels: flimo_knn_k.hip.  Chunks of whole poses as flimo_scan_fitness, c->linearize_chunk pairs at most unless one pose alone
+// has more: per chunk the poses' matrices go up, five launches (block search, walk over the tiles, the plane and the row per
+// pair, the sums' two levels), 29 numbers per pose -- and the rows and counts, where asked for -- come back.  Reads d_scan only.
+extern "C" int flimo_scan_linearize(flimo_ctx* c, const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, int32_t* valid,
+                                    double* H, double* g, double* cost, double* rows, int32_t* pair_cnt) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if ((np > 0 && !x26) || !valid || !H || !g || !cost) return fail(c, FLIMO_ERR_INVALID, "scan linearize: null poses / valid / H / g / cost");
+  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "scan linearize: max_dist must be >= 0 or INFINITY");
+  if (std::isnan(max_curv) || max_curv < 0.f) return fail(c, FLIMO_ERR_INVALID, "scan linearize: max_curv must be >= 0 or INFINITY");
+  if (k < 3 || k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "scan linearize: k must be in 3..%d", FLIMO_KNN_MAX_K);
+  if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan linearize: the number of poses must be below 2^31");
+  for (size_t j = 0; j < np; j++)
+    for (int t = 0; t < 7; t++)
+      if (!std::isfinite(x26[26 * j + t])) return fail(c, FLIMO_ERR_INVALID, "scan linearize: pose %zu has a non-finite position or rotation", j);
+  if (np == 0) return FLIMO_OK;
+  const size_t n = c->scan_n;
+  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  if (n > ((size_t)1 << 28)) return fail(c, FLIMO_ERR_TOO_LARGE, "scan linearize: a scan of more than 2^28 points");
+  if (n == 0 || !c->grid_valid || max_dist == 0.f) {      // an empty scan or map, a gate that admits nothing: no pair has a plane
+    for (size_t j = 0; j < np; j++) { valid[j] = 0; cost[j] = 0.0; }
+    for (size_t i = 0; i < np * 21; i++) H[i] = 0.0;
+    for (size_t i = 0; i < np * 6; i++) g[i] = 0.0;
+    if (rows) for (size_t i = 0; i < np * n * 7; i++) rows[i] = std::numeric_limits<double>::quiet_NaN();
+    if (pair_cnt) for (size_t i = 0; i < np * n; i++) pair_cnt[i] = 0;
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  { const int rcf = flush_deskew(c); if (rcf) return rcf; }
+  // scratch of this call, released on every exit path
+  struct Scratch {
+    float* poses = nullptr; int32_t* cnt = nullptr; double* mom = nullptr; uint2* work = nullptr; unsigned* nwork = nullptr; double* rows = nullptr;
+    unsigned char* ok = nullptr; double* part = nullptr; int32_t* part_cnt = nullptr; double* sums = nullptr; int32_t* valid = nullptr;
+    ~Scratch() {
+      (void)hipFree(poses); (void)hipFree(cnt); (void)hipFree(mom); (void)hipFree(work); (void)hipFree(nwork); (void)hipFree(rows); (void)hipFree(ok);
+      (void)hipFree(part); (void)hipFree(part_cnt); (void)hipFree(sums); (void)hipFree(valid);
+    }
+  } d;
+  // poses per chunk: whole poses, at least one; the kernels' pair numbers are 32-bit and a search launch has the poses as its grid's y
+  const size_t pairs_max = std::min<size_t>(std::max<size_t>(c->linearize_chunk, 1), (size_t)1 << 28);
+  const size_t m = std::min(np, std::min<size_t>(std::max<size_t>(pairs_max / n, 1), FIT_MAX_POSES));
+  const size_t nseg = scan_linearize_segments((unsigned)n);
+  HIPCHK(c, hipMalloc(&d.poses, m * 12 * sizeof(float)));
+  HIPCHK(c, hipMalloc(&d.cnt, m * n * sizeof(int32_t)));
+  HIPCHK(c, hipMalloc(&d.mom, m * n * 9 * sizeof(double)));
+  HIPCHK(c, hipMalloc(&d.work, m * n * sizeof(uint2)));
+  HIPCHK(c, hipMalloc(&d.nwork, sizeof(unsigned)));
+  HIPCHK(c, hipMalloc(&d.rows, m * n * 7 * sizeof(double)));
+  HIPCHK(c, hipMalloc(&d.ok, m * n));
+  HIPCHK(c, hipMalloc(&d.part, m * nseg * 28 * sizeof(double)));
+  HIPCHK(c, hipMalloc(&d.part_cnt, m * nseg * sizeof(int32_t)));
+  HIPCHK(c, hipMalloc(&d.sums, m * 28 * sizeof(double)));
+  HIPCHK(c, hipMalloc(&d.valid, m * sizeof(int32_t)));
+  std::vector<float> rt(m * 12);
+  std::vector<double> sums(m * 28);
+  for (size_t a = 0; a < np; a += m) {
+    const size_t kk = std::min(m, np - a);
+    for (size_t j = 0; j < kk; j++) {
+      PoseMats P;
+      pose_from_x26(x26 + 26 * (a + j), P);
+      memcpy(&rt[12 * j], P.RT, 12 * sizeof(float));
+    }
+    HIPCHK(c, hipMemcpyAsync(d.poses, rt.data(), kk * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_scan_linearize(c->stream, c->grid, c->d_map_raw, c->d_scan, (unsigned)n, d.poses, (unsigned)kk, k, max_dist, min_pts, max_curv,
+                                    d.cnt, d.mom, d.work, d.nwork, d.rows, d.ok, d.part, d.part_cnt, d.sums, d.valid));
+    HIPCHK(c, hipMemcpyAsync(valid + a, d.valid, kk * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums.data(), d.sums, kk * 28 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (rows) HIPCHK(c, hipMemcpyAsync(rows + a * n * 7, d.rows, kk * n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (pair_cnt) HIPCHK(c, hipMemcpyAsync(pair_cnt + a * n, d.cnt, kk * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    // (the next chunk's poses overwrite rt and d.poses: one wait per chunk)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t j = 0; j < kk; j++) {
+      memcpy(H + 21 * (a + j), &sums[28 * j], 21 * sizeof(double));
+      memcpy(g + 6 * (a + j), &sums[28 * j + 21], 6 * sizeof(double));
+      cost[a + j] = sums[28 * j + 27];
+    }
+  }
+  return FLIMO_OK;
+}
+extern "C" int flimo_set_linearize_chunk(flimo_ctx* c, size_t pairs) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->linearize_chunk = pairs ? pairs : (size_t)1 << 20;
   return FLIMO_OK;
 }
 

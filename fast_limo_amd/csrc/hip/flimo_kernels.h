@@ -285,4 +285,14 @@ constexpr unsigned FIT_MAX_POSES = 65535;
 hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* scan, unsigned n, const float* poses, unsigned np, float max_dist,
                                float* sqd, int32_t* idx, uint2* work, unsigned* nwork, int32_t* inliers, double* sum_sqd);
 
+// The normals' search for every (pose, point of the resident scan) pair of a chunk of poses, finished into the pair's
+// point-to-plane row {J0..J5, d} and the per-pose sums of the normal equations (flimo_scan_linearize, flimo_c.h).  sums [np][28]:
+// the 21 upper-triangle sums of H, the 6 of g, the cost; valid [np].  n * np <= 2^28, np <= FIT_MAX_POSES.
+// Scratch per pair: cnt (4 B), mom (72 B), work (8 B), rows (56 B), ok (1 B); per pose and segment of the scan
+// (scan_linearize_segments(n) of them): part (28 doubles), part_cnt; nwork (one counter).
+unsigned scan_linearize_segments(unsigned n);
+hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4* map_raw, const float4* scan, unsigned n, const float* poses,
+                                 unsigned np, int k, float max_dist, int min_pts, float max_curv, int32_t* cnt, double* mom, uint2* work,
+                                 unsigned* nwork, double* rows, unsigned char* ok, double* part, int32_t* part_cnt, double* sums, int32_t* valid);
+
 }  // namespace flimo

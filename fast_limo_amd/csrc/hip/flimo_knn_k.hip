@@ -500,6 +500,39 @@ __device__ __forceinline__ void kk_jacobi_rot(double& app, double& aqq, double& 
 constexpr int KK_JACOBI_SWEEPS = 12;
 __device__ __forceinline__ void kk_swap_if(bool c, double& a, double& b) { const double x = c ? b : a, y = c ? a : b; a = x; b = y; }
 
+// The plane of a symmetric 3 x 3 covariance: a cyclic Jacobi until the off-diagonal is exactly 0, the eigenvalues in ascending order
+// (on a tie the lower column first), the smallest one's unit vector, oriented.  has_vp: towards the viewpoint, (tvx, tvy, tvz) being
+// viewpoint - query; else the component of largest magnitude (the lowest axis of equal ones) made positive.  Shared by every
+// kernel that ends a neighbourhood in a plane: their bits are the same by construction.
+__device__ __forceinline__ void kk_plane(double a00, double a01, double a02, double a11, double a12, double a22, bool has_vp, double tvx, double tvy,
+                                         double tvz, double& l0, double& l1, double& l2, double& nx, double& ny, double& nz) {
+  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+  for (int sweep = 0; sweep < KK_JACOBI_SWEEPS; sweep++) {
+    if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
+    kk_jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+    kk_jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+    kk_jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+  }
+  // ascending eigenvalues; on a tie the lower column first.  Only the smallest one's vector is kept.
+  l0 = a00; l1 = a11; l2 = a22;
+  const bool s01 = l1 < l0;
+  kk_swap_if(s01, l0, l1); kk_swap_if(s01, v00, v01); kk_swap_if(s01, v10, v11); kk_swap_if(s01, v20, v21);
+  const bool s12 = l2 < l1;
+  kk_swap_if(s12, l1, l2); kk_swap_if(s12, v01, v02); kk_swap_if(s12, v11, v12); kk_swap_if(s12, v21, v22);
+  const bool t01 = l1 < l0;
+  kk_swap_if(t01, l0, l1); kk_swap_if(t01, v00, v01); kk_swap_if(t01, v10, v11); kk_swap_if(t01, v20, v21);
+  nx = v00; ny = v10; nz = v20;
+  bool flip;
+  if (has_vp) {
+    flip = nx * tvx + ny * tvy + nz * tvz < 0.0;
+  } else {
+    const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+    const double big = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
+    flip = big < 0.0;
+  }
+  if (flip) { nx = -nx; ny = -ny; nz = -nz; }
+}
+
 struct NormalsOut {
   float4* normal;        // [n] nx ny nz curvature
   int32_t* cnt;          // [n]
@@ -576,31 +609,8 @@ __global__ __launch_bounds__(KK_BLOCK) void knnk_normals_finish_kernel(NormalsAr
     double* C = O.cov + 6 * (size_t)q;
     C[0] = enough ? a00 : nan; C[1] = enough ? a01 : nan; C[2] = enough ? a02 : nan; C[3] = enough ? a11 : nan; C[4] = enough ? a12 : nan; C[5] = enough ? a22 : nan;
   }
-  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-  for (int sweep = 0; sweep < KK_JACOBI_SWEEPS; sweep++) {
-    if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
-    kk_jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
-    kk_jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
-    kk_jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
-  }
-  // ascending eigenvalues; on a tie the lower column first.  Only the smallest one's vector is kept.
-  double l0 = a00, l1 = a11, l2 = a22;
-  const bool s01 = l1 < l0;
-  kk_swap_if(s01, l0, l1); kk_swap_if(s01, v00, v01); kk_swap_if(s01, v10, v11); kk_swap_if(s01, v20, v21);
-  const bool s12 = l2 < l1;
-  kk_swap_if(s12, l1, l2); kk_swap_if(s12, v01, v02); kk_swap_if(s12, v11, v12); kk_swap_if(s12, v21, v22);
-  const bool t01 = l1 < l0;
-  kk_swap_if(t01, l0, l1); kk_swap_if(t01, v00, v01); kk_swap_if(t01, v10, v11); kk_swap_if(t01, v20, v21);
-  double nx = v00, ny = v10, nz = v20;
-  bool flip;
-  if (A.has_vp) {
-    flip = nx * ((double)A.vx - qx) + ny * ((double)A.vy - qy) + nz * ((double)A.vz - qz) < 0.0;
-  } else {
-    const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
-    const double big = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
-    flip = big < 0.0;
-  }
-  if (flip) { nx = -nx; ny = -ny; nz = -nz; }
+  double l0, l1, l2, nx, ny, nz;
+  kk_plane(a00, a01, a02, a11, a12, a22, A.has_vp != 0, (double)A.vx - qx, (double)A.vy - qy, (double)A.vz - qz, l0, l1, l2, nx, ny, nz);
   const double tr = l0 + l1 + l2;
   const double curv = tr == 0.0 ? 0.0 : l0 / tr;
   const float fn = __int_as_float(0x7fc00000);
@@ -762,6 +772,181 @@ __global__ __launch_bounds__(FIT_RED) void fit_reduce_kernel(const float* __rest
   if (threadIdx.x == 0) { inliers[blockIdx.x] = s_cnt[0]; sum_sqd[blockIdx.x] = s_sum[0]; }
 }
 
+// ---- point-to-plane normal equations of the resident scan under pose hypotheses (flimo_scan_linearize) --------------------------
+// One query per (pose, scan point) pair, the world point as above.  The search is knnk_normals_kernel's for any k, a workgroup
+// serving KK_BLOCK / L consecutive scan points of ONE pose as fit_search_kernel does; the pair's moments (72 B) and count go to the
+// chunk's scratch, a pair the block search cannot prove to the worklist and the walk over the tiles.  A third launch, one THREAD per
+// pair, runs kk_plane on the moments -- flimo_map_normals' plane of the query w, bit for bit -- and writes the pair's row
+// {J0..J5, d} and its validity; every term is float64 in the association flimo_c.h states.  The sums have two levels, both of one
+// fixed shape that depends on n alone:
+//   level 1  the scan's slots are cut into segments of LIN_SEG; one workgroup of LIN_RED threads per (segment, pose): thread t adds
+//            the 28 products of slots t, t + LIN_RED, ... of its segment in ascending order (an invalid slot adds +0.0), a butterfly
+//            over the 64 lanes of each wave, then ((wave 0 + wave 1) + (wave 2 + wave 3))
+//   level 2  one thread per (pose, number) adds the pose's segment partials in ascending order of the segment
+// No atomics on floating-point values.
+constexpr int LIN_RED = 256;                    // threads of a level-1 workgroup
+constexpr int LIN_SEG = 4096;                   // slots of a segment: 16 per thread
+constexpr int LIN_NUM = 28;                     // 21 of H, 6 of g, the cost
+
+struct LinArgs {
+  FitArgs F;             // scan, poses, n, np, b0, r2, gate_key
+  NormalsArgs N;         // k, need, gate_key (has_vp = 0; the queries are the pairs' world points)
+  double max_curv;
+};
+
+__device__ __forceinline__ void lin_worklist(bool live, int sub, size_t at, kk_u64 kth, const NormalsArgs& N, uint2* __restrict__ work,
+                                             unsigned* __restrict__ nwork) {
+  if (live && sub == 0) {
+    const unsigned w = atomicAdd(nwork, 1u);
+    work[w] = make_uint2((unsigned)at, __float_as_uint(kth < N.gate_key ? kk_key_dist(kth) : N.r2));
+  }
+}
+
+template <int L>
+__global__ __launch_bounds__(KK_BLOCK) void lin_search_kernel(GridView G, LinArgs A, const float4* __restrict__ map_raw, int32_t* __restrict__ cnt,
+                                                              double* __restrict__ mom, uint2* __restrict__ work, unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63;
+  const int sub = lane & (L - 1);
+  const unsigned pose = blockIdx.y;
+  const size_t gi = ((size_t)A.F.b0 + blockIdx.x) * (KK_BLOCK / L) + threadIdx.x / (unsigned)L;
+  const bool live = gi < (size_t)A.F.n;
+  const size_t at = live ? (size_t)pose * (size_t)A.F.n + gi : 0;
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  if (live) fit_world(A.F, pose, (unsigned)gi, gx, gy, gz);
+  kk_u64 mine;
+  unsigned long long cand = 0;
+  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, A.N.k, A.N.r2, A.N.gate_key, mine, cand);
+  if (!proven) lin_worklist(live, sub, at, __shfl(mine, A.N.k - 1, L), A.N, work, nwork);
+  knnk_moments<L>(A.N, lane, (int)at, live && proven, mine, gx, gy, gz, map_raw, cnt, mom);
+}
+
+// the worklist's pairs, one wave per entry: knnk_far_kernel's walk, the same end
+__global__ __launch_bounds__(KK_BLOCK, 5) void lin_far_kernel(GridView G, LinArgs A, const float4* __restrict__ map_raw, int32_t* __restrict__ cnt,
+                                                              double* __restrict__ mom, const uint2* __restrict__ work,
+                                                              const unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int maxdim = grid_maxdim(G);
+  const int ndir = G.ntx * G.nty * G.ntz;
+  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
+  const size_t pairs = (size_t)A.F.n * (size_t)A.F.np;
+  const unsigned nw = (unsigned)min((size_t)*nwork, pairs);
+  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < nw; w += gridDim.x * (KK_BLOCK / 64)) {
+    const uint2 e = work[w];
+    const size_t at = min((size_t)e.x, pairs - 1);
+    float gx, gy, gz;
+    fit_world(A.F, (unsigned)(at / A.F.n), (unsigned)(at % A.F.n), gx, gy, gz);
+    kk_u64 mine;
+    unsigned long long cand = 0;
+    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, gx, gy, gz, lane, A.N.k, __uint_as_float(e.y), A.N.gate_key, mine, cand);
+    knnk_moments<64>(A.N, lane, (int)at, true, mine, gx, gy, gz, map_raw, cnt, mom);
+  }
+}
+
+// One thread per pair, after both searches: the plane as knnk_normals_finish_kernel forms it, the validity, the row.
+__global__ __launch_bounds__(KK_BLOCK) void lin_finish_kernel(LinArgs A, const int32_t* __restrict__ cnt, const double* __restrict__ mom,
+                                                              double* __restrict__ rows, unsigned char* __restrict__ ok) {
+  const size_t at = (size_t)blockIdx.x * KK_BLOCK + threadIdx.x;
+  if (at >= (size_t)A.F.n * (size_t)A.F.np) return;
+  const unsigned pose = (unsigned)(at / A.F.n), i = (unsigned)(at % A.F.n);
+  float gx, gy, gz;
+  fit_world(A.F, pose, i, gx, gy, gz);
+  const double wx = (double)gx, wy = (double)gy, wz = (double)gz;
+  const int c = cnt[at];
+  const bool enough = c >= A.N.need;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double* M = mom + (size_t)KK_MOM * at;
+  const double n = (double)c;
+  double mx = 0.0, my = 0.0, mz = 0.0, a00 = 1.0, a01 = 0.0, a02 = 0.0, a11 = 1.0, a12 = 0.0, a22 = 1.0;      // (too few: nothing to rotate)
+  if (enough) {
+    mx = M[0]; my = M[1]; mz = M[2];
+    a00 = M[3] / n; a01 = M[4] / n; a02 = M[5] / n; a11 = M[6] / n; a12 = M[7] / n; a22 = M[8] / n;
+  }
+  double l0, l1, l2, nx, ny, nz;
+  kk_plane(a00, a01, a02, a11, a12, a22, false, 0.0, 0.0, 0.0, l0, l1, l2, nx, ny, nz);
+  const double tr = l0 + l1 + l2;
+  const double curv = tr == 0.0 ? 0.0 : l0 / tr;
+  const bool valid = enough && curv <= A.max_curv;
+  const double cx = wx + mx, cy = wy + my, cz = wz + mz;      // the centroid as flimo_map_normals returns it
+  const double d = nx * (wx - cx) + (ny * (wy - cy) + nz * (wz - cz));
+  const float* R = A.F.poses + 12 * (size_t)pose;
+  const double a0 = (double)R[0] * nx + ((double)R[4] * ny + (double)R[8] * nz), a1 = (double)R[1] * nx + ((double)R[5] * ny + (double)R[9] * nz),
+               a2 = (double)R[2] * nx + ((double)R[6] * ny + (double)R[10] * nz);
+  const float4 p4 = A.F.scan[i];
+  const double px = (double)p4.x, py = (double)p4.y, pz = (double)p4.z;
+  const double b0 = py * a2 - pz * a1, b1 = pz * a0 - px * a2, b2 = px * a1 - py * a0;
+  double* Rw = rows + (size_t)7 * at;
+  Rw[0] = valid ? a0 : nan; Rw[1] = valid ? a1 : nan; Rw[2] = valid ? a2 : nan; Rw[3] = valid ? b0 : nan; Rw[4] = valid ? b1 : nan;
+  Rw[5] = valid ? b2 : nan; Rw[6] = valid ? d : nan;
+  ok[at] = valid ? 1 : 0;
+}
+
+// level 1: workgroup (segment, pose) over the slots [seg * LIN_SEG, min(n, (seg + 1) * LIN_SEG)) of its pose
+__global__ __launch_bounds__(LIN_RED) void lin_reduce_kernel(const double* __restrict__ rows, const unsigned char* __restrict__ ok, unsigned n,
+                                                             unsigned nseg, double* __restrict__ part, int32_t* __restrict__ part_cnt) {
+  __shared__ double s_sum[LIN_RED / 64][LIN_NUM];
+  __shared__ int s_cnt[LIN_RED / 64];
+  const unsigned seg = blockIdx.x, pose = blockIdx.y;
+  const size_t base = (size_t)pose * (size_t)n;
+  const unsigned end = min(n, (seg + 1u) * (unsigned)LIN_SEG);
+  double acc[LIN_NUM];
+#pragma unroll
+  for (int t = 0; t < LIN_NUM; t++) acc[t] = 0.0;
+  int c = 0;
+  for (unsigned i = seg * (unsigned)LIN_SEG + threadIdx.x; i < end; i += LIN_RED) {
+    const bool v = ok[base + i] != 0;
+    const double* Rw = rows + (size_t)7 * (base + i);
+    double J[7];
+#pragma unroll
+    for (int t = 0; t < 7; t++) J[t] = Rw[t];
+    int t = 0;
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+      for (int b = a; b < 6; b++) { acc[t] = acc[t] + (v ? J[a] * J[b] : 0.0); t++; }
+#pragma unroll
+    for (int a = 0; a < 6; a++) acc[21 + a] = acc[21 + a] + (v ? J[a] * J[6] : 0.0);
+    acc[27] = acc[27] + (v ? J[6] * J[6] : 0.0);
+    c += v ? 1 : 0;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int t = 0; t < LIN_NUM; t++) {
+    double v = acc[t];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
+    acc[t] = v;
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) {
+#pragma unroll
+    for (int t = 0; t < LIN_NUM; t++) s_sum[wave][t] = acc[t];
+    s_cnt[wave] = c;
+  }
+  __syncthreads();
+  const size_t slot = (size_t)pose * (size_t)nseg + seg;
+  if (threadIdx.x < LIN_NUM) part[slot * LIN_NUM + threadIdx.x] = (s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x]) + (s_sum[2][threadIdx.x] + s_sum[3][threadIdx.x]);
+  if (threadIdx.x == 0) part_cnt[slot] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+}
+
+// level 2: thread (pose, number) adds the pose's segment partials in ascending order; sums: [np][LIN_NUM]
+__global__ __launch_bounds__(KK_BLOCK) void lin_final_kernel(const double* __restrict__ part, const int32_t* __restrict__ part_cnt, unsigned np,
+                                                             unsigned nseg, double* __restrict__ sums, int32_t* __restrict__ valid) {
+  const size_t g = (size_t)blockIdx.x * KK_BLOCK + threadIdx.x;
+  if (g >= (size_t)np * (LIN_NUM + 1)) return;
+  const size_t pose = g / (LIN_NUM + 1);
+  const int t = (int)(g % (LIN_NUM + 1));
+  if (t == LIN_NUM) {
+    int c = 0;
+    for (unsigned s = 0; s < nseg; s++) c += part_cnt[pose * nseg + s];
+    valid[pose] = c;
+  } else {
+    double v = 0.0;
+    for (unsigned s = 0; s < nseg; s++) v = v + part[(pose * nseg + s) * LIN_NUM + t];
+    sums[pose * LIN_NUM + t] = v;
+  }
+}
+
 // lanes per query from k: a list of k keys needs k lanes
 int knnk_plan(int k) { return k <= 16 ? 16 : 64; }
 
@@ -827,6 +1012,45 @@ hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* 
   const unsigned far_blocks = (unsigned)std::min<size_t>(4096, (pairs + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
   hipLaunchKernelGGL(fit_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, sqd, idx, work, nwork);
   hipLaunchKernelGGL(fit_reduce_kernel, dim3(np), dim3(FIT_RED), 0, st, sqd, n, inliers, sum_sqd);
+  return hipGetLastError();
+}
+
+unsigned scan_linearize_segments(unsigned n) { return (unsigned)(((size_t)n + LIN_SEG - 1) / LIN_SEG); }
+
+hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4* map_raw, const float4* scan, unsigned n, const float* poses,
+                                 unsigned np, int k, float max_dist, int min_pts, float max_curv, int32_t* cnt, double* mom, uint2* work,
+                                 unsigned* nwork, double* rows, unsigned char* ok, double* part, int32_t* part_cnt, double* sums, int32_t* valid) {
+  if (n == 0 || np == 0) return hipSuccess;
+  if ((unsigned long long)n * np > 0x10000000ull || np > FIT_MAX_POSES || k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
+  LinArgs A;
+  A.F.scan = scan; A.F.poses = poses; A.F.n = n; A.F.np = np; A.F.b0 = 0;
+  A.F.r2 = max_dist * max_dist;              // one float32 product, as launch_knn_k's
+  uint32_t r2_bits;
+  memcpy(&r2_bits, &A.F.r2, sizeof r2_bits);
+  A.F.gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
+  A.N.qxyz = nullptr; A.N.first = 0; A.N.nq = 0; A.N.k = k; A.N.need = std::max(3, min_pts);
+  A.N.r2 = A.F.r2; A.N.gate_key = A.F.gate_key;
+  A.N.vx = A.N.vy = A.N.vz = 0.f; A.N.has_vp = 0;
+  A.max_curv = (double)max_curv;
+  hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  const size_t pairs = (size_t)n * np;
+  const int L = knnk_plan(k);
+  const unsigned qpb = (unsigned)(KK_BLOCK / L);
+  const unsigned bpp = (unsigned)(((size_t)n + qpb - 1) / qpb);      // workgroups per pose
+  for (; A.F.b0 < bpp; A.F.b0 += FIT_MAX_GRID_X) {
+    const dim3 grid(std::min(bpp - A.F.b0, FIT_MAX_GRID_X), np);
+    if (L == 16) hipLaunchKernelGGL((lin_search_kernel<16>), grid, dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
+    else hipLaunchKernelGGL((lin_search_kernel<64>), grid, dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
+  }
+  A.F.b0 = 0;
+  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, (pairs + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
+  hipLaunchKernelGGL(lin_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
+  hipLaunchKernelGGL(lin_finish_kernel, dim3((unsigned)((pairs + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, A, cnt, mom, rows, ok);
+  const unsigned nseg = scan_linearize_segments(n);
+  hipLaunchKernelGGL(lin_reduce_kernel, dim3(nseg, np), dim3(LIN_RED), 0, st, rows, ok, n, nseg, part, part_cnt);
+  hipLaunchKernelGGL(lin_final_kernel, dim3((unsigned)(((size_t)np * (LIN_NUM + 1) + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, part, part_cnt,
+                     np, nseg, sums, valid);
   return hipGetLastError();
 }
 

@@ -291,6 +291,25 @@ int flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float max
   }
   return flimo_scan_fitness(c, x26, np, max_dist, inliers, sum_sqd, nn_sqd, nn_idx);
 }
+int flimo_loc_scan_linearize(flimo_loc* L, const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, int32_t* valid, double* H,
+                             double* g, double* cost, double* rows, int32_t* pair_cnt) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
+  if (!c) {                          // no map yet, and no resident scan: flimo_scan_linearize's own argument checks, then nothing per point
+    if ((np > 0 && !x26) || !valid || !H || !g || !cost || std::isnan(max_dist) || max_dist < 0.f || std::isnan(max_curv) || max_curv < 0.f)
+      return FLIMO_ERR_INVALID;
+    if (k < 3 || k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
+    if (np >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
+    for (size_t j = 0; j < np; j++)
+      for (int t = 0; t < 7; t++)
+        if (!std::isfinite(x26[26 * j + t])) return FLIMO_ERR_INVALID;
+    for (size_t j = 0; j < np; j++) { valid[j] = 0; cost[j] = 0.0; }
+    for (size_t i = 0; i < np * 21; i++) H[i] = 0.0;
+    for (size_t i = 0; i < np * 6; i++) g[i] = 0.0;
+    return FLIMO_OK;
+  }
+  return flimo_scan_linearize(c, x26, np, k, max_dist, min_pts, max_curv, valid, H, g, cost, rows, pair_cnt);
+}
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
 // the map insert that ends a scan runs on the Mapper's worker thread (Mapper::add_scan): wait for it / switch it off

@@ -514,6 +514,28 @@ int Mapper::fitness(const double* x26, size_t np, float max_dist, std::vector<in
                             (nn_sqd && np && n) ? nn_sqd->data() : nullptr, (nn_idx && np && n) ? nn_idx->data() : nullptr);
 }
 
+// one linearisation of the resident scan at pose hypotheses (an insert or a crop on the worker thread ends first)
+int Mapper::linearize(const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, std::vector<int32_t>& valid,
+                      std::vector<double>& H, std::vector<double>& g, std::vector<double>& cost, std::vector<double>* rows,
+                      std::vector<int32_t>* pair_cnt) {
+  sync();
+  valid.clear(); H.clear(); g.clear(); cost.clear();
+  if (rows) rows->clear();
+  if (pair_cnt) pair_cnt->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (!x26 && np > 0) return FLIMO_ERR_INVALID;
+  if (np >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
+  const size_t n = flimo_scan_size(ctx_);
+  valid.assign(np, 0); H.assign(np * 21, 0.0); g.assign(np * 6, 0.0); cost.assign(np, 0.0);
+  if (rows) rows->assign(np * n * 7, (double)NAN);
+  if (pair_cnt) pair_cnt->assign(np * n, 0);
+  // (vectors of no element may hand out a null pointer, which the call rejects)
+  int32_t none_i = 0; double none_d = 0.0;
+  return flimo_scan_linearize(ctx_, x26, np, k, max_dist, min_pts, max_curv, np ? valid.data() : &none_i, np ? H.data() : &none_d,
+                              np ? g.data() : &none_d, np ? cost.data() : &none_d, (rows && np && n) ? rows->data() : nullptr,
+                              (pair_cnt && np && n) ? pair_cnt->data() : nullptr);
+}
+
 void Mapper::add(pcl::PointCloud<PointType>::Ptr& pc, double time) {   // Mapper.cpp:88-96
   if (!pc || pc->points.size() < 1) return;
   sync();

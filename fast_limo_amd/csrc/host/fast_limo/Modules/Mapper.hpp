@@ -90,6 +90,15 @@ class fast_limo::Mapper {
   // Returns a FLIMO_* code.
   int fitness(const double* x26, size_t np, float max_dist, std::vector<int32_t>& inliers, std::vector<double>& sum_sqd,
               std::vector<float>* nn_sqd = nullptr, std::vector<int32_t>* nn_idx = nullptr);
+  // One linearisation of a point-to-plane registration of that scan at each of np pose hypotheses (flimo_scan_linearize): per pose
+  // the plane of every moved scan point's k nearest stored points (gate max_dist, at least max(3, min_pts) of them, curvature at
+  // most max_curv) and the sums of the 6 x 6 normal equations over the valid pairs.  valid [np]; H [np][21]: the upper triangle,
+  // row-major; g [np][6]; cost [np]; rows [np][scan size][7] (optional): J0..J5, d per pair, NaN when invalid; pair_cnt
+  // [np][scan size] (optional): neighbours per pair.  The step solves H xi = -g, xi = (drho, dphi) in the body frame.  Returns a
+  // FLIMO_* code.
+  int linearize(const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, std::vector<int32_t>& valid,
+                std::vector<double>& H, std::vector<double>& g, std::vector<double>& cost, std::vector<double>* rows = nullptr,
+                std::vector<int32_t>* pair_cnt = nullptr);
   void sync();                                  // wait for a running insert or crop (no-op when idle)
   void set_async(bool on) { sync(); async_ = on; }
   double last_insert_seconds() { sync(); return insert_seconds_; }

@@ -387,6 +387,43 @@ int flimo_scan_to_world(flimo_ctx* ctx, const double x26[26], float* world_xyz_o
  * (pose, point) pairs -- whole poses --, not per call. */
 int flimo_scan_fitness(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t np, float max_dist, int32_t* inliers /* [np] */,
                        double* sum_sqd /* [np] */, float* nn_sqd /* [np][n], may be NULL */, int32_t* nn_idx /* [np][n], may be NULL */);
+/* ---- one linearisation of a point-to-plane registration of the resident scan, for each of np pose hypotheses: the 6 x 6 normal
+ *      equations per pose, without the world points, the neighbourhoods or the planes ever leaving the GPU.  The caller solves and
+ *      iterates (fast_limo_amd.api.scan_align does); flimo_scan_fitness ranks the guesses, this refines the best ones. ----
+ * x26 [np][26]: the poses; only pos and rot are read.  n = flimo_scan_size(ctx).  Every step is a quantity an existing call defines:
+ *  - w(j, i): the float32 world point of resident scan point i under pose j, exactly as in flimo_scan_fitness (pose_from_x26's
+ *    matrix, c0*x + (c1*y + (c2*z + c3)), uncontracted).
+ *  - the plane of pair (j, i): exactly what flimo_map_normals(q = w(j, i), k, max_dist, min_pts, viewpoint = NULL) returns -- cnt, the
+ *    float64 centroid c, the eigenvalues l0 <= l1 <= l2 and the float64 unit normal nrm in its NULL-viewpoint orientation, bit for
+ *    bit; curvature = l0 / (l0 + l1 + l2), 0 for a zero trace, as that call forms it.
+ *  - the pair is VALID iff cnt >= max(3, min_pts) and curvature <= (double)max_curv (a float64 compare; max_curv == INFINITY: no
+ *    curvature gate).
+ *  - the terms of a valid pair, all float64, nothing contracted, in exactly this association (p: the float32 scan point widened; R:
+ *    the nine float32 rotation entries of the pose's matrix widened; w widened):
+ *      d  = nrm.x*(w.x - c.x) + (nrm.y*(w.y - c.y) + nrm.z*(w.z - c.z))
+ *      a  = R^T nrm:  a0 = R00*nrm.x + (R10*nrm.y + R20*nrm.z), a1 and a2 likewise with R's columns 1 and 2
+ *      b  = p x a:    b0 = p.y*a2 - p.z*a1, b1 = p.z*a0 - p.x*a2, b2 = p.x*a1 - p.y*a0
+ *      J  = (a0, a1, a2, b0, b1, b2)
+ *    J is the derivative of d under the body-frame perturbation t <- t + R*drho, R <- R*Exp(dphi) with the plane held fixed; it is
+ *    built from scan coordinates, not world coordinates, so the system stays well conditioned kilometres from the origin.
+ * Outputs, host memory, per pose over its valid pairs:
+ *  - H [np][21]: the upper-triangle sums of J_a*J_b, row-major 00, 01 .. 05, 11 .. 55;  g [np][6]: the sums of J_a*d;
+ *    cost [np]: the sum of d*d;  valid [np]: the exact count.  The Gauss-Newton step solves H xi = -g, xi = (drho, dphi).
+ *    Every sum is taken in ONE fixed shape over the scan's n slots, an invalid slot adding +0.0, without floating-point atomics
+ *    (DESIGN.md section 8 states the shape; it is a function of n alone): the bits of a pose's 28 numbers depend on the scan, the
+ *    map's stored points, the pose and the four parameters -- not on np, the other poses, how the call is cut into chunks, the map's
+ *    cell size or which path of the search finished a pair.
+ *  - rows [np][n][7] (may be NULL): J0..J5, d per pair, NaN for an invalid pair.
+ *  - pair_cnt [np][n] (may be NULL): the neighbour count of the pair, for invalid pairs as well.
+ * FLIMO_OK with all sums and valid 0 (rows NaN, pair_cnt 0) for an empty map, an empty scan and max_dist == 0; np == 0 returns
+ * FLIMO_OK and touches nothing; a NaN scan point gives an invalid pair.  FLIMO_ERR_INVALID: NULL ctx / x26 (np > 0) / valid / H / g /
+ * cost, max_dist or max_curv NaN or negative, a non-finite value among x26[j][0..6] of any pose.  FLIMO_ERR_UNSUPPORTED: k outside
+ * 3 .. FLIMO_KNN_MAX_K.  FLIMO_ERR_TOO_LARGE: np >= 2^31; there is no limit on np * n.  The outputs are untouched on an error.
+ * A pending deskew is run first; the call changes neither the resident scan nor the map nor the bits of a later pass.  Calling rules
+ * and cost as flimo_scan_fitness; device memory is taken per chunk of 2^20 (pose, point) pairs -- whole poses --, 141 B a pair. */
+int flimo_scan_linearize(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t np, int k, float max_dist, int min_pts, float max_curv,
+                         int32_t* valid /* [np] */, double* H /* [np][21] */, double* g /* [np][6] */, double* cost /* [np] */,
+                         double* rows /* [np][n][7], may be NULL */, int32_t* pair_cnt /* [np][n], may be NULL */);
 /* Both clouds the caller of Localizer::updatePointCloud may ask for (pc2match: body frame; final_scan: world frame of pose x26,
  * Localizer.cpp:361-371) in ONE round trip: packed float4 records (x, y, z, unused) in pinned memory owned by the context, valid
  * until the next flimo_scan_clouds on it.  *n = points in each. */

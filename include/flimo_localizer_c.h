@@ -100,6 +100,12 @@ int    flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, 
  * answers like an empty scan (all inliers and sums 0; nn_sqd / nn_idx have no element). */
 int    flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
                               int32_t* nn_idx);
+/* One linearisation of a point-to-plane registration of that scan against the Localizer's map, per pose hypothesis:
+ * flimo_scan_linearize (include/flimo_c.h: same arguments, same results, same error codes) on the map's context, after an insert
+ * or a crop still running behind the last sweep has ended.  A Localizer that has no map yet answers like an empty scan (all sums and
+ * valid 0; rows / pair_cnt have no element).  The Localizer's own update does not use it. */
+int    flimo_loc_scan_linearize(flimo_loc* L, const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, int32_t* valid,
+                                double* H, double* g, double* cost, double* rows, int32_t* pair_cnt);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
