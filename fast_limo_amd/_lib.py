@@ -51,6 +51,16 @@ class FilterCfg(C.Structure):
                 ("end_of_sweep", C.c_int), ("sweep_ref_time", C.c_double), ("fov_active", C.c_int), ("fov_angle", C.c_float)]
 
 
+class CarveCfg(C.Structure):
+    """flimo_carve_cfg (include/flimo_c.h)."""
+    _fields_ = [("res", C.c_int), ("win", C.c_int), ("margin", C.c_float), ("rel_margin", C.c_float), ("max_depth", C.c_float)]
+
+
+def carve_cfg(res=256, win=1, margin=0.2, rel_margin=0.02, max_depth=float("inf")) -> CarveCfg:
+    """The documented defaults: a 256-pixel cube face, a 3 x 3 window, 0.2 m + 2 % of the depth, no depth bound."""
+    return CarveCfg(int(res), int(win), float(margin), float(rel_margin), float(max_depth))
+
+
 class ChainPass(C.Structure):
     _fields_ = [("M", C.c_int), ("stragglers", C.c_int), ("ties", C.c_int), ("HTH", C.c_double * 144), ("HTh", C.c_double * 12),
                 ("dx", C.c_double * 23), ("x_after", C.c_double * 26)]
@@ -76,7 +86,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -167,6 +177,9 @@ def load_hip():
     L.flimo_map_crop_box.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.flimo_map_crop_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.flimo_map_size.restype = C.c_size_t
+    L.flimo_map_seen_through.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(CarveCfg), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.flimo_map_carve.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(CarveCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.flimo_map_carve_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
     L.flimo_map_last_time.argtypes = [vp]
@@ -312,6 +325,40 @@ class HipCtx:
         o = (C.c_uint64 * 2)()
         self._chk(self._L.flimo_map_crop_stats(self._h, o))
         return dict(crops=int(o[0]), points_removed=int(o[1]))
+
+    def map_seen_through(self, x26, sensor, want_mask=True, **cfg):
+        """The stored points that the resident scan, moved to the world frame by ``x26``, looks through from ``sensor`` (world
+        frame) -- flimo_map_seen_through; ``cfg``: the fields of ``carve_cfg``.  Returns (mask [map size] bool in insertion order,
+        count); changes nothing."""
+        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
+        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
+        k = carve_cfg(**cfg)
+        n = self.map_size()
+        mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+        count = C.c_size_t(0)
+        self._chk(self._L.flimo_map_seen_through(self._h, x.ctypes.data, s.ctypes.data, C.byref(k), mask.ctypes.data if want_mask else None, n,
+                                                 C.byref(count)))
+        return (mask[:n].astype(bool) if want_mask else None), int(count.value)
+
+    def map_carve(self, x26, sensor, box=None, **cfg) -> int:
+        """Forget the stored points the resident scan looks through (``map_seen_through``) and, with ``box`` = (lo, hi), those outside
+        it, in one pass -- flimo_map_carve; afterwards the map is as after ``map_crop_box``.  Returns the number of points removed."""
+        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
+        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
+        k = carve_cfg(**cfg)
+        lo = hi = None
+        if box is not None:
+            lo = np.ascontiguousarray(box[0], dtype=np.float32).reshape(3)
+            hi = np.ascontiguousarray(box[1], dtype=np.float32).reshape(3)
+        removed = C.c_size_t(0)
+        self._chk(self._L.flimo_map_carve(self._h, x.ctypes.data, s.ctypes.data, C.byref(k), None if lo is None else lo.ctypes.data,
+                                          None if hi is None else hi.ctypes.data, C.byref(removed)))
+        return int(removed.value)
+
+    def map_carve_stats(self):
+        o = (C.c_uint64 * 2)()
+        self._chk(self._L.flimo_map_carve_stats(self._h, o))
+        return dict(carves=int(o[0]), points_removed=int(o[1]))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

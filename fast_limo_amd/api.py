@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -144,6 +144,16 @@ def load_host():
     L.flimo_loc_scan_fitness.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_scan_linearize.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_set_map_carving.restype = None
+    L.flimo_loc_set_map_carving.argtypes = [vp, C.c_int, C.POINTER(_lib.CarveCfg)]
+    L.flimo_carve_rule.restype = C.c_int
+    L.flimo_carve_rule.argtypes = [C.c_int, C.POINTER(C.c_int)]
+    L.flimo_carve_sensor.restype = None
+    L.flimo_carve_sensor.argtypes = [_lib.f64p, f32p]
+    L.flimo_loc_map_seen_through.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(_lib.CarveCfg), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.flimo_loc_map_carve.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(_lib.CarveCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.flimo_loc_last_carve_removed.restype = C.c_size_t
+    L.flimo_loc_last_carve_removed.argtypes = [vp]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -324,6 +334,47 @@ class Localizer:
         maximum) from the box centre, the map is cropped to position +- ``half_extent``.  A non-positive or non-finite extent
         switches it off."""
         self._L.flimo_loc_set_local_map(self._h, np.ascontiguousarray(half_extent, dtype=np.float32).reshape(3), float(recentre_dist))
+
+    def set_map_carving(self, every_n_sweeps, **cfg):
+        """Map carving (default off): on every ``every_n_sweeps``-th registered sweep that is inserted, the stored points that sweep
+        looks through are forgotten, behind the insert (flimo_loc_set_map_carving); ``cfg``: the fields of ``_lib.carve_cfg``.
+        ``every_n_sweeps <= 0`` or an invalid cfg switches it off."""
+        k = _lib.carve_cfg(**cfg)
+        self._L.flimo_loc_set_map_carving(self._h, int(every_n_sweeps), C.byref(k))
+
+    def map_seen_through(self, x26, sensor, **cfg):
+        """The stored points the scan of the last sweep looks through at ``x26`` from ``sensor`` (flimo_loc_map_seen_through):
+        ``(mask, count)`` as ``HipCtx.map_seen_through``.  Waits for an insert, a crop or a carve still running; changes nothing."""
+        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
+        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
+        k = _lib.carve_cfg(**cfg)
+        n = self.map_size()
+        mask = np.zeros(max(n, 1), np.uint8)
+        count = C.c_size_t(0)
+        rc = self._L.flimo_loc_map_seen_through(self._h, x.ctypes.data, s.ctypes.data, C.byref(k), mask.ctypes.data, n, C.byref(count))
+        if rc != 0:
+            raise FlimoError(f"flimo_loc_map_seen_through failed ({rc})")
+        return mask[:n].astype(bool), int(count.value)
+
+    def map_carve(self, x26, sensor, box=None, **cfg) -> int:
+        """Forget the stored points the scan of the last sweep looks through and, with ``box`` = (lo, hi), those outside it
+        (flimo_loc_map_carve), as ``HipCtx.map_carve``.  Returns the number of points removed."""
+        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
+        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
+        k = _lib.carve_cfg(**cfg)
+        lo = hi = None
+        if box is not None:
+            lo = np.ascontiguousarray(box[0], dtype=np.float32).reshape(3)
+            hi = np.ascontiguousarray(box[1], dtype=np.float32).reshape(3)
+        removed = C.c_size_t(0)
+        rc = self._L.flimo_loc_map_carve(self._h, x.ctypes.data, s.ctypes.data, C.byref(k), None if lo is None else lo.ctypes.data,
+                                         None if hi is None else hi.ctypes.data, C.byref(removed))
+        if rc != 0:
+            raise FlimoError(f"flimo_loc_map_carve failed ({rc})")
+        return int(removed.value)
+
+    def last_carve_removed(self) -> int:
+        return int(self._L.flimo_loc_last_carve_removed(self._h))
 
     def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
         """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,
@@ -510,6 +561,37 @@ class LocalMapRule:
                                           C.byref(self.have), lo, hi)
         self.off = rc < 0
         return (lo, hi) if rc == 1 else None
+
+
+class CarveRule:
+    """The carving policy's counting rule (flimo_carve_rule) restated, with its state: ``step()`` -- once per inserted sweep -- returns
+    True when the map is to be carved now; ``off`` is True when ``every_n_sweeps`` switches the policy off."""
+
+    def __init__(self, every_n_sweeps):
+        self.every = int(every_n_sweeps)
+        self.count = 0
+        self.off = self.every <= 0
+
+    def step(self) -> bool:
+        if self.off:
+            return False
+        self.count += 1
+        if self.count < self.every:
+            return False
+        self.count = 0
+        return True
+
+
+def carve_sensor(x26) -> np.ndarray:
+    """The sensor origin the carving policy uses for a state (flimo_carve_sensor restated): float32(t + R l), float64 arithmetic,
+    R from the attitude quaternion x26[3:7] (x y z w) as Eigen forms it, l = x26[11:14] the lidar-to-baselink translation."""
+    x26 = np.asarray(x26, np.float64)
+    x, y, z, w = x26[3:7]
+    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
+    twx, twy, twz, txx, txy, txz, tyy, tyz, tzz = tx * w, ty * w, tz * w, tx * x, ty * x, tz * x, ty * y, tz * y, tz * z
+    R = ((1.0 - (tyy + tzz), txy - twz, txz + twy), (txy + twz, 1.0 - (txx + tzz), tyz - twx), (txz - twy, tyz + twx, 1.0 - (txx + tyy)))
+    l = x26[11:14]
+    return np.float32([x26[a] + ((R[a][0] * l[0] + R[a][1] * l[1]) + R[a][2] * l[2]) for a in range(3)])
 
 
 def fitness_cost(inliers, sum_sqd, n, max_dist):

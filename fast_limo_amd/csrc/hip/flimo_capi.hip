@@ -51,6 +51,7 @@ struct flimo_ctx {
   bool full_rebuild = false;       // FLIMO_FULL_REBUILD=1: sort the whole map on every insert (A/B of the merge)
   uint64_t grid_merges = 0, grid_builds = 0, grid_regrids = 0, index_overflows = 0, pool_grows = 0;
   uint64_t crops = 0, crop_removed = 0;   // flimo_map_crop_box: calls that removed points, points removed so far
+  uint64_t carves = 0, carve_removed = 0; // flimo_map_carve: the same
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
@@ -1063,6 +1064,37 @@ extern "C" int flimo_map_add(flimo_ctx* c, const float* xyz, size_t n, size_t st
 //     that names map positions goes: the pruning bound, the neighbour records behind flimo_match_fetch, a pass queued ahead.
 // d_map_raw, pt_leaf and d_map_sorted keep their capacity: the next adds re-use the freed tail.  The book's per-batch scratch
 // (sized by the kept count for this one call) and the transient buffer are released before the call returns.
+// (steps 2-3, shared with flimo_map_carve: kept_pts [kept] is what the compaction left, bb the kept points' box; calls / points: the
+// entry's own counters)
+static int map_keep_only(flimo_ctx* c, const float4* kept_pts, size_t kept, size_t n_old, const float bb[6], uint64_t* calls, uint64_t* points,
+                         size_t* removed, const char* what) {
+  if (kept > n_old) return fail(c, FLIMO_ERR_HIP, "%s: compaction reported %zu of %zu points", what, kept, n_old);
+  if (kept == n_old) return FLIMO_OK;
+  // ---- clear() ... ----
+  HIPCHK(c, c->gbook.finish(c->stream, c->scratch));
+  const double last_time = c->map_last_time;
+  const bool had_center = c->have_fine_center;
+  (void)flimo_map_clear(c);
+  c->map_last_time = last_time;                      // (a crop is no insert)
+  c->gbook.release();                                // the nodes of the forgotten regions go with the rest
+  index_free(c->idx);
+  index_free(c->fine_idx);
+  (void)hipFree(c->d_crowd_bits);
+  c->d_crowd_bits = nullptr; c->crowd_bits_cap = 0;
+  c->crowd_cells.clear(); c->crowd_listed = 0;
+  c->last_nq = 0; c->recs_valid = c->dbg_valid = false;      // the last pass's records name positions of the old arrays
+  (*calls)++;
+  *points += n_old - kept;
+  if (removed) *removed = n_old - kept;
+  if (kept == 0) return FLIMO_OK;
+  // ---- ... + initialize(kept) ----
+  c->have_fine_center = had_center;                  // (the sensor is where it was: the second level stays around it)
+  const int rc = map_add_device(c, kept_pts, kept, last_time, bb);
+  c->gbook.release_batch_scratch();
+  if (rc) return rc;
+  if (c->map_n != kept) return fail(c, FLIMO_ERR_HIP, "%s: %zu of the %zu kept points were stored", what, c->map_n, kept);
+  return FLIMO_OK;
+}
 extern "C" int flimo_map_crop_box(flimo_ctx* c, const float lo[3], const float hi[3], size_t* removed) {
   if (removed) *removed = 0;
   if (!c) return FLIMO_ERR_INVALID;
@@ -1079,36 +1111,96 @@ extern "C" int flimo_map_crop_box(flimo_ctx* c, const float lo[3], const float h
   size_t kept = 0;
   float bb[6];
   HIPCHK(c, map_crop_compact(c->stream, c->d_map_raw, n_old, lo, hi, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
-  if (kept > n_old) return fail(c, FLIMO_ERR_HIP, "crop box: compaction reported %zu of %zu points", kept, n_old);
-  if (kept == n_old) return FLIMO_OK;
-  // ---- clear() ... ----
-  HIPCHK(c, c->gbook.finish(c->stream, c->scratch));
-  const double last_time = c->map_last_time;
-  const bool had_center = c->have_fine_center;
-  (void)flimo_map_clear(c);
-  c->map_last_time = last_time;                      // (a crop is no insert)
-  c->gbook.release();                                // the nodes of the forgotten regions go with the rest
-  index_free(c->idx);
-  index_free(c->fine_idx);
-  (void)hipFree(c->d_crowd_bits);
-  c->d_crowd_bits = nullptr; c->crowd_bits_cap = 0;
-  c->crowd_cells.clear(); c->crowd_listed = 0;
-  c->last_nq = 0; c->recs_valid = c->dbg_valid = false;      // the last pass's records name positions of the old arrays
-  c->crops++;
-  c->crop_removed += n_old - kept;
-  if (removed) *removed = n_old - kept;
-  if (kept == 0) return FLIMO_OK;
-  // ---- ... + initialize(kept) ----
-  c->have_fine_center = had_center;                  // (the sensor is where it was: the second level stays around it)
-  const int rc = map_add_device(c, kept_pts.p, kept, last_time, bb);
-  c->gbook.release_batch_scratch();
-  if (rc) return rc;
-  if (c->map_n != kept) return fail(c, FLIMO_ERR_HIP, "crop box: %zu of the %zu kept points were stored", c->map_n, kept);
-  return FLIMO_OK;
+  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->crops, &c->crop_removed, removed, "crop box");
 }
 extern "C" int flimo_map_crop_stats(const flimo_ctx* c, uint64_t out[2]) {
   if (!c || !out) return FLIMO_ERR_INVALID;
   out[0] = c->crops; out[1] = c->crop_removed;
+  return FLIMO_OK;
+}
+
+
+// ---- seeing through: the stored points the resident scan looks past (visibility cleaning of the map) ---------------------------
+// kernels: flimo_map.hip.  The range image of the scan at x26 around the sensor (clear + one launch over the scan, into scratch kept
+// on the context), then either the predicate alone (flimo_map_seen_through: a mask-and-count launch) or the predicate inside the
+// crop's ordered compaction (flimo_map_carve), whose host side from there on is the crop's (map_keep_only).  Reads d_scan and
+// d_map_raw only: d_scan_world and the pass's buffers are left alone.
+static int flush_deskew(flimo_ctx* c);
+static int carve_check(flimo_ctx* c, const double x26[26], const float sensor[3], const flimo_carve_cfg* cfg, const char* what, CarveCfg* out) {
+  if (!x26 || !sensor || !cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null pose / sensor / cfg", what);
+  for (int t = 0; t < 7; t++)
+    if (!std::isfinite(x26[t])) return fail(c, FLIMO_ERR_INVALID, "%s: non-finite position or rotation", what);
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(sensor[a])) return fail(c, FLIMO_ERR_INVALID, "%s: non-finite sensor origin", what);
+  if (cfg->res < 8 || cfg->res > 1024) return fail(c, FLIMO_ERR_INVALID, "%s: res must be in 8..1024", what);
+  if (cfg->win < 0 || cfg->win > 3) return fail(c, FLIMO_ERR_INVALID, "%s: win must be in 0..3", what);
+  if (!(cfg->margin >= 0.f) || !(cfg->rel_margin >= 0.f)) return fail(c, FLIMO_ERR_INVALID, "%s: margin and rel_margin must be >= 0", what);
+  if (!(cfg->max_depth > 0.f)) return fail(c, FLIMO_ERR_INVALID, "%s: max_depth must be > 0 or INFINITY", what);
+  for (int a = 0; a < 3; a++) out->s[a] = sensor[a];
+  out->res = cfg->res; out->win = cfg->win;
+  out->margin = cfg->margin; out->rel_margin = cfg->rel_margin; out->max_depth = cfg->max_depth;
+  return FLIMO_OK;
+}
+// the range image of the resident scan (a pending deskew runs first, as in flimo_scan_to_world)
+static int carve_build_image(flimo_ctx* c, const double x26[26], const CarveCfg& K) {
+  PoseMats P;
+  pose_from_x26(x26, P);
+  { const int rcf = flush_deskew(c); if (rcf) return rcf; }
+  HIPCHK(c, carve_image(c->stream, c->d_scan, c->scan_n, P, K, c->scratch));
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_seen_through(flimo_ctx* c, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg,
+                                      unsigned char* mask, size_t cap, size_t* count) {
+  if (!c) return FLIMO_ERR_INVALID;
+  CarveCfg K;
+  { const int rc = carve_check(c, x26, sensor_xyz, cfg, "seen through", &K); if (rc) return rc; }
+  if (mask && cap < c->map_n) return fail(c, FLIMO_ERR_INVALID, "seen through: the mask holds %zu of %zu points", cap, c->map_n);
+  const size_t n = c->map_n;
+  if (n == 0 || c->scan_n == 0) {                     // no map, or no return: nothing is seen through
+    if (mask) memset(mask, 0, n);
+    if (count) *count = 0;
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  { const int rc = carve_build_image(c, x26, K); if (rc) return rc; }
+  struct Tmp { unsigned char* p = nullptr; ~Tmp() { (void)hipFree(p); } } d_mask;
+  if (mask) HIPCHK(c, hipMalloc(&d_mask.p, n));
+  size_t cnt = 0;
+  HIPCHK(c, carve_mask(c->stream, c->d_map_raw, n, K, c->scratch, d_mask.p, &cnt));
+  if (cnt > n) return fail(c, FLIMO_ERR_HIP, "seen through: counted %zu of %zu points", cnt, n);
+  if (mask) {
+    HIPCHK(c, hipMemcpyAsync(mask, d_mask.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (count) *count = cnt;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_carve(flimo_ctx* c, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg, const float lo[3],
+                               const float hi[3], size_t* removed) {
+  if (!c) return FLIMO_ERR_INVALID;
+  CarveCfg K;
+  { const int rc = carve_check(c, x26, sensor_xyz, cfg, "carve", &K); if (rc) return rc; }
+  if ((lo == nullptr) != (hi == nullptr)) return fail(c, FLIMO_ERR_INVALID, "carve: a box needs both lo and hi");
+  if (lo)
+    for (int a = 0; a < 3; a++)
+      if (!(lo[a] <= hi[a])) return fail(c, FLIMO_ERR_INVALID, "carve: lo <= hi must hold on every axis (no NaN)");
+  if (removed) *removed = 0;
+  if (c->map_n == 0 || c->scan_n == 0) return FLIMO_OK;      // (no return: nothing is seen through, and the box alone is flimo_map_crop_box's)
+  ctx_enter(c);
+  const size_t n_old = c->map_n;
+  { const int rc = carve_build_image(c, x26, K); if (rc) return rc; }
+  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
+  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  size_t kept = 0;
+  float bb[6];
+  HIPCHK(c, map_carve_compact(c->stream, c->d_map_raw, n_old, K, lo, hi, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
+  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->carves, &c->carve_removed, removed, "carve");
+}
+extern "C" int flimo_map_carve_stats(const flimo_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return FLIMO_ERR_INVALID;
+  out[0] = c->carves; out[1] = c->carve_removed;
   return FLIMO_OK;
 }
 

@@ -132,9 +132,12 @@ struct MapBuildScratch {
   // the ordered compaction of a crop (map_crop_compact): per tile {state, count}, then the tile ticket and the kept count
   unsigned long long* crop_desc = nullptr;
   size_t crop_tiles_cap = 0;
+  // the range image of a carve (carve_image): [6][res][res] depth bits, then the count word of carve_mask; grown on demand
+  unsigned int* carve_img = nullptr;
+  size_t carve_img_words = 0;
 };
 // slots of the mail words
-enum MailSlot { MAIL_BOOK = 0 /* 6 */, MAIL_BOOK_END = 8 /* 2 */, MAIL_CROWD = 12, MAIL_BOXCOUNT = 13, MAIL_BBOX = 16 /* 6 */, MAIL_VOXEL = 24 /* 4 */, MAIL_TILES = 28 /* build: tiles, overflow; merge: tiles, overflow */, MAIL_ROWS = 32 /* an insert found the point array or the escape pool full */, MAIL_ESCAPES = 33 /* escape slots a full layout asked for */, MAIL_CROP = 36 /* kept count of a crop */,
+enum MailSlot { MAIL_BOOK = 0 /* 6 */, MAIL_BOOK_END = 8 /* 2 */, MAIL_CROWD = 12, MAIL_BOXCOUNT = 13, MAIL_BBOX = 16 /* 6 */, MAIL_VOXEL = 24 /* 4 */, MAIL_TILES = 28 /* build: tiles, overflow; merge: tiles, overflow */, MAIL_ROWS = 32 /* an insert found the point array or the escape pool full */, MAIL_ESCAPES = 33 /* escape slots a full layout asked for */, MAIL_CROP = 36 /* kept count of a crop */, MAIL_CARVE = 37 /* points a scan sees through */,
                 MAIL_TAG = 62 /* number of the last mail_words, written behind its words */, MAIL_WORDS = 64 };
 struct MailPart { const void* src; int n; int dst; };
 // queues ONE small kernel that copies up to 6 runs of words into the mail slots; `rearm_bbox`: S.bbox is reset to the empty box
@@ -148,6 +151,17 @@ hipError_t mail_wait(hipStream_t st, MapBuildScratch& S);   // the words of the 
 // ticket); *kept and the kept points' box bb (untouched when nothing is kept) come back through the mail words.  Ends synchronised.
 hipError_t map_crop_compact(hipStream_t st, const float4* in, size_t n, const float lo[3], const float hi[3], float4* out, int blocks,
                             MapBuildScratch& S, size_t* kept, float bb[6]);
+
+// Seeing through (flimo_map_seen_through / flimo_map_carve).  cfg: sensor origin (world frame), cube-face resolution, window
+// half-width, margins, depth bound.  carve_image: the range image of the scan at pose P (cleared, then one minimum per scan point
+// that has a pixel) into S.carve_img; no synchronisation.  carve_mask: d_mask[i] (may be null) = 1 where in[i] is seen through that
+// image, *count of them; ends synchronised.  map_carve_compact: map_crop_compact with "not seen through, and inside [lo, hi]
+// where both are given" as the kept points.
+struct CarveCfg { float s[3]; int res, win; float margin, rel_margin, max_depth; };
+hipError_t carve_image(hipStream_t st, const float4* scan, size_t n, const PoseMats& P, const CarveCfg& cfg, MapBuildScratch& S);
+hipError_t carve_mask(hipStream_t st, const float4* in, size_t n, const CarveCfg& cfg, MapBuildScratch& S, unsigned char* d_mask, size_t* count);
+hipError_t map_carve_compact(hipStream_t st, const float4* in, size_t n, const CarveCfg& cfg, const float* lo, const float* hi, float4* out,
+                             int blocks, MapBuildScratch& S, size_t* kept, float bb[6]);
 
 // min/max of n float4 points (NaN-free) -> host bbox[6]
 hipError_t map_bbox(hipStream_t st, const float4* pts, size_t n, MapBuildScratch& S, float bbox_host[6]);

@@ -1671,13 +1671,20 @@ hipError_t voxel_grid(hipStream_t st, const float4* in, size_t n, float leaf, fl
 // (64 predecessors per round trip) instead of reading every earlier tile; a tile is 8192 points, so that the hops are few.  No atomic but the ticket; the box of the kept points:
 // one set of ordered-uint min / max per wave at the end of the launch.
 // desc[t]: bits 0..31 count, bits 32..33 state (0 nothing yet -- the host zeroes the words, 1 the tile's own count, 2 inclusive sum)
-struct CropBox { float lo[3], hi[3]; };
+struct CropBox {
+  float lo[3], hi[3];
+  __device__ __forceinline__ bool operator()(const float4& p) const {
+    return (p.x >= lo[0]) & (p.x <= hi[0]) & (p.y >= lo[1]) & (p.y <= hi[1]) & (p.z >= lo[2]) & (p.z <= hi[2]);
+  }
+};
 // Measured (rocprofv3, 20M points cut to 0.6M / 1M points losing 10 %): 8 rows per wave and 4 workgroups per CU 437 / 135 us, 8 per CU
 // 704 / 138 (the look-back walks over every tile in flight: more workgroups, more hops), 16 rows and 2 per CU 280 / 77, 32 rows
 // and 2 per CU 254 / 51 (1.3 TB/s; shipped), 32 rows and 1 per CU 264 / 51, 4 per CU 309 / 52.
 constexpr int CROP_ROWS = 32;
 constexpr int CROP_TILE = 256 * CROP_ROWS;
-__global__ __launch_bounds__(256) void crop_compact_kernel(const float4* __restrict__ in, uint32_t n, CropBox B, uint32_t ntiles,
+// Keep: the predicate of a kept point (CropBox; CarveKeep below: flimo_map_carve)
+template <class Keep>
+__global__ __launch_bounds__(256) void crop_compact_kernel(const float4* __restrict__ in, uint32_t n, Keep B, uint32_t ntiles,
                                                            unsigned long long* __restrict__ desc, unsigned int* __restrict__ ticket,
                                                            float4* __restrict__ out, uint32_t* __restrict__ kept_out,
                                                            unsigned* __restrict__ box) {
@@ -1700,8 +1707,7 @@ __global__ __launch_bounds__(256) void crop_compact_kernel(const float4* __restr
       const uint32_t i = base + (uint32_t)r * 64u + (uint32_t)lane;
       const bool inb = i < n;
       p[r] = inb ? in[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-      const bool k = inb & (p[r].x >= B.lo[0]) & (p[r].x <= B.hi[0]) & (p[r].y >= B.lo[1]) & (p[r].y <= B.hi[1]) &
-                     (p[r].z >= B.lo[2]) & (p[r].z <= B.hi[2]);
+      const bool k = inb & B(p[r]);
       keep[r] = __ballot(k);
       n_keep += (unsigned int)__popcll(keep[r]);
     }
@@ -1770,8 +1776,147 @@ __global__ __launch_bounds__(256) void crop_compact_kernel(const float4* __restr
   }
 }
 
-hipError_t map_crop_compact(hipStream_t st, const float4* in, size_t n, const float lo[3], const float hi[3], float4* out, int blocks,
-                            MapBuildScratch& S, size_t* kept, float bb[6]) {
+// ---- seeing through (flimo_map_seen_through / flimo_map_carve): a cube-map range image of the resident scan around the sensor, and
+// the stored points that lie in front of it.  Every operation is float32 with one rounding (no contraction, IEEE division), and
+// the image is a minimum over integers (the bits of a positive float order as the float does): the result depends neither on the
+// order of the scan nor on the launch shape, and tests/carve_common.py restates it in numpy bit for bit.
+//  pixel of x: v = x - s; face = the axis of largest |v| (x before y before z on ties) and its sign; depth m = |v_axis|;
+//              (u, t) = the other two components in cyclic order over m; column / row = min(res - 1, (int)((u + 1) * hr)).
+//  No pixel: a non-finite v, or m == 0 (the sensor itself).
+struct CarveView {
+  float s[3];
+  int res, win;
+  float hr, margin, rel_margin, max_depth;
+  const unsigned* img;     // [6][res][res] depth bits, CARVE_EMPTY: no return
+};
+constexpr unsigned CARVE_EMPTY = 0x7f800000u;      // +inf
+__device__ __forceinline__ bool carve_pixel(const CarveView& V, float x, float y, float z, int& face, int& it, int& iu, float& m) {
+  const float vx = x - V.s[0], vy = y - V.s[1], vz = z - V.s[2];
+  const float ax = fabsf(vx), ay = fabsf(vy), az = fabsf(vz);
+  if (!((ax <= FLT_MAX) & (ay <= FLT_MAX) & (az <= FLT_MAX))) return false;      // (NaN compares false)
+  int axis;
+  float va, a, b;
+  if (ax >= ay && ax >= az) { axis = 0; va = vx; a = vy; b = vz; }
+  else if (ay >= az) { axis = 1; va = vy; a = vz; b = vx; }
+  else { axis = 2; va = vz; a = vx; b = vy; }
+  m = fabsf(va);
+  if (m == 0.f) return false;
+  face = 2 * axis + (va < 0.f ? 1 : 0);
+  const float u = a / m, t = b / m;                 // in [-1, 1]
+  iu = min(V.res - 1, (int)((u + 1.0f) * V.hr));
+  it = min(V.res - 1, (int)((t + 1.0f) * V.hr));
+  return true;
+}
+// a stored point is seen through: its pixel holds a return, its window lies wholly on the face (no wrapping over the cube's edges:
+// the strip of `win` pixels along them keeps its points), and every return of the window is farther than the point by the margin
+__device__ __forceinline__ bool carve_seen_through(const CarveView& V, float x, float y, float z) {
+  int f, it, iu;
+  float m;
+  if (!carve_pixel(V, x, y, z, f, it, iu, m)) return false;
+  if (!(m <= V.max_depth)) return false;
+  if (it - V.win < 0 || it + V.win >= V.res || iu - V.win < 0 || iu + V.win >= V.res) return false;
+  const unsigned* F = V.img + (size_t)f * (size_t)V.res * (size_t)V.res;
+  if (F[it * V.res + iu] == CARVE_EMPTY) return false;          // an empty pixel is no evidence
+  const float thr = m + (V.margin + V.rel_margin * m);
+  bool through = true;
+  for (int dt = -V.win; dt <= V.win; dt++)
+    for (int du = -V.win; du <= V.win; du++) {
+      const unsigned d = F[(it + dt) * V.res + (iu + du)];
+      through &= (d == CARVE_EMPTY) | (thr < __uint_as_float(d));
+    }
+  return through;
+}
+__global__ __launch_bounds__(256) void carve_clear_kernel(unsigned* __restrict__ img, uint32_t words) {
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < words; i += gridDim.x * 256u) img[i] = CARVE_EMPTY;
+}
+// one thread per scan point: the world point as transform_kernel forms it (flimo_kernels.hip), its pixel, one device-scope minimum
+__global__ __launch_bounds__(256) void carve_image_kernel(const float4* __restrict__ scan, uint32_t n, PoseMats P, CarveView V,
+                                                          unsigned* __restrict__ img) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n) return;
+  const float4 p = scan[k];
+  const float* M = P.RT;
+  const float x = M[0] * p.x + (M[1] * p.y + (M[2] * p.z + M[3]));
+  const float y = M[4] * p.x + (M[5] * p.y + (M[6] * p.z + M[7]));
+  const float z = M[8] * p.x + (M[9] * p.y + (M[10] * p.z + M[11]));
+  int f, it, iu;
+  float m;
+  if (!carve_pixel(V, x, y, z, f, it, iu, m)) return;
+  atomicMin(&img[((size_t)f * V.res + it) * V.res + iu], __float_as_uint(m));
+}
+// the predicate alone: mask[i] (where given) and the number of points seen through (one integer add per wave)
+__global__ __launch_bounds__(256) void carve_mask_kernel(const float4* __restrict__ in, uint32_t n, CarveView V,
+                                                         unsigned char* __restrict__ mask, unsigned int* __restrict__ count) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool through = false;
+  if (i < n) {
+    const float4 p = in[i];
+    through = carve_seen_through(V, p.x, p.y, p.z);
+    if (mask) mask[i] = through ? 1 : 0;
+  }
+  const unsigned long long b = __ballot(through);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned int)__popcll(b));
+}
+// kept by a carve: not seen through and, with a box, inside it
+struct CarveKeep {
+  CarveView V;
+  CropBox B;
+  int has_box;
+  __device__ __forceinline__ bool operator()(const float4& p) const {
+    return !carve_seen_through(V, p.x, p.y, p.z) & (!has_box | B(p));
+  }
+};
+
+static CarveView carve_view(const CarveCfg& cfg, const unsigned* img) {
+  CarveView V;
+  for (int a = 0; a < 3; a++) V.s[a] = cfg.s[a];
+  V.res = cfg.res; V.win = cfg.win;
+  V.hr = (float)(0.5 * cfg.res);
+  V.margin = cfg.margin; V.rel_margin = cfg.rel_margin; V.max_depth = cfg.max_depth;
+  V.img = img;
+  return V;
+}
+hipError_t carve_image(hipStream_t st, const float4* scan, size_t n, const PoseMats& P, const CarveCfg& cfg, MapBuildScratch& S) {
+  if (n > 0x7fffffffull || cfg.res < 1 || cfg.res > 1024) return hipErrorInvalidValue;
+  const size_t words = (size_t)6 * cfg.res * cfg.res;
+  hipError_t e;
+  if (words > S.carve_img_words) {
+    if (S.carve_img) (void)hipFree(S.carve_img);
+    S.carve_img = nullptr; S.carve_img_words = 0;
+    // (the image, then one word: the count of carve_mask)
+    if ((e = hipMalloc(&S.carve_img, (words + 1) * sizeof(unsigned))) != hipSuccess) return e;
+    S.carve_img_words = words;
+  }
+  const unsigned cblocks = (unsigned)std::min<size_t>((words + 255) / 256, 2048);
+  hipLaunchKernelGGL(carve_clear_kernel, dim3(cblocks), dim3(256), 0, st, S.carve_img, (uint32_t)words);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(carve_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scan, (uint32_t)n, P, carve_view(cfg, S.carve_img),
+                     S.carve_img);
+  return hipGetLastError();
+}
+hipError_t carve_mask(hipStream_t st, const float4* in, size_t n, const CarveCfg& cfg, MapBuildScratch& S, unsigned char* d_mask, size_t* count) {
+  *count = 0;
+  if (n == 0) return hipSuccess;
+  if (n > 0x7fffffffull || !S.carve_img || (size_t)6 * cfg.res * cfg.res > S.carve_img_words) return hipErrorInvalidValue;
+  hipError_t e = ensure_mail(S);
+  if (e != hipSuccess) return e;
+  unsigned int* cnt = S.carve_img + S.carve_img_words;
+  if ((e = hipMemsetAsync(cnt, 0, sizeof(unsigned int), st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(carve_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, (uint32_t)n, carve_view(cfg, S.carve_img), d_mask, cnt);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const MailPart part{cnt, 1, MAIL_CARVE};
+  e = mail_words(st, S, &part, 1);
+  if (e == hipSuccess) e = mail_wait(st, S);
+  if (e != hipSuccess) return e;
+  *count = (size_t)S.mail_host[MAIL_CARVE];
+  return hipSuccess;
+}
+
+// the ordered compaction of crop_compact_kernel under the predicate `keep`; ends synchronised
+template <class Keep>
+static hipError_t compact_ordered(hipStream_t st, const float4* in, size_t n, const Keep& keep, float4* out, int blocks, MapBuildScratch& S,
+                                  size_t* kept, float bb[6]) {
   *kept = 0;
   if (n == 0) return hipSuccess;
   if (n > 0x7fffffffull) return hipErrorInvalidValue;
@@ -1789,11 +1934,9 @@ hipError_t map_crop_compact(hipStream_t st, const float4* in, size_t n, const fl
   if ((e = hipMemsetAsync(S.crop_desc, 0, (tiles + 1) * sizeof(unsigned long long), st)) != hipSuccess) return e;
   unsigned int* ticket = reinterpret_cast<unsigned int*>(S.crop_desc + tiles);
   uint32_t* kept_dev = ticket + 1;
-  CropBox B;
-  for (int a = 0; a < 3; a++) { B.lo[a] = lo[a]; B.hi[a] = hi[a]; }
   const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)std::max(blocks, 1)));
-  hipLaunchKernelGGL(crop_compact_kernel, dim3(grid), dim3(256), 0, st, in, (uint32_t)n, B, (uint32_t)tiles, S.crop_desc, ticket, out, kept_dev,
-                     (unsigned*)S.bbox);
+  hipLaunchKernelGGL(crop_compact_kernel<Keep>, dim3(grid), dim3(256), 0, st, in, (uint32_t)n, keep, (uint32_t)tiles, S.crop_desc, ticket, out,
+                     kept_dev, (unsigned*)S.bbox);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const MailPart parts[2] = {{kept_dev, 1, MAIL_CROP}, {S.bbox, 6, MAIL_BBOX}};
   e = mail_words(st, S, parts, 2, true);
@@ -1809,6 +1952,21 @@ hipError_t map_crop_compact(hipStream_t st, const float4* in, size_t n, const fl
     for (int i = 0; i < 6; i++) bb[i] = o2f_host(S.mail_host[MAIL_BBOX + i]);
   return hipSuccess;
 }
+hipError_t map_crop_compact(hipStream_t st, const float4* in, size_t n, const float lo[3], const float hi[3], float4* out, int blocks,
+                            MapBuildScratch& S, size_t* kept, float bb[6]) {
+  CropBox B;
+  for (int a = 0; a < 3; a++) { B.lo[a] = lo[a]; B.hi[a] = hi[a]; }
+  return compact_ordered(st, in, n, B, out, blocks, S, kept, bb);
+}
+hipError_t map_carve_compact(hipStream_t st, const float4* in, size_t n, const CarveCfg& cfg, const float* lo, const float* hi, float4* out,
+                             int blocks, MapBuildScratch& S, size_t* kept, float bb[6]) {
+  if (!S.carve_img || (size_t)6 * cfg.res * cfg.res > S.carve_img_words) { *kept = 0; return hipErrorInvalidValue; }
+  CarveKeep K;
+  K.V = carve_view(cfg, S.carve_img);
+  K.has_box = (lo && hi) ? 1 : 0;
+  for (int a = 0; a < 3; a++) { K.B.lo[a] = K.has_box ? lo[a] : 0.f; K.B.hi[a] = K.has_box ? hi[a] : 0.f; }
+  return compact_ordered(st, in, n, K, out, blocks, S, kept, bb);
+}
 
 void map_scratch_free(MapBuildScratch& S) {
   if (S.cub_tmp) hipFree(S.cub_tmp);
@@ -1817,6 +1975,7 @@ void map_scratch_free(MapBuildScratch& S) {
   if (S.bbox) hipFree(S.bbox);
   if (S.filt_desc) hipFree(S.filt_desc);
   if (S.crop_desc) (void)hipFree(S.crop_desc);
+  if (S.carve_img) (void)hipFree(S.carve_img);
   if (S.filt_mail_host) hipHostFree(S.filt_mail_host);
   if (S.mail_host) hipHostFree(S.mail_host);
   S = MapBuildScratch();

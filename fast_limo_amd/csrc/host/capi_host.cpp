@@ -216,6 +216,44 @@ int flimo_local_map_rule(const double p[3], const float half_extent[3], float re
                          float lo[3], float hi[3]) {
   return fast_limo::Localizer::local_map_rule(p, half_extent, recentre_dist, centre, have_centre, lo, hi);
 }
+void flimo_loc_set_map_carving(flimo_loc* L, int every_n_sweeps, const flimo_carve_cfg* cfg) { if (L) L->loc->set_map_carving(every_n_sweeps, cfg); }
+int flimo_carve_rule(int every_n_sweeps, int* count) { return fast_limo::Localizer::carve_rule(every_n_sweeps, count); }
+void flimo_carve_sensor(const double x26[26], float sensor_xyz[3]) { if (x26 && sensor_xyz) fast_limo::Localizer::carve_sensor(x26, sensor_xyz); }
+// no map yet: the answer of an empty one, after the calls' own argument checks
+static int carve_of_no_map(const double x26[26], const float sensor[3], const flimo_carve_cfg* cfg) {
+  if (!x26 || !sensor || !cfg) return FLIMO_ERR_INVALID;
+  for (int t = 0; t < 7; t++) if (!std::isfinite(x26[t])) return FLIMO_ERR_INVALID;
+  for (int a = 0; a < 3; a++) if (!std::isfinite(sensor[a])) return FLIMO_ERR_INVALID;
+  if (cfg->res < 8 || cfg->res > 1024 || cfg->win < 0 || cfg->win > 3 || !(cfg->margin >= 0.f) || !(cfg->rel_margin >= 0.f) || !(cfg->max_depth > 0.f))
+    return FLIMO_ERR_INVALID;
+  return FLIMO_OK;
+}
+int flimo_loc_map_seen_through(flimo_loc* L, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg, unsigned char* mask,
+                               size_t cap, size_t* count) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
+  if (!c) {
+    const int rc = carve_of_no_map(x26, sensor_xyz, cfg);
+    if (rc == FLIMO_OK && count) *count = 0;
+    return rc;
+  }
+  return flimo_map_seen_through(c, x26, sensor_xyz, cfg, mask, cap, count);
+}
+int flimo_loc_map_carve(flimo_loc* L, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg, const float lo[3],
+                        const float hi[3], size_t* removed) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();
+  if (!c) {
+    int rc = carve_of_no_map(x26, sensor_xyz, cfg);
+    if (rc == FLIMO_OK && (lo == nullptr) != (hi == nullptr)) rc = FLIMO_ERR_INVALID;
+    if (rc == FLIMO_OK && lo)
+      for (int a = 0; a < 3; a++) if (!(lo[a] <= hi[a])) rc = FLIMO_ERR_INVALID;
+    if (rc == FLIMO_OK && removed) *removed = 0;
+    return rc;
+  }
+  return flimo_map_carve(c, x26, sensor_xyz, cfg, lo, hi, removed);
+}
+size_t flimo_loc_last_carve_removed(flimo_loc* L) { return L ? L->map->last_carve_removed() : 0; }
 int flimo_loc_map_radius_search(flimo_loc* L, const float* q_xyz, size_t nq, float radius, unsigned flags, uint64_t* offsets, int32_t* idx,
                                 float* sqd, float* xyz, size_t cap, uint64_t* total) {
   if (!L) return FLIMO_ERR_INVALID;

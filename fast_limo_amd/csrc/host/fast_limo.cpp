@@ -287,6 +287,12 @@ void Mapper::run_crop(const float lo[3], const float hi[3]) {
   if (rc != FLIMO_OK) std::cout << "FAST_LIMO::map crop failed: " << flimo_last_error(ctx_) << "\n";
   crop_removed_ = removed;
 }
+void Mapper::run_carve(const CarveJob& j) {
+  size_t removed = 0;
+  const int rc = flimo_map_carve(ctx_, j.x26, j.sensor, &j.cfg, j.has_box ? j.lo : nullptr, j.has_box ? j.hi : nullptr, &removed);
+  if (rc != FLIMO_OK) std::cout << "FAST_LIMO::map carve failed: " << flimo_last_error(ctx_) << "\n";
+  carve_removed_ = removed;
+}
 void Mapper::worker_main() {
   std::unique_lock<std::mutex> lk(wm_);
   for (;;) {
@@ -299,15 +305,18 @@ void Mapper::worker_main() {
     }
     wcv_.wait(lk, [this] { return busy_.load() || quit_.load(); });
     if (quit_) return;
-    // an insert, then the crop that follows it -- also one that was asked for while the insert ran (crop_box)
-    while (job_insert_ || job_crop_) {
-      const bool ins = job_insert_, crop = !ins && job_crop_;
+    // an insert, then the crop or the carve that follows it -- also one that was asked for while the insert ran (crop_box, carve)
+    while (job_insert_ || job_crop_ || job_carve_) {
+      const bool ins = job_insert_, crop = !ins && job_crop_, carve = !ins && !crop && job_carve_;
       float lo[3], hi[3];
+      CarveJob cj;
       if (ins) job_insert_ = false;
       if (crop) { job_crop_ = false; std::memcpy(lo, job_lo_, sizeof(lo)); std::memcpy(hi, job_hi_, sizeof(hi)); }
+      if (carve) { job_carve_ = false; cj = carve_job_; }
       lk.unlock();
       if (ins) run_insert(job_x_, job_stamp_);      // the only user of ctx_ while busy_ is set
-      else run_crop(lo, hi);
+      else if (crop) run_crop(lo, hi);
+      else run_carve(cj);
       lk.lock();
     }
     busy_ = false;
@@ -344,6 +353,29 @@ void Mapper::crop_box(const float lo[3], const float hi[3]) {
       }
     }
     sync();                                         // (a second crop before the first one ran: one after the other)
+  }
+  wcv_.notify_all();
+}
+void Mapper::carve(const double x26[26], const float sensor[3], const flimo_carve_cfg& cfg, const float* lo, const float* hi) {
+  if (!ctx_) return;
+  CarveJob j;
+  std::memcpy(j.x26, x26, sizeof(j.x26));
+  std::memcpy(j.sensor, sensor, sizeof(j.sensor));
+  j.cfg = cfg;
+  j.has_box = lo && hi;
+  if (j.has_box) { std::memcpy(j.lo, lo, sizeof(j.lo)); std::memcpy(j.hi, hi, sizeof(j.hi)); }
+  if (!async_ || !worker_.joinable()) { sync(); run_carve(j); return; }
+  for (;;) {
+    {
+      std::lock_guard<std::mutex> lk(wm_);
+      if (!job_carve_) {                           // behind whatever the worker is doing now, as crop_box
+        carve_job_ = j;
+        job_carve_ = true;
+        busy_ = true;
+        break;
+      }
+    }
+    sync();
   }
   wcv_.notify_all();
 }
@@ -666,6 +698,33 @@ int Localizer::local_map_rule(const double p[3], const float half_extent[3], flo
   }
   *have_centre = 1;
   return 1;
+}
+int Localizer::carve_rule(int every_n_sweeps, int* count) {
+  if (every_n_sweeps <= 0 || !count) return -1;
+  if (++*count < every_n_sweeps) return 0;
+  *count = 0;
+  return 1;
+}
+void Localizer::carve_sensor(const double x26[26], float sensor[3]) {
+  double R[9];
+  const double x = x26[3], y = x26[4], z = x26[5], w = x26[6];       // Eigen toRotationMatrix, float64
+  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz;         R[2] = txz + twy;
+  R[3] = txy + twz;         R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
+  R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.0 - (txx + tyy);
+  const double* l = x26 + 11;                                        // lidar -> baselink translation
+  for (int a = 0; a < 3; a++) sensor[a] = (float)(x26[a] + ((R[3 * a] * l[0] + R[3 * a + 1] * l[1]) + R[3 * a + 2] * l[2]));
+}
+static bool carve_cfg_valid(const flimo_carve_cfg* c) {
+  return c && c->res >= 8 && c->res <= 1024 && c->win >= 0 && c->win <= 3 && c->margin >= 0.f && c->rel_margin >= 0.f && c->max_depth > 0.f;
+}
+void Localizer::set_map_carving(int every_n_sweeps, const flimo_carve_cfg* cfg) {
+  carve_on_ = every_n_sweeps > 0 && carve_cfg_valid(cfg);
+  carve_count_ = 0;
+  if (!carve_on_) return;
+  carve_every_ = every_n_sweeps;
+  carve_cfg_ = *cfg;
 }
 void Localizer::set_local_map(const float half_extent[3], float recentre_dist) {
   double c[3] = {0.0, 0.0, 0.0}, p0[3] = {0.0, 0.0, 0.0};
@@ -2114,10 +2173,18 @@ void Localizer::finishUpdate(bool ok, double t0, double t1, double t2) {
     if (dev_front_end_ && (download_clouds || config.debug)) downloadClouds(x26);   // before the insert takes the context
     else debugClouds(x26, true);
     if (add_to_map) map_->add_scan(x26, scan_stamp);               // returns at once; the insert overlaps the next scan's host work
-    if (add_to_map && local_map_on_) {                             // local map: forget what lies outside the box around the sensor
+    if (add_to_map && (local_map_on_ || carve_on_)) {
+      // local map: forget what lies outside the box around the sensor; carving: forget what this sweep looks through.  Both due on
+      // one sweep: ONE carve with the box (one relayout).  Behind the insert, on its worker: nothing waits here
       float lo[3], hi[3];
-      if (local_map_rule(x26, local_half_, local_recentre_, local_centre_, &local_have_centre_, lo, hi) == 1)
-        map_->crop_box(lo, hi);                                    // behind the insert, on its worker: nothing waits here
+      const bool crop = local_map_on_ && local_map_rule(x26, local_half_, local_recentre_, local_centre_, &local_have_centre_, lo, hi) == 1;
+      if (carve_on_ && carve_rule(carve_every_, &carve_count_) == 1) {
+        float sensor[3];
+        carve_sensor(x26, sensor);
+        map_->carve(x26, sensor, carve_cfg_, crop ? lo : nullptr, crop ? hi : nullptr);
+      } else if (crop) {
+        map_->crop_box(lo, hi);
+      }
     }
     t4 = now_s();
   } else {

@@ -90,6 +90,16 @@ class fast_limo::Localizer {
   // now, -1 = these arguments switch the policy off (nothing is touched).
   static int local_map_rule(const double p[3], const float half_extent[3], float recentre_dist, double centre[3], int* have_centre,
                             float lo[3], float hi[3]);
+  // Map carving (off by default; flimo_map_carve): on every every_n_sweeps-th registered sweep that is inserted into the map, the
+  // stored points that sweep looks through are forgotten (Mapper::carve, behind the insert), seen from sensor = float(t + R *
+  // lidar-to-baselink translation) of the sweep's final state, computed in float64.  When the local-map rule fires on the same sweep,
+  // ONE carve with the box is issued instead of a crop and a carve.  every_n_sweeps <= 0 or an invalid cfg switches it off.
+  void set_map_carving(int every_n_sweeps, const flimo_carve_cfg* cfg);
+  // The counting rule, as a pure function (flimo_carve_rule): 1 = carve now (*count back to 0), 0 = not now (*count advanced),
+  // -1 = every_n_sweeps <= 0 switches the policy off (nothing is touched).  *count = 0 before the first sweep.
+  static int carve_rule(int every_n_sweeps, int* count);
+  // the sensor origin of a state in the world frame, as the policy forms it (flimo_carve_sensor)
+  static void carve_sensor(const double x26[26], float sensor[3]);
 
   static Localizer& getInstance() {
     static Localizer* loc = new Localizer();
@@ -113,6 +123,9 @@ class fast_limo::Localizer {
 
   Mapper* map_;
   bool own_map_;
+  bool carve_on_ = false;               // set_map_carving
+  int carve_every_ = 0, carve_count_ = 0;
+  flimo_carve_cfg carve_cfg_{};
   bool local_map_on_ = false;           // set_local_map
   float local_half_[3] = {0.f, 0.f, 0.f}, local_recentre_ = 0.f;
   double local_centre_[3] = {0.0, 0.0, 0.0};

@@ -14,6 +14,7 @@
 #include "fast_limo/Objects/Match.hpp"
 #include "fast_limo/Objects/State.hpp"
 #include "fast_limo/Utils/Config.hpp"
+#include "flimo_c.h"
 
 struct flimo_ctx;
 
@@ -54,6 +55,11 @@ class fast_limo::Mapper {
   // asked for it does not wait.  sync() waits for it like for an insert.
   void crop_box(const float lo[3], const float hi[3]);
   size_t last_crop_removed() { sync(); return crop_removed_; }   // points the last crop_box removed
+  // Forget the stored points that the scan RESIDENT in the context looks through from `sensor` (world frame) at pose x26, and --
+  // with a box (lo, hi both non-null) -- those outside it, in one pass (flimo_map_carve).  Queued like crop_box: with asynchronous
+  // inserts a job on the worker thread BEHIND the insert of the sweep that asked for it, whose scan is still the resident one there.
+  void carve(const double x26[26], const float sensor[3], const flimo_carve_cfg& cfg, const float* lo = nullptr, const float* hi = nullptr);
+  size_t last_carve_removed() { sync(); return carve_removed_; }   // points the last carve removed
   // octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the GPU map (flimo_radius_search).  The reference's Mapper hides
   // its octree, so this is an addition: the stored points with (p - query).squaredNorm() < radius * radius (strict, float32), in
   // ascending order of (distance, insertion index) -- the reference's traversal order is not reproduced.  As the template
@@ -133,6 +139,11 @@ class fast_limo::Mapper {
   double job_stamp_ = 0.0;
   float job_lo_[3] = {0, 0, 0}, job_hi_[3] = {0, 0, 0};
   size_t crop_removed_ = 0;
+  struct CarveJob { double x26[26]; float sensor[3]; flimo_carve_cfg cfg; bool has_box = false; float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}; };
+  bool job_carve_ = false;                        // (under wm_, as job_crop_)
+  CarveJob carve_job_;
+  size_t carve_removed_ = 0;
+  void run_carve(const CarveJob& j);
   double handoff_time_ = 0.0;
   double insert_seconds_ = 0.0;
   void run_insert(const double x26[26], double stamp);

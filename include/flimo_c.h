@@ -94,6 +94,51 @@ int flimo_map_clear(flimo_ctx* ctx);
  * leaves the map as flimo_map_clear does, except flimo_map_last_time, which a crop never touches.  FLIMO_ERR_INVALID for a NULL /
  * NaN / lo > hi box.  Same calling rules as flimo_map_add: no pass of this context in flight. */
 int flimo_map_crop_box(flimo_ctx* ctx, const float lo[3], const float hi[3], size_t* removed);
+/* Forgetting by sight: the stored points that the scan resident in the context (flimo_scan_set / flimo_deskew...) measurably looks
+ * THROUGH from the sensor origin -- a car that drove off, a person who walked by, a door now open.  The standard visibility
+ * (range-image) cleaning of a LiDAR map; the counterpart of flimo_scan_fitness, which finds scan points without map support.
+ *
+ * Definition (every operation float32, IEEE, nothing contracted; tests/carve_common.py restates it in numpy, bit for bit):
+ *  - pixel of a point x (a scan point moved to the world frame, or a stored point): v = x - sensor_xyz.  No pixel when a component of
+ *    v is not finite or the depth m below is 0.  Face axis: x if |vx| >= |vy| and |vx| >= |vz|, else y if |vy| >= |vz|, else z;
+ *    m = |v_axis| (the depth a z-buffer on a cube face stores), face = 2 * axis + (v_axis < 0).  (a, b) = the other two components
+ *    in cyclic order (x: y,z  y: z,x  z: x,y); u = a / m, t = b / m; hr = (float)(0.5 * res); column iu = min(res - 1,
+ *    (int)((u + 1.0f) * hr)), row it likewise from t.  A cube map needs only '/' and compares, no atan2 / asin.
+ *  - range image D[6][res][res]: the minimum of m over the scan's world points that have a pixel -- point i of
+ *    flimo_scan_to_world(ctx, x26, ..), the same matrix, the same c0*x + (c1*y + (c2*z + c3)); a pending deskew runs first --,
+ *    +inf where there is none.  A minimum over the floats' bits: the order of the scan and the launch shape do not matter.
+ *  - a stored point q with pixel (f, it, iu) and depth m is seen through iff m <= max_depth (INFINITY: no bound), the window
+ *    [it - win, it + win] x [iu - win, iu + win] lies wholly on the face, D[f][it][iu] is finite (an empty pixel is no evidence),
+ *    and with thr = m + (margin + rel_margin * m), thr < D (strict) at every pixel of the window that holds a return.
+ *  The window never wraps over a cube edge: a stored point whose pixel is closer than `win` pixels to its face's border is KEPT,
+ *  whatever the scan says (a strip of win / res of each face along the cube's edges; another sweep, from another place, sees it
+ *  elsewhere on a face).  With margin, rel_margin >= 0 the scan's own points are never seen through, inserted or not.  win >= 1 is
+ *  the recommended setting: at win 0 a grazing surface is carved by its own neighbouring returns.
+ * x26: pos and rot are read.  sensor_xyz: the sensor origin in the WORLD frame (the caller's: t + R * lidar-to-body translation). */
+typedef struct flimo_carve_cfg {
+  int res;            /* pixels along a cube face's side, 8..1024 (the image is 24 * res * res bytes of device scratch) */
+  int win;            /* half-width of the window of pixels a point is tested against, 0..3 */
+  float margin;       /* metres a return must lie behind the point, >= 0 */
+  float rel_margin;   /* ... plus this share of the point's depth, >= 0 */
+  float max_depth;    /* points deeper than this are kept; > 0 or INFINITY */
+} flimo_carve_cfg;
+/* The predicate alone: mask[i] (may be NULL; cap >= flimo_map_size elements otherwise) = 1 where stored point i (insertion order) is
+ * seen through, 0 elsewhere; *count (may be NULL) = how many are.  Changes nothing: not the map, not the scan, not the bits of a
+ * later pass.  An empty map or an empty scan: FLIMO_OK, count 0. */
+int flimo_map_seen_through(flimo_ctx* ctx, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg,
+                           unsigned char* mask, size_t cap, size_t* count);
+/* Keeps the stored points that are NOT seen through and -- when a box is given (lo, hi both non-NULL; both NULL: no box) -- lie
+ * inside [lo, hi] (inclusive, as flimo_map_crop_box), in insertion order, in one pass over the map; a sweep that is due a crop and a
+ * carve pays for one relayout.  Afterwards everything is as flimo_map_crop_box documents: the map is clear() + initialize(kept),
+ * insertion indices are renumbered, flimo_map_last_time is untouched.  *removed (may be NULL) receives how many points went.
+ * Removing nothing changes nothing; removing everything leaves the map as a crop that removes everything does.  An empty map or an
+ * empty scan: FLIMO_OK, *removed = 0, nothing changes -- also with a box (the box alone is flimo_map_crop_box's business).
+ * Both calls: FLIMO_ERR_INVALID -- outputs and map untouched -- for a NULL ctx / x26 / sensor_xyz / cfg, a non-finite position,
+ * rotation or sensor value, res outside 8..1024, win outside 0..3, a NaN or negative margin / rel_margin, max_depth NaN or <= 0, a
+ * NaN / lo > hi box or only one of lo / hi, cap < flimo_map_size with a non-NULL mask.  Same calling rules as flimo_map_crop_box:
+ * no pass of this context in flight. */
+int flimo_map_carve(flimo_ctx* ctx, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg,
+                    const float lo[3], const float hi[3], size_t* removed);
 size_t flimo_map_size(const flimo_ctx* ctx);
 double flimo_map_last_time(const flimo_ctx* ctx);
 /* copies the stored points (insertion order: what neighbour indices refer to) as packed xyz; *n receives the total count

@@ -63,6 +63,9 @@ double flimo_last_candidates_per_query(const flimo_ctx* ctx);
 int flimo_map_grid_selfcheck(flimo_ctx* ctx, uint64_t* mismatches, uint64_t stats[2]);
 /* flimo_map_crop_box so far: out[0] = calls that removed points (each one full layout), out[1] = points removed */
 int flimo_map_crop_stats(const flimo_ctx* ctx, uint64_t out[2]);
+/* flimo_map_carve so far: out[0] = calls that removed points (each one full layout), out[1] = points removed.  (flimo_map_crop_stats
+ * counts crops only: a carve with a box is a carve.) */
+int flimo_map_carve_stats(const flimo_ctx* ctx, uint64_t out[2]);
 /* flimo_radius_search's walk, counted: cand[i] = stored points query i's walk loads and tests at this radius (what the count and
  * the fill launch each read, 16 bytes apiece); cand: host, [nq].  Arguments as flimo_radius_search. */
 int flimo_radius_candidates(flimo_ctx* ctx, const float* q_xyz, size_t nq, float radius, uint64_t* cand);

@@ -76,6 +76,29 @@ void   flimo_loc_set_local_map(flimo_loc* L, const float half_extent[3], float r
  * written), -1 when the arguments switch the policy off (nothing written). */
 int    flimo_local_map_rule(const double p[3], const float half_extent[3], float recentre_dist, double centre[3], int* have_centre,
                             float lo[3], float hi[3]);
+/* Map carving, default off (flimo_map_carve, include/flimo_c.h: forget the stored points a sweep looks through -- cars that left,
+ * people who walked by).  On every every_n_sweeps-th registered sweep that is inserted into the map, a carve with that sweep's scan
+ * and final state is queued on the insert's worker thread behind the insert: the sweep does not wait for it.  The sensor origin is
+ * float(t + R * lidar-to-baselink translation), computed in float64 from the state (flimo_carve_sensor).  When the local-map rule
+ * fires on the same sweep, ONE carve with the box is issued instead of a crop and a carve: one relayout.  every_n_sweeps <= 0, a
+ * NULL cfg or one flimo_map_carve rejects switches the policy off.  Recommended: win >= 1, margin a few range sigmas. */
+void   flimo_loc_set_map_carving(flimo_loc* L, int every_n_sweeps, const flimo_carve_cfg* cfg);
+/* The counting rule above as a pure host function.  *count: the policy's state (in / out; 0 before the first sweep).  Called once
+ * per inserted sweep: returns 1 when the map is to be carved now (*count = 0), 0 when not (*count advanced), -1 when every_n_sweeps
+ * <= 0 or count is NULL (nothing written). */
+int    flimo_carve_rule(int every_n_sweeps, int* count);
+/* ... and the sensor origin of a state: sensor_xyz[a] = (float)(x26[a] + ((R[a][0] * l[0] + R[a][1] * l[1]) + R[a][2] * l[2])), R the
+ * float64 rotation matrix of the state's attitude (x26[3..6], x y z w), l = x26[11..13] the lidar-to-baselink translation. */
+void   flimo_carve_sensor(const double x26[26], float sensor_xyz[3]);
+/* flimo_map_seen_through / flimo_map_carve (include/flimo_c.h: same arguments, same results, same error codes) on the map's context
+ * with the scan resident there -- after updatePointCloud: pc2match --, after an insert, a crop or a carve still running behind the
+ * last sweep has ended.  A Localizer that has no map yet answers like an empty one (count / removed 0). */
+int    flimo_loc_map_seen_through(flimo_loc* L, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg,
+                                  unsigned char* mask, size_t cap, size_t* count);
+int    flimo_loc_map_carve(flimo_loc* L, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg, const float lo[3],
+                           const float hi[3], size_t* removed);
+/* points the last carve removed -- the policy's or flimo_loc_map_carve's (waits for one still running) */
+size_t flimo_loc_last_carve_removed(flimo_loc* L);
 /* octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the Localizer's map: flimo_radius_search (include/flimo_c.h: same
  * arguments, same results, same error codes) on the map's context, after an insert or a crop still running behind the last sweep
  * has ended.  A Localizer that has no map yet answers like an empty one (all offsets 0). */
