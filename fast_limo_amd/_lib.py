@@ -61,6 +61,47 @@ def carve_cfg(res=256, win=1, margin=0.2, rel_margin=0.02, max_depth=float("inf"
     return CarveCfg(int(res), int(win), float(margin), float(rel_margin), float(max_depth))
 
 
+class OutlierCfg(C.Structure):
+    """flimo_outlier_cfg (include/flimo_c.h)."""
+    _fields_ = [("k", C.c_int), ("max_dist", C.c_float), ("min_pts", C.c_int), ("std_mul", C.c_float)]
+
+
+class OutlierStats(C.Structure):
+    """flimo_outlier_stats (include/flimo_c.h)."""
+    _fields_ = [("n", C.c_uint64), ("n_stat", C.c_uint64), ("mu", C.c_double), ("sigma", C.c_double), ("threshold", C.c_double),
+                ("few", C.c_uint64), ("far", C.c_uint64), ("outliers", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(n=int(self.n), n_stat=int(self.n_stat), mu=float(self.mu), sigma=float(self.sigma), threshold=float(self.threshold),
+                    few=int(self.few), far=int(self.far), outliers=int(self.outliers))
+
+
+def outlier_cfg(k=8, max_dist=float("inf"), min_pts=0, std_mul=1.0) -> OutlierCfg:
+    """PCL's StatisticalOutlierRemoval with 8 neighbours and one sigma unless told otherwise: no gate, no count rule."""
+    return OutlierCfg(int(k), float(max_dist), int(min_pts), float(std_mul))
+
+
+def outliers_call(call, n, want, cfg):
+    """The output arrays of flimo_map_outliers / flimo_loc_map_outliers (``call`` takes: cfg, mask, mean_dist, cnt, stats) as a dict
+    with the outputs named in ``want`` (of "mask", "mean_dist", "cnt") and "stats"; shared with ``api.Localizer``."""
+    unknown = set(want) - {"mask", "mean_dist", "cnt"}
+    if unknown:
+        raise ValueError(f"outliers: unknown outputs {sorted(unknown)}")
+    k = outlier_cfg(**cfg)
+    arr = {}
+    for name, dt in (("mask", np.uint8), ("mean_dist", np.float64), ("cnt", np.int32)):
+        if name in want:
+            arr[name] = np.zeros(max(n, 1), dt)
+    st = OutlierStats()
+    ptr = lambda name: arr[name].ctypes.data if name in arr else None
+    call(C.byref(k), ptr("mask"), ptr("mean_dist"), ptr("cnt"), C.byref(st))
+    out = {name: a[:n] for name, a in arr.items()}
+    if "mask" in out:
+        out["mask"] = out["mask"].astype(bool)
+    out["stats"] = st.as_dict()
+    return out
+
+
 class ChainPass(C.Structure):
     _fields_ = [("M", C.c_int), ("stragglers", C.c_int), ("ties", C.c_int), ("HTH", C.c_double * 144), ("HTh", C.c_double * 12),
                 ("dx", C.c_double * 23), ("x_after", C.c_double * 26)]
@@ -86,7 +127,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -180,6 +221,9 @@ def load_hip():
     L.flimo_map_seen_through.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(CarveCfg), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.flimo_map_carve.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(CarveCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.flimo_map_carve_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.flimo_map_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(OutlierCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OutlierStats)]
+    L.flimo_map_remove_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(OutlierCfg), C.POINTER(C.c_size_t), C.POINTER(OutlierStats)]
+    L.flimo_set_outlier_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
     L.flimo_map_last_time.argtypes = [vp]
@@ -359,6 +403,29 @@ class HipCtx:
         o = (C.c_uint64 * 2)()
         self._chk(self._L.flimo_map_carve_stats(self._h, o))
         return dict(carves=int(o[0]), points_removed=int(o[1]))
+
+    def map_outliers(self, first=0, n=None, want=("mask", "mean_dist", "cnt"), **cfg):
+        """The stored points first .. first + n - 1 (``n`` None: up to the map's end) that belong to no surface, by the statistics
+        of their k nearest neighbours -- flimo_map_outliers; ``cfg``: the fields of ``outlier_cfg``.  Returns a dict: ``mask`` [n]
+        bool, ``mean_dist`` [n] float64, ``cnt`` [n] int32 (those named in ``want``) and ``stats``; changes nothing."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return outliers_call(lambda *a: self._chk(self._L.flimo_map_outliers(self._h, first, n, *a)), n, want, cfg)
+
+    def map_remove_outliers(self, first=0, n=None, **cfg):
+        """Forget the outliers of ``map_outliers`` -- flimo_map_remove_outliers; afterwards the map is as after ``map_crop_box``.
+        Returns (points removed, stats)."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        k = outlier_cfg(**cfg)
+        removed = C.c_size_t(0)
+        st = OutlierStats()
+        self._chk(self._L.flimo_map_remove_outliers(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)))
+        return int(removed.value), st.as_dict()
+
+    def set_outlier_chunk(self, n):
+        """Points per search launch of ``map_outliers`` / ``map_remove_outliers`` (flimo_set_outlier_chunk; 0: the default of 2^20)."""
+        self._chk(self._L.flimo_set_outlier_chunk(self._h, int(n)))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

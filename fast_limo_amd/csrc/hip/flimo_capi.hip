@@ -52,9 +52,11 @@ struct flimo_ctx {
   uint64_t grid_merges = 0, grid_builds = 0, grid_regrids = 0, index_overflows = 0, pool_grows = 0;
   uint64_t crops = 0, crop_removed = 0;   // flimo_map_crop_box: calls that removed points, points removed so far
   uint64_t carves = 0, carve_removed = 0; // flimo_map_carve: the same
+  uint64_t outlier_removals = 0, outlier_removed = 0;   // flimo_map_remove_outliers: the same
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
+  size_t outlier_chunk = (size_t)1 << 20;   // points per search launch of flimo_map_outliers (flimo_set_outlier_chunk)
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
@@ -1477,6 +1479,133 @@ extern "C" int flimo_map_normals_range(flimo_ctx* c, size_t first, size_t n, int
 extern "C" int flimo_set_normals_chunk(flimo_ctx* c, size_t n) {
   if (!c) return FLIMO_ERR_INVALID;
   c->normals_chunk = n ? n : (size_t)1 << 20;
+  return FLIMO_OK;
+}
+
+// ---- outliers by neighbour statistics (PCL's StatisticalOutlierRemoval / RadiusOutlierRemoval over the map) --------------------
+// kernels: flimo_knn_k.hip.  The search runs in chunks of c->outlier_chunk points into mean[] / cnt[] of the WHOLE range (12 B a
+// point: the threshold needs all of them first); then the sum of the means and |T| (two launches, a wait), mu on the host, the sum
+// of the squared deviations (two launches, a wait), sigma and the threshold on the host, the mask and its two counts (one launch).
+// The removal hands the device mask to the crop's ordered compaction; from there on its host side is the crop's (map_keep_only).
+static void outlier_stats_none(flimo_outlier_stats* s) {
+  if (!s) return;
+  const double dn = std::numeric_limits<double>::quiet_NaN();
+  s->n = s->n_stat = 0; s->mu = s->sigma = s->threshold = dn; s->few = s->far = s->outliers = 0;
+}
+static int outlier_check(flimo_ctx* c, size_t first, size_t n, const flimo_outlier_cfg* cfg, const char* what) {
+  static_assert(FLIMO_KNN_MAX_K == KNNK_MAX_K, "the header's limit is the kernels'");
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
+  if (first > c->map_n || n > c->map_n - first)
+    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
+  if (std::isnan(cfg->max_dist) || cfg->max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: max_dist must be >= 0 or INFINITY", what);
+  if (std::isnan(cfg->std_mul) || cfg->std_mul < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: std_mul must be >= 0 or INFINITY", what);
+  if (cfg->k < 1 || cfg->k > FLIMO_KNN_MAX_K - 1) return fail(c, FLIMO_ERR_UNSUPPORTED, "%s: k must be in 1..%d", what, FLIMO_KNN_MAX_K - 1);
+  if (cfg->min_pts < 0 || cfg->min_pts > cfg->k) return fail(c, FLIMO_ERR_INVALID, "%s: min_pts must be in 0..k", what);
+  return FLIMO_OK;
+}
+struct OutlierScratch {
+  double* mean = nullptr; int32_t* cnt = nullptr; unsigned char* mask = nullptr; uint2* work = nullptr; unsigned* nwork = nullptr;
+  double* part = nullptr; unsigned* part_cnt = nullptr; unsigned long long* words = nullptr;      // words: {sum bits, |T|, few | far << 32}
+  ~OutlierScratch() {
+    (void)hipFree(mean); (void)hipFree(cnt); (void)hipFree(mask); (void)hipFree(work); (void)hipFree(nwork); (void)hipFree(part);
+    (void)hipFree(part_cnt); (void)hipFree(words);
+  }
+};
+// the predicate over [first, first + n), n > 0, arguments checked: d.mean, d.cnt, d.mask filled on the device, *st on the host; ends
+// synchronised
+static int outliers_device(flimo_ctx* c, size_t first, size_t n, const flimo_outlier_cfg& cfg, OutlierScratch& d, flimo_outlier_stats* st) {
+  if (!c->grid_valid) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map outliers: a map of %zu points has no index", c->map_n);
+  ctx_enter(c);
+  const size_t m = std::min(std::min(n, std::max<size_t>(c->outlier_chunk, 1)), (size_t)1 << 24);
+  const unsigned nseg = outlier_segments(n);
+  HIPCHK(c, hipMalloc(&d.mean, n * sizeof(double)));
+  HIPCHK(c, hipMalloc(&d.cnt, n * sizeof(int32_t)));
+  HIPCHK(c, hipMalloc(&d.mask, n));
+  HIPCHK(c, hipMalloc(&d.work, m * sizeof(uint2)));
+  HIPCHK(c, hipMalloc(&d.nwork, sizeof(unsigned)));
+  HIPCHK(c, hipMalloc(&d.part, nseg * sizeof(double)));
+  HIPCHK(c, hipMalloc(&d.part_cnt, nseg * sizeof(unsigned)));
+  HIPCHK(c, hipMalloc(&d.words, 3 * sizeof(unsigned long long)));
+  // (a chunk's worklist is read by its own second launch only: the stream orders the chunks, nothing waits in between)
+  for (size_t a = 0; a < n; a += m)
+    HIPCHK(c, launch_outlier_search(c->stream, c->grid, c->d_map_raw, (unsigned)(first + a), (int)std::min(m, n - a), cfg.k, cfg.max_dist, d.mean + a,
+                                    d.cnt + a, d.work, d.nwork));
+  const int need = std::max(1, cfg.min_pts);
+  unsigned long long w[3] = {0, 0, 0};
+  HIPCHK(c, launch_outlier_sum(c->stream, d.mean, d.cnt, (unsigned)n, need, 0, 0.0, d.part, d.part_cnt, d.words));
+  HIPCHK(c, hipMemcpyAsync(w, d.words, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double dn = std::numeric_limits<double>::quiet_NaN();
+  const uint64_t N = w[1];
+  if (N > n) return fail(c, FLIMO_ERR_HIP, "map outliers: counted %llu of %zu points", (unsigned long long)N, n);
+  double sum_m, mu = dn, sigma = dn, threshold = dn;
+  memcpy(&sum_m, &w[0], sizeof sum_m);
+  if (N > 0) {
+    mu = sum_m / (double)N;
+    sigma = 0.0;
+    if (N > 1) {
+      HIPCHK(c, launch_outlier_sum(c->stream, d.mean, d.cnt, (unsigned)n, need, 1, mu, d.part, d.part_cnt, d.words));
+      HIPCHK(c, hipMemcpyAsync(w, d.words, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      double sum_d;
+      memcpy(&sum_d, &w[0], sizeof sum_d);
+      sigma = std::sqrt(sum_d / (double)(N - 1));
+    }
+    threshold = mu + (double)cfg.std_mul * sigma;
+  }
+  unsigned* counts = reinterpret_cast<unsigned*>(d.words + 2);
+  HIPCHK(c, launch_outlier_mask(c->stream, d.mean, d.cnt, (unsigned)n, cfg.min_pts, need, std::isfinite(cfg.std_mul), threshold, d.mask, counts));
+  HIPCHK(c, hipMemcpyAsync(&w[2], d.words + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  st->n = n; st->n_stat = N; st->mu = mu; st->sigma = sigma; st->threshold = threshold;
+  st->few = w[2] & 0xffffffffull; st->far = w[2] >> 32; st->outliers = st->few + st->far;
+  if (st->outliers > n) return fail(c, FLIMO_ERR_HIP, "map outliers: marked %llu of %zu points", (unsigned long long)st->outliers, n);
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_outliers(flimo_ctx* c, size_t first, size_t n, const flimo_outlier_cfg* cfg, unsigned char* mask, double* mean_dist,
+                                  int32_t* cnt, flimo_outlier_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = outlier_check(c, first, n, cfg, "map outliers"); if (rc) return rc; }
+  if (n == 0) { outlier_stats_none(stats); return FLIMO_OK; }
+  if (n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map outliers: the range must hold fewer than 2^31 points");
+  OutlierScratch d;
+  flimo_outlier_stats st;
+  { const int rc = outliers_device(c, first, n, *cfg, d, &st); if (rc) return rc; }
+  if (mask) HIPCHK(c, hipMemcpyAsync(mask, d.mask, n, hipMemcpyDeviceToHost, c->stream));
+  if (mean_dist) HIPCHK(c, hipMemcpyAsync(mean_dist, d.mean, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (cnt) HIPCHK(c, hipMemcpyAsync(cnt, d.cnt, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (stats) *stats = st;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_remove_outliers(flimo_ctx* c, size_t first, size_t n, const flimo_outlier_cfg* cfg, size_t* removed,
+                                         flimo_outlier_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = outlier_check(c, first, n, cfg, "remove outliers"); if (rc) return rc; }
+  if (n == 0) { if (removed) *removed = 0; outlier_stats_none(stats); return FLIMO_OK; }
+  if (n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "remove outliers: the range must hold fewer than 2^31 points");
+  OutlierScratch d;
+  flimo_outlier_stats st;
+  { const int rc = outliers_device(c, first, n, *cfg, d, &st); if (rc) return rc; }
+  if (removed) *removed = 0;
+  if (stats) *stats = st;
+  if (st.outliers == 0) return FLIMO_OK;               // removing nothing changes nothing
+  const size_t n_old = c->map_n;
+  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
+  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  size_t kept = 0;
+  float bb[6];
+  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d.mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
+  if (kept != n_old - (size_t)st.outliers)
+    return fail(c, FLIMO_ERR_HIP, "remove outliers: the compaction kept %zu of %zu points, %llu marked", kept, n_old, (unsigned long long)st.outliers);
+  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->outlier_removals, &c->outlier_removed, removed, "remove outliers");
+}
+extern "C" int flimo_set_outlier_chunk(flimo_ctx* c, size_t n) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->outlier_chunk = n ? n : (size_t)1 << 20;
   return FLIMO_OK;
 }
 

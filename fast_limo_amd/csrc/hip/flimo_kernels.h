@@ -163,6 +163,11 @@ hipError_t carve_mask(hipStream_t st, const float4* in, size_t n, const CarveCfg
 hipError_t map_carve_compact(hipStream_t st, const float4* in, size_t n, const CarveCfg& cfg, const float* lo, const float* hi, float4* out,
                              int blocks, MapBuildScratch& S, size_t* kept, float bb[6]);
 
+// map_crop_compact with "index outside [first, first + n_mask), or d_mask[index - first] == 0" as the kept points
+// (flimo_map_remove_outliers); d_mask: device, [n_mask]
+hipError_t map_mask_compact(hipStream_t st, const float4* in, size_t n, const unsigned char* d_mask, size_t first, size_t n_mask, float4* out,
+                            int blocks, MapBuildScratch& S, size_t* kept, float bb[6]);
+
 // min/max of n float4 points (NaN-free) -> host bbox[6]
 hipError_t map_bbox(hipStream_t st, const float4* pts, size_t n, MapBuildScratch& S, float bbox_host[6]);
 // Spatial (Morton) sort of the scan: out[i] = (xyz of in[perm[i]], w = bit pattern of perm[i]).
@@ -290,6 +295,22 @@ hipError_t launch_knn_k(hipStream_t st, const GridView& G, const float4* map_raw
 hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, unsigned first, int nq, int k,
                                 float max_dist, int min_pts, const float* viewpoint, float4* normal, int32_t* cnt, double* centroid, double* cov,
                                 double* eig, double* mom, uint2* work, unsigned* nwork);
+// The same search with a list of k + 1 keys for the stored points first .. first + nq - 1 themselves, each ended in its mean
+// neighbour distance (flimo_map_outliers, flimo_c.h): the point's own slot dropped, cnt [nq] = the slots left (<= k), mean [nq] =
+// kk_slot_sum of the float64 widenings of fl_sqrt(sqd) over them / cnt, NaN for cnt 0.  Scratch: work ([nq]), nwork.
+hipError_t launch_outlier_search(hipStream_t st, const GridView& G, const float4* map_raw, unsigned first, int nq, int k, float max_dist,
+                                 double* mean, int32_t* cnt, uint2* work, unsigned* nwork);
+// The statistics over a range's n slots, T = {i : cnt[i] >= need}, in two levels of one fixed shape (flimo_knn_k.hip).  pass 0:
+// out[0] = the bits of the float64 sum of mean over T, out[1] = |T|; pass 1: out[0] = the bits of the sum of (mean - mu)^2 over T.
+// part / part_cnt: outlier_segments(n) words each; out: two device words.
+unsigned outlier_segments(size_t n);
+hipError_t launch_outlier_sum(hipStream_t st, const double* mean, const int32_t* cnt, unsigned n, int need, int pass, double mu, double* part,
+                              unsigned* part_cnt, unsigned long long* out);
+// mask[i] = cnt[i] < min_pts, or (stat_on and cnt[i] >= need and mean[i] > threshold); counts[0] / counts[1] (device): how many by
+// the first / the second rule
+hipError_t launch_outlier_mask(hipStream_t st, const double* mean, const int32_t* cnt, unsigned n, int min_pts, int need, bool stat_on,
+                               double threshold, unsigned char* mask, unsigned* counts);
+
 // The same search with k = 1 for every (pose, point of the resident scan) pair of a chunk of poses (flimo_scan_fitness, flimo_c.h):
 // the world point is transform_kernel's, from poses [np][12] (the upper three rows of PoseMats::RT).  sqd [np][n]: the nearest
 // stored point's squared distance, -1 for an empty query; idx [np][n] (optional): its insertion index, -1; inliers / sum_sqd [np]:

@@ -947,6 +947,148 @@ __global__ __launch_bounds__(KK_BLOCK) void lin_final_kernel(const double* __res
   }
 }
 
+// ---- mean neighbour distances of stored points (flimo_map_outliers) -------------------------------------------------------------
+// Query i is stored point first + i, the search is knnk_normals_kernel's with a list of k + 1 keys: the point is its own neighbour
+// at distance 0.  The group ends the query in registers: the slot whose insertion index is the point's own is dropped -- when no
+// slot holds it and the list is full (more than k exact duplicates of lower index come first), the last one is --, c = the slots
+// left, S = kk_slot_sum over the float64 widenings of fl_sqrt(sqd) with the dropped and the empty slots at +0.0: 8 B + 4 B per
+// point, the list goes nowhere.  The statistics over a range's mean[] / cnt[] have two levels of one fixed shape that depends on n
+// alone (lin_reduce_kernel's):
+//   level 1  the range's slots are cut into segments of OUT_SEG; one workgroup of OUT_RED threads per segment: thread t adds the
+//            terms of slots t, t + OUT_RED, ... of its segment in ascending order (a slot outside T adds +0.0), a butterfly over
+//            the 64 lanes of each wave, then ((wave 0 + wave 1) + (wave 2 + wave 3))
+//   level 2  one thread adds the segment partials in ascending order of the segment
+// The term is m (pass 0, which also counts T) or (m - mu) * (m - mu) (pass 1).  No atomics on floating-point values.
+constexpr int OUT_RED = 256;                    // threads of a level-1 workgroup
+constexpr int OUT_SEG = 4096;                   // slots of a segment: 16 per thread
+
+struct OutlierArgs {
+  unsigned first;        // query i is stored point first + i
+  int nq, k1;            // queries of the chunk; k + 1: the list's length
+  float r2;
+  kk_u64 gate_key;
+};
+
+template <int L>
+__device__ __forceinline__ void knnk_mean_dist(const OutlierArgs& A, int lane, int q, bool live, kk_u64 mine, double* __restrict__ mean,
+                                               int32_t* __restrict__ cnt) {
+  const int sub = lane & (L - 1);
+  const bool has = live && sub < A.k1 && mine < A.gate_key;
+  const bool self = has && (uint32_t)mine == A.first + (unsigned)q;
+  const unsigned long long bs = __ballot(self);
+  const bool any_self = L == 64 ? bs != 0ull : kk_group_mask<L>(bs, lane) != 0u;
+  const bool keep = has && !self && (any_self || sub != A.k1 - 1);      // (no own slot: a result in slot k is the full list's last)
+  const unsigned long long bk = __ballot(keep);
+  const int c = L == 64 ? __popcll(bk) : __popc(kk_group_mask<L>(bk, lane));
+  const double s = kk_slot_sum<L>(keep ? (double)fl_sqrt(kk_key_dist(mine)) : 0.0);
+  if (live && sub == 0) {
+    cnt[q] = c;
+    mean[q] = c > 0 ? s / (double)c : __longlong_as_double(0x7ff8000000000000ll);
+  }
+}
+
+template <int L>
+__global__ __launch_bounds__(KK_BLOCK) void knnk_outlier_kernel(GridView G, OutlierArgs A, const float4* __restrict__ map_raw, double* __restrict__ mean,
+                                                                int32_t* __restrict__ cnt, uint2* __restrict__ work, unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63;
+  const int sub = lane & (L - 1);
+  const size_t gq = ((size_t)blockIdx.x * KK_BLOCK + threadIdx.x) / (unsigned)L;
+  const bool live = gq < (size_t)A.nq;
+  const int q = live ? (int)gq : 0;
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  if (live) { const float4 p = map_raw[(size_t)A.first + (size_t)q]; gx = p.x; gy = p.y; gz = p.z; }
+  kk_u64 mine;
+  unsigned long long cand = 0;
+  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, A.k1, A.r2, A.gate_key, mine, cand);
+  if (!proven) {
+    // (the list's last distance, when there is one, bounds the true one: the walk's first bound)
+    const kk_u64 kth = __shfl(mine, A.k1 - 1, L);
+    if (live && sub == 0) {
+      const unsigned at = atomicAdd(nwork, 1u);
+      work[at] = make_uint2((unsigned)q, __float_as_uint(kth < A.gate_key ? kk_key_dist(kth) : A.r2));
+    }
+  }
+  knnk_mean_dist<L>(A, lane, q, live && proven, mine, mean, cnt);
+}
+
+// the worklist's queries, one wave per entry: knnk_far_kernel's walk, the same end
+__global__ __launch_bounds__(KK_BLOCK, 5) void knnk_outlier_far_kernel(GridView G, OutlierArgs A, const float4* __restrict__ map_raw,
+                                                                       double* __restrict__ mean, int32_t* __restrict__ cnt,
+                                                                       const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int maxdim = grid_maxdim(G);
+  const int ndir = G.ntx * G.nty * G.ntz;
+  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
+  const unsigned n = min(*nwork, (unsigned)A.nq);
+  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < n; w += gridDim.x * (KK_BLOCK / 64)) {
+    const uint2 e = work[w];
+    const int q = (int)min(e.x, (unsigned)(A.nq - 1));
+    const float4 p = map_raw[(size_t)A.first + (size_t)q];
+    kk_u64 mine;
+    unsigned long long cand = 0;
+    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, p.x, p.y, p.z, lane, A.k1, __uint_as_float(e.y), A.gate_key, mine, cand);
+    knnk_mean_dist<64>(A, lane, q, true, mine, mean, cnt);
+  }
+}
+
+// level 1 of the statistics: workgroup `seg` over the slots [seg * OUT_SEG, min(n, (seg + 1) * OUT_SEG)) of the range; T: cnt >= need
+template <int PASS>
+__global__ __launch_bounds__(OUT_RED) void outlier_sum_kernel(const double* __restrict__ mean, const int32_t* __restrict__ cnt, unsigned n, int need,
+                                                              double mu, double* __restrict__ part, unsigned* __restrict__ part_cnt) {
+  __shared__ double s_sum[OUT_RED / 64];
+  __shared__ unsigned s_cnt[OUT_RED / 64];
+  const unsigned seg = blockIdx.x;
+  const unsigned end = min(n, (seg + 1u) * (unsigned)OUT_SEG);
+  double acc = 0.0;
+  unsigned c = 0;
+  for (unsigned i = seg * (unsigned)OUT_SEG + threadIdx.x; i < end; i += OUT_RED) {
+    const bool in = cnt[i] >= need;
+    const double m = mean[i];
+    const double d = m - mu;
+    acc = acc + (in ? (PASS == 0 ? m : d * d) : 0.0);
+    c += in ? 1u : 0u;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) acc = acc + __shfl_xor(acc, o, 64);
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) { s_sum[wave] = acc; s_cnt[wave] = c; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[seg] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+    part_cnt[seg] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+  }
+}
+// level 2: one thread adds the partials in ascending order; out: {the sum's bits, the count}
+__global__ void outlier_final_kernel(const double* __restrict__ part, const unsigned* __restrict__ part_cnt, unsigned nseg,
+                                     unsigned long long* __restrict__ out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double v = 0.0;
+  unsigned long long c = 0;
+  for (unsigned s = 0; s < nseg; s++) { v = v + part[s]; c += part_cnt[s]; }
+  out[0] = (unsigned long long)__double_as_longlong(v);
+  out[1] = c;
+}
+// the predicate: few = cnt < min_pts; far = the statistical rule is on, the point is of T and its mean is beyond the threshold
+__global__ __launch_bounds__(KK_BLOCK) void outlier_mask_kernel(const double* __restrict__ mean, const int32_t* __restrict__ cnt, unsigned n, int min_pts,
+                                                                int need, int stat_on, double threshold, unsigned char* __restrict__ mask,
+                                                                unsigned* __restrict__ counts) {
+  const size_t g = (size_t)blockIdx.x * KK_BLOCK + threadIdx.x;
+  bool few = false, far = false;
+  if (g < (size_t)n) {
+    const int c = cnt[g];
+    few = c < min_pts;
+    far = stat_on != 0 && c >= need && mean[g] > threshold;      // (a NaN threshold -- T is empty -- selects nothing)
+    mask[g] = (few || far) ? 1 : 0;
+  }
+  const unsigned long long bf = __ballot(few), ba = __ballot(far);
+  if ((threadIdx.x & 63) == 0) {
+    if (bf) atomicAdd(&counts[0], (unsigned)__popcll(bf));
+    if (ba) atomicAdd(&counts[1], (unsigned)__popcll(ba));
+  }
+}
+
 // lanes per query from k: a list of k keys needs k lanes
 int knnk_plan(int k) { return k <= 16 ? 16 : 64; }
 
@@ -990,6 +1132,49 @@ hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4*
   const unsigned far_blocks = (unsigned)std::min<size_t>(4096, ((size_t)nq + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
   hipLaunchKernelGGL(knnk_normals_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
   hipLaunchKernelGGL(knnk_normals_finish_kernel, dim3((unsigned)(((size_t)nq + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, A, map_raw, mom, O);
+  return hipGetLastError();
+}
+
+hipError_t launch_outlier_search(hipStream_t st, const GridView& G, const float4* map_raw, unsigned first, int nq, int k, float max_dist,
+                                 double* mean, int32_t* cnt, uint2* work, unsigned* nwork) {
+  if (nq <= 0) return hipSuccess;
+  if (k < 1 || k + 1 > KNNK_MAX_K) return hipErrorInvalidValue;
+  OutlierArgs A;
+  A.first = first; A.nq = nq; A.k1 = k + 1;
+  A.r2 = max_dist * max_dist;                // one float32 product, as launch_knn_k's
+  uint32_t r2_bits;
+  memcpy(&r2_bits, &A.r2, sizeof r2_bits);
+  A.gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
+  hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  const int L = knnk_plan(A.k1);
+  const unsigned blocks = (unsigned)(((size_t)nq * L + KK_BLOCK - 1) / KK_BLOCK);
+  if (L == 16) hipLaunchKernelGGL((knnk_outlier_kernel<16>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, mean, cnt, work, nwork);
+  else hipLaunchKernelGGL((knnk_outlier_kernel<64>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, mean, cnt, work, nwork);
+  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, ((size_t)nq + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
+  hipLaunchKernelGGL(knnk_outlier_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, mean, cnt, work, nwork);
+  return hipGetLastError();
+}
+
+unsigned outlier_segments(size_t n) { return (unsigned)((n + OUT_SEG - 1) / OUT_SEG); }
+
+hipError_t launch_outlier_sum(hipStream_t st, const double* mean, const int32_t* cnt, unsigned n, int need, int pass, double mu, double* part,
+                              unsigned* part_cnt, unsigned long long* out) {
+  if (n == 0) return hipErrorInvalidValue;
+  const unsigned nseg = outlier_segments(n);
+  if (pass == 0) hipLaunchKernelGGL((outlier_sum_kernel<0>), dim3(nseg), dim3(OUT_RED), 0, st, mean, cnt, n, need, mu, part, part_cnt);
+  else hipLaunchKernelGGL((outlier_sum_kernel<1>), dim3(nseg), dim3(OUT_RED), 0, st, mean, cnt, n, need, mu, part, part_cnt);
+  hipLaunchKernelGGL(outlier_final_kernel, dim3(1), dim3(64), 0, st, part, part_cnt, nseg, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_outlier_mask(hipStream_t st, const double* mean, const int32_t* cnt, unsigned n, int min_pts, int need, bool stat_on,
+                               double threshold, unsigned char* mask, unsigned* counts) {
+  if (n == 0) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(outlier_mask_kernel, dim3((unsigned)(((size_t)n + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, mean, cnt, n, min_pts, need,
+                     stat_on ? 1 : 0, threshold, mask, counts);
   return hipGetLastError();
 }
 

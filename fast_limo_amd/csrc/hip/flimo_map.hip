@@ -1673,7 +1673,7 @@ hipError_t voxel_grid(hipStream_t st, const float4* in, size_t n, float leaf, fl
 // desc[t]: bits 0..31 count, bits 32..33 state (0 nothing yet -- the host zeroes the words, 1 the tile's own count, 2 inclusive sum)
 struct CropBox {
   float lo[3], hi[3];
-  __device__ __forceinline__ bool operator()(const float4& p) const {
+  __device__ __forceinline__ bool operator()(const float4& p, uint32_t = 0u) const {      // (the point's index: not used)
     return (p.x >= lo[0]) & (p.x <= hi[0]) & (p.y >= lo[1]) & (p.y <= hi[1]) & (p.z >= lo[2]) & (p.z <= hi[2]);
   }
 };
@@ -1682,7 +1682,8 @@ struct CropBox {
 // and 2 per CU 254 / 51 (1.3 TB/s; shipped), 32 rows and 1 per CU 264 / 51, 4 per CU 309 / 52.
 constexpr int CROP_ROWS = 32;
 constexpr int CROP_TILE = 256 * CROP_ROWS;
-// Keep: the predicate of a kept point (CropBox; CarveKeep below: flimo_map_carve)
+// Keep: the predicate of a kept point, given the point and its index (CropBox; CarveKeep below: flimo_map_carve; MaskKeep:
+// flimo_map_remove_outliers)
 template <class Keep>
 __global__ __launch_bounds__(256) void crop_compact_kernel(const float4* __restrict__ in, uint32_t n, Keep B, uint32_t ntiles,
                                                            unsigned long long* __restrict__ desc, unsigned int* __restrict__ ticket,
@@ -1707,7 +1708,7 @@ __global__ __launch_bounds__(256) void crop_compact_kernel(const float4* __restr
       const uint32_t i = base + (uint32_t)r * 64u + (uint32_t)lane;
       const bool inb = i < n;
       p[r] = inb ? in[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-      const bool k = inb & B(p[r]);
+      const bool k = inb & B(p[r], i);
       keep[r] = __ballot(k);
       n_keep += (unsigned int)__popcll(keep[r]);
     }
@@ -1862,8 +1863,18 @@ struct CarveKeep {
   CarveView V;
   CropBox B;
   int has_box;
-  __device__ __forceinline__ bool operator()(const float4& p) const {
+  __device__ __forceinline__ bool operator()(const float4& p, uint32_t) const {
     return !carve_seen_through(V, p.x, p.y, p.z) & (!has_box | B(p));
+  }
+};
+// kept by flimo_map_remove_outliers: outside the range [first, first + n), or not marked in the range's device mask (an index
+// beyond the map is beyond the range: nothing is read for it)
+struct MaskKeep {
+  const unsigned char* mask;     // [n]
+  uint32_t first, n;
+  __device__ __forceinline__ bool operator()(const float4&, uint32_t i) const {
+    const uint32_t j = i - first;
+    return j < n ? mask[j] == 0 : true;
   }
 };
 
@@ -1957,6 +1968,12 @@ hipError_t map_crop_compact(hipStream_t st, const float4* in, size_t n, const fl
   CropBox B;
   for (int a = 0; a < 3; a++) { B.lo[a] = lo[a]; B.hi[a] = hi[a]; }
   return compact_ordered(st, in, n, B, out, blocks, S, kept, bb);
+}
+hipError_t map_mask_compact(hipStream_t st, const float4* in, size_t n, const unsigned char* d_mask, size_t first, size_t n_mask, float4* out,
+                            int blocks, MapBuildScratch& S, size_t* kept, float bb[6]) {
+  if (!d_mask || first > n || n_mask > n - first) { *kept = 0; return hipErrorInvalidValue; }
+  const MaskKeep K{d_mask, (uint32_t)first, (uint32_t)n_mask};
+  return compact_ordered(st, in, n, K, out, blocks, S, kept, bb);
 }
 hipError_t map_carve_compact(hipStream_t st, const float4* in, size_t n, const CarveCfg& cfg, const float* lo, const float* hi, float4* out,
                              int blocks, MapBuildScratch& S, size_t* kept, float bb[6]) {

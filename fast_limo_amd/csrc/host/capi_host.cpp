@@ -254,6 +254,34 @@ int flimo_loc_map_carve(flimo_loc* L, const double x26[26], const float sensor_x
   return flimo_map_carve(c, x26, sensor_xyz, cfg, lo, hi, removed);
 }
 size_t flimo_loc_last_carve_removed(flimo_loc* L) { return L ? L->map->last_carve_removed() : 0; }
+// no map yet: the answer of an empty one, after the calls' own argument checks
+static int outliers_of_no_map(size_t first, size_t n, const flimo_outlier_cfg* cfg, flimo_outlier_stats* stats) {
+  if (!cfg || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
+  if (std::isnan(cfg->max_dist) || cfg->max_dist < 0.f || std::isnan(cfg->std_mul) || cfg->std_mul < 0.f) return FLIMO_ERR_INVALID;
+  if (cfg->k < 1 || cfg->k > FLIMO_KNN_MAX_K - 1) return FLIMO_ERR_UNSUPPORTED;
+  if (cfg->min_pts < 0 || cfg->min_pts > cfg->k) return FLIMO_ERR_INVALID;
+  if (stats) {
+    stats->n = stats->n_stat = 0; stats->mu = stats->sigma = stats->threshold = (double)NAN; stats->few = stats->far = stats->outliers = 0;
+  }
+  return FLIMO_OK;
+}
+int flimo_loc_map_outliers(flimo_loc* L, size_t first, size_t n, const flimo_outlier_cfg* cfg, unsigned char* mask, double* mean_dist, int32_t* cnt,
+                           flimo_outlier_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
+  if (!c) return outliers_of_no_map(first, n, cfg, stats);
+  return flimo_map_outliers(c, first, n, cfg, mask, mean_dist, cnt, stats);
+}
+int flimo_loc_map_remove_outliers(flimo_loc* L, size_t first, size_t n, const flimo_outlier_cfg* cfg, size_t* removed, flimo_outlier_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();
+  if (!c) {
+    const int rc = outliers_of_no_map(first, n, cfg, stats);
+    if (rc == FLIMO_OK && removed) *removed = 0;
+    return rc;
+  }
+  return flimo_map_remove_outliers(c, first, n, cfg, removed, stats);
+}
 int flimo_loc_map_radius_search(flimo_loc* L, const float* q_xyz, size_t nq, float radius, unsigned flags, uint64_t* offsets, int32_t* idx,
                                 float* sqd, float* xyz, size_t cap, uint64_t* total) {
   if (!L) return FLIMO_ERR_INVALID;

@@ -526,6 +526,27 @@ int Mapper::normals_range(size_t first, size_t n, int k, float max_dist, int min
   return normals_run(nullptr, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
 }
 
+// outliers of the map by neighbour statistics (an insert, a crop or a carve on the worker thread ends first)
+int Mapper::outliers(size_t first, size_t n, const flimo_outlier_cfg& cfg, std::vector<unsigned char>& mask, std::vector<double>* mean_dist,
+                     std::vector<int32_t>* cnt, flimo_outlier_stats* stats) {
+  sync();
+  mask.clear();
+  if (mean_dist) mean_dist->clear();
+  if (cnt) cnt->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (first > flimo_map_size(ctx_) || n > flimo_map_size(ctx_) - first) return FLIMO_ERR_INVALID;
+  mask.assign(n, 0);
+  if (mean_dist) mean_dist->assign(n, (double)NAN);
+  if (cnt) cnt->assign(n, 0);
+  return flimo_map_outliers(ctx_, first, n, &cfg, n ? mask.data() : nullptr, (mean_dist && n) ? mean_dist->data() : nullptr,
+                            (cnt && n) ? cnt->data() : nullptr, stats);
+}
+int Mapper::remove_outliers(size_t first, size_t n, const flimo_outlier_cfg& cfg, size_t* removed, flimo_outlier_stats* stats) {
+  sync();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  return flimo_map_remove_outliers(ctx_, first, n, &cfg, removed, stats);
+}
+
 // fitness of the resident scan at pose hypotheses (an insert or a crop on the worker thread ends first)
 int Mapper::fitness(const double* x26, size_t np, float max_dist, std::vector<int32_t>& inliers, std::vector<double>& sum_sqd,
                     std::vector<float>* nn_sqd, std::vector<int32_t>* nn_idx) {

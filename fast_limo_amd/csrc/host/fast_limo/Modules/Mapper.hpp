@@ -60,6 +60,15 @@ class fast_limo::Mapper {
   // inserts a job on the worker thread BEHIND the insert of the sweep that asked for it, whose scan is still the resident one there.
   void carve(const double x26[26], const float sensor[3], const flimo_carve_cfg& cfg, const float* lo = nullptr, const float* hi = nullptr);
   size_t last_carve_removed() { sync(); return carve_removed_; }   // points the last carve removed
+  // The stored points first .. first + n - 1 that belong to no surface, by the statistics of their k nearest neighbours
+  // (flimo_map_outliers: PCL's StatisticalOutlierRemoval / RadiusOutlierRemoval): mask [n] (1 = outlier), and where a vector is
+  // given mean_dist [n], cnt [n]; stats (may be null).  Changes nothing.  Returns a FLIMO_* code.
+  int outliers(size_t first, size_t n, const flimo_outlier_cfg& cfg, std::vector<unsigned char>& mask, std::vector<double>* mean_dist = nullptr,
+               std::vector<int32_t>* cnt = nullptr, flimo_outlier_stats* stats = nullptr);
+  // ... and forget them (flimo_map_remove_outliers); afterwards the map is as after crop_box.  A whole-map statistic plus a relayout:
+  // the caller's schedule decides when, so it runs at once -- after an insert, a crop or a carve still on the worker thread --
+  // and is not queued.  removed / stats may be null.  Returns a FLIMO_* code.
+  int remove_outliers(size_t first, size_t n, const flimo_outlier_cfg& cfg, size_t* removed = nullptr, flimo_outlier_stats* stats = nullptr);
   // octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the GPU map (flimo_radius_search).  The reference's Mapper hides
   // its octree, so this is an addition: the stored points with (p - query).squaredNorm() < radius * radius (strict, float32), in
   // ascending order of (distance, insertion index) -- the reference's traversal order is not reproduced.  As the template

@@ -139,6 +139,56 @@ int flimo_map_seen_through(flimo_ctx* ctx, const double x26[26], const float sen
  * no pass of this context in flight. */
 int flimo_map_carve(flimo_ctx* ctx, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg,
                     const float lo[3], const float hi[3], size_t* removed);
+/* Forgetting by neighbour statistics: the stored points that belong to no surface -- returns from rain, dust and multipath, the
+ * thin residue a carve leaves behind a departed car.  PCL's StatisticalOutlierRemoval and RadiusOutlierRemoval over the map, one
+ * call, the neighbour lists never leaving the GPU.
+ *
+ * Definition (tests/outliers_common.py restates it in numpy).  Point i of the range is stored point first + i, insertion order:
+ *  - neighbour list L_i = flimo_knn_k(p_i, k + 1, max_dist): the same predicate (strict float32 sqd < max_dist * max_dist, one
+ *    float32 product; INFINITY: no gate), the same unique order (float32 squared-distance bits, then insertion index), over the WHOLE
+ *    map whatever the range.
+ *  - the point itself: the slot whose index is first + i is dropped.  When no slot holds it and the list is full -- more than k exact
+ *    duplicates with lower indices precede the point --, the last slot is dropped.  (A gate that admits not even the point itself:
+ *    the list is empty, nothing is dropped.)  cnt[i] = c_i = the slots left, <= k.
+ *  - distances d_j = (double)sqrtf(sqd_j), the correctly rounded float32 square root, widened.
+ *  - S_i = the pairwise tree ((s0 + s1) + (s2 + s3)) + ... over the 64 slots of L_i in their original positions, the dropped slot
+ *    and the empty slots holding +0.0; mean_dist[i] = m_i = S_i / c_i, NaN for c_i = 0.  The bits depend on the list alone.
+ *  - statistics set T = { i : c_i >= max(1, min_pts) }, N = |T| = n_stat; mu = (sum over T of m_i) / N; sigma = sqrt((sum over T of
+ *    (m_i - mu)^2) / (N - 1)), two passes, 0 for N = 1; threshold = mu + (double)std_mul * sigma.  The two sums are float64, taken
+ *    on the device in one fixed shape over the range's n slots (a slot outside T adds +0.0), no floating-point
+ *    atomics: their bits depend on the stored points, first, n and the cfg only -- not on the chunking, the cell size or the path
+ *    of the search.  The divisions, the square root and the threshold are the host's.  N = 0: mu, sigma and threshold are NaN and
+ *    the statistical rule selects nothing.
+ *  - point i is an outlier iff c_i < min_pts (the count rule: `few`), or std_mul is finite and i is in T and m_i > threshold (the
+ *    statistical rule: `far`).  T makes the two disjoint: outliers = few + far.
+ * min_pts = 0, max_dist = INFINITY is StatisticalOutlierRemoval (mean k, std_mul); std_mul = INFINITY, max_dist = r, min_pts = m
+ * is RadiusOutlierRemoval (radius r, at least m neighbours) for m <= k. */
+typedef struct flimo_outlier_cfg {
+  int   k;         /* neighbours per point, the point itself excluded: 1 .. FLIMO_KNN_MAX_K - 1 (63) */
+  float max_dist;  /* gate as flimo_knn_k (strict sqd < max_dist*max_dist, one float32 product); INFINITY: none */
+  int   min_pts;   /* count rule: a point with fewer neighbours inside the gate is an outlier; 0 .. k; 0: off */
+  float std_mul;   /* statistical rule: mean distance > mu + std_mul * sigma; >= 0; INFINITY: off */
+} flimo_outlier_cfg;
+typedef struct flimo_outlier_stats {
+  uint64_t n, n_stat;          /* points of the range; those that enter mu / sigma */
+  double   mu, sigma, threshold;
+  uint64_t few, far, outliers; /* by the count rule, by the statistical rule, together */
+} flimo_outlier_stats;
+/* The predicate alone over the stored points first .. first + n - 1: mask[i] = 1 where point i is an outlier, 0 elsewhere;
+ * mean_dist[i] = m_i; cnt[i] = c_i; *stats.  Each output may be NULL.  Changes nothing: not the map, not the scan, not the bits of
+ * a later pass.  n = 0 (also on an empty map, first = 0): FLIMO_OK, the counts of *stats 0, mu / sigma / threshold NaN. */
+int flimo_map_outliers(flimo_ctx* ctx, size_t first, size_t n, const flimo_outlier_cfg* cfg, unsigned char* mask, double* mean_dist,
+                       int32_t* cnt, flimo_outlier_stats* stats);
+/* Keeps every stored point that is outside the range or is not an outlier, in insertion order, in one ordered compaction pass (the
+ * range form cleans what was added since the last cleaning; the neighbours are the whole map's all the same).  Afterwards
+ * everything is as flimo_map_crop_box documents: the map is clear() + initialize(kept), insertion indices are renumbered,
+ * flimo_map_last_time is untouched.  *removed (may be NULL) receives how many points went, *stats (may be NULL) the predicate's.
+ * Removing nothing changes nothing; removing everything leaves the map as a crop that removes everything does.
+ * Both calls: FLIMO_ERR_INVALID -- outputs and map untouched -- for a NULL ctx or cfg, first + n beyond flimo_map_size, max_dist
+ * or std_mul NaN or negative, min_pts outside 0..k; FLIMO_ERR_UNSUPPORTED for k outside 1..63.  Same calling rules as
+ * flimo_map_crop_box: no pass of this context in flight. */
+int flimo_map_remove_outliers(flimo_ctx* ctx, size_t first, size_t n, const flimo_outlier_cfg* cfg, size_t* removed,
+                              flimo_outlier_stats* stats);
 size_t flimo_map_size(const flimo_ctx* ctx);
 double flimo_map_last_time(const flimo_ctx* ctx);
 /* copies the stored points (insertion order: what neighbour indices refer to) as packed xyz; *n receives the total count

@@ -99,6 +99,14 @@ int    flimo_loc_map_carve(flimo_loc* L, const double x26[26], const float senso
                            const float hi[3], size_t* removed);
 /* points the last carve removed -- the policy's or flimo_loc_map_carve's (waits for one still running) */
 size_t flimo_loc_last_carve_removed(flimo_loc* L);
+/* flimo_map_outliers / flimo_map_remove_outliers (include/flimo_c.h: same arguments, same results, same error codes) on the map's
+ * context, after an insert, a crop or a carve still running behind the last sweep has ended.  A Localizer that has no map yet
+ * answers like an empty one (first = n = 0: zero counts, NaN statistics).  There is no policy that calls them: a whole-map
+ * statistic plus a relayout belongs on the caller's schedule, not behind every sweep. */
+int    flimo_loc_map_outliers(flimo_loc* L, size_t first, size_t n, const flimo_outlier_cfg* cfg, unsigned char* mask, double* mean_dist,
+                              int32_t* cnt, flimo_outlier_stats* stats);
+int    flimo_loc_map_remove_outliers(flimo_loc* L, size_t first, size_t n, const flimo_outlier_cfg* cfg, size_t* removed,
+                                     flimo_outlier_stats* stats);
 /* octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the Localizer's map: flimo_radius_search (include/flimo_c.h: same
  * arguments, same results, same error codes) on the map's context, after an insert or a crop still running behind the last sweep
  * has ended.  A Localizer that has no map yet answers like an empty one (all offsets 0). */
