@@ -314,6 +314,31 @@ static int ensure_dev(flimo_ctx* c, T*& p, size_t& cap, size_t need, bool keep, 
   return FLIMO_OK;
 }
 
+// The device scratch of one call: get<T>(count) allocates, the destructor frees whatever was got, on every exit path.  Nothing is
+// kept from call to call.  A failed allocation is remembered, later ones are then not tried and return null: ok() after a group of
+// them reports it.
+struct DevScratch {
+  std::vector<void*> got;
+  hipError_t err = hipSuccess;
+  DevScratch() = default;
+  DevScratch(const DevScratch&) = delete;
+  DevScratch& operator=(const DevScratch&) = delete;
+  ~DevScratch() { for (void* p : got) (void)hipFree(p); }
+  template <typename T>
+  T* get(size_t count) {
+    void* p = nullptr;
+    if (err == hipSuccess) err = hipMalloc(&p, count * sizeof(T));
+    if (err != hipSuccess) return nullptr;
+    got.push_back(p);
+    return static_cast<T*>(p);
+  }
+  void drop(void* p) {      // frees one buffer before the call ends
+    got.erase(std::remove(got.begin(), got.end(), p), got.end());
+    (void)hipFree(p);
+  }
+  int ok(flimo_ctx* c) const { return err == hipSuccess ? FLIMO_OK : fail(c, FLIMO_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(err)); }
+};
+
 // (the float32 pose algebra of a pass -- State casts, get_RT / get_RT_inv / get_extr_RT_inv, the conjugate rotations of
 //  calculate_H -- lives in flimo_pose.h: the host and the device filter form the same constants from the same code)
 
@@ -1223,12 +1248,21 @@ extern "C" int flimo_map_points(flimo_ctx* c, float* out, size_t cap, size_t* n)
   return FLIMO_OK;
 }
 
+// ---- what the query entries share ----------------------------------------------------------------
+// never a stored map without its index
+static int ensure_index(flimo_ctx* c) { return !c->grid_valid && c->map_n > 0 ? rebuild_grid(c) : FLIMO_OK; }
+// the distance gate of the k-NN entries; what: the caller's name in the message
+static int check_gate(flimo_ctx* c, const char* what, float max_dist) {
+  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: max_dist must be >= 0 or INFINITY", what);
+  return FLIMO_OK;
+}
+
 // ---- kNN --------------------------------------------------------------------------------------
 extern "C" int flimo_knn(flimo_ctx* c, const float* q, size_t nq, int k, int32_t* idx, float* sqd, int32_t* cnt) {
   if (!c || !q || !idx || !sqd || !cnt) return FLIMO_ERR_INVALID;
   if (k < 1 || k > 5) return fail(c, FLIMO_ERR_UNSUPPORTED, "k must be in 1..5");
   if (nq == 0) return FLIMO_OK;
-  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (!c->grid_valid) {                       // Octree::knn with root_ == nullptr returns nothing
     for (size_t i = 0; i < nq; i++) cnt[i] = 0;
     for (size_t i = 0; i < nq * (size_t)k; i++) { idx[i] = -1; sqd[i] = 0.f; }
@@ -1236,27 +1270,25 @@ extern "C" int flimo_knn(flimo_ctx* c, const float* q, size_t nq, int k, int32_t
   }
   ctx_enter(c);
   // scratch of this call, released on every exit path
-  struct Scratch {
-    float* q = nullptr; int32_t* idx = nullptr; float* sqd = nullptr; int32_t* cnt = nullptr;
-    ~Scratch() { (void)hipFree(q); (void)hipFree(idx); (void)hipFree(sqd); (void)hipFree(cnt); }
-  } d;
-  HIPCHK(c, hipMalloc(&d.q, nq * 3 * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.idx, nq * k * sizeof(int32_t)));
-  HIPCHK(c, hipMalloc(&d.sqd, nq * k * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.cnt, nq * sizeof(int32_t)));
-  HIPCHK(c, hipMemcpyAsync(d.q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  DevScratch d;
+  float* d_q = d.get<float>(nq * 3);
+  int32_t* d_idx = d.get<int32_t>(nq * k);
+  float* d_sqd = d.get<float>(nq * k);
+  int32_t* d_cnt = d.get<int32_t>(nq);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(d_q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
   // (no gate like a pass's MAX_DIST_PLANE: Octree::knn answers from anywhere.  A few rings of cells near the map, then -- round 6 --
   //  the best-first search over the tiles that exist (knn_far_kernel): a query hundreds of metres from every point of a sparse map
   //  of kilometres costs a look at the directory and at the nearest tiles, not (2r+1)^2 row lookups per ring)
-  launch_knn(c->stream, c->grid, d.q, (int)nq, k, 1 << 29, d.idx, d.sqd, d.cnt);
+  launch_knn(c->stream, c->grid, d_q, (int)nq, k, 1 << 29, d_idx, d_sqd, d_cnt);
   if (c->ties && c->gbook.active) {    // exactly tied distances: the reference's first-met choice (device copy of its octree)
     const BookView book{c->gbook.node_c, c->gbook.node_child, c->gbook.node_cnt, c->gbook.root, c->d_tie_settled};
-    launch_knn_tie(c->stream, c->grid, book, d.q, (int)nq, k, d.idx, d.sqd, d.cnt);
+    launch_knn_tie(c->stream, c->grid, book, d_q, (int)nq, k, d_idx, d_sqd, d_cnt);
   }
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(idx, d.idx, nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(sqd, d.sqd, nq * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cnt, d.cnt, nq * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(idx, d_idx, nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(sqd, d_sqd, nq * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cnt, d_cnt, nq * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return FLIMO_OK;
 }
@@ -1275,33 +1307,28 @@ extern "C" int flimo_radius_search(flimo_ctx* c, const float* q, size_t nq, floa
   if (total) *total = 0;
   offsets[0] = 0;
   if (nq == 0) return FLIMO_OK;
-  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (!c->grid_valid) {                       // Octree::radiusSearch with root_ == nullptr returns nothing (Octree.hpp:459)
     for (size_t i = 0; i <= nq; i++) offsets[i] = 0;
     return FLIMO_OK;
   }
   ctx_enter(c);
   // scratch of this call, released on every exit path
-  struct Scratch {
-    float* q = nullptr; uint32_t* cnt = nullptr; unsigned long long* off = nullptr; void* tmp = nullptr;
-    int32_t* idx = nullptr; float* sqd = nullptr; float* xyz = nullptr; unsigned long long *keys = nullptr, *keys2 = nullptr;
-    ~Scratch() {
-      (void)hipFree(q); (void)hipFree(cnt); (void)hipFree(off); (void)hipFree(tmp); (void)hipFree(idx); (void)hipFree(sqd); (void)hipFree(xyz);
-      (void)hipFree(keys); (void)hipFree(keys2);
-    }
-  } d;
+  DevScratch d;
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "offsets are copied as they are");
-  HIPCHK(c, hipMalloc(&d.q, nq * 3 * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.cnt, (nq + 1) * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc(&d.off, (nq + 1) * sizeof(unsigned long long)));
+  float* d_q = d.get<float>(nq * 3);
+  uint32_t* d_cnt = d.get<uint32_t>(nq + 1);
+  unsigned long long* d_off = d.get<unsigned long long>(nq + 1);
+  { const int rc = d.ok(c); if (rc) return rc; }
   size_t scan_bytes = 0;
-  HIPCHK(c, radius_offsets(c->stream, nullptr, scan_bytes, d.cnt, d.off, nq));
-  HIPCHK(c, hipMalloc(&d.tmp, scan_bytes + 16));
-  HIPCHK(c, hipMemcpyAsync(d.q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.cnt + nq, 0, sizeof(uint32_t), c->stream));
-  HIPCHK(c, launch_radius_count(c->stream, c->grid, d.q, (int)nq, radius, d.cnt, nullptr));
-  HIPCHK(c, radius_offsets(c->stream, d.tmp, scan_bytes, d.cnt, d.off, nq));
-  HIPCHK(c, hipMemcpyAsync(offsets, d.off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, radius_offsets(c->stream, nullptr, scan_bytes, d_cnt, d_off, nq));
+  unsigned char* d_tmp = d.get<unsigned char>(scan_bytes + 16);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(d_q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_cnt + nq, 0, sizeof(uint32_t), c->stream));
+  HIPCHK(c, launch_radius_count(c->stream, c->grid, d_q, (int)nq, radius, d_cnt, nullptr));
+  HIPCHK(c, radius_offsets(c->stream, d_tmp, scan_bytes, d_cnt, d_off, nq));
+  HIPCHK(c, hipMemcpyAsync(offsets, d_off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint64_t n = offsets[nq];
   if (total) *total = n;
@@ -1309,25 +1336,28 @@ extern "C" int flimo_radius_search(flimo_ctx* c, const float* q, size_t nq, floa
   if (n > 0x7fffffffull) return fail(c, FLIMO_ERR_TOO_LARGE, "radius search: %llu results (the limit is 2^31 - 1)", (unsigned long long)n);
   if (n > cap) return fail(c, FLIMO_ERR_TOO_LARGE, "radius search: %llu results, room for %zu", (unsigned long long)n, cap);
   if (n == 0) return FLIMO_OK;
-  if (idx) HIPCHK(c, hipMalloc(&d.idx, n * sizeof(int32_t)));
-  if (sqd) HIPCHK(c, hipMalloc(&d.sqd, n * sizeof(float)));
-  if (xyz) HIPCHK(c, hipMalloc(&d.xyz, n * 3 * sizeof(float)));
+  int32_t* d_idx = idx ? d.get<int32_t>(n) : nullptr;
+  float* d_sqd = sqd ? d.get<float>(n) : nullptr;
+  float* d_xyz = xyz ? d.get<float>(n * 3) : nullptr;
+  { const int rc = d.ok(c); if (rc) return rc; }
   if (flags & FLIMO_RADIUS_SORTED) {
-    HIPCHK(c, hipMalloc(&d.keys, n * sizeof(unsigned long long)));
-    HIPCHK(c, hipMalloc(&d.keys2, n * sizeof(unsigned long long)));
+    unsigned long long* d_keys = d.get<unsigned long long>(n);
+    unsigned long long* d_keys2 = d.get<unsigned long long>(n);
+    { const int rc = d.ok(c); if (rc) return rc; }
     size_t sort_bytes = 0;
-    HIPCHK(c, radius_sort_segments(c->stream, nullptr, sort_bytes, d.keys, d.keys2, (size_t)n, nq, d.off));
-    (void)hipFree(d.tmp); d.tmp = nullptr;
-    HIPCHK(c, hipMalloc(&d.tmp, sort_bytes + 16));
-    HIPCHK(c, launch_radius_fill(c->stream, c->grid, d.q, (int)nq, radius, d.off, nullptr, nullptr, nullptr, d.keys));
-    HIPCHK(c, radius_sort_segments(c->stream, d.tmp, sort_bytes, d.keys, d.keys2, (size_t)n, nq, d.off));
-    HIPCHK(c, launch_radius_unpack(c->stream, d.keys2, (size_t)n, c->d_map_raw, d.idx, d.sqd, d.xyz));
+    HIPCHK(c, radius_sort_segments(c->stream, nullptr, sort_bytes, d_keys, d_keys2, (size_t)n, nq, d_off));
+    d.drop(d_tmp);
+    d_tmp = d.get<unsigned char>(sort_bytes + 16);
+    { const int rc = d.ok(c); if (rc) return rc; }
+    HIPCHK(c, launch_radius_fill(c->stream, c->grid, d_q, (int)nq, radius, d_off, nullptr, nullptr, nullptr, d_keys));
+    HIPCHK(c, radius_sort_segments(c->stream, d_tmp, sort_bytes, d_keys, d_keys2, (size_t)n, nq, d_off));
+    HIPCHK(c, launch_radius_unpack(c->stream, d_keys2, (size_t)n, c->d_map_raw, d_idx, d_sqd, d_xyz));
   } else {
-    HIPCHK(c, launch_radius_fill(c->stream, c->grid, d.q, (int)nq, radius, d.off, d.idx, d.sqd, d.xyz, nullptr));
+    HIPCHK(c, launch_radius_fill(c->stream, c->grid, d_q, (int)nq, radius, d_off, d_idx, d_sqd, d_xyz, nullptr));
   }
-  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d.idx, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (sqd) HIPCHK(c, hipMemcpyAsync(sqd, d.sqd, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, d.xyz, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d_idx, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (sqd) HIPCHK(c, hipMemcpyAsync(sqd, d_sqd, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, d_xyz, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return FLIMO_OK;
 }
@@ -1338,19 +1368,17 @@ extern "C" int flimo_radius_candidates(flimo_ctx* c, const float* q, size_t nq, 
   if (!(radius >= 0.f) || std::isinf(radius)) return fail(c, FLIMO_ERR_INVALID, "radius candidates: the radius must be finite and >= 0");
   if (nq > 0x7fff0000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "radius candidates: too many queries");
   if (nq == 0) return FLIMO_OK;
-  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (!c->grid_valid) { for (size_t i = 0; i < nq; i++) cand[i] = 0; return FLIMO_OK; }
   ctx_enter(c);
-  struct Scratch {
-    float* q = nullptr; uint32_t* cnt = nullptr; unsigned long long* cand = nullptr;
-    ~Scratch() { (void)hipFree(q); (void)hipFree(cnt); (void)hipFree(cand); }
-  } d;
-  HIPCHK(c, hipMalloc(&d.q, nq * 3 * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.cnt, nq * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc(&d.cand, nq * sizeof(unsigned long long)));
-  HIPCHK(c, hipMemcpyAsync(d.q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, launch_radius_count(c->stream, c->grid, d.q, (int)nq, radius, d.cnt, d.cand));
-  HIPCHK(c, hipMemcpyAsync(cand, d.cand, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  DevScratch d;
+  float* d_q = d.get<float>(nq * 3);
+  uint32_t* d_cnt = d.get<uint32_t>(nq);
+  unsigned long long* d_cand = d.get<unsigned long long>(nq);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(d_q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_radius_count(c->stream, c->grid, d_q, (int)nq, radius, d_cnt, d_cand));
+  HIPCHK(c, hipMemcpyAsync(cand, d_cand, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return FLIMO_OK;
 }
@@ -1361,11 +1389,11 @@ extern "C" int flimo_radius_candidates(flimo_ctx* c, const float* q, size_t nq, 
 static int knn_k_run(flimo_ctx* c, const float* q, size_t nq, int k, float max_dist, int32_t* idx, float* sqd, float* xyz, int32_t* cnt,
                      uint64_t* cand) {
   static_assert(FLIMO_KNN_MAX_K == KNNK_MAX_K, "the header's limit is the kernels'");
-  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "knn_k: max_dist must be >= 0 or INFINITY");
+  { const int rc = check_gate(c, "knn_k", max_dist); if (rc) return rc; }
   if (k < 1 || k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "knn_k: k must be in 1..%d", FLIMO_KNN_MAX_K);
   if ((unsigned long long)nq * (unsigned long long)k >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "knn_k: nq * k must be below 2^31");
   if (nq == 0) return FLIMO_OK;
-  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (!c->grid_valid) {                       // Octree::knn with root_ == nullptr returns nothing
     for (size_t i = 0; i < nq; i++) { if (cnt) cnt[i] = 0; if (cand) cand[i] = 0; }
     for (size_t i = 0; i < nq * (size_t)k; i++) { if (idx) idx[i] = -1; if (sqd) sqd[i] = 0.f; }
@@ -1374,23 +1402,21 @@ static int knn_k_run(flimo_ctx* c, const float* q, size_t nq, int k, float max_d
   }
   ctx_enter(c);
   // scratch of this call, released on every exit path
-  struct Scratch {
-    float* q = nullptr; int32_t* idx = nullptr; float* sqd = nullptr; float* xyz = nullptr; int32_t* cnt = nullptr; unsigned long long* cand = nullptr;
-    ~Scratch() { (void)hipFree(q); (void)hipFree(idx); (void)hipFree(sqd); (void)hipFree(xyz); (void)hipFree(cnt); (void)hipFree(cand); }
-  } d;
-  HIPCHK(c, hipMalloc(&d.q, nq * 3 * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.idx, nq * k * sizeof(int32_t)));
-  HIPCHK(c, hipMalloc(&d.sqd, nq * k * sizeof(float)));
-  if (xyz) HIPCHK(c, hipMalloc(&d.xyz, nq * k * 3 * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.cnt, nq * sizeof(int32_t)));
-  if (cand) HIPCHK(c, hipMalloc(&d.cand, nq * sizeof(unsigned long long)));
-  HIPCHK(c, hipMemcpyAsync(d.q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, launch_knn_k(c->stream, c->grid, c->d_map_raw, d.q, (int)nq, k, max_dist, d.idx, d.sqd, d.xyz, d.cnt, d.cand));
-  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d.idx, nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (sqd) HIPCHK(c, hipMemcpyAsync(sqd, d.sqd, nq * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, d.xyz, nq * k * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (cnt) HIPCHK(c, hipMemcpyAsync(cnt, d.cnt, nq * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (cand) HIPCHK(c, hipMemcpyAsync(cand, d.cand, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  DevScratch d;
+  float* d_q = d.get<float>(nq * 3);
+  int32_t* d_idx = d.get<int32_t>(nq * k);
+  float* d_sqd = d.get<float>(nq * k);
+  float* d_xyz = xyz ? d.get<float>(nq * k * 3) : nullptr;
+  int32_t* d_cnt = d.get<int32_t>(nq);
+  unsigned long long* d_cand = cand ? d.get<unsigned long long>(nq) : nullptr;
+  { const int rc = d.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(d_q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_knn_k(c->stream, c->grid, c->d_map_raw, d_q, (int)nq, k, max_dist, d_idx, d_sqd, d_xyz, d_cnt, d_cand));
+  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d_idx, nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (sqd) HIPCHK(c, hipMemcpyAsync(sqd, d_sqd, nq * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, d_xyz, nq * k * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (cnt) HIPCHK(c, hipMemcpyAsync(cnt, d_cnt, nq * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (cand) HIPCHK(c, hipMemcpyAsync(cand, d_cand, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return FLIMO_OK;
 }
@@ -1412,13 +1438,13 @@ extern "C" int flimo_knn_k_candidates(flimo_ctx* c, const float* q, size_t nq, i
 static int normals_run(flimo_ctx* c, const float* q, size_t first, size_t nq, int k, float max_dist, int min_pts, const float* viewpoint,
                        float* normal, int32_t* cnt, double* centroid, double* cov, double* eig) {
   if (!normal || !cnt) return fail(c, FLIMO_ERR_INVALID, "map normals: null normal / cnt");
-  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "map normals: max_dist must be >= 0 or INFINITY");
+  { const int rc = check_gate(c, "map normals", max_dist); if (rc) return rc; }
   if (viewpoint && (std::isnan(viewpoint[0]) || std::isnan(viewpoint[1]) || std::isnan(viewpoint[2])))
     return fail(c, FLIMO_ERR_INVALID, "map normals: NaN viewpoint");
   if (k < 1 || k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map normals: k must be in 1..%d", FLIMO_KNN_MAX_K);
   if (nq >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map normals: the number of queries must be below 2^31");
   if (nq == 0) return FLIMO_OK;
-  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (!c->grid_valid) {                       // an empty map: no neighbours anywhere
     const float fn = std::numeric_limits<float>::quiet_NaN();
     const double dn = std::numeric_limits<double>::quiet_NaN();
@@ -1431,35 +1457,29 @@ static int normals_run(flimo_ctx* c, const float* q, size_t first, size_t nq, in
   }
   ctx_enter(c);
   // scratch of this call, released on every exit path
-  struct Scratch {
-    float* q = nullptr; float4* normal = nullptr; int32_t* cnt = nullptr; double *centroid = nullptr, *cov = nullptr, *eig = nullptr;
-    double* mom = nullptr; uint2* work = nullptr; unsigned* nwork = nullptr;
-    ~Scratch() {
-      (void)hipFree(q); (void)hipFree(normal); (void)hipFree(cnt); (void)hipFree(centroid); (void)hipFree(cov); (void)hipFree(eig);
-      (void)hipFree(mom); (void)hipFree(work); (void)hipFree(nwork);
-    }
-  } d;
+  DevScratch d;
   const size_t m = std::min(nq, std::max<size_t>(c->normals_chunk, 1));
-  if (q) HIPCHK(c, hipMalloc(&d.q, m * 3 * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.normal, m * sizeof(float4)));
-  HIPCHK(c, hipMalloc(&d.cnt, m * sizeof(int32_t)));
-  if (centroid) HIPCHK(c, hipMalloc(&d.centroid, m * 3 * sizeof(double)));
-  if (cov) HIPCHK(c, hipMalloc(&d.cov, m * 6 * sizeof(double)));
-  if (eig) HIPCHK(c, hipMalloc(&d.eig, m * 6 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d.mom, m * 9 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d.work, m * sizeof(uint2)));
-  HIPCHK(c, hipMalloc(&d.nwork, sizeof(unsigned)));
+  float* d_q = q ? d.get<float>(m * 3) : nullptr;
+  float4* d_normal = d.get<float4>(m);
+  int32_t* d_cnt = d.get<int32_t>(m);
+  double* d_centroid = centroid ? d.get<double>(m * 3) : nullptr;
+  double* d_cov = cov ? d.get<double>(m * 6) : nullptr;
+  double* d_eig = eig ? d.get<double>(m * 6) : nullptr;
+  double* d_mom = d.get<double>(m * 9);
+  uint2* d_work = d.get<uint2>(m);
+  unsigned* d_nwork = d.get<unsigned>(1);
+  { const int rc = d.ok(c); if (rc) return rc; }
   for (size_t a = 0; a < nq; a += m) {
     const size_t n = std::min(m, nq - a);
-    if (q) HIPCHK(c, hipMemcpyAsync(d.q, q + 3 * a, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_knn_k_normals(c->stream, c->grid, c->d_map_raw, d.q, (unsigned)(first + a), (int)n, k, max_dist, min_pts, viewpoint, d.normal,
-                                   d.cnt, d.centroid, d.cov, d.eig, d.mom, d.work, d.nwork));
-    HIPCHK(c, hipMemcpyAsync(normal + 4 * a, d.normal, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cnt + a, d.cnt, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (centroid) HIPCHK(c, hipMemcpyAsync(centroid + 3 * a, d.centroid, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (cov) HIPCHK(c, hipMemcpyAsync(cov + 6 * a, d.cov, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (eig) HIPCHK(c, hipMemcpyAsync(eig + 6 * a, d.eig, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    // (the next chunk's upload overwrites d.q; the copies above read host memory the caller owns: one wait per chunk)
+    if (q) HIPCHK(c, hipMemcpyAsync(d_q, q + 3 * a, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_knn_k_normals(c->stream, c->grid, c->d_map_raw, d_q, (unsigned)(first + a), (int)n, k, max_dist, min_pts, viewpoint, d_normal,
+                                   d_cnt, d_centroid, d_cov, d_eig, d_mom, d_work, d_nwork));
+    HIPCHK(c, hipMemcpyAsync(normal + 4 * a, d_normal, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt + a, d_cnt, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (centroid) HIPCHK(c, hipMemcpyAsync(centroid + 3 * a, d_centroid, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (cov) HIPCHK(c, hipMemcpyAsync(cov + 6 * a, d_cov, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (eig) HIPCHK(c, hipMemcpyAsync(eig + 6 * a, d_eig, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    // (the next chunk's upload overwrites d_q; the copies above read host memory the caller owns: one wait per chunk)
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return FLIMO_OK;
@@ -1497,44 +1517,41 @@ static int outlier_check(flimo_ctx* c, size_t first, size_t n, const flimo_outli
   if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
   if (first > c->map_n || n > c->map_n - first)
     return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
-  if (std::isnan(cfg->max_dist) || cfg->max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: max_dist must be >= 0 or INFINITY", what);
+  { const int rc = check_gate(c, what, cfg->max_dist); if (rc) return rc; }
   if (std::isnan(cfg->std_mul) || cfg->std_mul < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: std_mul must be >= 0 or INFINITY", what);
   if (cfg->k < 1 || cfg->k > FLIMO_KNN_MAX_K - 1) return fail(c, FLIMO_ERR_UNSUPPORTED, "%s: k must be in 1..%d", what, FLIMO_KNN_MAX_K - 1);
   if (cfg->min_pts < 0 || cfg->min_pts > cfg->k) return fail(c, FLIMO_ERR_INVALID, "%s: min_pts must be in 0..k", what);
   return FLIMO_OK;
 }
-struct OutlierScratch {
-  double* mean = nullptr; int32_t* cnt = nullptr; unsigned char* mask = nullptr; uint2* work = nullptr; unsigned* nwork = nullptr;
-  double* part = nullptr; unsigned* part_cnt = nullptr; unsigned long long* words = nullptr;      // words: {sum bits, |T|, few | far << 32}
-  ~OutlierScratch() {
-    (void)hipFree(mean); (void)hipFree(cnt); (void)hipFree(mask); (void)hipFree(work); (void)hipFree(nwork); (void)hipFree(part);
-    (void)hipFree(part_cnt); (void)hipFree(words);
-  }
+struct OutlierDev {      // what outliers_device leaves on the device for its caller, and the owner of all it allocated
+  DevScratch mem;
+  double* mean = nullptr; int32_t* cnt = nullptr; unsigned char* mask = nullptr;
 };
 // the predicate over [first, first + n), n > 0, arguments checked: d.mean, d.cnt, d.mask filled on the device, *st on the host; ends
 // synchronised
-static int outliers_device(flimo_ctx* c, size_t first, size_t n, const flimo_outlier_cfg& cfg, OutlierScratch& d, flimo_outlier_stats* st) {
-  if (!c->grid_valid) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+static int outliers_device(flimo_ctx* c, size_t first, size_t n, const flimo_outlier_cfg& cfg, OutlierDev& d, flimo_outlier_stats* st) {
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map outliers: a map of %zu points has no index", c->map_n);
   ctx_enter(c);
   const size_t m = std::min(std::min(n, std::max<size_t>(c->outlier_chunk, 1)), (size_t)1 << 24);
   const unsigned nseg = outlier_segments(n);
-  HIPCHK(c, hipMalloc(&d.mean, n * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d.cnt, n * sizeof(int32_t)));
-  HIPCHK(c, hipMalloc(&d.mask, n));
-  HIPCHK(c, hipMalloc(&d.work, m * sizeof(uint2)));
-  HIPCHK(c, hipMalloc(&d.nwork, sizeof(unsigned)));
-  HIPCHK(c, hipMalloc(&d.part, nseg * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d.part_cnt, nseg * sizeof(unsigned)));
-  HIPCHK(c, hipMalloc(&d.words, 3 * sizeof(unsigned long long)));
+  d.mean = d.mem.get<double>(n);
+  d.cnt = d.mem.get<int32_t>(n);
+  d.mask = d.mem.get<unsigned char>(n);
+  uint2* d_work = d.mem.get<uint2>(m);
+  unsigned* d_nwork = d.mem.get<unsigned>(1);
+  double* d_part = d.mem.get<double>(nseg);
+  unsigned* d_part_cnt = d.mem.get<unsigned>(nseg);
+  unsigned long long* d_words = d.mem.get<unsigned long long>(3);      // {sum bits, |T|, few | far << 32}
+  { const int rc = d.mem.ok(c); if (rc) return rc; }
   // (a chunk's worklist is read by its own second launch only: the stream orders the chunks, nothing waits in between)
   for (size_t a = 0; a < n; a += m)
     HIPCHK(c, launch_outlier_search(c->stream, c->grid, c->d_map_raw, (unsigned)(first + a), (int)std::min(m, n - a), cfg.k, cfg.max_dist, d.mean + a,
-                                    d.cnt + a, d.work, d.nwork));
+                                    d.cnt + a, d_work, d_nwork));
   const int need = std::max(1, cfg.min_pts);
   unsigned long long w[3] = {0, 0, 0};
-  HIPCHK(c, launch_outlier_sum(c->stream, d.mean, d.cnt, (unsigned)n, need, 0, 0.0, d.part, d.part_cnt, d.words));
-  HIPCHK(c, hipMemcpyAsync(w, d.words, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, launch_outlier_sum(c->stream, d.mean, d.cnt, (unsigned)n, need, 0, 0.0, d_part, d_part_cnt, d_words));
+  HIPCHK(c, hipMemcpyAsync(w, d_words, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const double dn = std::numeric_limits<double>::quiet_NaN();
   const uint64_t N = w[1];
@@ -1545,8 +1562,8 @@ static int outliers_device(flimo_ctx* c, size_t first, size_t n, const flimo_out
     mu = sum_m / (double)N;
     sigma = 0.0;
     if (N > 1) {
-      HIPCHK(c, launch_outlier_sum(c->stream, d.mean, d.cnt, (unsigned)n, need, 1, mu, d.part, d.part_cnt, d.words));
-      HIPCHK(c, hipMemcpyAsync(w, d.words, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, launch_outlier_sum(c->stream, d.mean, d.cnt, (unsigned)n, need, 1, mu, d_part, d_part_cnt, d_words));
+      HIPCHK(c, hipMemcpyAsync(w, d_words, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
       double sum_d;
       memcpy(&sum_d, &w[0], sizeof sum_d);
@@ -1554,9 +1571,9 @@ static int outliers_device(flimo_ctx* c, size_t first, size_t n, const flimo_out
     }
     threshold = mu + (double)cfg.std_mul * sigma;
   }
-  unsigned* counts = reinterpret_cast<unsigned*>(d.words + 2);
+  unsigned* counts = reinterpret_cast<unsigned*>(d_words + 2);
   HIPCHK(c, launch_outlier_mask(c->stream, d.mean, d.cnt, (unsigned)n, cfg.min_pts, need, std::isfinite(cfg.std_mul), threshold, d.mask, counts));
-  HIPCHK(c, hipMemcpyAsync(&w[2], d.words + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&w[2], d_words + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   st->n = n; st->n_stat = N; st->mu = mu; st->sigma = sigma; st->threshold = threshold;
   st->few = w[2] & 0xffffffffull; st->far = w[2] >> 32; st->outliers = st->few + st->far;
@@ -1569,7 +1586,7 @@ extern "C" int flimo_map_outliers(flimo_ctx* c, size_t first, size_t n, const fl
   { const int rc = outlier_check(c, first, n, cfg, "map outliers"); if (rc) return rc; }
   if (n == 0) { outlier_stats_none(stats); return FLIMO_OK; }
   if (n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map outliers: the range must hold fewer than 2^31 points");
-  OutlierScratch d;
+  OutlierDev d;
   flimo_outlier_stats st;
   { const int rc = outliers_device(c, first, n, *cfg, d, &st); if (rc) return rc; }
   if (mask) HIPCHK(c, hipMemcpyAsync(mask, d.mask, n, hipMemcpyDeviceToHost, c->stream));
@@ -1585,7 +1602,7 @@ extern "C" int flimo_map_remove_outliers(flimo_ctx* c, size_t first, size_t n, c
   { const int rc = outlier_check(c, first, n, cfg, "remove outliers"); if (rc) return rc; }
   if (n == 0) { if (removed) *removed = 0; outlier_stats_none(stats); return FLIMO_OK; }
   if (n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "remove outliers: the range must hold fewer than 2^31 points");
-  OutlierScratch d;
+  OutlierDev d;
   flimo_outlier_stats st;
   { const int rc = outliers_device(c, first, n, *cfg, d, &st); if (rc) return rc; }
   if (removed) *removed = 0;
@@ -3197,18 +3214,39 @@ extern "C" int flimo_scan_to_world(flimo_ctx* c, const double x26[26], float* ou
 // per chunk the poses' matrices go up (pose_from_x26 on the host, as flimo_scan_to_world forms them), three launches (block search,
 // walk over the tiles, the reduction per pose), two numbers per pose -- and the slots, where asked for -- come back; device scratch
 // is the chunk's, whatever np.  Reads d_scan only: d_scan_world and the pass's buffers are left alone.
+// what the two entries over pose hypotheses share: the poses' check (what: the caller's name in the message) ...
+static int check_poses_finite(flimo_ctx* c, const char* what, const double* x26, size_t np) {
+  for (size_t j = 0; j < np; j++)
+    for (int t = 0; t < 7; t++)
+      if (!std::isfinite(x26[26 * j + t])) return fail(c, FLIMO_ERR_INVALID, "%s: pose %zu has a non-finite position or rotation", what, j);
+  return FLIMO_OK;
+}
+// ... the poses per chunk of at most chunk_pairs pairs, n > 0 points each: whole poses, at least one; the kernels' pair numbers are
+// 32-bit and a search launch has the poses as its grid's y ...
+static size_t pose_chunk(size_t chunk_pairs, size_t n, size_t np) {
+  const size_t pairs_max = std::min<size_t>(std::max<size_t>(chunk_pairs, 1), (size_t)1 << 28);
+  return std::min(np, std::min<size_t>(std::max<size_t>(pairs_max / n, 1), FIT_MAX_POSES));
+}
+// ... and the RT rows of k poses, formed in rt and sent to d_poses
+static int upload_poses(flimo_ctx* c, const double* x26, size_t k, std::vector<float>& rt, float* d_poses) {
+  for (size_t j = 0; j < k; j++) {
+    PoseMats P;
+    pose_from_x26(x26 + 26 * j, P);
+    memcpy(&rt[12 * j], P.RT, 12 * sizeof(float));
+  }
+  HIPCHK(c, hipMemcpyAsync(d_poses, rt.data(), k * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  return FLIMO_OK;
+}
 extern "C" int flimo_scan_fitness(flimo_ctx* c, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
                                   int32_t* nn_idx) {
   if (!c) return FLIMO_ERR_INVALID;
   if ((np > 0 && !x26) || !inliers || !sum_sqd) return fail(c, FLIMO_ERR_INVALID, "scan fitness: null poses / inliers / sum_sqd");
-  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "scan fitness: max_dist must be >= 0 or INFINITY");
+  { const int rc = check_gate(c, "scan fitness", max_dist); if (rc) return rc; }
   if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan fitness: the number of poses must be below 2^31");
-  for (size_t j = 0; j < np; j++)
-    for (int t = 0; t < 7; t++)
-      if (!std::isfinite(x26[26 * j + t])) return fail(c, FLIMO_ERR_INVALID, "scan fitness: pose %zu has a non-finite position or rotation", j);
+  { const int rc = check_poses_finite(c, "scan fitness", x26, np); if (rc) return rc; }
   if (np == 0) return FLIMO_OK;
   const size_t n = c->scan_n;
-  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (n == 0 || !c->grid_valid || max_dist == 0.f) {      // an empty scan or map, a gate that admits nothing: every query is empty
     for (size_t j = 0; j < np; j++) { inliers[j] = 0; sum_sqd[j] = 0.0; }
     if (nn_sqd) for (size_t i = 0; i < np * n; i++) nn_sqd[i] = -1.f;
@@ -3218,40 +3256,27 @@ extern "C" int flimo_scan_fitness(flimo_ctx* c, const double* x26, size_t np, fl
   ctx_enter(c);
   { const int rcf = flush_deskew(c); if (rcf) return rcf; }
   // scratch of this call, released on every exit path
-  struct Scratch {
-    float* poses = nullptr; float* sqd = nullptr; int32_t* idx = nullptr; uint2* work = nullptr; unsigned* nwork = nullptr;
-    int32_t* inliers = nullptr; double* sum = nullptr;
-    ~Scratch() {
-      (void)hipFree(poses); (void)hipFree(sqd); (void)hipFree(idx); (void)hipFree(work); (void)hipFree(nwork); (void)hipFree(inliers);
-      (void)hipFree(sum);
-    }
-  } d;
-  // poses per chunk: whole poses, at least one; the kernels' pair numbers are 32-bit and a search launch has the poses as its grid's y
-  const size_t pairs_max = std::min<size_t>(std::max<size_t>(c->fitness_chunk, 1), (size_t)1 << 28);
-  const size_t m = std::min(np, std::min<size_t>(std::max<size_t>(pairs_max / n, 1), FIT_MAX_POSES));
-  HIPCHK(c, hipMalloc(&d.poses, m * 12 * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.sqd, m * n * sizeof(float)));
-  if (nn_idx) HIPCHK(c, hipMalloc(&d.idx, m * n * sizeof(int32_t)));
-  HIPCHK(c, hipMalloc(&d.work, m * n * sizeof(uint2)));
-  HIPCHK(c, hipMalloc(&d.nwork, sizeof(unsigned)));
-  HIPCHK(c, hipMalloc(&d.inliers, m * sizeof(int32_t)));
-  HIPCHK(c, hipMalloc(&d.sum, m * sizeof(double)));
+  DevScratch d;
+  const size_t m = pose_chunk(c->fitness_chunk, n, np);
+  float* d_poses = d.get<float>(m * 12);
+  float* d_sqd = d.get<float>(m * n);
+  int32_t* d_idx = nn_idx ? d.get<int32_t>(m * n) : nullptr;
+  uint2* d_work = d.get<uint2>(m * n);
+  unsigned* d_nwork = d.get<unsigned>(1);
+  int32_t* d_inliers = d.get<int32_t>(m);
+  double* d_sum = d.get<double>(m);
+  { const int rc = d.ok(c); if (rc) return rc; }
   std::vector<float> rt(m * 12);
   for (size_t a = 0; a < np; a += m) {
     const size_t k = std::min(m, np - a);
-    for (size_t j = 0; j < k; j++) {
-      PoseMats P;
-      pose_from_x26(x26 + 26 * (a + j), P);
-      memcpy(&rt[12 * j], P.RT, 12 * sizeof(float));
-    }
-    HIPCHK(c, hipMemcpyAsync(d.poses, rt.data(), k * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_scan_fitness(c->stream, c->grid, c->d_scan, (unsigned)n, d.poses, (unsigned)k, max_dist, d.sqd, d.idx, d.work, d.nwork,
-                                  d.inliers, d.sum));
-    HIPCHK(c, hipMemcpyAsync(inliers + a, d.inliers, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sum_sqd + a, d.sum, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (nn_sqd) HIPCHK(c, hipMemcpyAsync(nn_sqd + a * n, d.sqd, k * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (nn_idx) HIPCHK(c, hipMemcpyAsync(nn_idx + a * n, d.idx, k * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    // (the next chunk's poses overwrite rt and d.poses: one wait per chunk)
+    { const int rc = upload_poses(c, x26 + 26 * a, k, rt, d_poses); if (rc) return rc; }
+    HIPCHK(c, launch_scan_fitness(c->stream, c->grid, c->d_scan, (unsigned)n, d_poses, (unsigned)k, max_dist, d_sqd, d_idx, d_work, d_nwork,
+                                  d_inliers, d_sum));
+    HIPCHK(c, hipMemcpyAsync(inliers + a, d_inliers, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sum_sqd + a, d_sum, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (nn_sqd) HIPCHK(c, hipMemcpyAsync(nn_sqd + a * n, d_sqd, k * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nn_idx) HIPCHK(c, hipMemcpyAsync(nn_idx + a * n, d_idx, k * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    // (the next chunk's poses overwrite rt and d_poses: one wait per chunk)
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return FLIMO_OK;
@@ -3270,16 +3295,14 @@ extern "C" int flimo_scan_linearize(flimo_ctx* c, const double* x26, size_t np, 
                                     double* H, double* g, double* cost, double* rows, int32_t* pair_cnt) {
   if (!c) return FLIMO_ERR_INVALID;
   if ((np > 0 && !x26) || !valid || !H || !g || !cost) return fail(c, FLIMO_ERR_INVALID, "scan linearize: null poses / valid / H / g / cost");
-  if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "scan linearize: max_dist must be >= 0 or INFINITY");
+  { const int rc = check_gate(c, "scan linearize", max_dist); if (rc) return rc; }
   if (std::isnan(max_curv) || max_curv < 0.f) return fail(c, FLIMO_ERR_INVALID, "scan linearize: max_curv must be >= 0 or INFINITY");
   if (k < 3 || k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "scan linearize: k must be in 3..%d", FLIMO_KNN_MAX_K);
   if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan linearize: the number of poses must be below 2^31");
-  for (size_t j = 0; j < np; j++)
-    for (int t = 0; t < 7; t++)
-      if (!std::isfinite(x26[26 * j + t])) return fail(c, FLIMO_ERR_INVALID, "scan linearize: pose %zu has a non-finite position or rotation", j);
+  { const int rc = check_poses_finite(c, "scan linearize", x26, np); if (rc) return rc; }
   if (np == 0) return FLIMO_OK;
   const size_t n = c->scan_n;
-  if (!c->grid_valid && c->map_n > 0) { int rc0 = rebuild_grid(c); if (rc0) return rc0; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (n > ((size_t)1 << 28)) return fail(c, FLIMO_ERR_TOO_LARGE, "scan linearize: a scan of more than 2^28 points");
   if (n == 0 || !c->grid_valid || max_dist == 0.f) {      // an empty scan or map, a gate that admits nothing: no pair has a plane
     for (size_t j = 0; j < np; j++) { valid[j] = 0; cost[j] = 0.0; }
@@ -3292,46 +3315,33 @@ extern "C" int flimo_scan_linearize(flimo_ctx* c, const double* x26, size_t np, 
   ctx_enter(c);
   { const int rcf = flush_deskew(c); if (rcf) return rcf; }
   // scratch of this call, released on every exit path
-  struct Scratch {
-    float* poses = nullptr; int32_t* cnt = nullptr; double* mom = nullptr; uint2* work = nullptr; unsigned* nwork = nullptr; double* rows = nullptr;
-    unsigned char* ok = nullptr; double* part = nullptr; int32_t* part_cnt = nullptr; double* sums = nullptr; int32_t* valid = nullptr;
-    ~Scratch() {
-      (void)hipFree(poses); (void)hipFree(cnt); (void)hipFree(mom); (void)hipFree(work); (void)hipFree(nwork); (void)hipFree(rows); (void)hipFree(ok);
-      (void)hipFree(part); (void)hipFree(part_cnt); (void)hipFree(sums); (void)hipFree(valid);
-    }
-  } d;
-  // poses per chunk: whole poses, at least one; the kernels' pair numbers are 32-bit and a search launch has the poses as its grid's y
-  const size_t pairs_max = std::min<size_t>(std::max<size_t>(c->linearize_chunk, 1), (size_t)1 << 28);
-  const size_t m = std::min(np, std::min<size_t>(std::max<size_t>(pairs_max / n, 1), FIT_MAX_POSES));
+  DevScratch d;
+  const size_t m = pose_chunk(c->linearize_chunk, n, np);
   const size_t nseg = scan_linearize_segments((unsigned)n);
-  HIPCHK(c, hipMalloc(&d.poses, m * 12 * sizeof(float)));
-  HIPCHK(c, hipMalloc(&d.cnt, m * n * sizeof(int32_t)));
-  HIPCHK(c, hipMalloc(&d.mom, m * n * 9 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d.work, m * n * sizeof(uint2)));
-  HIPCHK(c, hipMalloc(&d.nwork, sizeof(unsigned)));
-  HIPCHK(c, hipMalloc(&d.rows, m * n * 7 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d.ok, m * n));
-  HIPCHK(c, hipMalloc(&d.part, m * nseg * 28 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d.part_cnt, m * nseg * sizeof(int32_t)));
-  HIPCHK(c, hipMalloc(&d.sums, m * 28 * sizeof(double)));
-  HIPCHK(c, hipMalloc(&d.valid, m * sizeof(int32_t)));
+  float* d_poses = d.get<float>(m * 12);
+  int32_t* d_cnt = d.get<int32_t>(m * n);
+  double* d_mom = d.get<double>(m * n * 9);
+  uint2* d_work = d.get<uint2>(m * n);
+  unsigned* d_nwork = d.get<unsigned>(1);
+  double* d_rows = d.get<double>(m * n * 7);
+  unsigned char* d_ok = d.get<unsigned char>(m * n);
+  double* d_part = d.get<double>(m * nseg * 28);
+  int32_t* d_part_cnt = d.get<int32_t>(m * nseg);
+  double* d_sums = d.get<double>(m * 28);
+  int32_t* d_valid = d.get<int32_t>(m);
+  { const int rc = d.ok(c); if (rc) return rc; }
   std::vector<float> rt(m * 12);
   std::vector<double> sums(m * 28);
   for (size_t a = 0; a < np; a += m) {
     const size_t kk = std::min(m, np - a);
-    for (size_t j = 0; j < kk; j++) {
-      PoseMats P;
-      pose_from_x26(x26 + 26 * (a + j), P);
-      memcpy(&rt[12 * j], P.RT, 12 * sizeof(float));
-    }
-    HIPCHK(c, hipMemcpyAsync(d.poses, rt.data(), kk * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_scan_linearize(c->stream, c->grid, c->d_map_raw, c->d_scan, (unsigned)n, d.poses, (unsigned)kk, k, max_dist, min_pts, max_curv,
-                                    d.cnt, d.mom, d.work, d.nwork, d.rows, d.ok, d.part, d.part_cnt, d.sums, d.valid));
-    HIPCHK(c, hipMemcpyAsync(valid + a, d.valid, kk * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sums.data(), d.sums, kk * 28 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (rows) HIPCHK(c, hipMemcpyAsync(rows + a * n * 7, d.rows, kk * n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (pair_cnt) HIPCHK(c, hipMemcpyAsync(pair_cnt + a * n, d.cnt, kk * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    // (the next chunk's poses overwrite rt and d.poses: one wait per chunk)
+    { const int rc = upload_poses(c, x26 + 26 * a, kk, rt, d_poses); if (rc) return rc; }
+    HIPCHK(c, launch_scan_linearize(c->stream, c->grid, c->d_map_raw, c->d_scan, (unsigned)n, d_poses, (unsigned)kk, k, max_dist, min_pts, max_curv,
+                                    d_cnt, d_mom, d_work, d_nwork, d_rows, d_ok, d_part, d_part_cnt, d_sums, d_valid));
+    HIPCHK(c, hipMemcpyAsync(valid + a, d_valid, kk * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums.data(), d_sums, kk * 28 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (rows) HIPCHK(c, hipMemcpyAsync(rows + a * n * 7, d_rows, kk * n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (pair_cnt) HIPCHK(c, hipMemcpyAsync(pair_cnt + a * n, d_cnt, kk * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    // (the next chunk's poses overwrite rt and d_poses: one wait per chunk)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t j = 0; j < kk; j++) {
       memcpy(H + 21 * (a + j), &sums[28 * j], 21 * sizeof(double));

@@ -327,9 +327,10 @@ __global__ __launch_bounds__(KK_BLOCK) void knnk_far_kernel(GridView G, const fl
   }
 }
 
-// ---- the two searches once more as device functions, for kernels that end a query differently (below).  knnk_kernel and
-//      knnk_far_kernel above stay as they are: inlining these into them changes their register allocation (92 -> 100 VGPRs, five
-//      waves per SIMD -> four); the text is the same, statement for statement. ----
+// ---- the two searches once more as device functions, for kk_search_kernel / kk_walk_kernel, which end a query as their job says
+//      (below).  knnk_kernel and knnk_far_kernel above stay as they are; the text is the same, statement for statement.  Calling
+//      these from them gives knnk_kernel<16> and knnk_far_kernel 100 VGPRs each (92 and 91 now): four waves per SIMD instead of
+//      five.  __launch_bounds__(KK_BLOCK, 5) on top brings both to 96 VGPRs, with 16 and 12 bytes of scratch per lane. ----
 // The block search of one query by the L lanes of its group (every lane of the wave calls it; a group without a query passes
 // live = false): `mine` ends as this lane's entry of the k-best list.  Returns whether the list is proven exact; if not, the tiles'
 // walk (knnk_tile_walk) has to finish the query.
@@ -453,6 +454,66 @@ __device__ __forceinline__ void knnk_tile_walk(const GridView& G, int maxdim, in
   }
 }
 
+// ---- the search for kernels that end a query otherwise than knnk_store: one pair of kernels over a JOB, passed by value ----------
+// A job numbers its queries by SLOTS and says where they come from and how they end:
+//   slot<L>(at, x, y, z)   the slot of this lane's group and its query; returns whether there is one (if not: slot 0, no query)
+//   total()          the number of slots: the walk clamps a worklist entry by it
+//   query(at, x, y, z)     the query of a slot, for the walk (the pairs' costs a division the search's workgroups do not need)
+//   k, r2, gate_key
+//   finish<L>(lane, at, live, mine, gx, gy, gz)      the end of a query whose list is exact, by the L lanes that hold it; every lane
+//                    of the wave calls it, live = false for a group without a query or with one the walk has yet to finish
+//   LANES            lanes per query, 0: knnk_plan(k);  PAIRS: the slots are (pose, scan point) pairs (KkPairs below)
+// kk_search_kernel is knnk_kernel's search with that end.  A query the block search cannot prove goes to the worklist (its slot,
+// its first bound: the list's k-th distance, when there is one, bounds the true one) by one atomicAdd of its leading lane on
+// `nwork`; kk_walk_kernel, one wave per entry, runs knnk_far_kernel's walk and the same end.
+template <int L>
+__device__ __forceinline__ bool kk_flat_slot(int nq, size_t& at) {      // slots 0 .. nq - 1, KK_BLOCK / L of them per workgroup
+  const size_t gq = ((size_t)blockIdx.x * KK_BLOCK + threadIdx.x) / (unsigned)L;
+  const bool live = gq < (size_t)nq;
+  at = live ? gq : 0;
+  return live;
+}
+
+template <int L, class Job>
+__global__ __launch_bounds__(KK_BLOCK) void kk_search_kernel(GridView G, Job J, uint2* __restrict__ work, unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63;
+  const int sub = lane & (L - 1);
+  size_t at;
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  const bool live = J.template slot<L>(at, gx, gy, gz);
+  kk_u64 mine;
+  unsigned long long cand = 0;
+  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, J.k, J.r2, J.gate_key, mine, cand);
+  if (!proven) {
+    const kk_u64 kth = __shfl(mine, J.k - 1, L);
+    if (live && sub == 0) {
+      const unsigned w = atomicAdd(nwork, 1u);
+      work[w] = make_uint2((unsigned)at, __float_as_uint(kth < J.gate_key ? kk_key_dist(kth) : J.r2));
+    }
+  }
+  J.template finish<L>(lane, at, live && proven, mine, gx, gy, gz);
+}
+
+template <class Job>
+__global__ __launch_bounds__(KK_BLOCK, 5) void kk_walk_kernel(GridView G, Job J, const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int maxdim = grid_maxdim(G);
+  const int ndir = G.ntx * G.nty * G.ntz;
+  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
+  const size_t total = J.total();
+  const unsigned nw = (unsigned)min((size_t)*nwork, total);
+  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < nw; w += gridDim.x * (KK_BLOCK / 64)) {
+    const uint2 e = work[w];
+    const size_t at = min((size_t)e.x, total - 1);
+    float gx, gy, gz;
+    J.query(at, gx, gy, gz);
+    kk_u64 mine;
+    unsigned long long cand = 0;
+    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, gx, gy, gz, lane, J.k, __uint_as_float(e.y), J.gate_key, mine, cand);
+    J.template finish<64>(lane, at, true, mine, gx, gy, gz);
+  }
+}
+
 // ---- normals and covariances of the k-NN neighbourhoods (flimo_map_normals) ---------------------------------------------------
 // The same search; instead of knnk_store the group finishes its query in registers.  Lane `sub` holds slot sub of the list; it
 // loads that stored point and forms r = (double)p - (double)q (exact).  Every sum is a butterfly over the 64 SLOTS of a list,
@@ -558,10 +619,10 @@ __device__ __forceinline__ void knnk_query(const NormalsArgs& A, const float4* _
 // the group's end of a query whose list is exact: cnt, and the record {mean of r (3), sums of the centred products (6)}
 constexpr int KK_MOM = 9;
 template <int L>
-__device__ __forceinline__ void knnk_moments(const NormalsArgs& A, int lane, int q, bool live, kk_u64 mine, float gx, float gy, float gz,
+__device__ __forceinline__ void knnk_moments(int k, kk_u64 gate_key, int lane, int q, bool live, kk_u64 mine, float gx, float gy, float gz,
                                              const float4* __restrict__ map_raw, int32_t* __restrict__ cnt, double* __restrict__ mom) {
   const int sub = lane & (L - 1);
-  const bool has = live && sub < A.k && mine < A.gate_key;
+  const bool has = live && sub < k && mine < gate_key;
   const unsigned long long bal = __ballot(has);
   const int c = L == 64 ? __popcll(bal) : __popc(kk_group_mask<L>(bal, lane));
   const double qx = (double)gx, qy = (double)gy, qz = (double)gz;
@@ -621,131 +682,86 @@ __global__ __launch_bounds__(KK_BLOCK) void knnk_normals_finish_kernel(NormalsAr
   }
 }
 
-// knnk_kernel's search with that end.  A query the block search cannot prove goes to the worklist (its number, its first bound):
-// one atomicAdd of its leading lane on `nwork`.
-template <int L>
-__global__ __launch_bounds__(KK_BLOCK) void knnk_normals_kernel(GridView G, NormalsArgs A, const float4* __restrict__ map_raw, int32_t* __restrict__ cnt,
-                                                                double* __restrict__ mom, uint2* __restrict__ work, unsigned* __restrict__ nwork) {
-  const int lane = threadIdx.x & 63;
-  const int sub = lane & (L - 1);
-  const size_t gq = ((size_t)blockIdx.x * KK_BLOCK + threadIdx.x) / (unsigned)L;
-  const bool live = gq < (size_t)A.nq;
-  const int q = live ? (int)gq : 0;
-  float gx = 0.f, gy = 0.f, gz = 0.f;
-  if (live) knnk_query(A, map_raw, q, gx, gy, gz);
-  kk_u64 mine;
-  unsigned long long cand = 0;
-  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, A.k, A.r2, A.gate_key, mine, cand);
-  if (!proven) {
-    // (the list's k-th distance, when there is one, bounds the true one: knnk_far_kernel's first bound)
-    const kk_u64 kth = __shfl(mine, A.k - 1, L);
-    if (live && sub == 0) {
-      const unsigned at = atomicAdd(nwork, 1u);
-      work[at] = make_uint2((unsigned)q, __float_as_uint(kth < A.gate_key ? kk_key_dist(kth) : A.r2));
-    }
+// the queries of a chunk, ended in their moments (the arguments above are knnk_normals_finish_kernel's too)
+struct NormalsJob : NormalsArgs {
+  static constexpr int LANES = 0;
+  static constexpr bool PAIRS = false;
+  const float4* map_raw;
+  int32_t* cnt;
+  double* mom;
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
+    const bool live = kk_flat_slot<L>(nq, at);
+    if (live) query(at, x, y, z);
+    return live;
   }
-  knnk_moments<L>(A, lane, q, live && proven, mine, gx, gy, gz, map_raw, cnt, mom);
-}
-
-// the worklist's queries, one wave per entry: knnk_far_kernel's walk, the same end
-__global__ __launch_bounds__(KK_BLOCK, 5) void knnk_normals_far_kernel(GridView G, NormalsArgs A, const float4* __restrict__ map_raw,
-                                                                       int32_t* __restrict__ cnt, double* __restrict__ mom,
-                                                                       const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int maxdim = grid_maxdim(G);
-  const int ndir = G.ntx * G.nty * G.ntz;
-  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
-  const unsigned n = min(*nwork, (unsigned)A.nq);
-  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < n; w += gridDim.x * (KK_BLOCK / 64)) {
-    const uint2 e = work[w];
-    const int q = (int)min(e.x, (unsigned)(A.nq - 1));
-    float gx, gy, gz;
-    knnk_query(A, map_raw, q, gx, gy, gz);
-    kk_u64 mine;
-    unsigned long long cand = 0;
-    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, gx, gy, gz, lane, A.k, __uint_as_float(e.y), A.gate_key, mine, cand);
-    knnk_moments<64>(A, lane, q, true, mine, gx, gy, gz, map_raw, cnt, mom);
+  __host__ __device__ size_t total() const { return (size_t)nq; }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { knnk_query(*this, map_raw, (int)at, x, y, z); }
+  template <int L>
+  __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float gx, float gy, float gz) const {
+    knnk_moments<L>(k, gate_key, lane, (int)at, live, mine, gx, gy, gz, map_raw, cnt, mom);
   }
-}
+};
 
 // ---- fitness of the resident scan under pose hypotheses (flimo_scan_fitness) ----------------------------------------------------
 // One query per (pose, scan point) pair: the world point is transform_kernel's (flimo_kernels.hip) float32
 // c0*x + (c1*y + (c2*z + c3)) from the pose's RT, the search is the one above with k = 1 and the gate.  A workgroup serves
-// FIT_QPB consecutive scan points of ONE pose, so the 12 floats of its RT are uniform over the wave.  The nearest key of a pair goes
+// KK_BLOCK / FIT_L consecutive scan points of ONE pose, so the 12 floats of its RT are uniform over the wave.  The nearest key of a pair goes
 // into the pair's slot (sqd, -1.0f when the query is empty; the insertion index beside it when asked for): by the group when the
-// block search proves it, by the walk over the tiles otherwise (worklist, as knnk_normals_kernel).  A third launch, one workgroup
+// block search proves it, by the walk over the tiles otherwise (FitJob).  A third launch, one workgroup
 // per pose, counts and sums the pose's n slots in ONE shape: thread t adds slots t, t + FIT_RED, ... in float64, then a tree over
 // the FIT_RED partials in shared memory.  No atomics on floating-point values: the bits of a pose's sum depend on its slots alone.
 constexpr int FIT_L = 8;                        // lanes per query: a list of one key; measured against 16 (profiles/scan_fitness/README.md)
-constexpr int FIT_QPB = KK_BLOCK / FIT_L;       // queries per workgroup
 constexpr int FIT_RED = 256;                    // threads of the reduction's workgroup
-constexpr unsigned FIT_MAX_GRID_X = 1u << 20;   // a search launch's grid is (workgroups of a pose, poses); a pose of more workgroups takes several launches
 
-struct FitArgs {
+// the (pose, scan point) pairs of a chunk of poses as slots: pair (pose, i) is slot pose * n + i
+struct KkPairs {
   const float4* scan;    // the resident scan (body frame), [n]
   const float* poses;    // the chunk's poses: [np][12], the upper three rows of RT (pose_from_x26)
   unsigned n, np;        // points of the scan, poses of the chunk: n * np <= 2^31, np < 2^16 (the grid's y)
   unsigned b0;           // the search launch's first workgroup of a pose
-  float r2;
-  kk_u64 gate_key;
+  __device__ void world(unsigned pose, unsigned i, float& x, float& y, float& z) const {
+    const float4 p = scan[i];
+    const float* M = poses + 12 * (size_t)pose;
+    x = M[0] * p.x + (M[1] * p.y + (M[2] * p.z + M[3]));
+    y = M[4] * p.x + (M[5] * p.y + (M[6] * p.z + M[7]));
+    z = M[8] * p.x + (M[9] * p.y + (M[10] * p.z + M[11]));
+  }
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {      // a workgroup: KK_BLOCK / L points of pose blockIdx.y
+    const size_t gi = ((size_t)b0 + blockIdx.x) * (KK_BLOCK / L) + threadIdx.x / (unsigned)L;
+    const bool live = gi < (size_t)n;
+    at = live ? (size_t)blockIdx.y * (size_t)n + gi : 0;
+    if (live) world(blockIdx.y, (unsigned)gi, x, y, z);
+    return live;
+  }
+  __host__ __device__ size_t total() const { return (size_t)n * (size_t)np; }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { world((unsigned)(at / n), (unsigned)(at % n), x, y, z); }
 };
-
-__device__ __forceinline__ void fit_world(const FitArgs& A, unsigned pose, unsigned i, float& x, float& y, float& z) {
-  const float4 p = A.scan[i];
-  const float* M = A.poses + 12 * (size_t)pose;
-  x = M[0] * p.x + (M[1] * p.y + (M[2] * p.z + M[3]));
-  y = M[4] * p.x + (M[5] * p.y + (M[6] * p.z + M[7]));
-  z = M[8] * p.x + (M[9] * p.y + (M[10] * p.z + M[11]));
-}
 __device__ __forceinline__ void fit_store(size_t at, bool has, kk_u64 key, float* __restrict__ sqd, int32_t* __restrict__ idx) {
   sqd[at] = has ? kk_key_dist(key) : -1.f;
   if (idx) idx[at] = has ? (int32_t)(uint32_t)key : -1;
 }
 
-template <int L>
-__global__ __launch_bounds__(KK_BLOCK) void fit_search_kernel(GridView G, FitArgs A, float* __restrict__ sqd, int32_t* __restrict__ idx,
-                                                              uint2* __restrict__ work, unsigned* __restrict__ nwork) {
-  const int lane = threadIdx.x & 63;
-  const int sub = lane & (L - 1);
-  const unsigned pose = blockIdx.y;
-  const size_t gi = ((size_t)A.b0 + blockIdx.x) * (KK_BLOCK / L) + threadIdx.x / (unsigned)L;
-  const bool live = gi < (size_t)A.n;
-  float gx = 0.f, gy = 0.f, gz = 0.f;
-  if (live) fit_world(A, pose, (unsigned)gi, gx, gy, gz);
-  kk_u64 mine;
-  unsigned long long cand = 0;
-  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, 1, A.r2, A.gate_key, mine, cand);
-  if (live && sub == 0) {      // (k = 1: the group's first lane holds the list)
-    const size_t at = (size_t)pose * (size_t)A.n + gi;
-    if (!proven) {
-      // (the candidate's distance, when there is one, bounds the true one: the walk's first bound)
-      const unsigned w = atomicAdd(nwork, 1u);
-      work[w] = make_uint2((unsigned)at, __float_as_uint(mine < A.gate_key ? kk_key_dist(mine) : A.r2));
-    }
-    fit_store(at, proven && mine < A.gate_key, mine, sqd, idx);
+// the pairs, each ended in its slot of sqd / idx (k = 1: the group's first lane holds the list)
+struct FitJob {
+  static constexpr int LANES = FIT_L;
+  static constexpr bool PAIRS = true;
+  static constexpr int k = 1;
+  KkPairs P;
+  float r2;
+  kk_u64 gate_key;
+  float* sqd;
+  int32_t* idx;
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const { return P.slot<L>(at, x, y, z); }
+  __host__ __device__ size_t total() const { return P.total(); }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { P.query(at, x, y, z); }
+  template <int L>
+  __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float, float, float) const {
+    if (live && (lane & (L - 1)) == 0) fit_store(at, mine < gate_key, mine, sqd, idx);
   }
-}
-
-// the worklist's pairs, one wave per entry: knnk_far_kernel's walk, the same slot
-__global__ __launch_bounds__(KK_BLOCK, 5) void fit_far_kernel(GridView G, FitArgs A, float* __restrict__ sqd, int32_t* __restrict__ idx,
-                                                              const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int maxdim = grid_maxdim(G);
-  const int ndir = G.ntx * G.nty * G.ntz;
-  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
-  const size_t pairs = (size_t)A.n * (size_t)A.np;
-  const unsigned nw = (unsigned)min((size_t)*nwork, pairs);
-  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < nw; w += gridDim.x * (KK_BLOCK / 64)) {
-    const uint2 e = work[w];
-    const size_t at = min((size_t)e.x, pairs - 1);
-    float gx, gy, gz;
-    fit_world(A, (unsigned)(at / A.n), (unsigned)(at % A.n), gx, gy, gz);
-    kk_u64 mine;
-    unsigned long long cand = 0;
-    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, gx, gy, gz, lane, 1, __uint_as_float(e.y), A.gate_key, mine, cand);
-    if (lane == 0) fit_store(at, mine < A.gate_key, mine, sqd, idx);
-  }
-}
+};
 
 // One workgroup per pose over its n slots: the number of slots that hold a distance and their float64 sum, in one fixed shape.
 __global__ __launch_bounds__(FIT_RED) void fit_reduce_kernel(const float* __restrict__ sqd, unsigned n, int32_t* __restrict__ inliers,
@@ -773,8 +789,8 @@ __global__ __launch_bounds__(FIT_RED) void fit_reduce_kernel(const float* __rest
 }
 
 // ---- point-to-plane normal equations of the resident scan under pose hypotheses (flimo_scan_linearize) --------------------------
-// One query per (pose, scan point) pair, the world point as above.  The search is knnk_normals_kernel's for any k, a workgroup
-// serving KK_BLOCK / L consecutive scan points of ONE pose as fit_search_kernel does; the pair's moments (72 B) and count go to the
+// One query per (pose, scan point) pair, the world point as above.  The search is the normals' for any k, a workgroup serving
+// KK_BLOCK / L consecutive scan points of ONE pose as the fitness' does (LinJob); the pair's moments (72 B) and count go to the
 // chunk's scratch, a pair the block search cannot prove to the worklist and the walk over the tiles.  A third launch, one THREAD per
 // pair, runs kk_plane on the moments -- flimo_map_normals' plane of the query w, bit for bit -- and writes the pair's row
 // {J0..J5, d} and its validity; every term is float64 in the association flimo_c.h states.  The sums have two levels, both of one
@@ -788,71 +804,40 @@ constexpr int LIN_RED = 256;                    // threads of a level-1 workgrou
 constexpr int LIN_SEG = 4096;                   // slots of a segment: 16 per thread
 constexpr int LIN_NUM = 28;                     // 21 of H, 6 of g, the cost
 
-struct LinArgs {
-  FitArgs F;             // scan, poses, n, np, b0, r2, gate_key
-  NormalsArgs N;         // k, need, gate_key (has_vp = 0; the queries are the pairs' world points)
+// the pairs, each ended in its moments; need and max_curv are lin_finish_kernel's
+struct LinJob {
+  static constexpr int LANES = 0;
+  static constexpr bool PAIRS = true;
+  KkPairs P;
+  int need;              // neighbours below which a pair has no plane
   double max_curv;
+  int k;
+  float r2;
+  kk_u64 gate_key;
+  const float4* map_raw;
+  int32_t* cnt;
+  double* mom;
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const { return P.slot<L>(at, x, y, z); }
+  __host__ __device__ size_t total() const { return P.total(); }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { P.query(at, x, y, z); }
+  template <int L>
+  __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float gx, float gy, float gz) const {
+    knnk_moments<L>(k, gate_key, lane, (int)at, live, mine, gx, gy, gz, map_raw, cnt, mom);
+  }
 };
 
-__device__ __forceinline__ void lin_worklist(bool live, int sub, size_t at, kk_u64 kth, const NormalsArgs& N, uint2* __restrict__ work,
-                                             unsigned* __restrict__ nwork) {
-  if (live && sub == 0) {
-    const unsigned w = atomicAdd(nwork, 1u);
-    work[w] = make_uint2((unsigned)at, __float_as_uint(kth < N.gate_key ? kk_key_dist(kth) : N.r2));
-  }
-}
-
-template <int L>
-__global__ __launch_bounds__(KK_BLOCK) void lin_search_kernel(GridView G, LinArgs A, const float4* __restrict__ map_raw, int32_t* __restrict__ cnt,
-                                                              double* __restrict__ mom, uint2* __restrict__ work, unsigned* __restrict__ nwork) {
-  const int lane = threadIdx.x & 63;
-  const int sub = lane & (L - 1);
-  const unsigned pose = blockIdx.y;
-  const size_t gi = ((size_t)A.F.b0 + blockIdx.x) * (KK_BLOCK / L) + threadIdx.x / (unsigned)L;
-  const bool live = gi < (size_t)A.F.n;
-  const size_t at = live ? (size_t)pose * (size_t)A.F.n + gi : 0;
-  float gx = 0.f, gy = 0.f, gz = 0.f;
-  if (live) fit_world(A.F, pose, (unsigned)gi, gx, gy, gz);
-  kk_u64 mine;
-  unsigned long long cand = 0;
-  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, A.N.k, A.N.r2, A.N.gate_key, mine, cand);
-  if (!proven) lin_worklist(live, sub, at, __shfl(mine, A.N.k - 1, L), A.N, work, nwork);
-  knnk_moments<L>(A.N, lane, (int)at, live && proven, mine, gx, gy, gz, map_raw, cnt, mom);
-}
-
-// the worklist's pairs, one wave per entry: knnk_far_kernel's walk, the same end
-__global__ __launch_bounds__(KK_BLOCK, 5) void lin_far_kernel(GridView G, LinArgs A, const float4* __restrict__ map_raw, int32_t* __restrict__ cnt,
-                                                              double* __restrict__ mom, const uint2* __restrict__ work,
-                                                              const unsigned* __restrict__ nwork) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int maxdim = grid_maxdim(G);
-  const int ndir = G.ntx * G.nty * G.ntz;
-  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
-  const size_t pairs = (size_t)A.F.n * (size_t)A.F.np;
-  const unsigned nw = (unsigned)min((size_t)*nwork, pairs);
-  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < nw; w += gridDim.x * (KK_BLOCK / 64)) {
-    const uint2 e = work[w];
-    const size_t at = min((size_t)e.x, pairs - 1);
-    float gx, gy, gz;
-    fit_world(A.F, (unsigned)(at / A.F.n), (unsigned)(at % A.F.n), gx, gy, gz);
-    kk_u64 mine;
-    unsigned long long cand = 0;
-    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, gx, gy, gz, lane, A.N.k, __uint_as_float(e.y), A.N.gate_key, mine, cand);
-    knnk_moments<64>(A.N, lane, (int)at, true, mine, gx, gy, gz, map_raw, cnt, mom);
-  }
-}
-
 // One thread per pair, after both searches: the plane as knnk_normals_finish_kernel forms it, the validity, the row.
-__global__ __launch_bounds__(KK_BLOCK) void lin_finish_kernel(LinArgs A, const int32_t* __restrict__ cnt, const double* __restrict__ mom,
+__global__ __launch_bounds__(KK_BLOCK) void lin_finish_kernel(LinJob A, const int32_t* __restrict__ cnt, const double* __restrict__ mom,
                                                               double* __restrict__ rows, unsigned char* __restrict__ ok) {
   const size_t at = (size_t)blockIdx.x * KK_BLOCK + threadIdx.x;
-  if (at >= (size_t)A.F.n * (size_t)A.F.np) return;
-  const unsigned pose = (unsigned)(at / A.F.n), i = (unsigned)(at % A.F.n);
+  if (at >= (size_t)A.P.n * (size_t)A.P.np) return;
+  const unsigned pose = (unsigned)(at / A.P.n), i = (unsigned)(at % A.P.n);
   float gx, gy, gz;
-  fit_world(A.F, pose, i, gx, gy, gz);
+  A.P.world(pose, i, gx, gy, gz);
   const double wx = (double)gx, wy = (double)gy, wz = (double)gz;
   const int c = cnt[at];
-  const bool enough = c >= A.N.need;
+  const bool enough = c >= A.need;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const double* M = mom + (size_t)KK_MOM * at;
   const double n = (double)c;
@@ -868,10 +853,10 @@ __global__ __launch_bounds__(KK_BLOCK) void lin_finish_kernel(LinArgs A, const i
   const bool valid = enough && curv <= A.max_curv;
   const double cx = wx + mx, cy = wy + my, cz = wz + mz;      // the centroid as flimo_map_normals returns it
   const double d = nx * (wx - cx) + (ny * (wy - cy) + nz * (wz - cz));
-  const float* R = A.F.poses + 12 * (size_t)pose;
+  const float* R = A.P.poses + 12 * (size_t)pose;
   const double a0 = (double)R[0] * nx + ((double)R[4] * ny + (double)R[8] * nz), a1 = (double)R[1] * nx + ((double)R[5] * ny + (double)R[9] * nz),
                a2 = (double)R[2] * nx + ((double)R[6] * ny + (double)R[10] * nz);
-  const float4 p4 = A.F.scan[i];
+  const float4 p4 = A.P.scan[i];
   const double px = (double)p4.x, py = (double)p4.y, pz = (double)p4.z;
   const double b0 = py * a2 - pz * a1, b1 = pz * a0 - px * a2, b2 = px * a1 - py * a0;
   double* Rw = rows + (size_t)7 * at;
@@ -948,7 +933,7 @@ __global__ __launch_bounds__(KK_BLOCK) void lin_final_kernel(const double* __res
 }
 
 // ---- mean neighbour distances of stored points (flimo_map_outliers) -------------------------------------------------------------
-// Query i is stored point first + i, the search is knnk_normals_kernel's with a list of k + 1 keys: the point is its own neighbour
+// Query i is stored point first + i, the search is the normals' with a list of k + 1 keys (OutlierJob): the point is its own neighbour
 // at distance 0.  The group ends the query in registers: the slot whose insertion index is the point's own is dropped -- when no
 // slot holds it and the list is full (more than k exact duplicates of lower index come first), the last one is --, c = the slots
 // left, S = kk_slot_sum over the float64 widenings of fl_sqrt(sqd) with the dropped and the empty slots at +0.0: 8 B + 4 B per
@@ -962,22 +947,15 @@ __global__ __launch_bounds__(KK_BLOCK) void lin_final_kernel(const double* __res
 constexpr int OUT_RED = 256;                    // threads of a level-1 workgroup
 constexpr int OUT_SEG = 4096;                   // slots of a segment: 16 per thread
 
-struct OutlierArgs {
-  unsigned first;        // query i is stored point first + i
-  int nq, k1;            // queries of the chunk; k + 1: the list's length
-  float r2;
-  kk_u64 gate_key;
-};
-
 template <int L>
-__device__ __forceinline__ void knnk_mean_dist(const OutlierArgs& A, int lane, int q, bool live, kk_u64 mine, double* __restrict__ mean,
-                                               int32_t* __restrict__ cnt) {
+__device__ __forceinline__ void knnk_mean_dist(unsigned first, int k1, kk_u64 gate_key, int lane, int q, bool live, kk_u64 mine,
+                                               double* __restrict__ mean, int32_t* __restrict__ cnt) {
   const int sub = lane & (L - 1);
-  const bool has = live && sub < A.k1 && mine < A.gate_key;
-  const bool self = has && (uint32_t)mine == A.first + (unsigned)q;
+  const bool has = live && sub < k1 && mine < gate_key;
+  const bool self = has && (uint32_t)mine == first + (unsigned)q;
   const unsigned long long bs = __ballot(self);
   const bool any_self = L == 64 ? bs != 0ull : kk_group_mask<L>(bs, lane) != 0u;
-  const bool keep = has && !self && (any_self || sub != A.k1 - 1);      // (no own slot: a result in slot k is the full list's last)
+  const bool keep = has && !self && (any_self || sub != k1 - 1);      // (no own slot: a result in slot k is the full list's last)
   const unsigned long long bk = __ballot(keep);
   const int c = L == 64 ? __popcll(bk) : __popc(kk_group_mask<L>(bk, lane));
   const double s = kk_slot_sum<L>(keep ? (double)fl_sqrt(kk_key_dist(mine)) : 0.0);
@@ -987,49 +965,30 @@ __device__ __forceinline__ void knnk_mean_dist(const OutlierArgs& A, int lane, i
   }
 }
 
-template <int L>
-__global__ __launch_bounds__(KK_BLOCK) void knnk_outlier_kernel(GridView G, OutlierArgs A, const float4* __restrict__ map_raw, double* __restrict__ mean,
-                                                                int32_t* __restrict__ cnt, uint2* __restrict__ work, unsigned* __restrict__ nwork) {
-  const int lane = threadIdx.x & 63;
-  const int sub = lane & (L - 1);
-  const size_t gq = ((size_t)blockIdx.x * KK_BLOCK + threadIdx.x) / (unsigned)L;
-  const bool live = gq < (size_t)A.nq;
-  const int q = live ? (int)gq : 0;
-  float gx = 0.f, gy = 0.f, gz = 0.f;
-  if (live) { const float4 p = map_raw[(size_t)A.first + (size_t)q]; gx = p.x; gy = p.y; gz = p.z; }
-  kk_u64 mine;
-  unsigned long long cand = 0;
-  const bool proven = knnk_block_search<L>(G, live, gx, gy, gz, lane, A.k1, A.r2, A.gate_key, mine, cand);
-  if (!proven) {
-    // (the list's last distance, when there is one, bounds the true one: the walk's first bound)
-    const kk_u64 kth = __shfl(mine, A.k1 - 1, L);
-    if (live && sub == 0) {
-      const unsigned at = atomicAdd(nwork, 1u);
-      work[at] = make_uint2((unsigned)q, __float_as_uint(kth < A.gate_key ? kk_key_dist(kth) : A.r2));
-    }
+// the stored points of a chunk, ended in their mean neighbour distance
+struct OutlierJob {
+  static constexpr int LANES = 0;
+  static constexpr bool PAIRS = false;
+  unsigned first;        // query i is stored point first + i
+  int nq, k;             // queries of the chunk; the list's length: the neighbours asked for + 1
+  float r2;
+  kk_u64 gate_key;
+  const float4* map_raw;
+  double* mean;
+  int32_t* cnt;
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
+    const bool live = kk_flat_slot<L>(nq, at);
+    if (live) query(at, x, y, z);
+    return live;
   }
-  knnk_mean_dist<L>(A, lane, q, live && proven, mine, mean, cnt);
-}
-
-// the worklist's queries, one wave per entry: knnk_far_kernel's walk, the same end
-__global__ __launch_bounds__(KK_BLOCK, 5) void knnk_outlier_far_kernel(GridView G, OutlierArgs A, const float4* __restrict__ map_raw,
-                                                                       double* __restrict__ mean, int32_t* __restrict__ cnt,
-                                                                       const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int maxdim = grid_maxdim(G);
-  const int ndir = G.ntx * G.nty * G.ntz;
-  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
-  const unsigned n = min(*nwork, (unsigned)A.nq);
-  for (unsigned w = blockIdx.x * (KK_BLOCK / 64) + wave; w < n; w += gridDim.x * (KK_BLOCK / 64)) {
-    const uint2 e = work[w];
-    const int q = (int)min(e.x, (unsigned)(A.nq - 1));
-    const float4 p = map_raw[(size_t)A.first + (size_t)q];
-    kk_u64 mine;
-    unsigned long long cand = 0;
-    knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, p.x, p.y, p.z, lane, A.k1, __uint_as_float(e.y), A.gate_key, mine, cand);
-    knnk_mean_dist<64>(A, lane, q, true, mine, mean, cnt);
+  __host__ __device__ size_t total() const { return (size_t)nq; }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
+  template <int L>
+  __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float, float, float) const {
+    knnk_mean_dist<L>(first, k, gate_key, lane, (int)at, live, mine, mean, cnt);
   }
-}
+};
 
 // level 1 of the statistics: workgroup `seg` over the slots [seg * OUT_SEG, min(n, (seg + 1) * OUT_SEG)) of the range; T: cnt >= need
 template <int PASS>
@@ -1092,14 +1051,47 @@ __global__ __launch_bounds__(KK_BLOCK) void outlier_mask_kernel(const double* __
 // lanes per query from k: a list of k keys needs k lanes
 int knnk_plan(int k) { return k <= 16 ? 16 : 64; }
 
+// the gate: r2 [m^2] and the key every list starts filled with
+static void kk_gate(float max_dist, float& r2, kk_u64& gate_key) {
+  r2 = max_dist * max_dist;                  // one float32 product, as the radius search's (Octree.hpp:467); INFINITY: no gate
+  uint32_t r2_bits;
+  memcpy(&r2_bits, &r2, sizeof r2_bits);
+  gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
+}
+
+constexpr unsigned KK_MAX_GRID_X = 1u << 20;    // the pairs' search grid is (workgroups of a pose, poses); a pose of more workgroups takes several launches
+
+template <int L, class Job>
+static void kk_launch_search(hipStream_t st, const GridView& G, Job J, uint2* work, unsigned* nwork) {
+  constexpr unsigned qpb = KK_BLOCK / L;      // queries per workgroup
+  if constexpr (Job::PAIRS) {
+    const unsigned bpp = (unsigned)(((size_t)J.P.n + qpb - 1) / qpb);      // workgroups per pose
+    for (J.P.b0 = 0; J.P.b0 < bpp; J.P.b0 += KK_MAX_GRID_X)
+      hipLaunchKernelGGL((kk_search_kernel<L, Job>), dim3(std::min(bpp - J.P.b0, KK_MAX_GRID_X), J.P.np), dim3(KK_BLOCK), 0, st, G, J, work, nwork);
+  } else {
+    hipLaunchKernelGGL((kk_search_kernel<L, Job>), dim3((unsigned)((J.total() + qpb - 1) / qpb)), dim3(KK_BLOCK), 0, st, G, J, work, nwork);
+  }
+}
+// the worklist emptied, the block search, the walk over the tiles of what it could not prove
+template <class Job>
+static hipError_t kk_launch(hipStream_t st, const GridView& G, const Job& J, uint2* work, unsigned* nwork) {
+  const hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  if constexpr (Job::LANES != 0) kk_launch_search<Job::LANES>(st, G, J, work, nwork);
+  else if (knnk_plan(J.k) == 16) kk_launch_search<16>(st, G, J, work, nwork);
+  else kk_launch_search<64>(st, G, J, work, nwork);
+  const unsigned walk_blocks = (unsigned)std::min<size_t>(4096, (J.total() + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
+  hipLaunchKernelGGL(kk_walk_kernel<Job>, dim3(walk_blocks), dim3(KK_BLOCK), 0, st, G, J, work, nwork);
+  return hipSuccess;
+}
+
 hipError_t launch_knn_k(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, int nq, int k, float max_dist, int32_t* idx,
                         float* sqd, float* xyz, int32_t* cnt, unsigned long long* cand) {
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
-  const float r2 = max_dist * max_dist;      // one float32 product, as the radius search's (Octree.hpp:467); INFINITY: no gate
-  uint32_t r2_bits;
-  memcpy(&r2_bits, &r2, sizeof r2_bits);
-  const kk_u64 gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
+  float r2;
+  kk_u64 gate_key;
+  kk_gate(max_dist, r2, gate_key);
   const int L = knnk_plan(k);
   const unsigned blocks = (unsigned)(((size_t)nq * L + KK_BLOCK - 1) / KK_BLOCK);
   if (L == 16) hipLaunchKernelGGL((knnk_kernel<16>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, q, nq, k, r2, gate_key, map_raw, idx, sqd, xyz, cnt, cand);
@@ -1114,24 +1106,16 @@ hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4*
                                 double* eig, double* mom, uint2* work, unsigned* nwork) {
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
-  NormalsArgs A;
-  A.qxyz = q; A.first = first; A.nq = nq; A.k = k; A.need = std::max(3, min_pts);
-  A.r2 = max_dist * max_dist;
-  uint32_t r2_bits;
-  memcpy(&r2_bits, &A.r2, sizeof r2_bits);
-  A.gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
-  A.has_vp = viewpoint != nullptr;
-  A.vx = viewpoint ? viewpoint[0] : 0.f; A.vy = viewpoint ? viewpoint[1] : 0.f; A.vz = viewpoint ? viewpoint[2] : 0.f;
+  NormalsJob J;
+  J.qxyz = q; J.first = first; J.nq = nq; J.k = k; J.need = std::max(3, min_pts);
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.has_vp = viewpoint != nullptr;
+  J.vx = viewpoint ? viewpoint[0] : 0.f; J.vy = viewpoint ? viewpoint[1] : 0.f; J.vz = viewpoint ? viewpoint[2] : 0.f;
+  J.map_raw = map_raw; J.cnt = cnt; J.mom = mom;
   const NormalsOut O{normal, cnt, centroid, cov, eig};
-  hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
+  const hipError_t e = kk_launch(st, G, J, work, nwork);
   if (e != hipSuccess) return e;
-  const int L = knnk_plan(k);
-  const unsigned blocks = (unsigned)(((size_t)nq * L + KK_BLOCK - 1) / KK_BLOCK);
-  if (L == 16) hipLaunchKernelGGL((knnk_normals_kernel<16>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
-  else hipLaunchKernelGGL((knnk_normals_kernel<64>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
-  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, ((size_t)nq + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
-  hipLaunchKernelGGL(knnk_normals_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
-  hipLaunchKernelGGL(knnk_normals_finish_kernel, dim3((unsigned)(((size_t)nq + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, A, map_raw, mom, O);
+  hipLaunchKernelGGL(knnk_normals_finish_kernel, dim3((unsigned)(((size_t)nq + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, static_cast<const NormalsArgs&>(J), map_raw, mom, O);
   return hipGetLastError();
 }
 
@@ -1139,21 +1123,12 @@ hipError_t launch_outlier_search(hipStream_t st, const GridView& G, const float4
                                  double* mean, int32_t* cnt, uint2* work, unsigned* nwork) {
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k + 1 > KNNK_MAX_K) return hipErrorInvalidValue;
-  OutlierArgs A;
-  A.first = first; A.nq = nq; A.k1 = k + 1;
-  A.r2 = max_dist * max_dist;                // one float32 product, as launch_knn_k's
-  uint32_t r2_bits;
-  memcpy(&r2_bits, &A.r2, sizeof r2_bits);
-  A.gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
-  hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
-  if (e != hipSuccess) return e;
-  const int L = knnk_plan(A.k1);
-  const unsigned blocks = (unsigned)(((size_t)nq * L + KK_BLOCK - 1) / KK_BLOCK);
-  if (L == 16) hipLaunchKernelGGL((knnk_outlier_kernel<16>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, mean, cnt, work, nwork);
-  else hipLaunchKernelGGL((knnk_outlier_kernel<64>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, mean, cnt, work, nwork);
-  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, ((size_t)nq + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
-  hipLaunchKernelGGL(knnk_outlier_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, mean, cnt, work, nwork);
-  return hipGetLastError();
+  OutlierJob J;
+  J.first = first; J.nq = nq; J.k = k + 1;
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.map_raw = map_raw; J.mean = mean; J.cnt = cnt;
+  const hipError_t e = kk_launch(st, G, J, work, nwork);
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 unsigned outlier_segments(size_t n) { return (unsigned)((n + OUT_SEG - 1) / OUT_SEG); }
@@ -1182,20 +1157,12 @@ hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* 
                                float* sqd, int32_t* idx, uint2* work, unsigned* nwork, int32_t* inliers, double* sum_sqd) {
   if (n == 0 || np == 0) return hipSuccess;
   if ((unsigned long long)n * np > 0x80000000ull || np > FIT_MAX_POSES) return hipErrorInvalidValue;
-  FitArgs A;
-  A.scan = scan; A.poses = poses; A.n = n; A.np = np; A.b0 = 0;
-  A.r2 = max_dist * max_dist;                // one float32 product, as launch_knn_k's
-  uint32_t r2_bits;
-  memcpy(&r2_bits, &A.r2, sizeof r2_bits);
-  A.gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
-  hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
+  FitJob J;
+  J.P = KkPairs{scan, poses, n, np, 0};
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.sqd = sqd; J.idx = idx;
+  const hipError_t e = kk_launch(st, G, J, work, nwork);
   if (e != hipSuccess) return e;
-  const size_t pairs = (size_t)n * np;
-  const unsigned bpp = (unsigned)(((size_t)n + FIT_QPB - 1) / FIT_QPB);      // workgroups per pose
-  for (; A.b0 < bpp; A.b0 += FIT_MAX_GRID_X)
-    hipLaunchKernelGGL((fit_search_kernel<FIT_L>), dim3(std::min(bpp - A.b0, FIT_MAX_GRID_X), np), dim3(KK_BLOCK), 0, st, G, A, sqd, idx, work, nwork);
-  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, (pairs + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
-  hipLaunchKernelGGL(fit_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, sqd, idx, work, nwork);
   hipLaunchKernelGGL(fit_reduce_kernel, dim3(np), dim3(FIT_RED), 0, st, sqd, n, inliers, sum_sqd);
   return hipGetLastError();
 }
@@ -1207,31 +1174,17 @@ hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4
                                  unsigned* nwork, double* rows, unsigned char* ok, double* part, int32_t* part_cnt, double* sums, int32_t* valid) {
   if (n == 0 || np == 0) return hipSuccess;
   if ((unsigned long long)n * np > 0x10000000ull || np > FIT_MAX_POSES || k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
-  LinArgs A;
-  A.F.scan = scan; A.F.poses = poses; A.F.n = n; A.F.np = np; A.F.b0 = 0;
-  A.F.r2 = max_dist * max_dist;              // one float32 product, as launch_knn_k's
-  uint32_t r2_bits;
-  memcpy(&r2_bits, &A.F.r2, sizeof r2_bits);
-  A.F.gate_key = std::isinf(max_dist) ? KK_NONE : (kk_u64)r2_bits << 32;
-  A.N.qxyz = nullptr; A.N.first = 0; A.N.nq = 0; A.N.k = k; A.N.need = std::max(3, min_pts);
-  A.N.r2 = A.F.r2; A.N.gate_key = A.F.gate_key;
-  A.N.vx = A.N.vy = A.N.vz = 0.f; A.N.has_vp = 0;
-  A.max_curv = (double)max_curv;
-  hipError_t e = hipMemsetAsync(nwork, 0, sizeof(unsigned), st);
+  LinJob J;
+  J.P = KkPairs{scan, poses, n, np, 0};
+  J.need = std::max(3, min_pts);
+  J.max_curv = (double)max_curv;
+  J.k = k;
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.map_raw = map_raw; J.cnt = cnt; J.mom = mom;
+  const hipError_t e = kk_launch(st, G, J, work, nwork);
   if (e != hipSuccess) return e;
   const size_t pairs = (size_t)n * np;
-  const int L = knnk_plan(k);
-  const unsigned qpb = (unsigned)(KK_BLOCK / L);
-  const unsigned bpp = (unsigned)(((size_t)n + qpb - 1) / qpb);      // workgroups per pose
-  for (; A.F.b0 < bpp; A.F.b0 += FIT_MAX_GRID_X) {
-    const dim3 grid(std::min(bpp - A.F.b0, FIT_MAX_GRID_X), np);
-    if (L == 16) hipLaunchKernelGGL((lin_search_kernel<16>), grid, dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
-    else hipLaunchKernelGGL((lin_search_kernel<64>), grid, dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
-  }
-  A.F.b0 = 0;
-  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, (pairs + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
-  hipLaunchKernelGGL(lin_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, A, map_raw, cnt, mom, work, nwork);
-  hipLaunchKernelGGL(lin_finish_kernel, dim3((unsigned)((pairs + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, A, cnt, mom, rows, ok);
+  hipLaunchKernelGGL(lin_finish_kernel, dim3((unsigned)((pairs + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, J, cnt, mom, rows, ok);
   const unsigned nseg = scan_linearize_segments(n);
   hipLaunchKernelGGL(lin_reduce_kernel, dim3(nseg, np), dim3(LIN_RED), 0, st, rows, ok, n, nseg, part, part_cnt);
   hipLaunchKernelGGL(lin_final_kernel, dim3((unsigned)(((size_t)np * (LIN_NUM + 1) + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, part, part_cnt,
