@@ -102,6 +102,36 @@ def outliers_call(call, n, want, cfg):
     return out
 
 
+class FpfhCfg(C.Structure):
+    """flimo_fpfh_cfg (include/flimo_c.h)."""
+    _fields_ = [("k", C.c_int), ("max_dist", C.c_float), ("normal_k", C.c_int), ("normal_max_dist", C.c_float), ("normal_min_pts", C.c_int),
+                ("has_viewpoint", C.c_int), ("viewpoint", C.c_float * 3)]
+
+
+def fpfh_cfg(k=32, max_dist=float("inf"), normal_k=10, normal_max_dist=float("inf"), normal_min_pts=3, viewpoint=None) -> FpfhCfg:
+    """A feature neighbourhood of 32 and normals from 10 neighbours unless told otherwise: no gates, the normals' own orientation."""
+    vp = (0.0, 0.0, 0.0) if viewpoint is None else tuple(float(v) for v in np.asarray(viewpoint, dtype=np.float32).reshape(3))
+    return FpfhCfg(int(k), float(max_dist), int(normal_k), float(normal_max_dist), int(normal_min_pts), 0 if viewpoint is None else 1,
+                   (C.c_float * 3)(*vp))
+
+
+def fpfh_call(call, n, want, cfg):
+    """The output arrays of flimo_map_fpfh / flimo_loc_map_fpfh (``call`` takes: cfg, fpfh, spfh, cnt) as a dict with "fpfh" and the
+    outputs named in ``want`` (of "spfh", "cnt"); shared with ``api.Localizer``."""
+    unknown = set(want) - {"spfh", "cnt"}
+    if unknown:
+        raise ValueError(f"fpfh: unknown outputs {sorted(unknown)}")
+    k = fpfh_cfg(**cfg)
+    arr = {"fpfh": np.zeros((max(n, 1), 33), np.float32)}
+    if "spfh" in want:
+        arr["spfh"] = np.zeros((max(n, 1), 33), np.uint8)
+    if "cnt" in want:
+        arr["cnt"] = np.zeros(max(n, 1), np.int32)
+    ptr = lambda name: arr[name].ctypes.data if name in arr else None
+    call(C.byref(k), ptr("fpfh"), ptr("spfh"), ptr("cnt"))
+    return {name: a[:n] for name, a in arr.items()}
+
+
 class ChainPass(C.Structure):
     _fields_ = [("M", C.c_int), ("stragglers", C.c_int), ("ties", C.c_int), ("HTH", C.c_double * 144), ("HTh", C.c_double * 12),
                 ("dx", C.c_double * 23), ("x_after", C.c_double * 26)]
@@ -127,7 +157,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -224,6 +254,8 @@ def load_hip():
     L.flimo_map_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(OutlierCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OutlierStats)]
     L.flimo_map_remove_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(OutlierCfg), C.POINTER(C.c_size_t), C.POINTER(OutlierStats)]
     L.flimo_set_outlier_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_map_fpfh.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(FpfhCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_set_fpfh_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
     L.flimo_map_last_time.argtypes = [vp]
@@ -426,6 +458,19 @@ class HipCtx:
     def set_outlier_chunk(self, n):
         """Points per search launch of ``map_outliers`` / ``map_remove_outliers`` (flimo_set_outlier_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_outlier_chunk(self._h, int(n)))
+
+    def map_fpfh(self, first=0, n=None, want=("spfh", "cnt"), **cfg):
+        """FPFH descriptors (pcl::FPFHEstimation: 33 bins) of the stored points first .. first + n - 1 (``n`` None: up to the map's
+        end) -- flimo_map_fpfh; ``cfg``: the fields of ``fpfh_cfg`` (k, max_dist, normal_k, normal_max_dist, normal_min_pts,
+        viewpoint).  Returns a dict: ``fpfh`` [n, 33] float32, and of ``want`` ``spfh`` [n, 33] uint8, ``cnt`` [n] int32.  The
+        normals and the SPFH rows are formed for the whole map whatever the range; changes nothing."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return fpfh_call(lambda *a: self._chk(self._L.flimo_map_fpfh(self._h, first, n, *a)), n, want, cfg)
+
+    def set_fpfh_chunk(self, n):
+        """Points per search launch of ``map_fpfh`` (flimo_set_fpfh_chunk; 0: the default of 2^20)."""
+        self._chk(self._L.flimo_set_fpfh_chunk(self._h, int(n)))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -156,6 +156,7 @@ def load_host():
     L.flimo_loc_last_carve_removed.argtypes = [vp]
     L.flimo_loc_map_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.OutlierCfg), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(_lib.OutlierStats)]
+    L.flimo_loc_map_fpfh.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.FpfhCfg), C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_map_remove_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.OutlierCfg), C.POINTER(C.c_size_t),
                                                 C.POINTER(_lib.OutlierStats)]
     L.flimo_local_map_rule.restype = C.c_int
@@ -403,6 +404,13 @@ class Localizer:
         self._outliers_chk(self._L.flimo_loc_map_remove_outliers(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
                            "flimo_loc_map_remove_outliers")
         return int(removed.value), st.as_dict()
+
+    def map_fpfh(self, first=0, n=None, want=("spfh", "cnt"), **cfg):
+        """FPFH descriptors of the map's stored points (flimo_loc_map_fpfh), as ``HipCtx.map_fpfh``.  Waits for an insert, a crop or
+        a carve still running; changes nothing.  The Localizer's own update does not use it."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return _lib.fpfh_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_fpfh(self._h, first, n, *a), "flimo_loc_map_fpfh"), n, want, cfg)
 
     def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
         """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,

@@ -57,6 +57,7 @@ struct flimo_ctx {
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
   size_t outlier_chunk = (size_t)1 << 20;   // points per search launch of flimo_map_outliers (flimo_set_outlier_chunk)
+  size_t fpfh_chunk = (size_t)1 << 20;      // points per search launch of flimo_map_fpfh (flimo_set_fpfh_chunk)
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
@@ -1623,6 +1624,68 @@ extern "C" int flimo_map_remove_outliers(flimo_ctx* c, size_t first, size_t n, c
 extern "C" int flimo_set_outlier_chunk(flimo_ctx* c, size_t n) {
   if (!c) return FLIMO_ERR_INVALID;
   c->outlier_chunk = n ? n : (size_t)1 << 20;
+  return FLIMO_OK;
+}
+
+// ---- FPFH descriptors of the stored points (pcl::FPFHEstimation over the map) ---------------------------------------------------
+// kernels: flimo_knn_k.hip.  Three stages on the context's stream, the first two over the WHOLE map whatever the range (a neighbour
+// can be anywhere), in chunks of c->fpfh_chunk points: the normals of flimo_map_normals_range left on the device (16 B a stored
+// point; three launches a chunk), the SPFH rows and list lengths (34 B a stored point; two launches a chunk), then the FPFH rows of
+// the range (two launches a chunk, 136 B a point of the chunk come back).  Per chunk the scratch is the normals' moments and count
+// (76 B a point) and the worklist (8 B a point); nothing of points x k entries exists anywhere.
+extern "C" int flimo_map_fpfh(flimo_ctx* c, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh, uint8_t* spfh, int32_t* cnt) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "map fpfh: null cfg");
+  if (first > c->map_n || n > c->map_n - first)
+    return fail(c, FLIMO_ERR_INVALID, "map fpfh: the range [%zu, %zu + %zu) ends beyond the map's %zu points", first, first, n, c->map_n);
+  if (n > 0 && !fpfh) return fail(c, FLIMO_ERR_INVALID, "map fpfh: null fpfh");
+  { const int rc = check_gate(c, "map fpfh", cfg->max_dist); if (rc) return rc; }
+  { const int rc = check_gate(c, "map fpfh (normals)", cfg->normal_max_dist); if (rc) return rc; }
+  if (cfg->has_viewpoint && (std::isnan(cfg->viewpoint[0]) || std::isnan(cfg->viewpoint[1]) || std::isnan(cfg->viewpoint[2])))
+    return fail(c, FLIMO_ERR_INVALID, "map fpfh: NaN viewpoint");
+  if (cfg->normal_min_pts < 0) return fail(c, FLIMO_ERR_INVALID, "map fpfh: normal_min_pts must be >= 0");
+  if (cfg->k < 2 || cfg->k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map fpfh: k must be in 2..%d", FLIMO_KNN_MAX_K);
+  if (cfg->normal_k < 1 || cfg->normal_k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map fpfh: normal_k must be in 1..%d", FLIMO_KNN_MAX_K);
+  if (n == 0) return FLIMO_OK;
+  const size_t N = c->map_n;
+  if (N >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map fpfh: the map must hold fewer than 2^31 points");
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map fpfh: a map of %zu points has no index", N);
+  ctx_enter(c);
+  DevScratch d;
+  const size_t m = std::min(N, std::max<size_t>(c->fpfh_chunk, 1));      // points of a chunk, of the map's stages and of the range's
+  float4* d_normal = d.get<float4>(N);
+  unsigned char* d_spfh = d.get<unsigned char>(N * 33);
+  unsigned char* d_len = d.get<unsigned char>(N);
+  int32_t* d_ncnt = d.get<int32_t>(m);
+  double* d_mom = d.get<double>(m * 9);
+  uint2* d_work = d.get<uint2>(m);
+  unsigned* d_nwork = d.get<unsigned>(1);
+  float* d_fpfh = d.get<float>(std::min(m, n) * 33);
+  int32_t* d_cnt = d.get<int32_t>(std::min(m, n));
+  { const int rc = d.ok(c); if (rc) return rc; }
+  // (a chunk's worklist and moments are read by its own launches only: the stream orders the chunks, nothing waits in between)
+  const float* vp = cfg->has_viewpoint ? cfg->viewpoint : nullptr;
+  for (size_t a = 0; a < N; a += m)
+    HIPCHK(c, launch_knn_k_normals(c->stream, c->grid, c->d_map_raw, nullptr, (unsigned)a, (int)std::min(m, N - a), cfg->normal_k, cfg->normal_max_dist,
+                                   cfg->normal_min_pts, vp, d_normal + a, d_ncnt, nullptr, nullptr, nullptr, d_mom, d_work, d_nwork));
+  for (size_t a = 0; a < N; a += m)
+    HIPCHK(c, launch_fpfh_spfh(c->stream, c->grid, c->d_map_raw, d_normal, (unsigned)a, (int)std::min(m, N - a), cfg->k, cfg->max_dist, d_spfh, d_len,
+                               d_work, d_nwork));
+  if (spfh) HIPCHK(c, hipMemcpyAsync(spfh, d_spfh + first * 33, n * 33, hipMemcpyDeviceToHost, c->stream));
+  for (size_t a = 0; a < n; a += m) {
+    const size_t na = std::min(m, n - a);
+    HIPCHK(c, launch_fpfh_sum(c->stream, c->grid, c->d_map_raw, d_spfh, d_len, (unsigned)(first + a), (int)na, cfg->k, cfg->max_dist, d_fpfh, d_cnt,
+                              d_work, d_nwork));
+    HIPCHK(c, hipMemcpyAsync(fpfh + 33 * a, d_fpfh, na * 33 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (cnt) HIPCHK(c, hipMemcpyAsync(cnt + a, d_cnt, na * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the next chunk overwrites d_fpfh / d_cnt)
+  }
+  return FLIMO_OK;
+}
+extern "C" int flimo_set_fpfh_chunk(flimo_ctx* c, size_t n) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->fpfh_chunk = n ? n : (size_t)1 << 20;
   return FLIMO_OK;
 }
 

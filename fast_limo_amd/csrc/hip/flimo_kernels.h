@@ -311,6 +311,16 @@ hipError_t launch_outlier_sum(hipStream_t st, const double* mean, const int32_t*
 hipError_t launch_outlier_mask(hipStream_t st, const double* mean, const int32_t* cnt, unsigned n, int min_pts, int need, bool stat_on,
                                double threshold, unsigned char* mask, unsigned* counts);
 
+// FPFH descriptors of stored points (flimo_map_fpfh, flimo_c.h), after launch_knn_k_normals has left the normals of ALL stored
+// points in `normals`.  launch_fpfh_spfh: the search with a list of k keys for the stored points first .. first + nq - 1, each ended
+// in the 33 integer counts of its pair features, spfh [map size][33], and the length of its list, len [map size] (rows first ..).
+// launch_fpfh_sum: the same search again, each point ended in the weighted sum of its neighbours' rows, every bin one kk_slot_sum,
+// each group of 11 scaled to 100: fpfh [nq][33], cnt [nq] (rows 0 ..).  Scratch: work ([nq]), nwork.
+hipError_t launch_fpfh_spfh(hipStream_t st, const GridView& G, const float4* map_raw, const float4* normals, unsigned first, int nq, int k,
+                            float max_dist, unsigned char* spfh, unsigned char* len, uint2* work, unsigned* nwork);
+hipError_t launch_fpfh_sum(hipStream_t st, const GridView& G, const float4* map_raw, const unsigned char* spfh, const unsigned char* len,
+                           unsigned first, int nq, int k, float max_dist, float* fpfh, int32_t* cnt, uint2* work, unsigned* nwork);
+
 // The same search with k = 1 for every (pose, point of the resident scan) pair of a chunk of poses (flimo_scan_fitness, flimo_c.h):
 // the world point is transform_kernel's, from poses [np][12] (the upper three rows of PoseMats::RT).  sqd [np][n]: the nearest
 // stored point's squared distance, -1 for an empty query; idx [np][n] (optional): its insertion index, -1; inliers / sum_sqd [np]:

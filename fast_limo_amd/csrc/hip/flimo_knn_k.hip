@@ -27,6 +27,7 @@
 #include <string.h>
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include "flimo_types.h"
 #include "flimo_math.h"
 #include "flimo_kernels.h"
@@ -494,8 +495,14 @@ __global__ __launch_bounds__(KK_BLOCK) void kk_search_kernel(GridView G, Job J, 
   J.template finish<L>(lane, at, live && proven, mine, gx, gy, gz);
 }
 
+// (waves per SIMD the walk's register budget is cut for: 5 unless a job whose end needs more registers than that leaves asks for fewer)
+template <class Job, class = void>
+struct KkWalkWaves { static constexpr int value = 5; };
 template <class Job>
-__global__ __launch_bounds__(KK_BLOCK, 5) void kk_walk_kernel(GridView G, Job J, const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
+struct KkWalkWaves<Job, std::void_t<decltype(Job::WALK_WAVES)>> { static constexpr int value = Job::WALK_WAVES; };
+
+template <class Job>
+__global__ __launch_bounds__(KK_BLOCK, KkWalkWaves<Job>::value) void kk_walk_kernel(GridView G, Job J, const uint2* __restrict__ work, const unsigned* __restrict__ nwork) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int maxdim = grid_maxdim(G);
   const int ndir = G.ntx * G.nty * G.ntz;
@@ -1048,6 +1055,169 @@ __global__ __launch_bounds__(KK_BLOCK) void outlier_mask_kernel(const double* __
   }
 }
 
+// ---- FPFH descriptors of stored points (flimo_map_fpfh) --------------------------------------------------------------------------
+// Two more ends of the normals' search with stored points as queries, over the normals of ALL stored points left on the device by
+// launch_knn_k_normals (a neighbour can be anywhere).  Every term is float64 in the association flimo_c.h states.
+//   SpfhJob  lane `sub` holds slot sub of the list of point j: it loads that stored point and its normal and forms the pair's three
+//            angles and their bins (Darboux frame, PCL's computePairFeatures); a slot at distance 0 -- the point itself, its exact
+//            duplicates --, a NaN normal on either side or a degenerate frame is no pair.  The 33 counts are popcounts of ballots:
+//            integers, so the order of the lanes does not matter.  33 B + 1 B (the list's length c) per point.
+//   FpfhJob  searches again (cheaper than 8 B x k per point of the whole map kept between the launches); lane `sub` gathers the row
+//            and the length of its slot's point, forms weight * (count * 100 / (c - 1)) per bin, and every bin is one kk_slot_sum:
+//            the tree over the 64 slots whose bits depend on the list alone.  Each group of 11 is scaled to a sum of 100.
+// No floating-point atomics; both jobs take the worklist and the walk over the tiles as every other job does.
+constexpr int FPFH_BINS = 11;                   // per angle
+constexpr int FPFH_DIM = 3 * FPFH_BINS;
+
+__device__ __forceinline__ int fpfh_bin(double x) { return (int)fmin(fmax(floor(x), 0.0), (double)(FPFH_BINS - 1)); }
+
+template <int L>
+__device__ __forceinline__ void knnk_spfh(unsigned first, int k, kk_u64 gate_key, int lane, size_t at, bool live, kk_u64 mine, float gx, float gy,
+                                          float gz, const float4* __restrict__ map_raw, const float4* __restrict__ normals,
+                                          unsigned char* __restrict__ spfh, unsigned char* __restrict__ len) {
+  const int sub = lane & (L - 1);
+  const bool has = live && sub < k && mine < gate_key;
+  const unsigned long long bal = __ballot(has);
+  const int c = L == 64 ? __popcll(bal) : __popc(kk_group_mask<L>(bal, lane));
+  const size_t j = (size_t)first + at;
+  bool pair = has && kk_key_dist(mine) != 0.f;
+  int h1 = 0, h2 = 0, h3 = 0;
+  if (pair) {
+    const uint32_t t = (uint32_t)mine;
+    const float4 pt = map_raw[t], nt4 = normals[t], ns4 = normals[j];
+    pair = ns4.x == ns4.x && ns4.y == ns4.y && ns4.z == ns4.z && nt4.x == nt4.x && nt4.y == nt4.y && nt4.z == nt4.z;
+    if (pair) {
+      const double nsx = (double)ns4.x, nsy = (double)ns4.y, nsz = (double)ns4.z, ntx = (double)nt4.x, nty = (double)nt4.y, ntz = (double)nt4.z;
+      double dx = (double)pt.x - (double)gx, dy = (double)pt.y - (double)gy, dz = (double)pt.z - (double)gz;
+      const double f4 = sqrt(dx * dx + (dy * dy + dz * dz));
+      const double a1 = (nsx * dx + (nsy * dy + nsz * dz)) / f4, a2 = (ntx * dx + (nty * dy + ntz * dz)) / f4;
+      const bool swap = fabs(a1) < fabs(a2);      // the frame sits on the point whose normal is closer to the line (PCL: acos(|a1|) > acos(|a2|))
+      const double ux = swap ? ntx : nsx, uy = swap ? nty : nsy, uz = swap ? ntz : nsz;
+      const double mx = swap ? nsx : ntx, my = swap ? nsy : nty, mz = swap ? nsz : ntz;
+      const double f3 = swap ? -a2 : a1;
+      if (swap) { dx = -dx; dy = -dy; dz = -dz; }
+      double vx = dy * uz - dz * uy, vy = dz * ux - dx * uz, vz = dx * uy - dy * ux;
+      const double vn = sqrt(vx * vx + (vy * vy + vz * vz));
+      pair = vn != 0.0;
+      if (pair) {
+        vx = vx / vn; vy = vy / vn; vz = vz / vn;
+        const double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx;
+        const double f2 = vx * mx + (vy * my + vz * mz);
+        const double f1 = atan2(wx * mx + (wy * my + wz * mz), ux * mx + (uy * my + uz * mz));
+        h1 = fpfh_bin(11.0 * ((f1 + M_PI) * (1.0 / (2.0 * M_PI))));
+        h2 = fpfh_bin(11.0 * ((f2 + 1.0) * 0.5));
+        h3 = fpfh_bin(11.0 * ((f3 + 1.0) * 0.5));
+      }
+    }
+  }
+  // bin B of the row belongs to lane B % L of the group
+  constexpr int NR = (FPFH_DIM + L - 1) / L;
+  int r[NR];
+#pragma unroll
+  for (int i = 0; i < NR; i++) r[i] = 0;
+#pragma unroll
+  for (int B = 0; B < FPFH_DIM; B++) {
+    const int h = B < FPFH_BINS ? h1 : (B < 2 * FPFH_BINS ? h2 : h3);
+    const unsigned long long bb = __ballot(pair && h == B % FPFH_BINS);
+    const int n = L == 64 ? __popcll(bb) : __popc(kk_group_mask<L>(bb, lane));
+    if (sub == (B & (L - 1))) r[B / L] = n;
+  }
+  if (live) {
+#pragma unroll
+    for (int i = 0; i < NR; i++)
+      if (sub + i * L < FPFH_DIM) spfh[j * FPFH_DIM + (size_t)(sub + i * L)] = (unsigned char)r[i];
+    if (sub == 0) len[j] = (unsigned char)c;
+  }
+}
+
+// the stored points of a chunk, ended in their SPFH row and the length of their list (both arrays are the whole map's)
+struct SpfhJob {
+  static constexpr int LANES = 0;
+  static constexpr bool PAIRS = false;
+  static constexpr int WALK_WAVES = 4;      // (the pair's float64 frame and atan2: 132 B a lane spilled at 5)
+  unsigned first;        // query i is stored point first + i
+  int nq, k;
+  float r2;
+  kk_u64 gate_key;
+  const float4* map_raw;
+  const float4* normals; // [map size]: nx ny nz curvature, NaN where there is no plane
+  unsigned char* spfh;   // [map size][FPFH_DIM]
+  unsigned char* len;    // [map size]
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
+    const bool live = kk_flat_slot<L>(nq, at);
+    if (live) query(at, x, y, z);
+    return live;
+  }
+  __host__ __device__ size_t total() const { return (size_t)nq; }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
+  template <int L>
+  __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float gx, float gy, float gz) const {
+    knnk_spfh<L>(first, k, gate_key, lane, at, live, mine, gx, gy, gz, map_raw, normals, spfh, len);
+  }
+};
+
+template <int L>
+__device__ __forceinline__ void knnk_fpfh(int k, kk_u64 gate_key, int lane, size_t at, bool live, kk_u64 mine, const unsigned char* __restrict__ spfh,
+                                          const unsigned char* __restrict__ len, float* __restrict__ fpfh, int32_t* __restrict__ cnt) {
+  const int sub = lane & (L - 1);
+  const bool has = live && sub < k && mine < gate_key;
+  const unsigned long long bal = __ballot(has);
+  const int c = L == 64 ? __popcll(bal) : __popc(kk_group_mask<L>(bal, lane));
+  double w = 0.0, inc = 0.0;
+  const unsigned char* row = spfh;
+  if (has) {
+    const uint32_t t = (uint32_t)mine;
+    const float sqd = kk_key_dist(mine);
+    w = sqd != 0.f ? 1.0 / (double)sqd : 0.0;
+    const int ct = (int)len[t];
+    inc = ct >= 2 ? 100.0 / (double)(ct - 1) : 0.0;
+    row = spfh + (size_t)t * FPFH_DIM;
+  }
+#pragma unroll
+  for (int g = 0; g < 3; g++) {
+    double F[FPFH_BINS];
+#pragma unroll
+    for (int b = 0; b < FPFH_BINS; b++) F[b] = kk_slot_sum<L>(has ? w * ((double)row[g * FPFH_BINS + b] * inc) : 0.0);
+    double S = F[0];
+#pragma unroll
+    for (int b = 1; b < FPFH_BINS; b++) S = S + F[b];
+    double own = 0.0;
+#pragma unroll
+    for (int b = 0; b < FPFH_BINS; b++) own = sub == b ? F[b] : own;
+    const double scale = 100.0 / S;
+    if (live && sub < FPFH_BINS) fpfh[at * FPFH_DIM + (size_t)(g * FPFH_BINS + sub)] = S != 0.0 ? (float)(own * scale) : 0.f;
+  }
+  if (live && sub == 0) cnt[at] = c;
+}
+
+// the stored points of a chunk of the range, ended in their FPFH row (the chunk's) from the rows of SpfhJob (the whole map's)
+struct FpfhJob {
+  static constexpr int LANES = 0;
+  static constexpr bool PAIRS = false;
+  unsigned first;
+  int nq, k;
+  float r2;
+  kk_u64 gate_key;
+  const float4* map_raw;
+  const unsigned char* spfh;
+  const unsigned char* len;
+  float* fpfh;           // [nq][FPFH_DIM]
+  int32_t* cnt;          // [nq]
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
+    const bool live = kk_flat_slot<L>(nq, at);
+    if (live) query(at, x, y, z);
+    return live;
+  }
+  __host__ __device__ size_t total() const { return (size_t)nq; }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
+  template <int L>
+  __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float, float, float) const {
+    knnk_fpfh<L>(k, gate_key, lane, at, live, mine, spfh, len, fpfh, cnt);
+  }
+};
+
 // lanes per query from k: a list of k keys needs k lanes
 int knnk_plan(int k) { return k <= 16 ? 16 : 64; }
 
@@ -1127,6 +1297,30 @@ hipError_t launch_outlier_search(hipStream_t st, const GridView& G, const float4
   J.first = first; J.nq = nq; J.k = k + 1;
   kk_gate(max_dist, J.r2, J.gate_key);
   J.map_raw = map_raw; J.mean = mean; J.cnt = cnt;
+  const hipError_t e = kk_launch(st, G, J, work, nwork);
+  return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_fpfh_spfh(hipStream_t st, const GridView& G, const float4* map_raw, const float4* normals, unsigned first, int nq, int k,
+                            float max_dist, unsigned char* spfh, unsigned char* len, uint2* work, unsigned* nwork) {
+  if (nq <= 0) return hipSuccess;
+  if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
+  SpfhJob J;
+  J.first = first; J.nq = nq; J.k = k;
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.map_raw = map_raw; J.normals = normals; J.spfh = spfh; J.len = len;
+  const hipError_t e = kk_launch(st, G, J, work, nwork);
+  return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_fpfh_sum(hipStream_t st, const GridView& G, const float4* map_raw, const unsigned char* spfh, const unsigned char* len,
+                           unsigned first, int nq, int k, float max_dist, float* fpfh, int32_t* cnt, uint2* work, unsigned* nwork) {
+  if (nq <= 0) return hipSuccess;
+  if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
+  FpfhJob J;
+  J.first = first; J.nq = nq; J.k = k;
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.map_raw = map_raw; J.spfh = spfh; J.len = len; J.fpfh = fpfh; J.cnt = cnt;
   const hipError_t e = kk_launch(st, G, J, work, nwork);
   return e != hipSuccess ? e : hipGetLastError();
 }

@@ -342,6 +342,19 @@ int flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, flo
   }
   return flimo_map_normals_range(c, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
 }
+int flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh, uint8_t* spfh, int32_t* cnt) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
+  if (!c) {                          // no map yet: the answer of an empty one, after flimo_map_fpfh's own argument checks
+    if (!cfg || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
+    if (std::isnan(cfg->max_dist) || cfg->max_dist < 0.f || std::isnan(cfg->normal_max_dist) || cfg->normal_max_dist < 0.f) return FLIMO_ERR_INVALID;
+    if (cfg->has_viewpoint && (std::isnan(cfg->viewpoint[0]) || std::isnan(cfg->viewpoint[1]) || std::isnan(cfg->viewpoint[2]))) return FLIMO_ERR_INVALID;
+    if (cfg->normal_min_pts < 0) return FLIMO_ERR_INVALID;
+    if (cfg->k < 2 || cfg->k > FLIMO_KNN_MAX_K || cfg->normal_k < 1 || cfg->normal_k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
+    return FLIMO_OK;
+  }
+  return flimo_map_fpfh(c, first, n, cfg, fpfh, spfh, cnt);
+}
 int flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
                            int32_t* nn_idx) {
   if (!L) return FLIMO_ERR_INVALID;

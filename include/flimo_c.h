@@ -285,6 +285,53 @@ int flimo_map_normals(flimo_ctx* ctx, const float* q_xyz, size_t nq, int k, floa
 int flimo_map_normals_range(flimo_ctx* ctx, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3],
                             float* normal, int32_t* cnt, double* centroid, double* cov, double* eig);
 
+/* ---- FPFH descriptors of the stored points: pcl::FPFHEstimation over the map (the reference's relocation/KISS-matcher branch starts
+ * its global registration from them) ----
+ * 11 + 11 + 11 bins, weight 1 / squared distance, no separate own-SPFH term.  The neighbour lists and the normals never leave the
+ * GPU.  The scan's descriptors come from the same call on a second context whose map is the scan.
+ *
+ * Definition (tests/fpfh_common.py restates it in numpy).  All arithmetic is float64 on the float32 inputs widened, nothing
+ * contracted, in exactly the written association.  Point i of the range is stored point j = first + i, insertion order:
+ *  - normals: N[j] = the float32 normal[j][0..2] of flimo_map_normals_range(0, flimo_map_size, normal_k, normal_max_dist,
+ *    normal_min_pts, viewpoint or NULL), bit for bit: NaN below max(3, normal_min_pts) neighbours.  Of EVERY stored point.
+ *  - list L_j = flimo_knn_k(p_j, k, max_dist) over the whole map, c_j entries: the same predicate, the same unique order; slot s
+ *    holds the index j_s and the float32 sqd_s.
+ *  - pair features of source s = j and target t = j_s, for every slot with sqd_s != 0 (this drops the point itself and its exact
+ *    duplicates); no pair if a component of N[s] or N[t] is NaN.  d = p_t - p_s; f4 = sqrt(d.x*d.x + (d.y*d.y + d.z*d.z));
+ *    a1 = (N[s].x*d.x + (N[s].y*d.y + N[s].z*d.z)) / f4, a2 the same with N[t].  If fabs(a1) < fabs(a2): u = N[t], m = N[s],
+ *    d = -d, f3 = -a2; otherwise u = N[s], m = N[t], f3 = a1 (PCL's acos(|a1|) > acos(|a2|) without the acos).  v = d x u, each
+ *    component a*b - c*d as two products and one subtraction; vn = sqrt(v.x*v.x + (v.y*v.y + v.z*v.z)); no pair if vn == 0;
+ *    v = v / vn (three divisions).  w = u x v; f2 = v.x*m.x + (v.y*m.y + v.z*m.z); f1 = atan2(w.m, u.m), the dot products in the
+ *    same association, the device's float64 atan2.  Bins, each clamped to 0..10: h1 = floor(11.0 * ((f1 + M_PI) * (1.0 / (2.0 *
+ *    M_PI)))), h2 = floor(11.0 * ((f2 + 1.0) * 0.5)), h3 = floor(11.0 * ((f3 + 1.0) * 0.5)).
+ *  - spfh[j][0..32]: the integer counts per bin (h1 in 0..10, h2 in 11..21, h3 in 22..32) over the pairs of j; the increment is
+ *    inc_j = c_j >= 2 ? 100.0 / (double)(c_j - 1) : 0.0 (PCL's 100 / (indices.size() - 1)).  A point with a NaN normal has an
+ *    all-zero row; its FPFH is still formed from its neighbours.
+ *  - fpfh: for slot s of L_j, w_s = sqd_s != 0 ? 1.0 / (double)sqd_s : +0.0 and t_s[b] = w_s * ((double)spfh[j_s][b] * inc_{j_s});
+ *    F[b] = the pairwise tree ((t_0 + t_1) + (t_2 + t_3)) + ... over the 64 slots, empty ones holding +0.0 (flimo_map_outliers'
+ *    tree).  Per group g of 11 bins S_g = F[11g] + F[11g+1] + ... in ascending order; fpfh[i][b] = S_g != 0 ? (float)(F[b] *
+ *    (100.0 / S_g)) : 0.0f.  cnt[i] = c_j.
+ * The integer rows depend on nothing but the lists and the normals and the sums have one fixed shape: the bits of a row do not
+ * depend on the chunking, the cell size or the path of the search.
+ * Cost: the normals and the SPFH rows are formed for the WHOLE map whatever the range (a neighbour can be anywhere), nothing is kept
+ * between calls; device scratch is 50 B a stored point plus 220 B a point of a chunk of 2^20.
+ * n = 0 (also on an empty map, first = 0): FLIMO_OK, nothing touched.  FLIMO_ERR_INVALID -- outputs untouched -- for a NULL ctx or
+ * cfg, a NULL fpfh with n > 0, first + n beyond flimo_map_size, max_dist or normal_max_dist NaN or negative, a NaN viewpoint with
+ * has_viewpoint, normal_min_pts < 0; FLIMO_ERR_UNSUPPORTED for k outside 2..FLIMO_KNN_MAX_K or normal_k outside
+ * 1..FLIMO_KNN_MAX_K.  Calling rules as flimo_map_outliers: no pass of this context in flight; changes nothing: not the map, not the
+ * scan, not the bits of a later pass. */
+typedef struct flimo_fpfh_cfg {
+  int   k;               /* feature neighbourhood, the point itself included: 2 .. FLIMO_KNN_MAX_K */
+  float max_dist;        /* gate of that neighbourhood, as flimo_knn_k; INFINITY: none */
+  int   normal_k;        /* the normals: those of flimo_map_normals_range with normal_k, normal_max_dist, normal_min_pts, viewpoint */
+  float normal_max_dist;
+  int   normal_min_pts;
+  int   has_viewpoint;   /* 0: the normals' own orientation rule */
+  float viewpoint[3];
+} flimo_fpfh_cfg;
+int flimo_map_fpfh(flimo_ctx* ctx, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh /* [n][33], required */,
+                   uint8_t* spfh /* [n][33], may be NULL */, int32_t* cnt /* [n], may be NULL */);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

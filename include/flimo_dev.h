@@ -78,6 +78,10 @@ int flimo_set_normals_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_map_outliers / flimo_map_remove_outliers search in chunks of n points (default 2^20; 0 restores it): the chunk bounds the
  * search's worklist, 8 B a point; equal results whatever the chunk. */
 int flimo_set_outlier_chunk(flimo_ctx* ctx, size_t n);
+/* flimo_map_fpfh works in chunks of n points (default 2^20; 0 restores it), in its two stages over the whole map and in the one
+ * over the range: the chunk bounds the normals' moments, the worklist and the rows on their way back, 220 B a point; equal results
+ * whatever the chunk. */
+int flimo_set_fpfh_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_scan_fitness works in chunks of whole poses, at most `pairs` (pose, point) pairs each (default 2^22; 0 restores it); a
  * single pose with more points than that runs alone.  The chunk bounds the call's device scratch.  The results do not depend on it
  * (tests, A/B). */

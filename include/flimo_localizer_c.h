@@ -125,6 +125,11 @@ int    flimo_loc_map_normals(flimo_loc* L, const float* q_xyz, size_t nq, int k,
                              float* normal, int32_t* cnt, double* centroid, double* cov, double* eig);
 int    flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3],
                                    float* normal, int32_t* cnt, double* centroid, double* cov, double* eig);
+/* FPFH descriptors of the Localizer's stored points: flimo_map_fpfh (include/flimo_c.h: same arguments, same results, same error
+ * codes) on the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  A Localizer that
+ * has no map yet answers like an empty one (first = n = 0: nothing touched; any other range lies beyond it).  The Localizer's own
+ * update does not use it. */
+int    flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh, uint8_t* spfh, int32_t* cnt);
 /* How well the scan resident in the map's context -- after updatePointCloud: pc2match -- fits the Localizer's map at each of np pose
  * hypotheses: flimo_scan_fitness (include/flimo_c.h: same arguments, same results, same error codes; n = the size of pc2match) on
  * the map's context, after an insert or a crop still running behind the last sweep has ended.  A Localizer that has no map yet
