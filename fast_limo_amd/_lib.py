@@ -132,6 +132,48 @@ def fpfh_call(call, n, want, cfg):
     return {name: a[:n] for name, a in arr.items()}
 
 
+class CorrCfg(C.Structure):
+    """flimo_corr_cfg (include/flimo_c.h)."""
+    _fields_ = [("edge_sim", C.c_float), ("min_edge", C.c_float), ("max_dist", C.c_float)]
+
+
+CORR_OK, CORR_DEGENERATE, CORR_REJECTED = 0, 1, 2      # FLIMO_CORR_*: the status of a hypothesis
+
+
+def corr_cfg(edge_sim=0.9, min_edge=0.0, max_dist=float("inf")) -> CorrCfg:
+    """PCL's SampleConsensusPrerejective similarity threshold of 0.9 unless told otherwise: no shortest edge, no inlier gate."""
+    return CorrCfg(float(edge_sim), float(min_edge), float(max_dist))
+
+
+_NONE = C.create_string_buffer(8)      # what an array of no element points at: the call wants its required pointers non-null
+
+
+def corr_call(call, src, dst, tri, want, cfg):
+    """The output arrays of flimo_corr_poses / flimo_loc_corr_poses (``call`` takes: src, dst, m, tri, nh, cfg, status, inliers,
+    sum_sqd, pose, pair_sqd) as a dict with "status", "inliers", "sum_sqd" and the outputs named in ``want`` (of "pose", "pair_sqd");
+    shared with ``api.Localizer``."""
+    unknown = set(want) - {"pose", "pair_sqd"}
+    if unknown:
+        raise ValueError(f"corr_poses: unknown outputs {sorted(unknown)}")
+    s = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dst, dtype=np.float32).reshape(-1, 3)
+    if s.shape != d.shape:
+        raise ValueError("corr_poses: src and dst must hold the same number of points")
+    t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+    m, nh = s.shape[0], t.shape[0]
+    k = corr_cfg(**cfg)
+    out = {"status": np.zeros(nh, np.int32), "inliers": np.zeros(nh, np.int32), "sum_sqd": np.zeros(nh, np.float64)}
+    if "pose" in want:
+        out["pose"] = np.full((nh, 7), np.nan)
+    if "pair_sqd" in want:
+        out["pair_sqd"] = np.full((nh, m), -1, np.float32)
+    # (an array of no element may have no address)
+    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(_NONE))
+    call(ptr(s), ptr(d), m, ptr(t), nh, C.byref(k), ptr(out["status"]), ptr(out["inliers"]), ptr(out["sum_sqd"]), ptr(out.get("pose")),
+         ptr(out.get("pair_sqd")))
+    return out
+
+
 class ChainPass(C.Structure):
     _fields_ = [("M", C.c_int), ("stragglers", C.c_int), ("ties", C.c_int), ("HTH", C.c_double * 144), ("HTh", C.c_double * 12),
                 ("dx", C.c_double * 23), ("x_after", C.c_double * 26)]
@@ -158,7 +200,7 @@ FRAME_DTYPE = np.dtype([
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
     "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_scan_size", "flimo_scan_get",
+    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
@@ -276,6 +318,10 @@ def load_hip():
     L.flimo_scan_linearize.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_set_linearize_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_corr_poses.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(CorrCfg), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_corr_pose_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CorrCfg), C.c_void_p, C.c_void_p]
+    L.flimo_set_corr_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.flimo_scan_size.restype = C.c_size_t
     L.flimo_scan_size.argtypes = [vp]
@@ -608,6 +654,19 @@ class HipCtx:
     def set_linearize_chunk(self, pairs):
         """(pose, point) pairs per chunk of ``scan_linearize`` (flimo_set_linearize_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_linearize_chunk(self._h, int(pairs)))
+
+    def corr_poses(self, src, dst, tri, want=("pose",), **cfg):
+        """flimo_corr_poses: pose hypotheses from point correspondences.  ``src`` [m, 3] (body frame) and ``dst`` [m, 3] (map frame)
+        are the putative pairs, ``tri`` [nh, 3] the caller's samples of three of them (``api.corr_triplets``); ``cfg``: the fields
+        of ``corr_cfg``.  Per sample the polygon pre-rejection, the closed-form pose and the pairs it brings within ``max_dist``.
+        Returns a dict: status [nh] (CORR_OK / CORR_DEGENERATE / CORR_REJECTED), inliers [nh] int32, sum_sqd [nh] float64[, pose
+        [nh, 7]: t, then the quaternion x y z w -- the first seven entries of an x26 row; NaN unless OK][, pair_sqd [nh, m] float32:
+        the squared distance of an inlier pair, -1 otherwise].  Reads neither the map nor the resident scan."""
+        return corr_call(lambda *a: self._chk(self._L.flimo_corr_poses(self._h, *a)), src, dst, tri, want, cfg)
+
+    def set_corr_chunk(self, n):
+        """Hypotheses per chunk of ``corr_poses`` (flimo_set_corr_chunk; 0: the default of 2^16)."""
+        self._chk(self._L.flimo_set_corr_chunk(self._h, int(n)))
 
     def scan_voxel_filter(self, leaf: float) -> int:
         n = C.c_size_t(0)

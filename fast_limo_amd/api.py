@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -144,6 +144,8 @@ def load_host():
     L.flimo_loc_scan_fitness.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_scan_linearize.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_corr_poses.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_lib.CorrCfg), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_set_map_carving.restype = None
     L.flimo_loc_set_map_carving.argtypes = [vp, C.c_int, C.POINTER(_lib.CarveCfg)]
     L.flimo_carve_rule.restype = C.c_int
@@ -490,6 +492,16 @@ class Localizer:
         return _lib.linearize_call(lambda *a: self._linearize_chk(self._L.flimo_loc_scan_linearize(self._h, *a)), x26s, n, k, max_dist, min_pts,
                                    max_curv, want_rows)
 
+    def _corr_chk(self, rc):
+        if rc != 0:
+            raise FlimoError(f"flimo_loc_corr_poses failed ({rc})")
+
+    def corr_poses(self, src, dst, tri, want=("pose",), **cfg):
+        """Pose hypotheses from point correspondences on the map's context (flimo_loc_corr_poses): the dict of
+        ``HipCtx.corr_poses``.  Waits for an insert, a crop or a carve still running behind the last sweep; reads neither the map nor
+        the resident scan.  The Localizer's own update does not use it."""
+        return _lib.corr_call(lambda *a: self._corr_chk(self._L.flimo_loc_corr_poses(self._h, *a)), src, dst, tri, want, cfg)
+
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))
 
@@ -635,6 +647,67 @@ def fitness_cost(inliers, sum_sqd, n, max_dist):
     distance to the map, one without a neighbour inside the gate pays the gate's: sum_sqd + (n - inliers) * max_dist^2 (float64).
     It is the one number that ranks hypotheses with different inlier counts; the lowest wins."""
     return np.asarray(sum_sqd, np.float64) + (float(n) - np.asarray(inliers, np.float64)) * (float(max_dist) * float(max_dist))
+
+
+def corr_triplets(m, nh, seed=0):
+    """[nh, 3] int32: ``nh`` samples of three DISTINCT indices below ``m`` (m >= 3) from ``numpy.random.default_rng(seed)`` -- the
+    minimal samples of ``corr_poses``.  Three draws a, b', c' from m, m - 1, m - 2 values, then b' and c' stepped over the indices
+    already taken: every ordered triple of distinct indices is equally likely."""
+    m, nh = int(m), int(nh)
+    if m < 3:
+        raise ValueError("corr_triplets: three distinct indices need m >= 3")
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, m, nh)
+    b = rng.integers(0, m - 1, nh)
+    c = rng.integers(0, m - 2, nh)
+    b = b + (b >= a)
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    c = c + (c >= lo)
+    c = c + (c >= hi)
+    return np.stack([a, b, c], axis=1).astype(np.int32)
+
+
+def corr_pose_host(src3, dst3, **cfg):
+    """The pose of ONE triplet of correspondences on the host (flimo_corr_pose_host: the function the solve kernel calls):
+    ``src3`` / ``dst3`` [3, 3] = the points a, b, c of either cloud; ``cfg``: the fields of ``_lib.corr_cfg``.  Returns (status,
+    pose7 [7] float64: t, x y z w, rt [3, 4] float32: the matrix ``scan_fitness`` would form from it); NaN unless CORR_OK."""
+    L = _lib.load_hip()
+    s = np.ascontiguousarray(src3, dtype=np.float32).reshape(9)
+    d = np.ascontiguousarray(dst3, dtype=np.float32).reshape(9)
+    k = _lib.corr_cfg(**cfg)
+    pose = np.zeros(7)
+    rt = np.zeros(12, np.float32)
+    rc = L.flimo_corr_pose_host(s.ctypes.data, d.ctypes.data, C.byref(k), pose.ctypes.data, rt.ctypes.data)
+    if rc < 0:
+        raise FlimoError(f"flimo_corr_pose_host failed ({rc})")
+    return int(rc), pose, rt.reshape(3, 4)
+
+
+def corr_consensus(obj, src, dst, nh, seed=0, top=8, x26_like=None, **cfg):
+    """Pose guesses from putative correspondences (``src[i]`` in the body frame is ``dst[i]`` in the map's): ``nh`` samples of
+    ``corr_triplets(m, nh, seed)`` through ``obj.corr_poses`` (a ``HipCtx`` or a ``Localizer``; ``cfg``: the fields of
+    ``_lib.corr_cfg``), the OK hypotheses ranked by ``inliers`` descending, then by ``fitness_cost(inliers, sum_sqd, m, max_dist)``
+    ascending (then by index).  Returns a dict of the best ``top``: x26 [k, 26] -- pos and rot filled in, everything else copied from
+    ``x26_like`` [26] or zero with identity extrinsics: rows for ``scan_fitness`` / ``scan_align`` --, inliers, sum_sqd, cost [k],
+    index [k] (the row of the hypothesis in tri), tri [k, 3]; and survivors: the number of OK hypotheses."""
+    s = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
+    m = s.shape[0]
+    tri = corr_triplets(m, nh, seed)
+    out = obj.corr_poses(s, dst, tri, want=("pose",), **cfg)
+    ok = np.nonzero(out["status"] == _lib.CORR_OK)[0]
+    max_dist = float(_lib.corr_cfg(**cfg).max_dist)
+    gate = max_dist if np.isfinite(max_dist) else 0.0      # (no gate: every pair is an inlier and pays its distance)
+    cost = fitness_cost(out["inliers"][ok], out["sum_sqd"][ok], m, gate)
+    order = np.lexsort((ok, cost, -out["inliers"][ok].astype(np.int64)))[:max(int(top), 0)]
+    best = ok[order]
+    base = np.zeros(26)
+    base[10] = 1.0
+    if x26_like is not None:
+        base = np.array(np.asarray(x26_like, np.float64).reshape(26))
+    x = np.tile(base, (best.size, 1))
+    x[:, 0:7] = out["pose"][best]
+    return dict(x26=x, inliers=out["inliers"][best], sum_sqd=out["sum_sqd"][best], cost=cost[order], index=best.astype(np.int64),
+                tri=tri[best], survivors=int(ok.size))
 
 
 ALIGN_RUNNING, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2      # scan_align's status per pose: ran every iteration / too few valid pairs / H not positive definite

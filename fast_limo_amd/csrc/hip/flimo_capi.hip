@@ -23,6 +23,7 @@
 #include "flimo_kernels.h"
 #include "flimo_math.h"
 #include "flimo_pose.h"
+#include "flimo_corr.h"
 #include "flimo_chain.h"
 #include "flimo_ieskf.h"
 #include "flimo_insert.h"
@@ -60,6 +61,7 @@ struct flimo_ctx {
   size_t fpfh_chunk = (size_t)1 << 20;      // points per search launch of flimo_map_fpfh (flimo_set_fpfh_chunk)
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
+  size_t corr_chunk = (size_t)1 << 16;      // hypotheses per chunk of flimo_corr_poses (flimo_set_corr_chunk)
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
   IndexTables idx;                 // the index of the main grid (GridView, flimo_types.h): tiles, directory, escapes, xstart
   GridView grid{};
@@ -3347,6 +3349,69 @@ extern "C" int flimo_scan_fitness(flimo_ctx* c, const double* x26, size_t np, fl
 extern "C" int flimo_set_fitness_chunk(flimo_ctx* c, size_t pairs) {
   if (!c) return FLIMO_ERR_INVALID;
   c->fitness_chunk = pairs ? pairs : (size_t)1 << 22;
+  return FLIMO_OK;
+}
+
+// ---- pose hypotheses from point correspondences (pcl::SampleConsensusPrerejective's sample, pre-rejection, pose and count) --------
+// kernels: flimo_corr.hip.  Both clouds go up once; the hypotheses run in chunks of c->corr_chunk (fewer when pair_sqd is asked for:
+// at most 2^26 slots a chunk): per chunk the triplets go up, the solve, the fill of pair_sqd where asked for and the count are
+// launched, and the chunk's results come back; device scratch is the chunk's, whatever nh.  Reads neither the map nor the scan.
+static bool corr_cfg_ok(const flimo_corr_cfg* k) {
+  return !(std::isnan(k->edge_sim) || k->edge_sim < 0.f || k->edge_sim > 1.f || std::isnan(k->min_edge) || k->min_edge < 0.f ||
+           std::isnan(k->max_dist) || k->max_dist < 0.f);
+}
+extern "C" int flimo_corr_poses(flimo_ctx* c, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
+                                const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!cfg || !status || !inliers || !sum_sqd || (m > 0 && (!src_xyz || !dst_xyz)) || (nh > 0 && !tri))
+    return fail(c, FLIMO_ERR_INVALID, "corr poses: null src / dst / tri / cfg / status / inliers / sum_sqd");
+  if (!corr_cfg_ok(cfg)) return fail(c, FLIMO_ERR_INVALID, "corr poses: edge_sim must be in 0..1, min_edge and max_dist >= 0 (max_dist may be INFINITY)");
+  if (m >= 0x80000000ull || nh >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "corr poses: m and nh must be below 2^31");
+  if (pair_sqd && (unsigned long long)nh * (unsigned long long)m >= 0x80000000ull)
+    return fail(c, FLIMO_ERR_TOO_LARGE, "corr poses: nh * m must be below 2^31 when pair_sqd is asked for");
+  if (nh == 0) return FLIMO_OK;
+  for (size_t i = 0; i < 3 * nh; i++)
+    if (tri[i] < 0 || (size_t)tri[i] >= m)
+      return fail(c, FLIMO_ERR_INVALID, "corr poses: index %d of hypothesis %zu is outside [0, %zu)", (int)tri[i], i / 3, m);
+  ctx_enter(c);
+  DevScratch d;
+  size_t k = std::min(nh, std::max<size_t>(c->corr_chunk, 1));      // hypotheses of a chunk
+  if (pair_sqd) k = std::min(k, std::max<size_t>(((size_t)1 << 26) / m, 1));
+  float* d_src = d.get<float>(3 * m);
+  float* d_dst = d.get<float>(3 * m);
+  int32_t* d_tri = d.get<int32_t>(3 * k);
+  int32_t* d_status = d.get<int32_t>(k);
+  double* d_pose = d.get<double>(7 * k);
+  float* d_rt = d.get<float>(12 * k);
+  int32_t* d_surv = d.get<int32_t>(k);
+  unsigned* d_nsurv = d.get<unsigned>(1);
+  int32_t* d_inliers = d.get<int32_t>(k);
+  double* d_sum = d.get<double>(k);
+  float* d_pair = pair_sqd ? d.get<float>(k * m) : nullptr;
+  { const int rc = d.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(d_src, src_xyz, 3 * m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_dst, dst_xyz, 3 * m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  for (size_t a = 0; a < nh; a += k) {
+    const size_t ka = std::min(k, nh - a);
+    HIPCHK(c, hipMemcpyAsync(d_tri, tri + 3 * a, 3 * ka * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_corr_poses(c->stream, d_src, d_dst, (unsigned)m, d_tri, (unsigned)ka, cfg->edge_sim, cfg->min_edge, cfg->max_dist, d_status,
+                                d_pose, d_rt, d_surv, d_nsurv, d_inliers, d_sum, d_pair));
+    HIPCHK(c, hipMemcpyAsync(status + a, d_status, ka * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(inliers + a, d_inliers, ka * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sum_sqd + a, d_sum, ka * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (pose) HIPCHK(c, hipMemcpyAsync(pose + 7 * a, d_pose, 7 * ka * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (pair_sqd) HIPCHK(c, hipMemcpyAsync(pair_sqd + a * m, d_pair, ka * m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the next chunk overwrites the chunk's buffers)
+  }
+  return FLIMO_OK;
+}
+extern "C" int flimo_corr_pose_host(const float src3[9], const float dst3[9], const flimo_corr_cfg* cfg, double pose7[7], float rt12[12]) {
+  if (!src3 || !dst3 || !cfg || !pose7 || !rt12 || !corr_cfg_ok(cfg)) return FLIMO_ERR_INVALID;
+  return corr_solve(src3, dst3, cfg->edge_sim, cfg->min_edge, pose7, rt12);
+}
+extern "C" int flimo_set_corr_chunk(flimo_ctx* c, size_t n) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->corr_chunk = n ? n : (size_t)1 << 16;
   return FLIMO_OK;
 }
 

@@ -340,4 +340,13 @@ hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4
                                  unsigned np, int k, float max_dist, int min_pts, float max_curv, int32_t* cnt, double* mom, uint2* work,
                                  unsigned* nwork, double* rows, unsigned char* ok, double* part, int32_t* part_cnt, double* sums, int32_t* valid);
 
+// flimo_corr.hip -- pose hypotheses from point correspondences (flimo_corr_poses, flimo_c.h) for a chunk of nh triplets tri [nh][3]
+// (every index already checked to lie in [0, m)) over the clouds src / dst [m][3], packed xyz: the solve per hypothesis (status
+// [nh], pose [nh][7]; NaN unless OK), then for the OK ones the count of the pairs their float32 matrix brings within max_dist
+// (inliers / sum_sqd [nh], 0 for the others; pair_sqd [nh][m], optional: the squared distance, -1 for a non-inlier).  nh * m < 2^31
+// when pair_sqd is given.  Scratch: rt ([nh][12]), surv ([nh]), nsurv.
+hipError_t launch_corr_poses(hipStream_t st, const float* src, const float* dst, unsigned m, const int32_t* tri, unsigned nh, float edge_sim,
+                             float min_edge, float max_dist, int32_t* status, double* pose, float* rt, int32_t* surv, unsigned* nsurv,
+                             int32_t* inliers, double* sum_sqd, float* pair_sqd);
+
 }  // namespace flimo

@@ -355,6 +355,11 @@ int flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh_cf
   }
   return flimo_map_fpfh(c, first, n, cfg, fpfh, spfh, cnt);
 }
+int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
+                         const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return L->map->corr_poses(src_xyz, dst_xyz, m, tri, nh, cfg, status, inliers, sum_sqd, pose, pair_sqd);
+}
 int flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
                            int32_t* nn_idx) {
   if (!L) return FLIMO_ERR_INVALID;

@@ -589,6 +589,14 @@ int Mapper::linearize(const double* x26, size_t np, int k, float max_dist, int m
                               (pair_cnt && np && n) ? pair_cnt->data() : nullptr);
 }
 
+// pose hypotheses from point correspondences (an insert, a crop or a carve on the worker thread ends first)
+int Mapper::corr_poses(const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh, const flimo_corr_cfg* cfg,
+                       int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
+  sync();
+  if (!ctx_ && !attach(device_, cell_size_)) return FLIMO_ERR_NO_DEVICE;
+  return flimo_corr_poses(ctx_, src_xyz, dst_xyz, m, tri, nh, cfg, status, inliers, sum_sqd, pose, pair_sqd);
+}
+
 void Mapper::add(pcl::PointCloud<PointType>::Ptr& pc, double time) {   // Mapper.cpp:88-96
   if (!pc || pc->points.size() < 1) return;
   sync();

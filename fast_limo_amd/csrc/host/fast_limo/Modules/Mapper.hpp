@@ -114,6 +114,12 @@ class fast_limo::Mapper {
   int linearize(const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, std::vector<int32_t>& valid,
                 std::vector<double>& H, std::vector<double>& g, std::vector<double>& cost, std::vector<double>* rows = nullptr,
                 std::vector<int32_t>* pair_cnt = nullptr);
+  // Pose hypotheses from point correspondences (flimo_corr_poses, same arguments and results): src[i] in the body frame is dst[i] in
+  // the map's; per triplet of tri the pre-rejection, the closed-form pose and the correspondences it explains.  Reads neither the map
+  // nor the resident scan: it only runs on this Mapper's context (created here if there is none yet), after an insert, a crop or a
+  // carve on the worker thread has ended.  Returns a FLIMO_* code.
+  int corr_poses(const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh, const flimo_corr_cfg* cfg,
+                 int32_t* status, int32_t* inliers, double* sum_sqd, double* pose = nullptr, float* pair_sqd = nullptr);
   void sync();                                  // wait for a running insert or crop (no-op when idle)
   void set_async(bool on) { sync(); async_ = on; }
   double last_insert_seconds() { sync(); return insert_seconds_; }

@@ -566,6 +566,66 @@ int flimo_scan_fitness(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t 
 int flimo_scan_linearize(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t np, int k, float max_dist, int min_pts, float max_curv,
                          int32_t* valid /* [np] */, double* H /* [np][21] */, double* g /* [np][6] */, double* cost /* [np] */,
                          double* rows /* [np][n][7], may be NULL */, int32_t* pair_cnt /* [np][n], may be NULL */);
+/* ---- pose hypotheses from point correspondences: what pcl::SampleConsensusPrerejective does per sample (the reference's
+ *      relocation branch gets the same from KISS-Matcher's pruning and solver) -- minimal samples of three correspondences, a cheap
+ *      polygon test, a closed-form rigid pose for each of the rest, and the count of the correspondences each pose explains, for
+ *      all of the caller's samples at once.  The poses are the pos / rot entries of x26 rows for flimo_scan_fitness and
+ *      flimo_scan_linearize. ----
+ * Correspondence i says that body-frame point src[i] is map point dst[i] (both packed xyz, [m][3]).  Hypothesis j is the triplet
+ * (a, b, c) = tri[j]; the samples are the caller's, so the call is deterministic.  Everything below is float64 on the float32 inputs
+ * widened, nothing contracted, in exactly the written association, unless it says float32; sq(v) = v.x*v.x + (v.y*v.y + v.z*v.z).
+ *  1. Edges, for both clouds: e_ab = sq(p_b - p_a), e_bc = sq(p_c - p_b), e_ca = sq(p_a - p_c).
+ *  2. The hypothesis is FLIMO_CORR_DEGENERATE if two of its indices are equal, or if any of the six edges fails
+ *     e >= (double)min_edge * (double)min_edge (a NaN coordinate fails it).
+ *  3. Otherwise it is FLIMO_CORR_REJECTED if any of the pairs (e_s, e_d) = the same edge in src and dst fails
+ *     fmin(e_s, e_d) >= s2 * fmax(e_s, e_d), s2 = (double)edge_sim * (double)edge_sim (no division; edge_sim == 0 rejects nothing).
+ *  4. Otherwise the pose is TRIAD's (only + - * / sqrt).  Per cloud: e1 = p_b - p_a, e2 = p_c - p_a, u1 = e1 / sqrt(sq(e1)) (three
+ *     divisions), cr = u1 x e2 = (y z' - z y', z x' - x z', x y' - y x'), u3 = cr / sqrt(sq(cr)), u2 = u3 x u1.  Then
+ *       R[r][c] = u1d[r]*u1s[c] + (u2d[r]*u2s[c] + u3d[r]*u3s[c])
+ *       cs = ((s_a + s_b) + s_c) / 3.0 per coordinate, cd likewise
+ *       t[r] = cd[r] - (R[r][0]*cs[0] + (R[r][1]*cs[1] + R[r][2]*cs[2]))
+ *     A non-finite entry of R or t (a collinear triangle) makes the hypothesis FLIMO_CORR_DEGENERATE.  The quaternion is Shepperd's:
+ *     the largest of (trace, R00, R11, R22) with trace = R00 + (R11 + R22), the first on a tie, selects the branch --
+ *       trace: w = 0.5*sqrt(1 + trace),               f = 0.25 / w, x = (R21 - R12)*f, y = (R02 - R20)*f, z = (R10 - R01)*f
+ *       R00:   x = 0.5*sqrt(1 + ((R00 - R11) - R22)), f = 0.25 / x, w = (R21 - R12)*f, y = (R01 + R10)*f, z = (R02 + R20)*f
+ *       R11:   y = 0.5*sqrt(1 + ((R11 - R00) - R22)), f = 0.25 / y, w = (R02 - R20)*f, x = (R01 + R10)*f, z = (R12 + R21)*f
+ *       R22:   z = 0.5*sqrt(1 + ((R22 - R00) - R11)), f = 0.25 / z, w = (R10 - R01)*f, x = (R02 + R20)*f, y = (R12 + R21)*f
+ *     -- without sign normalisation or renormalisation.  pose7 = (t, x, y, z, w).
+ *  5. The inlier test is float32, so that it is what flimo_scan_fitness would see: RT is the 3 x 4 matrix pose_from_x26 forms from
+ *     pose7 placed into an x26 (float32 casts, Eigen's toRotationMatrix); w_i = c0*x + (c1*y + (c2*z + c3)) of src[i] per row, the
+ *     arithmetic of flimo_scan_to_world; sqd_i = (w_i - dst[i]).squaredNorm() as the searches form it (dx*dx + (dy*dy + dz*dz));
+ *     pair i is an inlier iff sqd_i < max_dist * max_dist (one float32 product, a strict compare; INFINITY: no gate).
+ * Outputs, host memory:
+ *  - status [nh]: FLIMO_CORR_OK / _DEGENERATE / _REJECTED.
+ *  - pose [nh][7] (may be NULL): pose7.
+ *  - pair_sqd [nh][m] (may be NULL): sqd_i for an inlier, -1.0f for a non-inlier.
+ *  - inliers [nh]: the exact count.  sum_sqd [nh]: the float64 sum of the inliers' float32 sqd in the shape of flimo_scan_fitness'
+ *    sum with n = m: thread t of 256 adds slots t, t + 256, ... in ascending order (a non-inlier adds nothing), then
+ *    partial[t] += partial[t + o] for o = 128, 64 .. 1.  No floating-point atomics: the bits of a hypothesis's outputs depend on the
+ *    two clouds, its triplet and the cfg alone -- not on nh, the other hypotheses, the chunking or which survivors share a workgroup.
+ * A hypothesis that is not OK has inliers 0, sum_sqd +0.0, pose NaN, pair_sqd -1.
+ * nh == 0 returns FLIMO_OK and touches nothing.  FLIMO_ERR_INVALID: a NULL ctx / cfg / status / inliers / sum_sqd, NULL src or dst
+ * (m > 0) or tri (nh > 0), a cfg field that is NaN or negative, edge_sim > 1, a triplet index outside [0, m) (the host checks all of
+ * them before anything is launched).  FLIMO_ERR_TOO_LARGE: m or nh >= 2^31, or nh * m >= 2^31 when pair_sqd is asked for.  The
+ * outputs are untouched on an error.  The map and the resident scan are neither read nor changed; an empty context will do.  Calling
+ * rules as flimo_knn_k (no pass in flight).  Device memory: both clouds, and scratch per chunk of 2^16 hypotheses (at most 2^26
+ * slots of pair_sqd), not per call.
+ * flimo_corr_pose_host: steps 1 - 4 and the matrix of step 5 for ONE triplet on the host, by the same host / device function the
+ * kernel calls: src3 / dst3 = the points a, b, c.  Returns the status (>= 0; pose7 and rt12 -- the upper three rows of RT,
+ * row-major -- are NaN unless it is FLIMO_CORR_OK), or FLIMO_ERR_INVALID for a NULL pointer or a cfg the call above rejects. */
+typedef struct flimo_corr_cfg {
+  float edge_sim;   /* 0 .. 1: polygon pre-rejection, 0 = none */
+  float min_edge;   /* >= 0 [m]: shorter triangle edges are degenerate */
+  float max_dist;   /* >= 0 [m], INFINITY allowed: the inlier gate */
+} flimo_corr_cfg;
+#define FLIMO_CORR_OK 0
+#define FLIMO_CORR_DEGENERATE 1
+#define FLIMO_CORR_REJECTED 2
+int flimo_corr_poses(flimo_ctx* ctx, const float* src_xyz /* [m][3] */, const float* dst_xyz /* [m][3] */, size_t m,
+                     const int32_t* tri /* [nh][3] */, size_t nh, const flimo_corr_cfg* cfg,
+                     int32_t* status /* [nh] */, int32_t* inliers /* [nh] */, double* sum_sqd /* [nh] */,
+                     double* pose /* [nh][7], may be NULL */, float* pair_sqd /* [nh][m], may be NULL */);
+int flimo_corr_pose_host(const float src3[9], const float dst3[9], const flimo_corr_cfg* cfg, double pose7[7], float rt12[12]);
 /* Both clouds the caller of Localizer::updatePointCloud may ask for (pc2match: body frame; final_scan: world frame of pose x26,
  * Localizer.cpp:361-371) in ONE round trip: packed float4 records (x, y, z, unused) in pinned memory owned by the context, valid
  * until the next flimo_scan_clouds on it.  *n = points in each. */

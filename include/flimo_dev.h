@@ -82,6 +82,9 @@ int flimo_set_outlier_chunk(flimo_ctx* ctx, size_t n);
  * over the range: the chunk bounds the normals' moments, the worklist and the rows on their way back, 220 B a point; equal results
  * whatever the chunk. */
 int flimo_set_fpfh_chunk(flimo_ctx* ctx, size_t n);
+/* flimo_corr_poses works in chunks of n hypotheses (default 2^16; 0 restores it): the chunk bounds the call's device scratch, 136 B
+ * a hypothesis (and m floats each where pair_sqd is asked for: then at most 2^26 slots a chunk); equal results whatever the chunk. */
+int flimo_set_corr_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_scan_fitness works in chunks of whole poses, at most `pairs` (pose, point) pairs each (default 2^22; 0 restores it); a
  * single pose with more points than that runs alone.  The chunk bounds the call's device scratch.  The results do not depend on it
  * (tests, A/B). */

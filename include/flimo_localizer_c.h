@@ -130,6 +130,11 @@ int    flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, 
  * has no map yet answers like an empty one (first = n = 0: nothing touched; any other range lies beyond it).  The Localizer's own
  * update does not use it. */
 int    flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh, uint8_t* spfh, int32_t* cnt);
+/* Pose hypotheses from point correspondences: flimo_corr_poses (include/flimo_c.h: same arguments, same results, same error
+ * codes) on the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  Neither the map
+ * nor the resident scan is read; a Localizer that has no context yet creates it.  The Localizer's own update does not use it. */
+int    flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
+                            const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd);
 /* How well the scan resident in the map's context -- after updatePointCloud: pc2match -- fits the Localizer's map at each of np pose
  * hypotheses: flimo_scan_fitness (include/flimo_c.h: same arguments, same results, same error codes; n = the size of pc2match) on
  * the map's context, after an insert or a crop still running behind the last sweep has ended.  A Localizer that has no map yet
