@@ -174,6 +174,26 @@ def corr_call(call, src, dst, tri, want, cfg):
     return out
 
 
+DESC_MAX_DIM, DESC_MAX_K = 64, 8      # FLIMO_DESC_MAX_DIM / FLIMO_DESC_MAX_K
+
+
+def desc_rows(desc):
+    """A descriptor array as the calls take it: C-contiguous float32 [n, dim] (a 1-D array is one column)."""
+    d = np.ascontiguousarray(desc, dtype=np.float32)
+    return d.reshape(-1, 1) if d.ndim == 1 else d.reshape(d.shape[0], int(np.prod(d.shape[1:])))
+
+
+def desc_match_call(call, q, k):
+    """The output arrays of flimo_desc_match / flimo_loc_desc_match (``call`` takes: q, nq, dim, k, idx, dist, cnt) as a dict
+    ``idx`` [nq, k] int32, ``dist`` [nq, k] float32, ``cnt`` [nq] int32; shared with ``api.Localizer``."""
+    q = desc_rows(q)
+    nq, kk = q.shape[0], max(int(k), 1)
+    out = {"idx": np.full((nq, kk), -1, np.int32), "dist": np.zeros((nq, kk), np.float32), "cnt": np.zeros(nq, np.int32)}
+    ptr = lambda a: a.ctypes.data if a.size else C.addressof(_NONE)      # (an array of no element may have no address)
+    call(ptr(q), nq, q.shape[1], int(k), ptr(out["idx"]), ptr(out["dist"]), ptr(out["cnt"]))
+    return out
+
+
 class ChainPass(C.Structure):
     _fields_ = [("M", C.c_int), ("stragglers", C.c_int), ("ties", C.c_int), ("HTH", C.c_double * 144), ("HTh", C.c_double * 12),
                 ("dx", C.c_double * 23), ("x_after", C.c_double * 26)]
@@ -200,7 +220,7 @@ FRAME_DTYPE = np.dtype([
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
     "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_scan_size", "flimo_scan_get",
+    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
@@ -322,6 +342,15 @@ def load_hip():
                                    C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_corr_pose_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CorrCfg), C.c_void_p, C.c_void_p]
     L.flimo_set_corr_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_desc_ref_set.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int]
+    L.flimo_desc_ref_size.restype = C.c_size_t
+    L.flimo_desc_ref_size.argtypes = [vp]
+    L.flimo_desc_ref_dim.argtypes = [vp]
+    L.flimo_desc_match.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_desc_dist_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.flimo_set_desc_chunk.argtypes = [vp, C.c_size_t, C.c_size_t]
+    L.flimo_desc_last_ms.restype = C.c_float
+    L.flimo_desc_last_ms.argtypes = [vp]
     L.flimo_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.flimo_scan_size.restype = C.c_size_t
     L.flimo_scan_size.argtypes = [vp]
@@ -667,6 +696,32 @@ class HipCtx:
     def set_corr_chunk(self, n):
         """Hypotheses per chunk of ``corr_poses`` (flimo_set_corr_chunk; 0: the default of 2^16)."""
         self._chk(self._L.flimo_set_corr_chunk(self._h, int(n)))
+
+    def desc_ref_set(self, desc):
+        """flimo_desc_ref_set: ``desc`` [nr, dim] float32 becomes the context's resident reference set of ``desc_match`` (the map's
+        descriptors: set once, matched against many times); it replaces the previous one, no rows clear it."""
+        d = desc_rows(desc)
+        self._chk(self._L.flimo_desc_ref_set(self._h, d.ctypes.data if d.size else None, d.shape[0], d.shape[1] if d.shape[0] else 0))
+
+    def desc_ref_size(self) -> int:
+        return int(self._L.flimo_desc_ref_size(self._h))
+
+    def desc_ref_dim(self) -> int:
+        return int(self._L.flimo_desc_ref_dim(self._h))
+
+    def desc_match(self, q, k=2):
+        """flimo_desc_match: per row of ``q`` [nq, dim] the first ``k`` rows of the resident reference set by (bits of the float32
+        squared distance, index) -- the distance is include/flimo_c.h's fmaf chain, exact and reproducible.  Returns a dict: idx
+        [nq, k] int32 (-1 beyond cnt), dist [nq, k] float32 (0 beyond cnt), cnt [nq].  Rows with a non-finite entry never match."""
+        return desc_match_call(lambda *a: self._chk(self._L.flimo_desc_match(self._h, *a)), q, k)
+
+    def set_desc_chunk(self, queries_per_chunk=0, refs_per_split=0):
+        """Queries per chunk of ``desc_match`` and reference rows per split of its grid (flimo_set_desc_chunk; 0: the defaults)."""
+        self._chk(self._L.flimo_set_desc_chunk(self._h, int(queries_per_chunk), int(refs_per_split)))
+
+    def desc_last_ms(self) -> float:
+        """GPU ms of the last ``desc_match``'s launches (flimo_desc_last_ms; 0 unless ``set_timing`` is on)."""
+        return float(self._L.flimo_desc_last_ms(self._h))
 
     def scan_voxel_filter(self, leaf: float) -> int:
         n = C.c_size_t(0)

@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -146,6 +146,8 @@ def load_host():
                                            C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_corr_poses.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_lib.CorrCfg), C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_desc_ref_set.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int]
+    L.flimo_loc_desc_match.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_set_map_carving.restype = None
     L.flimo_loc_set_map_carving.argtypes = [vp, C.c_int, C.POINTER(_lib.CarveCfg)]
     L.flimo_carve_rule.restype = C.c_int
@@ -502,6 +504,21 @@ class Localizer:
         the resident scan.  The Localizer's own update does not use it."""
         return _lib.corr_call(lambda *a: self._corr_chk(self._L.flimo_loc_corr_poses(self._h, *a)), src, dst, tri, want, cfg)
 
+    def desc_ref_set(self, desc):
+        """``desc`` [nr, dim] becomes the resident reference set of ``desc_match`` on the map's context (flimo_loc_desc_ref_set), as
+        ``HipCtx.desc_ref_set``.  Waits for an insert, a crop or a carve still running; reads neither the map nor the scan."""
+        d = _lib.desc_rows(desc)
+        self._outliers_chk(self._L.flimo_loc_desc_ref_set(self._h, d.ctypes.data if d.size else None, d.shape[0], d.shape[1] if d.shape[0] else 0),
+                           "flimo_loc_desc_ref_set")
+
+    def desc_ref_size(self) -> int:
+        return self.hip.desc_ref_size()
+
+    def desc_match(self, q, k=2):
+        """Nearest rows of the resident reference set (flimo_loc_desc_match): the dict of ``HipCtx.desc_match``.  The Localizer's own
+        update does not use it."""
+        return _lib.desc_match_call(lambda *a: self._outliers_chk(self._L.flimo_loc_desc_match(self._h, *a), "flimo_loc_desc_match"), q, k)
+
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))
 
@@ -708,6 +725,64 @@ def corr_consensus(obj, src, dst, nh, seed=0, top=8, x26_like=None, **cfg):
     x[:, 0:7] = out["pose"][best]
     return dict(x26=x, inliers=out["inliers"][best], sum_sqd=out["sum_sqd"][best], cost=cost[order], index=best.astype(np.int64),
                 tri=tri[best], survivors=int(ok.size))
+
+
+def desc_pairs(ref_obj, qry_obj, q_desc, r_desc, ratio=0.9, mutual=True):
+    """Putative pairs (qi, rj) -- two int64 arrays, ascending in qi -- between the rows of ``q_desc`` and ``r_desc`` by nearest
+    descriptor, Lowe's ratio test and a mutual check.  ``ref_obj`` holds ``r_desc`` as its resident reference set, ``qry_obj`` holds
+    ``q_desc`` (``desc_ref_set`` on a ``HipCtx`` or a ``Localizer``: the context whose map is the scan exists anyway, its FPFH came
+    from it).  Forward: ``ref_obj.desc_match(q_desc, k=2)``; query i proposes (i, idx[i, 0]) when it has a neighbour, neither row of
+    the pair is all-zero (points FPFH found no feature for), and -- float64 on the squared distances -- cnt < 2 or
+    d0 <= ratio^2 * d1.  Mutual: the DISTINCT proposed reference rows go through ``qry_obj.desc_match(.., k=1)``; a pair stays when
+    the answer is i.  That second call is nq-by-at-most-nq: no reverse pass over the map."""
+    q = _lib.desc_rows(q_desc)
+    r = _lib.desc_rows(r_desc)
+    fwd = ref_obj.desc_match(q, k=2)
+    idx, dist, cnt = fwd["idx"], fwd["dist"].astype(np.float64), fwd["cnt"]
+    j0 = np.where(cnt >= 1, idx[:, 0], 0).astype(np.int64)
+    keep = (cnt >= 1) & np.any(q != 0, axis=1)
+    if r.shape[0]:
+        keep &= np.any(r[j0] != 0, axis=1)
+    keep &= (cnt < 2) | (dist[:, 0] <= (float(ratio) * float(ratio)) * dist[:, 1])
+    qi = np.nonzero(keep)[0].astype(np.int64)
+    rj = j0[qi]
+    if mutual and qi.size:
+        sel, inv = np.unique(rj, return_inverse=True)
+        back = qry_obj.desc_match(r[sel], k=1)
+        answer = np.where(back["cnt"] >= 1, back["idx"][:, 0], -1).astype(np.int64)
+        stay = answer[inv] == qi
+        qi, rj = qi[stay], rj[stay]
+    return qi, rj
+
+
+def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=True, nh=4096, seed=0, top=8, corr=None, fitness_max_dist=1.0, align=None,
+               x26_like=None):
+    """A pose of a scan in a map from nothing but the two clouds -- plumbing over six calls, every parameter the caller's.
+    ``map_obj`` (a ``HipCtx`` or a ``Localizer``) holds the map, and the scan (body frame) as its resident scan; ``scan_obj`` is a
+    context whose MAP is that scan.  FPFH of both sides (``fpfh``: the fields of ``_lib.fpfh_cfg``; ``scan_fpfh``: the scan side's
+    where they differ -- a viewpoint is in the frame of its cloud), ``desc_ref_set`` on both,
+    ``desc_pairs(ratio, mutual)``, ``corr_consensus`` on the paired points (``nh``, ``seed``, ``top``, ``corr``: the fields of
+    ``_lib.corr_cfg``), ``scan_fitness`` of the returned rows on ``map_obj`` ranked by ``fitness_cost`` at ``fitness_max_dist``,
+    ``scan_align`` (``align``: its keyword arguments) of the best row.  Returns the dict of each stage: pairs (qi, rj), fpfh (the
+    scan's rows, the map's), src, dst,
+    consensus, fitness (inliers, sum_sqd, cost, x26: the rows in ranked order), align, and x26: the refined best row."""
+    fpfh, corr, align = dict(fpfh or {}), dict(corr or {}), dict(align or {})
+    m_hip, s_hip = getattr(map_obj, "hip", map_obj), getattr(scan_obj, "hip", scan_obj)
+    f_map = map_obj.map_fpfh(want=(), **fpfh)["fpfh"]
+    f_scan = scan_obj.map_fpfh(want=(), **(fpfh if scan_fpfh is None else dict(scan_fpfh)))["fpfh"]
+    map_obj.desc_ref_set(f_map)
+    scan_obj.desc_ref_set(f_scan)
+    qi, rj = desc_pairs(map_obj, scan_obj, f_scan, f_map, ratio=ratio, mutual=mutual)
+    src, dst = s_hip.map_points()[qi], m_hip.map_points()[rj]
+    cons = corr_consensus(map_obj, src, dst, nh, seed=seed, top=top, x26_like=x26_like, **corr)
+    inliers, sum_sqd = map_obj.scan_fitness(cons["x26"], max_dist=fitness_max_dist)
+    cost = fitness_cost(inliers, sum_sqd, m_hip.scan_size(), fitness_max_dist)
+    order = np.lexsort((np.arange(cost.size), cost))
+    ranked = cons["x26"][order]
+    aligned = scan_align(map_obj, ranked[:1], **align)
+    return dict(pairs=(qi, rj), fpfh=(f_scan, f_map), src=src, dst=dst, consensus=cons,
+                fitness=dict(inliers=inliers[order], sum_sqd=sum_sqd[order], cost=cost[order], x26=ranked), align=aligned,
+                x26=aligned["x26"][0] if ranked.shape[0] else None)
 
 
 ALIGN_RUNNING, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2      # scan_align's status per pose: ran every iteration / too few valid pairs / H not positive definite

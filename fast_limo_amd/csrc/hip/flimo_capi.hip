@@ -24,6 +24,7 @@
 #include "flimo_math.h"
 #include "flimo_pose.h"
 #include "flimo_corr.h"
+#include "flimo_desc.h"
 #include "flimo_chain.h"
 #include "flimo_ieskf.h"
 #include "flimo_insert.h"
@@ -62,6 +63,14 @@ struct flimo_ctx {
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   size_t corr_chunk = (size_t)1 << 16;      // hypotheses per chunk of flimo_corr_poses (flimo_set_corr_chunk)
+  // the resident reference set of flimo_desc_match (flimo_desc_ref_set): the rows in the MFMA operand layout and their norms
+  float* d_desc_rt = nullptr;
+  float* d_desc_norm = nullptr;
+  size_t desc_nr = 0;
+  int desc_dim = 0;
+  size_t desc_chunk = (size_t)1 << 16;      // queries per chunk of flimo_desc_match (flimo_set_desc_chunk)
+  size_t desc_split = 0;                    // reference rows per split of its grid; 0: chosen per chunk, to fill the device
+  float desc_last_ms = 0.f;                 // GPU time of the last call's launches (timing level >= 1)
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
   IndexTables idx;                 // the index of the main grid (GridView, flimo_types.h): tiles, directory, escapes, xstart
   GridView grid{};
@@ -573,6 +582,7 @@ extern "C" void flimo_ctx_destroy(flimo_ctx* c) {
   if (c->book) insert_book_destroy(c->book);
   c->gbook.release();
   (void)hipFree(c->d_batch);
+  (void)hipFree(c->d_desc_rt); (void)hipFree(c->d_desc_norm);
   delete c;
 }
 
@@ -3414,6 +3424,113 @@ extern "C" int flimo_set_corr_chunk(flimo_ctx* c, size_t n) {
   c->corr_chunk = n ? n : (size_t)1 << 16;
   return FLIMO_OK;
 }
+
+// ---- nearest descriptors: the resident reference set and the match (the step between flimo_map_fpfh and flimo_corr_poses) ---------
+// kernels: flimo_desc.hip.  flimo_desc_ref_set uploads the rows once, and two launches leave their norms and their MFMA operand
+// layout on the device.  flimo_desc_match runs the queries in chunks of c->desc_chunk: per chunk the rows go up, three launches
+// (the queries' norms, the match over (query tiles) x (splits of the reference set), the merge of the splits), idx / dist / cnt
+// come back; device scratch is the chunk's, whatever nq.  Reads neither the map nor the scan.
+static void desc_ref_free(flimo_ctx* c) {
+  (void)hipFree(c->d_desc_rt); (void)hipFree(c->d_desc_norm);
+  c->d_desc_rt = c->d_desc_norm = nullptr;
+  c->desc_nr = 0;
+  c->desc_dim = 0;
+}
+extern "C" int flimo_desc_ref_set(flimo_ctx* c, const float* desc, size_t nr, int dim) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (nr > 0 && !desc) return fail(c, FLIMO_ERR_INVALID, "desc ref set: null desc");
+  if (nr > 0 && (dim < 1 || dim > FLIMO_DESC_MAX_DIM)) return fail(c, FLIMO_ERR_UNSUPPORTED, "desc ref set: dim must be in 1..%d", FLIMO_DESC_MAX_DIM);
+  if (nr >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "desc ref set: nr must be below 2^31");
+  ctx_enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  desc_ref_free(c);
+  if (nr == 0) return FLIMO_OK;
+  const size_t ntiles = (nr + 31) / 32;
+  DevScratch d;
+  float* d_rows = d.get<float>(nr * (size_t)dim);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMalloc(&c->d_desc_rt, ntiles * (size_t)desc_steps(dim) * 64 * sizeof(float)));
+  HIPCHK(c, hipMalloc(&c->d_desc_norm, ntiles * 32 * sizeof(float)));
+  HIPCHK(c, hipMemcpyAsync(d_rows, desc, nr * (size_t)dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_desc_norms(c->stream, d_rows, (unsigned)nr, dim, c->d_desc_norm, (unsigned)(ntiles * 32)));
+  HIPCHK(c, launch_desc_pack(c->stream, d_rows, (unsigned)nr, dim, c->d_desc_rt));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->desc_nr = nr;
+  c->desc_dim = dim;
+  return FLIMO_OK;
+}
+extern "C" size_t flimo_desc_ref_size(const flimo_ctx* c) { return c ? c->desc_nr : 0; }
+extern "C" int flimo_desc_ref_dim(const flimo_ctx* c) { return c ? c->desc_dim : 0; }
+extern "C" int flimo_desc_match(flimo_ctx* c, const float* q, size_t nq, int dim, int k, int32_t* idx, float* dist, int32_t* cnt) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if ((nq > 0 && !q) || !idx || !dist || !cnt) return fail(c, FLIMO_ERR_INVALID, "desc match: null q / idx / dist / cnt");
+  if (dim < 1 || dim > FLIMO_DESC_MAX_DIM) return fail(c, FLIMO_ERR_UNSUPPORTED, "desc match: dim must be in 1..%d", FLIMO_DESC_MAX_DIM);
+  if (k < 1 || k > FLIMO_DESC_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "desc match: k must be in 1..%d", FLIMO_DESC_MAX_K);
+  if (nq >= 0x80000000ull || (unsigned long long)nq * (unsigned long long)k >= 0x80000000ull)
+    return fail(c, FLIMO_ERR_TOO_LARGE, "desc match: nq and nq * k must be below 2^31");
+  if (c->desc_nr > 0 && dim != c->desc_dim)
+    return fail(c, FLIMO_ERR_INVALID, "desc match: the queries have dim %d, the resident set %d", dim, c->desc_dim);
+  if (nq == 0) return FLIMO_OK;
+  c->desc_last_ms = 0.f;
+  if (c->desc_nr == 0) {      // nothing to be nearest to
+    for (size_t i = 0; i < nq; i++) cnt[i] = 0;
+    for (size_t i = 0; i < nq * (size_t)k; i++) { idx[i] = -1; dist[i] = 0.f; }
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  const size_t m = std::min(nq, std::max<size_t>(c->desc_chunk, 1));      // queries of a chunk
+  const size_t ntiles = (c->desc_nr + 31) / 32;
+  // reference tiles per split: the caller's, or as many splits as bring the grid to about four workgroups a compute unit, none
+  // below 32 tiles; never more than 32768 splits
+  size_t tps;
+  if (c->desc_split) tps = (c->desc_split + 31) / 32;
+  else {
+    const size_t groups = (m + (size_t)desc_query_tile(dim) - 1) / (size_t)desc_query_tile(dim);
+    const size_t want = std::max<size_t>(1024 / groups, 1);
+    tps = std::max<size_t>((ntiles + want - 1) / want, 32);
+  }
+  tps = std::max(tps, (ntiles + 32767) / 32768);
+  const size_t nsplit = (ntiles + tps - 1) / tps;
+  const int kl = desc_list_len(k);
+  DevScratch d;
+  float* d_q = d.get<float>(m * (size_t)dim);
+  float* d_qnorm = d.get<float>(m);
+  unsigned long long* d_part = d.get<unsigned long long>(nsplit * m * (size_t)kl);
+  int32_t* d_idx = d.get<int32_t>(m * (size_t)k);
+  float* d_dist = d.get<float>(m * (size_t)k);
+  int32_t* d_cnt = d.get<int32_t>(m);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (c->timing) { HIPCHK(c, hipEventCreate(&ev[0])); HIPCHK(c, hipEventCreate(&ev[1])); }
+  for (size_t a = 0; a < nq; a += m) {
+    const size_t na = std::min(m, nq - a);
+    HIPCHK(c, hipMemcpyAsync(d_q, q + a * (size_t)dim, na * (size_t)dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (ev[0]) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    HIPCHK(c, launch_desc_match(c->stream, c->d_desc_rt, c->d_desc_norm, (unsigned)c->desc_nr, (unsigned)tps, d_q, d_qnorm, (unsigned)na, dim, k,
+                                d_part, d_idx, d_dist, d_cnt));
+    if (ev[1]) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    HIPCHK(c, hipMemcpyAsync(idx + a * (size_t)k, d_idx, na * (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dist + a * (size_t)k, d_dist, na * (size_t)k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt + a, d_cnt, na * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the next chunk overwrites the chunk's buffers)
+    if (ev[0]) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->desc_last_ms += ms; }
+  }
+  if (ev[0]) { (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); }
+  return FLIMO_OK;
+}
+extern "C" int flimo_desc_dist_host(const float* a, const float* b, int dim, float* d) {
+  if (!a || !b || !d) return FLIMO_ERR_INVALID;
+  if (dim < 1 || dim > FLIMO_DESC_MAX_DIM) return FLIMO_ERR_UNSUPPORTED;
+  *d = desc_dist(desc_norm(a, dim), desc_norm(b, dim), desc_dot(a, b, dim));
+  return FLIMO_OK;
+}
+extern "C" int flimo_set_desc_chunk(flimo_ctx* c, size_t queries_per_chunk, size_t refs_per_split) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->desc_chunk = queries_per_chunk ? queries_per_chunk : (size_t)1 << 16;
+  c->desc_split = refs_per_split;
+  return FLIMO_OK;
+}
+extern "C" float flimo_desc_last_ms(const flimo_ctx* c) { return c ? c->desc_last_ms : 0.f; }
 
 // ---- point-to-plane normal equations of the resident scan under pose hypotheses: one linearisation of a registration ----------
 // kernels: flimo_knn_k.hip.  Chunks of whole poses as flimo_scan_fitness, c->linearize_chunk pairs at most unless one pose alone

@@ -349,4 +349,18 @@ hipError_t launch_corr_poses(hipStream_t st, const float* src, const float* dst,
                              float min_edge, float max_dist, int32_t* status, double* pose, float* rt, int32_t* surv, unsigned* nsurv,
                              int32_t* inliers, double* sum_sqd, float* pair_sqd);
 
+// flimo_desc.hip -- nearest descriptors (flimo_desc_match, flimo_c.h).  The resident reference set is two arrays: norm
+// [ceil(nr / 32) * 32] (launch_desc_norms with npad = that; NaN for an excluded row and for the padding) and rt
+// [ceil(nr / 32)][desc_steps(dim)][64], the rows in the MFMA's A-operand layout (launch_desc_pack).  launch_desc_match answers a
+// chunk of nq queries q [nq][dim] against it: the queries' norms (qnorm [nq], scratch), the match over splits of tiles_per_split
+// >= 1 reference tiles each (part: scratch, [splits][nq][desc_list_len(k)] keys; splits <= 65535), the merge into idx / dist
+// [nq][k] and cnt [nq].  A workgroup of the match takes desc_query_tile(dim) queries.
+int desc_steps(int dim);
+int desc_query_tile(int dim);
+int desc_list_len(int k);
+hipError_t launch_desc_norms(hipStream_t st, const float* x, unsigned n, int dim, float* norm, unsigned npad);
+hipError_t launch_desc_pack(hipStream_t st, const float* x, unsigned n, int dim, float* rt);
+hipError_t launch_desc_match(hipStream_t st, const float* rt, const float* rnorm, unsigned nr, unsigned tiles_per_split, const float* q,
+                             float* qnorm, unsigned nq, int dim, int k, unsigned long long* part, int32_t* idx, float* dist, int32_t* cnt);
+
 }  // namespace flimo

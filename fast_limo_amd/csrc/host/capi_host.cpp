@@ -360,6 +360,14 @@ int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xy
   if (!L) return FLIMO_ERR_INVALID;
   return L->map->corr_poses(src_xyz, dst_xyz, m, tri, nh, cfg, status, inliers, sum_sqd, pose, pair_sqd);
 }
+int flimo_loc_desc_ref_set(flimo_loc* L, const float* desc, size_t nr, int dim) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return L->map->desc_ref_set(desc, nr, dim);
+}
+int flimo_loc_desc_match(flimo_loc* L, const float* q, size_t nq, int dim, int k, int32_t* idx, float* dist, int32_t* cnt) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return L->map->desc_match(q, nq, dim, k, idx, dist, cnt);
+}
 int flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
                            int32_t* nn_idx) {
   if (!L) return FLIMO_ERR_INVALID;

@@ -597,6 +597,18 @@ int Mapper::corr_poses(const float* src_xyz, const float* dst_xyz, size_t m, con
   return flimo_corr_poses(ctx_, src_xyz, dst_xyz, m, tri, nh, cfg, status, inliers, sum_sqd, pose, pair_sqd);
 }
 
+// nearest descriptors: the resident reference set and the match (an insert, a crop or a carve on the worker thread ends first)
+int Mapper::desc_ref_set(const float* desc, size_t nr, int dim) {
+  sync();
+  if (!ctx_ && !attach(device_, cell_size_)) return FLIMO_ERR_NO_DEVICE;
+  return flimo_desc_ref_set(ctx_, desc, nr, dim);
+}
+int Mapper::desc_match(const float* q, size_t nq, int dim, int k, int32_t* idx, float* dist, int32_t* cnt) {
+  sync();
+  if (!ctx_ && !attach(device_, cell_size_)) return FLIMO_ERR_NO_DEVICE;
+  return flimo_desc_match(ctx_, q, nq, dim, k, idx, dist, cnt);
+}
+
 void Mapper::add(pcl::PointCloud<PointType>::Ptr& pc, double time) {   // Mapper.cpp:88-96
   if (!pc || pc->points.size() < 1) return;
   sync();

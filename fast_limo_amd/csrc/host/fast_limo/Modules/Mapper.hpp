@@ -120,6 +120,11 @@ class fast_limo::Mapper {
   // carve on the worker thread has ended.  Returns a FLIMO_* code.
   int corr_poses(const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh, const flimo_corr_cfg* cfg,
                  int32_t* status, int32_t* inliers, double* sum_sqd, double* pose = nullptr, float* pair_sqd = nullptr);
+  // Nearest descriptors (flimo_desc_ref_set / flimo_desc_match, same arguments and results): the reference set stays resident in
+  // this Mapper's context (created here if there is none yet); neither call reads the map or the resident scan, both run after an
+  // insert, a crop or a carve on the worker thread has ended.  Return a FLIMO_* code.
+  int desc_ref_set(const float* desc, size_t nr, int dim);
+  int desc_match(const float* q, size_t nq, int dim, int k, int32_t* idx, float* dist, int32_t* cnt);
   void sync();                                  // wait for a running insert or crop (no-op when idle)
   void set_async(bool on) { sync(); async_ = on; }
   double last_insert_seconds() { sync(); return insert_seconds_; }

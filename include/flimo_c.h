@@ -626,6 +626,48 @@ int flimo_corr_poses(flimo_ctx* ctx, const float* src_xyz /* [m][3] */, const fl
                      int32_t* status /* [nh] */, int32_t* inliers /* [nh] */, double* sum_sqd /* [nh] */,
                      double* pose /* [nh][7], may be NULL */, float* pair_sqd /* [nh][m], may be NULL */);
 int flimo_corr_pose_host(const float src3[9], const float dst3[9], const flimo_corr_cfg* cfg, double pose7[7], float rt12[12]);
+/* ---- nearest descriptors: which row of one descriptor array belongs to which row of another -- the step between flimo_map_fpfh
+ *      (33-float rows) and flimo_corr_poses (matched pairs); pcl::search over FPFH space, brute force and exact, for all query
+ *      rows at once.  tests/desc_common.py restates everything below in numpy; the tests compare every bit. ----
+ * flimo_desc_ref_set makes a REFERENCE SET resident on the device (the map's descriptors: computed once, matched against many
+ * times): desc [nr][dim] row-major, host memory.  It replaces the previous set; nr == 0 clears it.  It touches neither the map nor
+ * the scan nor the bits of any later pass, and is freed with the context.  flimo_desc_ref_size / flimo_desc_ref_dim: the resident
+ * set's rows and dim (0, 0: none).
+ * flimo_desc_match answers, per query row q[i], with the first k reference rows in the order below.  Everything is float32 with
+ * ONE rounding per written operation; fmaf is the correctly rounded fused multiply-add.
+ *  - dot(a, b) = c_dim, where c_0 = +0.0f and c_{t+1} = fmaf(a[t], b[t], c_t) for t = 0 .. dim - 1 ascending.
+ *  - n(a) = dot(a, a), the same chain.
+ *  - d(q, r) = (n(q) + n(r)) - 2 dot(q, r): one float32 addition, then one rounding of the difference (2 dot is exact, so
+ *    fmaf(-2, dot, n(q) + n(r)) and t - (dot + dot) are the same number); a negative result becomes +0.0f: d < 0 ? 0 : d.
+ *  Consequences: two bit-identical rows are at distance exactly 0.  d is the squared L2 distance within
+ *  (2 dim + 4) * 2^-24 * (n(q) + n(r)) of the exact value -- the standard bound of the three chains plus the two final roundings;
+ *  about 0.25 for two FPFH rows at their largest possible norms (three histograms of sum 100: n <= 30 000), far less typically.
+ *  That is the expanded form's accuracy, NOT the difference form's (sum of (q[t] - r[t])^2), which is relative to d itself: for
+ *  two nearly equal long rows d may be all rounding error.  The order below is exact all the same.
+ *  - Exclusion: a row with a non-finite entry is EXCLUDED -- as a query it has cnt 0, as a reference row it is never returned.  A
+ *    pair whose d comes out NaN (huge finite entries that overflow a chain: inf - inf) is not returned either.  d = +inf is a
+ *    distance like any other.
+ *  - Order: (float32 bits of d, reference index), ascending.  d is non-negative, so bit order is value order; the order is total
+ *    and unique, and does not depend on how the work is tiled, split or chunked.
+ * Outputs, host memory: idx [nq][k] the reference rows, dist [nq][k] their d, cnt [nq] = min(k, admissible reference rows of the
+ * query); the slots beyond cnt hold idx = -1, dist = 0.
+ * No resident set: FLIMO_OK, every cnt 0.  nq == 0: FLIMO_OK, nothing touched.  FLIMO_ERR_INVALID: NULL ctx / q (nq > 0) / idx /
+ * dist / cnt, dim not equal to the resident set's, NULL desc with nr > 0.  FLIMO_ERR_UNSUPPORTED: dim outside 1 ..
+ * FLIMO_DESC_MAX_DIM, k outside 1 .. FLIMO_DESC_MAX_K.  FLIMO_ERR_TOO_LARGE: nr or nq >= 2^31, nq * k >= 2^31.  The outputs are
+ * untouched on an error.  Calling rules as flimo_corr_poses (no pass in flight); neither the map nor the scan is read.  Device
+ * memory: the resident set (its rows padded to an even dim and to whole tiles of 32, and 4 B a row), and per chunk of 2^16 queries
+ * their rows, results and the partial lists of the grid's reference splits -- not per call.
+ * flimo_desc_dist_host: d for ONE pair on the host, by the same host / device functions the device code uses for the norms and the
+ * final step (NaN for a pair that the match excludes).  FLIMO_ERR_INVALID for a NULL pointer, FLIMO_ERR_UNSUPPORTED for a dim
+ * outside 1 .. FLIMO_DESC_MAX_DIM. */
+#define FLIMO_DESC_MAX_DIM 64
+#define FLIMO_DESC_MAX_K 8
+int flimo_desc_ref_set(flimo_ctx* ctx, const float* desc /* [nr][dim] */, size_t nr, int dim);
+size_t flimo_desc_ref_size(const flimo_ctx* ctx);
+int flimo_desc_ref_dim(const flimo_ctx* ctx);
+int flimo_desc_match(flimo_ctx* ctx, const float* q /* [nq][dim] */, size_t nq, int dim, int k, int32_t* idx /* [nq][k] */,
+                     float* dist /* [nq][k] */, int32_t* cnt /* [nq] */);
+int flimo_desc_dist_host(const float* a, const float* b, int dim, float* d);
 /* Both clouds the caller of Localizer::updatePointCloud may ask for (pc2match: body frame; final_scan: world frame of pose x26,
  * Localizer.cpp:361-371) in ONE round trip: packed float4 records (x, y, z, unused) in pinned memory owned by the context, valid
  * until the next flimo_scan_clouds on it.  *n = points in each. */

@@ -85,6 +85,13 @@ int flimo_set_fpfh_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_corr_poses works in chunks of n hypotheses (default 2^16; 0 restores it): the chunk bounds the call's device scratch, 136 B
  * a hypothesis (and m floats each where pair_sqd is asked for: then at most 2^26 slots a chunk); equal results whatever the chunk. */
 int flimo_set_corr_chunk(flimo_ctx* ctx, size_t n);
+/* flimo_desc_match works in chunks of queries_per_chunk queries (default 2^16; 0 restores it), and its grid splits the resident set
+ * into runs of refs_per_split rows, rounded up to whole tiles of 32 (0, the default: chosen per call so that the grid fills the
+ * device); the two bound the call's device scratch: per query of a chunk its row, its results and 16 or 64 B a split.  Equal
+ * results whatever the two (tests: one tile of queries, one tile of references a split). */
+int flimo_set_desc_chunk(flimo_ctx* ctx, size_t queries_per_chunk, size_t refs_per_split);
+/* GPU milliseconds of the launches of the last flimo_desc_match on the context, all chunks together (0 unless flimo_set_timing is on) */
+float flimo_desc_last_ms(const flimo_ctx* ctx);
 /* flimo_scan_fitness works in chunks of whole poses, at most `pairs` (pose, point) pairs each (default 2^22; 0 restores it); a
  * single pose with more points than that runs alone.  The chunk bounds the call's device scratch.  The results do not depend on it
  * (tests, A/B). */

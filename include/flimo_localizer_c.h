@@ -135,6 +135,12 @@ int    flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh
  * nor the resident scan is read; a Localizer that has no context yet creates it.  The Localizer's own update does not use it. */
 int    flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
                             const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd);
+/* Nearest descriptors: flimo_desc_ref_set / flimo_desc_match (include/flimo_c.h: same arguments, same results, same error codes) on
+ * the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  The reference set stays
+ * resident there (flimo_desc_ref_size(flimo_loc_ctx(L)) tells its size); neither the map nor the resident scan is read; a Localizer
+ * that has no context yet creates it.  The Localizer's own update does not use them. */
+int    flimo_loc_desc_ref_set(flimo_loc* L, const float* desc, size_t nr, int dim);
+int    flimo_loc_desc_match(flimo_loc* L, const float* q, size_t nq, int dim, int k, int32_t* idx, float* dist, int32_t* cnt);
 /* How well the scan resident in the map's context -- after updatePointCloud: pc2match -- fits the Localizer's map at each of np pose
  * hypotheses: flimo_scan_fitness (include/flimo_c.h: same arguments, same results, same error codes; n = the size of pc2match) on
  * the map's context, after an insert or a crop still running behind the last sweep has ended.  A Localizer that has no map yet
