@@ -174,6 +174,43 @@ def corr_call(call, src, dst, tri, want, cfg):
     return out
 
 
+class CorrGraphCfg(C.Structure):
+    """flimo_corr_graph_cfg (include/flimo_c.h)."""
+    _fields_ = [("tol", C.c_float), ("min_edge", C.c_float), ("edge_sim", C.c_float)]
+
+
+CORR_GRAPH_MAX_M = 32768      # FLIMO_CORR_GRAPH_MAX_M
+
+
+def corr_graph_cfg(tol=0.05, min_edge=0.0, edge_sim=0.0) -> CorrGraphCfg:
+    """Edge lengths within 5 cm of each other unless told otherwise: no shortest edge, no polygon test."""
+    return CorrGraphCfg(float(tol), float(min_edge), float(edge_sim))
+
+
+def corr_graph_call(call, src, dst, want, cfg):
+    """The output arrays of flimo_corr_graph / flimo_loc_corr_graph (``call`` takes: src, dst, m, cfg, degree, core, max_core, adj)
+    as a dict with "degree", "core" [m] int32, "max_core" (an int; 0 for m = 0) and, named in ``want``, "adj" [m, (m + 63) // 64]
+    uint64; shared with ``api.Localizer``."""
+    unknown = set(want) - {"adj"}
+    if unknown:
+        raise ValueError(f"corr_graph: unknown outputs {sorted(unknown)}")
+    s = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dst, dtype=np.float32).reshape(-1, 3)
+    if s.shape != d.shape:
+        raise ValueError("corr_graph: src and dst must hold the same number of points")
+    m = s.shape[0]
+    k = corr_graph_cfg(**cfg)
+    out = {"degree": np.zeros(m, np.int32), "core": np.zeros(m, np.int32)}
+    if "adj" in want:
+        out["adj"] = np.zeros((m, (m + 63) // 64), np.uint64)
+    top = C.c_int32(0)
+    # (an array of no element may have no address)
+    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(_NONE))
+    call(ptr(s), ptr(d), m, C.byref(k), ptr(out["degree"]), ptr(out["core"]), C.byref(top), ptr(out.get("adj")))
+    out["max_core"] = int(top.value)
+    return out
+
+
 DESC_MAX_DIM, DESC_MAX_K = 64, 8      # FLIMO_DESC_MAX_DIM / FLIMO_DESC_MAX_K
 
 
@@ -220,7 +257,7 @@ FRAME_DTYPE = np.dtype([
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
     "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
+    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_corr_graph", "flimo_corr_compatible_host", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
     "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
@@ -342,6 +379,8 @@ def load_hip():
                                    C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_corr_pose_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CorrCfg), C.c_void_p, C.c_void_p]
     L.flimo_set_corr_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_corr_graph.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CorrGraphCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_corr_compatible_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CorrGraphCfg)]
     L.flimo_desc_ref_set.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int]
     L.flimo_desc_ref_size.restype = C.c_size_t
     L.flimo_desc_ref_size.argtypes = [vp]
@@ -696,6 +735,14 @@ class HipCtx:
     def set_corr_chunk(self, n):
         """Hypotheses per chunk of ``corr_poses`` (flimo_set_corr_chunk; 0: the default of 2^16)."""
         self._chk(self._L.flimo_set_corr_chunk(self._h, int(n)))
+
+    def corr_graph(self, src, dst, want=(), **cfg):
+        """flimo_corr_graph: which of the putative pairs ``src`` [m, 3] / ``dst`` [m, 3] can be true together.  Pairs i and j are
+        joined when the edge between them is as long in ``src`` as in ``dst`` to within ``tol`` (``cfg``: the fields of
+        ``corr_graph_cfg``).  Returns a dict: degree [m] int32, core [m] int32 (the core numbers of that graph), max_core[, adj
+        [m, (m + 63) // 64] uint64 when "adj" is in ``want``: bit j & 63 of word j >> 6 of row i].  m at most CORR_GRAPH_MAX_M.
+        Reads neither the map nor the resident scan."""
+        return corr_graph_call(lambda *a: self._chk(self._L.flimo_corr_graph(self._h, *a)), src, dst, want, cfg)
 
     def desc_ref_set(self, desc):
         """flimo_desc_ref_set: ``desc`` [nr, dim] float32 becomes the context's resident reference set of ``desc_match`` (the map's

@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -146,6 +146,8 @@ def load_host():
                                            C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_corr_poses.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_lib.CorrCfg), C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_corr_graph.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_lib.CorrGraphCfg), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
     L.flimo_loc_desc_ref_set.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int]
     L.flimo_loc_desc_match.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_set_map_carving.restype = None
@@ -504,6 +506,13 @@ class Localizer:
         the resident scan.  The Localizer's own update does not use it."""
         return _lib.corr_call(lambda *a: self._corr_chk(self._L.flimo_loc_corr_poses(self._h, *a)), src, dst, tri, want, cfg)
 
+    def corr_graph(self, src, dst, want=(), **cfg):
+        """The consistency graph of point correspondences and its core numbers on the map's context (flimo_loc_corr_graph): the dict
+        of ``HipCtx.corr_graph``.  Waits for an insert, a crop or a carve still running behind the last sweep; reads neither the map
+        nor the resident scan.  The Localizer's own update does not use it."""
+        return _lib.corr_graph_call(lambda *a: self._outliers_chk(self._L.flimo_loc_corr_graph(self._h, *a), "flimo_loc_corr_graph"), src, dst,
+                                    want, cfg)
+
     def desc_ref_set(self, desc):
         """``desc`` [nr, dim] becomes the resident reference set of ``desc_match`` on the map's context (flimo_loc_desc_ref_set), as
         ``HipCtx.desc_ref_set``.  Waits for an insert, a crop or a carve still running; reads neither the map nor the scan."""
@@ -727,6 +736,31 @@ def corr_consensus(obj, src, dst, nh, seed=0, top=8, x26_like=None, **cfg):
                 tri=tri[best], survivors=int(ok.size))
 
 
+def corr_compatible_host(si, sj, di, dj, **cfg):
+    """Whether the correspondences (si, di) and (sj, dj) can both be true, on the host (flimo_corr_compatible_host: the function
+    the adjacency kernel of ``corr_graph`` calls); ``cfg``: the fields of ``_lib.corr_graph_cfg``.  It sees points, not indices."""
+    L = _lib.load_hip()
+    p = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (si, sj, di, dj)]
+    k = _lib.corr_graph_cfg(**cfg)
+    rc = L.flimo_corr_compatible_host(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, p[3].ctypes.data, C.byref(k))
+    if rc < 0:
+        raise FlimoError(f"flimo_corr_compatible_host failed ({rc})")
+    return bool(rc)
+
+
+def corr_prune(obj, src, dst, min_core=None, **cfg):
+    """The putative pairs worth sampling from: those in the innermost core of their consistency graph (``obj.corr_graph``: a
+    ``HipCtx`` or a ``Localizer``; ``cfg``: the fields of ``_lib.corr_graph_cfg``).  True pairs are compatible with each other,
+    false ones with few.  Returns a dict: keep -- the ascending int64 indices with core >= ``min_core`` (None: max_core) --, core,
+    degree [m] and max_core.  No pairs: nothing is called, the arrays are empty and max_core is 0."""
+    s = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
+    if s.shape[0] == 0:
+        return dict(keep=np.zeros(0, np.int64), core=np.zeros(0, np.int32), degree=np.zeros(0, np.int32), max_core=0)
+    out = obj.corr_graph(s, dst, want=(), **cfg)
+    level = out["max_core"] if min_core is None else int(min_core)
+    return dict(keep=np.nonzero(out["core"] >= level)[0].astype(np.int64), core=out["core"], degree=out["degree"], max_core=int(out["max_core"]))
+
+
 def desc_pairs(ref_obj, qry_obj, q_desc, r_desc, ratio=0.9, mutual=True):
     """Putative pairs (qi, rj) -- two int64 arrays, ascending in qi -- between the rows of ``q_desc`` and ``r_desc`` by nearest
     descriptor, Lowe's ratio test and a mutual check.  ``ref_obj`` holds ``r_desc`` as its resident reference set, ``qry_obj`` holds
@@ -756,7 +790,7 @@ def desc_pairs(ref_obj, qry_obj, q_desc, r_desc, ratio=0.9, mutual=True):
 
 
 def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=True, nh=4096, seed=0, top=8, corr=None, fitness_max_dist=1.0, align=None,
-               x26_like=None):
+               x26_like=None, prune=None):
     """A pose of a scan in a map from nothing but the two clouds -- plumbing over six calls, every parameter the caller's.
     ``map_obj`` (a ``HipCtx`` or a ``Localizer``) holds the map, and the scan (body frame) as its resident scan; ``scan_obj`` is a
     context whose MAP is that scan.  FPFH of both sides (``fpfh``: the fields of ``_lib.fpfh_cfg``; ``scan_fpfh``: the scan side's
@@ -765,7 +799,11 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
     ``_lib.corr_cfg``), ``scan_fitness`` of the returned rows on ``map_obj`` ranked by ``fitness_cost`` at ``fitness_max_dist``,
     ``scan_align`` (``align``: its keyword arguments) of the best row.  Returns the dict of each stage: pairs (qi, rj), fpfh (the
     scan's rows, the map's), src, dst,
-    consensus, fitness (inliers, sum_sqd, cost, x26: the rows in ranked order), align, and x26: the refined best row."""
+    consensus, fitness (inliers, sum_sqd, cost, x26: the rows in ranked order), align, and x26: the refined best row.
+    ``prune``: None, or a dict of ``corr_prune``'s keyword arguments -- the pairs then go through ``corr_prune`` on ``map_obj``, and
+    ``corr_consensus`` samples from ``src[keep]``, ``dst[keep]`` alone.  The returned pairs, src and dst stay the unpruned ones;
+    ``prune`` is added to the result, the dict ``corr_prune`` returned, and ``consensus["tri"]`` then indexes the KEPT pairs:
+    pair ``prune["keep"][t]`` of the unpruned ones."""
     fpfh, corr, align = dict(fpfh or {}), dict(corr or {}), dict(align or {})
     m_hip, s_hip = getattr(map_obj, "hip", map_obj), getattr(scan_obj, "hip", scan_obj)
     f_map = map_obj.map_fpfh(want=(), **fpfh)["fpfh"]
@@ -774,15 +812,20 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
     scan_obj.desc_ref_set(f_scan)
     qi, rj = desc_pairs(map_obj, scan_obj, f_scan, f_map, ratio=ratio, mutual=mutual)
     src, dst = s_hip.map_points()[qi], m_hip.map_points()[rj]
-    cons = corr_consensus(map_obj, src, dst, nh, seed=seed, top=top, x26_like=x26_like, **corr)
+    pruned = None if prune is None else corr_prune(map_obj, src, dst, **dict(prune))
+    s_in, d_in = (src, dst) if pruned is None else (src[pruned["keep"]], dst[pruned["keep"]])
+    cons = corr_consensus(map_obj, s_in, d_in, nh, seed=seed, top=top, x26_like=x26_like, **corr)
     inliers, sum_sqd = map_obj.scan_fitness(cons["x26"], max_dist=fitness_max_dist)
     cost = fitness_cost(inliers, sum_sqd, m_hip.scan_size(), fitness_max_dist)
     order = np.lexsort((np.arange(cost.size), cost))
     ranked = cons["x26"][order]
     aligned = scan_align(map_obj, ranked[:1], **align)
-    return dict(pairs=(qi, rj), fpfh=(f_scan, f_map), src=src, dst=dst, consensus=cons,
-                fitness=dict(inliers=inliers[order], sum_sqd=sum_sqd[order], cost=cost[order], x26=ranked), align=aligned,
-                x26=aligned["x26"][0] if ranked.shape[0] else None)
+    out = dict(pairs=(qi, rj), fpfh=(f_scan, f_map), src=src, dst=dst, consensus=cons,
+               fitness=dict(inliers=inliers[order], sum_sqd=sum_sqd[order], cost=cost[order], x26=ranked), align=aligned,
+               x26=aligned["x26"][0] if ranked.shape[0] else None)
+    if pruned is not None:
+        out["prune"] = pruned
+    return out
 
 
 ALIGN_RUNNING, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2      # scan_align's status per pose: ran every iteration / too few valid pairs / H not positive definite

@@ -3425,6 +3425,60 @@ extern "C" int flimo_set_corr_chunk(flimo_ctx* c, size_t n) {
   return FLIMO_OK;
 }
 
+// ---- the consistency graph of the correspondences and its core numbers (the step between the putative pairs and the samples) ------
+// kernels: flimo_corr.hip.  Both clouds go up, the bit matrix and the degrees are two launches, then the rounds of the h-index
+// iteration are enqueued CORR_GRAPH_ROUNDS at a time and the last one's flag is read: the iteration has ended when a round changed
+// nothing, however many that takes.  Everything comes back at the end; the scratch (the matrix, at most 128 MB) is the call's.
+static constexpr int CORR_GRAPH_ROUNDS = 8;      // rounds per read of the flags: one wait of the host per batch
+static bool corr_graph_cfg_ok(const flimo_corr_graph_cfg* k) {
+  return std::isfinite(k->tol) && k->tol >= 0.f && std::isfinite(k->min_edge) && k->min_edge >= 0.f && !std::isnan(k->edge_sim) &&
+         k->edge_sim >= 0.f && k->edge_sim <= 1.f;
+}
+extern "C" int flimo_corr_graph(flimo_ctx* c, const float* src_xyz, const float* dst_xyz, size_t m, const flimo_corr_graph_cfg* cfg, int32_t* degree,
+                                int32_t* core, int32_t* max_core, uint64_t* adj) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!cfg || !degree || !core || (m > 0 && (!src_xyz || !dst_xyz))) return fail(c, FLIMO_ERR_INVALID, "corr graph: null src / dst / cfg / degree / core");
+  if (!corr_graph_cfg_ok(cfg)) return fail(c, FLIMO_ERR_INVALID, "corr graph: tol and min_edge must be finite and >= 0, edge_sim in 0..1");
+  if (m > (size_t)FLIMO_CORR_GRAPH_MAX_M) return fail(c, FLIMO_ERR_TOO_LARGE, "corr graph: m must be at most %d", FLIMO_CORR_GRAPH_MAX_M);
+  if (m == 0) return FLIMO_OK;
+  ctx_enter(c);
+  const size_t W = (m + 63) / 64;
+  DevScratch d;
+  float* d_src = d.get<float>(3 * m);
+  float* d_dst = d.get<float>(3 * m);
+  uint64_t* d_adj = d.get<uint64_t>(m * W);
+  int32_t* d_degree = d.get<int32_t>(m);
+  int32_t* d_c[2] = {d.get<int32_t>(m), d.get<int32_t>(m)};
+  unsigned* d_flags = d.get<unsigned>(CORR_GRAPH_ROUNDS);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(d_src, src_xyz, 3 * m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_dst, dst_xyz, 3 * m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_corr_adjacency(c->stream, d_src, d_dst, (unsigned)m, cfg->tol, cfg->min_edge, cfg->edge_sim, d_adj, d_degree, d_c[0]));
+  int cur = 0;
+  for (;;) {
+    unsigned flags[CORR_GRAPH_ROUNDS];
+    HIPCHK(c, launch_corr_core_rounds(c->stream, d_adj, (unsigned)m, d_c, &cur, d_flags, CORR_GRAPH_ROUNDS));
+    HIPCHK(c, hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flags[CORR_GRAPH_ROUNDS - 1] == 0u) break;      // (a round that changed nothing: so did every round behind it)
+  }
+  std::vector<int32_t> h_core(m);      // (the outputs stay untouched until nothing can fail any more)
+  HIPCHK(c, hipMemcpyAsync(h_core.data(), d_c[cur], m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(degree, d_degree, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (adj) HIPCHK(c, hipMemcpyAsync(adj, d_adj, m * W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::copy(h_core.begin(), h_core.end(), core);
+  if (max_core) *max_core = *std::max_element(h_core.begin(), h_core.end());
+  return FLIMO_OK;
+}
+extern "C" int flimo_corr_compatible_host(const float si[3], const float sj[3], const float di[3], const float dj[3], const flimo_corr_graph_cfg* cfg) {
+  if (!si || !sj || !di || !dj || !cfg || !corr_graph_cfg_ok(cfg)) return FLIMO_ERR_INVALID;
+  const double a[3] = {(double)si[0], (double)si[1], (double)si[2]}, b[3] = {(double)sj[0], (double)sj[1], (double)sj[2]};
+  const double p[3] = {(double)di[0], (double)di[1], (double)di[2]}, q[3] = {(double)dj[0], (double)dj[1], (double)dj[2]};
+  return corr_compatible(a, b, p, q, (double)cfg->min_edge * (double)cfg->min_edge, (double)cfg->tol, (double)cfg->edge_sim * (double)cfg->edge_sim) ? 1 : 0;
+}
+
 // ---- nearest descriptors: the resident reference set and the match (the step between flimo_map_fpfh and flimo_corr_poses) ---------
 // kernels: flimo_desc.hip.  flimo_desc_ref_set uploads the rows once, and two launches leave their norms and their MFMA operand
 // layout on the device.  flimo_desc_match runs the queries in chunks of c->desc_chunk: per chunk the rows go up, three launches

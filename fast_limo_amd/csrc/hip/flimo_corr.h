@@ -2,6 +2,7 @@
 // The pose of one minimal sample of three point correspondences (flimo_corr_poses, include/flimo_c.h): the edge tests and the
 // closed-form TRIAD solve, float64 on the float32 inputs widened, only + - * / sqrt, in the association the header states.  Host AND
 // device: the solve kernel (flimo_corr.hip) and flimo_corr_pose_host run this one function, compiled without FMA contraction.
+// corr_compatible is the edge predicate of flimo_corr_graph, under the same rules.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "flimo_pose.h"
@@ -14,6 +15,20 @@ constexpr int CORR_OK = 0, CORR_DEGENERATE = 1, CORR_REJECTED = 2;      // FLIMO
 
 __host__ __device__ inline double corr_sq(double x, double y, double z) { return x * x + (y * y + z * z); }
 __host__ __device__ inline bool corr_finite(double v) { return v - v == 0.0; }      // (false for NaN and the infinities)
+
+// Two correspondences i and j can both be true (flimo_corr_graph, include/flimo_c.h): the edge i -> j has the same length in both
+// clouds to within tol, is not shorter than min_edge in either, and passes corr_solve's polygon test.  The points are the float32
+// inputs widened; min2 = (double)min_edge * (double)min_edge, s2 = (double)edge_sim * (double)edge_sim.  i == j is the caller's.
+// Host AND device: the adjacency kernel (flimo_corr.hip) and flimo_corr_compatible_host run this one function.
+__host__ __device__ inline bool corr_compatible(const double si[3], const double sj[3], const double di[3], const double dj[3], double min2,
+                                                double tol, double s2) {
+  const double es = corr_sq(sj[0] - si[0], sj[1] - si[1], sj[2] - si[2]);
+  const double ed = corr_sq(dj[0] - di[0], dj[1] - di[1], dj[2] - di[2]);
+  if (!(es >= min2) || !(ed >= min2)) return false;      // (a NaN coordinate fails here)
+  if (!(fabs(sqrt(es) - sqrt(ed)) <= tol)) return false;      // (two infinite edges: inf - inf fails)
+  const double lo = es < ed ? es : ed, hi = es < ed ? ed : es;
+  return lo >= s2 * hi;
+}
 
 // the orthonormal frame of a triangle: u1 along a -> b, u3 along u1 x (c - a), u2 = u3 x u1; U = {u1, u2, u3}
 __host__ __device__ inline void corr_frame(const double p[9], double U[9]) {

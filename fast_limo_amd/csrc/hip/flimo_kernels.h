@@ -348,6 +348,14 @@ hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4
 hipError_t launch_corr_poses(hipStream_t st, const float* src, const float* dst, unsigned m, const int32_t* tri, unsigned nh, float edge_sim,
                              float min_edge, float max_dist, int32_t* status, double* pose, float* rt, int32_t* surv, unsigned* nsurv,
                              int32_t* inliers, double* sum_sqd, float* pair_sqd);
+// ... and the consistency graph of the correspondences (flimo_corr_graph, flimo_c.h), 0 < m <= FLIMO_CORR_GRAPH_MAX_M.
+// launch_corr_adjacency: two launches -- the bit matrix adj [m][(m + 63) / 64], then the rows' popcounts to degree [m] and to c0 [m],
+// the start of the core iteration.  launch_corr_core_rounds enqueues `rounds` rounds of the h-index iteration between the two
+// buffers c[0] / c[1] (*cur names the one that holds the estimate, before and after); round r leaves flags[r] != 0 iff it changed
+// an estimate (flags [rounds] is cleared first).  The estimates are the core numbers once a round changed nothing.
+hipError_t launch_corr_adjacency(hipStream_t st, const float* src, const float* dst, unsigned m, float tol, float min_edge, float edge_sim,
+                                 uint64_t* adj, int32_t* degree, int32_t* c0);
+hipError_t launch_corr_core_rounds(hipStream_t st, const uint64_t* adj, unsigned m, int32_t* c[2], int* cur, unsigned* flags, int rounds);
 
 // flimo_desc.hip -- nearest descriptors (flimo_desc_match, flimo_c.h).  The resident reference set is two arrays: norm
 // [ceil(nr / 32) * 32] (launch_desc_norms with npad = that; NaN for an excluded row and for the padding) and rt

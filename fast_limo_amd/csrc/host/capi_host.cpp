@@ -360,6 +360,11 @@ int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xy
   if (!L) return FLIMO_ERR_INVALID;
   return L->map->corr_poses(src_xyz, dst_xyz, m, tri, nh, cfg, status, inliers, sum_sqd, pose, pair_sqd);
 }
+int flimo_loc_corr_graph(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const flimo_corr_graph_cfg* cfg, int32_t* degree,
+                         int32_t* core, int32_t* max_core, uint64_t* adj) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return L->map->corr_graph(src_xyz, dst_xyz, m, cfg, degree, core, max_core, adj);
+}
 int flimo_loc_desc_ref_set(flimo_loc* L, const float* desc, size_t nr, int dim) {
   if (!L) return FLIMO_ERR_INVALID;
   return L->map->desc_ref_set(desc, nr, dim);

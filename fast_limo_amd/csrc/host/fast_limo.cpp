@@ -597,6 +597,13 @@ int Mapper::corr_poses(const float* src_xyz, const float* dst_xyz, size_t m, con
   return flimo_corr_poses(ctx_, src_xyz, dst_xyz, m, tri, nh, cfg, status, inliers, sum_sqd, pose, pair_sqd);
 }
 
+int Mapper::corr_graph(const float* src_xyz, const float* dst_xyz, size_t m, const flimo_corr_graph_cfg* cfg, int32_t* degree, int32_t* core,
+                       int32_t* max_core, uint64_t* adj) {
+  sync();
+  if (!ctx_ && !attach(device_, cell_size_)) return FLIMO_ERR_NO_DEVICE;
+  return flimo_corr_graph(ctx_, src_xyz, dst_xyz, m, cfg, degree, core, max_core, adj);
+}
+
 // nearest descriptors: the resident reference set and the match (an insert, a crop or a carve on the worker thread ends first)
 int Mapper::desc_ref_set(const float* desc, size_t nr, int dim) {
   sync();

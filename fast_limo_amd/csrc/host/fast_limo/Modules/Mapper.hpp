@@ -120,6 +120,10 @@ class fast_limo::Mapper {
   // carve on the worker thread has ended.  Returns a FLIMO_* code.
   int corr_poses(const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh, const flimo_corr_cfg* cfg,
                  int32_t* status, int32_t* inliers, double* sum_sqd, double* pose = nullptr, float* pair_sqd = nullptr);
+  // The consistency graph of those correspondences and its core numbers (flimo_corr_graph, same arguments and results): which
+  // pairs can be true together.  Runs under the rules of corr_poses.  Returns a FLIMO_* code.
+  int corr_graph(const float* src_xyz, const float* dst_xyz, size_t m, const flimo_corr_graph_cfg* cfg, int32_t* degree, int32_t* core,
+                 int32_t* max_core = nullptr, uint64_t* adj = nullptr);
   // Nearest descriptors (flimo_desc_ref_set / flimo_desc_match, same arguments and results): the reference set stays resident in
   // this Mapper's context (created here if there is none yet); neither call reads the map or the resident scan, both run after an
   // insert, a crop or a carve on the worker thread has ended.  Return a FLIMO_* code.

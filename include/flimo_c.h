@@ -626,6 +626,51 @@ int flimo_corr_poses(flimo_ctx* ctx, const float* src_xyz /* [m][3] */, const fl
                      int32_t* status /* [nh] */, int32_t* inliers /* [nh] */, double* sum_sqd /* [nh] */,
                      double* pose /* [nh][7], may be NULL */, float* pair_sqd /* [nh][m], may be NULL */);
 int flimo_corr_pose_host(const float src3[9], const float dst3[9], const flimo_corr_cfg* cfg, double pose7[7], float rt12[12]);
+/* ---- the consistency graph of the correspondences and its core numbers: the step between the putative pairs and the samples of
+ *      flimo_corr_poses (what the reference's relocation branch gets from ROBIN's pruning of the compatibility graph).  A rigid
+ *      motion preserves distances: correspondences i and j can both be true only if the edge from i to j is as long in src as in
+ *      dst.  True pairs are therefore compatible with each other -- a clique --, a false pair is compatible with few others, and the
+ *      core numbers of the graph tell the two apart.  tests/corr_graph_common.py restates everything below in numpy; every output
+ *      is an integer or a bit and is compared exactly. ----
+ * Vertices are the correspondences (src[i], dst[i]), both clouds packed xyz, [m][3].  Everything is float64 on the float32 inputs
+ * widened, nothing contracted, in exactly the written association; sq(v) as for flimo_corr_poses.  For i != j, with
+ * e_s = sq(s_j - s_i) and e_d = sq(d_j - d_i), {i, j} is an EDGE iff all three hold:
+ *  1. e_s >= min2 and e_d >= min2, min2 = (double)min_edge * (double)min_edge;
+ *  2. fabs(sqrt(e_s) - sqrt(e_d)) <= (double)tol;
+ *  3. fmin(e_s, e_d) >= s2 * fmax(e_s, e_d), s2 = (double)edge_sim * (double)edge_sim (the polygon test of flimo_corr_poses on this
+ *     edge; edge_sim == 0 rejects nothing).
+ * Consequences: a NaN coordinate fails test 1, so its vertex is isolated (an infinite one fails test 1 or 2).  i == j is never an
+ * edge.  The predicate is symmetric bit for bit: (a - b)^2 and (b - a)^2 are the same double.  Several scan points paired with ONE
+ * map point have e_d = 0: with min_edge > 0 they are never compatible with each other -- the many-to-one case a ratio test leaves
+ * behind.
+ * Outputs, host memory:
+ *  - adj [m][(m + 63) / 64] (may be NULL): bit j & 63 of word j >> 6 of row i is 1 iff {i, j} is an edge; the padding bits beyond m
+ *    are 0.
+ *  - degree [m]: the number of edges at i.
+ *  - core [m]: the core number of i -- the largest c such that i lies in a set of vertices each of which has at least c neighbours
+ *    inside the set.  It is unique: how it is computed cannot show in the result.
+ *  - max_core (may be NULL): the largest core.
+ * m == 0 returns FLIMO_OK and touches nothing (a max_core of 0 is the caller's to assume).  FLIMO_ERR_INVALID: a NULL ctx / cfg /
+ * degree / core, NULL src or dst (m > 0), a cfg field that is NaN or negative, edge_sim > 1, an infinite tol or min_edge.
+ * FLIMO_ERR_TOO_LARGE: m > FLIMO_CORR_GRAPH_MAX_M (the bit matrix is m * ((m + 63) / 64) * 8 B of device memory: 128 MB at the
+ * limit; it is the call's, freed when it returns).  The outputs are untouched on an error.  The map and the resident scan are neither
+ * read nor changed; an empty context will do.  Calling rules as flimo_corr_poses.  The core numbers are iterated on the device until
+ * a round changes nothing: the number of rounds depends on the graph (about m / 2 for a chain, tens for a clique among noise) and is
+ * not capped.
+ * flimo_corr_compatible_host: the three tests for ONE pair of correspondences on the host, by the same host / device function the
+ * adjacency kernel calls: 1 / 0, or FLIMO_ERR_INVALID for a NULL pointer or a cfg the call above rejects.  It sees points, not
+ * indices: that i == j is no edge is the call's rule, not this function's. */
+typedef struct flimo_corr_graph_cfg {
+  float tol;        /* >= 0 [m]: two pairs are compatible when their two edge lengths differ by at most this */
+  float min_edge;   /* >= 0 [m]: shorter edges (in either cloud) are never compatible */
+  float edge_sim;   /* 0 .. 1: the polygon test of flimo_corr_poses on this edge, 0 = none */
+} flimo_corr_graph_cfg;
+#define FLIMO_CORR_GRAPH_MAX_M 32768
+int flimo_corr_graph(flimo_ctx* ctx, const float* src_xyz /* [m][3] */, const float* dst_xyz /* [m][3] */, size_t m,
+                     const flimo_corr_graph_cfg* cfg, int32_t* degree /* [m] */, int32_t* core /* [m] */,
+                     int32_t* max_core /* may be NULL */, uint64_t* adj /* [m][(m + 63) / 64], may be NULL */);
+int flimo_corr_compatible_host(const float si[3], const float sj[3], const float di[3], const float dj[3],
+                               const flimo_corr_graph_cfg* cfg);
 /* ---- nearest descriptors: which row of one descriptor array belongs to which row of another -- the step between flimo_map_fpfh
  *      (33-float rows) and flimo_corr_poses (matched pairs); pcl::search over FPFH space, brute force and exact, for all query
  *      rows at once.  tests/desc_common.py restates everything below in numpy; the tests compare every bit. ----

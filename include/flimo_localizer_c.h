@@ -135,6 +135,10 @@ int    flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh
  * nor the resident scan is read; a Localizer that has no context yet creates it.  The Localizer's own update does not use it. */
 int    flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
                             const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd);
+/* The consistency graph of correspondences and its core numbers: flimo_corr_graph (include/flimo_c.h: same arguments, same results,
+ * same error codes) on the map's context, under the rules of flimo_loc_corr_poses.  The Localizer's own update does not use it. */
+int    flimo_loc_corr_graph(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const flimo_corr_graph_cfg* cfg,
+                            int32_t* degree, int32_t* core, int32_t* max_core, uint64_t* adj);
 /* Nearest descriptors: flimo_desc_ref_set / flimo_desc_match (include/flimo_c.h: same arguments, same results, same error codes) on
  * the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  The reference set stays
  * resident there (flimo_desc_ref_size(flimo_loc_ctx(L)) tells its size); neither the map nor the resident scan is read; a Localizer
