@@ -264,6 +264,7 @@ HIP_SYMBOLS = [
     "flimo_set_timing", "flimo_set_timing_stride", "flimo_set_timing_deferred", "flimo_pass_count", "flimo_fused_pass_count", "flimo_tie_stats", "flimo_map_index_bytes", "flimo_map_index_layout", "flimo_fine_stats", "flimo_map_grid_selfcheck", "flimo_set_debug_records", "flimo_last_kernel_ms",
     "flimo_last_candidates_per_query", "flimo_last_widen_count", "flimo_last_stragglers", "flimo_stragglers_by_pass", "flimo_timing_totals", "flimo_timing_split", "flimo_set_path_switches", "flimo_set_wait_timeout_ms", "flimo_insert_rule_replay", "flimo_plane_fit5_host", "flimo_plane_eval5_host", "flimo_calculate_H_host",
     "flimo_update_chain", "flimo_chain_stats", "flimo_set_update_mode", "flimo_update_mode", "flimo_scan_adopt", "flimo_set_pass_pipeline", "flimo_pass_pipeline_end", "flimo_pass_pipeline_last", "flimo_pass_pipeline_stats", "flimo_device_large_bar",
+    "flimo_ieskf_op_shape", "flimo_ieskf_eval", "flimo_ieskf_eval_host", "flimo_ieskf_run_fixed",
 ]
 
 _hip = None
@@ -449,6 +450,11 @@ def load_hip():
     L.flimo_stragglers_by_pass.argtypes = [vp, C.POINTER(C.c_int)]
     L.flimo_last_candidates_per_query.restype = C.c_double
     L.flimo_last_candidates_per_query.argtypes = [vp]
+    L.flimo_ieskf_op_shape.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.flimo_ieskf_eval.argtypes = [vp, C.c_int, f64p, C.c_size_t, f64p]
+    L.flimo_ieskf_eval_host.argtypes = [C.c_int, f64p, C.c_size_t, f64p, C.c_void_p]
+    L.flimo_ieskf_run_fixed.argtypes = [vp, f64p, f64p, f64p, C.c_double, C.c_double, C.c_int, C.c_int, f64p, f64p, C.c_void_p, f64p, f64p,
+                                        C.POINTER(C.c_int)]
     for name in HIP_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("flimo_ctx_create",):
@@ -1001,6 +1007,40 @@ class HipCtx:
         self._chk(self._L.flimo_chain_stats(self._h, o, int(reset)))
         return dict(algebra_ms=o[0], algebra_n=int(o[1]), chains=int(o[2]), handed_back=int(o[3]), declined=int(o[4]))
 
+    def ieskf_eval(self, op, items):
+        """The device filter's helper ``op`` (IK_* below; include/flimo_dev.h: flimo_ieskf_eval) on a batch: items [n, n_in] ->
+        [n, n_out], on the GPU."""
+        a, no = ik_items(op, items)
+        out = np.zeros((a.shape[0], no))
+        if a.shape[0]:
+            self._chk(self._L.flimo_ieskf_eval(self._h, int(op), a.reshape(-1), a.shape[0], out.reshape(-1)))
+        return out
+
+    def ieskf_run_fixed(self, x26, P, limits, partials, extras=None, tag_ok=None, R=0.001, D=5.0, max_iter=3):
+        """The whole device algebra on caller-given sums (flimo_ieskf_run_fixed): ``partials`` [n_sets, 8, 91], ``extras``
+        [n_sets, 2] (stragglers, ties; zeros when None), ``tag_ok`` [n_sets] or None.  Returns (iterations, final): per iteration
+        run a dict pre_dxn, pre_AG, HTH, HTh, dx, x_after (None when it handed back), pose (66 float32), prev_RT, status, it, t,
+        passes, went_on; final: status, reason, passes, it, t, x, passinfo [12, 3], sums [91]."""
+        x, Pm, lim, part = ik_fixed_args(x26, P, limits, partials)
+        ns = part.shape[0]
+        ex = np.zeros((ns, 2)) if extras is None else np.ascontiguousarray(extras, dtype=np.float64).reshape(ns, 2)
+        tg = None if tag_ok is None else np.ascontiguousarray(tag_ok, dtype=np.int32).reshape(ns)
+        it_out = np.zeros((int(max_iter) + 1, IK_ITER_N))
+        fin = np.zeros(IK_FINAL_N)
+        n = C.c_int(0)
+        self._chk(self._L.flimo_ieskf_run_fixed(self._h, x, Pm, lim, float(R), float(D), int(max_iter), ns, part.reshape(-1), ex.reshape(-1),
+                                                None if tg is None else tg.ctypes.data, it_out.reshape(-1), fin, C.byref(n)))
+        its = []
+        for r in it_out[:n.value]:
+            on = bool(r[590])
+            its.append(dict(pre_dxn=r[0:23].copy(), pre_AG=r[23:299].copy(), HTH=r[299:443].reshape(12, 12).copy() if on else None,
+                            HTh=r[443:455].copy() if on else None, dx=r[455:478].copy() if on else None,
+                            x_after=r[478:504].copy() if on else None, pose=r[504:570].astype(np.float32), prev_RT=r[570:586].astype(np.float32),
+                            status=int(r[586]), it=int(r[587]), t=int(r[588]), passes=int(r[589]), went_on=on))
+        final = dict(status=int(fin[0]), reason=int(fin[1]), passes=int(fin[2]), it=int(fin[3]), t=int(fin[4]), x=fin[5:31].copy(),
+                     passinfo=fin[31:67].reshape(12, 3).copy(), sums=fin[67:158].copy())
+        return its, final
+
     def last_widen_count(self) -> int:
         return int(self._L.flimo_last_widen_count(self._h))
 
@@ -1017,6 +1057,40 @@ class HipCtx:
 
     def last_candidates_per_query(self) -> float:
         return float(self._L.flimo_last_candidates_per_query(self._h))
+
+
+# flimo_ieskf_eval's ops (include/flimo_dev.h: FLIMO_IK_*) and the record sizes of flimo_ieskf_run_fixed
+(IK_SO3_LOG, IK_A_T, IK_EXP_QUAT, IK_COS_SINC_SQRT, IK_S2_BX, IK_S2_BOXMINUS, IK_S2_J, IK_GJ12_INVERSE, IK_GJ12_SOLVE, IK_PRE) = range(10)
+IK_ITER_N, IK_FINAL_N, IK_HLOG_N = 591, 158, 207
+
+
+def ik_op_shape(op):
+    ni, no = C.c_int(0), C.c_int(0)
+    if load_hip().flimo_ieskf_op_shape(int(op), C.byref(ni), C.byref(no)) != 0:
+        raise FlimoError(f"flimo_ieskf_op_shape({op}): unknown op")
+    return ni.value, no.value
+
+
+def ik_items(op, items):
+    ni, no = ik_op_shape(op)
+    return np.ascontiguousarray(items, dtype=np.float64).reshape(-1, ni), no
+
+
+def ik_fixed_args(x26, P, limits, partials):
+    return (np.ascontiguousarray(x26, dtype=np.float64).reshape(26), np.ascontiguousarray(P, dtype=np.float64).reshape(529),
+            np.ascontiguousarray(limits, dtype=np.float64).reshape(23), np.ascontiguousarray(partials, dtype=np.float64).reshape(-1, 8, 91))
+
+
+def ieskf_eval_host(op, items):
+    """The host twin of ``HipCtx.ieskf_eval`` (flimo_ieskf_eval_host; no GPU): returns (out [n, n_out], branch [n] int32)."""
+    a, no = ik_items(op, items)
+    out = np.zeros((a.shape[0], no))
+    br = np.zeros(max(a.shape[0], 1), np.int32)
+    if a.shape[0]:
+        rc = load_hip().flimo_ieskf_eval_host(int(op), a.reshape(-1), a.shape[0], out.reshape(-1), br.ctypes.data)
+        if rc != 0:
+            raise FlimoError(f"flimo_ieskf_eval_host({op}) failed ({rc})")
+    return out, br[:a.shape[0]]
 
 
 def device_large_bar(device: int = 0) -> bool:

@@ -47,6 +47,7 @@ HOST_SYMBOLS = [
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
     "flimo_eskf_update_fixed", "flimo_eskf_predict", "flimo_host_eigen_solver6", "flimo_host_plane", "flimo_host_state_update", "flimo_host_time_order",
+    "flimo_ieskf_gj12_host", "flimo_ieskf_run_fixed_host",
 ]
 
 
@@ -912,6 +913,41 @@ def eskf_update_fixed(x26, P, H, h, max_iters=3, limits=None, R=0.001, D=5.0):
     L.flimo_eskf_update_fixed(x, Pm, H.reshape(-1) if H.size else np.zeros(1), h if h.size else np.zeros(1), H.shape[0],
                               max_iters, lim, R, D, C.byref(n))
     return x, Pm.reshape(23, 23), n.value
+
+
+def ieskf_gj12_host(op, items):
+    """The host filter's own elimination (flimo_host::inverse_gj / solve_gj, n = 12) on a batch: ``op`` _lib.IK_GJ12_INVERSE
+    (items [n, 144] -> [n, 145]) or _lib.IK_GJ12_SOLVE ([n, 156] -> [n, 13]); the last column is ``ok``."""
+    L = load_host()
+    L.flimo_ieskf_gj12_host.argtypes = [C.c_int, f64p, C.c_size_t, f64p]
+    a, no = _lib.ik_items(op, items)
+    out = np.zeros((a.shape[0], no))
+    if a.shape[0]:
+        rc = L.flimo_ieskf_gj12_host(int(op), a.reshape(-1), a.shape[0], out.reshape(-1))
+        if rc != 0:
+            raise FlimoError(f"flimo_ieskf_gj12_host({op}) failed ({rc})")
+    return out
+
+
+def ieskf_run_fixed_host(x26, P, limits, partials, R=0.001, D=5.0, max_iter=3):
+    """The host twin of ``HipCtx.ieskf_run_fixed`` (flimo_ieskf_run_fixed_host): the host filter on the same per-iteration sums.
+    Returns a dict: log (per completed pass a dict M, HTH, HTh, dx, x_after, t: the filter's own count so far), x, P, it (the iteration the loop ended in), t,
+    passes."""
+    L = load_host()
+    L.flimo_ieskf_run_fixed_host.argtypes = [f64p, f64p, f64p, C.c_double, C.c_double, C.c_int, C.c_int, f64p, f64p, C.POINTER(C.c_int),
+                                             f64p, f64p, C.POINTER(C.c_int)]
+    x, Pm, lim, part = _lib.ik_fixed_args(x26, P, limits, partials)
+    lg = np.zeros((int(max_iter) + 1, _lib.IK_HLOG_N))
+    n = C.c_int(0)
+    xo, Po = np.zeros(26), np.zeros(529)
+    loop = (C.c_int * 3)()
+    rc = L.flimo_ieskf_run_fixed_host(x, Pm, lim, float(R), float(D), int(max_iter), part.shape[0], part.reshape(-1), lg.reshape(-1),
+                                      C.byref(n), xo, Po, loop)
+    if rc != 0:
+        raise FlimoError(f"flimo_ieskf_run_fixed_host failed ({rc})")
+    log = [dict(M=int(r[0]), HTH=r[1:145].reshape(12, 12).copy(), HTh=r[145:157].copy(), dx=r[157:180].copy(), x_after=r[180:206].copy(), t=int(r[206]))
+           for r in lg[:n.value]]
+    return dict(log=log, x=xo, P=Po.reshape(23, 23), it=int(loop[0]), t=int(loop[1]), passes=int(loop[2]))
 
 
 def eigen_solver6(A):

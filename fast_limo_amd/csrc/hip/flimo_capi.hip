@@ -2978,6 +2978,110 @@ extern "C" int flimo_chain_stats(flimo_ctx* c, double out[5], int reset) {
   return FLIMO_OK;
 }
 
+// ---- developer entries: the filter's device algebra on its own (flimo_dev.h) ----
+extern "C" int flimo_ieskf_op_shape(int op, int* n_in, int* n_out) { return ieskf_op_shape(op, n_in, n_out) ? FLIMO_OK : FLIMO_ERR_INVALID; }
+extern "C" int flimo_ieskf_eval_host(int op, const double* in, size_t n, double* out, int* branch) {
+  if (!in || !out) return FLIMO_ERR_INVALID;
+  return ieskf_eval_host(op, in, n, out, branch) ? FLIMO_OK : FLIMO_ERR_INVALID;
+}
+extern "C" int flimo_ieskf_eval(flimo_ctx* c, int op, const double* in, size_t n, double* out) {
+  int ni = 0, no = 0;
+  if (!c || !in || !out || !ieskf_op_shape(op, &ni, &no) || n > ((size_t)1 << 20)) return FLIMO_ERR_INVALID;
+  if (n == 0) return FLIMO_OK;
+  { const int rca = check_abandoned(c); if (rca) return rca; }
+  ctx_enter(c);
+  double *d_in = nullptr, *d_out = nullptr;
+  HIPCHK(c, hipMalloc((void**)&d_in, n * ni * sizeof(double)));
+  hipError_t e = hipMalloc((void**)&d_out, n * no * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, n * ni * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, n * no * sizeof(double), c->stream);
+  if (e == hipSuccess) { launch_ieskf_eval(c->stream, op, d_in, (int)n, d_out); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * no * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d_in); (void)hipFree(d_out);
+  if (e != hipSuccess) return fail(c, FLIMO_ERR_HIP, "flimo_ieskf_eval failed: %s", hipGetErrorString(e));
+  return FLIMO_OK;
+}
+
+// The whole device algebra on caller-given sums: the extra launch and the algebra launch per iteration (what tools/ieskf_bench.hip
+// queues), the stream drained after each so that what the iteration left can be read.
+extern "C" int flimo_ieskf_run_fixed(flimo_ctx* c, const double x26[26], const double P[529], const double limits[23], double R, double D,
+                                     int max_iter, int n_sets, const double* partials, const double* extras, const int* tag_ok,
+                                     double* iter_out, double* final_out, int* n_iter_out) {
+  if (!c || !x26 || !P || !limits || !partials || !extras || !iter_out || !final_out || !n_iter_out) return FLIMO_ERR_INVALID;
+  if (max_iter < 0 || max_iter + 1 > CH_MAX_PASSES || n_sets < 1) return FLIMO_ERR_INVALID;
+  { const int rca = check_abandoned(c); if (rca) return rca; }
+  ctx_enter(c);
+  const int n_pass = max_iter + 1;
+  *n_iter_out = 0;
+  for (size_t k = 0; k < (size_t)n_pass * FLIMO_IK_ITER_N; k++) iter_out[k] = 0.0;
+  for (int k = 0; k < FLIMO_IK_FINAL_N; k++) final_out[k] = 0.0;
+  PoseMats P0;
+  pose_from_x26(x26, P0);
+  ChainPrior& pr = *c->h_chain_prior;
+  memcpy(pr.x, x26, sizeof(pr.x));
+  memcpy(pr.P, P, sizeof(pr.P));
+  memcpy(pr.limit, limits, sizeof(pr.limit));
+  pr.R = R; pr.D = D; pr.max_iter = max_iter; pr.pad = 0;
+  ik_pre_serial(x26, x26, P, R, pr.dxn, pr.AG, pr.AG + 144);
+  __atomic_thread_fence(__ATOMIC_RELEASE);
+  const unsigned long long tag = ++c->chain_tag;
+  ChainCtl ctl{};
+  ctl.S = c->d_chain;
+  ctl.gran = reinterpret_cast<double2*>(c->d_chain_gran);
+  ctl.res = reinterpret_cast<double2*>(c->d_chain_res);
+  ctl.log = reinterpret_cast<double2*>(c->d_chain_log);
+  ctl.tag = tag;
+  HIPCHK(c, hipMemsetAsync(c->d_chain, 0, chain_state_size(), c->stream));
+  std::vector<double> g((size_t)FIT_GROUPS * FIT_LIVE_PAD * 2);
+  std::vector<unsigned char> sbuf(chain_state_size());
+  const volatile unsigned long long* rt = reinterpret_cast<const volatile unsigned long long*>(c->h_chain_res);
+  for (int i = 0; i < n_pass; i++) {
+    const int set = std::min(i, n_sets - 1);
+    const unsigned long long seq = 1000ull + (unsigned long long)i;
+    const unsigned long long gtag = (tag_ok && !tag_ok[set]) ? seq + 500ull : seq;
+    double tagd;
+    memcpy(&tagd, &gtag, 8);
+    for (size_t k = 0; k < g.size(); k += 2) { g[k] = 0.0; g[k + 1] = tagd; }
+    for (int q = 0; q < FIT_GROUPS; q++)
+      for (int k = 0; k < FIT_LIVE; k++) g[2 * ((size_t)q * FIT_LIVE_PAD + k)] = partials[((size_t)set * FIT_GROUPS + q) * FIT_LIVE + k];
+    g[2 * FIT_LIVE] = extras[2 * set]; g[2 * (FIT_LIVE + 1)] = extras[2 * set + 1];
+    HIPCHK(c, hipMemcpyAsync(c->d_chain_gran, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ctl.prior = i == 0 ? c->d_chain_prior : nullptr;
+    launch_ieskf_extra(c->stream, ctl);
+    // what the extra launch left is overwritten by nobody before the next one: read behind the algebra launch
+    launch_ieskf(c->stream, ctl, seq, i == 0 ? P0.RT : nullptr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(sbuf.data(), c->d_chain, sbuf.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const ChainState& S = *reinterpret_cast<const ChainState*>(sbuf.data());
+    double* o = iter_out + (size_t)i * FLIMO_IK_ITER_N;
+    int k = 0;
+    for (int e = 0; e < 23; e++) o[k++] = S.pre_dxn[e];
+    for (int e = 0; e < 276; e++) o[k++] = S.pre_AG[e];
+    const bool went_on = S.head.status == 0 && S.passes == i + 1;
+    if (went_on) {
+      const volatile unsigned long long* lt = reinterpret_cast<const volatile unsigned long long*>(c->h_chain_log) + (size_t)i * CH_LOGN * 2;
+      const double* lv = c->h_chain_log + (size_t)i * CH_LOGN * 2;
+      for (int e = 0; e < CH_LOGN; e++) if (lt[2 * e + 1] != tag) return fail(c, FLIMO_ERR_HIP, "the algebra's log did not arrive");
+      for (int e = 0; e < CH_LOGN; e++) o[k + e] = lv[2 * e];
+    }
+    k += CH_LOGN;
+    const float* pm = reinterpret_cast<const float*>(&S.head.pose);
+    for (int e = 0; e < (int)(sizeof(PoseMats) / 4); e++) o[k++] = (double)pm[e];
+    for (int e = 0; e < 16; e++) o[k++] = (double)S.head.prev_RT[e];
+    o[k++] = (double)S.head.status; o[k++] = (double)S.it; o[k++] = (double)S.t; o[k++] = (double)S.passes; o[k++] = went_on ? 1.0 : 0.0;
+    static_assert(23 + 276 + CH_LOGN + sizeof(PoseMats) / 4 + 16 + 5 == FLIMO_IK_ITER_N, "flimo_dev.h: the per-iteration record");
+    *n_iter_out = i + 1;
+    if (S.head.status != 0) break;
+  }
+  for (int k = 0; k < CH_RES; k++) if (rt[2 * k + 1] != tag) return fail(c, FLIMO_ERR_HIP, "the algebra ended without handing back (granule %d)", k);
+  static_assert(CH_RES == FLIMO_IK_FINAL_N, "flimo_dev.h: the final record");
+  for (int k = 0; k < CH_RES; k++) final_out[k] = c->h_chain_res[2 * k];
+  return FLIMO_OK;
+}
+
 extern "C" int flimo_update_chain(flimo_ctx* c, const flimo_match_cfg* cfg, flimo_chain_io* io) {
   if (!c || !cfg || !io) return FLIMO_ERR_INVALID;
   io->status = FLIMO_CHAIN_DECLINED; io->reason = 0; io->passes = 0; io->it_next = -1; io->t = 0; io->meas_valid = 0; io->meas_M = 0;

@@ -105,6 +105,11 @@ size_t chain_state_size();
 void launch_ieskf(hipStream_t st, const ChainCtl& ch, unsigned long long seq, const float* used_RT_host_or_null,
                   hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 void launch_ieskf_extra(hipStream_t st, const ChainCtl& ch, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);   // developer tool
+// developer entries (include/flimo_dev.h: flimo_ieskf_eval, flimo_ieskf_eval_host): the helpers of flimo_ieskf.h in batches.
+// d_in / d_out: device memory, n items of the op's shape (ieskf_op_shape).
+bool ieskf_op_shape(int op, int* n_in, int* n_out);
+void launch_ieskf_eval(hipStream_t st, int op, const double* d_in, int n, double* d_out);
+bool ieskf_eval_host(int op, const double* in, size_t n, double* out, int* branch);
 // PipeHead's epoch of the pass numbered seq: never zero (zero means "do not wait"), top bit clear (set: an end code)
 __host__ __device__ inline unsigned int ch_epoch_of(unsigned long long seq) { return (unsigned int)(seq & 0x3fffffffull) | 0x40000000u; }
 constexpr int CH_POLL_MS = 50;           // a pass's workgroups give up waiting for their constants after this long (status FAILED)

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <memory>
 #include "../../../include/flimo_localizer_c.h"
+#include "../../../include/flimo_dev.h"
 #include "fast_limo/Modules/Localizer.hpp"
 #include "fast_limo/Objects/Plane.hpp"
 #include "flimo_ikfom.hpp"
@@ -504,6 +505,71 @@ int flimo_eskf_predict(double x26[26], double P[529], double dt, const double Qd
   f.predict(dt, Q, in);
   f.get_x().to_flat(x26);
   std::memcpy(P, &f.get_P().a[0][0], sizeof(double) * 529);
+  return FLIMO_OK;
+}
+
+// ---- host twins of the device filter's developer entries (flimo_dev.h) ----
+int flimo_ieskf_gj12_host(int op, const double* in, size_t n, double* out) {
+  if (!in || !out || (op != FLIMO_IK_GJ12_INVERSE && op != FLIMO_IK_GJ12_SOLVE)) return FLIMO_ERR_INVALID;
+  const bool solve = op == FLIMO_IK_GJ12_SOLVE;
+  const int ni = solve ? 156 : 144, nr = solve ? 12 : 144;
+  for (size_t i = 0; i < n; i++) {
+    const double* a = in + i * ni;
+    double* o = out + i * (nr + 1);
+    for (int e = 0; e < nr; e++) o[e] = 0.0;
+    double r[144];
+    const bool ok = solve ? flimo_host::solve_gj(12, a, a + 144, r) : flimo_host::inverse_gj(12, a, r);
+    if (ok) for (int e = 0; e < nr; e++) o[e] = r[e];
+    o[nr] = ok ? 1.0 : 0.0;
+  }
+  return FLIMO_OK;
+}
+
+int flimo_ieskf_run_fixed_host(const double x26[26], const double P[529], const double limits[23], double R, double D, int max_iter,
+                               int n_sets, const double* partials, double* log_out, int* n_log, double x_out[26], double P_out[529],
+                               int loop[3]) {
+  if (!x26 || !P || !limits || !partials || !log_out || !n_log || !x_out || !P_out || !loop || max_iter < 0 || n_sets < 1)
+    return FLIMO_ERR_INVALID;
+  flimo_host::Esekf f;
+  flimo_host::StateIkfom s;
+  s.from_flat(x26);
+  f.change_x(s);
+  flimo_host::Esekf::Cov C;
+  std::memcpy(&C.a[0][0], P, sizeof(double) * 529);
+  f.change_P(C);
+  f.init(max_iter, limits);
+  f.keep_log = true;
+  int pass = 0, M_now = 0;
+  f.h_reduced = [&](const flimo_host::StateIkfom&, flimo_host::ReducedMeas& out) {
+    const double* g = partials + (size_t)(pass < n_sets ? pass : n_sets - 1) * 8 * 91;
+    double sum[91];
+    for (int k = 0; k < 91; k++) {
+      double r = g[k];
+      for (int q = 1; q < 8; q++) r += g[q * 91 + k];          // slot order, as the device adds them
+      sum[k] = r;
+    }
+    int k = 0;
+    for (int i = 0; i < 12; i++) for (int j = i; j < 12; j++) { out.HTH[i * 12 + j] = sum[k]; out.HTH[j * 12 + i] = sum[k]; k++; }
+    for (int i = 0; i < 12; i++) out.HTh[i] = sum[k++];
+    out.M = M_now = (int)std::llrint(sum[90]);
+    pass++;
+  };
+  f.h_dense = [&](flimo_host::DenseMeas& dm) { dm.H.assign((size_t)M_now * 12, 0.0); dm.h.assign((size_t)M_now, 0.0); };
+  f.update_iterated_dyn_share_modified(R, D);
+  f.get_x().to_flat(x_out);
+  std::memcpy(P_out, &f.get_P().a[0][0], sizeof(double) * 529);
+  *n_log = (int)f.log.size();
+  for (size_t p = 0; p < f.log.size() && p < (size_t)max_iter + 1; p++) {
+    const flimo_host::PassLog& L = f.log[p];
+    double* o = log_out + p * 207;
+    o[0] = (double)L.M;
+    for (int e = 0; e < 144; e++) o[1 + e] = L.HTH[e];
+    for (int e = 0; e < 12; e++) o[145 + e] = L.HTh[e];
+    for (int e = 0; e < 23; e++) o[157 + e] = L.dx[e];
+    for (int e = 0; e < 26; e++) o[180 + e] = L.x_after[e];
+    o[206] = (double)L.t;
+  }
+  loop[0] = (int)f.log.size() - 2; loop[1] = f.log.empty() ? 0 : f.log.back().t; loop[2] = (int)f.log.size();
   return FLIMO_OK;
 }
 

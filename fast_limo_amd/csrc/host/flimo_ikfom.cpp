@@ -1013,6 +1013,7 @@ void Esekf::update_iterated_dyn_share_modified(double R, double D) {
       for (int i = 0; i < 12; i++) { lg.HTh[i] = HTh[i]; for (int j = 0; j < 12; j++) lg.HTH[i * 12 + j] = HTH(i, j); }
       for (int i = 0; i < n; i++) lg.dx[i] = dx_[i];
       x_.to_flat(lg.x_after);
+      lg.t = t;
       log.push_back(lg);
     }
 

@@ -128,6 +128,7 @@ struct DenseMeas {        // only for the M < 23 branch
 struct PassLog {
   int M;
   double HTH[144], HTh[12], dx[kDof], x_after[26];
+  int t = 0;              // the loop's count of passes that met the limits, this one included (esekfom.hpp:1757); host loop only
 };
 
 // The whole update run by the measurement side in one go (the GPU library's flimo_update_chain): what comes back

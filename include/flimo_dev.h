@@ -129,6 +129,51 @@ int flimo_pass_pipeline_stats(const flimo_ctx* ctx, unsigned long long out[4]);
  * (hipDeviceAttributeIsLargeBar), whatever a context then made of it -- a context on such a device queues passes ahead */
 int flimo_device_large_bar(int device, int* large_bar);
 
+/* ---- the filter's device algebra on its own (csrc/hip/flimo_ieskf.h; tests/test_gpu_ieskf.py, tests/test_ieskf_host.py) ----
+ * Batch evaluation of its helpers: item i reads in[i * n_in ..] and writes out[i * n_out ..], all doubles, quaternions as x y z w.
+ *   op                       in (n_in)                                  out (n_out)
+ *   FLIMO_IK_SO3_LOG         q[4]                                (4)    log[3]                                    (3)
+ *   FLIMO_IK_A_T             v[3]                                (3)    A_matrix(v)^T, row-major                  (9)
+ *   FLIMO_IK_EXP_QUAT        v[3], scale                         (4)    q[4]                                      (4)
+ *   FLIMO_IK_COS_SINC_SQRT   x2                                  (1)    cos, sinc                                 (2)
+ *   FLIMO_IK_S2_BX           g[3]                                (3)    Bx 3 x 2                                  (6)
+ *   FLIMO_IK_S2_BOXMINUS     g[3], other[3]                      (6)    g boxminus other                          (2)
+ *   FLIMO_IK_S2_J            now[3], prop[3], delta[2]           (8)    Nx_yy(now) Mx(prop, delta), 2 x 2         (4)
+ *   FLIMO_IK_GJ12_INVERSE    T[144]                              (144)  T^-1 [144], ok                            (145)
+ *   FLIMO_IK_GJ12_SOLVE      T[144], v[12]                       (156)  u[12] with T u = v, ok                    (13)
+ *   FLIMO_IK_PRE             x[26], x_prop[26], P_prop[529], R   (582)  dx_new[23], A11^-1[144], G2[132]          (299)
+ * On the device the scalar helpers run one lane per item, the two Gauss-Jordan routines one wave per system, FLIMO_IK_PRE
+ * (ik_pre_block) one 256-thread workgroup per item.  ok = 0: a zero pivot; the other outputs of that item mean nothing. */
+enum {
+  FLIMO_IK_SO3_LOG = 0, FLIMO_IK_A_T = 1, FLIMO_IK_EXP_QUAT = 2, FLIMO_IK_COS_SINC_SQRT = 3, FLIMO_IK_S2_BX = 4,
+  FLIMO_IK_S2_BOXMINUS = 5, FLIMO_IK_S2_J = 6, FLIMO_IK_GJ12_INVERSE = 7, FLIMO_IK_GJ12_SOLVE = 8, FLIMO_IK_PRE = 9
+};
+int flimo_ieskf_op_shape(int op, int* n_in, int* n_out);
+int flimo_ieskf_eval(flimo_ctx* ctx, int op, const double* in, size_t n, double* out);
+/* The same source compiled for the host (GJ12_INVERSE: ik_inverse_gj12_serial, PRE: ik_pre_serial; GJ12_SOLVE has no twin in this
+ * library: see flimo_localizer_c.h).  branch (optional, [n]): which way item i went --
+ *   SO3_LOG, A_T: 1 = the norm is below MTK's tolerance;  EXP_QUAT, COS_SINC_SQRT: 1 = the Taylor series;  S2_BX: 1 = the chart at -L e_x;
+ *   S2_BOXMINUS: 0 general, 1 equal, 2 antipodal, + 4 when `other` is on the chart at -L e_x;
+ *   S2_J: bit 0 = |delta| below the tolerance, bit 1 / bit 2 = now / prop on the chart at -L e_x;  the others: 0. */
+int flimo_ieskf_eval_host(int op, const double* in, size_t n, double* out, int* branch);
+/* The whole device algebra on caller-given sums, on the context's stream: per iteration the launch of the measurement-independent
+ * half and the launch from the sums to the next state (the two one-workgroup launches tools/ieskf_bench.hip queues), the stream
+ * drained after each.  max_iter + 1 <= 12.  Iteration i reads set min(i, n_sets - 1):
+ *   partials [n_sets][8][91]  the 91 sums (upper triangle of H^T H row by row, H^T h, M) as eight groups' partial sums;
+ *   extras   [n_sets][2]      stragglers, ties;   tag_ok [n_sets] or NULL: 0 = the set's granules carry another pass's number.
+ * iter_out [max_iter + 1][FLIMO_IK_ITER_N], *n_iter = iterations run (the one that handed back included); record of an iteration:
+ *   [0] pre_dxn[23]  [23] pre_AG[276] as its first launch left them;  [299] the log entry HTH[144] HTh[12] dx[23] x_after[26] (zeros
+ *   when the iteration handed back);  [504] the head's PoseMats (66 floats)  [570] prev_RT[16]  [586] status  [587] it  [588] t
+ *   [589] passes  [590] 1 = the chain went on.
+ * final_out [FLIMO_IK_FINAL_N]: [0] status [1] reason [2] passes [3] it [4] t [5] x[26] [31] per pass M, stragglers, ties [67] the
+ * handed-back 91 sums. */
+#define FLIMO_IK_ITER_N 591
+#define FLIMO_IK_FINAL_N 158
+int flimo_ieskf_run_fixed(flimo_ctx* ctx, const double x26[26], const double P[529], const double limits[23], double R, double D,
+                          int max_iter, int n_sets, const double* partials, const double* extras, const int* tag_ok,
+                          double* iter_out, double* final_out, int* n_iter);
+/* (host twins, libfast_limo.so: flimo_ieskf_gj12_host and flimo_ieskf_run_fixed_host, include/flimo_localizer_c.h) */
+
 /* ---- host-side evaluation, no GPU (round 6: out of the boundary header): what the host C++ mirror's Plane / calculate_H objects and
  * the CPU tests call ----
  * Replays the map's insert rule (Octree::initialize / update, Objects/Octree.hpp:282-432) over a

@@ -218,6 +218,17 @@ int    flimo_eskf_update_fixed(double x26[26], double P[529], const double* H, c
                                const double limits[23], double R, double D, int* n_passes);
 int    flimo_eskf_predict(double x26[26], double P[529], double dt, const double Qdiag[12], const double acc[3],
                           const double gyro[3]);
+/* Host twins of the device filter's developer entries (include/flimo_dev.h) -- for unit tests.
+ * flimo_ieskf_gj12_host: the host filter's own elimination, flimo_host::inverse_gj / solve_gj with n = 12; op, in, out as
+ * flimo_ieskf_eval takes FLIMO_IK_GJ12_INVERSE (7) / FLIMO_IK_GJ12_SOLVE (8).
+ * flimo_ieskf_run_fixed_host: flimo_ieskf_run_fixed on flimo_host::Esekf, h_reduced returning the same sets, the eight partials
+ * added in slot order.  log_out [max_iter + 1][207]: per completed pass M, HTH[144], HTh[12], dx[23], x_after[26] and the filter's own
+ * count t of the passes that met `limits` so far, this one included (esekfom.hpp:1749-1757); *n_log passes;
+ * loop[3]: the iteration the loop ended in, t then, passes. */
+int    flimo_ieskf_gj12_host(int op, const double* in, size_t n, double* out);
+int    flimo_ieskf_run_fixed_host(const double x26[26], const double P[529], const double limits[23], double R, double D,
+                                  int max_iter, int n_sets, const double* partials, double* log_out, int* n_log, double x_out[26],
+                                  double P_out[529], int loop[3]);
 /* The filter's restatement of Eigen::EigenSolver<Matrix<double,6,6>> (IKFoM_toolkit/esekfom/esekfom.hpp:1736-1738, degeneracy
  * handling): A row-major; eigenvalues in the solver's order (real, imaginary part), real parts of the normalised eigenvectors as
  * the columns of V (row-major) -- for unit tests */
