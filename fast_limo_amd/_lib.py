@@ -132,6 +132,40 @@ def fpfh_call(call, n, want, cfg):
     return {name: a[:n] for name, a in arr.items()}
 
 
+class KeypointCfg(C.Structure):
+    """flimo_keypoint_cfg (include/flimo_c.h)."""
+    _fields_ = [("k", C.c_int), ("max_dist", C.c_float), ("min_pts", C.c_int), ("gamma21", C.c_float), ("gamma32", C.c_float),
+                ("nms_k", C.c_int), ("nms_max_dist", C.c_float)]
+
+
+def keypoint_cfg(k=32, max_dist=float("inf"), min_pts=5, gamma21=0.975, gamma32=0.975, nms_k=32, nms_max_dist=float("inf")) -> KeypointCfg:
+    """PCL's ISSKeypoint3D thresholds (0.975, 0.975, 5 neighbours) over neighbourhoods of 32 unless told otherwise: no gates."""
+    return KeypointCfg(int(k), float(max_dist), int(min_pts), float(gamma21), float(gamma32), int(nms_k), float(nms_max_dist))
+
+
+def keypoints_call(call, n, want, cfg):
+    """The output arrays of flimo_map_keypoints / flimo_loc_map_keypoints (``call`` takes: cfg, mask, saliency, cnt, count) as a dict
+    with "mask" (bool), "count", "index" (the ascending int64 indices of the ones, relative to the range) and the outputs named in
+    ``want`` (of "saliency", "cnt"); shared with ``api.Localizer``."""
+    unknown = set(want) - {"saliency", "cnt"}
+    if unknown:
+        raise ValueError(f"keypoints: unknown outputs {sorted(unknown)}")
+    k = keypoint_cfg(**cfg)
+    arr = {"mask": np.zeros(max(n, 1), np.uint8)}
+    if "saliency" in want:
+        arr["saliency"] = np.zeros(max(n, 1), np.float64)
+    if "cnt" in want:
+        arr["cnt"] = np.zeros(max(n, 1), np.int32)
+    count = C.c_size_t(0)
+    ptr = lambda name: arr[name].ctypes.data if name in arr else None
+    call(C.byref(k), ptr("mask"), ptr("saliency"), ptr("cnt"), C.byref(count))
+    out = {name: a[:n] for name, a in arr.items()}
+    out["mask"] = out["mask"].astype(bool)
+    out["count"] = int(count.value)
+    out["index"] = np.flatnonzero(out["mask"]).astype(np.int64)
+    return out
+
+
 class CorrCfg(C.Structure):
     """flimo_corr_cfg (include/flimo_c.h)."""
     _fields_ = [("edge_sim", C.c_float), ("min_edge", C.c_float), ("max_dist", C.c_float)]
@@ -256,7 +290,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_corr_graph", "flimo_corr_compatible_host", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -356,6 +390,8 @@ def load_hip():
     L.flimo_set_outlier_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_map_fpfh.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(FpfhCfg), C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_set_fpfh_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_map_keypoints.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(KeypointCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.flimo_set_keypoints_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
     L.flimo_map_last_time.argtypes = [vp]
@@ -591,6 +627,20 @@ class HipCtx:
     def set_fpfh_chunk(self, n):
         """Points per search launch of ``map_fpfh`` (flimo_set_fpfh_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_fpfh_chunk(self._h, int(n)))
+
+    def map_keypoints(self, first=0, n=None, want=("saliency", "cnt"), **cfg):
+        """ISS keypoints (pcl::ISSKeypoint3D with k-bounded neighbourhoods and broken ties) among the stored points first .. first +
+        n - 1 (``n`` None: up to the map's end) -- flimo_map_keypoints; ``cfg``: the fields of ``keypoint_cfg`` (k, max_dist, min_pts,
+        gamma21, gamma32, nms_k, nms_max_dist).  Returns a dict: ``mask`` [n] bool, ``count``, ``index`` (the ascending int64 indices of
+        the ones, relative to ``first``), and of ``want`` ``saliency`` [n] float64 (NaN: not salient), ``cnt`` [n] int32.  The
+        saliency is formed for the whole map whatever the range; changes nothing."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return keypoints_call(lambda *a: self._chk(self._L.flimo_map_keypoints(self._h, first, n, *a)), n, want, cfg)
+
+    def set_keypoints_chunk(self, n):
+        """Points per search launch of ``map_keypoints`` (flimo_set_keypoints_chunk; 0: the default of 2^20)."""
+        self._chk(self._L.flimo_set_keypoints_chunk(self._h, int(n)))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

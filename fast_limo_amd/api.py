@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -164,6 +164,8 @@ def load_host():
     L.flimo_loc_map_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.OutlierCfg), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(_lib.OutlierStats)]
     L.flimo_loc_map_fpfh.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.FpfhCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_map_keypoints.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.KeypointCfg), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_size_t)]
     L.flimo_loc_map_remove_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.OutlierCfg), C.POINTER(C.c_size_t),
                                                 C.POINTER(_lib.OutlierStats)]
     L.flimo_local_map_rule.restype = C.c_int
@@ -418,6 +420,14 @@ class Localizer:
         first = int(first)
         n = max(self.map_size() - first, 0) if n is None else int(n)
         return _lib.fpfh_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_fpfh(self._h, first, n, *a), "flimo_loc_map_fpfh"), n, want, cfg)
+
+    def map_keypoints(self, first=0, n=None, want=("saliency", "cnt"), **cfg):
+        """ISS keypoints of the map's stored points (flimo_loc_map_keypoints), as ``HipCtx.map_keypoints``.  Waits for an insert, a
+        crop or a carve still running; changes nothing.  The Localizer's own update does not use it."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return _lib.keypoints_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_keypoints(self._h, first, n, *a), "flimo_loc_map_keypoints"),
+                                   n, want, cfg)
 
     def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
         """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,
@@ -791,7 +801,7 @@ def desc_pairs(ref_obj, qry_obj, q_desc, r_desc, ratio=0.9, mutual=True):
 
 
 def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=True, nh=4096, seed=0, top=8, corr=None, fitness_max_dist=1.0, align=None,
-               x26_like=None, prune=None):
+               x26_like=None, prune=None, keypoints=None, scan_keypoints=None):
     """A pose of a scan in a map from nothing but the two clouds -- plumbing over six calls, every parameter the caller's.
     ``map_obj`` (a ``HipCtx`` or a ``Localizer``) holds the map, and the scan (body frame) as its resident scan; ``scan_obj`` is a
     context whose MAP is that scan.  FPFH of both sides (``fpfh``: the fields of ``_lib.fpfh_cfg``; ``scan_fpfh``: the scan side's
@@ -804,14 +814,29 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
     ``prune``: None, or a dict of ``corr_prune``'s keyword arguments -- the pairs then go through ``corr_prune`` on ``map_obj``, and
     ``corr_consensus`` samples from ``src[keep]``, ``dst[keep]`` alone.  The returned pairs, src and dst stay the unpruned ones;
     ``prune`` is added to the result, the dict ``corr_prune`` returned, and ``consensus["tri"]`` then indexes the KEPT pairs:
-    pair ``prune["keep"][t]`` of the unpruned ones."""
+    pair ``prune["keep"][t]`` of the unpruned ones.
+    ``keypoints``: None, or a dict of the fields of ``_lib.keypoint_cfg`` (``scan_keypoints``: the scan side's where they differ) --
+    both sides then run ``map_keypoints``, and ``desc_ref_set`` and ``desc_pairs`` see the keypoints' FPFH rows alone; FPFH itself is
+    still formed for every point.  The returned pairs, src and dst are in the ORIGINAL indices; ``keypoints`` is added to the result:
+    (the scan's ascending indices, the map's)."""
     fpfh, corr, align = dict(fpfh or {}), dict(corr or {}), dict(align or {})
     m_hip, s_hip = getattr(map_obj, "hip", map_obj), getattr(scan_obj, "hip", scan_obj)
     f_map = map_obj.map_fpfh(want=(), **fpfh)["fpfh"]
     f_scan = scan_obj.map_fpfh(want=(), **(fpfh if scan_fpfh is None else dict(scan_fpfh)))["fpfh"]
-    map_obj.desc_ref_set(f_map)
-    scan_obj.desc_ref_set(f_scan)
-    qi, rj = desc_pairs(map_obj, scan_obj, f_scan, f_map, ratio=ratio, mutual=mutual)
+    if keypoints is None:
+        kp = None
+        map_obj.desc_ref_set(f_map)
+        scan_obj.desc_ref_set(f_scan)
+        qi, rj = desc_pairs(map_obj, scan_obj, f_scan, f_map, ratio=ratio, mutual=mutual)
+    else:
+        kp_map = map_obj.map_keypoints(want=(), **dict(keypoints))["index"]
+        kp_scan = scan_obj.map_keypoints(want=(), **dict(keypoints if scan_keypoints is None else scan_keypoints))["index"]
+        kp = (kp_scan, kp_map)
+        k_scan, k_map = np.ascontiguousarray(f_scan[kp_scan]), np.ascontiguousarray(f_map[kp_map])
+        map_obj.desc_ref_set(k_map)
+        scan_obj.desc_ref_set(k_scan)
+        qi, rj = desc_pairs(map_obj, scan_obj, k_scan, k_map, ratio=ratio, mutual=mutual)
+        qi, rj = kp_scan[qi], kp_map[rj]
     src, dst = s_hip.map_points()[qi], m_hip.map_points()[rj]
     pruned = None if prune is None else corr_prune(map_obj, src, dst, **dict(prune))
     s_in, d_in = (src, dst) if pruned is None else (src[pruned["keep"]], dst[pruned["keep"]])
@@ -826,6 +851,8 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
                x26=aligned["x26"][0] if ranked.shape[0] else None)
     if pruned is not None:
         out["prune"] = pruned
+    if kp is not None:
+        out["keypoints"] = kp
     return out
 
 

@@ -60,6 +60,7 @@ struct flimo_ctx {
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
   size_t outlier_chunk = (size_t)1 << 20;   // points per search launch of flimo_map_outliers (flimo_set_outlier_chunk)
   size_t fpfh_chunk = (size_t)1 << 20;      // points per search launch of flimo_map_fpfh (flimo_set_fpfh_chunk)
+  size_t keypoints_chunk = (size_t)1 << 20; // points per search launch of flimo_map_keypoints (flimo_set_keypoints_chunk)
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   size_t corr_chunk = (size_t)1 << 16;      // hypotheses per chunk of flimo_corr_poses (flimo_set_corr_chunk)
@@ -1698,6 +1699,71 @@ extern "C" int flimo_map_fpfh(flimo_ctx* c, size_t first, size_t n, const flimo_
 extern "C" int flimo_set_fpfh_chunk(flimo_ctx* c, size_t n) {
   if (!c) return FLIMO_ERR_INVALID;
   c->fpfh_chunk = n ? n : (size_t)1 << 20;
+  return FLIMO_OK;
+}
+
+// ---- ISS keypoints of the stored points (pcl::ISSKeypoint3D over the map) -------------------------------------------------------
+// kernels: flimo_knn_k.hip.  Two stages on the context's stream, in chunks of c->keypoints_chunk points: the saliency of the WHOLE
+// map whatever the range (a neighbour can be anywhere; 8 B a stored point, three launches a chunk: flimo_map_normals_range's two
+// searches and one thread per point in the place of its eigen-decomposition's outputs), then the suppression over the range (two
+// launches a chunk, 1 B a point of the chunk comes back).  Per chunk the scratch is the moments and count (76 B a point), the
+// worklist (8 B) and the mask (1 B); nothing of points x k entries exists anywhere.
+extern "C" int flimo_map_keypoints(flimo_ctx* c, size_t first, size_t n, const flimo_keypoint_cfg* cfg, unsigned char* mask, double* saliency,
+                                   int32_t* cnt, size_t* count) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "map keypoints: null cfg");
+  if (first > c->map_n || n > c->map_n - first)
+    return fail(c, FLIMO_ERR_INVALID, "map keypoints: the range [%zu, %zu + %zu) ends beyond the map's %zu points", first, first, n, c->map_n);
+  { const int rc = check_gate(c, "map keypoints", cfg->max_dist); if (rc) return rc; }
+  { const int rc = check_gate(c, "map keypoints (suppression)", cfg->nms_max_dist); if (rc) return rc; }
+  if (!(cfg->gamma21 > 0.f && cfg->gamma21 <= 1.f) || !(cfg->gamma32 > 0.f && cfg->gamma32 <= 1.f))
+    return fail(c, FLIMO_ERR_INVALID, "map keypoints: gamma21 and gamma32 must be in (0, 1]");
+  if (cfg->min_pts < 0) return fail(c, FLIMO_ERR_INVALID, "map keypoints: min_pts must be >= 0");
+  if (cfg->k < 3 || cfg->k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map keypoints: k must be in 3..%d", FLIMO_KNN_MAX_K);
+  if (cfg->nms_k < 2 || cfg->nms_k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map keypoints: nms_k must be in 2..%d", FLIMO_KNN_MAX_K);
+  const size_t N = c->map_n;
+  if (N >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map keypoints: the map must hold fewer than 2^31 points");
+  if (n == 0) { if (count) *count = 0; return FLIMO_OK; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map keypoints: a map of %zu points has no index", N);
+  ctx_enter(c);
+  DevScratch d;
+  const size_t m = std::min(N, std::max<size_t>(c->keypoints_chunk, 1));      // points of a chunk, of the map's stage and of the range's
+  double* d_sal = d.get<double>(N);
+  int32_t* d_rcnt = cnt ? d.get<int32_t>(n) : nullptr;
+  int32_t* d_ncnt = d.get<int32_t>(m);
+  double* d_mom = d.get<double>(m * 9);
+  uint2* d_work = d.get<uint2>(m);
+  unsigned* d_nwork = d.get<unsigned>(1);
+  unsigned* d_count = d.get<unsigned>(1);
+  unsigned char* d_mask = d.get<unsigned char>(std::min(m, n));
+  { const int rc = d.ok(c); if (rc) return rc; }
+  // (a chunk's worklist and moments are read by its own launches only: the stream orders the chunks, nothing waits in between)
+  for (size_t a = 0; a < N; a += m)
+    HIPCHK(c, launch_iss_saliency(c->stream, c->grid, c->d_map_raw, (unsigned)a, (int)std::min(m, N - a), cfg->k, cfg->max_dist, cfg->min_pts,
+                                  cfg->gamma21, cfg->gamma32, d_sal, (unsigned)first, (unsigned)n, d_rcnt, d_ncnt, d_mom, d_work, d_nwork));
+  HIPCHK(c, hipMemsetAsync(d_count, 0, sizeof(unsigned), c->stream));
+  if (saliency) HIPCHK(c, hipMemcpyAsync(saliency, d_sal + first, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (cnt) HIPCHK(c, hipMemcpyAsync(cnt, d_rcnt, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  for (size_t a = 0; a < n; a += m) {
+    const size_t na = std::min(m, n - a);
+    HIPCHK(c, launch_iss_suppress(c->stream, c->grid, c->d_map_raw, d_sal, (unsigned)(first + a), (int)na, cfg->nms_k, cfg->nms_max_dist, d_mask,
+                                  d_count, d_work, d_nwork));
+    if (mask) {
+      HIPCHK(c, hipMemcpyAsync(mask + a, d_mask, na, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));      // (the next chunk overwrites d_mask)
+    }
+  }
+  unsigned h_count = 0;
+  HIPCHK(c, hipMemcpyAsync(&h_count, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((size_t)h_count > n) return fail(c, FLIMO_ERR_HIP, "map keypoints: counted %u of %zu points", h_count, n);
+  if (count) *count = (size_t)h_count;
+  return FLIMO_OK;
+}
+extern "C" int flimo_set_keypoints_chunk(flimo_ctx* c, size_t n) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->keypoints_chunk = n ? n : (size_t)1 << 20;
   return FLIMO_OK;
 }
 

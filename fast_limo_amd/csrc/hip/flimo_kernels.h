@@ -321,6 +321,19 @@ hipError_t launch_fpfh_spfh(hipStream_t st, const GridView& G, const float4* map
 hipError_t launch_fpfh_sum(hipStream_t st, const GridView& G, const float4* map_raw, const unsigned char* spfh, const unsigned char* len,
                            unsigned first, int nq, int k, float max_dist, float* fpfh, int32_t* cnt, uint2* work, unsigned* nwork);
 
+// ISS keypoints of stored points (flimo_map_keypoints, flimo_c.h).  launch_iss_saliency: launch_knn_k_normals' search and moments
+// for the stored points first .. first + nq - 1, each ended by one thread in its saliency -- l0 of flimo_map_normals_range where
+// cnt >= max(3, min_pts), l0 > 0, l1 < gamma21 * l2 and l0 < gamma32 * l1 (float64, strict), a quiet NaN otherwise: sal [map size]
+// (rows first ..); rcnt (optional) [rn]: cnt of the points inside [rfirst, rfirst + rn).  Scratch: cnt ([nq]), mom ([nq][9]), work
+// ([nq]), nwork.  launch_iss_suppress: the search with a list of k keys for the stored points first .. first + nq - 1, each ended
+// in mask [nq] (rows 0 ..): salient, and no other point of its list salient with a greater saliency, or an equal one and a lower
+// index; *count (device) grows by the ones.  Scratch: work ([nq]), nwork.
+hipError_t launch_iss_saliency(hipStream_t st, const GridView& G, const float4* map_raw, unsigned first, int nq, int k, float max_dist, int min_pts,
+                               float gamma21, float gamma32, double* sal, unsigned rfirst, unsigned rn, int32_t* rcnt, int32_t* cnt, double* mom,
+                               uint2* work, unsigned* nwork);
+hipError_t launch_iss_suppress(hipStream_t st, const GridView& G, const float4* map_raw, const double* sal, unsigned first, int nq, int k,
+                               float max_dist, unsigned char* mask, unsigned* count, uint2* work, unsigned* nwork);
+
 // The same search with k = 1 for every (pose, point of the resident scan) pair of a chunk of poses (flimo_scan_fitness, flimo_c.h):
 // the world point is transform_kernel's, from poses [np][12] (the upper three rows of PoseMats::RT).  sqd [np][n]: the nearest
 // stored point's squared distance, -1 for an empty query; idx [np][n] (optional): its insertion index, -1; inliers / sum_sqd [np]:

@@ -1218,6 +1218,84 @@ struct FpfhJob {
   }
 };
 
+// ---- ISS keypoints of stored points (flimo_map_keypoints) ------------------------------------------------------------------------
+// Saliency: NormalsJob's moments with stored points as queries, then one THREAD per point in the place of
+// knnk_normals_finish_kernel: the same sums / n, the same kk_plane -- the eigenvalues are flimo_map_normals_range's by
+// construction -- and the three strict float64 tests; sal [map size] holds l0 of a salient point and a quiet NaN otherwise (no
+// compare with a NaN holds, so a point that is not salient neither beats a neighbour nor survives).  cnt of the points inside the
+// range [rfirst, rfirst + rn) goes to rcnt when asked for.
+__global__ __launch_bounds__(KK_BLOCK) void iss_saliency_kernel(unsigned first, int nq, int need, double gamma21, double gamma32,
+                                                                const int32_t* __restrict__ cnt, const double* __restrict__ mom, double* __restrict__ sal,
+                                                                unsigned rfirst, unsigned rn, int32_t* __restrict__ rcnt) {
+  const size_t gq = (size_t)blockIdx.x * KK_BLOCK + threadIdx.x;
+  if (gq >= (size_t)nq) return;
+  const int c = cnt[gq];
+  const double* M = mom + (size_t)KK_MOM * gq;
+  const double n = (double)c;
+  double s = __longlong_as_double(0x7ff8000000000000ll);
+  if (c >= need) {
+    double l0, l1, l2, nx, ny, nz;
+    kk_plane(M[3] / n, M[4] / n, M[5] / n, M[6] / n, M[7] / n, M[8] / n, false, 0.0, 0.0, 0.0, l0, l1, l2, nx, ny, nz);
+    if (l0 > 0.0 && l1 < gamma21 * l2 && l0 < gamma32 * l1) s = l0;
+  }
+  const unsigned j = first + (unsigned)gq;
+  sal[j] = s;
+  if (rcnt && j >= rfirst && j - rfirst < rn) rcnt[j - rfirst] = c;
+}
+
+// Suppression: the search once more with a list of nms_k keys.  Lane `sub` holds slot sub of the list of point j = first + at and
+// gathers the saliency of that slot's point: it BEATS j when it is another point (by index: an exact duplicate is at distance 0 too)
+// whose saliency is greater, or equal with a lower insertion index.  The group's ballot decides; integers only.
+template <int L>
+__device__ __forceinline__ void knnk_iss(unsigned first, int k, kk_u64 gate_key, int lane, size_t at, bool live, kk_u64 mine,
+                                         const double* __restrict__ sal, unsigned char* __restrict__ mask, unsigned* __restrict__ count) {
+  const int sub = lane & (L - 1);
+  const bool has = live && sub < k && mine < gate_key;
+  const unsigned j = first + (unsigned)at;
+  bool beats = false;
+  double sj = 0.0;
+  if (live) sj = sal[j];
+  if (has) {
+    const uint32_t t = (uint32_t)mine;
+    if (t != j) {
+      const double st = sal[t];
+      beats = st > sj || (st == sj && t < j);
+    }
+  }
+  const unsigned long long bb = __ballot(beats);
+  const bool beaten = L == 64 ? bb != 0ull : kk_group_mask<L>(bb, lane) != 0u;
+  const bool key = live && sj == sj && !beaten;
+  const unsigned long long bk = __ballot(key && sub == 0);
+  if (live && sub == 0) mask[at] = key ? 1 : 0;
+  if (lane == 0 && bk) atomicAdd(count, (unsigned)__popcll(bk));
+}
+
+// the stored points of a chunk of the range, ended in their mask byte (the chunk's) from the saliency of the whole map
+struct IssJob {
+  static constexpr int LANES = 0;
+  static constexpr bool PAIRS = false;
+  unsigned first;        // query i is stored point first + i
+  int nq, k;
+  float r2;
+  kk_u64 gate_key;
+  const float4* map_raw;
+  const double* sal;     // [map size]
+  unsigned char* mask;   // [nq]
+  unsigned* count;       // the keypoints so far
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
+    const bool live = kk_flat_slot<L>(nq, at);
+    if (live) query(at, x, y, z);
+    return live;
+  }
+  __host__ __device__ size_t total() const { return (size_t)nq; }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
+  template <int L>
+  __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float, float, float) const {
+    knnk_iss<L>(first, k, gate_key, lane, at, live, mine, sal, mask, count);
+  }
+};
+
 // lanes per query from k: a list of k keys needs k lanes
 int knnk_plan(int k) { return k <= 16 ? 16 : 64; }
 
@@ -1321,6 +1399,35 @@ hipError_t launch_fpfh_sum(hipStream_t st, const GridView& G, const float4* map_
   J.first = first; J.nq = nq; J.k = k;
   kk_gate(max_dist, J.r2, J.gate_key);
   J.map_raw = map_raw; J.spfh = spfh; J.len = len; J.fpfh = fpfh; J.cnt = cnt;
+  const hipError_t e = kk_launch(st, G, J, work, nwork);
+  return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_iss_saliency(hipStream_t st, const GridView& G, const float4* map_raw, unsigned first, int nq, int k, float max_dist, int min_pts,
+                               float gamma21, float gamma32, double* sal, unsigned rfirst, unsigned rn, int32_t* rcnt, int32_t* cnt, double* mom,
+                               uint2* work, unsigned* nwork) {
+  if (nq <= 0) return hipSuccess;
+  if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
+  NormalsJob J;
+  J.qxyz = nullptr; J.first = first; J.nq = nq; J.k = k; J.need = std::max(3, min_pts);
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.has_vp = 0; J.vx = J.vy = J.vz = 0.f;
+  J.map_raw = map_raw; J.cnt = cnt; J.mom = mom;
+  const hipError_t e = kk_launch(st, G, J, work, nwork);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(iss_saliency_kernel, dim3((unsigned)(((size_t)nq + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, first, nq, J.need,
+                     (double)gamma21, (double)gamma32, cnt, mom, sal, rfirst, rn, rcnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_iss_suppress(hipStream_t st, const GridView& G, const float4* map_raw, const double* sal, unsigned first, int nq, int k,
+                               float max_dist, unsigned char* mask, unsigned* count, uint2* work, unsigned* nwork) {
+  if (nq <= 0) return hipSuccess;
+  if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
+  IssJob J;
+  J.first = first; J.nq = nq; J.k = k;
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.map_raw = map_raw; J.sal = sal; J.mask = mask; J.count = count;
   const hipError_t e = kk_launch(st, G, J, work, nwork);
   return e != hipSuccess ? e : hipGetLastError();
 }

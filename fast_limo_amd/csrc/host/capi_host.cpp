@@ -356,6 +356,20 @@ int flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh_cf
   }
   return flimo_map_fpfh(c, first, n, cfg, fpfh, spfh, cnt);
 }
+int flimo_loc_map_keypoints(flimo_loc* L, size_t first, size_t n, const flimo_keypoint_cfg* cfg, unsigned char* mask, double* saliency, int32_t* cnt,
+                            size_t* count) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
+  if (!c) {                          // no map yet: the answer of an empty one, after flimo_map_keypoints' own argument checks
+    if (!cfg || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
+    if (std::isnan(cfg->max_dist) || cfg->max_dist < 0.f || std::isnan(cfg->nms_max_dist) || cfg->nms_max_dist < 0.f) return FLIMO_ERR_INVALID;
+    if (!(cfg->gamma21 > 0.f && cfg->gamma21 <= 1.f) || !(cfg->gamma32 > 0.f && cfg->gamma32 <= 1.f) || cfg->min_pts < 0) return FLIMO_ERR_INVALID;
+    if (cfg->k < 3 || cfg->k > FLIMO_KNN_MAX_K || cfg->nms_k < 2 || cfg->nms_k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
+    if (count) *count = 0;
+    return FLIMO_OK;
+  }
+  return flimo_map_keypoints(c, first, n, cfg, mask, saliency, cnt, count);
+}
 int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
                          const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
   if (!L) return FLIMO_ERR_INVALID;

@@ -547,6 +547,22 @@ int Mapper::remove_outliers(size_t first, size_t n, const flimo_outlier_cfg& cfg
   return flimo_map_remove_outliers(ctx_, first, n, &cfg, removed, stats);
 }
 
+// ISS keypoints of the map's stored points (an insert, a crop or a carve on the worker thread ends first)
+int Mapper::keypoints(size_t first, size_t n, const flimo_keypoint_cfg& cfg, std::vector<unsigned char>& mask, std::vector<double>* saliency,
+                      std::vector<int32_t>* cnt, size_t* count) {
+  sync();
+  mask.clear();
+  if (saliency) saliency->clear();
+  if (cnt) cnt->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (first > flimo_map_size(ctx_) || n > flimo_map_size(ctx_) - first) return FLIMO_ERR_INVALID;
+  mask.assign(n, 0);
+  if (saliency) saliency->assign(n, (double)NAN);
+  if (cnt) cnt->assign(n, 0);
+  return flimo_map_keypoints(ctx_, first, n, &cfg, n ? mask.data() : nullptr, (saliency && n) ? saliency->data() : nullptr,
+                             (cnt && n) ? cnt->data() : nullptr, count);
+}
+
 // fitness of the resident scan at pose hypotheses (an insert or a crop on the worker thread ends first)
 int Mapper::fitness(const double* x26, size_t np, float max_dist, std::vector<int32_t>& inliers, std::vector<double>& sum_sqd,
                     std::vector<float>* nn_sqd, std::vector<int32_t>* nn_idx) {

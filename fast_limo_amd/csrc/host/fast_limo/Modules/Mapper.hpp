@@ -69,6 +69,11 @@ class fast_limo::Mapper {
   // the caller's schedule decides when, so it runs at once -- after an insert, a crop or a carve still on the worker thread --
   // and is not queued.  removed / stats may be null.  Returns a FLIMO_* code.
   int remove_outliers(size_t first, size_t n, const flimo_outlier_cfg& cfg, size_t* removed = nullptr, flimo_outlier_stats* stats = nullptr);
+  // The stored points first .. first + n - 1 that are ISS keypoints (flimo_map_keypoints: pcl::ISSKeypoint3D with k-bounded
+  // neighbourhoods and broken ties): mask [n] (1 = keypoint), and where a vector is given saliency [n] (l0, NaN when not salient),
+  // cnt [n]; count (may be null): the ones of the mask.  Changes nothing.  Returns a FLIMO_* code.
+  int keypoints(size_t first, size_t n, const flimo_keypoint_cfg& cfg, std::vector<unsigned char>& mask, std::vector<double>* saliency = nullptr,
+                std::vector<int32_t>* cnt = nullptr, size_t* count = nullptr);
   // octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the GPU map (flimo_radius_search).  The reference's Mapper hides
   // its octree, so this is an addition: the stored points with (p - query).squaredNorm() < radius * radius (strict, float32), in
   // ascending order of (distance, insertion index) -- the reference's traversal order is not reproduced.  As the template

@@ -332,6 +332,44 @@ typedef struct flimo_fpfh_cfg {
 int flimo_map_fpfh(flimo_ctx* ctx, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh /* [n][33], required */,
                    uint8_t* spfh /* [n][33], may be NULL */, int32_t* cnt /* [n], may be NULL */);
 
+/* ---- ISS keypoints of the stored points: pcl::ISSKeypoint3D (Zhong 2009) over the map -- the detector that goes in front of the
+ * descriptors, so that flimo_map_fpfh's rows of plane interiors need not be matched ----
+ * The neighbour lists and the eigenvalues never leave the GPU; the non-maximum suppression is a gather over the list.
+ *
+ * Definition (tests/keypoints_common.py restates it in numpy).  Point i of the range is stored point j = first + i, insertion order.
+ *  - saliency of EVERY stored point t: (c_t, l0, l1, l2) = cnt and eig[0..2] of flimo_map_normals_range(t, 1, k, max_dist, min_pts,
+ *    NULL), bit for bit (the orientation does not enter).  t is SALIENT iff c_t >= max(3, min_pts), l0 > 0.0,
+ *    l1 < (double)gamma21 * l2 and l0 < (double)gamma32 * l1: each test one float64 product and a strict compare, no division; a
+ *    NaN fails.  s_t = l0 then.  saliency[i] = s_j, a quiet NaN when j is not salient; cnt[i] = c_j.
+ *  - suppression: N_j = flimo_knn_k(p_j, nms_k, nms_max_dist) over the whole map, the same predicate, the same unique order.  j is a
+ *    KEYPOINT iff it is salient and no entry t != j of N_j is salient with s_t > s_j, or with s_t == s_j and t < j: among exact ties
+ *    the lower insertion index wins, so of a point and its exact duplicates at most one survives.  mask[i] = 1 / 0; *count = the
+ *    number of ones, exact.
+ * Differences from PCL: the scatter is taken about the neighbourhood's centroid and divided by n, as flimo_map_normals forms it
+ * (PCL: about the point); the neighbourhoods are the max_nn form of a radius search -- the first k inside the gate --, not every
+ * point in the radius; ties are broken instead of both points kept; there is no border estimation.
+ * Every output is an integer, a bit, or a float64 that flimo_map_normals_range already defines: the bits do not depend on the
+ * chunking, the cell size, the range form or the path of the search.
+ * Cost: the saliency is formed for the WHOLE map whatever the range (a neighbour can be anywhere), nothing is kept between calls;
+ * device scratch is 8 B a stored point plus 85 B a point of a chunk of 2^20.
+ * n = 0 (also on an empty map, first = 0): FLIMO_OK, *count = 0, nothing else touched.  FLIMO_ERR_INVALID -- outputs untouched --
+ * for a NULL ctx or cfg, first + n beyond flimo_map_size, max_dist or nms_max_dist NaN or negative, gamma21 or gamma32 NaN or outside
+ * (0, 1], min_pts < 0; FLIMO_ERR_UNSUPPORTED for k outside 3..FLIMO_KNN_MAX_K or nms_k outside 2..FLIMO_KNN_MAX_K;
+ * FLIMO_ERR_TOO_LARGE for a map of 2^31 points or more.  Calling rules as flimo_map_fpfh: no pass of this context in flight;
+ * changes nothing: not the map, not the scan, not the bits of a later pass. */
+typedef struct flimo_keypoint_cfg {
+  int   k;             /* salient neighbourhood, the point itself included: 3 .. FLIMO_KNN_MAX_K */
+  float max_dist;      /* its gate, as flimo_knn_k (the salient radius); INFINITY: none */
+  int   min_pts;       /* fewer neighbours than max(3, min_pts): not salient; >= 0 */
+  float gamma21;       /* l1 < gamma21 * l2 required; in (0, 1] */
+  float gamma32;       /* l0 < gamma32 * l1 required; in (0, 1] */
+  int   nms_k;         /* suppression neighbourhood, the point itself included: 2 .. FLIMO_KNN_MAX_K */
+  float nms_max_dist;  /* its gate (the non-max radius); INFINITY: none */
+} flimo_keypoint_cfg;
+int flimo_map_keypoints(flimo_ctx* ctx, size_t first, size_t n, const flimo_keypoint_cfg* cfg,
+                        unsigned char* mask /* [n], may be NULL */, double* saliency /* [n], may be NULL */,
+                        int32_t* cnt /* [n], may be NULL */, size_t* count /* may be NULL */);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

@@ -82,6 +82,10 @@ int flimo_set_outlier_chunk(flimo_ctx* ctx, size_t n);
  * over the range: the chunk bounds the normals' moments, the worklist and the rows on their way back, 220 B a point; equal results
  * whatever the chunk. */
 int flimo_set_fpfh_chunk(flimo_ctx* ctx, size_t n);
+/* flimo_map_keypoints works in chunks of n points (default 2^20; 0 restores it), in its stage over the whole map and in the one over
+ * the range: the chunk bounds the moments, the worklist and the mask on its way back, 85 B a point; equal results whatever the
+ * chunk. */
+int flimo_set_keypoints_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_corr_poses works in chunks of n hypotheses (default 2^16; 0 restores it): the chunk bounds the call's device scratch, 136 B
  * a hypothesis (and m floats each where pair_sqd is asked for: then at most 2^26 slots a chunk); equal results whatever the chunk. */
 int flimo_set_corr_chunk(flimo_ctx* ctx, size_t n);

@@ -130,6 +130,12 @@ int    flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, 
  * has no map yet answers like an empty one (first = n = 0: nothing touched; any other range lies beyond it).  The Localizer's own
  * update does not use it. */
 int    flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh, uint8_t* spfh, int32_t* cnt);
+/* ISS keypoints of the Localizer's stored points: flimo_map_keypoints (include/flimo_c.h: same arguments, same results, same error
+ * codes) on the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  A Localizer that
+ * has no map yet answers like an empty one (first = n = 0: *count = 0; any other range lies beyond it).  The Localizer's own update
+ * does not use it. */
+int    flimo_loc_map_keypoints(flimo_loc* L, size_t first, size_t n, const flimo_keypoint_cfg* cfg, unsigned char* mask, double* saliency,
+                               int32_t* cnt, size_t* count);
 /* Pose hypotheses from point correspondences: flimo_corr_poses (include/flimo_c.h: same arguments, same results, same error
  * codes) on the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  Neither the map
  * nor the resident scan is read; a Localizer that has no context yet creates it.  The Localizer's own update does not use it. */
