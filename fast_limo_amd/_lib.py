@@ -166,6 +166,47 @@ def keypoints_call(call, n, want, cfg):
     return out
 
 
+class ClusterCfg(C.Structure):
+    """flimo_cluster_cfg (include/flimo_c.h)."""
+    _fields_ = [("tol", C.c_float), ("min_size", C.c_int), ("max_size", C.c_int)]
+
+
+class ClusterStats(C.Structure):
+    """flimo_cluster_stats (include/flimo_c.h)."""
+    _fields_ = [("n", C.c_uint64), ("clusters", C.c_uint64), ("largest", C.c_uint64), ("sel_clusters", C.c_uint64),
+                ("sel_points", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(n=int(self.n), clusters=int(self.clusters), largest=int(self.largest), sel_clusters=int(self.sel_clusters),
+                    sel_points=int(self.sel_points))
+
+
+def cluster_cfg(tol=0.5, min_size=1, max_size=0) -> ClusterCfg:
+    """Half a metre, every component selected unless told otherwise (``max_size`` 0: no upper bound)."""
+    return ClusterCfg(float(tol), int(min_size), int(max_size))
+
+
+def clusters_call(call, n, want, cfg):
+    """The output arrays of flimo_map_clusters / flimo_loc_map_clusters (``call`` takes: cfg, label, size, mask, stats) as a dict
+    with the outputs named in ``want`` (of "label", "size", "mask") and "stats"; shared with ``api.Localizer``."""
+    unknown = set(want) - {"label", "size", "mask"}
+    if unknown:
+        raise ValueError(f"clusters: unknown outputs {sorted(unknown)}")
+    k = cluster_cfg(**cfg)
+    arr = {}
+    for name, dt in (("label", np.int32), ("size", np.int32), ("mask", np.uint8)):
+        if name in want:
+            arr[name] = np.zeros(max(n, 1), dt)
+    st = ClusterStats()
+    ptr = lambda name: arr[name].ctypes.data if name in arr else None
+    call(C.byref(k), ptr("label"), ptr("size"), ptr("mask"), C.byref(st))
+    out = {name: a[:n] for name, a in arr.items()}
+    if "mask" in out:
+        out["mask"] = out["mask"].astype(bool)
+    out["stats"] = st.as_dict()
+    return out
+
+
 class CorrCfg(C.Structure):
     """flimo_corr_cfg (include/flimo_c.h)."""
     _fields_ = [("edge_sim", C.c_float), ("min_edge", C.c_float), ("max_dist", C.c_float)]
@@ -290,7 +331,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_clusters", "flimo_map_remove_clusters", "flimo_set_cluster_chunk", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_corr_graph", "flimo_corr_compatible_host", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -392,6 +433,9 @@ def load_hip():
     L.flimo_set_fpfh_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_map_keypoints.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(KeypointCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.flimo_set_keypoints_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_map_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(ClusterCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClusterStats)]
+    L.flimo_map_remove_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(ClusterCfg), C.POINTER(C.c_size_t), C.POINTER(ClusterStats)]
+    L.flimo_set_cluster_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
     L.flimo_map_last_time.argtypes = [vp]
@@ -641,6 +685,31 @@ class HipCtx:
     def set_keypoints_chunk(self, n):
         """Points per search launch of ``map_keypoints`` (flimo_set_keypoints_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_keypoints_chunk(self._h, int(n)))
+
+    def map_clusters(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
+        """Euclidean clusters (pcl::EuclideanClusterExtraction) of the stored points, for the points first .. first + n - 1 (``n``
+        None: up to the map's end) -- flimo_map_clusters; ``cfg``: the fields of ``cluster_cfg`` (tol, min_size, max_size).  Returns a
+        dict: of ``want`` ``label`` [n] int32 (the smallest insertion index of the point's component), ``size`` [n] int32, ``mask``
+        [n] bool (the component is selected), and ``stats``.  The components are the whole map's whatever the range; changes
+        nothing.  ``api.cluster_lists`` turns the labels into PCL's index lists."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return clusters_call(lambda *a: self._chk(self._L.flimo_map_clusters(self._h, first, n, *a)), n, want, cfg)
+
+    def map_remove_clusters(self, first=0, n=None, **cfg):
+        """Forget the points of the range whose ``map_clusters`` mask is set -- flimo_map_remove_clusters; afterwards the map is as
+        after ``map_crop_box``.  Returns (points removed, stats)."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        k = cluster_cfg(**cfg)
+        removed = C.c_size_t(0)
+        st = ClusterStats()
+        self._chk(self._L.flimo_map_remove_clusters(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)))
+        return int(removed.value), st.as_dict()
+
+    def set_cluster_chunk(self, n):
+        """Points per link launch of ``map_clusters`` / ``map_remove_clusters`` (flimo_set_cluster_chunk; 0: the default of 2^20)."""
+        self._chk(self._L.flimo_set_cluster_chunk(self._h, int(n)))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

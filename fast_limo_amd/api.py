@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_clusters", "flimo_loc_map_remove_clusters", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -168,6 +168,10 @@ def load_host():
                                           C.POINTER(C.c_size_t)]
     L.flimo_loc_map_remove_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.OutlierCfg), C.POINTER(C.c_size_t),
                                                 C.POINTER(_lib.OutlierStats)]
+    L.flimo_loc_map_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.ClusterCfg), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(_lib.ClusterStats)]
+    L.flimo_loc_map_remove_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.ClusterCfg), C.POINTER(C.c_size_t),
+                                                C.POINTER(_lib.ClusterStats)]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -429,6 +433,26 @@ class Localizer:
         return _lib.keypoints_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_keypoints(self._h, first, n, *a), "flimo_loc_map_keypoints"),
                                    n, want, cfg)
 
+    def map_clusters(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
+        """Euclidean clusters of the map's stored points (flimo_loc_map_clusters), as ``HipCtx.map_clusters``.  Waits for an insert, a
+        crop or a carve still running; changes nothing.  No policy calls it: when to clean is the caller's schedule."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return _lib.clusters_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_clusters(self._h, first, n, *a), "flimo_loc_map_clusters"),
+                                  n, want, cfg)
+
+    def map_remove_clusters(self, first=0, n=None, **cfg):
+        """Forget the selected clusters' points of the range (flimo_loc_map_remove_clusters), as ``HipCtx.map_remove_clusters``:
+        (points removed, stats)."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        k = _lib.cluster_cfg(**cfg)
+        removed = C.c_size_t(0)
+        st = _lib.ClusterStats()
+        self._outliers_chk(self._L.flimo_loc_map_remove_clusters(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
+                           "flimo_loc_map_remove_clusters")
+        return int(removed.value), st.as_dict()
+
     def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
         """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,
         as ``HipCtx.radius_search``.  Waits for an insert or a crop still running behind the last sweep; changes nothing."""
@@ -677,6 +701,25 @@ def carve_sensor(x26) -> np.ndarray:
     R = ((1.0 - (tyy + tzz), txy - twz, txz + twy), (txy + twz, 1.0 - (txx + tzz), tyz - twx), (txz - twy, tyz + twx, 1.0 - (txx + tyy)))
     l = x26[11:14]
     return np.float32([x26[a] + ((R[a][0] * l[0] + R[a][1] * l[1]) + R[a][2] * l[2]) for a in range(3)])
+
+
+def cluster_lists(label, min_size=1, max_size=0):
+    """The labels of ``map_clusters`` as pcl::EuclideanClusterExtraction reports clusters: a list of int64 index arrays (positions in
+    ``label``, each ascending), one per label whose count c in ``label`` has min_size <= c and (max_size == 0 or c <= max_size),
+    ordered by count descending, then by label.  Pure numpy."""
+    label = np.asarray(label).reshape(-1)
+    if int(min_size) < 0 or int(max_size) < 0 or 0 < int(max_size) < int(min_size):
+        raise ValueError("cluster_lists: min_size, max_size must be >= 0 and max_size 0 or >= min_size")
+    if label.size == 0:
+        return []
+    order = np.argsort(label, kind="stable")      # (stable: positions ascending within a label)
+    labs, start, cnt = np.unique(label[order], return_index=True, return_counts=True)
+    keep = cnt >= int(min_size)
+    if int(max_size) > 0:
+        keep &= cnt <= int(max_size)
+    pick = np.flatnonzero(keep)
+    pick = pick[np.lexsort((labs[pick], -cnt[pick]))]
+    return [order[start[j]:start[j] + cnt[j]].astype(np.int64) for j in pick]
 
 
 def fitness_cost(inliers, sum_sqd, n, max_dist):

@@ -55,12 +55,14 @@ struct flimo_ctx {
   uint64_t crops = 0, crop_removed = 0;   // flimo_map_crop_box: calls that removed points, points removed so far
   uint64_t carves = 0, carve_removed = 0; // flimo_map_carve: the same
   uint64_t outlier_removals = 0, outlier_removed = 0;   // flimo_map_remove_outliers: the same
+  uint64_t cluster_removals = 0, cluster_removed = 0;   // flimo_map_remove_clusters: the same
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
   size_t outlier_chunk = (size_t)1 << 20;   // points per search launch of flimo_map_outliers (flimo_set_outlier_chunk)
   size_t fpfh_chunk = (size_t)1 << 20;      // points per search launch of flimo_map_fpfh (flimo_set_fpfh_chunk)
   size_t keypoints_chunk = (size_t)1 << 20; // points per search launch of flimo_map_keypoints (flimo_set_keypoints_chunk)
+  size_t cluster_chunk = (size_t)1 << 20;   // points per link launch of flimo_map_clusters (flimo_set_cluster_chunk)
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   size_t corr_chunk = (size_t)1 << 16;      // hypotheses per chunk of flimo_corr_poses (flimo_set_corr_chunk)
@@ -1764,6 +1766,106 @@ extern "C" int flimo_map_keypoints(flimo_ctx* c, size_t first, size_t n, const f
 extern "C" int flimo_set_keypoints_chunk(flimo_ctx* c, size_t n) {
   if (!c) return FLIMO_ERR_INVALID;
   c->keypoints_chunk = n ? n : (size_t)1 << 20;
+  return FLIMO_OK;
+}
+
+// ---- Euclidean clusters of the stored points (pcl::EuclideanClusterExtraction over the map) -------------------------------------
+// kernels: flimo_cluster.hip.  Four launches on the context's stream over the WHOLE map whatever the range (a component can reach
+// anywhere): init, link in chunks of c->cluster_chunk stored points, flatten, finish; then the copies back, one wait.  Scratch: 8 B
+// a stored point (parent, count), 1 B a point of the range (mask), 4 B each for label and size where they are asked for; nothing of
+// points x neighbours exists anywhere.  The removal hands the device mask to the crop's ordered compaction (map_keep_only).
+static void cluster_stats_none(flimo_cluster_stats* s) {
+  if (s) s->n = s->clusters = s->largest = s->sel_clusters = s->sel_points = 0;
+}
+static int cluster_check(flimo_ctx* c, size_t first, size_t n, const flimo_cluster_cfg* cfg, const char* what) {
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
+  if (first > c->map_n || n > c->map_n - first)
+    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
+  if (!(cfg->tol >= 0.f) || std::isinf(cfg->tol)) return fail(c, FLIMO_ERR_INVALID, "%s: tol must be finite and >= 0", what);
+  if (cfg->min_size < 0 || cfg->max_size < 0) return fail(c, FLIMO_ERR_INVALID, "%s: min_size and max_size must be >= 0", what);
+  if (cfg->max_size > 0 && cfg->max_size < cfg->min_size) return fail(c, FLIMO_ERR_INVALID, "%s: max_size must be 0 or >= min_size", what);
+  if (c->map_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the map must hold fewer than 2^31 points", what);
+  return FLIMO_OK;
+}
+struct ClusterDev {      // what clusters_device leaves on the device for its caller, and the owner of all it allocated
+  DevScratch mem;
+  int32_t* label = nullptr; int32_t* size = nullptr; unsigned char* mask = nullptr;
+};
+// the components of the whole map and the selection over [first, first + n), arguments checked, map not empty: d.mask (n > 0) and,
+// where asked for, d.label / d.size filled on the device, *st on the host; ends synchronised
+static int clusters_device(flimo_ctx* c, size_t first, size_t n, const flimo_cluster_cfg& cfg, bool want_label, bool want_size, ClusterDev& d,
+                           flimo_cluster_stats* st) {
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  const size_t N = c->map_n;
+  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map clusters: a map of %zu points has no index", N);
+  ctx_enter(c);
+  const size_t m = std::min(std::min(N, std::max<size_t>(c->cluster_chunk, 1)), (size_t)1 << 24);      // (x 64 lanes: below 2^31 a launch)
+  uint32_t* d_parent = d.mem.get<uint32_t>(N);
+  uint32_t* d_count = d.mem.get<uint32_t>(N);
+  uint32_t* d_words = d.mem.get<uint32_t>(4);      // {components, largest, selected components, ones of the mask}
+  if (n > 0) d.mask = d.mem.get<unsigned char>(n);
+  if (n > 0 && want_label) d.label = d.mem.get<int32_t>(n);
+  if (n > 0 && want_size) d.size = d.mem.get<int32_t>(n);
+  { const int rc = d.mem.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemsetAsync(d_words, 0, 4 * sizeof(uint32_t), c->stream));
+  HIPCHK(c, launch_cluster_init(c->stream, d_parent, d_count, N));
+  for (size_t a = 0; a < N; a += m)
+    HIPCHK(c, launch_cluster_link(c->stream, c->grid, c->d_map_raw, (unsigned)a, (int)std::min(m, N - a), cfg.tol, d_parent));
+  HIPCHK(c, launch_cluster_flatten(c->stream, d_parent, d_count, N));
+  HIPCHK(c, launch_cluster_finish(c->stream, d_parent, d_count, N, first, n, cfg.min_size, cfg.max_size, d.label, d.size, d.mask, d_words));
+  uint32_t w[4] = {0, 0, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(w, d_words, sizeof w, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (w[0] < 1 || w[0] > N || w[1] < 1 || w[1] > N || w[2] > w[0] || w[3] > n)
+    return fail(c, FLIMO_ERR_HIP, "map clusters: counted %u components (largest %u, %u selected, %u points) of %zu points", w[0], w[1], w[2], w[3], N);
+  st->n = n; st->clusters = w[0]; st->largest = w[1]; st->sel_clusters = w[2]; st->sel_points = w[3];
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_clusters(flimo_ctx* c, size_t first, size_t n, const flimo_cluster_cfg* cfg, int32_t* label, int32_t* size,
+                                  unsigned char* mask, flimo_cluster_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = cluster_check(c, first, n, cfg, "map clusters"); if (rc) return rc; }
+  if (c->map_n == 0) { cluster_stats_none(stats); return FLIMO_OK; }
+  if (n == 0 && !stats) return FLIMO_OK;
+  ClusterDev d;
+  flimo_cluster_stats st;
+  { const int rc = clusters_device(c, first, n, *cfg, label != nullptr, size != nullptr, d, &st); if (rc) return rc; }
+  if (n > 0) {
+    if (label) HIPCHK(c, hipMemcpyAsync(label, d.label, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (size) HIPCHK(c, hipMemcpyAsync(size, d.size, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (mask) HIPCHK(c, hipMemcpyAsync(mask, d.mask, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (stats) *stats = st;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_remove_clusters(flimo_ctx* c, size_t first, size_t n, const flimo_cluster_cfg* cfg, size_t* removed,
+                                         flimo_cluster_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = cluster_check(c, first, n, cfg, "remove clusters"); if (rc) return rc; }
+  if (c->map_n == 0) { if (removed) *removed = 0; cluster_stats_none(stats); return FLIMO_OK; }
+  if (n == 0 && !stats) { if (removed) *removed = 0; return FLIMO_OK; }
+  ClusterDev d;
+  flimo_cluster_stats st;
+  { const int rc = clusters_device(c, first, n, *cfg, false, false, d, &st); if (rc) return rc; }
+  if (removed) *removed = 0;
+  if (stats) *stats = st;
+  if (st.sel_points == 0) return FLIMO_OK;             // removing nothing changes nothing
+  const size_t n_old = c->map_n;
+  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
+  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  size_t kept = 0;
+  float bb[6];
+  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d.mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
+  if (kept != n_old - (size_t)st.sel_points)
+    return fail(c, FLIMO_ERR_HIP, "remove clusters: the compaction kept %zu of %zu points, %llu marked", kept, n_old, (unsigned long long)st.sel_points);
+  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->cluster_removals, &c->cluster_removed, removed, "remove clusters");
+}
+extern "C" int flimo_set_cluster_chunk(flimo_ctx* c, size_t n) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->cluster_chunk = n ? n : (size_t)1 << 20;
   return FLIMO_OK;
 }
 

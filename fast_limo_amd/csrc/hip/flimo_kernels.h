@@ -261,8 +261,7 @@ void map_scratch_free(MapBuildScratch& S);
 
 // flimo_radius.hip -- Octree::radiusSearch (Octree.hpp:453-523): the stored points with sqdist3(q, p) < radius * radius, per query.
 // Count and fill are ONE walk (same rows, same candidates, same order); lanes per query and the kind of walk (rows of the ball's
-// box, or the directory's tiles for a box of many rows) follow from the radius and the grid alone (radius_plan).
-void radius_plan(const GridView& G, float radius, int& lanes, bool& tiles);
+// box, or the directory's tiles for a box of many rows) follow from the radius and the grid alone (radius_plan, flimo_radius.h).
 // cnt[q] = results of query q; cand (optional): candidates examined per query
 hipError_t launch_radius_count(hipStream_t st, const GridView& G, const float* q, int nq, float radius, uint32_t* cnt, unsigned long long* cand);
 // offsets[0 .. nq] = exclusive sum of cnt[0 .. nq] (cnt[nq] = 0 set by the caller); tmp == nullptr: tmp_bytes only
@@ -276,6 +275,19 @@ hipError_t launch_radius_fill(hipStream_t st, const GridView& G, const float* q,
 hipError_t radius_sort_segments(hipStream_t st, void* tmp, size_t& tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
                                 size_t total, size_t nq, const unsigned long long* offsets);
 hipError_t launch_radius_unpack(hipStream_t st, const unsigned long long* keys, size_t n, const float4* map_raw, int32_t* idx, float* sqd, float* xyz);
+
+// flimo_cluster.hip -- Euclidean clusters of the stored points (flimo_map_clusters, flimo_c.h): the connected components of
+// "sqdist3(p_i, p_j) < tol * tol".  parent, count: [n_map] device words.  init: parent[t] = t, count[t] = 0.  link: the stored
+// points first .. first + nq - 1 walk their balls (radius_plan's lanes and walk) and unite with the hits of lower index -- every
+// access to parent an agent-scope atomic; run it over the whole map, in chunks.  flatten (a launch of its own): parent[t] = the
+// smallest index of t's component, count[that index] = the component's points.  finish: label / size (each may be null) and mask
+// of the range [first, first + n), words[4] (zeroed by the caller) += {components, largest (a maximum), selected components} of
+// the whole map and the ones of the mask.
+hipError_t launch_cluster_init(hipStream_t st, uint32_t* parent, uint32_t* count, size_t n_map);
+hipError_t launch_cluster_link(hipStream_t st, const GridView& G, const float4* map_raw, unsigned first, int nq, float tol, uint32_t* parent);
+hipError_t launch_cluster_flatten(hipStream_t st, uint32_t* parent, uint32_t* count, size_t n_map);
+hipError_t launch_cluster_finish(hipStream_t st, const uint32_t* label_all, const uint32_t* count, size_t n_map, size_t first, size_t n, int min_size,
+                                 int max_size, int32_t* label, int32_t* size, unsigned char* mask, uint32_t* words);
 
 // flimo_knn_k.hip -- Octree::knn (Octree.hpp:526-555) for k up to KNNK_MAX_K with a distance gate: per query the first k stored points
 // in the order (float32 squared-distance bits, insertion index) among those with sqdist3(q, p) < max_dist * max_dist (INFINITY: no

@@ -370,6 +370,31 @@ int flimo_loc_map_keypoints(flimo_loc* L, size_t first, size_t n, const flimo_ke
   }
   return flimo_map_keypoints(c, first, n, cfg, mask, saliency, cnt, count);
 }
+// no map yet: the answer of an empty one, after flimo_map_clusters' own argument checks
+static int clusters_of_no_map(size_t first, size_t n, const flimo_cluster_cfg* cfg, flimo_cluster_stats* stats) {
+  if (!cfg || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
+  if (!(cfg->tol >= 0.f) || std::isinf(cfg->tol) || cfg->min_size < 0 || cfg->max_size < 0) return FLIMO_ERR_INVALID;
+  if (cfg->max_size > 0 && cfg->max_size < cfg->min_size) return FLIMO_ERR_INVALID;
+  if (stats) stats->n = stats->clusters = stats->largest = stats->sel_clusters = stats->sel_points = 0;
+  return FLIMO_OK;
+}
+int flimo_loc_map_clusters(flimo_loc* L, size_t first, size_t n, const flimo_cluster_cfg* cfg, int32_t* label, int32_t* size, unsigned char* mask,
+                           flimo_cluster_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
+  if (!c) return clusters_of_no_map(first, n, cfg, stats);
+  return flimo_map_clusters(c, first, n, cfg, label, size, mask, stats);
+}
+int flimo_loc_map_remove_clusters(flimo_loc* L, size_t first, size_t n, const flimo_cluster_cfg* cfg, size_t* removed, flimo_cluster_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();
+  if (!c) {
+    const int rc = clusters_of_no_map(first, n, cfg, stats);
+    if (rc == FLIMO_OK && removed) *removed = 0;
+    return rc;
+  }
+  return flimo_map_remove_clusters(c, first, n, cfg, removed, stats);
+}
 int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
                          const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
   if (!L) return FLIMO_ERR_INVALID;

@@ -563,6 +563,27 @@ int Mapper::keypoints(size_t first, size_t n, const flimo_keypoint_cfg& cfg, std
                              (cnt && n) ? cnt->data() : nullptr, count);
 }
 
+// Euclidean clusters of the map's stored points (an insert, a crop or a carve on the worker thread ends first)
+int Mapper::clusters(size_t first, size_t n, const flimo_cluster_cfg& cfg, std::vector<int32_t>* label, std::vector<int32_t>* size,
+                     std::vector<unsigned char>* mask, flimo_cluster_stats* stats) {
+  sync();
+  if (label) label->clear();
+  if (size) size->clear();
+  if (mask) mask->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (first > flimo_map_size(ctx_) || n > flimo_map_size(ctx_) - first) return FLIMO_ERR_INVALID;
+  if (label) label->assign(n, -1);
+  if (size) size->assign(n, 0);
+  if (mask) mask->assign(n, 0);
+  return flimo_map_clusters(ctx_, first, n, &cfg, (label && n) ? label->data() : nullptr, (size && n) ? size->data() : nullptr,
+                            (mask && n) ? mask->data() : nullptr, stats);
+}
+int Mapper::remove_clusters(size_t first, size_t n, const flimo_cluster_cfg& cfg, size_t* removed, flimo_cluster_stats* stats) {
+  sync();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  return flimo_map_remove_clusters(ctx_, first, n, &cfg, removed, stats);
+}
+
 // fitness of the resident scan at pose hypotheses (an insert or a crop on the worker thread ends first)
 int Mapper::fitness(const double* x26, size_t np, float max_dist, std::vector<int32_t>& inliers, std::vector<double>& sum_sqd,
                     std::vector<float>* nn_sqd, std::vector<int32_t>* nn_idx) {

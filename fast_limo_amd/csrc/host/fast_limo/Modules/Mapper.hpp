@@ -74,6 +74,14 @@ class fast_limo::Mapper {
   // cnt [n]; count (may be null): the ones of the mask.  Changes nothing.  Returns a FLIMO_* code.
   int keypoints(size_t first, size_t n, const flimo_keypoint_cfg& cfg, std::vector<unsigned char>& mask, std::vector<double>* saliency = nullptr,
                 std::vector<int32_t>* cnt = nullptr, size_t* count = nullptr);
+  // The Euclidean clusters of the stored points (flimo_map_clusters: pcl::EuclideanClusterExtraction), for the stored points
+  // first .. first + n - 1: where a vector is given label [n] (the smallest insertion index of the point's component), size [n],
+  // mask [n] (1 = its component is selected by min_size / max_size); stats (may be null).  Changes nothing.  Returns a FLIMO_* code.
+  int clusters(size_t first, size_t n, const flimo_cluster_cfg& cfg, std::vector<int32_t>* label, std::vector<int32_t>* size = nullptr,
+               std::vector<unsigned char>* mask = nullptr, flimo_cluster_stats* stats = nullptr);
+  // ... and forget the points of the range in selected components (flimo_map_remove_clusters); afterwards the map is as after
+  // crop_box.  As remove_outliers: it runs at once and is not queued.  removed / stats may be null.  Returns a FLIMO_* code.
+  int remove_clusters(size_t first, size_t n, const flimo_cluster_cfg& cfg, size_t* removed = nullptr, flimo_cluster_stats* stats = nullptr);
   // octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the GPU map (flimo_radius_search).  The reference's Mapper hides
   // its octree, so this is an addition: the stored points with (p - query).squaredNorm() < radius * radius (strict, float32), in
   // ascending order of (distance, insertion index) -- the reference's traversal order is not reproduced.  As the template

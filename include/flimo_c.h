@@ -370,6 +370,58 @@ int flimo_map_keypoints(flimo_ctx* ctx, size_t first, size_t n, const flimo_keyp
                         unsigned char* mask /* [n], may be NULL */, double* saliency /* [n], may be NULL */,
                         int32_t* cnt /* [n], may be NULL */, size_t* count /* may be NULL */);
 
+/* ---- Euclidean clusters of the stored points: pcl::EuclideanClusterExtraction over the map -- which stored points belong
+ * together.  Cleaning (forget every component of fewer than m points: the tight blob flimo_map_outliers cannot see), objects (the
+ * index lists a tracker starts from), segments for relocalisation ----
+ * The neighbour lists never leave the GPU: one walk of each point's ball ends in a lock-free union-find on the device.
+ *
+ * Definition (tests/clusters_common.py restates it in numpy):
+ *  - the vertices are the N stored points in insertion order: the order flimo_map_points returns and flimo_knn_k indexes.
+ *  - {i, j}, i != j, is an edge iff sqdist3(p_i, p_j) < tol * tol: strict, all float32; sqdist3 = dx*dx + (dy*dy + dz*dz),
+ *    uncontracted; tol * tol one float32 product.  flimo_radius_search's predicate with a stored point as the query; symmetric bit for
+ *    bit (a - b and b - a differ by sign only).
+ *  - tol == 0: no edges; every point, exact duplicates included, is its own cluster.  With tol > 0 exact duplicates share a cluster.
+ *  - a cluster is a connected component of that graph over the WHOLE map, whatever the range.
+ *  - label[i] = the smallest insertion index in the component of stored point first + i: unique, so the way it is computed cannot
+ *    show.  size[i] = that component's number of stored points.
+ *  - selection: a component is SELECTED iff min_size <= size and (max_size == 0 or size <= max_size); max_size == 0 means no upper
+ *    bound.  mask[i] = 1 iff the component of point first + i is selected, 0 otherwise.
+ *  - stats: n = points of the range; clusters, largest, sel_clusters = components, points of the largest one and selected components
+ *    of the WHOLE map; sel_points = ones of the mask (range only).
+ * Every output is an integer with one correct value: nothing depends on the chunking, the cell size, the range form, the order in
+ * which edges are met or the path of the walk.  PCL's "report clusters within [min, max]" is the same two fields; dropping debris
+ * is flimo_map_remove_clusters with min_size = 1, max_size = m - 1.
+ * Cost: the components are formed for the whole map whatever the range, nothing is kept between calls; device scratch is 8 B a
+ * stored point, 1 B a point of the range and 4 B each for label and size where they are asked for. */
+typedef struct flimo_cluster_cfg {
+  float tol;       /* two points closer than this (strict, float32) are joined; finite, >= 0 */
+  int   min_size;  /* selected: min_size <= size ...; >= 0 */
+  int   max_size;  /* ... <= max_size; 0: no upper bound; otherwise >= min_size */
+} flimo_cluster_cfg;
+typedef struct flimo_cluster_stats {
+  uint64_t n;            /* points of the range */
+  uint64_t clusters;     /* components of the whole map */
+  uint64_t largest;      /* points of the largest component */
+  uint64_t sel_clusters; /* selected components of the whole map */
+  uint64_t sel_points;   /* ones of the mask (range only) */
+} flimo_cluster_stats;
+/* label / size / mask [n] and *stats over the stored points first .. first + n - 1; every output may be NULL.  Changes nothing: not
+ * the map, not the scan, not the bits of a later pass.  n = 0 (also on an empty map, first = 0): FLIMO_OK, stats.n and
+ * stats.sel_points 0, the three whole-map fields still filled. */
+int flimo_map_clusters(flimo_ctx* ctx, size_t first, size_t n, const flimo_cluster_cfg* cfg, int32_t* label, int32_t* size,
+                       unsigned char* mask, flimo_cluster_stats* stats);
+/* Forgets the points OF THE RANGE whose mask is 1 (a range that cuts a component removes only the members inside it) and keeps the
+ * rest in insertion order, in the one ordered compaction pass flimo_map_remove_outliers uses.  Afterwards everything is as
+ * flimo_map_crop_box documents: the map is clear() + initialize(kept), insertion indices are renumbered, flimo_map_last_time is
+ * untouched.  *removed (may be NULL) receives how many points went (= stats.sel_points), *stats (may be NULL) the predicate's,
+ * taken before the removal.  Removing nothing changes nothing; removing everything leaves the map as a crop that removes
+ * everything does.
+ * Both calls: FLIMO_ERR_INVALID -- outputs and map untouched -- for a NULL ctx or cfg, first + n beyond flimo_map_size, tol NaN,
+ * negative or infinite, min_size < 0 or max_size < 0, 0 < max_size < min_size; FLIMO_ERR_TOO_LARGE for a map of 2^31 points or
+ * more.  Same calling rules as flimo_map_crop_box: no pass of this context in flight. */
+int flimo_map_remove_clusters(flimo_ctx* ctx, size_t first, size_t n, const flimo_cluster_cfg* cfg, size_t* removed,
+                              flimo_cluster_stats* stats);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

@@ -136,6 +136,14 @@ int    flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh
  * does not use it. */
 int    flimo_loc_map_keypoints(flimo_loc* L, size_t first, size_t n, const flimo_keypoint_cfg* cfg, unsigned char* mask, double* saliency,
                                int32_t* cnt, size_t* count);
+/* Euclidean clusters of the Localizer's stored points: flimo_map_clusters / flimo_map_remove_clusters (include/flimo_c.h: same
+ * arguments, same results, same error codes) on the map's context, after an insert, a crop or a carve still running behind the
+ * last sweep has ended.  A Localizer that has no map yet answers like an empty one (first = n = 0: every count 0; any other range
+ * lies beyond it).  There is no policy that calls them: a whole-map relayout belongs on the caller's schedule, as for the outliers. */
+int    flimo_loc_map_clusters(flimo_loc* L, size_t first, size_t n, const flimo_cluster_cfg* cfg, int32_t* label, int32_t* size,
+                              unsigned char* mask, flimo_cluster_stats* stats);
+int    flimo_loc_map_remove_clusters(flimo_loc* L, size_t first, size_t n, const flimo_cluster_cfg* cfg, size_t* removed,
+                                     flimo_cluster_stats* stats);
 /* Pose hypotheses from point correspondences: flimo_corr_poses (include/flimo_c.h: same arguments, same results, same error
  * codes) on the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  Neither the map
  * nor the resident scan is read; a Localizer that has no context yet creates it.  The Localizer's own update does not use it. */
