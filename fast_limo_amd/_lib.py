@@ -249,6 +249,68 @@ def corr_call(call, src, dst, tri, want, cfg):
     return out
 
 
+class PlaneCfg(C.Structure):
+    """flimo_plane_cfg (include/flimo_c.h)."""
+    _fields_ = [("dist", C.c_float), ("min_edge", C.c_float), ("min_sin", C.c_float), ("axis", C.c_float * 3), ("min_cos", C.c_float)]
+
+
+class PlaneSel(C.Structure):
+    """flimo_plane_sel (include/flimo_c.h)."""
+    _fields_ = [("normal", C.c_float * 3), ("anchor", C.c_float * 3), ("dist", C.c_float), ("side", C.c_int)]
+
+
+PLANE_OK, PLANE_DEGENERATE, PLANE_REJECTED = 0, 1, 2      # FLIMO_PLANE_*: the status of a hypothesis
+PLANE_SLAB = 8192      # FLIMO_PLANE_SLAB
+
+
+def plane_cfg(dist=0.05, min_edge=0.0, min_sin=0.0, axis=(0.0, 0.0, 1.0), min_cos=0.0) -> PlaneCfg:
+    """A 5 cm gate unless told otherwise: no shortest edge, no collinearity test, no axis constraint."""
+    ax = np.asarray(axis, np.float32).reshape(3)
+    return PlaneCfg(float(dist), float(min_edge), float(min_sin), (C.c_float * 3)(*[float(v) for v in ax]), float(min_cos))
+
+
+def plane_sel(normal, anchor, dist=0.05, side=0) -> PlaneSel:
+    """The plane of float32 ``normal`` through ``anchor`` with the gate ``dist``; side 0: |t| < dist, -1: t < dist, +1: t > -dist."""
+    nf = np.asarray(normal, np.float32).reshape(3)
+    an = np.asarray(anchor, np.float32).reshape(3)
+    return PlaneSel((C.c_float * 3)(*[float(v) for v in nf]), (C.c_float * 3)(*[float(v) for v in an]), float(dist), int(side))
+
+
+def _as_plane_sel(sel, kw):
+    if isinstance(sel, PlaneSel):
+        if kw:
+            raise ValueError("plane: give a PlaneSel or the fields of plane_sel, not both")
+        return sel
+    if sel is not None:
+        raise ValueError("plane: sel must be a PlaneSel")
+    return plane_sel(**kw)
+
+
+def planes_call(call, tri, want, cfg):
+    """The output arrays of flimo_map_planes / flimo_loc_map_planes (``call`` takes: tri, nh, cfg, status, inliers, sum_sq, plane) as
+    a dict with "status", "inliers", "sum_sq" and, named in ``want``, "plane" [nh, 4]; shared with ``api.Localizer``."""
+    unknown = set(want) - {"plane"}
+    if unknown:
+        raise ValueError(f"map_planes: unknown outputs {sorted(unknown)}")
+    t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+    nh = t.shape[0]
+    k = plane_cfg(**cfg)
+    out = {"status": np.zeros(nh, np.int32), "inliers": np.zeros(nh, np.int32), "sum_sq": np.zeros(nh, np.float64)}
+    if "plane" in want:
+        out["plane"] = np.full((nh, 4), np.nan)
+    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(_NONE))
+    call(ptr(t), nh, C.byref(k), ptr(out["status"]), ptr(out["inliers"]), ptr(out["sum_sq"]), ptr(out.get("plane")))
+    return out
+
+
+def plane_mask_call(call, n, sel, want_mask):
+    """flimo_map_plane_mask / flimo_loc_map_plane_mask (``call`` takes: sel, mask, count): (mask [n] bool or None, count)."""
+    mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+    count = C.c_size_t(0)
+    call(C.byref(sel), mask.ctypes.data if want_mask else None, C.byref(count))
+    return (mask[:n].astype(bool) if want_mask else None), int(count.value)
+
+
 class CorrGraphCfg(C.Structure):
     """flimo_corr_graph_cfg (include/flimo_c.h)."""
     _fields_ = [("tol", C.c_float), ("min_edge", C.c_float), ("edge_sim", C.c_float)]
@@ -331,7 +393,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_clusters", "flimo_map_remove_clusters", "flimo_set_cluster_chunk", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_clusters", "flimo_map_remove_clusters", "flimo_set_cluster_chunk", "flimo_map_planes", "flimo_plane_solve_host", "flimo_map_plane_mask", "flimo_map_remove_plane", "flimo_set_plane_chunk", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_corr_graph", "flimo_corr_compatible_host", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -436,6 +498,11 @@ def load_hip():
     L.flimo_map_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(ClusterCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClusterStats)]
     L.flimo_map_remove_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(ClusterCfg), C.POINTER(C.c_size_t), C.POINTER(ClusterStats)]
     L.flimo_set_cluster_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_map_planes.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(PlaneCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_plane_solve_host.argtypes = [C.c_void_p, C.POINTER(PlaneCfg), C.c_void_p, C.c_void_p]
+    L.flimo_map_plane_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PlaneSel), C.c_void_p, C.POINTER(C.c_size_t)]
+    L.flimo_map_remove_plane.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PlaneSel), C.POINTER(C.c_size_t)]
+    L.flimo_set_plane_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
     L.flimo_map_last_time.argtypes = [vp]
@@ -710,6 +777,36 @@ class HipCtx:
     def set_cluster_chunk(self, n):
         """Points per link launch of ``map_clusters`` / ``map_remove_clusters`` (flimo_set_cluster_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_cluster_chunk(self._h, int(n)))
+
+    def map_planes(self, tri, want=("plane",), **cfg):
+        """RANSAC plane hypotheses over the stored points -- flimo_map_planes.  ``tri`` [nh, 3] int32: the samples, three insertion
+        indices each (``api.corr_triplets(map_size, nh, seed)`` draws them); ``cfg``: the fields of ``plane_cfg`` (dist, min_edge,
+        min_sin, axis, min_cos).  Returns a dict: ``status`` [nh] (PLANE_OK / PLANE_DEGENERATE / PLANE_REJECTED), ``inliers`` [nh]
+        over ALL stored points, ``sum_sq`` [nh] float64 and, named in ``want``, ``plane`` [nh, 4] float64 (nx ny nz d; NaN unless
+        OK).  Changes nothing.  ``api.plane_consensus`` samples, calls and ranks."""
+        return planes_call(lambda *a: self._chk(self._L.flimo_map_planes(self._h, *a)), tri, want, cfg)
+
+    def map_plane_mask(self, sel=None, first=0, n=None, want_mask=True, **kw):
+        """The stored points first .. first + n - 1 against one plane -- flimo_map_plane_mask.  ``sel``: a ``PlaneSel``, or its
+        fields as keywords (normal, anchor, dist, side).  Returns (mask [n] bool or None, count).  Changes nothing."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        sel = _as_plane_sel(sel, kw)
+        return plane_mask_call(lambda *a: self._chk(self._L.flimo_map_plane_mask(self._h, first, n, *a)), n, sel, want_mask)
+
+    def map_remove_plane(self, sel=None, first=0, n=None, **kw):
+        """Forget the points of the range whose ``map_plane_mask`` is set -- flimo_map_remove_plane; afterwards the map is as after
+        ``map_crop_box``.  Returns the number of points removed."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        sel = _as_plane_sel(sel, kw)
+        removed = C.c_size_t(0)
+        self._chk(self._L.flimo_map_remove_plane(self._h, first, n, C.byref(sel), C.byref(removed)))
+        return int(removed.value)
+
+    def set_plane_chunk(self, n):
+        """Hypotheses per chunk of ``map_planes`` (flimo_set_plane_chunk; 0: the default of 2^10)."""
+        self._chk(self._L.flimo_set_plane_chunk(self._h, int(n)))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_clusters", "flimo_loc_map_remove_clusters", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_clusters", "flimo_loc_map_remove_clusters", "flimo_loc_map_planes", "flimo_loc_map_plane_mask", "flimo_loc_map_remove_plane", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -172,6 +172,9 @@ def load_host():
                                          C.POINTER(_lib.ClusterStats)]
     L.flimo_loc_map_remove_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.ClusterCfg), C.POINTER(C.c_size_t),
                                                 C.POINTER(_lib.ClusterStats)]
+    L.flimo_loc_map_planes.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(_lib.PlaneCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flimo_loc_map_plane_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.PlaneSel), C.c_void_p, C.POINTER(C.c_size_t)]
+    L.flimo_loc_map_remove_plane.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.PlaneSel), C.POINTER(C.c_size_t)]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -452,6 +455,29 @@ class Localizer:
         self._outliers_chk(self._L.flimo_loc_map_remove_clusters(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
                            "flimo_loc_map_remove_clusters")
         return int(removed.value), st.as_dict()
+
+    def map_planes(self, tri, want=("plane",), **cfg):
+        """RANSAC plane hypotheses over the map's stored points (flimo_loc_map_planes), as ``HipCtx.map_planes``.  Waits for an
+        insert, a crop or a carve still running; changes nothing.  No policy calls it."""
+        return _lib.planes_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_planes(self._h, *a), "flimo_loc_map_planes"), tri, want, cfg)
+
+    def map_plane_mask(self, sel=None, first=0, n=None, want_mask=True, **kw):
+        """The stored points of a range against one plane (flimo_loc_map_plane_mask), as ``HipCtx.map_plane_mask``: (mask, count)."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        sel = _lib._as_plane_sel(sel, kw)
+        return _lib.plane_mask_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_plane_mask(self._h, first, n, *a), "flimo_loc_map_plane_mask"),
+                                    n, sel, want_mask)
+
+    def map_remove_plane(self, sel=None, first=0, n=None, **kw):
+        """Forget the points of the range inside one plane's gate (flimo_loc_map_remove_plane), as ``HipCtx.map_remove_plane``: the
+        number of points removed."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        sel = _lib._as_plane_sel(sel, kw)
+        removed = C.c_size_t(0)
+        self._outliers_chk(self._L.flimo_loc_map_remove_plane(self._h, first, n, C.byref(sel), C.byref(removed)), "flimo_loc_map_remove_plane")
+        return int(removed.value)
 
     def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
         """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,
@@ -787,6 +813,43 @@ def corr_consensus(obj, src, dst, nh, seed=0, top=8, x26_like=None, **cfg):
     x = np.tile(base, (best.size, 1))
     x[:, 0:7] = out["pose"][best]
     return dict(x26=x, inliers=out["inliers"][best], sum_sqd=out["sum_sqd"][best], cost=cost[order], index=best.astype(np.int64),
+                tri=tri[best], survivors=int(ok.size))
+
+
+def plane_solve_host(p3, **cfg):
+    """The plane of ONE triplet of points on the host (flimo_plane_solve_host: the function the solve kernel of ``map_planes``
+    calls): ``p3`` [3, 3] = the points a, b, c; ``cfg``: the fields of ``_lib.plane_cfg``.  Returns (status, plane4 [4] float64:
+    nx ny nz d, nf [3] float32: the normal the inlier test uses); NaN unless PLANE_OK.  It sees points, not indices."""
+    L = _lib.load_hip()
+    p = np.ascontiguousarray(p3, dtype=np.float32).reshape(9)
+    k = _lib.plane_cfg(**cfg)
+    plane = np.zeros(4)
+    nf = np.zeros(3, np.float32)
+    rc = L.flimo_plane_solve_host(p.ctypes.data, C.byref(k), plane.ctypes.data, nf.ctypes.data)
+    if rc < 0:
+        raise FlimoError(f"flimo_plane_solve_host failed ({rc})")
+    return int(rc), plane, nf
+
+
+def plane_consensus(obj, nh, seed=0, top=4, **cfg):
+    """The dominant planes of the stored points of ``obj`` (a ``HipCtx`` or a ``Localizer``): ``nh`` samples of
+    ``corr_triplets(map_size, nh, seed)`` through ``obj.map_planes`` (``cfg``: the fields of ``_lib.plane_cfg``), the OK hypotheses
+    ranked by ``inliers`` descending, then ``sum_sq`` ascending, then index.  Returns a dict of the best ``top``: plane [k, 4], sel
+    (a list of ``PlaneSel`` ready for ``map_plane_mask`` / ``map_remove_plane``: the float32 normal, the sample's first point, the
+    same dist, side 0), inliers, sum_sq, index [k] (the row of the hypothesis in tri), tri [k, 3]; and survivors: the number of OK
+    hypotheses.  The ranking is RANSAC's; a least-squares refit of the winner is the caller's."""
+    n_map = int(obj.map_size())
+    tri = corr_triplets(n_map, nh, seed)
+    out = obj.map_planes(tri, want=("plane",), **cfg)
+    ok = np.nonzero(out["status"] == _lib.PLANE_OK)[0]
+    order = np.lexsort((ok, out["sum_sq"][ok], -out["inliers"][ok].astype(np.int64)))[:max(int(top), 0)]
+    best = ok[order]
+    dist = float(_lib.plane_cfg(**cfg).dist)
+    sel = []
+    if best.size:
+        pts = np.asarray(getattr(obj, "hip", obj).map_points(), np.float32).reshape(-1, 3)      # (the anchors: the samples' first points)
+        sel = [_lib.plane_sel(out["plane"][j, 0:3].astype(np.float32), pts[tri[j, 0]], dist, 0) for j in best]
+    return dict(plane=out["plane"][best], sel=sel, inliers=out["inliers"][best], sum_sq=out["sum_sq"][best], index=best.astype(np.int64),
                 tri=tri[best], survivors=int(ok.size))
 
 

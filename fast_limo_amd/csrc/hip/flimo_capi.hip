@@ -24,6 +24,7 @@
 #include "flimo_math.h"
 #include "flimo_pose.h"
 #include "flimo_corr.h"
+#include "flimo_plane.h"
 #include "flimo_desc.h"
 #include "flimo_chain.h"
 #include "flimo_ieskf.h"
@@ -56,6 +57,7 @@ struct flimo_ctx {
   uint64_t carves = 0, carve_removed = 0; // flimo_map_carve: the same
   uint64_t outlier_removals = 0, outlier_removed = 0;   // flimo_map_remove_outliers: the same
   uint64_t cluster_removals = 0, cluster_removed = 0;   // flimo_map_remove_clusters: the same
+  uint64_t plane_removals = 0, plane_removed = 0;       // flimo_map_remove_plane: the same
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
@@ -63,6 +65,7 @@ struct flimo_ctx {
   size_t fpfh_chunk = (size_t)1 << 20;      // points per search launch of flimo_map_fpfh (flimo_set_fpfh_chunk)
   size_t keypoints_chunk = (size_t)1 << 20; // points per search launch of flimo_map_keypoints (flimo_set_keypoints_chunk)
   size_t cluster_chunk = (size_t)1 << 20;   // points per link launch of flimo_map_clusters (flimo_set_cluster_chunk)
+  size_t plane_chunk = (size_t)1 << 10;     // hypotheses per chunk of flimo_map_planes (flimo_set_plane_chunk)
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   size_t corr_chunk = (size_t)1 << 16;      // hypotheses per chunk of flimo_corr_poses (flimo_set_corr_chunk)
@@ -1867,6 +1870,149 @@ extern "C" int flimo_set_cluster_chunk(flimo_ctx* c, size_t n) {
   if (!c) return FLIMO_ERR_INVALID;
   c->cluster_chunk = n ? n : (size_t)1 << 20;
   return FLIMO_OK;
+}
+
+// ---- RANSAC planes of the stored points (pcl::SACSegmentation's sample, model and count; ExtractIndices for the removal) ----------
+// kernels: flimo_plane.hip.  The triplets go up once; the hypotheses run in chunks of c->plane_chunk: per chunk the solve, the count
+// over every stored point and the finish are launched, into result arrays that hold all nh, and nothing waits between chunks (the
+// chunk's scratch is re-used in stream order); the results come back behind the last chunk, one wait.  Device scratch: chunk x
+// slabs x 12 B of partials and 36 B a hypothesis of the chunk (record, survivor entry), 60 B a hypothesis of the call (triplet,
+// status, inliers, sum, plane).  Reads d_map_raw alone: no index is needed, but a map never goes without one (ensure_index).
+static bool plane_cfg_ok(const flimo_plane_cfg* k) {
+  if (std::isnan(k->dist) || k->dist < 0.f || std::isnan(k->min_edge) || k->min_edge < 0.f) return false;
+  if (std::isnan(k->min_sin) || k->min_sin < 0.f || k->min_sin > 1.f || std::isnan(k->min_cos) || k->min_cos < 0.f || k->min_cos > 1.f) return false;
+  if (k->min_cos > 0.f && !(std::isfinite(k->axis[0]) && std::isfinite(k->axis[1]) && std::isfinite(k->axis[2]))) return false;
+  return true;
+}
+extern "C" int flimo_map_planes(flimo_ctx* c, const int32_t* tri, size_t nh, const flimo_plane_cfg* cfg, int32_t* status, int32_t* inliers,
+                                double* sum_sq, double* plane) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!cfg || !status || !inliers || !sum_sq || (nh > 0 && !tri))
+    return fail(c, FLIMO_ERR_INVALID, "map planes: null tri / cfg / status / inliers / sum_sq");
+  if (!plane_cfg_ok(cfg))
+    return fail(c, FLIMO_ERR_INVALID, "map planes: dist and min_edge must be >= 0 (dist may be INFINITY), min_sin and min_cos in 0..1, the axis finite");
+  const size_t N = c->map_n;
+  if (N >= 0x80000000ull || nh >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map planes: the map and nh must be below 2^31");
+  if (nh == 0) return FLIMO_OK;
+  for (size_t i = 0; i < 3 * nh; i++)
+    if (tri[i] < 0 || (size_t)tri[i] >= N)
+      return fail(c, FLIMO_ERR_INVALID, "map planes: index %d of hypothesis %zu is outside [0, %zu)", (int)tri[i], i / 3, N);
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  ctx_enter(c);
+  const size_t slabs = plane_slabs((unsigned)N);
+  // hypotheses of a chunk: the grid's second dimension and 2^26 partials bound it
+  size_t k = std::min(nh, std::max<size_t>(c->plane_chunk, 1));
+  k = std::min(k, std::min<size_t>((size_t)1 << 16, std::max<size_t>(((size_t)1 << 26) / slabs, 1)));
+  DevScratch d;
+  int32_t* d_tri = d.get<int32_t>(3 * nh);
+  int32_t* d_status = d.get<int32_t>(nh);
+  int32_t* d_inliers = d.get<int32_t>(nh);
+  double* d_sum = d.get<double>(nh);
+  double* d_plane = d.get<double>(4 * nh);
+  float4* d_rec = d.get<float4>(2 * k);
+  int32_t* d_surv = d.get<int32_t>(k);
+  unsigned* d_nsurv = d.get<unsigned>(1);
+  int32_t* d_pcnt = d.get<int32_t>(k * slabs);
+  double* d_psum = d.get<double>(k * slabs);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(d_tri, tri, 3 * nh * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  for (size_t a = 0; a < nh; a += k) {
+    const size_t ka = std::min(k, nh - a);
+    HIPCHK(c, launch_plane_chunk(c->stream, c->d_map_raw, (unsigned)N, d_tri + 3 * a, (unsigned)ka, cfg->dist, cfg->min_edge, cfg->min_sin, cfg->axis,
+                                 cfg->min_cos, d_status + a, d_plane + 4 * a, d_inliers + a, d_sum + a, d_rec, d_surv, d_nsurv, d_pcnt, d_psum));
+  }
+  // (into the stage first: the caller's arrays stay untouched if anything above or below fails)
+  const size_t per = sizeof(int32_t) * 2 + sizeof(double) * (plane ? 5 : 1);
+  { const int rc = ensure_stage(c, nh * per); if (rc) return rc; }
+  double* h_sum = (double*)c->h_stage;
+  double* h_plane = h_sum + nh;
+  int32_t* h_status = (int32_t*)(h_sum + nh * (plane ? 5 : 1));
+  int32_t* h_inliers = h_status + nh;
+  HIPCHK(c, hipMemcpyAsync(h_sum, d_sum, nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (plane) HIPCHK(c, hipMemcpyAsync(h_plane, d_plane, 4 * nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h_status, d_status, nh * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h_inliers, d_inliers, nh * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(sum_sq, h_sum, nh * sizeof(double));
+  if (plane) memcpy(plane, h_plane, 4 * nh * sizeof(double));
+  memcpy(status, h_status, nh * sizeof(int32_t));
+  memcpy(inliers, h_inliers, nh * sizeof(int32_t));
+  return FLIMO_OK;
+}
+extern "C" int flimo_plane_solve_host(const float p3[9], const flimo_plane_cfg* cfg, double plane4[4], float nf[3]) {
+  if (!p3 || !cfg || !plane4 || !nf || !plane_cfg_ok(cfg)) return FLIMO_ERR_INVALID;
+  return plane_solve(p3, cfg->min_edge, cfg->min_sin, cfg->axis, cfg->min_cos, plane4, nf);
+}
+extern "C" int flimo_set_plane_chunk(flimo_ctx* c, size_t n) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->plane_chunk = n ? n : (size_t)1 << 10;
+  return FLIMO_OK;
+}
+static int plane_sel_check(flimo_ctx* c, size_t first, size_t n, const flimo_plane_sel* sel, const char* what) {
+  if (!sel) return fail(c, FLIMO_ERR_INVALID, "%s: null sel", what);
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(sel->normal[a]) || !std::isfinite(sel->anchor[a])) return fail(c, FLIMO_ERR_INVALID, "%s: normal and anchor must be finite", what);
+  if (std::isnan(sel->dist) || sel->dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: dist must be >= 0 or INFINITY", what);
+  if (sel->side < -1 || sel->side > 1) return fail(c, FLIMO_ERR_INVALID, "%s: side must be -1, 0 or 1", what);
+  if (first > c->map_n || n > c->map_n - first)
+    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
+  if (c->map_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the map must hold fewer than 2^31 points", what);
+  return FLIMO_OK;
+}
+// the mask of the range on the device (d_mask [n], may be null) and its ones; arguments checked, n > 0; ends synchronised
+static int plane_mask_device(flimo_ctx* c, size_t first, size_t n, const flimo_plane_sel& sel, unsigned char* d_mask, unsigned* d_count, size_t* count) {
+  HIPCHK(c, hipMemsetAsync(d_count, 0, sizeof(unsigned), c->stream));
+  HIPCHK(c, launch_plane_mask(c->stream, c->d_map_raw, (unsigned)first, (unsigned)n, sel.normal, sel.anchor, sel.dist, sel.side, d_mask, d_count));
+  unsigned w = 0;
+  HIPCHK(c, hipMemcpyAsync(&w, d_count, sizeof w, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (w > n) return fail(c, FLIMO_ERR_HIP, "plane mask: marked %u of %zu points", w, n);
+  *count = w;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_plane_mask(flimo_ctx* c, size_t first, size_t n, const flimo_plane_sel* sel, unsigned char* mask, size_t* count) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = plane_sel_check(c, first, n, sel, "plane mask"); if (rc) return rc; }
+  if (n == 0) { if (count) *count = 0; return FLIMO_OK; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  ctx_enter(c);
+  DevScratch d;
+  unsigned char* d_mask = mask ? d.get<unsigned char>(n) : nullptr;
+  unsigned* d_count = d.get<unsigned>(1);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  size_t ones = 0;
+  { const int rc = plane_mask_device(c, first, n, *sel, d_mask, d_count, &ones); if (rc) return rc; }
+  if (mask) {
+    HIPCHK(c, hipMemcpyAsync(mask, d_mask, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (count) *count = ones;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_remove_plane(flimo_ctx* c, size_t first, size_t n, const flimo_plane_sel* sel, size_t* removed) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = plane_sel_check(c, first, n, sel, "remove plane"); if (rc) return rc; }
+  if (n == 0) { if (removed) *removed = 0; return FLIMO_OK; }
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  ctx_enter(c);
+  DevScratch d;
+  unsigned char* d_mask = d.get<unsigned char>(n);
+  unsigned* d_count = d.get<unsigned>(1);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  size_t ones = 0;
+  { const int rc = plane_mask_device(c, first, n, *sel, d_mask, d_count, &ones); if (rc) return rc; }
+  if (removed) *removed = 0;
+  if (ones == 0) return FLIMO_OK;                      // removing nothing changes nothing
+  const size_t n_old = c->map_n;
+  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
+  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  size_t kept = 0;
+  float bb[6];
+  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d_mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
+  if (kept != n_old - ones) return fail(c, FLIMO_ERR_HIP, "remove plane: the compaction kept %zu of %zu points, %zu marked", kept, n_old, ones);
+  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->plane_removals, &c->plane_removed, removed, "remove plane");
 }
 
 // ---- scan -------------------------------------------------------------------------------------

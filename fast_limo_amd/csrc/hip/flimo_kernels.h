@@ -382,6 +382,19 @@ hipError_t launch_corr_adjacency(hipStream_t st, const float* src, const float* 
                                  uint64_t* adj, int32_t* degree, int32_t* c0);
 hipError_t launch_corr_core_rounds(hipStream_t st, const uint64_t* adj, unsigned m, int32_t* c[2], int* cur, unsigned* flags, int rounds);
 
+// flimo_plane.hip -- RANSAC planes of the stored points (flimo_map_planes, flimo_c.h) for a chunk of k triplets tri [k][3] (every
+// index already checked to lie in [0, N)) over the N > 0 stored points map_raw: the solve per hypothesis (status [k], plane [k][4];
+// NaN unless OK), then for the OK ones the count over ALL stored points in slabs of PLANE_SLAB (flimo_plane.h) and the finish
+// (inliers / sum_sq [k], 0 for the others).  Three launches, no wait.  Scratch: rec ([k][2] float4), surv ([k]), nsurv, part_cnt /
+// part_sum ([plane_slabs(N)][k]).
+hipError_t launch_plane_chunk(hipStream_t st, const float4* map_raw, unsigned N, const int32_t* tri, unsigned k, float dist, float min_edge,
+                              float min_sin, const float axis[3], float min_cos, int32_t* status, double* plane, int32_t* inliers,
+                              double* sum_sq, float4* rec, int32_t* surv, unsigned* nsurv, int32_t* part_cnt, double* part_sum);
+// mask [n] (may be null) of the stored points first .. first + n - 1 against one plane (flimo_map_plane_mask); *count (zeroed by the
+// caller) += the ones
+hipError_t launch_plane_mask(hipStream_t st, const float4* map_raw, unsigned first, unsigned n, const float normal[3], const float anchor[3],
+                             float dist, int side, unsigned char* mask, unsigned* count);
+
 // flimo_desc.hip -- nearest descriptors (flimo_desc_match, flimo_c.h).  The resident reference set is two arrays: norm
 // [ceil(nr / 32) * 32] (launch_desc_norms with npad = that; NaN for an excluded row and for the padding) and rt
 // [ceil(nr / 32)][desc_steps(dim)][64], the rows in the MFMA's A-operand layout (launch_desc_pack).  launch_desc_match answers a

@@ -395,6 +395,50 @@ int flimo_loc_map_remove_clusters(flimo_loc* L, size_t first, size_t n, const fl
   }
   return flimo_map_remove_clusters(c, first, n, cfg, removed, stats);
 }
+// no map yet: the answers of an empty one, after the calls' own argument checks
+static bool plane_cfg_valid(const flimo_plane_cfg* k) {
+  if (std::isnan(k->dist) || k->dist < 0.f || std::isnan(k->min_edge) || k->min_edge < 0.f) return false;
+  if (std::isnan(k->min_sin) || k->min_sin < 0.f || k->min_sin > 1.f || std::isnan(k->min_cos) || k->min_cos < 0.f || k->min_cos > 1.f) return false;
+  return !(k->min_cos > 0.f && !(std::isfinite(k->axis[0]) && std::isfinite(k->axis[1]) && std::isfinite(k->axis[2])));
+}
+static int plane_sel_of_no_map(size_t first, size_t n, const flimo_plane_sel* sel) {
+  if (!sel || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(sel->normal[a]) || !std::isfinite(sel->anchor[a])) return FLIMO_ERR_INVALID;
+  if (std::isnan(sel->dist) || sel->dist < 0.f || sel->side < -1 || sel->side > 1) return FLIMO_ERR_INVALID;
+  return FLIMO_OK;
+}
+int flimo_loc_map_planes(flimo_loc* L, const int32_t* tri, size_t nh, const flimo_plane_cfg* cfg, int32_t* status, int32_t* inliers,
+                         double* sum_sq, double* plane) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
+  if (!c) {
+    if (!cfg || !status || !inliers || !sum_sq || !plane_cfg_valid(cfg)) return FLIMO_ERR_INVALID;
+    if (nh >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
+    return nh == 0 ? FLIMO_OK : FLIMO_ERR_INVALID;      // (every index lies outside a map of no points)
+  }
+  return flimo_map_planes(c, tri, nh, cfg, status, inliers, sum_sq, plane);
+}
+int flimo_loc_map_plane_mask(flimo_loc* L, size_t first, size_t n, const flimo_plane_sel* sel, unsigned char* mask, size_t* count) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();
+  if (!c) {
+    const int rc = plane_sel_of_no_map(first, n, sel);
+    if (rc == FLIMO_OK && count) *count = 0;
+    return rc;
+  }
+  return flimo_map_plane_mask(c, first, n, sel, mask, count);
+}
+int flimo_loc_map_remove_plane(flimo_loc* L, size_t first, size_t n, const flimo_plane_sel* sel, size_t* removed) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();
+  if (!c) {
+    const int rc = plane_sel_of_no_map(first, n, sel);
+    if (rc == FLIMO_OK && removed) *removed = 0;
+    return rc;
+  }
+  return flimo_map_remove_plane(c, first, n, sel, removed);
+}
 int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
                          const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
   if (!L) return FLIMO_ERR_INVALID;

@@ -422,6 +422,79 @@ int flimo_map_clusters(flimo_ctx* ctx, size_t first, size_t n, const flimo_clust
 int flimo_map_remove_clusters(flimo_ctx* ctx, size_t first, size_t n, const flimo_cluster_cfg* cfg, size_t* removed,
                               flimo_cluster_stats* stats);
 
+/* ---- RANSAC planes of the stored points: what pcl::SACSegmentation(SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE, SAC_RANSAC)
+ * does per sample, for all of the caller's samples at once against EVERY stored point -- the ground that holds the clusters of an
+ * outdoor map together (find it, flimo_map_remove_plane, then flimo_map_clusters), walls, a table top ----
+ * Nothing of size nh x N exists anywhere and the map never leaves the GPU.
+ *
+ * Definition (tests/planes_common.py restates it in numpy).  Hypothesis j is the triplet (a, b, c) = tri[j] of insertion indices
+ * into the N stored points (the order flimo_map_points returns).  The samples are the caller's, so the call is deterministic.
+ * Steps 1-5 are float64 on the float32 points widened, nothing contracted, exactly the written association;
+ * sq(v) = v.x*v.x + (v.y*v.y + v.z*v.z).
+ *  1. e1 = p_b - p_a, e2 = p_c - p_a, e3 = p_c - p_b.  DEGENERATE if two indices are equal, or if any of sq(e1), sq(e2), sq(e3)
+ *     fails ">= (double)min_edge * (double)min_edge".
+ *  2. cr = e1 x e2, each component y z' - z y' as two products and one subtraction; q = sq(cr).  DEGENERATE unless q > 0.0 and
+ *     q >= s2 * (sq(e1) * sq(e2)), s2 = (double)min_sin * (double)min_sin: the squared sine of the angle at a.  No division.
+ *  3. n = cr / sqrt(q), three divisions.  DEGENERATE if an entry is not finite.
+ *  4. sign: the component of largest magnitude is made positive (equal magnitudes: the lowest axis decides) -- flimo_map_normals'
+ *     rule with no viewpoint.  Negation is exact: (a, b, c) and (a, c, b) give the same bits.
+ *  5. REJECTED if min_cos > 0 and not fabs(n.x*ax + (n.y*ay + n.z*az)) >= (double)min_cos; the axis is used as given, NOT normalised.
+ *  6. otherwise d = -(n.x*a.x + (n.y*a.y + n.z*a.z)), plane[j] = (n, d), nf = (float)n.
+ *  7. the inlier test is float32 and anchored at the sample's first point, so that its precision does not depend on how far the map
+ *     lies from the origin: for stored point i, v = p_i - p_a (three float32 subtractions), t = nf.x*v.x + (nf.y*v.y + nf.z*v.z)
+ *     uncontracted, and i is an inlier iff fabsf(t) < dist.  The three sample points count like any other.
+ *  8. inliers[j] = the exact count over ALL N stored points.
+ *  9. sum_sq[j] = the float64 sum of (double)t * (double)t (exact products) over the inliers, in ONE fixed shape: slab s is the
+ *     points [s * FLIMO_PLANE_SLAB, min(N, (s + 1) * FLIMO_PLANE_SLAB)); within a slab thread T of 256 adds the slab's slots T,
+ *     T + 256, ... in ascending order into a partial that starts at +0.0 (a non-inlier adds nothing); then
+ *     partial[T] += partial[T + o] for o = 128, 64 .. 1; then S = ((0.0 + P_0) + P_1) + ... over the slabs in ascending order.
+ * A hypothesis that is not OK has inliers 0, sum_sq +0.0 and plane NaN.  No floating-point atomics: the bits of a hypothesis's
+ * outputs depend on the stored points, its triplet and the cfg alone -- not on nh, the other hypotheses, the order of tri, the
+ * chunking (flimo_set_plane_chunk), the cell size or which hypotheses share a workgroup.
+ * Cost: nh x N float32 tests; device scratch is chunk x ceil(N / FLIMO_PLANE_SLAB) x 12 B plus 36 B a hypothesis of the chunk and
+ * 60 B a hypothesis of the call. */
+#define FLIMO_PLANE_OK 0
+#define FLIMO_PLANE_DEGENERATE 1
+#define FLIMO_PLANE_REJECTED 2
+#define FLIMO_PLANE_SLAB 8192        /* part of the contract: the sum's shape */
+typedef struct flimo_plane_cfg {
+  float dist;      /* inlier gate [m]: |t| < dist, strict float32; >= 0, INFINITY allowed */
+  float min_edge;  /* >= 0 [m]: a sample triangle with a shorter edge is degenerate */
+  float min_sin;   /* 0..1: sine of the angle at vertex a below this: degenerate (near-collinear samples) */
+  float axis[3];   /* read only when min_cos > 0; used as given, NOT normalised */
+  float min_cos;   /* 0..1; > 0: |n . axis| >= min_cos required (SACMODEL_PERPENDICULAR_PLANE's eps_angle); 0: none */
+} flimo_plane_cfg;
+/* status / inliers / sum_sq [nh] and, where given, plane [nh][4].  Changes nothing: not the map, not the scan, not the bits of a
+ * later pass.  nh == 0: FLIMO_OK.  FLIMO_ERR_INVALID -- outputs untouched -- for a NULL ctx / cfg / status / inliers / sum_sq, a
+ * NULL tri with nh > 0, a cfg field that is NaN or negative, min_sin or min_cos above 1, a non-finite axis with min_cos > 0, a
+ * triplet index outside [0, N) (all are checked before any launch: nh > 0 on an empty map is invalid); FLIMO_ERR_TOO_LARGE for N
+ * or nh >= 2^31.  Same calling rules as flimo_map_clusters: no pass of this context in flight. */
+int flimo_map_planes(flimo_ctx* ctx, const int32_t* tri /* [nh][3] insertion indices */, size_t nh, const flimo_plane_cfg* cfg,
+                     int32_t* status /* [nh] */, int32_t* inliers /* [nh] */, double* sum_sq /* [nh] */,
+                     double* plane /* [nh][4] nx ny nz d, may be NULL */);
+/* Steps 1-6 for one triplet on the host (p3 = the points a, b, c, packed xyz), through the same function the kernel calls: the
+ * status, or FLIMO_ERR_INVALID for a NULL argument or a cfg flimo_map_planes rejects.  plane4 and nf are NaN unless the status is
+ * FLIMO_PLANE_OK.  Needs no context and no device. */
+int flimo_plane_solve_host(const float p3[9], const flimo_plane_cfg* cfg, double plane4[4], float nf[3]);
+
+/* The mask of ONE plane and the removal: step 7's arithmetic with nf = sel->normal and p_a = sel->anchor over the stored points
+ * first .. first + n - 1, the compare chosen by side.  With normal = (float)plane[j][0..2], anchor = stored point tri[j][0], the
+ * same dist, side 0 and the whole map, count == inliers[j].  side -1 with the ground's normal is "the ground and everything
+ * beneath it" (multipath ghosts under the road). */
+typedef struct flimo_plane_sel {
+  float normal[3]; float anchor[3]; float dist; int side;   /* side 0: |t| < dist;  -1: t < dist;  +1: t > -dist */
+} flimo_plane_sel;
+/* mask [n] (1 = inside) and *count (the ones); changes nothing.  n == 0 (also on an empty map): FLIMO_OK, *count = 0. */
+int flimo_map_plane_mask(flimo_ctx* ctx, size_t first, size_t n, const flimo_plane_sel* sel,
+                         unsigned char* mask /* [n], may be NULL */, size_t* count /* may be NULL */);
+/* Forgets the points of the range whose mask is 1 and keeps the rest in insertion order, in the one ordered compaction pass
+ * flimo_map_remove_clusters uses.  Afterwards everything is as flimo_map_crop_box documents: the map is clear() +
+ * initialize(kept), insertion indices are renumbered, flimo_map_last_time is untouched.  *removed (may be NULL) receives how many
+ * points went.  Removing nothing changes nothing; removing everything leaves the map as a crop that removes everything does.
+ * Both calls: FLIMO_ERR_INVALID -- outputs and map untouched -- for a NULL ctx or sel, a non-finite normal or anchor, dist NaN or
+ * negative, side outside -1..1, first + n beyond flimo_map_size; FLIMO_ERR_TOO_LARGE for a map of 2^31 points or more. */
+int flimo_map_remove_plane(flimo_ctx* ctx, size_t first, size_t n, const flimo_plane_sel* sel, size_t* removed);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

@@ -89,6 +89,9 @@ int flimo_set_keypoints_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_map_clusters / flimo_map_remove_clusters walk the stored points' balls in launches of n points (default 2^20; 0 restores
  * it; at most 2^24 are used): the chunk bounds a launch's lanes, not the scratch; equal results whatever the chunk. */
 int flimo_set_cluster_chunk(flimo_ctx* ctx, size_t n);
+/* flimo_map_planes works in chunks of n hypotheses (default 2^10; 0 restores it; at most 2^16 and 2^26 partials are used): the
+ * chunk bounds the partials, ceil(N / FLIMO_PLANE_SLAB) x 12 B a hypothesis, and the records; equal results whatever the chunk. */
+int flimo_set_plane_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_corr_poses works in chunks of n hypotheses (default 2^16; 0 restores it): the chunk bounds the call's device scratch, 136 B
  * a hypothesis (and m floats each where pair_sqd is asked for: then at most 2^26 slots a chunk); equal results whatever the chunk. */
 int flimo_set_corr_chunk(flimo_ctx* ctx, size_t n);

@@ -144,6 +144,14 @@ int    flimo_loc_map_clusters(flimo_loc* L, size_t first, size_t n, const flimo_
                               unsigned char* mask, flimo_cluster_stats* stats);
 int    flimo_loc_map_remove_clusters(flimo_loc* L, size_t first, size_t n, const flimo_cluster_cfg* cfg, size_t* removed,
                                      flimo_cluster_stats* stats);
+/* RANSAC planes of the Localizer's stored points: flimo_map_planes / flimo_map_plane_mask / flimo_map_remove_plane
+ * (include/flimo_c.h: same arguments, same results, same error codes) on the map's context, after an insert, a crop or a carve
+ * still running behind the last sweep has ended.  A Localizer that has no map yet answers like an empty one (nh = 0, first = n = 0:
+ * FLIMO_OK; anything else lies beyond it).  There is no policy that calls them. */
+int    flimo_loc_map_planes(flimo_loc* L, const int32_t* tri, size_t nh, const flimo_plane_cfg* cfg, int32_t* status, int32_t* inliers,
+                            double* sum_sq, double* plane);
+int    flimo_loc_map_plane_mask(flimo_loc* L, size_t first, size_t n, const flimo_plane_sel* sel, unsigned char* mask, size_t* count);
+int    flimo_loc_map_remove_plane(flimo_loc* L, size_t first, size_t n, const flimo_plane_sel* sel, size_t* removed);
 /* Pose hypotheses from point correspondences: flimo_corr_poses (include/flimo_c.h: same arguments, same results, same error
  * codes) on the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  Neither the map
  * nor the resident scan is read; a Localizer that has no context yet creates it.  The Localizer's own update does not use it. */
