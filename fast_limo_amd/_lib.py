@@ -311,6 +311,69 @@ def plane_mask_call(call, n, sel, want_mask):
     return (mask[:n].astype(bool) if want_mask else None), int(count.value)
 
 
+class VoxelCfg(C.Structure):
+    """flimo_voxel_cfg (include/flimo_c.h)."""
+    _fields_ = [("leaf", C.c_float), ("keep", C.c_int), ("max_pts", C.c_int)]
+
+
+class VoxelStats(C.Structure):
+    """flimo_voxel_stats (include/flimo_c.h)."""
+    _fields_ = [("n", C.c_uint64), ("voxels", C.c_uint64), ("largest", C.c_uint64), ("outside", C.c_uint64), ("sel_points", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(n=int(self.n), voxels=int(self.voxels), largest=int(self.largest), outside=int(self.outside),
+                    sel_points=int(self.sel_points))
+
+
+VOXEL_KEEP_FIRST, VOXEL_KEEP_NEAREST = 0, 1      # FLIMO_VOXEL_KEEP_*
+VOXEL_RUN = 64                                   # FLIMO_VOXEL_RUN
+VOXEL_HALF = 1 << 20                             # FLIMO_VOXEL_HALF
+VOXEL_OUTPUTS = (("ijk", np.int32, 3), ("count", np.int32, 1), ("first", np.int32, 1), ("rep", np.int32, 1),
+                 ("centroid", np.float64, 3), ("cov", np.float64, 6))
+
+
+def voxel_cfg(leaf=0.25, keep=VOXEL_KEEP_FIRST, max_pts=1) -> VoxelCfg:
+    """A 25 cm leaf that keeps the oldest point of a voxel unless told otherwise."""
+    return VoxelCfg(float(leaf), int(keep), int(max_pts))
+
+
+def voxels_call(call, cap, want, cfg):
+    """The output arrays of flimo_map_voxels / flimo_loc_map_voxels (``call`` takes: cfg, cap, nv, ijk, count, first, rep, centroid,
+    cov, stats) as a dict with the outputs named in ``want`` (of "ijk", "count", "first", "rep", "centroid", "cov"), "nv" and
+    "stats"; ``cap``: the map's size (no more voxels than points: one call); shared with ``api.Localizer``."""
+    unknown = set(want) - {name for name, _, _ in VOXEL_OUTPUTS}
+    if unknown:
+        raise ValueError(f"map_voxels: unknown outputs {sorted(unknown)}")
+    k = voxel_cfg(**cfg)
+    arr = {name: np.zeros((max(cap, 1), w) if w > 1 else max(cap, 1), dt) for name, dt, w in VOXEL_OUTPUTS if name in want}
+    nv = C.c_size_t(0)
+    st = VoxelStats()
+    ptr = lambda name: arr[name].ctypes.data if name in arr else None
+    call(C.byref(k), cap, C.byref(nv), ptr("ijk"), ptr("count"), ptr("first"), ptr("rep"), ptr("centroid"), ptr("cov"), C.byref(st))
+    out = {name: a[:nv.value].copy() for name, a in arr.items()}
+    out["nv"] = int(nv.value)
+    out["stats"] = st.as_dict()
+    return out
+
+
+def voxel_mask_call(call, n, want, cfg):
+    """flimo_map_voxel_mask / flimo_loc_map_voxel_mask (``call`` takes: cfg, voxel, mask, stats): a dict with the outputs named in
+    ``want`` (of "voxel", "mask") and "stats"."""
+    unknown = set(want) - {"voxel", "mask"}
+    if unknown:
+        raise ValueError(f"map_voxel_mask: unknown outputs {sorted(unknown)}")
+    k = voxel_cfg(**cfg)
+    arr = {name: np.zeros(max(n, 1), dt) for name, dt in (("voxel", np.int32), ("mask", np.uint8)) if name in want}
+    st = VoxelStats()
+    ptr = lambda name: arr[name].ctypes.data if name in arr else None
+    call(C.byref(k), ptr("voxel"), ptr("mask"), C.byref(st))
+    out = {name: a[:n] for name, a in arr.items()}
+    if "mask" in out:
+        out["mask"] = out["mask"].astype(bool)
+    out["stats"] = st.as_dict()
+    return out
+
+
 class CorrGraphCfg(C.Structure):
     """flimo_corr_graph_cfg (include/flimo_c.h)."""
     _fields_ = [("tol", C.c_float), ("min_edge", C.c_float), ("edge_sim", C.c_float)]
@@ -393,7 +456,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_clusters", "flimo_map_remove_clusters", "flimo_set_cluster_chunk", "flimo_map_planes", "flimo_plane_solve_host", "flimo_map_plane_mask", "flimo_map_remove_plane", "flimo_set_plane_chunk", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_clusters", "flimo_map_remove_clusters", "flimo_set_cluster_chunk", "flimo_map_planes", "flimo_plane_solve_host", "flimo_map_plane_mask", "flimo_map_remove_plane", "flimo_set_plane_chunk", "flimo_map_voxels", "flimo_map_voxel_mask", "flimo_map_thin", "flimo_voxel_key_host", "flimo_set_voxel_plan", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_corr_graph", "flimo_corr_compatible_host", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -503,6 +566,12 @@ def load_hip():
     L.flimo_map_plane_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PlaneSel), C.c_void_p, C.POINTER(C.c_size_t)]
     L.flimo_map_remove_plane.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PlaneSel), C.POINTER(C.c_size_t)]
     L.flimo_set_plane_chunk.argtypes = [vp, C.c_size_t]
+    L.flimo_map_voxels.argtypes = [vp, C.POINTER(VoxelCfg), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(VoxelStats)]
+    L.flimo_map_voxel_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(VoxelCfg), C.c_void_p, C.c_void_p, C.POINTER(VoxelStats)]
+    L.flimo_map_thin.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(VoxelCfg), C.POINTER(C.c_size_t), C.POINTER(VoxelStats)]
+    L.flimo_voxel_key_host.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.flimo_set_voxel_plan.argtypes = [vp, C.c_int]
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
     L.flimo_map_last_time.argtypes = [vp]
@@ -807,6 +876,37 @@ class HipCtx:
     def set_plane_chunk(self, n):
         """Hypotheses per chunk of ``map_planes`` (flimo_set_plane_chunk; 0: the default of 2^10)."""
         self._chk(self._L.flimo_set_plane_chunk(self._h, int(n)))
+
+    def map_voxels(self, want=("ijk", "count", "centroid"), **cfg):
+        """The voxels of the stored points on a lattice anchored at the world origin -- flimo_map_voxels.  ``cfg``: the fields of
+        ``voxel_cfg`` (leaf, keep, max_pts).  Returns a dict with the outputs named in ``want`` (of ``ijk`` [nv, 3] = (cx, cy, cz),
+        ``count``, ``first``, ``rep`` [nv], ``centroid`` [nv, 3] and ``cov`` [nv, 6] float64: xx xy xz yy yz zz), ``nv`` and
+        ``stats``; the voxels in ascending (cz, cy, cx).  Changes nothing."""
+        return voxels_call(lambda *a: self._chk(self._L.flimo_map_voxels(self._h, *a)), self.map_size(), want, cfg)
+
+    def map_voxel_mask(self, first=0, n=None, want=("voxel", "mask"), **cfg):
+        """The voxel and the thinning mask of the stored points first .. first + n - 1 -- flimo_map_voxel_mask: a dict with
+        ``voxel`` [n] (the position of the point's voxel in ``map_voxels``' listing, -1 outside the lattice), ``mask`` [n] bool
+        (True: ``map_thin`` would forget the point) and ``stats``.  Changes nothing."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return voxel_mask_call(lambda *a: self._chk(self._L.flimo_map_voxel_mask(self._h, first, n, *a)), n, want, cfg)
+
+    def map_thin(self, first=0, n=None, **cfg):
+        """Forget the points of the range ``map_voxel_mask`` marks -- flimo_map_thin; afterwards the map is as after ``map_crop_box``.
+        Returns (removed, stats)."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        k = voxel_cfg(**cfg)
+        removed = C.c_size_t(0)
+        st = VoxelStats()
+        self._chk(self._L.flimo_map_thin(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)))
+        return int(removed.value), st.as_dict()
+
+    def set_voxel_plan(self, plan):
+        """The lane plan of ``map_voxels``' moments (flimo_set_voxel_plan; 0: by the voxel's count, 1..3: groups of 8, 16, 64 lanes,
+        4: the many-runs path, + 8: the points written in sorted order first)."""
+        self._chk(self._L.flimo_set_voxel_plan(self._h, int(plan)))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_clusters", "flimo_loc_map_remove_clusters", "flimo_loc_map_planes", "flimo_loc_map_plane_mask", "flimo_loc_map_remove_plane", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_clusters", "flimo_loc_map_remove_clusters", "flimo_loc_map_planes", "flimo_loc_map_plane_mask", "flimo_loc_map_remove_plane", "flimo_loc_map_voxels", "flimo_loc_map_voxel_mask", "flimo_loc_map_thin", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -175,6 +175,11 @@ def load_host():
     L.flimo_loc_map_planes.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(_lib.PlaneCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flimo_loc_map_plane_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.PlaneSel), C.c_void_p, C.POINTER(C.c_size_t)]
     L.flimo_loc_map_remove_plane.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.PlaneSel), C.POINTER(C.c_size_t)]
+    L.flimo_loc_map_voxels.argtypes = [vp, C.POINTER(_lib.VoxelCfg), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_lib.VoxelStats)]
+    L.flimo_loc_map_voxel_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.VoxelCfg), C.c_void_p, C.c_void_p,
+                                           C.POINTER(_lib.VoxelStats)]
+    L.flimo_loc_map_thin.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.VoxelCfg), C.POINTER(C.c_size_t), C.POINTER(_lib.VoxelStats)]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -478,6 +483,34 @@ class Localizer:
         removed = C.c_size_t(0)
         self._outliers_chk(self._L.flimo_loc_map_remove_plane(self._h, first, n, C.byref(sel), C.byref(removed)), "flimo_loc_map_remove_plane")
         return int(removed.value)
+
+    def map_voxels(self, want=("ijk", "count", "centroid"), **cfg):
+        """The voxels of the map's stored points (flimo_loc_map_voxels), as ``HipCtx.map_voxels``.  Waits for an insert, a crop or a
+        carve still running; changes nothing.  No policy calls it."""
+        return _lib.voxels_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_voxels(self._h, *a), "flimo_loc_map_voxels"),
+                                self.map_size(), want, cfg)
+
+    def map_voxel_mask(self, first=0, n=None, want=("voxel", "mask"), **cfg):
+        """The voxel and the thinning mask of a range of stored points (flimo_loc_map_voxel_mask), as ``HipCtx.map_voxel_mask``."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        return _lib.voxel_mask_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_voxel_mask(self._h, first, n, *a), "flimo_loc_map_voxel_mask"),
+                                    n, want, cfg)
+
+    def map_thin(self, first=0, n=None, **cfg):
+        """Forget the points of the range that crowd their voxel (flimo_loc_map_thin), as ``HipCtx.map_thin``: (removed, stats)."""
+        first = int(first)
+        n = max(self.map_size() - first, 0) if n is None else int(n)
+        k = _lib.voxel_cfg(**cfg)
+        removed = C.c_size_t(0)
+        st = _lib.VoxelStats()
+        self._outliers_chk(self._L.flimo_loc_map_thin(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)), "flimo_loc_map_thin")
+        return int(removed.value), st.as_dict()
+
+    def voxel_cloud(self, res):
+        """The decimated map one publishes or saves: the centroids of the voxels of edge ``res`` as float32 [nv, 3], in ascending
+        (cz, cy, cx) -- ``map_voxels`` with only the centroid asked for."""
+        return self.map_voxels(want=("centroid",), leaf=res)["centroid"].astype(np.float32)
 
     def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
         """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,
@@ -829,6 +862,19 @@ def plane_solve_host(p3, **cfg):
     if rc < 0:
         raise FlimoError(f"flimo_plane_solve_host failed ({rc})")
     return int(rc), plane, nf
+
+
+def voxel_key_host(p, leaf):
+    """The voxel of ONE point on the host (flimo_voxel_key_host: the function the key kernel of ``map_voxels`` calls): (inside,
+    ijk [3] int32 = (cx, cy, cz), key); an outside point has ijk 0 and the all-ones key.  Needs no device."""
+    L = _lib.load_hip()
+    q = np.ascontiguousarray(p, dtype=np.float32).reshape(3)
+    ijk = np.zeros(3, np.int32)
+    key = C.c_uint64(0)
+    rc = L.flimo_voxel_key_host(q.ctypes.data, float(leaf), ijk.ctypes.data, C.byref(key))
+    if rc < 0:
+        raise FlimoError(f"flimo_voxel_key_host failed ({rc})")
+    return rc == 0, ijk, int(key.value)
 
 
 def plane_consensus(obj, nh, seed=0, top=4, **cfg):

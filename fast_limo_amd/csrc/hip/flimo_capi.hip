@@ -25,6 +25,7 @@
 #include "flimo_pose.h"
 #include "flimo_corr.h"
 #include "flimo_plane.h"
+#include "flimo_voxel.h"
 #include "flimo_desc.h"
 #include "flimo_chain.h"
 #include "flimo_ieskf.h"
@@ -58,6 +59,7 @@ struct flimo_ctx {
   uint64_t outlier_removals = 0, outlier_removed = 0;   // flimo_map_remove_outliers: the same
   uint64_t cluster_removals = 0, cluster_removed = 0;   // flimo_map_remove_clusters: the same
   uint64_t plane_removals = 0, plane_removed = 0;       // flimo_map_remove_plane: the same
+  uint64_t thin_removals = 0, thin_removed = 0;         // flimo_map_thin: the same
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
@@ -66,6 +68,7 @@ struct flimo_ctx {
   size_t keypoints_chunk = (size_t)1 << 20; // points per search launch of flimo_map_keypoints (flimo_set_keypoints_chunk)
   size_t cluster_chunk = (size_t)1 << 20;   // points per link launch of flimo_map_clusters (flimo_set_cluster_chunk)
   size_t plane_chunk = (size_t)1 << 10;     // hypotheses per chunk of flimo_map_planes (flimo_set_plane_chunk)
+  int voxel_plan = 0;                       // lane plan of flimo_map_voxels' moments (flimo_set_voxel_plan; 0: by the voxel's count)
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
   size_t fitness_chunk = (size_t)1 << 22;   // (pose, point) pairs per chunk of flimo_scan_fitness (flimo_set_fitness_chunk)
   size_t corr_chunk = (size_t)1 << 16;      // hypotheses per chunk of flimo_corr_poses (flimo_set_corr_chunk)
@@ -2013,6 +2016,239 @@ extern "C" int flimo_map_remove_plane(flimo_ctx* c, size_t first, size_t n, cons
   HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d_mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
   if (kept != n_old - ones) return fail(c, FLIMO_ERR_HIP, "remove plane: the compaction kept %zu of %zu points, %zu marked", kept, n_old, ones);
   return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->plane_removals, &c->plane_removed, removed, "remove plane");
+}
+
+// ---- voxel statistics and thinning of the stored points (pcl::VoxelGrid's leaves over the map, on a lattice that stays put) -------
+// kernels: flimo_voxel.hip.  Keys, sort, heads and scan; the host reads the voxel count (one wait) and sizes the per-voxel arrays;
+// segments, classes and -- where centroid, cov or the nearest member are wanted -- the run numbers; the host reads the classes' sizes
+// (a second wait); moments; the per-point stage; the results come back through the pinned stage, so the caller's arrays stay
+// untouched if anything fails.  Device scratch: 32 B a stored point (two key and two index arrays, head, scan; the 12 B of the
+// sort's inputs are freed behind it) plus the sort's temporary storage, 16 B more a point under the sorted-copy plan; 24 B a voxel,
+// 48 B more with the centroid and 52 B more with covariance and nearest; 84 B a run slot of the many-runs path (24 B without the
+// second pass); 5 B a point of the range.
+static void voxel_stats_none(flimo_voxel_stats* s) {
+  if (s) s->n = s->voxels = s->largest = s->outside = s->sel_points = 0;
+}
+static bool voxel_cfg_ok(const flimo_voxel_cfg* k) {
+  if (!(k->leaf > 0.f) || std::isinf(k->leaf) || !std::isfinite(1.0f / k->leaf)) return false;      // (a NaN fails the first test)
+  if (k->keep < FLIMO_VOXEL_KEEP_FIRST || k->keep > FLIMO_VOXEL_KEEP_NEAREST || k->max_pts < 1) return false;
+  return !(k->keep == FLIMO_VOXEL_KEEP_NEAREST && k->max_pts != 1);
+}
+static int voxel_check(flimo_ctx* c, size_t first, size_t n, const flimo_voxel_cfg* cfg, const char* what) {
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
+  if (!voxel_cfg_ok(cfg))
+    return fail(c, FLIMO_ERR_INVALID, "%s: leaf must be finite and > 0 with a finite 1 / leaf, keep 0 or 1, max_pts >= 1 (1 with keep nearest)", what);
+  if (first > c->map_n || n > c->map_n - first)
+    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
+  if (c->map_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the map must hold fewer than 2^31 points", what);
+  return FLIMO_OK;
+}
+struct VoxelDev {      // what voxels_device leaves on the device for its caller, and the owner of all it allocated
+  DevScratch mem;
+  size_t nv = 0;
+  int32_t* ijk = nullptr; int32_t* count = nullptr; int32_t* first = nullptr; int32_t* rep = nullptr;
+  double* centroid = nullptr; double* cov = nullptr;
+  int32_t* voxel = nullptr; unsigned char* mask = nullptr;
+};
+// the voxels of the whole map and the selection over [first, first + n), arguments checked, map not empty.  moments: 0 none, 1 the
+// centroid, 2 covariance and nearest as well.  cap: FLIMO_ERR_TOO_LARGE when the map has more voxels (d.nv is set first).  Ends
+// synchronised; *st on the host.
+static int voxels_device(flimo_ctx* c, size_t first, size_t n, const flimo_voxel_cfg& cfg, int moments, size_t cap, bool want_voxel, bool want_mask,
+                         VoxelDev& d, flimo_voxel_stats* st) {
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  ctx_enter(c);
+  const size_t N = c->map_n;
+  const int plan = c->voxel_plan;
+  if (cfg.keep == FLIMO_VOXEL_KEEP_NEAREST) moments = 2;
+  size_t tmp_bytes = 0;
+  HIPCHK(c, voxel_tmp_bytes(N, &tmp_bytes));
+  unsigned long long* d_keys_in = d.mem.get<unsigned long long>(N);
+  unsigned long long* d_keys = d.mem.get<unsigned long long>(N);
+  uint32_t* d_vals_in = d.mem.get<uint32_t>(N);
+  uint32_t* d_perm = d.mem.get<uint32_t>(N);
+  uint32_t* d_head = d.mem.get<uint32_t>(N);
+  uint32_t* d_pos = d.mem.get<uint32_t>(N);
+  uint32_t* d_words = d.mem.get<uint32_t>(VOXEL_WORDS);
+  void* d_tmp = d.mem.get<unsigned char>(tmp_bytes);
+  { const int rc = d.mem.ok(c); if (rc) return rc; }
+  HIPCHK(c, hipMemsetAsync(d_words, 0, VOXEL_WORDS * sizeof(uint32_t), c->stream));
+  HIPCHK(c, launch_voxel_sort(c->stream, c->d_map_raw, (unsigned)N, 1.0f / cfg.leaf, d_keys_in, d_keys, d_vals_in, d_perm, d_head, d_pos, d_tmp,
+                              tmp_bytes, d_words));
+  uint32_t h3[3] = {0, 0, 0};      // {scan of the last position, its head flag, the outside points}
+  HIPCHK(c, hipMemcpyAsync(&h3[0], d_pos + (N - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&h3[1], d_head + (N - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&h3[2], d_words + VOXEL_W_OUTSIDE, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t nv = (size_t)h3[0] + h3[1], outside = h3[2];
+  if (nv > N || outside > N || (nv == 0) != (outside == N))
+    return fail(c, FLIMO_ERR_HIP, "map voxels: counted %zu voxels and %zu outside points of %zu points", nv, outside, N);
+  d.nv = nv;
+  if (nv > cap) return fail(c, FLIMO_ERR_TOO_LARGE, "map voxels: the map has %zu voxels, the arrays hold %zu", nv, cap);
+  d.mem.drop(d_keys_in);
+  d.mem.drop(d_vals_in);
+  uint32_t* d_seg = d.mem.get<uint32_t>(nv + 1);
+  d.ijk = d.mem.get<int32_t>(3 * nv + 1);
+  d.first = d.mem.get<int32_t>(nv + 1);
+  d.count = d.mem.get<int32_t>(nv + 1);
+  uint32_t* d_runs = nullptr; uint32_t* d_roff = nullptr; uint32_t* d_lists = nullptr;
+  if (moments) {
+    d_runs = d.mem.get<uint32_t>(nv + 1);
+    d_roff = d.mem.get<uint32_t>(nv + 1);
+    d_lists = d.mem.get<uint32_t>(4 * nv + 1);
+    d.centroid = d.mem.get<double>(3 * nv + 1);
+    if (moments > 1) {
+      d.cov = d.mem.get<double>(6 * nv + 1);
+      d.rep = d.mem.get<int32_t>(nv + 1);
+    }
+  }
+  { const int rc = d.mem.ok(c); if (rc) return rc; }
+  HIPCHK(c, launch_voxel_classify(c->stream, d_keys, d_perm, d_head, d_pos, (unsigned)N, (unsigned)nv, (unsigned)(N - outside), plan, d_seg, d.ijk,
+                                  d.first, d.count, d_runs, d_roff, d_lists, d_tmp, tmp_bytes, d_words));
+  uint32_t w[VOXEL_WORDS] = {0};
+  uint32_t R = 0;
+  HIPCHK(c, hipMemcpyAsync(w, d_words, sizeof w, hipMemcpyDeviceToHost, c->stream));
+  if (moments) HIPCHK(c, hipMemcpyAsync(&R, d_roff + nv, sizeof R, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const unsigned* nl = w + VOXEL_W_LIST;
+  if (w[VOXEL_W_LARGEST] > N || (nv > 0 && w[VOXEL_W_LARGEST] < 1) ||
+      (moments && ((size_t)nl[0] + nl[1] + nl[2] + nl[3] != nv || (size_t)R > N / 64 + nv)))
+    return fail(c, FLIMO_ERR_HIP, "map voxels: the classes hold %u + %u + %u + %u of %zu voxels, %u run slots, largest %u", nl[0], nl[1], nl[2],
+                nl[3], nv, R, w[VOXEL_W_LARGEST]);
+  if (moments && nv > 0) {
+    double* d_rs = nullptr; double* d_rc = nullptr; double* d_rq = nullptr; uint32_t* d_rp = nullptr;
+    if (nl[3]) {
+      d_rs = d.mem.get<double>(3 * (size_t)R);
+      if (moments > 1) {
+        d_rc = d.mem.get<double>(6 * (size_t)R);
+        d_rq = d.mem.get<double>(R);
+        d_rp = d.mem.get<uint32_t>(R);
+      }
+    }
+    const float4* pts = c->d_map_raw;
+    const uint32_t* gather = d_perm;
+    if (plan & VOXEL_PLAN_SORTED) {
+      float4* d_sorted = d.mem.get<float4>(N);
+      { const int rc = d.mem.ok(c); if (rc) return rc; }
+      HIPCHK(c, launch_voxel_sorted_copy(c->stream, c->d_map_raw, d_perm, (unsigned)N, d_sorted));
+      pts = d_sorted;
+      gather = nullptr;
+    }
+    { const int rc = d.mem.ok(c); if (rc) return rc; }
+    HIPCHK(c, launch_voxel_moments(c->stream, pts, gather, d_perm, d_seg, (unsigned)nv, d_lists, nl, d_roff, R, moments > 1, d_rs, d_rc, d_rq, d_rp,
+                                   d.centroid, d.cov, d.rep));
+  }
+  if (cfg.keep == FLIMO_VOXEL_KEEP_FIRST) d.rep = d.first;      // (the oldest member)
+  uint32_t sel = 0;
+  if (n > 0) {
+    if (want_voxel) d.voxel = d.mem.get<int32_t>(n);
+    if (want_mask) d.mask = d.mem.get<unsigned char>(n);
+    { const int rc = d.mem.ok(c); if (rc) return rc; }
+    HIPCHK(c, launch_voxel_points(c->stream, d_keys, d_perm, d_head, d_pos, d_seg, d.rep, (unsigned)N, (unsigned)first, (unsigned)n, cfg.keep,
+                                  (unsigned)cfg.max_pts, d.voxel, d.mask, d_words));
+    HIPCHK(c, hipMemcpyAsync(&sel, d_words + VOXEL_W_SEL, sizeof sel, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((size_t)sel > n) return fail(c, FLIMO_ERR_HIP, "map voxels: selected %u of %zu points", sel, n);
+  st->n = n; st->voxels = nv; st->largest = w[VOXEL_W_LARGEST]; st->outside = outside; st->sel_points = sel;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_voxels(flimo_ctx* c, const flimo_voxel_cfg* cfg, size_t cap, size_t* nv, int32_t* ijk, int32_t* count, int32_t* first,
+                                int32_t* rep, double* centroid, double* cov, flimo_voxel_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = voxel_check(c, 0, 0, cfg, "map voxels"); if (rc) return rc; }
+  const size_t N = c->map_n;
+  if (N == 0) { if (nv) *nv = 0; voxel_stats_none(stats); return FLIMO_OK; }
+  const bool arrays = ijk || count || first || rep || centroid || cov;
+  VoxelDev d;
+  flimo_voxel_stats st;
+  const int moments = cov ? 2 : centroid ? 1 : 0;
+  {
+    // (the selection is counted over the whole map, and only where the stats are asked for)
+    const int rc = voxels_device(c, 0, stats ? N : 0, *cfg, moments, arrays ? cap : (size_t)-1, false, false, d, &st);
+    if (nv && (rc == FLIMO_OK || (rc == FLIMO_ERR_TOO_LARGE && d.nv > cap))) *nv = d.nv;
+    if (rc) return rc;
+  }
+  const size_t m = d.nv;
+  if (arrays && m > 0) {
+    const size_t bytes = m * ((centroid ? 24 : 0) + (cov ? 48 : 0) + (ijk ? 12 : 0) + (count ? 4 : 0) + (first ? 4 : 0) + (rep ? 4 : 0));
+    { const int rc = ensure_stage(c, bytes); if (rc) return rc; }
+    char* h = (char*)c->h_stage;      // (the float64 arrays first: every part stays aligned)
+    struct Part { void* dst; const void* src; size_t bytes; char* at; } parts[6] = {
+        {centroid, d.centroid, 24 * m, nullptr}, {cov, d.cov, 48 * m, nullptr}, {ijk, d.ijk, 12 * m, nullptr},
+        {count, d.count, 4 * m, nullptr},        {first, d.first, 4 * m, nullptr}, {rep, d.rep, 4 * m, nullptr}};
+    for (Part& p : parts) {
+      if (!p.dst) continue;
+      p.at = h;
+      h += p.bytes;
+      HIPCHK(c, hipMemcpyAsync(p.at, p.src, p.bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (const Part& p : parts)
+      if (p.dst) memcpy(p.dst, p.at, p.bytes);
+  }
+  if (stats) *stats = st;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_voxel_mask(flimo_ctx* c, size_t first, size_t n, const flimo_voxel_cfg* cfg, int32_t* voxel, unsigned char* mask,
+                                    flimo_voxel_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = voxel_check(c, first, n, cfg, "voxel mask"); if (rc) return rc; }
+  if (c->map_n == 0) { voxel_stats_none(stats); return FLIMO_OK; }
+  if (n == 0 && !stats) return FLIMO_OK;
+  VoxelDev d;
+  flimo_voxel_stats st;
+  { const int rc = voxels_device(c, first, n, *cfg, 0, (size_t)-1, voxel != nullptr, mask != nullptr, d, &st); if (rc) return rc; }
+  if (n > 0 && (voxel || mask)) {
+    { const int rc = ensure_stage(c, n * 5); if (rc) return rc; }
+    int32_t* h_voxel = (int32_t*)c->h_stage;
+    unsigned char* h_mask = (unsigned char*)c->h_stage + 4 * n;
+    if (voxel) HIPCHK(c, hipMemcpyAsync(h_voxel, d.voxel, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (mask) HIPCHK(c, hipMemcpyAsync(h_mask, d.mask, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (voxel) memcpy(voxel, h_voxel, n * sizeof(int32_t));
+    if (mask) memcpy(mask, h_mask, n);
+  }
+  if (stats) *stats = st;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_thin(flimo_ctx* c, size_t first, size_t n, const flimo_voxel_cfg* cfg, size_t* removed, flimo_voxel_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = voxel_check(c, first, n, cfg, "map thin"); if (rc) return rc; }
+  if (c->map_n == 0) { if (removed) *removed = 0; voxel_stats_none(stats); return FLIMO_OK; }
+  if (n == 0 && !stats) { if (removed) *removed = 0; return FLIMO_OK; }
+  VoxelDev d;
+  flimo_voxel_stats st;
+  { const int rc = voxels_device(c, first, n, *cfg, 0, (size_t)-1, false, true, d, &st); if (rc) return rc; }
+  if (removed) *removed = 0;
+  if (stats) *stats = st;
+  if (st.sel_points == 0) return FLIMO_OK;             // removing nothing changes nothing
+  const size_t n_old = c->map_n;
+  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
+  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  size_t kept = 0;
+  float bb[6];
+  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d.mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
+  if (kept != n_old - (size_t)st.sel_points)
+    return fail(c, FLIMO_ERR_HIP, "map thin: the compaction kept %zu of %zu points, %llu marked", kept, n_old, (unsigned long long)st.sel_points);
+  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->thin_removals, &c->thin_removed, removed, "map thin");
+}
+extern "C" int flimo_voxel_key_host(const float p[3], float leaf, int32_t ijk[3], uint64_t* key) {
+  const flimo_voxel_cfg k{leaf, FLIMO_VOXEL_KEEP_FIRST, 1};
+  if (!p || !voxel_cfg_ok(&k)) return FLIMO_ERR_INVALID;
+  int32_t cell[3];
+  unsigned long long kk = 0;
+  const bool inside = voxel_key(p[0], p[1], p[2], 1.0f / leaf, cell, &kk);
+  if (ijk) { ijk[0] = cell[0]; ijk[1] = cell[1]; ijk[2] = cell[2]; }
+  if (key) *key = kk;
+  return inside ? 0 : 1;
+}
+extern "C" int flimo_set_voxel_plan(flimo_ctx* c, int plan) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (plan < 0 || (plan & ~VOXEL_PLAN_SORTED) > VOXEL_PLAN_RUNS) return fail(c, FLIMO_ERR_INVALID, "voxel plan: %d is none of 0..4, + 8", plan);
+  c->voxel_plan = plan;
+  return FLIMO_OK;
 }
 
 // ---- scan -------------------------------------------------------------------------------------

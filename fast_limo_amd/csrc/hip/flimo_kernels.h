@@ -395,6 +395,32 @@ hipError_t launch_plane_chunk(hipStream_t st, const float4* map_raw, unsigned N,
 hipError_t launch_plane_mask(hipStream_t st, const float4* map_raw, unsigned first, unsigned n, const float normal[3], const float anchor[3],
                              float dist, int side, unsigned char* mask, unsigned* count);
 
+// flimo_voxel.hip -- voxel statistics of the stored points (flimo_map_voxels, flimo_c.h), in stages on one stream; words
+// [VOXEL_WORDS] (flimo_voxel.h) is zeroed by the caller, tmp holds voxel_tmp_bytes(n).
+//  launch_voxel_sort      keys, the stable sort (keys_out / vals_out: sorted keys and the insertion index of every sorted position),
+//                         head flags and their exclusive scan pos; words[VOXEL_W_OUTSIDE] += the outside points.  The caller
+//                         reads nv = pos[n - 1] + head[n - 1] and the outside count before the next stage.
+//  launch_voxel_classify  seg [nv + 1], ijk [nv][3], first [nv], count [nv], words[VOXEL_W_LARGEST]; with lists ([4][nv]; null: no
+//                         moments are wanted) the voxels of each lane plan (lengths in words[VOXEL_W_LIST ..]), runs [nv + 1] and
+//                         their exclusive scan roff [nv + 1] (roff[nv]: the run slots R the many-runs path needs).
+//  launch_voxel_moments   centroid [nv][3] and, with second, cov [nv][6] and rep [nv]; pts is read through gather (null: pts is
+//                         in sorted order, launch_voxel_sorted_copy); rs [R][3], rc [R][6], rq [R], rp [R]: the run slots.
+//  launch_voxel_points    voxel [nr] / mask [nr] (may be null) of the stored points first .. first + nr - 1 and
+//                         words[VOXEL_W_SEL] += the ones; rep is read for VOXEL_KEEP_NEAREST only.
+hipError_t voxel_tmp_bytes(size_t n, size_t* bytes);
+hipError_t launch_voxel_sort(hipStream_t st, const float4* map_raw, unsigned n, float inv, unsigned long long* keys_in, unsigned long long* keys_out,
+                             uint32_t* vals_in, uint32_t* vals_out, uint32_t* head, uint32_t* pos, void* tmp, size_t tmp_bytes, uint32_t* words);
+hipError_t launch_voxel_classify(hipStream_t st, const unsigned long long* keys, const uint32_t* perm, const uint32_t* head, const uint32_t* pos,
+                                 unsigned n, unsigned nv, unsigned inside, int plan, uint32_t* seg, int32_t* ijk, int32_t* first, int32_t* count,
+                                 uint32_t* runs, uint32_t* roff, uint32_t* lists, void* tmp, size_t tmp_bytes, uint32_t* words);
+hipError_t launch_voxel_sorted_copy(hipStream_t st, const float4* map_raw, const uint32_t* perm, unsigned n, float4* out);
+hipError_t launch_voxel_moments(hipStream_t st, const float4* pts, const uint32_t* gather, const uint32_t* perm, const uint32_t* seg, unsigned nv,
+                                const uint32_t* lists, const unsigned nlist[4], const uint32_t* roff, unsigned R, int second, double* rs,
+                                double* rc, double* rq, uint32_t* rp, double* centroid, double* cov, int32_t* rep);
+hipError_t launch_voxel_points(hipStream_t st, const unsigned long long* keys, const uint32_t* perm, const uint32_t* head, const uint32_t* pos,
+                               const uint32_t* seg, const int32_t* rep, unsigned n, unsigned first, unsigned nr, int keep, unsigned max_pts,
+                               int32_t* voxel, unsigned char* mask, uint32_t* words);
+
 // flimo_desc.hip -- nearest descriptors (flimo_desc_match, flimo_c.h).  The resident reference set is two arrays: norm
 // [ceil(nr / 32) * 32] (launch_desc_norms with npad = that; NaN for an excluded row and for the padding) and rt
 // [ceil(nr / 32)][desc_steps(dim)][64], the rows in the MFMA's A-operand layout (launch_desc_pack).  launch_desc_match answers a

@@ -439,6 +439,43 @@ int flimo_loc_map_remove_plane(flimo_loc* L, size_t first, size_t n, const flimo
   }
   return flimo_map_remove_plane(c, first, n, sel, removed);
 }
+// no map yet: the answer of an empty one, after the calls' own argument checks
+static int voxels_of_no_map(size_t first, size_t n, const flimo_voxel_cfg* k, flimo_voxel_stats* stats) {
+  if (!k || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
+  if (!(k->leaf > 0.f) || std::isinf(k->leaf) || !std::isfinite(1.0f / k->leaf)) return FLIMO_ERR_INVALID;
+  if (k->keep < FLIMO_VOXEL_KEEP_FIRST || k->keep > FLIMO_VOXEL_KEEP_NEAREST || k->max_pts < 1) return FLIMO_ERR_INVALID;
+  if (k->keep == FLIMO_VOXEL_KEEP_NEAREST && k->max_pts != 1) return FLIMO_ERR_INVALID;
+  if (stats) stats->n = stats->voxels = stats->largest = stats->outside = stats->sel_points = 0;
+  return FLIMO_OK;
+}
+int flimo_loc_map_voxels(flimo_loc* L, const flimo_voxel_cfg* cfg, size_t cap, size_t* nv, int32_t* ijk, int32_t* count, int32_t* first,
+                         int32_t* rep, double* centroid, double* cov, flimo_voxel_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
+  if (!c) {
+    const int rc = voxels_of_no_map(0, 0, cfg, stats);
+    if (rc == FLIMO_OK && nv) *nv = 0;
+    return rc;
+  }
+  return flimo_map_voxels(c, cfg, cap, nv, ijk, count, first, rep, centroid, cov, stats);
+}
+int flimo_loc_map_voxel_mask(flimo_loc* L, size_t first, size_t n, const flimo_voxel_cfg* cfg, int32_t* voxel, unsigned char* mask,
+                             flimo_voxel_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();
+  if (!c) return voxels_of_no_map(first, n, cfg, stats);
+  return flimo_map_voxel_mask(c, first, n, cfg, voxel, mask, stats);
+}
+int flimo_loc_map_thin(flimo_loc* L, size_t first, size_t n, const flimo_voxel_cfg* cfg, size_t* removed, flimo_voxel_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  flimo_ctx* c = L->map->ctx();
+  if (!c) {
+    const int rc = voxels_of_no_map(first, n, cfg, stats);
+    if (rc == FLIMO_OK && removed) *removed = 0;
+    return rc;
+  }
+  return flimo_map_thin(c, first, n, cfg, removed, stats);
+}
 int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
                          const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
   if (!L) return FLIMO_ERR_INVALID;

@@ -584,6 +584,46 @@ int Mapper::remove_clusters(size_t first, size_t n, const flimo_cluster_cfg& cfg
   return flimo_map_remove_clusters(ctx_, first, n, &cfg, removed, stats);
 }
 
+// voxel statistics and thinning of the map's stored points (an insert, a crop or a carve on the worker thread ends first)
+int Mapper::voxels(const flimo_voxel_cfg& cfg, std::vector<int32_t>* ijk, std::vector<int32_t>* count, std::vector<int32_t>* first,
+                   std::vector<int32_t>* rep, std::vector<double>* centroid, std::vector<double>* cov, flimo_voxel_stats* stats) {
+  sync();
+  std::vector<int32_t>* iv[4] = {ijk, count, first, rep};
+  const size_t iw[4] = {3, 1, 1, 1};
+  for (auto* v : iv) if (v) v->clear();
+  if (centroid) centroid->clear();
+  if (cov) cov->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  const size_t cap = flimo_map_size(ctx_);      // (no more voxels than points: one call)
+  for (int i = 0; i < 4; i++) if (iv[i]) iv[i]->assign(iw[i] * cap, 0);
+  if (centroid) centroid->assign(3 * cap, 0.0);
+  if (cov) cov->assign(6 * cap, 0.0);
+  size_t nv = 0;
+  auto ptr = [cap](auto* v) { return (v && cap) ? v->data() : nullptr; };
+  const int rc = flimo_map_voxels(ctx_, &cfg, cap, &nv, ptr(ijk), ptr(count), ptr(first), ptr(rep), ptr(centroid), ptr(cov), stats);
+  if (rc != FLIMO_OK) nv = 0;
+  for (int i = 0; i < 4; i++) if (iv[i]) iv[i]->resize(iw[i] * nv);
+  if (centroid) centroid->resize(3 * nv);
+  if (cov) cov->resize(6 * nv);
+  return rc;
+}
+int Mapper::voxel_mask(size_t first, size_t n, const flimo_voxel_cfg& cfg, std::vector<int32_t>* voxel, std::vector<unsigned char>* mask,
+                       flimo_voxel_stats* stats) {
+  sync();
+  if (voxel) voxel->clear();
+  if (mask) mask->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (first > flimo_map_size(ctx_) || n > flimo_map_size(ctx_) - first) return FLIMO_ERR_INVALID;
+  if (voxel) voxel->assign(n, -1);
+  if (mask) mask->assign(n, 0);
+  return flimo_map_voxel_mask(ctx_, first, n, &cfg, (voxel && n) ? voxel->data() : nullptr, (mask && n) ? mask->data() : nullptr, stats);
+}
+int Mapper::thin(size_t first, size_t n, const flimo_voxel_cfg& cfg, size_t* removed, flimo_voxel_stats* stats) {
+  sync();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  return flimo_map_thin(ctx_, first, n, &cfg, removed, stats);
+}
+
 // fitness of the resident scan at pose hypotheses (an insert or a crop on the worker thread ends first)
 int Mapper::fitness(const double* x26, size_t np, float max_dist, std::vector<int32_t>& inliers, std::vector<double>& sum_sqd,
                     std::vector<float>* nn_sqd, std::vector<int32_t>* nn_idx) {

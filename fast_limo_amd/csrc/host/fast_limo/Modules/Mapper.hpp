@@ -82,6 +82,18 @@ class fast_limo::Mapper {
   // ... and forget the points of the range in selected components (flimo_map_remove_clusters); afterwards the map is as after
   // crop_box.  As remove_outliers: it runs at once and is not queued.  removed / stats may be null.  Returns a FLIMO_* code.
   int remove_clusters(size_t first, size_t n, const flimo_cluster_cfg& cfg, size_t* removed = nullptr, flimo_cluster_stats* stats = nullptr);
+  // The voxels of the stored points on a lattice anchored at the world origin (flimo_map_voxels: pcl::VoxelGrid's leaves over the
+  // map, float64 sums of one fixed shape): where a vector is given ijk [nv][3], count [nv], first [nv], rep [nv], centroid [nv][3],
+  // cov [nv][6]; stats (may be null).  Changes nothing.  Returns a FLIMO_* code.
+  int voxels(const flimo_voxel_cfg& cfg, std::vector<int32_t>* ijk, std::vector<int32_t>* count = nullptr, std::vector<int32_t>* first = nullptr,
+             std::vector<int32_t>* rep = nullptr, std::vector<double>* centroid = nullptr, std::vector<double>* cov = nullptr,
+             flimo_voxel_stats* stats = nullptr);
+  // ... the voxel [n] and the thinning mask [n] of the stored points first .. first + n - 1 (flimo_map_voxel_mask) ...
+  int voxel_mask(size_t first, size_t n, const flimo_voxel_cfg& cfg, std::vector<int32_t>* voxel, std::vector<unsigned char>* mask = nullptr,
+                 flimo_voxel_stats* stats = nullptr);
+  // ... and forget the masked points of the range (flimo_map_thin); afterwards the map is as after crop_box.  As remove_clusters: it
+  // runs at once and is not queued.  removed / stats may be null.  Returns a FLIMO_* code.
+  int thin(size_t first, size_t n, const flimo_voxel_cfg& cfg, size_t* removed = nullptr, flimo_voxel_stats* stats = nullptr);
   // octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the GPU map (flimo_radius_search).  The reference's Mapper hides
   // its octree, so this is an addition: the stored points with (p - query).squaredNorm() < radius * radius (strict, float32), in
   // ascending order of (distance, insertion index) -- the reference's traversal order is not reproduced.  As the template

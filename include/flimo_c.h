@@ -495,6 +495,75 @@ int flimo_map_plane_mask(flimo_ctx* ctx, size_t first, size_t n, const flimo_pla
  * negative, side outside -1..1, first + n beyond flimo_map_size; FLIMO_ERR_TOO_LARGE for a map of 2^31 points or more. */
 int flimo_map_remove_plane(flimo_ctx* ctx, size_t first, size_t n, const flimo_plane_sel* sel, size_t* removed);
 
+/* ---- voxel statistics and thinning of the stored points: what pcl::VoxelGrid computes per leaf -- count, centroid -- and the
+ * covariance an NDT or voxel-map matcher keeps per cell, over the map; and the way to forget by DENSITY: a place visited fifty
+ * times keeps no more points than a registration needs, without the map leaving the GPU ----
+ *
+ * Definition (tests/voxels_common.py restates it in numpy).  Stored point i (insertion order, the order flimo_map_points returns)
+ * is p_i; stored points are always finite.
+ * Lattice: anchored at the world origin, so a voxel is the same set of space whatever the map's extent.  inv = 1.0f / leaf (one
+ *   float32 division); c_a = floorf(p_a * inv) for a = x, y, z (one float32 product, then floorf): the cells of pcl::VoxelGrid and
+ *   of the scan's voxel filter, shifted by whole cells.  A point is OUTSIDE when any fabsf(c_a) >= FLIMO_VOXEL_HALF (2^20): it
+ *   belongs to no voxel, is never selected and never removed, and is counted in stats.outside.  Otherwise
+ *   key = ((cz + 2^20) << 42) | ((cy + 2^20) << 21) | (cx + 2^20).
+ * Voxels: the occupied keys of the WHOLE map whatever the range (as flimo_map_clusters treats components), listed in ascending
+ *   key, which is ascending (cz, cy, cx): PCL's output order.  Voxel v has the members m_0 < m_1 < ... < m_{c-1} (insertion
+ *   indices).  ijk[v] = (cx, cy, cz), count[v] = c, first[v] = m_0.
+ * SHAPE of a float64 sum over values u_0 .. u_{c-1} taken in member order: run j holds the slots 64 j .. 64 j + 63
+ *   (FLIMO_VOXEL_RUN), an absent slot holds +0.0; a run's sum is the pairwise tree ((u0 + u1) + (u2 + u3)) + ... over its 64 slots
+ *   (flimo_map_outliers' tree; equivalently the butterfly t[s] += t[s ^ o] for o = 1, 2, 4, 8, 16, 32); then
+ *   S = ((+0.0 + R_0) + R_1) + ... over the runs in ascending order.  The leading +0.0 fixes the sign of a zero sum.
+ * centroid[v][a] = S_a / (double)c, S_a the SHAPE over (double)p[m_r][a].
+ * cov[v] = (xx, xy, xz, yy, yz, zz): each entry the SHAPE over d_a * d_b with d = (double)p - centroid (three float64
+ *   subtractions, one product), divided by (double)c -- the / n convention of flimo_map_normals; two passes, never E[xx] - E[x]^2.
+ * rep[v]: with keep == FLIMO_VOXEL_KEEP_FIRST m_0; with FLIMO_VOXEL_KEEP_NEAREST the member with the smallest
+ *   q = d.x*d.x + (d.y*d.y + d.z*d.z), float64 and uncontracted, ties to the smallest insertion index.
+ * Selection (the thinning rule; mask[i] = 1: stored point first + i goes).  KEEP_FIRST with max_pts = m >= 1: a point goes iff at
+ *   least m members of its voxel have a smaller insertion index -- a voxel of at most m points is untouched, the oldest m stay;
+ *   over a range of newly added points this is "drop what arrives where the voxel is already full", the octree's batch-drop rule
+ *   made exact and independent of batch boundaries.  KEEP_NEAREST (max_pts must be 1): a point goes iff it is not rep of its
+ *   voxel.  Both rules are idempotent: a second thinning with the same cfg removes nothing.
+ * voxel[i]: the position of the point's voxel in the listing, -1 for an outside point.
+ * stats: n (the range; flimo_map_voxels: the whole map), voxels, largest, outside (whole map), sel_points (ones of the mask over
+ *   the range).  With n == 0 the whole-map fields are still formed where stats is given.
+ * Nothing depends on the chunking, the map index's cell size, the number of insert batches, the lane plan (flimo_set_voxel_plan)
+ * or what else the context did before.  No floating-point atomics.
+ * Cost: one 64-bit radix sort of the stored points and two passes over them; device scratch is 32 B a stored point plus the
+ * sort's own, at most 124 B a voxel and 84 B a run of a voxel above 1024 points. */
+#define FLIMO_VOXEL_KEEP_FIRST 0
+#define FLIMO_VOXEL_KEEP_NEAREST 1
+#define FLIMO_VOXEL_RUN 64              /* part of the contract: the sum's shape */
+#define FLIMO_VOXEL_HALF 1048576        /* 2^20 cells either side of the origin on every axis */
+typedef struct flimo_voxel_cfg {
+  float leaf;      /* edge of a voxel [m]: finite, > 0, 1.0f / leaf finite */
+  int keep;        /* FLIMO_VOXEL_KEEP_FIRST / FLIMO_VOXEL_KEEP_NEAREST */
+  int max_pts;     /* >= 1: the members a voxel keeps; 1 with KEEP_NEAREST */
+} flimo_voxel_cfg;
+typedef struct flimo_voxel_stats { uint64_t n, voxels, largest, outside, sel_points; } flimo_voxel_stats;
+/* The voxels of the whole map.  Every output may be NULL.  *nv (the number of voxels, <= flimo_map_size) is written whenever the
+ * call gets that far: a non-NULL per-voxel array with cap < nv returns FLIMO_ERR_TOO_LARGE, *nv set, the arrays untouched; a
+ * caller passes cap = flimo_map_size and makes one call.  Changes nothing: not the map, not the scan, not the bits of a later
+ * pass.  An empty map: FLIMO_OK, *nv = 0, stats 0. */
+int flimo_map_voxels(flimo_ctx* ctx, const flimo_voxel_cfg* cfg, size_t cap, size_t* nv, int32_t* ijk /* [nv][3] */, int32_t* count /* [nv] */,
+                     int32_t* first /* [nv] */, int32_t* rep /* [nv] */, double* centroid /* [nv][3] */, double* cov /* [nv][6] */,
+                     flimo_voxel_stats* stats);
+/* voxel [n] and mask [n] of the stored points first .. first + n - 1 (either may be NULL), the voxels being those of the whole map.
+ * Changes nothing. */
+int flimo_map_voxel_mask(flimo_ctx* ctx, size_t first, size_t n, const flimo_voxel_cfg* cfg, int32_t* voxel /* [n] */,
+                         unsigned char* mask /* [n] */, flimo_voxel_stats* stats);
+/* Forgets the points of the range whose mask is 1 and keeps the rest in insertion order, in the one ordered compaction pass
+ * flimo_map_remove_plane uses.  Afterwards everything is as flimo_map_crop_box documents: the map is clear() + initialize(kept),
+ * insertion indices are renumbered, flimo_map_last_time is untouched.  *removed (may be NULL) receives how many points went
+ * (== stats->sel_points).  Removing nothing changes nothing.
+ * All three calls: FLIMO_ERR_INVALID -- outputs and map untouched -- for a NULL ctx or cfg, leaf NaN, <= 0 or infinite or with
+ * 1.0f / leaf not finite, keep outside 0..1, max_pts < 1, KEEP_NEAREST with max_pts != 1, first + n beyond flimo_map_size;
+ * FLIMO_ERR_TOO_LARGE for a map of 2^31 points or more.  Same calling rules as flimo_map_clusters: no pass of this context in flight. */
+int flimo_map_thin(flimo_ctx* ctx, size_t first, size_t n, const flimo_voxel_cfg* cfg, size_t* removed, flimo_voxel_stats* stats);
+/* The lattice for one point on the host, through the same function the key kernel calls: 0 inside (ijk = (cx, cy, cz) and key
+ * written), 1 outside (ijk = 0, key all ones), FLIMO_ERR_INVALID for a NULL p or a leaf flimo_map_voxels rejects.  ijk and key may
+ * be NULL.  Needs no context and no device. */
+int flimo_voxel_key_host(const float p[3], float leaf, int32_t ijk[3], uint64_t* key);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

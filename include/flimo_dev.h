@@ -92,6 +92,11 @@ int flimo_set_cluster_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_map_planes works in chunks of n hypotheses (default 2^10; 0 restores it; at most 2^16 and 2^26 partials are used): the
  * chunk bounds the partials, ceil(N / FLIMO_PLANE_SLAB) x 12 B a hypothesis, and the records; equal results whatever the chunk. */
 int flimo_set_plane_chunk(flimo_ctx* ctx, size_t n);
+/* The lane plan of flimo_map_voxels' moments stage: 0 chooses by the voxel's count (at most 8 points: a group of 8 lanes; at most
+ * 16: 16 lanes; at most 1024: a wave; more: the many-runs path, one wave per run of 64 and a chain over the runs); 1, 2, 3 force
+ * the groups of 8, 16, 64 lanes for every voxel, 4 the many-runs path.  + 8: the points are first written in sorted order, so the
+ * moments read them without a gather.  Equal results whatever the plan; FLIMO_ERR_INVALID for any other value. */
+int flimo_set_voxel_plan(flimo_ctx* ctx, int plan);
 /* flimo_corr_poses works in chunks of n hypotheses (default 2^16; 0 restores it): the chunk bounds the call's device scratch, 136 B
  * a hypothesis (and m floats each where pair_sqd is asked for: then at most 2^26 slots a chunk); equal results whatever the chunk. */
 int flimo_set_corr_chunk(flimo_ctx* ctx, size_t n);

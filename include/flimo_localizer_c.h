@@ -152,6 +152,15 @@ int    flimo_loc_map_planes(flimo_loc* L, const int32_t* tri, size_t nh, const f
                             double* sum_sq, double* plane);
 int    flimo_loc_map_plane_mask(flimo_loc* L, size_t first, size_t n, const flimo_plane_sel* sel, unsigned char* mask, size_t* count);
 int    flimo_loc_map_remove_plane(flimo_loc* L, size_t first, size_t n, const flimo_plane_sel* sel, size_t* removed);
+/* Voxel statistics and thinning of the Localizer's stored points: flimo_map_voxels / flimo_map_voxel_mask / flimo_map_thin
+ * (include/flimo_c.h: same arguments, same results, same error codes) on the map's context, after an insert, a crop or a carve
+ * still running behind the last sweep has ended.  A Localizer that has no map yet answers like an empty one (first = n = 0:
+ * FLIMO_OK, *nv = 0, stats 0; anything else lies beyond it).  There is no policy that calls them. */
+int    flimo_loc_map_voxels(flimo_loc* L, const flimo_voxel_cfg* cfg, size_t cap, size_t* nv, int32_t* ijk, int32_t* count, int32_t* first,
+                            int32_t* rep, double* centroid, double* cov, flimo_voxel_stats* stats);
+int    flimo_loc_map_voxel_mask(flimo_loc* L, size_t first, size_t n, const flimo_voxel_cfg* cfg, int32_t* voxel, unsigned char* mask,
+                                flimo_voxel_stats* stats);
+int    flimo_loc_map_thin(flimo_loc* L, size_t first, size_t n, const flimo_voxel_cfg* cfg, size_t* removed, flimo_voxel_stats* stats);
 /* Pose hypotheses from point correspondences: flimo_corr_poses (include/flimo_c.h: same arguments, same results, same error
  * codes) on the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  Neither the map
  * nor the resident scan is read; a Localizer that has no context yet creates it.  The Localizer's own update does not use it. */
