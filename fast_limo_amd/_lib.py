@@ -710,6 +710,11 @@ class HipCtx:
         if rc != 0:
             raise FlimoError(f"{_ERRS.get(rc, rc)}: {self._L.flimo_last_error(self._h).decode()}")
 
+    def _range(self, first, n):
+        """(first, n) of a range entry; ``n`` None: up to the map's end."""
+        first = int(first)
+        return first, max(self.map_size() - first, 0) if n is None else int(n)
+
     # ---- map ----
     def map_config(self, min_extent=0.2, bucket_size=2, downsample=True, cell_size=0.0):
         cfg = MapCfg(min_extent, bucket_size, int(downsample), cell_size)
@@ -776,15 +781,13 @@ class HipCtx:
         """The stored points first .. first + n - 1 (``n`` None: up to the map's end) that belong to no surface, by the statistics
         of their k nearest neighbours -- flimo_map_outliers; ``cfg``: the fields of ``outlier_cfg``.  Returns a dict: ``mask`` [n]
         bool, ``mean_dist`` [n] float64, ``cnt`` [n] int32 (those named in ``want``) and ``stats``; changes nothing."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         return outliers_call(lambda *a: self._chk(self._L.flimo_map_outliers(self._h, first, n, *a)), n, want, cfg)
 
     def map_remove_outliers(self, first=0, n=None, **cfg):
         """Forget the outliers of ``map_outliers`` -- flimo_map_remove_outliers; afterwards the map is as after ``map_crop_box``.
         Returns (points removed, stats)."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         k = outlier_cfg(**cfg)
         removed = C.c_size_t(0)
         st = OutlierStats()
@@ -800,8 +803,7 @@ class HipCtx:
         end) -- flimo_map_fpfh; ``cfg``: the fields of ``fpfh_cfg`` (k, max_dist, normal_k, normal_max_dist, normal_min_pts,
         viewpoint).  Returns a dict: ``fpfh`` [n, 33] float32, and of ``want`` ``spfh`` [n, 33] uint8, ``cnt`` [n] int32.  The
         normals and the SPFH rows are formed for the whole map whatever the range; changes nothing."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         return fpfh_call(lambda *a: self._chk(self._L.flimo_map_fpfh(self._h, first, n, *a)), n, want, cfg)
 
     def set_fpfh_chunk(self, n):
@@ -814,8 +816,7 @@ class HipCtx:
         gamma21, gamma32, nms_k, nms_max_dist).  Returns a dict: ``mask`` [n] bool, ``count``, ``index`` (the ascending int64 indices of
         the ones, relative to ``first``), and of ``want`` ``saliency`` [n] float64 (NaN: not salient), ``cnt`` [n] int32.  The
         saliency is formed for the whole map whatever the range; changes nothing."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         return keypoints_call(lambda *a: self._chk(self._L.flimo_map_keypoints(self._h, first, n, *a)), n, want, cfg)
 
     def set_keypoints_chunk(self, n):
@@ -828,15 +829,13 @@ class HipCtx:
         dict: of ``want`` ``label`` [n] int32 (the smallest insertion index of the point's component), ``size`` [n] int32, ``mask``
         [n] bool (the component is selected), and ``stats``.  The components are the whole map's whatever the range; changes
         nothing.  ``api.cluster_lists`` turns the labels into PCL's index lists."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         return clusters_call(lambda *a: self._chk(self._L.flimo_map_clusters(self._h, first, n, *a)), n, want, cfg)
 
     def map_remove_clusters(self, first=0, n=None, **cfg):
         """Forget the points of the range whose ``map_clusters`` mask is set -- flimo_map_remove_clusters; afterwards the map is as
         after ``map_crop_box``.  Returns (points removed, stats)."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         k = cluster_cfg(**cfg)
         removed = C.c_size_t(0)
         st = ClusterStats()
@@ -858,16 +857,14 @@ class HipCtx:
     def map_plane_mask(self, sel=None, first=0, n=None, want_mask=True, **kw):
         """The stored points first .. first + n - 1 against one plane -- flimo_map_plane_mask.  ``sel``: a ``PlaneSel``, or its
         fields as keywords (normal, anchor, dist, side).  Returns (mask [n] bool or None, count).  Changes nothing."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         sel = _as_plane_sel(sel, kw)
         return plane_mask_call(lambda *a: self._chk(self._L.flimo_map_plane_mask(self._h, first, n, *a)), n, sel, want_mask)
 
     def map_remove_plane(self, sel=None, first=0, n=None, **kw):
         """Forget the points of the range whose ``map_plane_mask`` is set -- flimo_map_remove_plane; afterwards the map is as after
         ``map_crop_box``.  Returns the number of points removed."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         sel = _as_plane_sel(sel, kw)
         removed = C.c_size_t(0)
         self._chk(self._L.flimo_map_remove_plane(self._h, first, n, C.byref(sel), C.byref(removed)))
@@ -888,15 +885,13 @@ class HipCtx:
         """The voxel and the thinning mask of the stored points first .. first + n - 1 -- flimo_map_voxel_mask: a dict with
         ``voxel`` [n] (the position of the point's voxel in ``map_voxels``' listing, -1 outside the lattice), ``mask`` [n] bool
         (True: ``map_thin`` would forget the point) and ``stats``.  Changes nothing."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         return voxel_mask_call(lambda *a: self._chk(self._L.flimo_map_voxel_mask(self._h, first, n, *a)), n, want, cfg)
 
     def map_thin(self, first=0, n=None, **cfg):
         """Forget the points of the range ``map_voxel_mask`` marks -- flimo_map_thin; afterwards the map is as after ``map_crop_box``.
         Returns (removed, stats)."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         k = voxel_cfg(**cfg)
         removed = C.c_size_t(0)
         st = VoxelStats()

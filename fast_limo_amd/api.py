@@ -403,108 +403,103 @@ class Localizer:
         return int(self._L.flimo_loc_last_carve_removed(self._h))
 
     @staticmethod
-    def _outliers_chk(rc, what):
+    def _entry_chk(rc, what):
         if rc != 0:
             raise FlimoError(f"{what} failed ({rc})")
+
+    def _range(self, first, n):
+        """(first, n) of a range entry; ``n`` None: up to the map's end."""
+        first = int(first)
+        return first, max(self.map_size() - first, 0) if n is None else int(n)
 
     def map_outliers(self, first=0, n=None, want=("mask", "mean_dist", "cnt"), **cfg):
         """The map's outliers by neighbour statistics (flimo_loc_map_outliers), as ``HipCtx.map_outliers``.  Waits for an insert, a
         crop or a carve still running; changes nothing.  No policy calls it: when to clean is the caller's schedule."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
-        return _lib.outliers_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_outliers(self._h, first, n, *a), "flimo_loc_map_outliers"),
+        first, n = self._range(first, n)
+        return _lib.outliers_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_outliers(self._h, first, n, *a), "flimo_loc_map_outliers"),
                                   n, want, cfg)
 
     def map_remove_outliers(self, first=0, n=None, **cfg):
         """Forget them (flimo_loc_map_remove_outliers), as ``HipCtx.map_remove_outliers``: (points removed, stats)."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         k = _lib.outlier_cfg(**cfg)
         removed = C.c_size_t(0)
         st = _lib.OutlierStats()
-        self._outliers_chk(self._L.flimo_loc_map_remove_outliers(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
-                           "flimo_loc_map_remove_outliers")
+        self._entry_chk(self._L.flimo_loc_map_remove_outliers(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
+                        "flimo_loc_map_remove_outliers")
         return int(removed.value), st.as_dict()
 
     def map_fpfh(self, first=0, n=None, want=("spfh", "cnt"), **cfg):
         """FPFH descriptors of the map's stored points (flimo_loc_map_fpfh), as ``HipCtx.map_fpfh``.  Waits for an insert, a crop or
         a carve still running; changes nothing.  The Localizer's own update does not use it."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
-        return _lib.fpfh_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_fpfh(self._h, first, n, *a), "flimo_loc_map_fpfh"), n, want, cfg)
+        first, n = self._range(first, n)
+        return _lib.fpfh_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_fpfh(self._h, first, n, *a), "flimo_loc_map_fpfh"), n, want, cfg)
 
     def map_keypoints(self, first=0, n=None, want=("saliency", "cnt"), **cfg):
         """ISS keypoints of the map's stored points (flimo_loc_map_keypoints), as ``HipCtx.map_keypoints``.  Waits for an insert, a
         crop or a carve still running; changes nothing.  The Localizer's own update does not use it."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
-        return _lib.keypoints_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_keypoints(self._h, first, n, *a), "flimo_loc_map_keypoints"),
+        first, n = self._range(first, n)
+        return _lib.keypoints_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_keypoints(self._h, first, n, *a), "flimo_loc_map_keypoints"),
                                    n, want, cfg)
 
     def map_clusters(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
         """Euclidean clusters of the map's stored points (flimo_loc_map_clusters), as ``HipCtx.map_clusters``.  Waits for an insert, a
         crop or a carve still running; changes nothing.  No policy calls it: when to clean is the caller's schedule."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
-        return _lib.clusters_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_clusters(self._h, first, n, *a), "flimo_loc_map_clusters"),
+        first, n = self._range(first, n)
+        return _lib.clusters_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_clusters(self._h, first, n, *a), "flimo_loc_map_clusters"),
                                   n, want, cfg)
 
     def map_remove_clusters(self, first=0, n=None, **cfg):
         """Forget the selected clusters' points of the range (flimo_loc_map_remove_clusters), as ``HipCtx.map_remove_clusters``:
         (points removed, stats)."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         k = _lib.cluster_cfg(**cfg)
         removed = C.c_size_t(0)
         st = _lib.ClusterStats()
-        self._outliers_chk(self._L.flimo_loc_map_remove_clusters(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
-                           "flimo_loc_map_remove_clusters")
+        self._entry_chk(self._L.flimo_loc_map_remove_clusters(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
+                        "flimo_loc_map_remove_clusters")
         return int(removed.value), st.as_dict()
 
     def map_planes(self, tri, want=("plane",), **cfg):
         """RANSAC plane hypotheses over the map's stored points (flimo_loc_map_planes), as ``HipCtx.map_planes``.  Waits for an
         insert, a crop or a carve still running; changes nothing.  No policy calls it."""
-        return _lib.planes_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_planes(self._h, *a), "flimo_loc_map_planes"), tri, want, cfg)
+        return _lib.planes_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_planes(self._h, *a), "flimo_loc_map_planes"), tri, want, cfg)
 
     def map_plane_mask(self, sel=None, first=0, n=None, want_mask=True, **kw):
         """The stored points of a range against one plane (flimo_loc_map_plane_mask), as ``HipCtx.map_plane_mask``: (mask, count)."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         sel = _lib._as_plane_sel(sel, kw)
-        return _lib.plane_mask_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_plane_mask(self._h, first, n, *a), "flimo_loc_map_plane_mask"),
+        return _lib.plane_mask_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_plane_mask(self._h, first, n, *a), "flimo_loc_map_plane_mask"),
                                     n, sel, want_mask)
 
     def map_remove_plane(self, sel=None, first=0, n=None, **kw):
         """Forget the points of the range inside one plane's gate (flimo_loc_map_remove_plane), as ``HipCtx.map_remove_plane``: the
         number of points removed."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         sel = _lib._as_plane_sel(sel, kw)
         removed = C.c_size_t(0)
-        self._outliers_chk(self._L.flimo_loc_map_remove_plane(self._h, first, n, C.byref(sel), C.byref(removed)), "flimo_loc_map_remove_plane")
+        self._entry_chk(self._L.flimo_loc_map_remove_plane(self._h, first, n, C.byref(sel), C.byref(removed)), "flimo_loc_map_remove_plane")
         return int(removed.value)
 
     def map_voxels(self, want=("ijk", "count", "centroid"), **cfg):
         """The voxels of the map's stored points (flimo_loc_map_voxels), as ``HipCtx.map_voxels``.  Waits for an insert, a crop or a
         carve still running; changes nothing.  No policy calls it."""
-        return _lib.voxels_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_voxels(self._h, *a), "flimo_loc_map_voxels"),
+        return _lib.voxels_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_voxels(self._h, *a), "flimo_loc_map_voxels"),
                                 self.map_size(), want, cfg)
 
     def map_voxel_mask(self, first=0, n=None, want=("voxel", "mask"), **cfg):
         """The voxel and the thinning mask of a range of stored points (flimo_loc_map_voxel_mask), as ``HipCtx.map_voxel_mask``."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
-        return _lib.voxel_mask_call(lambda *a: self._outliers_chk(self._L.flimo_loc_map_voxel_mask(self._h, first, n, *a), "flimo_loc_map_voxel_mask"),
+        first, n = self._range(first, n)
+        return _lib.voxel_mask_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_voxel_mask(self._h, first, n, *a), "flimo_loc_map_voxel_mask"),
                                     n, want, cfg)
 
     def map_thin(self, first=0, n=None, **cfg):
         """Forget the points of the range that crowd their voxel (flimo_loc_map_thin), as ``HipCtx.map_thin``: (removed, stats)."""
-        first = int(first)
-        n = max(self.map_size() - first, 0) if n is None else int(n)
+        first, n = self._range(first, n)
         k = _lib.voxel_cfg(**cfg)
         removed = C.c_size_t(0)
         st = _lib.VoxelStats()
-        self._outliers_chk(self._L.flimo_loc_map_thin(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)), "flimo_loc_map_thin")
+        self._entry_chk(self._L.flimo_loc_map_thin(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)), "flimo_loc_map_thin")
         return int(removed.value), st.as_dict()
 
     def voxel_cloud(self, res):
@@ -604,15 +599,15 @@ class Localizer:
         """The consistency graph of point correspondences and its core numbers on the map's context (flimo_loc_corr_graph): the dict
         of ``HipCtx.corr_graph``.  Waits for an insert, a crop or a carve still running behind the last sweep; reads neither the map
         nor the resident scan.  The Localizer's own update does not use it."""
-        return _lib.corr_graph_call(lambda *a: self._outliers_chk(self._L.flimo_loc_corr_graph(self._h, *a), "flimo_loc_corr_graph"), src, dst,
+        return _lib.corr_graph_call(lambda *a: self._entry_chk(self._L.flimo_loc_corr_graph(self._h, *a), "flimo_loc_corr_graph"), src, dst,
                                     want, cfg)
 
     def desc_ref_set(self, desc):
         """``desc`` [nr, dim] becomes the resident reference set of ``desc_match`` on the map's context (flimo_loc_desc_ref_set), as
         ``HipCtx.desc_ref_set``.  Waits for an insert, a crop or a carve still running; reads neither the map nor the scan."""
         d = _lib.desc_rows(desc)
-        self._outliers_chk(self._L.flimo_loc_desc_ref_set(self._h, d.ctypes.data if d.size else None, d.shape[0], d.shape[1] if d.shape[0] else 0),
-                           "flimo_loc_desc_ref_set")
+        self._entry_chk(self._L.flimo_loc_desc_ref_set(self._h, d.ctypes.data if d.size else None, d.shape[0], d.shape[1] if d.shape[0] else 0),
+                        "flimo_loc_desc_ref_set")
 
     def desc_ref_size(self) -> int:
         return self.hip.desc_ref_size()
@@ -620,7 +615,7 @@ class Localizer:
     def desc_match(self, q, k=2):
         """Nearest rows of the resident reference set (flimo_loc_desc_match): the dict of ``HipCtx.desc_match``.  The Localizer's own
         update does not use it."""
-        return _lib.desc_match_call(lambda *a: self._outliers_chk(self._L.flimo_loc_desc_match(self._h, *a), "flimo_loc_desc_match"), q, k)
+        return _lib.desc_match_call(lambda *a: self._entry_chk(self._L.flimo_loc_desc_match(self._h, *a), "flimo_loc_desc_match"), q, k)
 
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))

@@ -1113,8 +1113,8 @@ extern "C" int flimo_map_add(flimo_ctx* c, const float* xyz, size_t n, size_t st
 //     that names map positions goes: the pruning bound, the neighbour records behind flimo_match_fetch, a pass queued ahead.
 // d_map_raw, pt_leaf and d_map_sorted keep their capacity: the next adds re-use the freed tail.  The book's per-batch scratch
 // (sized by the kept count for this one call) and the transient buffer are released before the call returns.
-// (steps 2-3, shared with flimo_map_carve: kept_pts [kept] is what the compaction left, bb the kept points' box; calls / points: the
-// entry's own counters)
+// (steps 2-3, shared with flimo_map_carve and map_remove_masked: kept_pts [kept] is what the compaction left, bb the kept points'
+// box; calls / points: the entry's own counters)
 static int map_keep_only(flimo_ctx* c, const float4* kept_pts, size_t kept, size_t n_old, const float bb[6], uint64_t* calls, uint64_t* points,
                          size_t* removed, const char* what) {
   if (kept > n_old) return fail(c, FLIMO_ERR_HIP, "%s: compaction reported %zu of %zu points", what, kept, n_old);
@@ -1144,6 +1144,34 @@ static int map_keep_only(flimo_ctx* c, const float4* kept_pts, size_t kept, size
   if (c->map_n != kept) return fail(c, FLIMO_ERR_HIP, "%s: %zu of the %zu kept points were stored", what, c->map_n, kept);
   return FLIMO_OK;
 }
+// the transient buffer a compaction writes the kept points into: released on every exit path
+struct KeptPts {
+  float4* p = nullptr;
+  KeptPts() = default;
+  KeptPts(const KeptPts&) = delete;
+  KeptPts& operator=(const KeptPts&) = delete;
+  ~KeptPts() { (void)hipFree(p); }
+};
+// blocks of a compaction launch: two a compute unit
+static int compact_blocks(const flimo_ctx* c) {
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  return 2 * cus;
+}
+// What the mask-driven removals share: the points of [first, first + n) whose byte of d_mask (device, [n]) is set go, `marked` of
+// them by the entry's own count; then steps 2-3 above.  calls / points: the entry's own counters; what: its name in the messages.
+static int map_remove_masked(flimo_ctx* c, const unsigned char* d_mask, size_t first, size_t n, size_t marked, uint64_t* calls, uint64_t* points,
+                             size_t* removed, const char* what) {
+  const size_t n_old = c->map_n;
+  KeptPts kept_pts;
+  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
+  const int blocks = compact_blocks(c);
+  size_t kept = 0;
+  float bb[6];
+  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d_mask, first, n, kept_pts.p, blocks, c->scratch, &kept, bb));
+  if (kept != n_old - marked) return fail(c, FLIMO_ERR_HIP, "%s: the compaction kept %zu of %zu points, %zu marked", what, kept, n_old, marked);
+  return map_keep_only(c, kept_pts.p, kept, n_old, bb, calls, points, removed, what);
+}
 extern "C" int flimo_map_crop_box(flimo_ctx* c, const float lo[3], const float hi[3], size_t* removed) {
   if (removed) *removed = 0;
   if (!c) return FLIMO_ERR_INVALID;
@@ -1153,13 +1181,12 @@ extern "C" int flimo_map_crop_box(flimo_ctx* c, const float lo[3], const float h
   if (c->map_n == 0) return FLIMO_OK;
   ctx_enter(c);
   const size_t n_old = c->map_n;
-  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
+  KeptPts kept_pts;
   HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  const int blocks = compact_blocks(c);
   size_t kept = 0;
   float bb[6];
-  HIPCHK(c, map_crop_compact(c->stream, c->d_map_raw, n_old, lo, hi, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
+  HIPCHK(c, map_crop_compact(c->stream, c->d_map_raw, n_old, lo, hi, kept_pts.p, blocks, c->scratch, &kept, bb));
   return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->crops, &c->crop_removed, removed, "crop box");
 }
 extern "C" int flimo_map_crop_stats(const flimo_ctx* c, uint64_t out[2]) {
@@ -1238,13 +1265,12 @@ extern "C" int flimo_map_carve(flimo_ctx* c, const double x26[26], const float s
   ctx_enter(c);
   const size_t n_old = c->map_n;
   { const int rc = carve_build_image(c, x26, K); if (rc) return rc; }
-  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
+  KeptPts kept_pts;
   HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+  const int blocks = compact_blocks(c);
   size_t kept = 0;
   float bb[6];
-  HIPCHK(c, map_carve_compact(c->stream, c->d_map_raw, n_old, K, lo, hi, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
+  HIPCHK(c, map_carve_compact(c->stream, c->d_map_raw, n_old, K, lo, hi, kept_pts.p, blocks, c->scratch, &kept, bb));
   return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->carves, &c->carve_removed, removed, "carve");
 }
 extern "C" int flimo_map_carve_stats(const flimo_ctx* c, uint64_t out[2]) {
@@ -1276,6 +1302,29 @@ static int ensure_index(flimo_ctx* c) { return !c->grid_valid && c->map_n > 0 ? 
 // the distance gate of the k-NN entries; what: the caller's name in the message
 static int check_gate(flimo_ctx* c, const char* what, float max_dist) {
   if (std::isnan(max_dist) || max_dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: max_dist must be >= 0 or INFINITY", what);
+  return FLIMO_OK;
+}
+// the stored points [first, first + n) of the range entries (no first + n is formed: it could wrap)
+static int check_range(flimo_ctx* c, const char* what, size_t first, size_t n) {
+  if (first > c->map_n || n > c->map_n - first)
+    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
+  return FLIMO_OK;
+}
+// the entries whose kernels index the stored points with 32 bits
+static int check_map_size(flimo_ctx* c, const char* what) {
+  if (c->map_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the map must hold fewer than 2^31 points", what);
+  return FLIMO_OK;
+}
+// the entries that search a map they know is not empty: its index, or a failure
+static int need_index(flimo_ctx* c, const char* what) {
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "%s: a map of %zu points has no index", what, c->map_n);
+  return FLIMO_OK;
+}
+// the setters of the entries' chunk sizes: 0 puts the default back
+static int set_chunk(flimo_ctx* c, size_t flimo_ctx::*chunk, size_t n, size_t dflt) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->*chunk = n ? n : dflt;
   return FLIMO_OK;
 }
 
@@ -1515,14 +1564,10 @@ extern "C" int flimo_map_normals(flimo_ctx* c, const float* q, size_t nq, int k,
 extern "C" int flimo_map_normals_range(flimo_ctx* c, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3],
                                        float* normal, int32_t* cnt, double* centroid, double* cov, double* eig) {
   if (!c) return FLIMO_ERR_INVALID;
-  if (first > c->map_n || n > c->map_n - first) return fail(c, FLIMO_ERR_INVALID, "map normals: the range [%zu, %zu + %zu) ends beyond the map's %zu points", first, first, n, c->map_n);
+  { const int rc = check_range(c, "map normals", first, n); if (rc) return rc; }
   return normals_run(c, nullptr, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
 }
-extern "C" int flimo_set_normals_chunk(flimo_ctx* c, size_t n) {
-  if (!c) return FLIMO_ERR_INVALID;
-  c->normals_chunk = n ? n : (size_t)1 << 20;
-  return FLIMO_OK;
-}
+extern "C" int flimo_set_normals_chunk(flimo_ctx* c, size_t n) { return set_chunk(c, &flimo_ctx::normals_chunk, n, (size_t)1 << 20); }
 
 // ---- outliers by neighbour statistics (PCL's StatisticalOutlierRemoval / RadiusOutlierRemoval over the map) --------------------
 // kernels: flimo_knn_k.hip.  The search runs in chunks of c->outlier_chunk points into mean[] / cnt[] of the WHOLE range (12 B a
@@ -1537,8 +1582,7 @@ static void outlier_stats_none(flimo_outlier_stats* s) {
 static int outlier_check(flimo_ctx* c, size_t first, size_t n, const flimo_outlier_cfg* cfg, const char* what) {
   static_assert(FLIMO_KNN_MAX_K == KNNK_MAX_K, "the header's limit is the kernels'");
   if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
-  if (first > c->map_n || n > c->map_n - first)
-    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
+  { const int rc = check_range(c, what, first, n); if (rc) return rc; }
   { const int rc = check_gate(c, what, cfg->max_dist); if (rc) return rc; }
   if (std::isnan(cfg->std_mul) || cfg->std_mul < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: std_mul must be >= 0 or INFINITY", what);
   if (cfg->k < 1 || cfg->k > FLIMO_KNN_MAX_K - 1) return fail(c, FLIMO_ERR_UNSUPPORTED, "%s: k must be in 1..%d", what, FLIMO_KNN_MAX_K - 1);
@@ -1552,8 +1596,7 @@ struct OutlierDev {      // what outliers_device leaves on the device for its ca
 // the predicate over [first, first + n), n > 0, arguments checked: d.mean, d.cnt, d.mask filled on the device, *st on the host; ends
 // synchronised
 static int outliers_device(flimo_ctx* c, size_t first, size_t n, const flimo_outlier_cfg& cfg, OutlierDev& d, flimo_outlier_stats* st) {
-  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
-  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map outliers: a map of %zu points has no index", c->map_n);
+  { const int rc = need_index(c, "map outliers"); if (rc) return rc; }
   ctx_enter(c);
   const size_t m = std::min(std::min(n, std::max<size_t>(c->outlier_chunk, 1)), (size_t)1 << 24);
   const unsigned nseg = outlier_segments(n);
@@ -1630,23 +1673,9 @@ extern "C" int flimo_map_remove_outliers(flimo_ctx* c, size_t first, size_t n, c
   if (removed) *removed = 0;
   if (stats) *stats = st;
   if (st.outliers == 0) return FLIMO_OK;               // removing nothing changes nothing
-  const size_t n_old = c->map_n;
-  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
-  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
-  size_t kept = 0;
-  float bb[6];
-  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d.mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
-  if (kept != n_old - (size_t)st.outliers)
-    return fail(c, FLIMO_ERR_HIP, "remove outliers: the compaction kept %zu of %zu points, %llu marked", kept, n_old, (unsigned long long)st.outliers);
-  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->outlier_removals, &c->outlier_removed, removed, "remove outliers");
+  return map_remove_masked(c, d.mask, first, n, (size_t)st.outliers, &c->outlier_removals, &c->outlier_removed, removed, "remove outliers");
 }
-extern "C" int flimo_set_outlier_chunk(flimo_ctx* c, size_t n) {
-  if (!c) return FLIMO_ERR_INVALID;
-  c->outlier_chunk = n ? n : (size_t)1 << 20;
-  return FLIMO_OK;
-}
+extern "C" int flimo_set_outlier_chunk(flimo_ctx* c, size_t n) { return set_chunk(c, &flimo_ctx::outlier_chunk, n, (size_t)1 << 20); }
 
 // ---- FPFH descriptors of the stored points (pcl::FPFHEstimation over the map) ---------------------------------------------------
 // kernels: flimo_knn_k.hip.  Three stages on the context's stream, the first two over the WHOLE map whatever the range (a neighbour
@@ -1657,8 +1686,7 @@ extern "C" int flimo_set_outlier_chunk(flimo_ctx* c, size_t n) {
 extern "C" int flimo_map_fpfh(flimo_ctx* c, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh, uint8_t* spfh, int32_t* cnt) {
   if (!c) return FLIMO_ERR_INVALID;
   if (!cfg) return fail(c, FLIMO_ERR_INVALID, "map fpfh: null cfg");
-  if (first > c->map_n || n > c->map_n - first)
-    return fail(c, FLIMO_ERR_INVALID, "map fpfh: the range [%zu, %zu + %zu) ends beyond the map's %zu points", first, first, n, c->map_n);
+  { const int rc = check_range(c, "map fpfh", first, n); if (rc) return rc; }
   if (n > 0 && !fpfh) return fail(c, FLIMO_ERR_INVALID, "map fpfh: null fpfh");
   { const int rc = check_gate(c, "map fpfh", cfg->max_dist); if (rc) return rc; }
   { const int rc = check_gate(c, "map fpfh (normals)", cfg->normal_max_dist); if (rc) return rc; }
@@ -1669,9 +1697,8 @@ extern "C" int flimo_map_fpfh(flimo_ctx* c, size_t first, size_t n, const flimo_
   if (cfg->normal_k < 1 || cfg->normal_k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map fpfh: normal_k must be in 1..%d", FLIMO_KNN_MAX_K);
   if (n == 0) return FLIMO_OK;
   const size_t N = c->map_n;
-  if (N >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map fpfh: the map must hold fewer than 2^31 points");
-  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
-  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map fpfh: a map of %zu points has no index", N);
+  { const int rc = check_map_size(c, "map fpfh"); if (rc) return rc; }
+  { const int rc = need_index(c, "map fpfh"); if (rc) return rc; }
   ctx_enter(c);
   DevScratch d;
   const size_t m = std::min(N, std::max<size_t>(c->fpfh_chunk, 1));      // points of a chunk, of the map's stages and of the range's
@@ -1704,11 +1731,7 @@ extern "C" int flimo_map_fpfh(flimo_ctx* c, size_t first, size_t n, const flimo_
   }
   return FLIMO_OK;
 }
-extern "C" int flimo_set_fpfh_chunk(flimo_ctx* c, size_t n) {
-  if (!c) return FLIMO_ERR_INVALID;
-  c->fpfh_chunk = n ? n : (size_t)1 << 20;
-  return FLIMO_OK;
-}
+extern "C" int flimo_set_fpfh_chunk(flimo_ctx* c, size_t n) { return set_chunk(c, &flimo_ctx::fpfh_chunk, n, (size_t)1 << 20); }
 
 // ---- ISS keypoints of the stored points (pcl::ISSKeypoint3D over the map) -------------------------------------------------------
 // kernels: flimo_knn_k.hip.  Two stages on the context's stream, in chunks of c->keypoints_chunk points: the saliency of the WHOLE
@@ -1720,8 +1743,7 @@ extern "C" int flimo_map_keypoints(flimo_ctx* c, size_t first, size_t n, const f
                                    int32_t* cnt, size_t* count) {
   if (!c) return FLIMO_ERR_INVALID;
   if (!cfg) return fail(c, FLIMO_ERR_INVALID, "map keypoints: null cfg");
-  if (first > c->map_n || n > c->map_n - first)
-    return fail(c, FLIMO_ERR_INVALID, "map keypoints: the range [%zu, %zu + %zu) ends beyond the map's %zu points", first, first, n, c->map_n);
+  { const int rc = check_range(c, "map keypoints", first, n); if (rc) return rc; }
   { const int rc = check_gate(c, "map keypoints", cfg->max_dist); if (rc) return rc; }
   { const int rc = check_gate(c, "map keypoints (suppression)", cfg->nms_max_dist); if (rc) return rc; }
   if (!(cfg->gamma21 > 0.f && cfg->gamma21 <= 1.f) || !(cfg->gamma32 > 0.f && cfg->gamma32 <= 1.f))
@@ -1730,10 +1752,9 @@ extern "C" int flimo_map_keypoints(flimo_ctx* c, size_t first, size_t n, const f
   if (cfg->k < 3 || cfg->k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map keypoints: k must be in 3..%d", FLIMO_KNN_MAX_K);
   if (cfg->nms_k < 2 || cfg->nms_k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "map keypoints: nms_k must be in 2..%d", FLIMO_KNN_MAX_K);
   const size_t N = c->map_n;
-  if (N >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map keypoints: the map must hold fewer than 2^31 points");
+  { const int rc = check_map_size(c, "map keypoints"); if (rc) return rc; }
   if (n == 0) { if (count) *count = 0; return FLIMO_OK; }
-  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
-  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map keypoints: a map of %zu points has no index", N);
+  { const int rc = need_index(c, "map keypoints"); if (rc) return rc; }
   ctx_enter(c);
   DevScratch d;
   const size_t m = std::min(N, std::max<size_t>(c->keypoints_chunk, 1));      // points of a chunk, of the map's stage and of the range's
@@ -1769,11 +1790,7 @@ extern "C" int flimo_map_keypoints(flimo_ctx* c, size_t first, size_t n, const f
   if (count) *count = (size_t)h_count;
   return FLIMO_OK;
 }
-extern "C" int flimo_set_keypoints_chunk(flimo_ctx* c, size_t n) {
-  if (!c) return FLIMO_ERR_INVALID;
-  c->keypoints_chunk = n ? n : (size_t)1 << 20;
-  return FLIMO_OK;
-}
+extern "C" int flimo_set_keypoints_chunk(flimo_ctx* c, size_t n) { return set_chunk(c, &flimo_ctx::keypoints_chunk, n, (size_t)1 << 20); }
 
 // ---- Euclidean clusters of the stored points (pcl::EuclideanClusterExtraction over the map) -------------------------------------
 // kernels: flimo_cluster.hip.  Four launches on the context's stream over the WHOLE map whatever the range (a component can reach
@@ -1785,13 +1802,11 @@ static void cluster_stats_none(flimo_cluster_stats* s) {
 }
 static int cluster_check(flimo_ctx* c, size_t first, size_t n, const flimo_cluster_cfg* cfg, const char* what) {
   if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
-  if (first > c->map_n || n > c->map_n - first)
-    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
+  { const int rc = check_range(c, what, first, n); if (rc) return rc; }
   if (!(cfg->tol >= 0.f) || std::isinf(cfg->tol)) return fail(c, FLIMO_ERR_INVALID, "%s: tol must be finite and >= 0", what);
   if (cfg->min_size < 0 || cfg->max_size < 0) return fail(c, FLIMO_ERR_INVALID, "%s: min_size and max_size must be >= 0", what);
   if (cfg->max_size > 0 && cfg->max_size < cfg->min_size) return fail(c, FLIMO_ERR_INVALID, "%s: max_size must be 0 or >= min_size", what);
-  if (c->map_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the map must hold fewer than 2^31 points", what);
-  return FLIMO_OK;
+  return check_map_size(c, what);
 }
 struct ClusterDev {      // what clusters_device leaves on the device for its caller, and the owner of all it allocated
   DevScratch mem;
@@ -1801,10 +1816,9 @@ struct ClusterDev {      // what clusters_device leaves on the device for its ca
 // where asked for, d.label / d.size filled on the device, *st on the host; ends synchronised
 static int clusters_device(flimo_ctx* c, size_t first, size_t n, const flimo_cluster_cfg& cfg, bool want_label, bool want_size, ClusterDev& d,
                            flimo_cluster_stats* st) {
-  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
-  const size_t N = c->map_n;
-  if (!c->grid_valid) return fail(c, FLIMO_ERR_HIP, "map clusters: a map of %zu points has no index", N);
+  { const int rc = need_index(c, "map clusters"); if (rc) return rc; }
   ctx_enter(c);
+  const size_t N = c->map_n;
   const size_t m = std::min(std::min(N, std::max<size_t>(c->cluster_chunk, 1)), (size_t)1 << 24);      // (x 64 lanes: below 2^31 a launch)
   uint32_t* d_parent = d.mem.get<uint32_t>(N);
   uint32_t* d_count = d.mem.get<uint32_t>(N);
@@ -1857,23 +1871,9 @@ extern "C" int flimo_map_remove_clusters(flimo_ctx* c, size_t first, size_t n, c
   if (removed) *removed = 0;
   if (stats) *stats = st;
   if (st.sel_points == 0) return FLIMO_OK;             // removing nothing changes nothing
-  const size_t n_old = c->map_n;
-  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
-  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
-  size_t kept = 0;
-  float bb[6];
-  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d.mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
-  if (kept != n_old - (size_t)st.sel_points)
-    return fail(c, FLIMO_ERR_HIP, "remove clusters: the compaction kept %zu of %zu points, %llu marked", kept, n_old, (unsigned long long)st.sel_points);
-  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->cluster_removals, &c->cluster_removed, removed, "remove clusters");
+  return map_remove_masked(c, d.mask, first, n, (size_t)st.sel_points, &c->cluster_removals, &c->cluster_removed, removed, "remove clusters");
 }
-extern "C" int flimo_set_cluster_chunk(flimo_ctx* c, size_t n) {
-  if (!c) return FLIMO_ERR_INVALID;
-  c->cluster_chunk = n ? n : (size_t)1 << 20;
-  return FLIMO_OK;
-}
+extern "C" int flimo_set_cluster_chunk(flimo_ctx* c, size_t n) { return set_chunk(c, &flimo_ctx::cluster_chunk, n, (size_t)1 << 20); }
 
 // ---- RANSAC planes of the stored points (pcl::SACSegmentation's sample, model and count; ExtractIndices for the removal) ----------
 // kernels: flimo_plane.hip.  The triplets go up once; the hypotheses run in chunks of c->plane_chunk: per chunk the solve, the count
@@ -1946,21 +1946,15 @@ extern "C" int flimo_plane_solve_host(const float p3[9], const flimo_plane_cfg* 
   if (!p3 || !cfg || !plane4 || !nf || !plane_cfg_ok(cfg)) return FLIMO_ERR_INVALID;
   return plane_solve(p3, cfg->min_edge, cfg->min_sin, cfg->axis, cfg->min_cos, plane4, nf);
 }
-extern "C" int flimo_set_plane_chunk(flimo_ctx* c, size_t n) {
-  if (!c) return FLIMO_ERR_INVALID;
-  c->plane_chunk = n ? n : (size_t)1 << 10;
-  return FLIMO_OK;
-}
+extern "C" int flimo_set_plane_chunk(flimo_ctx* c, size_t n) { return set_chunk(c, &flimo_ctx::plane_chunk, n, (size_t)1 << 10); }
 static int plane_sel_check(flimo_ctx* c, size_t first, size_t n, const flimo_plane_sel* sel, const char* what) {
   if (!sel) return fail(c, FLIMO_ERR_INVALID, "%s: null sel", what);
   for (int a = 0; a < 3; a++)
     if (!std::isfinite(sel->normal[a]) || !std::isfinite(sel->anchor[a])) return fail(c, FLIMO_ERR_INVALID, "%s: normal and anchor must be finite", what);
   if (std::isnan(sel->dist) || sel->dist < 0.f) return fail(c, FLIMO_ERR_INVALID, "%s: dist must be >= 0 or INFINITY", what);
   if (sel->side < -1 || sel->side > 1) return fail(c, FLIMO_ERR_INVALID, "%s: side must be -1, 0 or 1", what);
-  if (first > c->map_n || n > c->map_n - first)
-    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
-  if (c->map_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the map must hold fewer than 2^31 points", what);
-  return FLIMO_OK;
+  { const int rc = check_range(c, what, first, n); if (rc) return rc; }
+  return check_map_size(c, what);
 }
 // the mask of the range on the device (d_mask [n], may be null) and its ones; arguments checked, n > 0; ends synchronised
 static int plane_mask_device(flimo_ctx* c, size_t first, size_t n, const flimo_plane_sel& sel, unsigned char* d_mask, unsigned* d_count, size_t* count) {
@@ -2006,16 +2000,7 @@ extern "C" int flimo_map_remove_plane(flimo_ctx* c, size_t first, size_t n, cons
   { const int rc = plane_mask_device(c, first, n, *sel, d_mask, d_count, &ones); if (rc) return rc; }
   if (removed) *removed = 0;
   if (ones == 0) return FLIMO_OK;                      // removing nothing changes nothing
-  const size_t n_old = c->map_n;
-  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
-  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
-  size_t kept = 0;
-  float bb[6];
-  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d_mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
-  if (kept != n_old - ones) return fail(c, FLIMO_ERR_HIP, "remove plane: the compaction kept %zu of %zu points, %zu marked", kept, n_old, ones);
-  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->plane_removals, &c->plane_removed, removed, "remove plane");
+  return map_remove_masked(c, d_mask, first, n, ones, &c->plane_removals, &c->plane_removed, removed, "remove plane");
 }
 
 // ---- voxel statistics and thinning of the stored points (pcl::VoxelGrid's leaves over the map, on a lattice that stays put) -------
@@ -2038,10 +2023,8 @@ static int voxel_check(flimo_ctx* c, size_t first, size_t n, const flimo_voxel_c
   if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
   if (!voxel_cfg_ok(cfg))
     return fail(c, FLIMO_ERR_INVALID, "%s: leaf must be finite and > 0 with a finite 1 / leaf, keep 0 or 1, max_pts >= 1 (1 with keep nearest)", what);
-  if (first > c->map_n || n > c->map_n - first)
-    return fail(c, FLIMO_ERR_INVALID, "%s: the range [%zu, %zu + %zu) ends beyond the map's %zu points", what, first, first, n, c->map_n);
-  if (c->map_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the map must hold fewer than 2^31 points", what);
-  return FLIMO_OK;
+  { const int rc = check_range(c, what, first, n); if (rc) return rc; }
+  return check_map_size(c, what);
 }
 struct VoxelDev {      // what voxels_device leaves on the device for its caller, and the owner of all it allocated
   DevScratch mem;
@@ -2222,17 +2205,7 @@ extern "C" int flimo_map_thin(flimo_ctx* c, size_t first, size_t n, const flimo_
   if (removed) *removed = 0;
   if (stats) *stats = st;
   if (st.sel_points == 0) return FLIMO_OK;             // removing nothing changes nothing
-  const size_t n_old = c->map_n;
-  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } kept_pts;
-  HIPCHK(c, hipMalloc(&kept_pts.p, n_old * sizeof(float4)));
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
-  size_t kept = 0;
-  float bb[6];
-  HIPCHK(c, map_mask_compact(c->stream, c->d_map_raw, n_old, d.mask, first, n, kept_pts.p, 2 * cus, c->scratch, &kept, bb));
-  if (kept != n_old - (size_t)st.sel_points)
-    return fail(c, FLIMO_ERR_HIP, "map thin: the compaction kept %zu of %zu points, %llu marked", kept, n_old, (unsigned long long)st.sel_points);
-  return map_keep_only(c, kept_pts.p, kept, n_old, bb, &c->thin_removals, &c->thin_removed, removed, "map thin");
+  return map_remove_masked(c, d.mask, first, n, (size_t)st.sel_points, &c->thin_removals, &c->thin_removed, removed, "map thin");
 }
 extern "C" int flimo_voxel_key_host(const float p[3], float leaf, int32_t ijk[3], uint64_t* key) {
   const flimo_voxel_cfg k{leaf, FLIMO_VOXEL_KEEP_FIRST, 1};

@@ -67,8 +67,15 @@ static Config to_config(const flimo_loc_cfg* c) {
   return cfg;
 }
 
+// The context of a live handle (Mapper::ctx waits for an insert, a crop or a carve on the worker thread).  Never null: see
+// flimo_loc_create.  The context answers for an empty map itself, so the forwarders below check nothing of their own.
+static flimo_ctx* ctx_of(flimo_loc* L) { return L->map->ctx(); }
+
 extern "C" {
 
+// Invariant: a flimo_loc that was handed out has a context.  Localizer::init attaches the Mapper, which creates it; without one this
+// call fails and hands out nothing; and Mapper::ctx_ is assigned in the constructor and in attach alone, never cleared afterwards.
+// "No map yet" is therefore a context whose map is empty.
 int flimo_loc_create(const flimo_loc_cfg* cfg, flimo_loc** out) {
   if (!cfg || !out) return FLIMO_ERR_INVALID;
   *out = nullptr;
@@ -192,8 +199,9 @@ int flimo_host_plane(const float* xyz, const float* sqd, int n, int num_match_po
 }
 int flimo_loc_map_add(flimo_loc* L, const float* xyz, size_t n, double stamp) {
   if (!L) return FLIMO_ERR_INVALID;
-  if (!L->map->ctx()) return FLIMO_ERR_NO_DEVICE;
-  return flimo_map_add(L->map->ctx(), xyz, n, 12, stamp);
+  flimo_ctx* c = ctx_of(L);
+  if (!c) return FLIMO_ERR_NO_DEVICE;
+  return flimo_map_add(c, xyz, n, 12, stamp);
 }
 size_t flimo_loc_map_size(flimo_loc* L) { return L ? (size_t)L->map->size() : 0; }
 void flimo_loc_get_x(flimo_loc* L, double x26[26]) { L->loc->filter().get_x().to_flat(x26); }
@@ -220,261 +228,89 @@ int flimo_local_map_rule(const double p[3], const float half_extent[3], float re
 void flimo_loc_set_map_carving(flimo_loc* L, int every_n_sweeps, const flimo_carve_cfg* cfg) { if (L) L->loc->set_map_carving(every_n_sweeps, cfg); }
 int flimo_carve_rule(int every_n_sweeps, int* count) { return fast_limo::Localizer::carve_rule(every_n_sweeps, count); }
 void flimo_carve_sensor(const double x26[26], float sensor_xyz[3]) { if (x26 && sensor_xyz) fast_limo::Localizer::carve_sensor(x26, sensor_xyz); }
-// no map yet: the answer of an empty one, after the calls' own argument checks
-static int carve_of_no_map(const double x26[26], const float sensor[3], const flimo_carve_cfg* cfg) {
-  if (!x26 || !sensor || !cfg) return FLIMO_ERR_INVALID;
-  for (int t = 0; t < 7; t++) if (!std::isfinite(x26[t])) return FLIMO_ERR_INVALID;
-  for (int a = 0; a < 3; a++) if (!std::isfinite(sensor[a])) return FLIMO_ERR_INVALID;
-  if (cfg->res < 8 || cfg->res > 1024 || cfg->win < 0 || cfg->win > 3 || !(cfg->margin >= 0.f) || !(cfg->rel_margin >= 0.f) || !(cfg->max_depth > 0.f))
-    return FLIMO_ERR_INVALID;
-  return FLIMO_OK;
-}
 int flimo_loc_map_seen_through(flimo_loc* L, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg, unsigned char* mask,
                                size_t cap, size_t* count) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
-  if (!c) {
-    const int rc = carve_of_no_map(x26, sensor_xyz, cfg);
-    if (rc == FLIMO_OK && count) *count = 0;
-    return rc;
-  }
-  return flimo_map_seen_through(c, x26, sensor_xyz, cfg, mask, cap, count);
+  return flimo_map_seen_through(ctx_of(L), x26, sensor_xyz, cfg, mask, cap, count);
 }
 int flimo_loc_map_carve(flimo_loc* L, const double x26[26], const float sensor_xyz[3], const flimo_carve_cfg* cfg, const float lo[3],
                         const float hi[3], size_t* removed) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();
-  if (!c) {
-    int rc = carve_of_no_map(x26, sensor_xyz, cfg);
-    if (rc == FLIMO_OK && (lo == nullptr) != (hi == nullptr)) rc = FLIMO_ERR_INVALID;
-    if (rc == FLIMO_OK && lo)
-      for (int a = 0; a < 3; a++) if (!(lo[a] <= hi[a])) rc = FLIMO_ERR_INVALID;
-    if (rc == FLIMO_OK && removed) *removed = 0;
-    return rc;
-  }
-  return flimo_map_carve(c, x26, sensor_xyz, cfg, lo, hi, removed);
+  return flimo_map_carve(ctx_of(L), x26, sensor_xyz, cfg, lo, hi, removed);
 }
 size_t flimo_loc_last_carve_removed(flimo_loc* L) { return L ? L->map->last_carve_removed() : 0; }
-// no map yet: the answer of an empty one, after the calls' own argument checks
-static int outliers_of_no_map(size_t first, size_t n, const flimo_outlier_cfg* cfg, flimo_outlier_stats* stats) {
-  if (!cfg || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
-  if (std::isnan(cfg->max_dist) || cfg->max_dist < 0.f || std::isnan(cfg->std_mul) || cfg->std_mul < 0.f) return FLIMO_ERR_INVALID;
-  if (cfg->k < 1 || cfg->k > FLIMO_KNN_MAX_K - 1) return FLIMO_ERR_UNSUPPORTED;
-  if (cfg->min_pts < 0 || cfg->min_pts > cfg->k) return FLIMO_ERR_INVALID;
-  if (stats) {
-    stats->n = stats->n_stat = 0; stats->mu = stats->sigma = stats->threshold = (double)NAN; stats->few = stats->far = stats->outliers = 0;
-  }
-  return FLIMO_OK;
-}
 int flimo_loc_map_outliers(flimo_loc* L, size_t first, size_t n, const flimo_outlier_cfg* cfg, unsigned char* mask, double* mean_dist, int32_t* cnt,
                            flimo_outlier_stats* stats) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
-  if (!c) return outliers_of_no_map(first, n, cfg, stats);
-  return flimo_map_outliers(c, first, n, cfg, mask, mean_dist, cnt, stats);
+  return flimo_map_outliers(ctx_of(L), first, n, cfg, mask, mean_dist, cnt, stats);
 }
 int flimo_loc_map_remove_outliers(flimo_loc* L, size_t first, size_t n, const flimo_outlier_cfg* cfg, size_t* removed, flimo_outlier_stats* stats) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();
-  if (!c) {
-    const int rc = outliers_of_no_map(first, n, cfg, stats);
-    if (rc == FLIMO_OK && removed) *removed = 0;
-    return rc;
-  }
-  return flimo_map_remove_outliers(c, first, n, cfg, removed, stats);
+  return flimo_map_remove_outliers(ctx_of(L), first, n, cfg, removed, stats);
 }
 int flimo_loc_map_radius_search(flimo_loc* L, const float* q_xyz, size_t nq, float radius, unsigned flags, uint64_t* offsets, int32_t* idx,
                                 float* sqd, float* xyz, size_t cap, uint64_t* total) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
-  if (!c) {                          // no map yet: Octree::radiusSearch with root_ == nullptr
-    if (!offsets || (nq > 0 && !q_xyz)) return FLIMO_ERR_INVALID;
-    for (size_t i = 0; i <= nq; i++) offsets[i] = 0;
-    if (total) *total = 0;
-    return FLIMO_OK;
-  }
-  return flimo_radius_search(c, q_xyz, nq, radius, flags, offsets, idx, sqd, xyz, cap, total);
+  return flimo_radius_search(ctx_of(L), q_xyz, nq, radius, flags, offsets, idx, sqd, xyz, cap, total);
 }
 int flimo_loc_map_knn(flimo_loc* L, const float* q_xyz, size_t nq, int k, float max_dist, int32_t* idx, float* sqd, float* xyz, int32_t* cnt) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
-  if (!c) {                          // no map yet: Octree::knn with root_ == nullptr
-    if ((nq > 0 && !q_xyz) || !idx || !sqd || !cnt || std::isnan(max_dist) || max_dist < 0.f) return FLIMO_ERR_INVALID;
-    if (k < 1 || k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
-    if ((unsigned long long)nq * (unsigned long long)k >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
-    for (size_t i = 0; i < nq; i++) cnt[i] = 0;
-    for (size_t i = 0; i < nq * (size_t)k; i++) { idx[i] = -1; sqd[i] = 0.f; }
-    if (xyz) for (size_t i = 0; i < nq * (size_t)k * 3; i++) xyz[i] = 0.f;
-    return FLIMO_OK;
-  }
-  return flimo_knn_k(c, q_xyz, nq, k, max_dist, idx, sqd, xyz, cnt);
-}
-// no map yet: the answer of an empty one, after flimo_map_normals' own argument checks
-static int normals_of_no_map(size_t nq, int k, float max_dist, const float* viewpoint, float* normal, int32_t* cnt, double* centroid, double* cov,
-                             double* eig) {
-  if (!normal || !cnt || std::isnan(max_dist) || max_dist < 0.f) return FLIMO_ERR_INVALID;
-  if (viewpoint && (std::isnan(viewpoint[0]) || std::isnan(viewpoint[1]) || std::isnan(viewpoint[2]))) return FLIMO_ERR_INVALID;
-  if (k < 1 || k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
-  if (nq >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
-  for (size_t i = 0; i < nq; i++) cnt[i] = 0;
-  for (size_t i = 0; i < nq * 4; i++) normal[i] = NAN;
-  if (centroid) for (size_t i = 0; i < nq * 3; i++) centroid[i] = (double)NAN;
-  if (cov) for (size_t i = 0; i < nq * 6; i++) cov[i] = (double)NAN;
-  if (eig) for (size_t i = 0; i < nq * 6; i++) eig[i] = (double)NAN;
-  return FLIMO_OK;
+  return flimo_knn_k(ctx_of(L), q_xyz, nq, k, max_dist, idx, sqd, xyz, cnt);
 }
 int flimo_loc_map_normals(flimo_loc* L, const float* q_xyz, size_t nq, int k, float max_dist, int min_pts, const float viewpoint[3], float* normal,
                           int32_t* cnt, double* centroid, double* cov, double* eig) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
-  if (!c) {
-    if (nq > 0 && !q_xyz) return FLIMO_ERR_INVALID;
-    return normals_of_no_map(nq, k, max_dist, viewpoint, normal, cnt, centroid, cov, eig);
-  }
-  return flimo_map_normals(c, q_xyz, nq, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
+  return flimo_map_normals(ctx_of(L), q_xyz, nq, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
 }
 int flimo_loc_map_normals_range(flimo_loc* L, size_t first, size_t n, int k, float max_dist, int min_pts, const float viewpoint[3], float* normal,
                                 int32_t* cnt, double* centroid, double* cov, double* eig) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();
-  if (!c) {
-    if (first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (beyond the size of a map of no points)
-    return normals_of_no_map(0, k, max_dist, viewpoint, normal, cnt, centroid, cov, eig);
-  }
-  return flimo_map_normals_range(c, first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
+  return flimo_map_normals_range(ctx_of(L), first, n, k, max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig);
 }
 int flimo_loc_map_fpfh(flimo_loc* L, size_t first, size_t n, const flimo_fpfh_cfg* cfg, float* fpfh, uint8_t* spfh, int32_t* cnt) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
-  if (!c) {                          // no map yet: the answer of an empty one, after flimo_map_fpfh's own argument checks
-    if (!cfg || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
-    if (std::isnan(cfg->max_dist) || cfg->max_dist < 0.f || std::isnan(cfg->normal_max_dist) || cfg->normal_max_dist < 0.f) return FLIMO_ERR_INVALID;
-    if (cfg->has_viewpoint && (std::isnan(cfg->viewpoint[0]) || std::isnan(cfg->viewpoint[1]) || std::isnan(cfg->viewpoint[2]))) return FLIMO_ERR_INVALID;
-    if (cfg->normal_min_pts < 0) return FLIMO_ERR_INVALID;
-    if (cfg->k < 2 || cfg->k > FLIMO_KNN_MAX_K || cfg->normal_k < 1 || cfg->normal_k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
-    return FLIMO_OK;
-  }
-  return flimo_map_fpfh(c, first, n, cfg, fpfh, spfh, cnt);
+  return flimo_map_fpfh(ctx_of(L), first, n, cfg, fpfh, spfh, cnt);
 }
 int flimo_loc_map_keypoints(flimo_loc* L, size_t first, size_t n, const flimo_keypoint_cfg* cfg, unsigned char* mask, double* saliency, int32_t* cnt,
                             size_t* count) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
-  if (!c) {                          // no map yet: the answer of an empty one, after flimo_map_keypoints' own argument checks
-    if (!cfg || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
-    if (std::isnan(cfg->max_dist) || cfg->max_dist < 0.f || std::isnan(cfg->nms_max_dist) || cfg->nms_max_dist < 0.f) return FLIMO_ERR_INVALID;
-    if (!(cfg->gamma21 > 0.f && cfg->gamma21 <= 1.f) || !(cfg->gamma32 > 0.f && cfg->gamma32 <= 1.f) || cfg->min_pts < 0) return FLIMO_ERR_INVALID;
-    if (cfg->k < 3 || cfg->k > FLIMO_KNN_MAX_K || cfg->nms_k < 2 || cfg->nms_k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
-    if (count) *count = 0;
-    return FLIMO_OK;
-  }
-  return flimo_map_keypoints(c, first, n, cfg, mask, saliency, cnt, count);
-}
-// no map yet: the answer of an empty one, after flimo_map_clusters' own argument checks
-static int clusters_of_no_map(size_t first, size_t n, const flimo_cluster_cfg* cfg, flimo_cluster_stats* stats) {
-  if (!cfg || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
-  if (!(cfg->tol >= 0.f) || std::isinf(cfg->tol) || cfg->min_size < 0 || cfg->max_size < 0) return FLIMO_ERR_INVALID;
-  if (cfg->max_size > 0 && cfg->max_size < cfg->min_size) return FLIMO_ERR_INVALID;
-  if (stats) stats->n = stats->clusters = stats->largest = stats->sel_clusters = stats->sel_points = 0;
-  return FLIMO_OK;
+  return flimo_map_keypoints(ctx_of(L), first, n, cfg, mask, saliency, cnt, count);
 }
 int flimo_loc_map_clusters(flimo_loc* L, size_t first, size_t n, const flimo_cluster_cfg* cfg, int32_t* label, int32_t* size, unsigned char* mask,
                            flimo_cluster_stats* stats) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
-  if (!c) return clusters_of_no_map(first, n, cfg, stats);
-  return flimo_map_clusters(c, first, n, cfg, label, size, mask, stats);
+  return flimo_map_clusters(ctx_of(L), first, n, cfg, label, size, mask, stats);
 }
 int flimo_loc_map_remove_clusters(flimo_loc* L, size_t first, size_t n, const flimo_cluster_cfg* cfg, size_t* removed, flimo_cluster_stats* stats) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();
-  if (!c) {
-    const int rc = clusters_of_no_map(first, n, cfg, stats);
-    if (rc == FLIMO_OK && removed) *removed = 0;
-    return rc;
-  }
-  return flimo_map_remove_clusters(c, first, n, cfg, removed, stats);
-}
-// no map yet: the answers of an empty one, after the calls' own argument checks
-static bool plane_cfg_valid(const flimo_plane_cfg* k) {
-  if (std::isnan(k->dist) || k->dist < 0.f || std::isnan(k->min_edge) || k->min_edge < 0.f) return false;
-  if (std::isnan(k->min_sin) || k->min_sin < 0.f || k->min_sin > 1.f || std::isnan(k->min_cos) || k->min_cos < 0.f || k->min_cos > 1.f) return false;
-  return !(k->min_cos > 0.f && !(std::isfinite(k->axis[0]) && std::isfinite(k->axis[1]) && std::isfinite(k->axis[2])));
-}
-static int plane_sel_of_no_map(size_t first, size_t n, const flimo_plane_sel* sel) {
-  if (!sel || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
-  for (int a = 0; a < 3; a++)
-    if (!std::isfinite(sel->normal[a]) || !std::isfinite(sel->anchor[a])) return FLIMO_ERR_INVALID;
-  if (std::isnan(sel->dist) || sel->dist < 0.f || sel->side < -1 || sel->side > 1) return FLIMO_ERR_INVALID;
-  return FLIMO_OK;
+  return flimo_map_remove_clusters(ctx_of(L), first, n, cfg, removed, stats);
 }
 int flimo_loc_map_planes(flimo_loc* L, const int32_t* tri, size_t nh, const flimo_plane_cfg* cfg, int32_t* status, int32_t* inliers,
                          double* sum_sq, double* plane) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
-  if (!c) {
-    if (!cfg || !status || !inliers || !sum_sq || !plane_cfg_valid(cfg)) return FLIMO_ERR_INVALID;
-    if (nh >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
-    return nh == 0 ? FLIMO_OK : FLIMO_ERR_INVALID;      // (every index lies outside a map of no points)
-  }
-  return flimo_map_planes(c, tri, nh, cfg, status, inliers, sum_sq, plane);
+  return flimo_map_planes(ctx_of(L), tri, nh, cfg, status, inliers, sum_sq, plane);
 }
 int flimo_loc_map_plane_mask(flimo_loc* L, size_t first, size_t n, const flimo_plane_sel* sel, unsigned char* mask, size_t* count) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();
-  if (!c) {
-    const int rc = plane_sel_of_no_map(first, n, sel);
-    if (rc == FLIMO_OK && count) *count = 0;
-    return rc;
-  }
-  return flimo_map_plane_mask(c, first, n, sel, mask, count);
+  return flimo_map_plane_mask(ctx_of(L), first, n, sel, mask, count);
 }
 int flimo_loc_map_remove_plane(flimo_loc* L, size_t first, size_t n, const flimo_plane_sel* sel, size_t* removed) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();
-  if (!c) {
-    const int rc = plane_sel_of_no_map(first, n, sel);
-    if (rc == FLIMO_OK && removed) *removed = 0;
-    return rc;
-  }
-  return flimo_map_remove_plane(c, first, n, sel, removed);
-}
-// no map yet: the answer of an empty one, after the calls' own argument checks
-static int voxels_of_no_map(size_t first, size_t n, const flimo_voxel_cfg* k, flimo_voxel_stats* stats) {
-  if (!k || first != 0 || n != 0) return FLIMO_ERR_INVALID;      // (a range beyond the size of a map of no points)
-  if (!(k->leaf > 0.f) || std::isinf(k->leaf) || !std::isfinite(1.0f / k->leaf)) return FLIMO_ERR_INVALID;
-  if (k->keep < FLIMO_VOXEL_KEEP_FIRST || k->keep > FLIMO_VOXEL_KEEP_NEAREST || k->max_pts < 1) return FLIMO_ERR_INVALID;
-  if (k->keep == FLIMO_VOXEL_KEEP_NEAREST && k->max_pts != 1) return FLIMO_ERR_INVALID;
-  if (stats) stats->n = stats->voxels = stats->largest = stats->outside = stats->sel_points = 0;
-  return FLIMO_OK;
+  return flimo_map_remove_plane(ctx_of(L), first, n, sel, removed);
 }
 int flimo_loc_map_voxels(flimo_loc* L, const flimo_voxel_cfg* cfg, size_t cap, size_t* nv, int32_t* ijk, int32_t* count, int32_t* first,
                          int32_t* rep, double* centroid, double* cov, flimo_voxel_stats* stats) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert, a crop or a carve on the worker thread)
-  if (!c) {
-    const int rc = voxels_of_no_map(0, 0, cfg, stats);
-    if (rc == FLIMO_OK && nv) *nv = 0;
-    return rc;
-  }
-  return flimo_map_voxels(c, cfg, cap, nv, ijk, count, first, rep, centroid, cov, stats);
+  return flimo_map_voxels(ctx_of(L), cfg, cap, nv, ijk, count, first, rep, centroid, cov, stats);
 }
 int flimo_loc_map_voxel_mask(flimo_loc* L, size_t first, size_t n, const flimo_voxel_cfg* cfg, int32_t* voxel, unsigned char* mask,
                              flimo_voxel_stats* stats) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();
-  if (!c) return voxels_of_no_map(first, n, cfg, stats);
-  return flimo_map_voxel_mask(c, first, n, cfg, voxel, mask, stats);
+  return flimo_map_voxel_mask(ctx_of(L), first, n, cfg, voxel, mask, stats);
 }
 int flimo_loc_map_thin(flimo_loc* L, size_t first, size_t n, const flimo_voxel_cfg* cfg, size_t* removed, flimo_voxel_stats* stats) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();
-  if (!c) {
-    const int rc = voxels_of_no_map(first, n, cfg, stats);
-    if (rc == FLIMO_OK && removed) *removed = 0;
-    return rc;
-  }
-  return flimo_map_thin(c, first, n, cfg, removed, stats);
+  return flimo_map_thin(ctx_of(L), first, n, cfg, removed, stats);
 }
 int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
                          const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
@@ -497,36 +333,12 @@ int flimo_loc_desc_match(flimo_loc* L, const float* q, size_t nq, int dim, int k
 int flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
                            int32_t* nn_idx) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
-  if (!c) {                          // no map yet, and no resident scan: flimo_scan_fitness' own argument checks, then nothing per point
-    if ((np > 0 && !x26) || !inliers || !sum_sqd || std::isnan(max_dist) || max_dist < 0.f) return FLIMO_ERR_INVALID;
-    if (np >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
-    for (size_t j = 0; j < np; j++)
-      for (int t = 0; t < 7; t++)
-        if (!std::isfinite(x26[26 * j + t])) return FLIMO_ERR_INVALID;
-    for (size_t j = 0; j < np; j++) { inliers[j] = 0; sum_sqd[j] = 0.0; }
-    return FLIMO_OK;
-  }
-  return flimo_scan_fitness(c, x26, np, max_dist, inliers, sum_sqd, nn_sqd, nn_idx);
+  return flimo_scan_fitness(ctx_of(L), x26, np, max_dist, inliers, sum_sqd, nn_sqd, nn_idx);
 }
 int flimo_loc_scan_linearize(flimo_loc* L, const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, int32_t* valid, double* H,
                              double* g, double* cost, double* rows, int32_t* pair_cnt) {
   if (!L) return FLIMO_ERR_INVALID;
-  flimo_ctx* c = L->map->ctx();      // (waits for an insert or a crop on the worker thread)
-  if (!c) {                          // no map yet, and no resident scan: flimo_scan_linearize's own argument checks, then nothing per point
-    if ((np > 0 && !x26) || !valid || !H || !g || !cost || std::isnan(max_dist) || max_dist < 0.f || std::isnan(max_curv) || max_curv < 0.f)
-      return FLIMO_ERR_INVALID;
-    if (k < 3 || k > FLIMO_KNN_MAX_K) return FLIMO_ERR_UNSUPPORTED;
-    if (np >= 0x80000000ull) return FLIMO_ERR_TOO_LARGE;
-    for (size_t j = 0; j < np; j++)
-      for (int t = 0; t < 7; t++)
-        if (!std::isfinite(x26[26 * j + t])) return FLIMO_ERR_INVALID;
-    for (size_t j = 0; j < np; j++) { valid[j] = 0; cost[j] = 0.0; }
-    for (size_t i = 0; i < np * 21; i++) H[i] = 0.0;
-    for (size_t i = 0; i < np * 6; i++) g[i] = 0.0;
-    return FLIMO_OK;
-  }
-  return flimo_scan_linearize(c, x26, np, k, max_dist, min_pts, max_curv, valid, H, g, cost, rows, pair_cnt);
+  return flimo_scan_linearize(ctx_of(L), x26, np, k, max_dist, min_pts, max_curv, valid, H, g, cost, rows, pair_cnt);
 }
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
