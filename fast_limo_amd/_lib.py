@@ -374,6 +374,80 @@ def voxel_mask_call(call, n, want, cfg):
     return out
 
 
+class RegionCfg(C.Structure):
+    """flimo_region_cfg (include/flimo_c.h)."""
+    _fields_ = [("tol", C.c_float), ("normal_k", C.c_int), ("normal_max_dist", C.c_float), ("normal_min_pts", C.c_int), ("min_cos", C.c_float),
+                ("max_curv", C.c_float), ("border", C.c_int), ("min_size", C.c_int), ("max_size", C.c_int)]
+
+
+class RegionStats(C.Structure):
+    """flimo_region_stats (include/flimo_c.h)."""
+    _fields_ = [("n", C.c_uint64), ("smooth", C.c_uint64), ("regions", C.c_uint64), ("largest", C.c_uint64), ("sel_regions", C.c_uint64),
+                ("unassigned", C.c_uint64), ("sel_points", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+REGION_OUTPUTS = (("label", np.int32, 1), ("count", np.int32, 1), ("first", np.int32, 1), ("centroid", np.float64, 3), ("cov", np.float64, 6))
+
+
+def region_cfg(tol=0.5, normal_k=16, normal_max_dist=float("inf"), normal_min_pts=3, min_cos=0.93969262, max_curv=0.05, border=1, min_size=1,
+               max_size=0) -> RegionCfg:
+    """Half a metre, normals of 16 neighbours within 20 degrees of each other (``min_cos`` is the cosine), curvature up to 0.05,
+    border points attached, every region selected unless told otherwise (``max_size`` 0: no upper bound)."""
+    return RegionCfg(float(tol), int(normal_k), float(normal_max_dist), int(normal_min_pts), float(min_cos), float(max_curv), int(border),
+                     int(min_size), int(max_size))
+
+
+def regions_call(call, n, want, cfg):
+    """The output arrays of flimo_map_regions / flimo_loc_map_regions (``call`` takes: cfg, label, size, mask, stats) as a dict
+    with the outputs named in ``want`` (of "label", "size", "mask") and "stats"; shared with ``api.Localizer``."""
+    unknown = set(want) - {"label", "size", "mask"}
+    if unknown:
+        raise ValueError(f"map_regions: unknown outputs {sorted(unknown)}")
+    k = region_cfg(**cfg)
+    arr = {name: np.zeros(max(n, 1), dt) for name, dt in (("label", np.int32), ("size", np.int32), ("mask", np.uint8)) if name in want}
+    st = RegionStats()
+    ptr = lambda name: arr[name].ctypes.data if name in arr else None
+    call(C.byref(k), ptr("label"), ptr("size"), ptr("mask"), C.byref(st))
+    out = {name: a[:n] for name, a in arr.items()}
+    if "mask" in out:
+        out["mask"] = out["mask"].astype(bool)
+    out["stats"] = st.as_dict()
+    return out
+
+
+REGION_LIST_CAP = 1024      # regions the first call of ``region_list_call`` has room for
+
+
+def region_list_call(call, chk, want, cfg):
+    """The output arrays of flimo_map_region_list / flimo_loc_map_region_list (``call`` takes: cfg, cap, nr, label, count, first,
+    centroid, cov, stats and returns the code, ``chk`` raises on one) as a dict with the outputs named in ``want`` (of "label",
+    "count", "first", "centroid", "cov"), "nr" and "stats".  Selected regions are few: one call with room for ``REGION_LIST_CAP`` of
+    them, and a second with room for ``nr`` only where the first answers FLIMO_ERR_TOO_LARGE."""
+    unknown = set(want) - {name for name, _, _ in REGION_OUTPUTS}
+    if unknown:
+        raise ValueError(f"map_region_list: unknown outputs {sorted(unknown)}")
+    k = region_cfg(**cfg)
+    nr = C.c_size_t(0)
+    st = RegionStats()
+    cap = REGION_LIST_CAP
+    while True:
+        arr = {name: np.zeros((cap, w) if w > 1 else cap, dt) for name, dt, w in REGION_OUTPUTS if name in want}
+        ptr = lambda name: arr[name].ctypes.data if name in arr else None
+        rc = call(C.byref(k), cap, C.byref(nr), ptr("label"), ptr("count"), ptr("first"), ptr("centroid"), ptr("cov"), C.byref(st))
+        if rc == -5 and nr.value > cap:      # FLIMO_ERR_TOO_LARGE: *nr says how many there are
+            cap = int(nr.value)
+            continue
+        chk(rc)
+        break
+    out = {name: a[:nr.value].copy() for name, a in arr.items()}
+    out["nr"] = int(nr.value)
+    out["stats"] = st.as_dict()
+    return out
+
+
 class CorrGraphCfg(C.Structure):
     """flimo_corr_graph_cfg (include/flimo_c.h)."""
     _fields_ = [("tol", C.c_float), ("min_edge", C.c_float), ("edge_sim", C.c_float)]
@@ -456,7 +530,7 @@ FRAME_DTYPE = np.dtype([
 # every symbol include/flimo_c.h declares (tests check the .so exports each one)
 HIP_SYMBOLS = [
     "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_clusters", "flimo_map_remove_clusters", "flimo_set_cluster_chunk", "flimo_map_planes", "flimo_plane_solve_host", "flimo_map_plane_mask", "flimo_map_remove_plane", "flimo_set_plane_chunk", "flimo_map_voxels", "flimo_map_voxel_mask", "flimo_map_thin", "flimo_voxel_key_host", "flimo_set_voxel_plan", "flimo_map_size", "flimo_map_last_time",
+    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_clusters", "flimo_map_remove_clusters", "flimo_set_cluster_chunk", "flimo_map_planes", "flimo_plane_solve_host", "flimo_map_plane_mask", "flimo_map_remove_plane", "flimo_set_plane_chunk", "flimo_map_voxels", "flimo_map_voxel_mask", "flimo_map_thin", "flimo_voxel_key_host", "flimo_set_voxel_plan", "flimo_map_regions", "flimo_map_region_list", "flimo_map_remove_regions", "flimo_region_joined_host", "flimo_set_region_chunk", "flimo_map_size", "flimo_map_last_time",
     "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_corr_graph", "flimo_corr_compatible_host", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
     "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
     "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
@@ -572,6 +646,13 @@ def load_hip():
     L.flimo_map_thin.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(VoxelCfg), C.POINTER(C.c_size_t), C.POINTER(VoxelStats)]
     L.flimo_voxel_key_host.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
     L.flimo_set_voxel_plan.argtypes = [vp, C.c_int]
+    L.flimo_map_regions.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(RegionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RegionStats)]
+    L.flimo_map_region_list.argtypes = [vp, C.POINTER(RegionCfg), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(RegionStats)]
+    L.flimo_map_remove_regions.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(RegionCfg), C.POINTER(C.c_size_t), C.POINTER(RegionStats)]
+    L.flimo_region_joined_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RegionCfg), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.flimo_set_region_chunk.argtypes = [vp, C.c_size_t]
     L.flimo_map_size.argtypes = [vp]
     L.flimo_map_last_time.restype = C.c_double
     L.flimo_map_last_time.argtypes = [vp]
@@ -902,6 +983,36 @@ class HipCtx:
         """The lane plan of ``map_voxels``' moments (flimo_set_voxel_plan; 0: by the voxel's count, 1..3: groups of 8, 16, 64 lanes,
         4: the many-runs path, + 8: the points written in sorted order first)."""
         self._chk(self._L.flimo_set_voxel_plan(self._h, int(plan)))
+
+    def map_regions(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
+        """Smooth-surface regions (pcl::RegionGrowing without its seed order) of the stored points, for the points first ..
+        first + n - 1 (``n`` None: up to the map's end) -- flimo_map_regions; ``cfg``: the fields of ``region_cfg`` (tol, normal_k,
+        normal_max_dist, normal_min_pts, min_cos, max_curv, border, min_size, max_size).  Returns a dict: of ``want`` ``label`` [n]
+        int32 (the smallest insertion index of the region's smooth points; -1: no region), ``size`` [n] int32, ``mask`` [n] bool (the
+        region is selected), and ``stats``.  The regions are the whole map's whatever the range; changes nothing."""
+        first, n = self._range(first, n)
+        return regions_call(lambda *a: self._chk(self._L.flimo_map_regions(self._h, first, n, *a)), n, want, cfg)
+
+    def map_region_list(self, want=("label", "count", "centroid", "cov"), **cfg):
+        """The selected regions of the stored points in ascending label -- flimo_map_region_list: a dict with the outputs named in
+        ``want`` (of ``label``, ``count``, ``first`` [nr], ``centroid`` [nr, 3] and ``cov`` [nr, 6] float64: xx xy xz yy yz zz, in
+        ``map_voxels``' summation shape), ``nr`` and ``stats``.  ``api.region_planes`` fits a plane to each.  Changes nothing."""
+        return region_list_call(lambda *a: self._L.flimo_map_region_list(self._h, *a), self._chk, want, cfg)
+
+    def map_remove_regions(self, first=0, n=None, **cfg):
+        """Forget the points of the range whose ``map_regions`` mask is set -- flimo_map_remove_regions; afterwards the map is as
+        after ``map_crop_box``.  Returns (points removed, stats)."""
+        first, n = self._range(first, n)
+        k = region_cfg(**cfg)
+        removed = C.c_size_t(0)
+        st = RegionStats()
+        self._chk(self._L.flimo_map_remove_regions(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)))
+        return int(removed.value), st.as_dict()
+
+    def set_region_chunk(self, n):
+        """Points per link launch of ``map_regions`` / ``map_region_list`` / ``map_remove_regions`` (flimo_set_region_chunk; 0: the
+        default of 2^20)."""
+        self._chk(self._L.flimo_set_region_chunk(self._h, int(n)))
 
     def map_size(self) -> int:
         return int(self._L.flimo_map_size(self._h))

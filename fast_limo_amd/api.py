@@ -42,7 +42,7 @@ class LocCfg(C.Structure):
 
 
 HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_clusters", "flimo_loc_map_remove_clusters", "flimo_loc_map_planes", "flimo_loc_map_plane_mask", "flimo_loc_map_remove_plane", "flimo_loc_map_voxels", "flimo_loc_map_voxel_mask", "flimo_loc_map_thin", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
+    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_clusters", "flimo_loc_map_remove_clusters", "flimo_loc_map_planes", "flimo_loc_map_plane_mask", "flimo_loc_map_remove_plane", "flimo_loc_map_voxels", "flimo_loc_map_voxel_mask", "flimo_loc_map_thin", "flimo_loc_map_regions", "flimo_loc_map_region_list", "flimo_loc_map_remove_regions", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
     "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
     "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
     "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
@@ -180,6 +180,12 @@ def load_host():
     L.flimo_loc_map_voxel_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.VoxelCfg), C.c_void_p, C.c_void_p,
                                            C.POINTER(_lib.VoxelStats)]
     L.flimo_loc_map_thin.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.VoxelCfg), C.POINTER(C.c_size_t), C.POINTER(_lib.VoxelStats)]
+    L.flimo_loc_map_regions.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.RegionCfg), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(_lib.RegionStats)]
+    L.flimo_loc_map_region_list.argtypes = [vp, C.POINTER(_lib.RegionCfg), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(_lib.RegionStats)]
+    L.flimo_loc_map_remove_regions.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.RegionCfg), C.POINTER(C.c_size_t),
+                                               C.POINTER(_lib.RegionStats)]
     L.flimo_local_map_rule.restype = C.c_int
     L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
     L.flimo_loc_last_sweep_tied.restype = C.c_int
@@ -506,6 +512,29 @@ class Localizer:
         """The decimated map one publishes or saves: the centroids of the voxels of edge ``res`` as float32 [nv, 3], in ascending
         (cz, cy, cx) -- ``map_voxels`` with only the centroid asked for."""
         return self.map_voxels(want=("centroid",), leaf=res)["centroid"].astype(np.float32)
+
+    def map_regions(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
+        """Smooth-surface regions of the map's stored points (flimo_loc_map_regions), as ``HipCtx.map_regions``.  Waits for an insert,
+        a crop or a carve still running; changes nothing.  No policy calls it."""
+        first, n = self._range(first, n)
+        return _lib.regions_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_regions(self._h, first, n, *a), "flimo_loc_map_regions"),
+                                 n, want, cfg)
+
+    def map_region_list(self, want=("label", "count", "centroid", "cov"), **cfg):
+        """The selected regions of the map's stored points (flimo_loc_map_region_list), as ``HipCtx.map_region_list``."""
+        return _lib.region_list_call(lambda *a: self._L.flimo_loc_map_region_list(self._h, *a),
+                                     lambda rc: self._entry_chk(rc, "flimo_loc_map_region_list"), want, cfg)
+
+    def map_remove_regions(self, first=0, n=None, **cfg):
+        """Forget the selected regions' points of the range (flimo_loc_map_remove_regions), as ``HipCtx.map_remove_regions``:
+        (points removed, stats)."""
+        first, n = self._range(first, n)
+        k = _lib.region_cfg(**cfg)
+        removed = C.c_size_t(0)
+        st = _lib.RegionStats()
+        self._entry_chk(self._L.flimo_loc_map_remove_regions(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
+                        "flimo_loc_map_remove_regions")
+        return int(removed.value), st.as_dict()
 
     def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
         """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,
@@ -870,6 +899,44 @@ def voxel_key_host(p, leaf):
     if rc < 0:
         raise FlimoError(f"flimo_voxel_key_host failed ({rc})")
     return rc == 0, ijk, int(key.value)
+
+
+def region_joined_host(pi, ni, pj, nj, **cfg):
+    """The predicates of ``map_regions`` for ONE pair on the host (flimo_region_joined_host: the functions the link kernel calls):
+    (smooth_i, smooth_j, joined) as bools; ``ni`` / ``nj`` are rows nx ny nz curvature, ``cfg`` the fields of ``_lib.region_cfg``.
+    The pair is an edge iff all three hold.  Needs no device."""
+    L = _lib.load_hip()
+    a = [np.ascontiguousarray(v, dtype=np.float32).reshape(m) for v, m in ((pi, 3), (ni, 4), (pj, 3), (nj, 4))]
+    k = _lib.region_cfg(**cfg)
+    out = [C.c_int(0), C.c_int(0), C.c_int(0)]
+    rc = L.flimo_region_joined_host(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, C.byref(k), *(C.byref(o) for o in out))
+    if rc != 0:
+        raise FlimoError(f"flimo_region_joined_host failed ({rc})")
+    return tuple(bool(o.value) for o in out)
+
+
+def region_planes(listing):
+    """One plane per listed region, from ``map_region_list``'s ``centroid`` and ``cov`` (both must be in ``listing``), on the host by
+    ``np.linalg.eigh``: a dict of ``normal`` [nr, 3] float64 -- the eigenvector of the smallest eigenvalue, with
+    ``flimo_map_normals``' sign rule without a viewpoint: its component of largest magnitude is positive, the lowest axis deciding
+    between equal magnitudes --, ``d`` [nr] with n . x + d = 0 on the plane through the centroid (d = -n . centroid),
+    ``eigenvalues`` [nr, 3] ascending, and ``rms`` [nr], the root mean square
+    distance of the region's members to the plane (the square root of the smallest eigenvalue, clamped at 0).  Regions are few: no
+    device eigen-solver is needed and the C ABI's floats stay exact."""
+    cen = np.asarray(listing["centroid"], np.float64).reshape(-1, 3)
+    cov = np.asarray(listing["cov"], np.float64).reshape(-1, 6)
+    m = np.empty((len(cov), 3, 3))
+    m[:, 0, 0], m[:, 0, 1], m[:, 0, 2], m[:, 1, 1], m[:, 1, 2], m[:, 2, 2] = cov.T
+    m[:, 1, 0], m[:, 2, 0], m[:, 2, 1] = m[:, 0, 1], m[:, 0, 2], m[:, 1, 2]
+    if len(m):
+        w, v = np.linalg.eigh(m)
+    else:
+        w, v = np.zeros((0, 3)), np.zeros((0, 3, 3))
+    n = v[:, :, 0].copy()
+    lead = np.argmax(np.abs(n), axis=1)      # (the first of equal magnitudes: the lowest axis)
+    n[n[np.arange(len(n)), lead] < 0.0] *= -1.0
+    d = -(n[:, 0] * cen[:, 0] + (n[:, 1] * cen[:, 1] + n[:, 2] * cen[:, 2]))
+    return dict(normal=n, d=d, eigenvalues=w, rms=np.sqrt(np.maximum(w[:, 0], 0.0)))
 
 
 def plane_consensus(obj, nh, seed=0, top=4, **cfg):

@@ -26,6 +26,7 @@
 #include "flimo_corr.h"
 #include "flimo_plane.h"
 #include "flimo_voxel.h"
+#include "flimo_region.h"
 #include "flimo_desc.h"
 #include "flimo_chain.h"
 #include "flimo_ieskf.h"
@@ -60,6 +61,7 @@ struct flimo_ctx {
   uint64_t cluster_removals = 0, cluster_removed = 0;   // flimo_map_remove_clusters: the same
   uint64_t plane_removals = 0, plane_removed = 0;       // flimo_map_remove_plane: the same
   uint64_t thin_removals = 0, thin_removed = 0;         // flimo_map_thin: the same
+  uint64_t region_removals = 0, region_removed = 0;     // flimo_map_remove_regions: the same
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch
@@ -67,6 +69,7 @@ struct flimo_ctx {
   size_t fpfh_chunk = (size_t)1 << 20;      // points per search launch of flimo_map_fpfh (flimo_set_fpfh_chunk)
   size_t keypoints_chunk = (size_t)1 << 20; // points per search launch of flimo_map_keypoints (flimo_set_keypoints_chunk)
   size_t cluster_chunk = (size_t)1 << 20;   // points per link launch of flimo_map_clusters (flimo_set_cluster_chunk)
+  size_t region_chunk = (size_t)1 << 20;    // points per link launch of flimo_map_regions (flimo_set_region_chunk)
   size_t plane_chunk = (size_t)1 << 10;     // hypotheses per chunk of flimo_map_planes (flimo_set_plane_chunk)
   int voxel_plan = 0;                       // lane plan of flimo_map_voxels' moments (flimo_set_voxel_plan; 0: by the voxel's count)
   size_t linearize_chunk = (size_t)1 << 20; // (pose, point) pairs per chunk of flimo_scan_linearize (flimo_set_linearize_chunk)
@@ -2216,6 +2219,221 @@ extern "C" int flimo_voxel_key_host(const float p[3], float leaf, int32_t ijk[3]
   if (ijk) { ijk[0] = cell[0]; ijk[1] = cell[1]; ijk[2] = cell[2]; }
   if (key) *key = kk;
   return inside ? 0 : 1;
+}
+
+// ---- smooth-surface regions of the stored points (pcl::RegionGrowing over the map, without its seed order) -----------------------
+// kernels: flimo_region.hip.  On the context's stream over the WHOLE map whatever the range (a region can reach anywhere): the
+// normals of flimo_map_normals_range left on the device, in chunks of c->normals_chunk points as flimo_map_fpfh forms them (three
+// launches a chunk); init, link in chunks of c->region_chunk stored points, flatten, count, finish; then the copies back, one wait.
+// Scratch: 28 B a stored point (normal, parent, count, attach), 84 B a point of a normals chunk (moments, count, worklist), 1 B a
+// point of the range (mask), 4 B each for label and size where they are asked for; nothing of points x neighbours exists anywhere.
+// The listing adds the voxels' sort (32 B a stored point plus the sort's own) and at most 116 B a listed region, 84 B a run of a
+// region above 1024 points.  The removal hands the device mask to the crop's ordered compaction (map_remove_masked).
+static void region_stats_none(flimo_region_stats* s) {
+  if (s) s->n = s->smooth = s->regions = s->largest = s->sel_regions = s->unassigned = s->sel_points = 0;
+}
+static bool region_cfg_ok(const flimo_region_cfg* k) {      // (every test fails for a NaN)
+  return k->tol >= 0.f && !std::isinf(k->tol) && k->min_cos >= 0.f && k->min_cos <= 1.f && k->max_curv >= 0.f;
+}
+static int region_check(flimo_ctx* c, size_t first, size_t n, const flimo_region_cfg* cfg, const char* what) {
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
+  { const int rc = check_range(c, what, first, n); if (rc) return rc; }
+  if (!region_cfg_ok(cfg))
+    return fail(c, FLIMO_ERR_INVALID, "%s: tol must be finite and >= 0, min_cos in 0..1, max_curv >= 0 or INFINITY", what);
+  { const int rc = check_gate(c, what, cfg->normal_max_dist); if (rc) return rc; }
+  if (cfg->normal_min_pts < 0) return fail(c, FLIMO_ERR_INVALID, "%s: normal_min_pts must be >= 0", what);
+  if (cfg->min_size < 0 || cfg->max_size < 0) return fail(c, FLIMO_ERR_INVALID, "%s: min_size and max_size must be >= 0", what);
+  if (cfg->max_size > 0 && cfg->max_size < cfg->min_size) return fail(c, FLIMO_ERR_INVALID, "%s: max_size must be 0 or >= min_size", what);
+  if (cfg->normal_k < 1 || cfg->normal_k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "%s: normal_k must be in 1..%d", what, FLIMO_KNN_MAX_K);
+  return check_map_size(c, what);
+}
+struct RegionDev {      // what regions_device leaves on the device for its caller, and the owner of all it allocated
+  DevScratch mem;
+  int32_t* label = nullptr; int32_t* size = nullptr; unsigned char* mask = nullptr;
+  unsigned long long* keys = nullptr; uint32_t* vals = nullptr;      // the listing's key and index of every stored point
+  size_t listed = 0;                                                 // stored points in selected regions
+};
+// the regions of the whole map and the selection over [first, first + n), arguments checked, map not empty: where asked for d.mask
+// (n > 0), d.label / d.size and d.keys / d.vals filled on the device, *st on the host; ends synchronised
+static int regions_device(flimo_ctx* c, size_t first, size_t n, const flimo_region_cfg& cfg, bool want_label, bool want_size, bool want_mask,
+                          bool want_keys, RegionDev& d, flimo_region_stats* st) {
+  { const int rc = need_index(c, "map regions"); if (rc) return rc; }
+  ctx_enter(c);
+  const size_t N = c->map_n;
+  const size_t mn = std::min(N, std::max<size_t>(c->normals_chunk, 1));
+  const size_t ml = std::min(std::min(N, std::max<size_t>(c->region_chunk, 1)), (size_t)1 << 24);      // (x 64 lanes: below 2^31 a launch)
+  float4* d_normal = d.mem.get<float4>(N);
+  uint32_t* d_parent = d.mem.get<uint32_t>(N);
+  uint32_t* d_count = d.mem.get<uint32_t>(N);
+  uint32_t* d_attach = d.mem.get<uint32_t>(N);
+  uint32_t* d_words = d.mem.get<uint32_t>(REGION_WORDS);
+  int32_t* d_ncnt = d.mem.get<int32_t>(mn);
+  double* d_mom = d.mem.get<double>(mn * 9);
+  uint2* d_work = d.mem.get<uint2>(mn);
+  unsigned* d_nwork = d.mem.get<unsigned>(1);
+  if (n > 0 && want_mask) d.mask = d.mem.get<unsigned char>(n);
+  if (n > 0 && want_label) d.label = d.mem.get<int32_t>(n);
+  if (n > 0 && want_size) d.size = d.mem.get<int32_t>(n);
+  if (want_keys) { d.keys = d.mem.get<unsigned long long>(N); d.vals = d.mem.get<uint32_t>(N); }
+  { const int rc = d.mem.ok(c); if (rc) return rc; }
+  // (a chunk's worklist and moments are read by its own launches only: the stream orders the chunks, nothing waits in between)
+  for (size_t a = 0; a < N; a += mn)
+    HIPCHK(c, launch_knn_k_normals(c->stream, c->grid, c->d_map_raw, nullptr, (unsigned)a, (int)std::min(mn, N - a), cfg.normal_k, cfg.normal_max_dist,
+                                   cfg.normal_min_pts, nullptr, d_normal + a, d_ncnt, nullptr, nullptr, nullptr, d_mom, d_work, d_nwork));
+  HIPCHK(c, hipMemsetAsync(d_words, 0, REGION_WORDS * sizeof(uint32_t), c->stream));
+  HIPCHK(c, launch_region_init(c->stream, d_parent, d_count, d_attach, N));
+  for (size_t a = 0; a < N; a += ml)
+    HIPCHK(c, launch_region_link(c->stream, c->grid, c->d_map_raw, d_normal, (unsigned)a, (int)std::min(ml, N - a), cfg.tol, cfg.min_cos, cfg.max_curv,
+                                 cfg.border, d_parent, d_attach));
+  HIPCHK(c, launch_region_labels(c->stream, d_parent, d_attach, d_normal, cfg.max_curv, d_count, d_words, N));
+  HIPCHK(c, launch_region_finish(c->stream, d_parent, d_count, N, first, n, cfg.min_size, cfg.max_size, d.label, d.size, d.mask,
+                                 d.keys, d.vals, d_words));
+  uint32_t w[REGION_WORDS] = {0};
+  HIPCHK(c, hipMemcpyAsync(w, d_words, sizeof w, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint32_t regions = w[REGION_W_REGIONS], smooth = w[REGION_W_SMOOTH], none = w[REGION_W_UNASSIGNED];
+  if (smooth > N || none > N - smooth || regions > smooth || (regions == 0) != (smooth == 0) || w[REGION_W_LARGEST] > N - none ||
+      (regions > 0 && w[REGION_W_LARGEST] < 1) || w[REGION_W_SEL] > regions || w[REGION_W_SEL_PTS] > n || w[REGION_W_LISTED] > N - none)
+    return fail(c, FLIMO_ERR_HIP, "map regions: counted %u regions (largest %u, %u selected, %u points) of %u smooth and %u unassigned of %zu points",
+                regions, w[REGION_W_LARGEST], w[REGION_W_SEL], w[REGION_W_SEL_PTS], smooth, none, N);
+  d.listed = w[REGION_W_LISTED];
+  st->n = n; st->smooth = smooth; st->regions = regions; st->largest = w[REGION_W_LARGEST]; st->sel_regions = w[REGION_W_SEL];
+  st->unassigned = none; st->sel_points = w[REGION_W_SEL_PTS];
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_regions(flimo_ctx* c, size_t first, size_t n, const flimo_region_cfg* cfg, int32_t* label, int32_t* size,
+                                 unsigned char* mask, flimo_region_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = region_check(c, first, n, cfg, "map regions"); if (rc) return rc; }
+  if (c->map_n == 0) { region_stats_none(stats); return FLIMO_OK; }
+  if (n == 0 && !stats) return FLIMO_OK;
+  RegionDev d;
+  flimo_region_stats st;
+  { const int rc = regions_device(c, first, n, *cfg, label != nullptr, size != nullptr, mask != nullptr, false, d, &st); if (rc) return rc; }
+  if (n > 0 && (label || size || mask)) {
+    if (label) HIPCHK(c, hipMemcpyAsync(label, d.label, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (size) HIPCHK(c, hipMemcpyAsync(size, d.size, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (mask) HIPCHK(c, hipMemcpyAsync(mask, d.mask, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (stats) *stats = st;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_region_list(flimo_ctx* c, const flimo_region_cfg* cfg, size_t cap, size_t* nr, int32_t* label, int32_t* count,
+                                     int32_t* first, double* centroid, double* cov, flimo_region_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = region_check(c, 0, 0, cfg, "map region list"); if (rc) return rc; }
+  const size_t N = c->map_n;
+  if (N == 0) { if (nr) *nr = 0; region_stats_none(stats); return FLIMO_OK; }
+  const bool arrays = label || count || first || centroid || cov;
+  if (!arrays && !nr && !stats) return FLIMO_OK;      // nothing is asked for
+  RegionDev d;
+  flimo_region_stats st;
+  { const int rc = regions_device(c, 0, N, *cfg, false, false, false, arrays, d, &st); if (rc) return rc; }
+  const size_t m = (size_t)st.sel_regions;
+  if (nr) *nr = m;
+  if (arrays && m > cap) return fail(c, FLIMO_ERR_TOO_LARGE, "map region list: %zu regions are selected, the arrays hold %zu", m, cap);
+  if (arrays && m > 0) {
+    // the voxels' machinery behind ready keys: a stable sort (members in ascending insertion index), heads, classes, moments
+    const int moments = cov ? 2 : centroid ? 1 : 0;
+    size_t tmp_bytes = 0;
+    HIPCHK(c, voxel_tmp_bytes(N, &tmp_bytes));
+    unsigned long long* d_keys = d.mem.get<unsigned long long>(N);
+    uint32_t* d_perm = d.mem.get<uint32_t>(N);
+    uint32_t* d_head = d.mem.get<uint32_t>(N);
+    uint32_t* d_pos = d.mem.get<uint32_t>(N);
+    uint32_t* d_vwords = d.mem.get<uint32_t>(VOXEL_WORDS);
+    void* d_tmp = d.mem.get<unsigned char>(tmp_bytes);
+    uint32_t* d_seg = d.mem.get<uint32_t>(m + 1);
+    int32_t* d_label = d.mem.get<int32_t>(m);
+    int32_t* d_first = d.mem.get<int32_t>(m);
+    int32_t* d_cnt = d.mem.get<int32_t>(m);
+    uint32_t* d_runs = nullptr; uint32_t* d_roff = nullptr; uint32_t* d_lists = nullptr;
+    double* d_centroid = nullptr; double* d_cov = nullptr; int32_t* d_rep = nullptr;
+    if (moments) {
+      d_runs = d.mem.get<uint32_t>(m + 1);
+      d_roff = d.mem.get<uint32_t>(m + 1);
+      d_lists = d.mem.get<uint32_t>(4 * m);
+      d_centroid = d.mem.get<double>(3 * m);
+      if (moments > 1) { d_cov = d.mem.get<double>(6 * m); d_rep = d.mem.get<int32_t>(m); }
+    }
+    { const int rc = d.mem.ok(c); if (rc) return rc; }
+    HIPCHK(c, hipMemsetAsync(d_vwords, 0, VOXEL_WORDS * sizeof(uint32_t), c->stream));
+    HIPCHK(c, launch_voxel_sort_keys(c->stream, (unsigned)N, d.keys, d_keys, d.vals, d_perm, d_head, d_pos, d_tmp, tmp_bytes));
+    HIPCHK(c, launch_voxel_classify(c->stream, d_keys, d_perm, d_head, d_pos, (unsigned)N, (unsigned)m, (unsigned)d.listed, c->voxel_plan, d_seg, nullptr,
+                                    d_first, d_cnt, d_runs, d_roff, d_lists, d_tmp, tmp_bytes, d_vwords));
+    uint32_t h2[2] = {0, 0};      // {scan of the last position, its head flag}: the heads must number the selected regions
+    uint32_t w[VOXEL_WORDS] = {0};
+    uint32_t R = 0;
+    HIPCHK(c, hipMemcpyAsync(&h2[0], d_pos + (N - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h2[1], d_head + (N - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w, d_vwords, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    if (moments) HIPCHK(c, hipMemcpyAsync(&R, d_roff + m, sizeof R, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const unsigned* nl = w + VOXEL_W_LIST;
+    if ((size_t)h2[0] + h2[1] != m || w[VOXEL_W_LARGEST] > N || (moments && ((size_t)nl[0] + nl[1] + nl[2] + nl[3] != m || (size_t)R > N / 64 + m)))
+      return fail(c, FLIMO_ERR_HIP, "map region list: %u heads for %zu regions, classes %u + %u + %u + %u, %u run slots", h2[0] + h2[1], m, nl[0], nl[1],
+                  nl[2], nl[3], R);
+    if (moments) {
+      double* d_rs = nullptr; double* d_rc = nullptr; double* d_rq = nullptr; uint32_t* d_rp = nullptr;
+      if (nl[3]) {
+        d_rs = d.mem.get<double>(3 * (size_t)R);
+        if (moments > 1) {
+          d_rc = d.mem.get<double>(6 * (size_t)R);
+          d_rq = d.mem.get<double>(R);
+          d_rp = d.mem.get<uint32_t>(R);
+        }
+      }
+      { const int rc = d.mem.ok(c); if (rc) return rc; }
+      HIPCHK(c, launch_voxel_moments(c->stream, c->d_map_raw, d_perm, d_perm, d_seg, (unsigned)m, d_lists, nl, d_roff, R, moments > 1, d_rs, d_rc, d_rq,
+                                     d_rp, d_centroid, d_cov, d_rep));
+    }
+    HIPCHK(c, launch_region_list_labels(c->stream, d_keys, d_seg, (unsigned)m, d_label));
+    // the results come back through the pinned stage, so the caller's arrays stay untouched if anything fails
+    const size_t bytes = m * ((centroid ? 24 : 0) + (cov ? 48 : 0) + (label ? 4 : 0) + (count ? 4 : 0) + (first ? 4 : 0));
+    { const int rc = ensure_stage(c, bytes); if (rc) return rc; }
+    char* h = (char*)c->h_stage;      // (the float64 arrays first: every part stays aligned)
+    struct Part { void* dst; const void* src; size_t bytes; char* at; } parts[5] = {
+        {centroid, d_centroid, 24 * m, nullptr}, {cov, d_cov, 48 * m, nullptr}, {label, d_label, 4 * m, nullptr},
+        {count, d_cnt, 4 * m, nullptr},          {first, d_first, 4 * m, nullptr}};
+    for (Part& p : parts) {
+      if (!p.dst) continue;
+      p.at = h;
+      h += p.bytes;
+      HIPCHK(c, hipMemcpyAsync(p.at, p.src, p.bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (const Part& p : parts)
+      if (p.dst) memcpy(p.dst, p.at, p.bytes);
+  }
+  if (stats) *stats = st;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_remove_regions(flimo_ctx* c, size_t first, size_t n, const flimo_region_cfg* cfg, size_t* removed,
+                                        flimo_region_stats* stats) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = region_check(c, first, n, cfg, "remove regions"); if (rc) return rc; }
+  if (c->map_n == 0) { if (removed) *removed = 0; region_stats_none(stats); return FLIMO_OK; }
+  if (n == 0 && !stats) { if (removed) *removed = 0; return FLIMO_OK; }
+  RegionDev d;
+  flimo_region_stats st;
+  { const int rc = regions_device(c, first, n, *cfg, false, false, true, false, d, &st); if (rc) return rc; }
+  if (removed) *removed = 0;
+  if (stats) *stats = st;
+  if (st.sel_points == 0) return FLIMO_OK;             // removing nothing changes nothing
+  return map_remove_masked(c, d.mask, first, n, (size_t)st.sel_points, &c->region_removals, &c->region_removed, removed, "remove regions");
+}
+extern "C" int flimo_set_region_chunk(flimo_ctx* c, size_t n) { return set_chunk(c, &flimo_ctx::region_chunk, n, (size_t)1 << 20); }
+extern "C" int flimo_region_joined_host(const float pi[3], const float ni[4], const float pj[3], const float nj[4], const flimo_region_cfg* cfg,
+                                        int* smooth_i, int* smooth_j, int* joined) {
+  if (!pi || !ni || !pj || !nj || !cfg || !region_cfg_ok(cfg)) return FLIMO_ERR_INVALID;
+  const float r2 = cfg->tol * cfg->tol;      // one float32 product
+  if (smooth_i) *smooth_i = region_smooth(ni[0], ni[1], ni[2], ni[3], cfg->max_curv) ? 1 : 0;
+  if (smooth_j) *smooth_j = region_smooth(nj[0], nj[1], nj[2], nj[3], cfg->max_curv) ? 1 : 0;
+  if (joined)
+    *joined = region_has_normal(ni[0], ni[1], ni[2], ni[3]) && region_has_normal(nj[0], nj[1], nj[2], nj[3]) &&
+                      region_joined(pi, ni, pj, nj, r2, cfg->min_cos) ? 1 : 0;
+  return FLIMO_OK;
 }
 extern "C" int flimo_set_voxel_plan(flimo_ctx* c, int plan) {
   if (!c) return FLIMO_ERR_INVALID;

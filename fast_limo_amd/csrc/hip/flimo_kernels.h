@@ -289,6 +289,28 @@ hipError_t launch_cluster_flatten(hipStream_t st, uint32_t* parent, uint32_t* co
 hipError_t launch_cluster_finish(hipStream_t st, const uint32_t* label_all, const uint32_t* count, size_t n_map, size_t first, size_t n, int min_size,
                                  int max_size, int32_t* label, int32_t* size, unsigned char* mask, uint32_t* words);
 
+// flimo_region.hip -- smooth-surface regions of the stored points (flimo_map_regions, flimo_c.h): the connected components of
+// "closer than tol and normals agree" over the SMOOTH points, the predicates of flimo_region.h.  normal: [n_map] rows of
+// flimo_map_normals_range (launch_knn_k_normals); parent, count, attach: [n_map] device words.  init: parent[t] = t, count[t] = 0,
+// attach[t] = none.  link: the stored points first .. first + nq - 1 walk their balls (radius_plan's lanes and walk); a smooth one
+// unites with the smooth hits of lower index whose normal agrees -- every access to parent an agent-scope atomic --, a border one
+// (border != 0: it has a normal and is not smooth) records in attach the smooth hit of smallest (distance bits, index) whose normal
+// agrees; run it over the whole map, in chunks.  labels (two launches): parent[t] = the label of t -- the smallest index of a smooth
+// t's component, the label of attach[t] for a border point, REGION_NONE otherwise --, count[label] = the region's points,
+// words[REGION_W_SMOOTH] += the smooth points.  finish:
+// label / size / mask (each may be null) of the range [first, first + n), words[REGION_WORDS] (flimo_region.h, zeroed by the caller);
+// with keys / vals ([n_map], may be null) the listing's key of every stored point: its label where its region is selected, all ones
+// otherwise.  list_labels: label[r] of the listing from the sorted keys and launch_voxel_classify's seg.
+hipError_t launch_region_init(hipStream_t st, uint32_t* parent, uint32_t* count, uint32_t* attach, size_t n_map);
+hipError_t launch_region_link(hipStream_t st, const GridView& G, const float4* map_raw, const float4* normal, unsigned first, int nq, float tol,
+                              float min_cos, float max_curv, int border, uint32_t* parent, uint32_t* attach);
+hipError_t launch_region_labels(hipStream_t st, uint32_t* parent, const uint32_t* attach, const float4* normal, float max_curv, uint32_t* count,
+                                uint32_t* words, size_t n_map);
+hipError_t launch_region_finish(hipStream_t st, const uint32_t* label_all, const uint32_t* count, size_t n_map,
+                                size_t first, size_t n, int min_size, int max_size, int32_t* label, int32_t* size, unsigned char* mask,
+                                unsigned long long* keys, uint32_t* vals, uint32_t* words);
+hipError_t launch_region_list_labels(hipStream_t st, const unsigned long long* keys, const uint32_t* seg, unsigned nr, int32_t* label);
+
 // flimo_knn_k.hip -- Octree::knn (Octree.hpp:526-555) for k up to KNNK_MAX_K with a distance gate: per query the first k stored points
 // in the order (float32 squared-distance bits, insertion index) among those with sqdist3(q, p) < max_dist * max_dist (INFINITY: no
 // gate).  The running k-best is a list distributed over the lanes that serve the query (knnk_plan lanes, chosen from k); a block
@@ -400,7 +422,7 @@ hipError_t launch_plane_mask(hipStream_t st, const float4* map_raw, unsigned fir
 //  launch_voxel_sort      keys, the stable sort (keys_out / vals_out: sorted keys and the insertion index of every sorted position),
 //                         head flags and their exclusive scan pos; words[VOXEL_W_OUTSIDE] += the outside points.  The caller
 //                         reads nv = pos[n - 1] + head[n - 1] and the outside count before the next stage.
-//  launch_voxel_classify  seg [nv + 1], ijk [nv][3], first [nv], count [nv], words[VOXEL_W_LARGEST]; with lists ([4][nv]; null: no
+//  launch_voxel_classify  seg [nv + 1], ijk [nv][3] (may be null), first [nv], count [nv], words[VOXEL_W_LARGEST]; with lists ([4][nv]; null: no
 //                         moments are wanted) the voxels of each lane plan (lengths in words[VOXEL_W_LIST ..]), runs [nv + 1] and
 //                         their exclusive scan roff [nv + 1] (roff[nv]: the run slots R the many-runs path needs).
 //  launch_voxel_moments   centroid [nv][3] and, with second, cov [nv][6] and rep [nv]; pts is read through gather (null: pts is
@@ -410,6 +432,9 @@ hipError_t launch_plane_mask(hipStream_t st, const float4* map_raw, unsigned fir
 hipError_t voxel_tmp_bytes(size_t n, size_t* bytes);
 hipError_t launch_voxel_sort(hipStream_t st, const float4* map_raw, unsigned n, float inv, unsigned long long* keys_in, unsigned long long* keys_out,
                              uint32_t* vals_in, uint32_t* vals_out, uint32_t* head, uint32_t* pos, void* tmp, size_t tmp_bytes, uint32_t* words);
+// ... the same behind ready keys (keys_in / vals_in [n], filled by the caller; all ones: the point belongs to no segment)
+hipError_t launch_voxel_sort_keys(hipStream_t st, unsigned n, unsigned long long* keys_in, unsigned long long* keys_out, uint32_t* vals_in,
+                                  uint32_t* vals_out, uint32_t* head, uint32_t* pos, void* tmp, size_t tmp_bytes);
 hipError_t launch_voxel_classify(hipStream_t st, const unsigned long long* keys, const uint32_t* perm, const uint32_t* head, const uint32_t* pos,
                                  unsigned n, unsigned nv, unsigned inside, int plan, uint32_t* seg, int32_t* ijk, int32_t* first, int32_t* count,
                                  uint32_t* runs, uint32_t* roff, uint32_t* lists, void* tmp, size_t tmp_bytes, uint32_t* words);

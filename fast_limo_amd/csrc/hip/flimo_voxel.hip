@@ -63,9 +63,11 @@ __global__ __launch_bounds__(256) void voxel_segment_kernel(const unsigned long 
   if (i >= n || !head[i]) return;
   const unsigned v = pos[i];
   seg[v] = i;
-  int32_t c[3];
-  voxel_cell_of_key(keys[i], c);
-  ijk[3 * (size_t)v] = c[0]; ijk[3 * (size_t)v + 1] = c[1]; ijk[3 * (size_t)v + 2] = c[2];
+  if (ijk) {      // (null: the keys are no cells -- flimo_region.hip's listing)
+    int32_t c[3];
+    voxel_cell_of_key(keys[i], c);
+    ijk[3 * (size_t)v] = c[0]; ijk[3 * (size_t)v + 1] = c[1]; ijk[3 * (size_t)v + 2] = c[2];
+  }
   first[v] = (int32_t)perm[i];
 }
 
@@ -379,6 +381,11 @@ hipError_t launch_voxel_sort(hipStream_t st, const float4* map_raw, unsigned n, 
                              uint32_t* vals_in, uint32_t* vals_out, uint32_t* head, uint32_t* pos, void* tmp, size_t tmp_bytes, uint32_t* words) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(voxel_key_kernel, vox_grid(n), dim3(256), 0, st, map_raw, n, inv, keys_in, vals_in, words);
+  return launch_voxel_sort_keys(st, n, keys_in, keys_out, vals_in, vals_out, head, pos, tmp, tmp_bytes);
+}
+hipError_t launch_voxel_sort_keys(hipStream_t st, unsigned n, unsigned long long* keys_in, unsigned long long* keys_out, uint32_t* vals_in,
+                                  uint32_t* vals_out, uint32_t* head, uint32_t* pos, void* tmp, size_t tmp_bytes) {
+  if (n == 0) return hipSuccess;
   size_t bytes = tmp_bytes;
   hipError_t e = sort_pairs_u64(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, st);
   if (e != hipSuccess) return e;

@@ -312,6 +312,20 @@ int flimo_loc_map_thin(flimo_loc* L, size_t first, size_t n, const flimo_voxel_c
   if (!L) return FLIMO_ERR_INVALID;
   return flimo_map_thin(ctx_of(L), first, n, cfg, removed, stats);
 }
+int flimo_loc_map_regions(flimo_loc* L, size_t first, size_t n, const flimo_region_cfg* cfg, int32_t* label, int32_t* size, unsigned char* mask,
+                          flimo_region_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_regions(ctx_of(L), first, n, cfg, label, size, mask, stats);
+}
+int flimo_loc_map_region_list(flimo_loc* L, const flimo_region_cfg* cfg, size_t cap, size_t* nr, int32_t* label, int32_t* count, int32_t* first,
+                              double* centroid, double* cov, flimo_region_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_region_list(ctx_of(L), cfg, cap, nr, label, count, first, centroid, cov, stats);
+}
+int flimo_loc_map_remove_regions(flimo_loc* L, size_t first, size_t n, const flimo_region_cfg* cfg, size_t* removed, flimo_region_stats* stats) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_remove_regions(ctx_of(L), first, n, cfg, removed, stats);
+}
 int flimo_loc_corr_poses(flimo_loc* L, const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh,
                          const flimo_corr_cfg* cfg, int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {
   if (!L) return FLIMO_ERR_INVALID;

@@ -624,6 +624,53 @@ int Mapper::thin(size_t first, size_t n, const flimo_voxel_cfg& cfg, size_t* rem
   return flimo_map_thin(ctx_, first, n, &cfg, removed, stats);
 }
 
+// smooth-surface regions of the map's stored points (an insert, a crop or a carve on the worker thread ends first)
+int Mapper::regions(size_t first, size_t n, const flimo_region_cfg& cfg, std::vector<int32_t>* label, std::vector<int32_t>* size,
+                    std::vector<unsigned char>* mask, flimo_region_stats* stats) {
+  sync();
+  if (label) label->clear();
+  if (size) size->clear();
+  if (mask) mask->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  if (first > flimo_map_size(ctx_) || n > flimo_map_size(ctx_) - first) return FLIMO_ERR_INVALID;
+  if (label) label->assign(n, -1);
+  if (size) size->assign(n, 0);
+  if (mask) mask->assign(n, 0);
+  return flimo_map_regions(ctx_, first, n, &cfg, (label && n) ? label->data() : nullptr, (size && n) ? size->data() : nullptr,
+                           (mask && n) ? mask->data() : nullptr, stats);
+}
+int Mapper::region_list(const flimo_region_cfg& cfg, std::vector<int32_t>* label, std::vector<int32_t>* count, std::vector<int32_t>* first,
+                        std::vector<double>* centroid, std::vector<double>* cov, flimo_region_stats* stats) {
+  sync();
+  std::vector<int32_t>* iv[3] = {label, count, first};
+  for (auto* v : iv) if (v) v->clear();
+  if (centroid) centroid->clear();
+  if (cov) cov->clear();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  // selected regions are few (the map's size would be a wasteful cap): room for 1024, and a second call only where there are more
+  size_t nr = 0, cap = 1024;
+  int rc = FLIMO_OK;
+  auto ptr = [](auto* v) { return v ? v->data() : nullptr; };
+  for (int attempt = 0; attempt < 2; attempt++) {
+    for (auto* v : iv) if (v) v->assign(cap, 0);
+    if (centroid) centroid->assign(3 * cap, 0.0);
+    if (cov) cov->assign(6 * cap, 0.0);
+    rc = flimo_map_region_list(ctx_, &cfg, cap, &nr, ptr(label), ptr(count), ptr(first), ptr(centroid), ptr(cov), stats);
+    if (rc != FLIMO_ERR_TOO_LARGE || nr <= cap) break;
+    cap = nr;
+  }
+  if (rc != FLIMO_OK) nr = 0;
+  for (auto* v : iv) if (v) v->resize(nr);
+  if (centroid) centroid->resize(3 * nr);
+  if (cov) cov->resize(6 * nr);
+  return rc;
+}
+int Mapper::remove_regions(size_t first, size_t n, const flimo_region_cfg& cfg, size_t* removed, flimo_region_stats* stats) {
+  sync();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  return flimo_map_remove_regions(ctx_, first, n, &cfg, removed, stats);
+}
+
 // fitness of the resident scan at pose hypotheses (an insert or a crop on the worker thread ends first)
 int Mapper::fitness(const double* x26, size_t np, float max_dist, std::vector<int32_t>& inliers, std::vector<double>& sum_sqd,
                     std::vector<float>* nn_sqd, std::vector<int32_t>* nn_idx) {

@@ -94,6 +94,19 @@ class fast_limo::Mapper {
   // ... and forget the masked points of the range (flimo_map_thin); afterwards the map is as after crop_box.  As remove_clusters: it
   // runs at once and is not queued.  removed / stats may be null.  Returns a FLIMO_* code.
   int thin(size_t first, size_t n, const flimo_voxel_cfg& cfg, size_t* removed = nullptr, flimo_voxel_stats* stats = nullptr);
+  // The smooth-surface regions of the stored points (flimo_map_regions: pcl::RegionGrowing without its seed order), for the stored
+  // points first .. first + n - 1: where a vector is given label [n] (the smallest insertion index of the region's smooth points,
+  // -1: no region), size [n], mask [n] (1 = its region is selected by min_size / max_size); stats (may be null).  Changes nothing.
+  // Returns a FLIMO_* code.
+  int regions(size_t first, size_t n, const flimo_region_cfg& cfg, std::vector<int32_t>* label, std::vector<int32_t>* size = nullptr,
+              std::vector<unsigned char>* mask = nullptr, flimo_region_stats* stats = nullptr);
+  // ... the selected regions in ascending label (flimo_map_region_list): where a vector is given label [nr], count [nr], first [nr],
+  // centroid [nr][3], cov [nr][6] ...
+  int region_list(const flimo_region_cfg& cfg, std::vector<int32_t>* label, std::vector<int32_t>* count = nullptr, std::vector<int32_t>* first = nullptr,
+                  std::vector<double>* centroid = nullptr, std::vector<double>* cov = nullptr, flimo_region_stats* stats = nullptr);
+  // ... and forget the points of the range in selected regions (flimo_map_remove_regions); afterwards the map is as after crop_box.
+  // As remove_clusters: it runs at once and is not queued.  removed / stats may be null.  Returns a FLIMO_* code.
+  int remove_regions(size_t first, size_t n, const flimo_region_cfg& cfg, size_t* removed = nullptr, flimo_region_stats* stats = nullptr);
   // octree::Octree::radiusSearch (Objects/Octree.hpp:453-523) over the GPU map (flimo_radius_search).  The reference's Mapper hides
   // its octree, so this is an addition: the stored points with (p - query).squaredNorm() < radius * radius (strict, float32), in
   // ascending order of (distance, insertion index) -- the reference's traversal order is not reproduced.  As the template

@@ -564,6 +564,89 @@ int flimo_map_thin(flimo_ctx* ctx, size_t first, size_t n, const flimo_voxel_cfg
  * be NULL.  Needs no context and no device. */
 int flimo_voxel_key_host(const float p[3], float leaf, int32_t ijk[3], uint64_t* key);
 
+/* ---- smooth-surface regions of the stored points: what pcl::RegionGrowing finds -- neighbours whose normals agree grow one
+ * region --, stated so that the seed order cannot show.  Walls, floor and ceiling as separate segments where flimo_map_clusters
+ * reports one component of everything that touches; the objects left over when the large smooth regions are forgotten
+ * (flimo_map_remove_regions, then flimo_map_clusters); one plane per region as a landmark or for map compression ----
+ * Normals and neighbour lists never leave the GPU.
+ *
+ * Definition (tests/regions_common.py restates it in numpy).  The vertices are the N stored points in insertion order: the order
+ * flimo_map_points returns and flimo_knn_k indexes.
+ *  1. normals: (n_i, curv_i) is the float32 row normal[i] = nx ny nz curvature of flimo_map_normals_range(first = 0, n = N, normal_k,
+ *     normal_max_dist, normal_min_pts, viewpoint = NULL), bit for bit.  A point HAS A NORMAL iff all four floats are finite.
+ *  2. smooth: point i is SMOOTH iff it has a normal and curv_i <= max_curv (a float32 compare; max_curv may be INFINITY).
+ *  3. edge: {i, j}, i != j, both smooth, is an edge iff sqdist3(p_i, p_j) < tol * tol -- exactly flimo_map_clusters' predicate -- and
+ *     fabsf(n_i.x*n_j.x + (n_i.y*n_j.y + n_i.z*n_j.z)) >= min_cos: float32, uncontracted, in this association, so the predicate is
+ *     symmetric bit for bit.  min_cos is a cosine, not an angle: no cosf enters the contract.
+ *  4. region: a connected component of that graph over the smooth points of the WHOLE map, whatever the range.  Its label is the
+ *     smallest insertion index among its smooth points.
+ *  5. border (border != 0): a point b that has a normal but is not smooth joins the region of the smooth point j that passes both
+ *     tests of 3. against b; among such j the one with the smallest key (bits of the float32 sqdist3(p_b, p_j), insertion index j):
+ *     flimo_knn_k's order.  Such a point never carries a region further, counts towards the region's size, and leaves the region's
+ *     label as 4. defines it, even where b's own index is smaller.
+ *  6. unassigned: a point with no region has label -1 and size 0; it is never selected and never removed.
+ *  7. selection and mask as flimo_map_clusters' (min_size, max_size; 0: no upper bound).  stats: n = points of the range; smooth,
+ *     regions, largest, sel_regions, unassigned over the WHOLE map; sel_points = ones of the mask (range only).
+ *  8. listing (flimo_map_region_list): the selected regions in ascending label; region r has the members m_0 < m_1 < ... in
+ *     insertion order, border members included: label[r], count[r], first[r] = m_0, centroid[r][3] and cov[r][6] float64 exactly as
+ *     flimo_map_voxels defines them for a voxel -- the same SHAPE of every sum (runs of FLIMO_VOXEL_RUN, the pairwise tree, the runs
+ *     chained from +0.0), two passes, divided by count.  No floating-point atomics.
+ *  9. tol == 0: no edges and no border attachment; every smooth point is its own region.  min_cos == 0 with max_curv == INFINITY:
+ *     the regions are the Euclidean clusters of the points that have a normal.
+ * Every integer output has one correct value given the normals, and no bit of the listing depends on the lane plan, the chunks, the
+ * cell size, the order in which edges are met or earlier calls.
+ * Cost: normals and regions are formed for the whole map whatever the range, nothing is kept between calls; device scratch is 28 B a
+ * stored point, 84 B a point of a normals chunk, 1 B a point of the range and 4 B each for label and size where they are asked for;
+ * the listing adds one 64-bit radix sort of the stored points. */
+typedef struct flimo_region_cfg {
+  float tol;             /* two points closer than this (strict, float32) can be joined; finite, >= 0 */
+  int   normal_k;        /* neighbourhood of the normals: 1 .. FLIMO_KNN_MAX_K */
+  float normal_max_dist; /* ... its distance gate; >= 0 or INFINITY */
+  int   normal_min_pts;  /* ... and the neighbours a normal needs (at least 3 are always needed); >= 0 */
+  float min_cos;         /* normals agree iff |n_i . n_j| >= min_cos; in 0 .. 1 */
+  float max_curv;        /* smooth iff curvature <= max_curv; >= 0 or INFINITY */
+  int   border;          /* != 0: points with a normal that are not smooth attach to a neighbouring region */
+  int   min_size;        /* selected: min_size <= size ...; >= 0 */
+  int   max_size;        /* ... <= max_size; 0: no upper bound; otherwise >= min_size */
+} flimo_region_cfg;
+typedef struct flimo_region_stats {
+  uint64_t n;            /* points of the range */
+  uint64_t smooth;       /* smooth points of the whole map */
+  uint64_t regions;      /* regions of the whole map */
+  uint64_t largest;      /* points of the largest region */
+  uint64_t sel_regions;  /* selected regions of the whole map */
+  uint64_t unassigned;   /* points of the whole map with no region */
+  uint64_t sel_points;   /* ones of the mask (range only) */
+} flimo_region_stats;
+/* label / size / mask [n] and *stats over the stored points first .. first + n - 1; every output may be NULL.  Changes nothing: not
+ * the map, not the scan, not the bits of a later pass.  n = 0 (also on an empty map, first = 0): FLIMO_OK, stats.n and
+ * stats.sel_points 0, the whole-map fields still filled. */
+int flimo_map_regions(flimo_ctx* ctx, size_t first, size_t n, const flimo_region_cfg* cfg, int32_t* label, int32_t* size,
+                      unsigned char* mask, flimo_region_stats* stats);
+/* The selected regions of the whole map (stats.n = flimo_map_size).  Every output may be NULL.  *nr (the number of selected regions)
+ * is written whenever the call gets that far: a non-NULL per-region array with cap < nr returns FLIMO_ERR_TOO_LARGE, *nr set, the
+ * arrays untouched; a caller passes cap = flimo_map_size and makes one call, or asks for *nr first.  Changes nothing.  An empty
+ * map: FLIMO_OK, *nr = 0, stats 0. */
+int flimo_map_region_list(flimo_ctx* ctx, const flimo_region_cfg* cfg, size_t cap, size_t* nr, int32_t* label /* [nr] */,
+                          int32_t* count /* [nr] */, int32_t* first /* [nr] */, double* centroid /* [nr][3] */, double* cov /* [nr][6] */,
+                          flimo_region_stats* stats);
+/* Forgets the points OF THE RANGE whose mask is 1 and keeps the rest in insertion order; afterwards everything is exactly as
+ * flimo_map_remove_clusters documents it.  *removed (may be NULL) receives how many points went (= stats.sel_points), *stats (may
+ * be NULL) the predicate's, taken before the removal.  Removing nothing changes nothing.
+ * All three calls: FLIMO_ERR_INVALID -- outputs and map untouched -- for a NULL ctx or cfg, first + n beyond flimo_map_size, tol NaN,
+ * negative or infinite, min_cos NaN or outside 0 .. 1, max_curv NaN or negative, normal_max_dist NaN or negative, normal_min_pts < 0,
+ * min_size < 0 or max_size < 0, 0 < max_size < min_size; FLIMO_ERR_UNSUPPORTED for normal_k outside 1 .. FLIMO_KNN_MAX_K;
+ * FLIMO_ERR_TOO_LARGE for a map of 2^31 points or more.  Same calling rules as flimo_map_clusters: no pass of this context in flight. */
+int flimo_map_remove_regions(flimo_ctx* ctx, size_t first, size_t n, const flimo_region_cfg* cfg, size_t* removed,
+                             flimo_region_stats* stats);
+/* The predicates for one pair on the host, through the same functions the link kernel calls (normals as rows nx ny nz curvature):
+ * *smooth_i / *smooth_j = 2. for either point; *joined = 1 iff both points have a normal and both tests of 3. pass -- so {i, j} is
+ * an edge iff all three are 1, and a border point b attaches to a smooth j only if joined.  Each output may be NULL.
+ * FLIMO_ERR_INVALID for a NULL input or a cfg whose tol, min_cos or max_curv flimo_map_regions rejects (the other fields are not
+ * read).  Needs no context and no device. */
+int flimo_region_joined_host(const float pi[3], const float ni[4], const float pj[3], const float nj[4], const flimo_region_cfg* cfg,
+                             int* smooth_i, int* smooth_j, int* joined);
+
 /* ---- scan: pc2match of the reference (Modules/Localizer.hpp:36) ---- */
 int flimo_scan_set(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 size_t flimo_scan_size(const flimo_ctx* ctx);

@@ -97,6 +97,11 @@ int flimo_set_plane_chunk(flimo_ctx* ctx, size_t n);
  * the groups of 8, 16, 64 lanes for every voxel, 4 the many-runs path.  + 8: the points are first written in sorted order, so the
  * moments read them without a gather.  Equal results whatever the plan; FLIMO_ERR_INVALID for any other value. */
 int flimo_set_voxel_plan(flimo_ctx* ctx, int plan);
+/* The link launches of flimo_map_regions / flimo_map_region_list / flimo_map_remove_regions work in chunks of n stored points
+ * (default 2^20; 0 restores it; at most 2^24 are used): a launch's lanes stay far below 2^31 whatever the map's size.  The normals
+ * in front of them go by flimo_set_normals_chunk, the listing's moments by flimo_set_voxel_plan (its + 8 is not used: they
+ * gather).  Equal results whatever the chunks and the plan. */
+int flimo_set_region_chunk(flimo_ctx* ctx, size_t n);
 /* flimo_corr_poses works in chunks of n hypotheses (default 2^16; 0 restores it): the chunk bounds the call's device scratch, 136 B
  * a hypothesis (and m floats each where pair_sqd is asked for: then at most 2^26 slots a chunk); equal results whatever the chunk. */
 int flimo_set_corr_chunk(flimo_ctx* ctx, size_t n);

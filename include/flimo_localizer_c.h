@@ -161,6 +161,17 @@ int    flimo_loc_map_voxels(flimo_loc* L, const flimo_voxel_cfg* cfg, size_t cap
 int    flimo_loc_map_voxel_mask(flimo_loc* L, size_t first, size_t n, const flimo_voxel_cfg* cfg, int32_t* voxel, unsigned char* mask,
                                 flimo_voxel_stats* stats);
 int    flimo_loc_map_thin(flimo_loc* L, size_t first, size_t n, const flimo_voxel_cfg* cfg, size_t* removed, flimo_voxel_stats* stats);
+/* Smooth-surface regions of the Localizer's stored points: flimo_map_regions / flimo_map_region_list / flimo_map_remove_regions
+ * (include/flimo_c.h: same arguments, same results, same error codes) on the map's context, after an insert, a crop or a carve
+ * still running behind the last sweep has ended.  A Localizer that has no map yet answers like an empty one (first = n = 0:
+ * FLIMO_OK, *nr = 0, stats 0; any other range lies beyond it).  There is no policy that calls them: which regions to forget, and
+ * when, is the caller's schedule. */
+int    flimo_loc_map_regions(flimo_loc* L, size_t first, size_t n, const flimo_region_cfg* cfg, int32_t* label, int32_t* size,
+                             unsigned char* mask, flimo_region_stats* stats);
+int    flimo_loc_map_region_list(flimo_loc* L, const flimo_region_cfg* cfg, size_t cap, size_t* nr, int32_t* label, int32_t* count,
+                                 int32_t* first, double* centroid, double* cov, flimo_region_stats* stats);
+int    flimo_loc_map_remove_regions(flimo_loc* L, size_t first, size_t n, const flimo_region_cfg* cfg, size_t* removed,
+                                    flimo_region_stats* stats);
 /* Pose hypotheses from point correspondences: flimo_corr_poses (include/flimo_c.h: same arguments, same results, same error
  * codes) on the map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  Neither the map
  * nor the resident scan is read; a Localizer that has no context yet creates it.  The Localizer's own update does not use it. */
