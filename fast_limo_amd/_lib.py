@@ -4,7 +4,7 @@
 ``libfast_limo.so``  -- host C++ mirror of the reference's Localizer / Mapper / esekf on top of it
 
 There is no Python or CPU fallback: if a library is missing or no gfx950 device is present the
-calls raise (``FlimoError``).
+calls raise (``FlimoError``).  The structures and the functions' signatures are in ``_abi``.
 """
 from __future__ import annotations
 
@@ -12,48 +12,21 @@ import ctypes as C
 import os
 import numpy as np
 
+from . import _abi
+# (every structure stays a name of this module: callers and tests say _lib.MatchCfg, _lib.Frame, ...)
+from ._abi import (CHAIN_MAX_PASSES, CarveCfg, ChainIO, ChainPass, ClusterCfg, ClusterStats, CorrCfg, CorrGraphCfg, FilterCfg, FpfhCfg, Frame,
+                   KeypointCfg, MapCfg, MatchCfg, OutlierCfg, OutlierStats, PlaneCfg, PlaneSel, RegionCfg, RegionStats, VoxelCfg, VoxelStats,
+                   f32p, f64p, i32p)
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_PKG)
-
-f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
-f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
-i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 
 
 class FlimoError(RuntimeError):
     pass
 
 
-class MapCfg(C.Structure):
-    _fields_ = [("min_extent", C.c_float), ("bucket_size", C.c_int), ("downsample", C.c_int),
-                ("cell_size", C.c_float)]
-
-
-class MatchCfg(C.Structure):
-    _fields_ = [("NUM_MATCH_POINTS", C.c_int), ("MAX_NUM_MATCHES", C.c_int), ("MAX_NUM_PC2MATCH", C.c_int),
-                ("MAX_DIST_PLANE", C.c_double), ("PLANE_THRESHOLD", C.c_double), ("estimate_extrinsics", C.c_int)]
-
-
-class Frame(C.Structure):
-    _fields_ = [("p", C.c_float * 3), ("q", C.c_float * 4), ("v", C.c_float * 3), ("g", C.c_float * 3),
-                ("w", C.c_float * 3), ("a", C.c_float * 3), ("bg", C.c_float * 3), ("ba", C.c_float * 3),
-                ("time", C.c_double)]
-
-
-CHAIN_MAX_PASSES = 12
 RADIUS_SORTED = 1      # FLIMO_RADIUS_SORTED
-
-
-class FilterCfg(C.Structure):
-    """flimo_filter_cfg (include/flimo_c.h)."""
-    _fields_ = [("crop_active", C.c_int), ("crop_min", C.c_float * 3), ("crop_max", C.c_float * 3), ("dist_active", C.c_int),
-                ("min_dist", C.c_float), ("rate_active", C.c_int), ("rate_value", C.c_int), ("time_kind", C.c_int),
-                ("end_of_sweep", C.c_int), ("sweep_ref_time", C.c_double), ("fov_active", C.c_int), ("fov_angle", C.c_float)]
-
-
-class CarveCfg(C.Structure):
-    """flimo_carve_cfg (include/flimo_c.h)."""
-    _fields_ = [("res", C.c_int), ("win", C.c_int), ("margin", C.c_float), ("rel_margin", C.c_float), ("max_depth", C.c_float)]
 
 
 def carve_cfg(res=256, win=1, margin=0.2, rel_margin=0.02, max_depth=float("inf")) -> CarveCfg:
@@ -61,51 +34,9 @@ def carve_cfg(res=256, win=1, margin=0.2, rel_margin=0.02, max_depth=float("inf"
     return CarveCfg(int(res), int(win), float(margin), float(rel_margin), float(max_depth))
 
 
-class OutlierCfg(C.Structure):
-    """flimo_outlier_cfg (include/flimo_c.h)."""
-    _fields_ = [("k", C.c_int), ("max_dist", C.c_float), ("min_pts", C.c_int), ("std_mul", C.c_float)]
-
-
-class OutlierStats(C.Structure):
-    """flimo_outlier_stats (include/flimo_c.h)."""
-    _fields_ = [("n", C.c_uint64), ("n_stat", C.c_uint64), ("mu", C.c_double), ("sigma", C.c_double), ("threshold", C.c_double),
-                ("few", C.c_uint64), ("far", C.c_uint64), ("outliers", C.c_uint64)]
-
-    def as_dict(self):
-        return dict(n=int(self.n), n_stat=int(self.n_stat), mu=float(self.mu), sigma=float(self.sigma), threshold=float(self.threshold),
-                    few=int(self.few), far=int(self.far), outliers=int(self.outliers))
-
-
 def outlier_cfg(k=8, max_dist=float("inf"), min_pts=0, std_mul=1.0) -> OutlierCfg:
     """PCL's StatisticalOutlierRemoval with 8 neighbours and one sigma unless told otherwise: no gate, no count rule."""
     return OutlierCfg(int(k), float(max_dist), int(min_pts), float(std_mul))
-
-
-def outliers_call(call, n, want, cfg):
-    """The output arrays of flimo_map_outliers / flimo_loc_map_outliers (``call`` takes: cfg, mask, mean_dist, cnt, stats) as a dict
-    with the outputs named in ``want`` (of "mask", "mean_dist", "cnt") and "stats"; shared with ``api.Localizer``."""
-    unknown = set(want) - {"mask", "mean_dist", "cnt"}
-    if unknown:
-        raise ValueError(f"outliers: unknown outputs {sorted(unknown)}")
-    k = outlier_cfg(**cfg)
-    arr = {}
-    for name, dt in (("mask", np.uint8), ("mean_dist", np.float64), ("cnt", np.int32)):
-        if name in want:
-            arr[name] = np.zeros(max(n, 1), dt)
-    st = OutlierStats()
-    ptr = lambda name: arr[name].ctypes.data if name in arr else None
-    call(C.byref(k), ptr("mask"), ptr("mean_dist"), ptr("cnt"), C.byref(st))
-    out = {name: a[:n] for name, a in arr.items()}
-    if "mask" in out:
-        out["mask"] = out["mask"].astype(bool)
-    out["stats"] = st.as_dict()
-    return out
-
-
-class FpfhCfg(C.Structure):
-    """flimo_fpfh_cfg (include/flimo_c.h)."""
-    _fields_ = [("k", C.c_int), ("max_dist", C.c_float), ("normal_k", C.c_int), ("normal_max_dist", C.c_float), ("normal_min_pts", C.c_int),
-                ("has_viewpoint", C.c_int), ("viewpoint", C.c_float * 3)]
 
 
 def fpfh_cfg(k=32, max_dist=float("inf"), normal_k=10, normal_max_dist=float("inf"), normal_min_pts=3, viewpoint=None) -> FpfhCfg:
@@ -115,101 +46,14 @@ def fpfh_cfg(k=32, max_dist=float("inf"), normal_k=10, normal_max_dist=float("in
                    (C.c_float * 3)(*vp))
 
 
-def fpfh_call(call, n, want, cfg):
-    """The output arrays of flimo_map_fpfh / flimo_loc_map_fpfh (``call`` takes: cfg, fpfh, spfh, cnt) as a dict with "fpfh" and the
-    outputs named in ``want`` (of "spfh", "cnt"); shared with ``api.Localizer``."""
-    unknown = set(want) - {"spfh", "cnt"}
-    if unknown:
-        raise ValueError(f"fpfh: unknown outputs {sorted(unknown)}")
-    k = fpfh_cfg(**cfg)
-    arr = {"fpfh": np.zeros((max(n, 1), 33), np.float32)}
-    if "spfh" in want:
-        arr["spfh"] = np.zeros((max(n, 1), 33), np.uint8)
-    if "cnt" in want:
-        arr["cnt"] = np.zeros(max(n, 1), np.int32)
-    ptr = lambda name: arr[name].ctypes.data if name in arr else None
-    call(C.byref(k), ptr("fpfh"), ptr("spfh"), ptr("cnt"))
-    return {name: a[:n] for name, a in arr.items()}
-
-
-class KeypointCfg(C.Structure):
-    """flimo_keypoint_cfg (include/flimo_c.h)."""
-    _fields_ = [("k", C.c_int), ("max_dist", C.c_float), ("min_pts", C.c_int), ("gamma21", C.c_float), ("gamma32", C.c_float),
-                ("nms_k", C.c_int), ("nms_max_dist", C.c_float)]
-
-
 def keypoint_cfg(k=32, max_dist=float("inf"), min_pts=5, gamma21=0.975, gamma32=0.975, nms_k=32, nms_max_dist=float("inf")) -> KeypointCfg:
     """PCL's ISSKeypoint3D thresholds (0.975, 0.975, 5 neighbours) over neighbourhoods of 32 unless told otherwise: no gates."""
     return KeypointCfg(int(k), float(max_dist), int(min_pts), float(gamma21), float(gamma32), int(nms_k), float(nms_max_dist))
 
 
-def keypoints_call(call, n, want, cfg):
-    """The output arrays of flimo_map_keypoints / flimo_loc_map_keypoints (``call`` takes: cfg, mask, saliency, cnt, count) as a dict
-    with "mask" (bool), "count", "index" (the ascending int64 indices of the ones, relative to the range) and the outputs named in
-    ``want`` (of "saliency", "cnt"); shared with ``api.Localizer``."""
-    unknown = set(want) - {"saliency", "cnt"}
-    if unknown:
-        raise ValueError(f"keypoints: unknown outputs {sorted(unknown)}")
-    k = keypoint_cfg(**cfg)
-    arr = {"mask": np.zeros(max(n, 1), np.uint8)}
-    if "saliency" in want:
-        arr["saliency"] = np.zeros(max(n, 1), np.float64)
-    if "cnt" in want:
-        arr["cnt"] = np.zeros(max(n, 1), np.int32)
-    count = C.c_size_t(0)
-    ptr = lambda name: arr[name].ctypes.data if name in arr else None
-    call(C.byref(k), ptr("mask"), ptr("saliency"), ptr("cnt"), C.byref(count))
-    out = {name: a[:n] for name, a in arr.items()}
-    out["mask"] = out["mask"].astype(bool)
-    out["count"] = int(count.value)
-    out["index"] = np.flatnonzero(out["mask"]).astype(np.int64)
-    return out
-
-
-class ClusterCfg(C.Structure):
-    """flimo_cluster_cfg (include/flimo_c.h)."""
-    _fields_ = [("tol", C.c_float), ("min_size", C.c_int), ("max_size", C.c_int)]
-
-
-class ClusterStats(C.Structure):
-    """flimo_cluster_stats (include/flimo_c.h)."""
-    _fields_ = [("n", C.c_uint64), ("clusters", C.c_uint64), ("largest", C.c_uint64), ("sel_clusters", C.c_uint64),
-                ("sel_points", C.c_uint64)]
-
-    def as_dict(self):
-        return dict(n=int(self.n), clusters=int(self.clusters), largest=int(self.largest), sel_clusters=int(self.sel_clusters),
-                    sel_points=int(self.sel_points))
-
-
 def cluster_cfg(tol=0.5, min_size=1, max_size=0) -> ClusterCfg:
     """Half a metre, every component selected unless told otherwise (``max_size`` 0: no upper bound)."""
     return ClusterCfg(float(tol), int(min_size), int(max_size))
-
-
-def clusters_call(call, n, want, cfg):
-    """The output arrays of flimo_map_clusters / flimo_loc_map_clusters (``call`` takes: cfg, label, size, mask, stats) as a dict
-    with the outputs named in ``want`` (of "label", "size", "mask") and "stats"; shared with ``api.Localizer``."""
-    unknown = set(want) - {"label", "size", "mask"}
-    if unknown:
-        raise ValueError(f"clusters: unknown outputs {sorted(unknown)}")
-    k = cluster_cfg(**cfg)
-    arr = {}
-    for name, dt in (("label", np.int32), ("size", np.int32), ("mask", np.uint8)):
-        if name in want:
-            arr[name] = np.zeros(max(n, 1), dt)
-    st = ClusterStats()
-    ptr = lambda name: arr[name].ctypes.data if name in arr else None
-    call(C.byref(k), ptr("label"), ptr("size"), ptr("mask"), C.byref(st))
-    out = {name: a[:n] for name, a in arr.items()}
-    if "mask" in out:
-        out["mask"] = out["mask"].astype(bool)
-    out["stats"] = st.as_dict()
-    return out
-
-
-class CorrCfg(C.Structure):
-    """flimo_corr_cfg (include/flimo_c.h)."""
-    _fields_ = [("edge_sim", C.c_float), ("min_edge", C.c_float), ("max_dist", C.c_float)]
 
 
 CORR_OK, CORR_DEGENERATE, CORR_REJECTED = 0, 1, 2      # FLIMO_CORR_*: the status of a hypothesis
@@ -218,45 +62,6 @@ CORR_OK, CORR_DEGENERATE, CORR_REJECTED = 0, 1, 2      # FLIMO_CORR_*: the statu
 def corr_cfg(edge_sim=0.9, min_edge=0.0, max_dist=float("inf")) -> CorrCfg:
     """PCL's SampleConsensusPrerejective similarity threshold of 0.9 unless told otherwise: no shortest edge, no inlier gate."""
     return CorrCfg(float(edge_sim), float(min_edge), float(max_dist))
-
-
-_NONE = C.create_string_buffer(8)      # what an array of no element points at: the call wants its required pointers non-null
-
-
-def corr_call(call, src, dst, tri, want, cfg):
-    """The output arrays of flimo_corr_poses / flimo_loc_corr_poses (``call`` takes: src, dst, m, tri, nh, cfg, status, inliers,
-    sum_sqd, pose, pair_sqd) as a dict with "status", "inliers", "sum_sqd" and the outputs named in ``want`` (of "pose", "pair_sqd");
-    shared with ``api.Localizer``."""
-    unknown = set(want) - {"pose", "pair_sqd"}
-    if unknown:
-        raise ValueError(f"corr_poses: unknown outputs {sorted(unknown)}")
-    s = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
-    d = np.ascontiguousarray(dst, dtype=np.float32).reshape(-1, 3)
-    if s.shape != d.shape:
-        raise ValueError("corr_poses: src and dst must hold the same number of points")
-    t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
-    m, nh = s.shape[0], t.shape[0]
-    k = corr_cfg(**cfg)
-    out = {"status": np.zeros(nh, np.int32), "inliers": np.zeros(nh, np.int32), "sum_sqd": np.zeros(nh, np.float64)}
-    if "pose" in want:
-        out["pose"] = np.full((nh, 7), np.nan)
-    if "pair_sqd" in want:
-        out["pair_sqd"] = np.full((nh, m), -1, np.float32)
-    # (an array of no element may have no address)
-    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(_NONE))
-    call(ptr(s), ptr(d), m, ptr(t), nh, C.byref(k), ptr(out["status"]), ptr(out["inliers"]), ptr(out["sum_sqd"]), ptr(out.get("pose")),
-         ptr(out.get("pair_sqd")))
-    return out
-
-
-class PlaneCfg(C.Structure):
-    """flimo_plane_cfg (include/flimo_c.h)."""
-    _fields_ = [("dist", C.c_float), ("min_edge", C.c_float), ("min_sin", C.c_float), ("axis", C.c_float * 3), ("min_cos", C.c_float)]
-
-
-class PlaneSel(C.Structure):
-    """flimo_plane_sel (include/flimo_c.h)."""
-    _fields_ = [("normal", C.c_float * 3), ("anchor", C.c_float * 3), ("dist", C.c_float), ("side", C.c_int)]
 
 
 PLANE_OK, PLANE_DEGENERATE, PLANE_REJECTED = 0, 1, 2      # FLIMO_PLANE_*: the status of a hypothesis
@@ -286,45 +91,6 @@ def _as_plane_sel(sel, kw):
     return plane_sel(**kw)
 
 
-def planes_call(call, tri, want, cfg):
-    """The output arrays of flimo_map_planes / flimo_loc_map_planes (``call`` takes: tri, nh, cfg, status, inliers, sum_sq, plane) as
-    a dict with "status", "inliers", "sum_sq" and, named in ``want``, "plane" [nh, 4]; shared with ``api.Localizer``."""
-    unknown = set(want) - {"plane"}
-    if unknown:
-        raise ValueError(f"map_planes: unknown outputs {sorted(unknown)}")
-    t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
-    nh = t.shape[0]
-    k = plane_cfg(**cfg)
-    out = {"status": np.zeros(nh, np.int32), "inliers": np.zeros(nh, np.int32), "sum_sq": np.zeros(nh, np.float64)}
-    if "plane" in want:
-        out["plane"] = np.full((nh, 4), np.nan)
-    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(_NONE))
-    call(ptr(t), nh, C.byref(k), ptr(out["status"]), ptr(out["inliers"]), ptr(out["sum_sq"]), ptr(out.get("plane")))
-    return out
-
-
-def plane_mask_call(call, n, sel, want_mask):
-    """flimo_map_plane_mask / flimo_loc_map_plane_mask (``call`` takes: sel, mask, count): (mask [n] bool or None, count)."""
-    mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
-    count = C.c_size_t(0)
-    call(C.byref(sel), mask.ctypes.data if want_mask else None, C.byref(count))
-    return (mask[:n].astype(bool) if want_mask else None), int(count.value)
-
-
-class VoxelCfg(C.Structure):
-    """flimo_voxel_cfg (include/flimo_c.h)."""
-    _fields_ = [("leaf", C.c_float), ("keep", C.c_int), ("max_pts", C.c_int)]
-
-
-class VoxelStats(C.Structure):
-    """flimo_voxel_stats (include/flimo_c.h)."""
-    _fields_ = [("n", C.c_uint64), ("voxels", C.c_uint64), ("largest", C.c_uint64), ("outside", C.c_uint64), ("sel_points", C.c_uint64)]
-
-    def as_dict(self):
-        return dict(n=int(self.n), voxels=int(self.voxels), largest=int(self.largest), outside=int(self.outside),
-                    sel_points=int(self.sel_points))
-
-
 VOXEL_KEEP_FIRST, VOXEL_KEEP_NEAREST = 0, 1      # FLIMO_VOXEL_KEEP_*
 VOXEL_RUN = 64                                   # FLIMO_VOXEL_RUN
 VOXEL_HALF = 1 << 20                             # FLIMO_VOXEL_HALF
@@ -337,59 +103,8 @@ def voxel_cfg(leaf=0.25, keep=VOXEL_KEEP_FIRST, max_pts=1) -> VoxelCfg:
     return VoxelCfg(float(leaf), int(keep), int(max_pts))
 
 
-def voxels_call(call, cap, want, cfg):
-    """The output arrays of flimo_map_voxels / flimo_loc_map_voxels (``call`` takes: cfg, cap, nv, ijk, count, first, rep, centroid,
-    cov, stats) as a dict with the outputs named in ``want`` (of "ijk", "count", "first", "rep", "centroid", "cov"), "nv" and
-    "stats"; ``cap``: the map's size (no more voxels than points: one call); shared with ``api.Localizer``."""
-    unknown = set(want) - {name for name, _, _ in VOXEL_OUTPUTS}
-    if unknown:
-        raise ValueError(f"map_voxels: unknown outputs {sorted(unknown)}")
-    k = voxel_cfg(**cfg)
-    arr = {name: np.zeros((max(cap, 1), w) if w > 1 else max(cap, 1), dt) for name, dt, w in VOXEL_OUTPUTS if name in want}
-    nv = C.c_size_t(0)
-    st = VoxelStats()
-    ptr = lambda name: arr[name].ctypes.data if name in arr else None
-    call(C.byref(k), cap, C.byref(nv), ptr("ijk"), ptr("count"), ptr("first"), ptr("rep"), ptr("centroid"), ptr("cov"), C.byref(st))
-    out = {name: a[:nv.value].copy() for name, a in arr.items()}
-    out["nv"] = int(nv.value)
-    out["stats"] = st.as_dict()
-    return out
-
-
-def voxel_mask_call(call, n, want, cfg):
-    """flimo_map_voxel_mask / flimo_loc_map_voxel_mask (``call`` takes: cfg, voxel, mask, stats): a dict with the outputs named in
-    ``want`` (of "voxel", "mask") and "stats"."""
-    unknown = set(want) - {"voxel", "mask"}
-    if unknown:
-        raise ValueError(f"map_voxel_mask: unknown outputs {sorted(unknown)}")
-    k = voxel_cfg(**cfg)
-    arr = {name: np.zeros(max(n, 1), dt) for name, dt in (("voxel", np.int32), ("mask", np.uint8)) if name in want}
-    st = VoxelStats()
-    ptr = lambda name: arr[name].ctypes.data if name in arr else None
-    call(C.byref(k), ptr("voxel"), ptr("mask"), C.byref(st))
-    out = {name: a[:n] for name, a in arr.items()}
-    if "mask" in out:
-        out["mask"] = out["mask"].astype(bool)
-    out["stats"] = st.as_dict()
-    return out
-
-
-class RegionCfg(C.Structure):
-    """flimo_region_cfg (include/flimo_c.h)."""
-    _fields_ = [("tol", C.c_float), ("normal_k", C.c_int), ("normal_max_dist", C.c_float), ("normal_min_pts", C.c_int), ("min_cos", C.c_float),
-                ("max_curv", C.c_float), ("border", C.c_int), ("min_size", C.c_int), ("max_size", C.c_int)]
-
-
-class RegionStats(C.Structure):
-    """flimo_region_stats (include/flimo_c.h)."""
-    _fields_ = [("n", C.c_uint64), ("smooth", C.c_uint64), ("regions", C.c_uint64), ("largest", C.c_uint64), ("sel_regions", C.c_uint64),
-                ("unassigned", C.c_uint64), ("sel_points", C.c_uint64)]
-
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
-
-
 REGION_OUTPUTS = (("label", np.int32, 1), ("count", np.int32, 1), ("first", np.int32, 1), ("centroid", np.float64, 3), ("cov", np.float64, 6))
+REGION_LIST_CAP = 1024      # regions the first call of ``map_region_list`` has room for
 
 
 def region_cfg(tol=0.5, normal_k=16, normal_max_dist=float("inf"), normal_min_pts=3, min_cos=0.93969262, max_curv=0.05, border=1, min_size=1,
@@ -400,89 +115,12 @@ def region_cfg(tol=0.5, normal_k=16, normal_max_dist=float("inf"), normal_min_pt
                      int(min_size), int(max_size))
 
 
-def regions_call(call, n, want, cfg):
-    """The output arrays of flimo_map_regions / flimo_loc_map_regions (``call`` takes: cfg, label, size, mask, stats) as a dict
-    with the outputs named in ``want`` (of "label", "size", "mask") and "stats"; shared with ``api.Localizer``."""
-    unknown = set(want) - {"label", "size", "mask"}
-    if unknown:
-        raise ValueError(f"map_regions: unknown outputs {sorted(unknown)}")
-    k = region_cfg(**cfg)
-    arr = {name: np.zeros(max(n, 1), dt) for name, dt in (("label", np.int32), ("size", np.int32), ("mask", np.uint8)) if name in want}
-    st = RegionStats()
-    ptr = lambda name: arr[name].ctypes.data if name in arr else None
-    call(C.byref(k), ptr("label"), ptr("size"), ptr("mask"), C.byref(st))
-    out = {name: a[:n] for name, a in arr.items()}
-    if "mask" in out:
-        out["mask"] = out["mask"].astype(bool)
-    out["stats"] = st.as_dict()
-    return out
-
-
-REGION_LIST_CAP = 1024      # regions the first call of ``region_list_call`` has room for
-
-
-def region_list_call(call, chk, want, cfg):
-    """The output arrays of flimo_map_region_list / flimo_loc_map_region_list (``call`` takes: cfg, cap, nr, label, count, first,
-    centroid, cov, stats and returns the code, ``chk`` raises on one) as a dict with the outputs named in ``want`` (of "label",
-    "count", "first", "centroid", "cov"), "nr" and "stats".  Selected regions are few: one call with room for ``REGION_LIST_CAP`` of
-    them, and a second with room for ``nr`` only where the first answers FLIMO_ERR_TOO_LARGE."""
-    unknown = set(want) - {name for name, _, _ in REGION_OUTPUTS}
-    if unknown:
-        raise ValueError(f"map_region_list: unknown outputs {sorted(unknown)}")
-    k = region_cfg(**cfg)
-    nr = C.c_size_t(0)
-    st = RegionStats()
-    cap = REGION_LIST_CAP
-    while True:
-        arr = {name: np.zeros((cap, w) if w > 1 else cap, dt) for name, dt, w in REGION_OUTPUTS if name in want}
-        ptr = lambda name: arr[name].ctypes.data if name in arr else None
-        rc = call(C.byref(k), cap, C.byref(nr), ptr("label"), ptr("count"), ptr("first"), ptr("centroid"), ptr("cov"), C.byref(st))
-        if rc == -5 and nr.value > cap:      # FLIMO_ERR_TOO_LARGE: *nr says how many there are
-            cap = int(nr.value)
-            continue
-        chk(rc)
-        break
-    out = {name: a[:nr.value].copy() for name, a in arr.items()}
-    out["nr"] = int(nr.value)
-    out["stats"] = st.as_dict()
-    return out
-
-
-class CorrGraphCfg(C.Structure):
-    """flimo_corr_graph_cfg (include/flimo_c.h)."""
-    _fields_ = [("tol", C.c_float), ("min_edge", C.c_float), ("edge_sim", C.c_float)]
-
-
 CORR_GRAPH_MAX_M = 32768      # FLIMO_CORR_GRAPH_MAX_M
 
 
 def corr_graph_cfg(tol=0.05, min_edge=0.0, edge_sim=0.0) -> CorrGraphCfg:
     """Edge lengths within 5 cm of each other unless told otherwise: no shortest edge, no polygon test."""
     return CorrGraphCfg(float(tol), float(min_edge), float(edge_sim))
-
-
-def corr_graph_call(call, src, dst, want, cfg):
-    """The output arrays of flimo_corr_graph / flimo_loc_corr_graph (``call`` takes: src, dst, m, cfg, degree, core, max_core, adj)
-    as a dict with "degree", "core" [m] int32, "max_core" (an int; 0 for m = 0) and, named in ``want``, "adj" [m, (m + 63) // 64]
-    uint64; shared with ``api.Localizer``."""
-    unknown = set(want) - {"adj"}
-    if unknown:
-        raise ValueError(f"corr_graph: unknown outputs {sorted(unknown)}")
-    s = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
-    d = np.ascontiguousarray(dst, dtype=np.float32).reshape(-1, 3)
-    if s.shape != d.shape:
-        raise ValueError("corr_graph: src and dst must hold the same number of points")
-    m = s.shape[0]
-    k = corr_graph_cfg(**cfg)
-    out = {"degree": np.zeros(m, np.int32), "core": np.zeros(m, np.int32)}
-    if "adj" in want:
-        out["adj"] = np.zeros((m, (m + 63) // 64), np.uint64)
-    top = C.c_int32(0)
-    # (an array of no element may have no address)
-    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(_NONE))
-    call(ptr(s), ptr(d), m, C.byref(k), ptr(out["degree"]), ptr(out["core"]), C.byref(top), ptr(out.get("adj")))
-    out["max_core"] = int(top.value)
-    return out
 
 
 DESC_MAX_DIM, DESC_MAX_K = 64, 8      # FLIMO_DESC_MAX_DIM / FLIMO_DESC_MAX_K
@@ -494,31 +132,6 @@ def desc_rows(desc):
     return d.reshape(-1, 1) if d.ndim == 1 else d.reshape(d.shape[0], int(np.prod(d.shape[1:])))
 
 
-def desc_match_call(call, q, k):
-    """The output arrays of flimo_desc_match / flimo_loc_desc_match (``call`` takes: q, nq, dim, k, idx, dist, cnt) as a dict
-    ``idx`` [nq, k] int32, ``dist`` [nq, k] float32, ``cnt`` [nq] int32; shared with ``api.Localizer``."""
-    q = desc_rows(q)
-    nq, kk = q.shape[0], max(int(k), 1)
-    out = {"idx": np.full((nq, kk), -1, np.int32), "dist": np.zeros((nq, kk), np.float32), "cnt": np.zeros(nq, np.int32)}
-    ptr = lambda a: a.ctypes.data if a.size else C.addressof(_NONE)      # (an array of no element may have no address)
-    call(ptr(q), nq, q.shape[1], int(k), ptr(out["idx"]), ptr(out["dist"]), ptr(out["cnt"]))
-    return out
-
-
-class ChainPass(C.Structure):
-    _fields_ = [("M", C.c_int), ("stragglers", C.c_int), ("ties", C.c_int), ("HTH", C.c_double * 144), ("HTh", C.c_double * 12),
-                ("dx", C.c_double * 23), ("x_after", C.c_double * 26)]
-
-
-class ChainIO(C.Structure):
-    """flimo_chain_io (include/flimo_c.h): arguments and results of flimo_update_chain."""
-    _fields_ = [("x26", C.c_double * 26), ("P", C.c_double * 529), ("limits", C.c_double * 23), ("R", C.c_double), ("D", C.c_double),
-                ("max_iter", C.c_int), ("want_log", C.c_int),
-                ("status", C.c_int), ("reason", C.c_int), ("passes", C.c_int), ("it_next", C.c_int), ("t", C.c_int),
-                ("x26_out", C.c_double * 26), ("meas_valid", C.c_int), ("meas_M", C.c_int), ("meas_HTH", C.c_double * 144),
-                ("meas_HTh", C.c_double * 12), ("log", ChainPass * CHAIN_MAX_PASSES)]
-
-
 MATCH_REC_DTYPE = np.dtype([
     ("H", np.float32, 12), ("h", np.float32), ("valid", np.float32), ("n", np.float32, 4),
     ("p_global", np.float32, 3), ("sqd", np.float32, 5), ("nbr", np.int32, 5), ("n_nbr", np.int32)])
@@ -527,71 +140,9 @@ FRAME_DTYPE = np.dtype([
     ("p", np.float32, 3), ("q", np.float32, 4), ("v", np.float32, 3), ("g", np.float32, 3), ("w", np.float32, 3),
     ("a", np.float32, 3), ("bg", np.float32, 3), ("ba", np.float32, 3), ("_pad", np.float32), ("time", np.float64)])
 
-# every symbol include/flimo_c.h declares (tests check the .so exports each one)
-HIP_SYMBOLS = [
-    "flimo_ctx_create", "flimo_ctx_destroy", "flimo_last_error", "flimo_version",
-    "flimo_map_config", "flimo_map_add", "flimo_map_clear", "flimo_map_crop_box", "flimo_map_crop_stats", "flimo_map_seen_through", "flimo_map_carve", "flimo_map_carve_stats", "flimo_map_outliers", "flimo_map_remove_outliers", "flimo_set_outlier_chunk", "flimo_map_fpfh", "flimo_set_fpfh_chunk", "flimo_map_keypoints", "flimo_set_keypoints_chunk", "flimo_map_clusters", "flimo_map_remove_clusters", "flimo_set_cluster_chunk", "flimo_map_planes", "flimo_plane_solve_host", "flimo_map_plane_mask", "flimo_map_remove_plane", "flimo_set_plane_chunk", "flimo_map_voxels", "flimo_map_voxel_mask", "flimo_map_thin", "flimo_voxel_key_host", "flimo_set_voxel_plan", "flimo_map_regions", "flimo_map_region_list", "flimo_map_remove_regions", "flimo_region_joined_host", "flimo_set_region_chunk", "flimo_map_size", "flimo_map_last_time",
-    "flimo_map_points", "flimo_knn", "flimo_radius_search", "flimo_radius_candidates", "flimo_knn_k", "flimo_knn_k_candidates", "flimo_map_normals", "flimo_map_normals_range", "flimo_set_normals_chunk", "flimo_scan_set", "flimo_scan_fitness", "flimo_set_fitness_chunk", "flimo_scan_linearize", "flimo_set_linearize_chunk", "flimo_corr_poses", "flimo_corr_pose_host", "flimo_set_corr_chunk", "flimo_corr_graph", "flimo_corr_compatible_host", "flimo_desc_ref_set", "flimo_desc_ref_size", "flimo_desc_ref_dim", "flimo_desc_match", "flimo_desc_dist_host", "flimo_set_desc_chunk", "flimo_desc_last_ms", "flimo_scan_size", "flimo_scan_get",
-    "flimo_scan_voxel_filter", "flimo_raw_scan_set", "flimo_raw_scan_filter_set", "flimo_raw_scan_filter_order_set", "flimo_raw_scan_order", "flimo_deskew_resident", "flimo_deskew_resident_offset", "flimo_deskew",
-    "flimo_match_reduce", "flimo_match_fetch", "flimo_match_fetch_H",
-    "flimo_scan_to_world", "flimo_scan_clouds", "flimo_scan_debug_clouds", "flimo_upload_stage", "flimo_match_reduce_overlap", "flimo_map_add_scan",
-    "flimo_set_timing", "flimo_set_timing_stride", "flimo_set_timing_deferred", "flimo_pass_count", "flimo_fused_pass_count", "flimo_tie_stats", "flimo_map_index_bytes", "flimo_map_index_layout", "flimo_fine_stats", "flimo_map_grid_selfcheck", "flimo_set_debug_records", "flimo_last_kernel_ms",
-    "flimo_last_candidates_per_query", "flimo_last_widen_count", "flimo_last_stragglers", "flimo_stragglers_by_pass", "flimo_timing_totals", "flimo_timing_split", "flimo_set_path_switches", "flimo_set_wait_timeout_ms", "flimo_insert_rule_replay", "flimo_plane_fit5_host", "flimo_plane_eval5_host", "flimo_calculate_H_host",
-    "flimo_update_chain", "flimo_chain_stats", "flimo_set_update_mode", "flimo_update_mode", "flimo_scan_adopt", "flimo_set_pass_pipeline", "flimo_pass_pipeline_end", "flimo_pass_pipeline_last", "flimo_pass_pipeline_stats", "flimo_device_large_bar",
-    "flimo_ieskf_op_shape", "flimo_ieskf_eval", "flimo_ieskf_eval_host", "flimo_ieskf_run_fixed",
-]
+HIP_SYMBOLS = _abi.HIP_SYMBOLS      # every symbol include/flimo_c.h and include/flimo_dev.h declare (tests check the .so exports each one)
 
 _hip = None
-
-
-def normals_call(call, nq, k, max_dist, min_pts, viewpoint, want):
-    """The output arrays of flimo_map_normals / flimo_map_normals_range and the call's common arguments (``call`` takes them: k,
-    max_dist, min_pts, viewpoint, normal, cnt, centroid, cov, eig); shared with ``api.Localizer``."""
-    unknown = set(want) - {"centroid", "cov", "eig"}
-    if unknown:
-        raise ValueError(f"normals: unknown outputs {sorted(unknown)}")
-    out = {"normal": np.empty((nq, 4), np.float32), "cnt": np.empty((nq,), np.int32)}
-    for name, w in (("centroid", 3), ("cov", 6), ("eig", 6)):
-        if name in want:
-            out[name] = np.empty((nq, w), np.float64)
-    vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float32).reshape(3)
-    # (an array of no element may have no address; the call wants its pointers non-null)
-    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(C.c_double()))
-    call(int(k), float(max_dist), int(min_pts), None if vp is None else vp.ctypes.data, ptr(out["normal"]), ptr(out["cnt"]),
-         ptr(out.get("centroid")), ptr(out.get("cov")), ptr(out.get("eig")))
-    return out
-
-
-def fitness_call(call, x26s, n, max_dist, want_nn):
-    """The output arrays of flimo_scan_fitness / flimo_loc_scan_fitness and the call's arguments (``call`` takes them: x26, np,
-    max_dist, inliers, sum_sqd, nn_sqd, nn_idx); ``n``: the size of the resident scan.  Shared with ``api.Localizer``."""
-    x = np.ascontiguousarray(x26s, dtype=np.float64).reshape(-1, 26)
-    m = x.shape[0]
-    inliers = np.zeros(m, np.int32)
-    sum_sqd = np.zeros(m, np.float64)
-    nn_sqd = np.full((m, n), -1, np.float32) if want_nn else None
-    nn_idx = np.full((m, n), -1, np.int32) if want_nn else None
-    # (an array of no element may have no address; the call wants its required pointers non-null)
-    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(C.c_double()))
-    call(x.ctypes.data if m else None, m, float(max_dist), ptr(inliers), ptr(sum_sqd), ptr(nn_sqd), ptr(nn_idx))
-    return (inliers, sum_sqd, nn_sqd, nn_idx) if want_nn else (inliers, sum_sqd)
-
-
-def linearize_call(call, x26s, n, k, max_dist, min_pts, max_curv, want_rows):
-    """The output arrays of flimo_scan_linearize / flimo_loc_scan_linearize and the call's arguments (``call`` takes them: x26, np, k,
-    max_dist, min_pts, max_curv, valid, H, g, cost, rows, pair_cnt); ``n``: the size of the resident scan.  Shared with
-    ``api.Localizer``.  Returns a dict: valid [np] int32, H [np, 21], g [np, 6], cost [np][, rows [np, n, 7], pair_cnt [np, n]]."""
-    x = np.ascontiguousarray(x26s, dtype=np.float64).reshape(-1, 26)
-    m = x.shape[0]
-    out = {"valid": np.zeros(m, np.int32), "H": np.zeros((m, 21)), "g": np.zeros((m, 6)), "cost": np.zeros(m)}
-    if want_rows:
-        out["rows"] = np.full((m, n, 7), np.nan)
-        out["pair_cnt"] = np.zeros((m, n), np.int32)
-    # (an array of no element may have no address; the call wants its required pointers non-null)
-    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else C.addressof(C.c_double()))
-    call(x.ctypes.data if m else None, m, int(k), float(max_dist), int(min_pts), float(max_curv), ptr(out["valid"]), ptr(out["H"]), ptr(out["g"]),
-         ptr(out["cost"]), ptr(out.get("rows")), ptr(out.get("pair_cnt")))
-    return out
 
 
 def hip_lib_path() -> str:
@@ -608,154 +159,7 @@ def load_hip():
     if not os.path.exists(path):
         raise FlimoError(f"{path} not found: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     L = C.CDLL(path)
-    vp = C.c_void_p
-    L.flimo_ctx_create.restype = C.c_int
-    L.flimo_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.flimo_ctx_destroy.restype = None
-    L.flimo_ctx_destroy.argtypes = [vp]
-    L.flimo_last_error.restype = C.c_char_p
-    L.flimo_last_error.argtypes = [vp]
-    L.flimo_version.restype = C.c_char_p
-    L.flimo_map_config.argtypes = [vp, C.POINTER(MapCfg)]
-    L.flimo_map_add.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.c_double]
-    L.flimo_map_clear.argtypes = [vp]
-    L.flimo_map_crop_box.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
-    L.flimo_map_crop_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.flimo_map_size.restype = C.c_size_t
-    L.flimo_map_seen_through.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(CarveCfg), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.flimo_map_carve.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(CarveCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
-    L.flimo_map_carve_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.flimo_map_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(OutlierCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OutlierStats)]
-    L.flimo_map_remove_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(OutlierCfg), C.POINTER(C.c_size_t), C.POINTER(OutlierStats)]
-    L.flimo_set_outlier_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_map_fpfh.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(FpfhCfg), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_set_fpfh_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_map_keypoints.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(KeypointCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
-    L.flimo_set_keypoints_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_map_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(ClusterCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClusterStats)]
-    L.flimo_map_remove_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(ClusterCfg), C.POINTER(C.c_size_t), C.POINTER(ClusterStats)]
-    L.flimo_set_cluster_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_map_planes.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(PlaneCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_plane_solve_host.argtypes = [C.c_void_p, C.POINTER(PlaneCfg), C.c_void_p, C.c_void_p]
-    L.flimo_map_plane_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PlaneSel), C.c_void_p, C.POINTER(C.c_size_t)]
-    L.flimo_map_remove_plane.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(PlaneSel), C.POINTER(C.c_size_t)]
-    L.flimo_set_plane_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_map_voxels.argtypes = [vp, C.POINTER(VoxelCfg), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.POINTER(VoxelStats)]
-    L.flimo_map_voxel_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(VoxelCfg), C.c_void_p, C.c_void_p, C.POINTER(VoxelStats)]
-    L.flimo_map_thin.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(VoxelCfg), C.POINTER(C.c_size_t), C.POINTER(VoxelStats)]
-    L.flimo_voxel_key_host.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
-    L.flimo_set_voxel_plan.argtypes = [vp, C.c_int]
-    L.flimo_map_regions.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(RegionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RegionStats)]
-    L.flimo_map_region_list.argtypes = [vp, C.POINTER(RegionCfg), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.POINTER(RegionStats)]
-    L.flimo_map_remove_regions.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(RegionCfg), C.POINTER(C.c_size_t), C.POINTER(RegionStats)]
-    L.flimo_region_joined_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RegionCfg), C.POINTER(C.c_int),
-                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.flimo_set_region_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_map_size.argtypes = [vp]
-    L.flimo_map_last_time.restype = C.c_double
-    L.flimo_map_last_time.argtypes = [vp]
-    L.flimo_map_points.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.flimo_knn.argtypes = [vp, f32p, C.c_size_t, C.c_int, i32p, f32p, i32p]
-    L.flimo_radius_search.argtypes = [vp, f32p, C.c_size_t, C.c_float, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_size_t, C.POINTER(C.c_uint64)]
-    L.flimo_radius_candidates.argtypes = [vp, f32p, C.c_size_t, C.c_float, C.c_void_p]
-    L.flimo_knn_k.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_knn_k_candidates.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p]
-    L.flimo_map_normals.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]
-    L.flimo_map_normals_range.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]
-    L.flimo_set_normals_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_scan_fitness.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_set_fitness_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_scan_linearize.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_set_linearize_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_corr_poses.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(CorrCfg), C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_corr_pose_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CorrCfg), C.c_void_p, C.c_void_p]
-    L.flimo_set_corr_chunk.argtypes = [vp, C.c_size_t]
-    L.flimo_corr_graph.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CorrGraphCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_corr_compatible_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CorrGraphCfg)]
-    L.flimo_desc_ref_set.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int]
-    L.flimo_desc_ref_size.restype = C.c_size_t
-    L.flimo_desc_ref_size.argtypes = [vp]
-    L.flimo_desc_ref_dim.argtypes = [vp]
-    L.flimo_desc_match.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_desc_dist_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.flimo_set_desc_chunk.argtypes = [vp, C.c_size_t, C.c_size_t]
-    L.flimo_desc_last_ms.restype = C.c_float
-    L.flimo_desc_last_ms.argtypes = [vp]
-    L.flimo_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
-    L.flimo_scan_size.restype = C.c_size_t
-    L.flimo_scan_size.argtypes = [vp]
-    L.flimo_scan_get.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.flimo_scan_voxel_filter.argtypes = [vp, C.c_float, C.POINTER(C.c_size_t)]
-    L.flimo_raw_scan_set.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, f64p]
-    L.flimo_deskew_resident.argtypes = [vp, C.c_void_p, C.c_size_t, f32p, f64p]
-    L.flimo_deskew.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, f64p, C.c_void_p, C.c_size_t, f32p, f64p]
-    L.flimo_match_reduce.argtypes = [vp, f64p, C.POINTER(MatchCfg), f64p, f64p, C.POINTER(C.c_int)]
-    L.flimo_match_fetch.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.flimo_match_fetch_H.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.flimo_scan_to_world.argtypes = [vp, f64p, C.c_void_p, C.c_size_t]
-    L.flimo_scan_clouds.argtypes = [vp, f64p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.flimo_scan_debug_clouds.argtypes = [vp, f64p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.flimo_upload_stage.argtypes = [vp, C.c_size_t, C.POINTER(C.c_void_p)]
-    L.flimo_map_add_scan.argtypes = [vp, f64p, C.c_double]
-    L.flimo_set_timing.argtypes = [vp, C.c_int]
-    L.flimo_set_wait_timeout_ms.argtypes = [vp, C.c_int]
-    L.flimo_set_timing_stride.argtypes = [vp, C.c_int]
-    L.flimo_set_timing_deferred.argtypes = [vp, C.c_int]
-    L.flimo_pass_count.restype = C.c_ulonglong
-    L.flimo_pass_count.argtypes = [vp]
-    L.flimo_tie_stats.argtypes = [vp, C.POINTER(C.c_ulonglong)]
-    L.flimo_fine_stats.argtypes = [vp, C.POINTER(C.c_ulonglong)]
-    L.flimo_map_index_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.flimo_map_index_layout.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
-    L.flimo_fused_pass_count.restype = C.c_ulonglong
-    L.flimo_fused_pass_count.argtypes = [vp]
-    L.flimo_map_grid_selfcheck.restype = C.c_int
-    L.flimo_map_grid_selfcheck.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    L.flimo_set_debug_records.argtypes = [vp, C.c_int]
-    L.flimo_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.flimo_timing_totals.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                      C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_int]
-    L.flimo_timing_split.argtypes = [vp, f64p, C.c_int]
-    L.flimo_set_path_switches.argtypes = [vp, C.c_int, C.c_int]
-    L.flimo_insert_rule_replay.argtypes = [C.c_float, C.c_int, f32p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
-    L.flimo_calculate_H_host.argtypes = [f64p, f32p, f32p, f32p, C.c_size_t, C.c_int, f64p, f64p]
-    L.flimo_update_chain.argtypes = [vp, C.POINTER(MatchCfg), C.POINTER(ChainIO)]
-    L.flimo_chain_stats.argtypes = [vp, f64p, C.c_int]
-    L.flimo_set_update_mode.argtypes = [vp, C.c_int]
-    L.flimo_scan_adopt.argtypes = [vp, vp]
-    L.flimo_raw_scan_filter_order_set.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(FilterCfg), C.c_int, C.POINTER(C.c_size_t),
-                                                  C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.flimo_raw_scan_order.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.flimo_deskew_resident_offset.argtypes = [vp, C.c_void_p, C.c_size_t, np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
-                                               np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS"), C.c_double]
-    L.flimo_set_pass_pipeline.argtypes = [vp, C.c_int]
-    L.flimo_pass_pipeline_end.argtypes = [vp]
-    L.flimo_pass_pipeline_last.argtypes = [vp]
-    L.flimo_pass_pipeline_stats.argtypes = [vp, C.POINTER(C.c_ulonglong)]
-    L.flimo_update_mode.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
-    L.flimo_last_widen_count.restype = C.c_int
-    L.flimo_last_widen_count.argtypes = [vp]
-    L.flimo_last_stragglers.restype = C.c_int
-    L.flimo_last_stragglers.argtypes = [vp]
-    L.flimo_stragglers_by_pass.argtypes = [vp, C.POINTER(C.c_int)]
-    L.flimo_last_candidates_per_query.restype = C.c_double
-    L.flimo_last_candidates_per_query.argtypes = [vp]
-    L.flimo_ieskf_op_shape.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.flimo_ieskf_eval.argtypes = [vp, C.c_int, f64p, C.c_size_t, f64p]
-    L.flimo_ieskf_eval_host.argtypes = [C.c_int, f64p, C.c_size_t, f64p, C.c_void_p]
-    L.flimo_ieskf_run_fixed.argtypes = [vp, f64p, f64p, f64p, C.c_double, C.c_double, C.c_int, C.c_int, f64p, f64p, C.c_void_p, f64p, f64p,
-                                        C.POINTER(C.c_int)]
-    for name in HIP_SYMBOLS:
-        fn = getattr(L, name)
-        if fn.restype is C.c_int and name not in ("flimo_ctx_create",):
-            pass
+    _abi.declare(L, 0)
     _hip = L
     return L
 
@@ -763,9 +167,449 @@ def load_hip():
 _ERRS = {-1: "no gfx950 device", -2: "invalid argument", -3: "HIP error", -4: "no map", -5: "too large",
          -6: "unsupported", -7: "TIMEOUT"}
 
+# ---- the entries a HipCtx and an api.Localizer share ----
+# The outputs of an entry that fills one row per point, query or listed item: (name, dtype, width), in the order of the call's
+# arguments (VOXEL_OUTPUTS and REGION_OUTPUTS above are two more).
+_OUTLIER_OUTPUTS = (("mask", np.uint8, 1), ("mean_dist", np.float64, 1), ("cnt", np.int32, 1))
+_FPFH_OUTPUTS = (("fpfh", np.float32, 33), ("spfh", np.uint8, 33), ("cnt", np.int32, 1))
+_KEYPOINT_OUTPUTS = (("mask", np.uint8, 1), ("saliency", np.float64, 1), ("cnt", np.int32, 1))
+_COMPONENT_OUTPUTS = (("label", np.int32, 1), ("size", np.int32, 1), ("mask", np.uint8, 1))      # clusters and regions
+_VOXEL_MASK_OUTPUTS = (("voxel", np.int32, 1), ("mask", np.uint8, 1))
+_NORMAL_OUTPUTS = (("normal", np.float32, 4), ("cnt", np.int32, 1), ("centroid", np.float64, 3), ("cov", np.float64, 6), ("eig", np.float64, 6))
 
-class HipCtx:
+_NONE = C.create_string_buffer(8)
+
+
+def _ptr(a):
+    """The address of an array as a call takes it.  None -- an output left out -- stays None; an array of no element, which may
+    have no address, points at eight spare bytes: the calls want their required pointers non-null."""
+    return None if a is None else (a.ctypes.data if a.size else C.addressof(_NONE))
+
+
+def _outputs(what, table, want, rows, always=()):
+    """The zeroed output arrays of an entry by name, ``rows`` long each: those of ``table`` that are in ``always`` or named in
+    ``want``.  A name in ``want`` that is none of the entry's optional outputs raises."""
+    unknown = set(want) - {name for name, _, _ in table if name not in always}
+    if unknown:
+        raise ValueError(f"{what}: unknown outputs {sorted(unknown)}")
+    return {name: np.zeros((rows, w) if w > 1 else rows, dt) for name, dt, w in table if name in always or name in want}
+
+
+def _ptrs(arr, table):
+    return [_ptr(arr.get(name)) for name, _, _ in table]
+
+
+def _result(arr, stats=None, rows=None):
+    """What the method returns: the arrays -- copies of their first ``rows`` rows where the call said how many it filled --,
+    ``mask`` as bool, and ``stats`` as a dict."""
+    out = dict(arr) if rows is None else {name: a[:rows].copy() for name, a in arr.items()}
+    if "mask" in out:
+        out["mask"] = out["mask"].astype(bool)
+    if stats is not None:
+        out["stats"] = stats.as_dict()
+    return out
+
+
+def _poses(x26s):
+    return np.ascontiguousarray(x26s, dtype=np.float64).reshape(-1, 26)
+
+
+def _pairs(what, src, dst):
+    s = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dst, dtype=np.float32).reshape(-1, 3)
+    if s.shape != d.shape:
+        raise ValueError(f"{what}: src and dst must hold the same number of points")
+    return s, d
+
+
+class _SharedEntries:
+    """The methods ``HipCtx`` and ``api.Localizer`` share, once; an entry is named by its symbol in libflimo_hip.so (a row of
+    ``_abi.PAIRED``).  A class supplies ``_L`` and ``_h`` (library and handle), ``_symbol(entry)`` (the symbol it calls for the
+    entry), ``_fail(entry, rc)`` (raise for a non-zero code), ``map_size()`` and ``_scan_size()`` (points of the resident
+    scan).  Through a ``Localizer`` every one of them first waits for an insert, a crop or a carve still running behind
+    the last sweep (the ``flimo_loc_*`` forwarder does)."""
+
+    def _code(self, entry, *args):
+        return getattr(self._L, self._symbol(entry))(self._h, *args)
+
+    def _entry(self, entry, *args):
+        rc = self._code(entry, *args)
+        if rc != 0:
+            self._fail(entry, rc)
+
+    def _range(self, first, n):
+        """(first, n) of a range entry; ``n`` None: up to the map's end."""
+        first = int(first)
+        return first, max(self.map_size() - first, 0) if n is None else int(n)
+
+    def _remove(self, entry, first, n, k, stats):
+        """The tail of the entries that forget the points of a range by a cfg: (points removed, stats)."""
+        first, n = self._range(first, n)
+        removed = C.c_size_t(0)
+        self._entry(entry, first, n, C.byref(k), C.byref(removed), C.byref(stats))
+        return int(removed.value), stats.as_dict()
+
+    def map_seen_through(self, x26, sensor, want_mask=True, **cfg):
+        """The stored points that the resident scan, moved to the world frame by ``x26``, looks through from ``sensor`` (world
+        frame) -- flimo_map_seen_through; ``cfg``: the fields of ``carve_cfg``.  Returns (mask [map size] bool in insertion order,
+        count); changes nothing.  A ``Localizer`` first waits for an insert, a crop or a carve still running behind the last sweep;
+        its resident scan is the last sweep's (``pc2match()``)."""
+        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
+        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
+        k = carve_cfg(**cfg)
+        n = self.map_size()
+        mask = np.zeros(n, np.uint8) if want_mask else None
+        count = C.c_size_t(0)
+        self._entry("flimo_map_seen_through", x.ctypes.data, s.ctypes.data, C.byref(k), _ptr(mask), n, C.byref(count))
+        return (mask.astype(bool) if want_mask else None), int(count.value)
+
+    def map_carve(self, x26, sensor, box=None, **cfg) -> int:
+        """Forget the stored points the resident scan looks through (``map_seen_through``) and, with ``box`` = (lo, hi), those outside
+        it, in one pass -- flimo_map_carve; afterwards the map is as after ``map_crop_box``.  Returns the number of points removed.
+        A ``Localizer`` first waits for an insert, a crop or a carve still running behind the last sweep."""
+        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
+        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
+        k = carve_cfg(**cfg)
+        lo = hi = None
+        if box is not None:
+            lo = np.ascontiguousarray(box[0], dtype=np.float32).reshape(3)
+            hi = np.ascontiguousarray(box[1], dtype=np.float32).reshape(3)
+        removed = C.c_size_t(0)
+        self._entry("flimo_map_carve", x.ctypes.data, s.ctypes.data, C.byref(k), _ptr(lo), _ptr(hi), C.byref(removed))
+        return int(removed.value)
+
+    def map_outliers(self, first=0, n=None, want=("mask", "mean_dist", "cnt"), **cfg):
+        """The stored points first .. first + n - 1 (``n`` None: up to the map's end) that belong to no surface, by the statistics
+        of their k nearest neighbours -- flimo_map_outliers; ``cfg``: the fields of ``outlier_cfg``.  Returns a dict: ``mask`` [n]
+        bool, ``mean_dist`` [n] float64, ``cnt`` [n] int32 (those named in ``want``) and ``stats``; changes nothing.  A ``Localizer``
+        first waits for an insert, a crop or a carve still running behind the last sweep; no policy of its own calls this."""
+        first, n = self._range(first, n)
+        out, k, st = _outputs("outliers", _OUTLIER_OUTPUTS, want, n), outlier_cfg(**cfg), OutlierStats()
+        self._entry("flimo_map_outliers", first, n, C.byref(k), *_ptrs(out, _OUTLIER_OUTPUTS), C.byref(st))
+        return _result(out, st)
+
+    def map_remove_outliers(self, first=0, n=None, **cfg):
+        """Forget the outliers of ``map_outliers`` -- flimo_map_remove_outliers; afterwards the map is as after ``map_crop_box``.
+        Returns (points removed, stats).  A ``Localizer`` first waits for an insert, a crop or a carve still running."""
+        return self._remove("flimo_map_remove_outliers", first, n, outlier_cfg(**cfg), OutlierStats())
+
+    def map_fpfh(self, first=0, n=None, want=("spfh", "cnt"), **cfg):
+        """FPFH descriptors (pcl::FPFHEstimation: 33 bins) of the stored points first .. first + n - 1 (``n`` None: up to the map's
+        end) -- flimo_map_fpfh; ``cfg``: the fields of ``fpfh_cfg`` (k, max_dist, normal_k, normal_max_dist, normal_min_pts,
+        viewpoint).  Returns a dict: ``fpfh`` [n, 33] float32, and of ``want`` ``spfh`` [n, 33] uint8, ``cnt`` [n] int32.  The
+        normals and the SPFH rows are formed for the whole map whatever the range; changes nothing.  A ``Localizer`` first waits
+        for an insert, a crop or a carve still running behind the last sweep; its own update does not use this."""
+        first, n = self._range(first, n)
+        out, k = _outputs("fpfh", _FPFH_OUTPUTS, want, n, always=("fpfh",)), fpfh_cfg(**cfg)
+        self._entry("flimo_map_fpfh", first, n, C.byref(k), *_ptrs(out, _FPFH_OUTPUTS))
+        return out
+
+    def map_keypoints(self, first=0, n=None, want=("saliency", "cnt"), **cfg):
+        """ISS keypoints (pcl::ISSKeypoint3D with k-bounded neighbourhoods and broken ties) among the stored points first .. first +
+        n - 1 (``n`` None: up to the map's end) -- flimo_map_keypoints; ``cfg``: the fields of ``keypoint_cfg`` (k, max_dist, min_pts,
+        gamma21, gamma32, nms_k, nms_max_dist).  Returns a dict: ``mask`` [n] bool, ``count``, ``index`` (the ascending int64 indices of
+        the ones, relative to ``first``), and of ``want`` ``saliency`` [n] float64 (NaN: not salient), ``cnt`` [n] int32.  The
+        saliency is formed for the whole map whatever the range; changes nothing.  A ``Localizer`` first waits for an insert, a
+        crop or a carve still running behind the last sweep; its own update does not use this."""
+        first, n = self._range(first, n)
+        out, k, count = _outputs("keypoints", _KEYPOINT_OUTPUTS, want, n, always=("mask",)), keypoint_cfg(**cfg), C.c_size_t(0)
+        self._entry("flimo_map_keypoints", first, n, C.byref(k), *_ptrs(out, _KEYPOINT_OUTPUTS), C.byref(count))
+        out = _result(out)
+        out["count"] = int(count.value)
+        out["index"] = np.flatnonzero(out["mask"]).astype(np.int64)
+        return out
+
+    def map_clusters(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
+        """Euclidean clusters (pcl::EuclideanClusterExtraction) of the stored points, for the points first .. first + n - 1 (``n``
+        None: up to the map's end) -- flimo_map_clusters; ``cfg``: the fields of ``cluster_cfg`` (tol, min_size, max_size).  Returns a
+        dict: of ``want`` ``label`` [n] int32 (the smallest insertion index of the point's component), ``size`` [n] int32, ``mask``
+        [n] bool (the component is selected), and ``stats``.  The components are the whole map's whatever the range; changes
+        nothing.  ``api.cluster_lists`` turns the labels into PCL's index lists.  A ``Localizer`` first waits for an insert, a crop
+        or a carve still running behind the last sweep; no policy of its own calls this."""
+        first, n = self._range(first, n)
+        out, k, st = _outputs("clusters", _COMPONENT_OUTPUTS, want, n), cluster_cfg(**cfg), ClusterStats()
+        self._entry("flimo_map_clusters", first, n, C.byref(k), *_ptrs(out, _COMPONENT_OUTPUTS), C.byref(st))
+        return _result(out, st)
+
+    def map_remove_clusters(self, first=0, n=None, **cfg):
+        """Forget the points of the range whose ``map_clusters`` mask is set -- flimo_map_remove_clusters; afterwards the map is as
+        after ``map_crop_box``.  Returns (points removed, stats).  A ``Localizer`` first waits for an insert, a crop or a carve
+        still running."""
+        return self._remove("flimo_map_remove_clusters", first, n, cluster_cfg(**cfg), ClusterStats())
+
+    def map_planes(self, tri, want=("plane",), **cfg):
+        """RANSAC plane hypotheses over the stored points -- flimo_map_planes.  ``tri`` [nh, 3] int32: the samples, three insertion
+        indices each (``api.corr_triplets(map_size, nh, seed)`` draws them); ``cfg``: the fields of ``plane_cfg`` (dist, min_edge,
+        min_sin, axis, min_cos).  Returns a dict: ``status`` [nh] (PLANE_OK / PLANE_DEGENERATE / PLANE_REJECTED), ``inliers`` [nh]
+        over ALL stored points, ``sum_sq`` [nh] float64 and, named in ``want``, ``plane`` [nh, 4] float64 (nx ny nz d; NaN unless
+        OK).  Changes nothing.  ``api.plane_consensus`` samples, calls and ranks.  A ``Localizer`` first waits for an insert, a
+        crop or a carve still running behind the last sweep; no policy of its own calls this."""
+        unknown = set(want) - {"plane"}
+        if unknown:
+            raise ValueError(f"map_planes: unknown outputs {sorted(unknown)}")
+        t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+        nh = t.shape[0]
+        k = plane_cfg(**cfg)
+        out = {"status": np.zeros(nh, np.int32), "inliers": np.zeros(nh, np.int32), "sum_sq": np.zeros(nh, np.float64)}
+        if "plane" in want:
+            out["plane"] = np.full((nh, 4), np.nan)
+        self._entry("flimo_map_planes", _ptr(t), nh, C.byref(k), _ptr(out["status"]), _ptr(out["inliers"]), _ptr(out["sum_sq"]),
+                    _ptr(out.get("plane")))
+        return out
+
+    def map_plane_mask(self, sel=None, first=0, n=None, want_mask=True, **kw):
+        """The stored points first .. first + n - 1 against one plane -- flimo_map_plane_mask.  ``sel``: a ``PlaneSel``, or its
+        fields as keywords (normal, anchor, dist, side).  Returns (mask [n] bool or None, count).  Changes nothing.  A
+        ``Localizer`` first waits for an insert, a crop or a carve still running behind the last sweep."""
+        first, n = self._range(first, n)
+        sel = _as_plane_sel(sel, kw)
+        mask = np.zeros(n, np.uint8) if want_mask else None
+        count = C.c_size_t(0)
+        self._entry("flimo_map_plane_mask", first, n, C.byref(sel), _ptr(mask), C.byref(count))
+        return (mask.astype(bool) if want_mask else None), int(count.value)
+
+    def map_remove_plane(self, sel=None, first=0, n=None, **kw):
+        """Forget the points of the range whose ``map_plane_mask`` is set -- flimo_map_remove_plane; afterwards the map is as after
+        ``map_crop_box``.  Returns the number of points removed.  A ``Localizer`` first waits for an insert, a crop or a carve
+        still running."""
+        first, n = self._range(first, n)
+        sel = _as_plane_sel(sel, kw)
+        removed = C.c_size_t(0)
+        self._entry("flimo_map_remove_plane", first, n, C.byref(sel), C.byref(removed))
+        return int(removed.value)
+
+    def map_voxels(self, want=("ijk", "count", "centroid"), **cfg):
+        """The voxels of the stored points on a lattice anchored at the world origin -- flimo_map_voxels.  ``cfg``: the fields of
+        ``voxel_cfg`` (leaf, keep, max_pts).  Returns a dict with the outputs named in ``want`` (of ``ijk`` [nv, 3] = (cx, cy, cz),
+        ``count``, ``first``, ``rep`` [nv], ``centroid`` [nv, 3] and ``cov`` [nv, 6] float64: xx xy xz yy yz zz), ``nv`` and
+        ``stats``; the voxels in ascending (cz, cy, cx).  Changes nothing.  A ``Localizer`` first waits for an insert, a crop or a
+        carve still running behind the last sweep; no policy of its own calls this."""
+        cap = self.map_size()      # (no more voxels than points: one call)
+        arr, k, nv, st = _outputs("map_voxels", VOXEL_OUTPUTS, want, cap), voxel_cfg(**cfg), C.c_size_t(0), VoxelStats()
+        self._entry("flimo_map_voxels", C.byref(k), cap, C.byref(nv), *_ptrs(arr, VOXEL_OUTPUTS), C.byref(st))
+        out = _result(arr, rows=nv.value)
+        out["nv"] = int(nv.value)
+        out["stats"] = st.as_dict()
+        return out
+
+    def map_voxel_mask(self, first=0, n=None, want=("voxel", "mask"), **cfg):
+        """The voxel and the thinning mask of the stored points first .. first + n - 1 -- flimo_map_voxel_mask: a dict with
+        ``voxel`` [n] (the position of the point's voxel in ``map_voxels``' listing, -1 outside the lattice), ``mask`` [n] bool
+        (True: ``map_thin`` would forget the point) and ``stats``.  Changes nothing.  A ``Localizer`` first waits for an insert, a
+        crop or a carve still running behind the last sweep."""
+        first, n = self._range(first, n)
+        out, k, st = _outputs("map_voxel_mask", _VOXEL_MASK_OUTPUTS, want, n), voxel_cfg(**cfg), VoxelStats()
+        self._entry("flimo_map_voxel_mask", first, n, C.byref(k), *_ptrs(out, _VOXEL_MASK_OUTPUTS), C.byref(st))
+        return _result(out, st)
+
+    def map_thin(self, first=0, n=None, **cfg):
+        """Forget the points of the range ``map_voxel_mask`` marks -- flimo_map_thin; afterwards the map is as after ``map_crop_box``.
+        Returns (removed, stats).  A ``Localizer`` first waits for an insert, a crop or a carve still running."""
+        return self._remove("flimo_map_thin", first, n, voxel_cfg(**cfg), VoxelStats())
+
+    def map_regions(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
+        """Smooth-surface regions (pcl::RegionGrowing without its seed order) of the stored points, for the points first ..
+        first + n - 1 (``n`` None: up to the map's end) -- flimo_map_regions; ``cfg``: the fields of ``region_cfg`` (tol, normal_k,
+        normal_max_dist, normal_min_pts, min_cos, max_curv, border, min_size, max_size).  Returns a dict: of ``want`` ``label`` [n]
+        int32 (the smallest insertion index of the region's smooth points; -1: no region), ``size`` [n] int32, ``mask`` [n] bool (the
+        region is selected), and ``stats``.  The regions are the whole map's whatever the range; changes nothing.  A ``Localizer``
+        first waits for an insert, a crop or a carve still running behind the last sweep; no policy of its own calls this."""
+        first, n = self._range(first, n)
+        out, k, st = _outputs("map_regions", _COMPONENT_OUTPUTS, want, n), region_cfg(**cfg), RegionStats()
+        self._entry("flimo_map_regions", first, n, C.byref(k), *_ptrs(out, _COMPONENT_OUTPUTS), C.byref(st))
+        return _result(out, st)
+
+    def map_region_list(self, want=("label", "count", "centroid", "cov"), **cfg):
+        """The selected regions of the stored points in ascending label -- flimo_map_region_list: a dict with the outputs named in
+        ``want`` (of ``label``, ``count``, ``first`` [nr], ``centroid`` [nr, 3] and ``cov`` [nr, 6] float64: xx xy xz yy yz zz, in
+        ``map_voxels``' summation shape), ``nr`` and ``stats``.  ``api.region_planes`` fits a plane to each.  Changes nothing.
+        Selected regions are few: one call with room for ``REGION_LIST_CAP`` of them, and a second with room for ``nr`` only where
+        the first answers FLIMO_ERR_TOO_LARGE.  A ``Localizer`` first waits for an insert, a crop or a carve still running."""
+        cap, nr, st = REGION_LIST_CAP, C.c_size_t(0), RegionStats()
+        while True:
+            arr, k = _outputs("map_region_list", REGION_OUTPUTS, want, cap), region_cfg(**cfg)
+            rc = self._code("flimo_map_region_list", C.byref(k), cap, C.byref(nr), *_ptrs(arr, REGION_OUTPUTS), C.byref(st))
+            if rc == 0:
+                break
+            if rc != -5 or nr.value <= cap:      # FLIMO_ERR_TOO_LARGE: *nr says how many there are
+                self._fail("flimo_map_region_list", rc)
+            cap = int(nr.value)
+        out = _result(arr, rows=nr.value)
+        out["nr"] = int(nr.value)
+        out["stats"] = st.as_dict()
+        return out
+
+    def map_remove_regions(self, first=0, n=None, **cfg):
+        """Forget the points of the range whose ``map_regions`` mask is set -- flimo_map_remove_regions; afterwards the map is as
+        after ``map_crop_box``.  Returns (points removed, stats).  A ``Localizer`` first waits for an insert, a crop or a carve
+        still running."""
+        return self._remove("flimo_map_remove_regions", first, n, region_cfg(**cfg), RegionStats())
+
+    # (HipCtx.knn_k, Localizer.map_knn)
+    def _knn_k(self, q, k, max_dist=float("inf"), want_xyz=False):
+        """flimo_knn_k (Octree::knn for any k up to 64, with a distance gate): per query the first ``k`` stored points in the order
+        (float32 squared-distance bits, insertion index) among those with squared distance < max_dist * max_dist (``inf``: no gate).
+        Returns (idx [nq, k], sqd [nq, k], cnt [nq][, xyz [nq, k, 3]]); idx = insertion indices (rows of ``map_points()``), slots
+        beyond cnt are idx -1, sqd 0, xyz 0.  A ``Localizer`` first waits for an insert, a crop or a carve still running behind the
+        last sweep; changes nothing."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        nq, kk = q.shape[0], max(int(k), 1)
+        idx = np.empty((nq, kk), np.int32)
+        sqd = np.empty((nq, kk), np.float32)
+        cnt = np.empty((nq,), np.int32)
+        xyz = np.empty((nq, kk, 3), np.float32) if want_xyz else None
+        self._entry("flimo_knn_k", q.ctypes.data if nq else None, nq, int(k), float(max_dist), _ptr(idx), _ptr(sqd), _ptr(xyz), _ptr(cnt))
+        return (idx, sqd, cnt, xyz) if want_xyz else (idx, sqd, cnt)
+
+    # (HipCtx.radius_search, Localizer.map_radius_search)
+    def _radius_search(self, q, radius, sorted=False, want_xyz=False):
+        """flimo_radius_search (Octree::radiusSearch for a batch): the stored points with squared float32 distance < radius * radius.
+        Returns (offsets [nq + 1], idx, sqd[, xyz]) in CSR form; idx = insertion indices (rows of ``map_points()``).  Unsorted: an
+        order that only a change of the map changes; ``sorted``: ascending by (distance bits, index).  A ``Localizer`` first waits
+        for an insert, a crop or a carve still running behind the last sweep; changes nothing."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        nq = q.shape[0]
+        off = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64(0)
+        # count, then size the arrays, then fill
+        self._entry("flimo_radius_search", q.ctypes.data, nq, float(radius), 0, off.ctypes.data, None, None, None, 0, C.byref(total))
+        n = int(total.value)
+        idx = np.empty(n, np.int32)
+        sqd = np.empty(n, np.float32)
+        xyz = np.empty((n, 3), np.float32) if want_xyz else None
+        if n > 0:
+            self._entry("flimo_radius_search", q.ctypes.data, nq, float(radius), RADIUS_SORTED if sorted else 0, off.ctypes.data,
+                        idx.ctypes.data, sqd.ctypes.data, xyz.ctypes.data if want_xyz else None, n, C.byref(total))
+        return (off, idx, sqd, xyz) if want_xyz else (off, idx, sqd)
+
+    def _normals_of(self, entry, head, nq, k, max_dist, min_pts, viewpoint, want):
+        out = _outputs("normals", _NORMAL_OUTPUTS, want, nq, always=("normal", "cnt"))
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float32).reshape(3)
+        self._entry(entry, *head, int(k), float(max_dist), int(min_pts), _ptr(vp), *_ptrs(out, _NORMAL_OUTPUTS))
+        return out
+
+    # (HipCtx.normals, Localizer.map_normals)
+    def _normals(self, q, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
+        """flimo_map_normals: plane normal and curvature of the neighbourhood ``knn_k(q, k, max_dist)`` of every query, computed on
+        the GPU in float64 (mean and covariance of p - q, divided by n; Jacobi eigen-decomposition).  Returns a dict: ``normal``
+        [nq, 4] float32 (nx ny nz curvature), ``cnt`` [nq], and of ``want`` ``centroid`` [nq, 3], ``cov`` [nq, 6] (xx xy xz yy yz zz),
+        ``eig`` [nq, 6] (l0 <= l1 <= l2, the float64 normal).  ``viewpoint``: the normals face it; None: the component of largest
+        magnitude is positive.  Fewer than max(3, min_pts) neighbours: NaN.  A ``Localizer`` first waits for an insert, a crop or a
+        carve still running behind the last sweep; changes nothing."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        return self._normals_of("flimo_map_normals", (q.ctypes.data if q.shape[0] else None, q.shape[0]), q.shape[0], k, max_dist, min_pts,
+                                viewpoint, want)
+
+    # (HipCtx.normals_range, Localizer.map_normals_range)
+    def _normals_range(self, first, n, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
+        """flimo_map_normals_range: ``normals`` of the stored points first .. first + n - 1 themselves (rows of ``map_points()``);
+        nothing is uploaded, the bits are those of ``normals(map_points()[first:first + n], ...)``.  A ``Localizer`` first waits
+        for an insert, a crop or a carve still running behind the last sweep."""
+        return self._normals_of("flimo_map_normals_range", (int(first), int(n)), int(n), k, max_dist, min_pts, viewpoint, want)
+
+    def scan_fitness(self, x26s, max_dist=float("inf"), want_nn=False):
+        """flimo_scan_fitness: how well the resident scan fits the map at each pose of ``x26s`` [np, 26] (only pos and rot are read).
+        Per pose the nearest stored point of every scan point moved by it (``scan_to_world`` + ``knn_k(k=1, max_dist)``, on the GPU):
+        returns (inliers [np] int32: points that have one within the gate, sum_sqd [np] float64: the sum of their squared distances
+        [, nn_sqd [np, n] float32: the distance or -1, nn_idx [np, n]: the stored point's insertion index or -1]).  A ``Localizer``
+        first waits for an insert, a crop or a carve still running behind the last sweep; its resident scan is that sweep's
+        (``pc2match()``)."""
+        x = _poses(x26s)
+        m, n = x.shape[0], self._scan_size()
+        inliers = np.zeros(m, np.int32)
+        sum_sqd = np.zeros(m, np.float64)
+        nn_sqd = np.full((m, n), -1, np.float32) if want_nn else None
+        nn_idx = np.full((m, n), -1, np.int32) if want_nn else None
+        self._entry("flimo_scan_fitness", x.ctypes.data if m else None, m, float(max_dist), _ptr(inliers), _ptr(sum_sqd), _ptr(nn_sqd),
+                    _ptr(nn_idx))
+        return (inliers, sum_sqd, nn_sqd, nn_idx) if want_nn else (inliers, sum_sqd)
+
+    def scan_linearize(self, x26s, k, max_dist, min_pts=3, max_curv=float("inf"), want_rows=False):
+        """flimo_scan_linearize: the point-to-plane normal equations of the resident scan against the map at each pose of ``x26s``
+        [np, 26] (only pos and rot are read).  Per pose and scan point the plane of ``normals(scan_to_world(x26), k, max_dist,
+        min_pts)``, gated by ``max_curv``; returns a dict: valid [np] int32, H [np, 21] (upper triangle, row-major), g [np, 6],
+        cost [np][, rows [np, n, 7]: J0..J5, d per pair, NaN when invalid; pair_cnt [np, n]].  The step solves H xi = -g
+        (``api.scan_align`` iterates it).  A ``Localizer`` first waits for an insert, a crop or a carve still running behind the
+        last sweep; its resident scan is that sweep's (``pc2match()``)."""
+        x = _poses(x26s)
+        m, n = x.shape[0], self._scan_size()
+        out = {"valid": np.zeros(m, np.int32), "H": np.zeros((m, 21)), "g": np.zeros((m, 6)), "cost": np.zeros(m)}
+        if want_rows:
+            out["rows"] = np.full((m, n, 7), np.nan)
+            out["pair_cnt"] = np.zeros((m, n), np.int32)
+        self._entry("flimo_scan_linearize", x.ctypes.data if m else None, m, int(k), float(max_dist), int(min_pts), float(max_curv),
+                    *(_ptr(out.get(name)) for name in ("valid", "H", "g", "cost", "rows", "pair_cnt")))
+        return out
+
+    def corr_poses(self, src, dst, tri, want=("pose",), **cfg):
+        """flimo_corr_poses: pose hypotheses from point correspondences.  ``src`` [m, 3] (body frame) and ``dst`` [m, 3] (map frame)
+        are the putative pairs, ``tri`` [nh, 3] the caller's samples of three of them (``api.corr_triplets``); ``cfg``: the fields
+        of ``corr_cfg``.  Per sample the polygon pre-rejection, the closed-form pose and the pairs it brings within ``max_dist``.
+        Returns a dict: status [nh] (CORR_OK / CORR_DEGENERATE / CORR_REJECTED), inliers [nh] int32, sum_sqd [nh] float64[, pose
+        [nh, 7]: t, then the quaternion x y z w -- the first seven entries of an x26 row; NaN unless OK][, pair_sqd [nh, m] float32:
+        the squared distance of an inlier pair, -1 otherwise].  Reads neither the map nor the resident scan.  A ``Localizer`` runs
+        it on the map's context and first waits for an insert, a crop or a carve still running behind the last sweep."""
+        unknown = set(want) - {"pose", "pair_sqd"}
+        if unknown:
+            raise ValueError(f"corr_poses: unknown outputs {sorted(unknown)}")
+        s, d = _pairs("corr_poses", src, dst)
+        t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+        m, nh = s.shape[0], t.shape[0]
+        k = corr_cfg(**cfg)
+        out = {"status": np.zeros(nh, np.int32), "inliers": np.zeros(nh, np.int32), "sum_sqd": np.zeros(nh, np.float64)}
+        if "pose" in want:
+            out["pose"] = np.full((nh, 7), np.nan)
+        if "pair_sqd" in want:
+            out["pair_sqd"] = np.full((nh, m), -1, np.float32)
+        self._entry("flimo_corr_poses", _ptr(s), _ptr(d), m, _ptr(t), nh, C.byref(k),
+                    *(_ptr(out.get(name)) for name in ("status", "inliers", "sum_sqd", "pose", "pair_sqd")))
+        return out
+
+    def corr_graph(self, src, dst, want=(), **cfg):
+        """flimo_corr_graph: which of the putative pairs ``src`` [m, 3] / ``dst`` [m, 3] can be true together.  Pairs i and j are
+        joined when the edge between them is as long in ``src`` as in ``dst`` to within ``tol`` (``cfg``: the fields of
+        ``corr_graph_cfg``).  Returns a dict: degree [m] int32, core [m] int32 (the core numbers of that graph), max_core[, adj
+        [m, (m + 63) // 64] uint64 when "adj" is in ``want``: bit j & 63 of word j >> 6 of row i].  m at most CORR_GRAPH_MAX_M.
+        Reads neither the map nor the resident scan.  A ``Localizer`` runs it on the map's context and first waits for an insert,
+        a crop or a carve still running behind the last sweep."""
+        unknown = set(want) - {"adj"}
+        if unknown:
+            raise ValueError(f"corr_graph: unknown outputs {sorted(unknown)}")
+        s, d = _pairs("corr_graph", src, dst)
+        m = s.shape[0]
+        k = corr_graph_cfg(**cfg)
+        out = {"degree": np.zeros(m, np.int32), "core": np.zeros(m, np.int32)}
+        if "adj" in want:
+            out["adj"] = np.zeros((m, (m + 63) // 64), np.uint64)
+        top = C.c_int32(0)
+        self._entry("flimo_corr_graph", _ptr(s), _ptr(d), m, C.byref(k), _ptr(out["degree"]), _ptr(out["core"]), C.byref(top),
+                    _ptr(out.get("adj")))
+        out["max_core"] = int(top.value)
+        return out
+
+    def desc_ref_set(self, desc):
+        """flimo_desc_ref_set: ``desc`` [nr, dim] float32 becomes the context's resident reference set of ``desc_match`` (the map's
+        descriptors: set once, matched against many times); it replaces the previous one, no rows clear it.  A ``Localizer`` keeps
+        it on the map's context and first waits for an insert, a crop or a carve still running behind the last sweep."""
+        d = desc_rows(desc)
+        self._entry("flimo_desc_ref_set", d.ctypes.data if d.size else None, d.shape[0], d.shape[1] if d.shape[0] else 0)
+
+    def desc_match(self, q, k=2):
+        """flimo_desc_match: per row of ``q`` [nq, dim] the first ``k`` rows of the resident reference set by (bits of the float32
+        squared distance, index) -- the distance is include/flimo_c.h's fmaf chain, exact and reproducible.  Returns a dict: idx
+        [nq, k] int32 (-1 beyond cnt), dist [nq, k] float32 (0 beyond cnt), cnt [nq].  Rows with a non-finite entry never match.  A
+        ``Localizer`` first waits for an insert, a crop or a carve still running behind the last sweep."""
+        q = desc_rows(q)
+        nq, kk = q.shape[0], max(int(k), 1)
+        out = {"idx": np.full((nq, kk), -1, np.int32), "dist": np.zeros((nq, kk), np.float32), "cnt": np.zeros(nq, np.int32)}
+        self._entry("flimo_desc_match", _ptr(q), nq, q.shape[1], int(k), _ptr(out["idx"]), _ptr(out["dist"]), _ptr(out["cnt"]))
+        return out
+
+
+class HipCtx(_SharedEntries):
     """Thin OO wrapper over one ``flimo_ctx`` (one GPU, one map, one stream)."""
+    knn_k, radius_search = _SharedEntries._knn_k, _SharedEntries._radius_search
+    normals, normals_range = _SharedEntries._normals, _SharedEntries._normals_range
 
     def __init__(self, device: int = 0):
         L = load_hip()
@@ -791,10 +635,14 @@ class HipCtx:
         if rc != 0:
             raise FlimoError(f"{_ERRS.get(rc, rc)}: {self._L.flimo_last_error(self._h).decode()}")
 
-    def _range(self, first, n):
-        """(first, n) of a range entry; ``n`` None: up to the map's end."""
-        first = int(first)
-        return first, max(self.map_size() - first, 0) if n is None else int(n)
+    def _symbol(self, entry):
+        return entry
+
+    def _fail(self, entry, rc):
+        self._chk(rc)
+
+    def _scan_size(self):
+        return self.scan_size()
 
     # ---- map ----
     def map_config(self, min_extent=0.2, bucket_size=2, downsample=True, cell_size=0.0):
@@ -824,190 +672,35 @@ class HipCtx:
         self._chk(self._L.flimo_map_crop_stats(self._h, o))
         return dict(crops=int(o[0]), points_removed=int(o[1]))
 
-    def map_seen_through(self, x26, sensor, want_mask=True, **cfg):
-        """The stored points that the resident scan, moved to the world frame by ``x26``, looks through from ``sensor`` (world
-        frame) -- flimo_map_seen_through; ``cfg``: the fields of ``carve_cfg``.  Returns (mask [map size] bool in insertion order,
-        count); changes nothing."""
-        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
-        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
-        k = carve_cfg(**cfg)
-        n = self.map_size()
-        mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
-        count = C.c_size_t(0)
-        self._chk(self._L.flimo_map_seen_through(self._h, x.ctypes.data, s.ctypes.data, C.byref(k), mask.ctypes.data if want_mask else None, n,
-                                                 C.byref(count)))
-        return (mask[:n].astype(bool) if want_mask else None), int(count.value)
-
-    def map_carve(self, x26, sensor, box=None, **cfg) -> int:
-        """Forget the stored points the resident scan looks through (``map_seen_through``) and, with ``box`` = (lo, hi), those outside
-        it, in one pass -- flimo_map_carve; afterwards the map is as after ``map_crop_box``.  Returns the number of points removed."""
-        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
-        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
-        k = carve_cfg(**cfg)
-        lo = hi = None
-        if box is not None:
-            lo = np.ascontiguousarray(box[0], dtype=np.float32).reshape(3)
-            hi = np.ascontiguousarray(box[1], dtype=np.float32).reshape(3)
-        removed = C.c_size_t(0)
-        self._chk(self._L.flimo_map_carve(self._h, x.ctypes.data, s.ctypes.data, C.byref(k), None if lo is None else lo.ctypes.data,
-                                          None if hi is None else hi.ctypes.data, C.byref(removed)))
-        return int(removed.value)
-
     def map_carve_stats(self):
         o = (C.c_uint64 * 2)()
         self._chk(self._L.flimo_map_carve_stats(self._h, o))
         return dict(carves=int(o[0]), points_removed=int(o[1]))
 
-    def map_outliers(self, first=0, n=None, want=("mask", "mean_dist", "cnt"), **cfg):
-        """The stored points first .. first + n - 1 (``n`` None: up to the map's end) that belong to no surface, by the statistics
-        of their k nearest neighbours -- flimo_map_outliers; ``cfg``: the fields of ``outlier_cfg``.  Returns a dict: ``mask`` [n]
-        bool, ``mean_dist`` [n] float64, ``cnt`` [n] int32 (those named in ``want``) and ``stats``; changes nothing."""
-        first, n = self._range(first, n)
-        return outliers_call(lambda *a: self._chk(self._L.flimo_map_outliers(self._h, first, n, *a)), n, want, cfg)
-
-    def map_remove_outliers(self, first=0, n=None, **cfg):
-        """Forget the outliers of ``map_outliers`` -- flimo_map_remove_outliers; afterwards the map is as after ``map_crop_box``.
-        Returns (points removed, stats)."""
-        first, n = self._range(first, n)
-        k = outlier_cfg(**cfg)
-        removed = C.c_size_t(0)
-        st = OutlierStats()
-        self._chk(self._L.flimo_map_remove_outliers(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)))
-        return int(removed.value), st.as_dict()
-
     def set_outlier_chunk(self, n):
         """Points per search launch of ``map_outliers`` / ``map_remove_outliers`` (flimo_set_outlier_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_outlier_chunk(self._h, int(n)))
-
-    def map_fpfh(self, first=0, n=None, want=("spfh", "cnt"), **cfg):
-        """FPFH descriptors (pcl::FPFHEstimation: 33 bins) of the stored points first .. first + n - 1 (``n`` None: up to the map's
-        end) -- flimo_map_fpfh; ``cfg``: the fields of ``fpfh_cfg`` (k, max_dist, normal_k, normal_max_dist, normal_min_pts,
-        viewpoint).  Returns a dict: ``fpfh`` [n, 33] float32, and of ``want`` ``spfh`` [n, 33] uint8, ``cnt`` [n] int32.  The
-        normals and the SPFH rows are formed for the whole map whatever the range; changes nothing."""
-        first, n = self._range(first, n)
-        return fpfh_call(lambda *a: self._chk(self._L.flimo_map_fpfh(self._h, first, n, *a)), n, want, cfg)
 
     def set_fpfh_chunk(self, n):
         """Points per search launch of ``map_fpfh`` (flimo_set_fpfh_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_fpfh_chunk(self._h, int(n)))
 
-    def map_keypoints(self, first=0, n=None, want=("saliency", "cnt"), **cfg):
-        """ISS keypoints (pcl::ISSKeypoint3D with k-bounded neighbourhoods and broken ties) among the stored points first .. first +
-        n - 1 (``n`` None: up to the map's end) -- flimo_map_keypoints; ``cfg``: the fields of ``keypoint_cfg`` (k, max_dist, min_pts,
-        gamma21, gamma32, nms_k, nms_max_dist).  Returns a dict: ``mask`` [n] bool, ``count``, ``index`` (the ascending int64 indices of
-        the ones, relative to ``first``), and of ``want`` ``saliency`` [n] float64 (NaN: not salient), ``cnt`` [n] int32.  The
-        saliency is formed for the whole map whatever the range; changes nothing."""
-        first, n = self._range(first, n)
-        return keypoints_call(lambda *a: self._chk(self._L.flimo_map_keypoints(self._h, first, n, *a)), n, want, cfg)
-
     def set_keypoints_chunk(self, n):
         """Points per search launch of ``map_keypoints`` (flimo_set_keypoints_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_keypoints_chunk(self._h, int(n)))
-
-    def map_clusters(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
-        """Euclidean clusters (pcl::EuclideanClusterExtraction) of the stored points, for the points first .. first + n - 1 (``n``
-        None: up to the map's end) -- flimo_map_clusters; ``cfg``: the fields of ``cluster_cfg`` (tol, min_size, max_size).  Returns a
-        dict: of ``want`` ``label`` [n] int32 (the smallest insertion index of the point's component), ``size`` [n] int32, ``mask``
-        [n] bool (the component is selected), and ``stats``.  The components are the whole map's whatever the range; changes
-        nothing.  ``api.cluster_lists`` turns the labels into PCL's index lists."""
-        first, n = self._range(first, n)
-        return clusters_call(lambda *a: self._chk(self._L.flimo_map_clusters(self._h, first, n, *a)), n, want, cfg)
-
-    def map_remove_clusters(self, first=0, n=None, **cfg):
-        """Forget the points of the range whose ``map_clusters`` mask is set -- flimo_map_remove_clusters; afterwards the map is as
-        after ``map_crop_box``.  Returns (points removed, stats)."""
-        first, n = self._range(first, n)
-        k = cluster_cfg(**cfg)
-        removed = C.c_size_t(0)
-        st = ClusterStats()
-        self._chk(self._L.flimo_map_remove_clusters(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)))
-        return int(removed.value), st.as_dict()
 
     def set_cluster_chunk(self, n):
         """Points per link launch of ``map_clusters`` / ``map_remove_clusters`` (flimo_set_cluster_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_cluster_chunk(self._h, int(n)))
 
-    def map_planes(self, tri, want=("plane",), **cfg):
-        """RANSAC plane hypotheses over the stored points -- flimo_map_planes.  ``tri`` [nh, 3] int32: the samples, three insertion
-        indices each (``api.corr_triplets(map_size, nh, seed)`` draws them); ``cfg``: the fields of ``plane_cfg`` (dist, min_edge,
-        min_sin, axis, min_cos).  Returns a dict: ``status`` [nh] (PLANE_OK / PLANE_DEGENERATE / PLANE_REJECTED), ``inliers`` [nh]
-        over ALL stored points, ``sum_sq`` [nh] float64 and, named in ``want``, ``plane`` [nh, 4] float64 (nx ny nz d; NaN unless
-        OK).  Changes nothing.  ``api.plane_consensus`` samples, calls and ranks."""
-        return planes_call(lambda *a: self._chk(self._L.flimo_map_planes(self._h, *a)), tri, want, cfg)
-
-    def map_plane_mask(self, sel=None, first=0, n=None, want_mask=True, **kw):
-        """The stored points first .. first + n - 1 against one plane -- flimo_map_plane_mask.  ``sel``: a ``PlaneSel``, or its
-        fields as keywords (normal, anchor, dist, side).  Returns (mask [n] bool or None, count).  Changes nothing."""
-        first, n = self._range(first, n)
-        sel = _as_plane_sel(sel, kw)
-        return plane_mask_call(lambda *a: self._chk(self._L.flimo_map_plane_mask(self._h, first, n, *a)), n, sel, want_mask)
-
-    def map_remove_plane(self, sel=None, first=0, n=None, **kw):
-        """Forget the points of the range whose ``map_plane_mask`` is set -- flimo_map_remove_plane; afterwards the map is as after
-        ``map_crop_box``.  Returns the number of points removed."""
-        first, n = self._range(first, n)
-        sel = _as_plane_sel(sel, kw)
-        removed = C.c_size_t(0)
-        self._chk(self._L.flimo_map_remove_plane(self._h, first, n, C.byref(sel), C.byref(removed)))
-        return int(removed.value)
-
     def set_plane_chunk(self, n):
         """Hypotheses per chunk of ``map_planes`` (flimo_set_plane_chunk; 0: the default of 2^10)."""
         self._chk(self._L.flimo_set_plane_chunk(self._h, int(n)))
-
-    def map_voxels(self, want=("ijk", "count", "centroid"), **cfg):
-        """The voxels of the stored points on a lattice anchored at the world origin -- flimo_map_voxels.  ``cfg``: the fields of
-        ``voxel_cfg`` (leaf, keep, max_pts).  Returns a dict with the outputs named in ``want`` (of ``ijk`` [nv, 3] = (cx, cy, cz),
-        ``count``, ``first``, ``rep`` [nv], ``centroid`` [nv, 3] and ``cov`` [nv, 6] float64: xx xy xz yy yz zz), ``nv`` and
-        ``stats``; the voxels in ascending (cz, cy, cx).  Changes nothing."""
-        return voxels_call(lambda *a: self._chk(self._L.flimo_map_voxels(self._h, *a)), self.map_size(), want, cfg)
-
-    def map_voxel_mask(self, first=0, n=None, want=("voxel", "mask"), **cfg):
-        """The voxel and the thinning mask of the stored points first .. first + n - 1 -- flimo_map_voxel_mask: a dict with
-        ``voxel`` [n] (the position of the point's voxel in ``map_voxels``' listing, -1 outside the lattice), ``mask`` [n] bool
-        (True: ``map_thin`` would forget the point) and ``stats``.  Changes nothing."""
-        first, n = self._range(first, n)
-        return voxel_mask_call(lambda *a: self._chk(self._L.flimo_map_voxel_mask(self._h, first, n, *a)), n, want, cfg)
-
-    def map_thin(self, first=0, n=None, **cfg):
-        """Forget the points of the range ``map_voxel_mask`` marks -- flimo_map_thin; afterwards the map is as after ``map_crop_box``.
-        Returns (removed, stats)."""
-        first, n = self._range(first, n)
-        k = voxel_cfg(**cfg)
-        removed = C.c_size_t(0)
-        st = VoxelStats()
-        self._chk(self._L.flimo_map_thin(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)))
-        return int(removed.value), st.as_dict()
 
     def set_voxel_plan(self, plan):
         """The lane plan of ``map_voxels``' moments (flimo_set_voxel_plan; 0: by the voxel's count, 1..3: groups of 8, 16, 64 lanes,
         4: the many-runs path, + 8: the points written in sorted order first)."""
         self._chk(self._L.flimo_set_voxel_plan(self._h, int(plan)))
-
-    def map_regions(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
-        """Smooth-surface regions (pcl::RegionGrowing without its seed order) of the stored points, for the points first ..
-        first + n - 1 (``n`` None: up to the map's end) -- flimo_map_regions; ``cfg``: the fields of ``region_cfg`` (tol, normal_k,
-        normal_max_dist, normal_min_pts, min_cos, max_curv, border, min_size, max_size).  Returns a dict: of ``want`` ``label`` [n]
-        int32 (the smallest insertion index of the region's smooth points; -1: no region), ``size`` [n] int32, ``mask`` [n] bool (the
-        region is selected), and ``stats``.  The regions are the whole map's whatever the range; changes nothing."""
-        first, n = self._range(first, n)
-        return regions_call(lambda *a: self._chk(self._L.flimo_map_regions(self._h, first, n, *a)), n, want, cfg)
-
-    def map_region_list(self, want=("label", "count", "centroid", "cov"), **cfg):
-        """The selected regions of the stored points in ascending label -- flimo_map_region_list: a dict with the outputs named in
-        ``want`` (of ``label``, ``count``, ``first`` [nr], ``centroid`` [nr, 3] and ``cov`` [nr, 6] float64: xx xy xz yy yz zz, in
-        ``map_voxels``' summation shape), ``nr`` and ``stats``.  ``api.region_planes`` fits a plane to each.  Changes nothing."""
-        return region_list_call(lambda *a: self._L.flimo_map_region_list(self._h, *a), self._chk, want, cfg)
-
-    def map_remove_regions(self, first=0, n=None, **cfg):
-        """Forget the points of the range whose ``map_regions`` mask is set -- flimo_map_remove_regions; afterwards the map is as
-        after ``map_crop_box``.  Returns (points removed, stats)."""
-        first, n = self._range(first, n)
-        k = region_cfg(**cfg)
-        removed = C.c_size_t(0)
-        st = RegionStats()
-        self._chk(self._L.flimo_map_remove_regions(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)))
-        return int(removed.value), st.as_dict()
 
     def set_region_chunk(self, n):
         """Points per link launch of ``map_regions`` / ``map_region_list`` / ``map_remove_regions`` (flimo_set_region_chunk; 0: the
@@ -1033,39 +726,6 @@ class HipCtx:
         self._chk(self._L.flimo_knn(self._h, q.reshape(-1), nq, k, idx.reshape(-1), sqd.reshape(-1), cnt))
         return idx, sqd, cnt
 
-    def knn_k(self, q, k, max_dist=float("inf"), want_xyz=False):
-        """flimo_knn_k (Octree::knn for any k up to 64, with a distance gate): per query the first ``k`` stored points in the order
-        (float32 squared-distance bits, insertion index) among those with squared distance < max_dist * max_dist (``inf``: no gate).
-        Returns (idx [nq, k], sqd [nq, k], cnt [nq][, xyz [nq, k, 3]]); idx = insertion indices (rows of ``map_points()``), slots
-        beyond cnt are idx -1, sqd 0, xyz 0."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
-        nq, kk = q.shape[0], max(int(k), 1)
-        idx = np.empty((nq, kk), np.int32)
-        sqd = np.empty((nq, kk), np.float32)
-        cnt = np.empty((nq,), np.int32)
-        xyz = np.empty((nq, kk, 3), np.float32) if want_xyz else None
-        # (an array of no element may have no address; the call wants its pointers non-null)
-        ptr = lambda a: a.ctypes.data if a.size else C.addressof(C.c_double())
-        self._chk(self._L.flimo_knn_k(self._h, q.ctypes.data if nq else None, nq, int(k), float(max_dist), ptr(idx), ptr(sqd),
-                                      ptr(xyz) if want_xyz else None, ptr(cnt)))
-        return (idx, sqd, cnt, xyz) if want_xyz else (idx, sqd, cnt)
-
-    def normals(self, q, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
-        """flimo_map_normals: plane normal and curvature of the neighbourhood ``knn_k(q, k, max_dist)`` of every query, computed on
-        the GPU in float64 (mean and covariance of p - q, divided by n; Jacobi eigen-decomposition).  Returns a dict: ``normal``
-        [nq, 4] float32 (nx ny nz curvature), ``cnt`` [nq], and of ``want`` ``centroid`` [nq, 3], ``cov`` [nq, 6] (xx xy xz yy yz zz),
-        ``eig`` [nq, 6] (l0 <= l1 <= l2, the float64 normal).  ``viewpoint``: the normals face it; None: the component of largest
-        magnitude is positive.  Fewer than max(3, min_pts) neighbours: NaN."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
-        return normals_call(lambda *a: self._chk(self._L.flimo_map_normals(self._h, q.ctypes.data if q.shape[0] else None, q.shape[0], *a)),
-                            q.shape[0], k, max_dist, min_pts, viewpoint, want)
-
-    def normals_range(self, first, n, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
-        """flimo_map_normals_range: ``normals`` of the stored points first .. first + n - 1 themselves (rows of ``map_points()``);
-        nothing is uploaded, the bits are those of ``normals(map_points()[first:first + n], ...)``."""
-        return normals_call(lambda *a: self._chk(self._L.flimo_map_normals_range(self._h, int(first), int(n), *a)),
-                            int(n), k, max_dist, min_pts, viewpoint, want)
-
     def set_normals_chunk(self, n):
         """Queries per launch of ``normals`` / ``normals_range`` (flimo_set_normals_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_normals_chunk(self._h, int(n)))
@@ -1081,7 +741,7 @@ class HipCtx:
         """Results per query of ``radius_search`` (count only: nothing but the offsets comes back)."""
         q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
         off = np.zeros(q.shape[0] + 1, np.uint64)
-        self._chk(self._L.flimo_radius_search(self._h, q.reshape(-1), q.shape[0], float(radius), 0, off.ctypes.data, None, None, None, 0, None))
+        self._chk(self._L.flimo_radius_search(self._h, q.ctypes.data, q.shape[0], float(radius), 0, off.ctypes.data, None, None, None, 0, None))
         return np.diff(off).astype(np.int64)
 
     def radius_candidates(self, q, radius):
@@ -1090,25 +750,6 @@ class HipCtx:
         cand = np.zeros(q.shape[0], np.uint64)
         self._chk(self._L.flimo_radius_candidates(self._h, q.reshape(-1), q.shape[0], float(radius), cand.ctypes.data))
         return cand
-
-    def radius_search(self, q, radius, sorted=False, want_xyz=False):
-        """flimo_radius_search (Octree::radiusSearch for a batch): the stored points with squared float32 distance < radius * radius.
-        Returns (offsets [nq + 1], idx, sqd[, xyz]) in CSR form; idx = insertion indices (rows of ``map_points()``).  Unsorted: an
-        order that only a change of the map changes; ``sorted``: ascending by (distance bits, index)."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
-        nq = q.shape[0]
-        off = np.zeros(nq + 1, np.uint64)
-        total = C.c_uint64(0)
-        # count, then size the arrays, then fill
-        self._chk(self._L.flimo_radius_search(self._h, q.reshape(-1), nq, float(radius), 0, off.ctypes.data, None, None, None, 0, C.byref(total)))
-        n = int(total.value)
-        idx = np.empty(n, np.int32)
-        sqd = np.empty(n, np.float32)
-        xyz = np.empty((n, 3), np.float32) if want_xyz else None
-        if n > 0:
-            self._chk(self._L.flimo_radius_search(self._h, q.reshape(-1), nq, float(radius), RADIUS_SORTED if sorted else 0, off.ctypes.data,
-                                                  idx.ctypes.data, sqd.ctypes.data, xyz.ctypes.data if want_xyz else None, n, C.byref(total)))
-        return (off, idx, sqd, xyz) if want_xyz else (off, idx, sqd)
 
     # ---- scan ----
     def scan_set(self, xyz):
@@ -1127,68 +768,23 @@ class HipCtx:
         self._chk(self._L.flimo_scan_get(self._h, out.ctypes.data, n, C.byref(m)))
         return out[:n]
 
-    def scan_fitness(self, x26s, max_dist=float("inf"), want_nn=False):
-        """flimo_scan_fitness: how well the resident scan fits the map at each pose of ``x26s`` [np, 26] (only pos and rot are read).
-        Per pose the nearest stored point of every scan point moved by it (``scan_to_world`` + ``knn_k(k=1, max_dist)``, on the GPU):
-        returns (inliers [np] int32: points that have one within the gate, sum_sqd [np] float64: the sum of their squared distances
-        [, nn_sqd [np, n] float32: the distance or -1, nn_idx [np, n]: the stored point's insertion index or -1])."""
-        return fitness_call(lambda *a: self._chk(self._L.flimo_scan_fitness(self._h, *a)), x26s, self.scan_size(), max_dist, want_nn)
-
     def set_fitness_chunk(self, pairs):
         """(pose, point) pairs per chunk of ``scan_fitness`` (flimo_set_fitness_chunk; 0: the default of 2^22)."""
         self._chk(self._L.flimo_set_fitness_chunk(self._h, int(pairs)))
-
-    def scan_linearize(self, x26s, k, max_dist, min_pts=3, max_curv=float("inf"), want_rows=False):
-        """flimo_scan_linearize: the point-to-plane normal equations of the resident scan against the map at each pose of ``x26s``
-        [np, 26] (only pos and rot are read).  Per pose and scan point the plane of ``normals(scan_to_world(x26), k, max_dist,
-        min_pts)``, gated by ``max_curv``; returns a dict: valid [np] int32, H [np, 21] (upper triangle, row-major), g [np, 6],
-        cost [np][, rows [np, n, 7]: J0..J5, d per pair, NaN when invalid; pair_cnt [np, n]].  The step solves H xi = -g
-        (``api.scan_align`` iterates it)."""
-        return linearize_call(lambda *a: self._chk(self._L.flimo_scan_linearize(self._h, *a)), x26s, self.scan_size(), k, max_dist, min_pts,
-                              max_curv, want_rows)
 
     def set_linearize_chunk(self, pairs):
         """(pose, point) pairs per chunk of ``scan_linearize`` (flimo_set_linearize_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_linearize_chunk(self._h, int(pairs)))
 
-    def corr_poses(self, src, dst, tri, want=("pose",), **cfg):
-        """flimo_corr_poses: pose hypotheses from point correspondences.  ``src`` [m, 3] (body frame) and ``dst`` [m, 3] (map frame)
-        are the putative pairs, ``tri`` [nh, 3] the caller's samples of three of them (``api.corr_triplets``); ``cfg``: the fields
-        of ``corr_cfg``.  Per sample the polygon pre-rejection, the closed-form pose and the pairs it brings within ``max_dist``.
-        Returns a dict: status [nh] (CORR_OK / CORR_DEGENERATE / CORR_REJECTED), inliers [nh] int32, sum_sqd [nh] float64[, pose
-        [nh, 7]: t, then the quaternion x y z w -- the first seven entries of an x26 row; NaN unless OK][, pair_sqd [nh, m] float32:
-        the squared distance of an inlier pair, -1 otherwise].  Reads neither the map nor the resident scan."""
-        return corr_call(lambda *a: self._chk(self._L.flimo_corr_poses(self._h, *a)), src, dst, tri, want, cfg)
-
     def set_corr_chunk(self, n):
         """Hypotheses per chunk of ``corr_poses`` (flimo_set_corr_chunk; 0: the default of 2^16)."""
         self._chk(self._L.flimo_set_corr_chunk(self._h, int(n)))
-
-    def corr_graph(self, src, dst, want=(), **cfg):
-        """flimo_corr_graph: which of the putative pairs ``src`` [m, 3] / ``dst`` [m, 3] can be true together.  Pairs i and j are
-        joined when the edge between them is as long in ``src`` as in ``dst`` to within ``tol`` (``cfg``: the fields of
-        ``corr_graph_cfg``).  Returns a dict: degree [m] int32, core [m] int32 (the core numbers of that graph), max_core[, adj
-        [m, (m + 63) // 64] uint64 when "adj" is in ``want``: bit j & 63 of word j >> 6 of row i].  m at most CORR_GRAPH_MAX_M.
-        Reads neither the map nor the resident scan."""
-        return corr_graph_call(lambda *a: self._chk(self._L.flimo_corr_graph(self._h, *a)), src, dst, want, cfg)
-
-    def desc_ref_set(self, desc):
-        """flimo_desc_ref_set: ``desc`` [nr, dim] float32 becomes the context's resident reference set of ``desc_match`` (the map's
-        descriptors: set once, matched against many times); it replaces the previous one, no rows clear it."""
-        d = desc_rows(desc)
-        self._chk(self._L.flimo_desc_ref_set(self._h, d.ctypes.data if d.size else None, d.shape[0], d.shape[1] if d.shape[0] else 0))
 
     def desc_ref_size(self) -> int:
         return int(self._L.flimo_desc_ref_size(self._h))
 
     def desc_ref_dim(self) -> int:
         return int(self._L.flimo_desc_ref_dim(self._h))
-
-    def desc_match(self, q, k=2):
-        """flimo_desc_match: per row of ``q`` [nq, dim] the first ``k`` rows of the resident reference set by (bits of the float32
-        squared distance, index) -- the distance is include/flimo_c.h's fmaf chain, exact and reproducible.  Returns a dict: idx
-        [nq, k] int32 (-1 beyond cnt), dist [nq, k] float32 (0 beyond cnt), cnt [nq].  Rows with a non-finite entry never match."""
-        return desc_match_call(lambda *a: self._chk(self._L.flimo_desc_match(self._h, *a)), q, k)
 
     def set_desc_chunk(self, queries_per_chunk=0, refs_per_split=0):
         """Queries per chunk of ``desc_match`` and reference rows per split of its grid (flimo_set_desc_chunk; 0: the defaults)."""
@@ -1518,9 +1114,7 @@ def ieskf_eval_host(op, items):
 def device_large_bar(device: int = 0) -> bool:
     """The hardware's side of the pipelined host loop (flimo_device_large_bar): the device maps its memory for the host."""
     v = C.c_int(0)
-    fn = load_hip().flimo_device_large_bar
-    fn.argtypes = [C.c_int, C.POINTER(C.c_int)]
-    rc = fn(int(device), C.byref(v))
+    rc = load_hip().flimo_device_large_bar(int(device), C.byref(v))
     if rc != 0:
         raise FlimoError(f"flimo_device_large_bar({device}) failed: {_ERRS.get(rc, rc)}")
     return bool(v.value)

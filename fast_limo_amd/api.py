@@ -10,45 +10,13 @@ import math
 import os
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
+from ._abi import LocCfg
 from ._lib import FlimoError, f32p, f64p
 
 _host = None
 
-
-class LocCfg(C.Structure):
-    _fields_ = [
-        ("NUM_MATCH_POINTS", C.c_int), ("MAX_NUM_MATCHES", C.c_int), ("MAX_NUM_PC2MATCH", C.c_int),
-        ("bucket_size", C.c_int),
-        ("MAX_DIST_PLANE", C.c_double), ("PLANE_THRESHOLD", C.c_double),
-        ("min_extent", C.c_float), ("downsampling", C.c_int),
-        ("MAX_NUM_ITERS", C.c_int), ("estimate_extrinsics", C.c_int),
-        ("LIMITS", C.c_double * 23),
-        ("cov_gyro", C.c_double), ("cov_acc", C.c_double), ("cov_bias_gyro", C.c_double), ("cov_bias_acc", C.c_double),
-        ("time_offset", C.c_int), ("end_of_sweep", C.c_int), ("num_threads", C.c_int),
-        ("imu2baselink_t", C.c_float * 3), ("imu2baselink_R", C.c_float * 9),
-        ("lidar2baselink_t", C.c_float * 3), ("lidar2baselink_R", C.c_float * 9),
-        ("accel_bias", C.c_float * 3), ("gyro_bias", C.c_float * 3), ("imu_sm", C.c_float * 9),
-        ("voxel_active", C.c_int), ("leaf_size", C.c_float),
-        ("crop_active", C.c_int), ("cropBoxMin", C.c_float * 3), ("cropBoxMax", C.c_float * 3),
-        ("dist_active", C.c_int), ("min_dist", C.c_double),
-        ("rate_active", C.c_int), ("rate_value", C.c_int),
-        ("fov_active", C.c_int), ("fov_angle", C.c_float),
-        ("sensor_type", C.c_int),
-        ("gravity_align", C.c_int), ("calibrate_accel", C.c_int), ("calibrate_gyro", C.c_int),
-        ("imu_calib_time", C.c_double),
-        ("gpu_device", C.c_int), ("gpu_cell_size", C.c_float), ("debug", C.c_int),
-    ]
-
-
-HOST_SYMBOLS = [
-    "flimo_loc_create", "flimo_loc_destroy", "flimo_loc_ctx", "flimo_loc_sync", "flimo_loc_set_async_insert", "flimo_loc_set_lazy_time_order", "flimo_loc_set_gpu_filters", "flimo_loc_set_exact_tied_order", "flimo_loc_set_local_map", "flimo_local_map_rule", "flimo_loc_set_map_carving", "flimo_carve_rule", "flimo_carve_sensor", "flimo_loc_map_seen_through", "flimo_loc_map_carve", "flimo_loc_last_carve_removed", "flimo_loc_map_outliers", "flimo_loc_map_remove_outliers", "flimo_loc_map_fpfh", "flimo_loc_map_keypoints", "flimo_loc_map_clusters", "flimo_loc_map_remove_clusters", "flimo_loc_map_planes", "flimo_loc_map_plane_mask", "flimo_loc_map_remove_plane", "flimo_loc_map_voxels", "flimo_loc_map_voxel_mask", "flimo_loc_map_thin", "flimo_loc_map_regions", "flimo_loc_map_region_list", "flimo_loc_map_remove_regions", "flimo_loc_map_radius_search", "flimo_loc_map_normals", "flimo_loc_map_normals_range", "flimo_loc_map_knn", "flimo_loc_last_sweep_tied", "flimo_loc_scan_fitness", "flimo_loc_scan_linearize", "flimo_loc_corr_poses", "flimo_loc_corr_graph", "flimo_loc_desc_ref_set", "flimo_loc_desc_match", "flimo_loc_set_propagation_wait", "flimo_loc_last_insert_seconds", "flimo_loc_update_imu", "flimo_loc_update_imu_n", "flimo_loc_replay", "flimo_loc_update_pointcloud", "flimo_loc_update_pointcloud_points",
-    "flimo_loc_map_add", "flimo_loc_map_size", "flimo_loc_get_x", "flimo_loc_set_x", "flimo_loc_get_P",
-    "flimo_loc_set_P", "flimo_loc_set_flags", "flimo_loc_num_passes", "flimo_loc_get_pass", "flimo_loc_get_pc2match",
-    "flimo_loc_get_final_scan", "flimo_loc_get_debug_cloud", "flimo_loc_get_stage_times", "flimo_loc_get_pose_cov", "flimo_loc_register_resident", "flimo_loc_host_profile",
-    "flimo_eskf_update_fixed", "flimo_eskf_predict", "flimo_host_eigen_solver6", "flimo_host_plane", "flimo_host_state_update", "flimo_host_time_order",
-    "flimo_ieskf_gj12_host", "flimo_ieskf_run_fixed_host",
-]
+HOST_SYMBOLS = _abi.HOST_SYMBOLS      # every symbol include/flimo_localizer_c.h declares (tests check the .so exports each one)
 
 
 # the reference's PointType (Common.hpp:100-113): xyz1, intensity, 4 bytes of padding, 8-byte time union
@@ -117,122 +85,7 @@ def load_host():
     if not os.path.exists(path):
         raise FlimoError(f"{path} not found: build first")
     L = C.CDLL(path)
-    vp = C.c_void_p
-    L.flimo_loc_create.argtypes = [C.POINTER(LocCfg), C.POINTER(vp)]
-    L.flimo_loc_destroy.restype = None
-    L.flimo_loc_destroy.argtypes = [vp]
-    L.flimo_loc_ctx.restype = vp
-    L.flimo_loc_ctx.argtypes = [vp]
-    L.flimo_loc_sync.restype = None
-    L.flimo_loc_sync.argtypes = [vp]
-    L.flimo_loc_set_async_insert.restype = None
-    L.flimo_loc_set_async_insert.argtypes = [vp, C.c_int]
-    L.flimo_loc_set_lazy_time_order.restype = None
-    L.flimo_loc_set_lazy_time_order.argtypes = [vp, C.c_int]
-    L.flimo_loc_set_gpu_filters.restype = None
-    L.flimo_loc_set_gpu_filters.argtypes = [vp, C.c_int]
-    L.flimo_loc_set_exact_tied_order.restype = None
-    L.flimo_loc_set_exact_tied_order.argtypes = [vp, C.c_int]
-    L.flimo_loc_set_local_map.restype = None
-    L.flimo_loc_set_local_map.argtypes = [vp, f32p, C.c_float]
-    L.flimo_loc_map_radius_search.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_size_t, C.POINTER(C.c_uint64)]
-    L.flimo_loc_map_knn.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_loc_map_normals.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-    L.flimo_loc_map_normals_range.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_loc_scan_fitness.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_loc_scan_linearize.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_loc_corr_poses.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_lib.CorrCfg), C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_loc_corr_graph.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_lib.CorrGraphCfg), C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p]
-    L.flimo_loc_desc_ref_set.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int]
-    L.flimo_loc_desc_match.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_loc_set_map_carving.restype = None
-    L.flimo_loc_set_map_carving.argtypes = [vp, C.c_int, C.POINTER(_lib.CarveCfg)]
-    L.flimo_carve_rule.restype = C.c_int
-    L.flimo_carve_rule.argtypes = [C.c_int, C.POINTER(C.c_int)]
-    L.flimo_carve_sensor.restype = None
-    L.flimo_carve_sensor.argtypes = [_lib.f64p, f32p]
-    L.flimo_loc_map_seen_through.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(_lib.CarveCfg), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.flimo_loc_map_carve.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(_lib.CarveCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
-    L.flimo_loc_last_carve_removed.restype = C.c_size_t
-    L.flimo_loc_last_carve_removed.argtypes = [vp]
-    L.flimo_loc_map_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.OutlierCfg), C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.POINTER(_lib.OutlierStats)]
-    L.flimo_loc_map_fpfh.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.FpfhCfg), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_loc_map_keypoints.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.KeypointCfg), C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.POINTER(C.c_size_t)]
-    L.flimo_loc_map_remove_outliers.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.OutlierCfg), C.POINTER(C.c_size_t),
-                                                C.POINTER(_lib.OutlierStats)]
-    L.flimo_loc_map_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.ClusterCfg), C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.POINTER(_lib.ClusterStats)]
-    L.flimo_loc_map_remove_clusters.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.ClusterCfg), C.POINTER(C.c_size_t),
-                                                C.POINTER(_lib.ClusterStats)]
-    L.flimo_loc_map_planes.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(_lib.PlaneCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.flimo_loc_map_plane_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.PlaneSel), C.c_void_p, C.POINTER(C.c_size_t)]
-    L.flimo_loc_map_remove_plane.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.PlaneSel), C.POINTER(C.c_size_t)]
-    L.flimo_loc_map_voxels.argtypes = [vp, C.POINTER(_lib.VoxelCfg), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_lib.VoxelStats)]
-    L.flimo_loc_map_voxel_mask.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.VoxelCfg), C.c_void_p, C.c_void_p,
-                                           C.POINTER(_lib.VoxelStats)]
-    L.flimo_loc_map_thin.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.VoxelCfg), C.POINTER(C.c_size_t), C.POINTER(_lib.VoxelStats)]
-    L.flimo_loc_map_regions.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.RegionCfg), C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.POINTER(_lib.RegionStats)]
-    L.flimo_loc_map_region_list.argtypes = [vp, C.POINTER(_lib.RegionCfg), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.POINTER(_lib.RegionStats)]
-    L.flimo_loc_map_remove_regions.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(_lib.RegionCfg), C.POINTER(C.c_size_t),
-                                               C.POINTER(_lib.RegionStats)]
-    L.flimo_local_map_rule.restype = C.c_int
-    L.flimo_local_map_rule.argtypes = [_lib.f64p, f32p, C.c_float, _lib.f64p, C.POINTER(C.c_int), f32p, f32p]
-    L.flimo_loc_last_sweep_tied.restype = C.c_int
-    L.flimo_loc_last_sweep_tied.argtypes = [vp]
-    L.flimo_loc_set_propagation_wait.restype = None
-    L.flimo_loc_set_propagation_wait.argtypes = [vp, C.c_double]
-    L.flimo_loc_last_insert_seconds.restype = C.c_double
-    L.flimo_loc_last_insert_seconds.argtypes = [vp]
-    L.flimo_loc_update_imu.argtypes = [vp, C.c_double, f32p, f32p]
-    L.flimo_loc_update_imu_n.argtypes = [vp, C.c_size_t, np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS"), f32p, f32p]
-    f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
-    L.flimo_loc_replay.argtypes = [vp, C.c_size_t, C.POINTER(C.c_void_p), np.ctypeslib.ndpointer(np.uintp, flags="C_CONTIGUOUS"), f64p, f64p,
-                                   C.c_size_t, f64p, f32p, f32p, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"), f64p]
-    L.flimo_loc_update_pointcloud.argtypes = [vp, f32p, C.c_size_t, C.c_double]
-    L.flimo_loc_update_pointcloud_points.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_double]
-    L.flimo_loc_map_add.argtypes = [vp, f32p, C.c_size_t, C.c_double]
-    L.flimo_loc_map_size.restype = C.c_size_t
-    L.flimo_loc_map_size.argtypes = [vp]
-    L.flimo_loc_get_x.restype = None
-    L.flimo_loc_get_x.argtypes = [vp, f64p]
-    L.flimo_loc_set_x.restype = None
-    L.flimo_loc_set_x.argtypes = [vp, f64p]
-    L.flimo_loc_get_P.restype = None
-    L.flimo_loc_get_P.argtypes = [vp, f64p]
-    L.flimo_loc_set_P.restype = None
-    L.flimo_loc_set_P.argtypes = [vp, f64p]
-    L.flimo_loc_set_flags.restype = None
-    L.flimo_loc_set_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-    L.flimo_loc_num_passes.argtypes = [vp]
-    L.flimo_loc_get_pass.restype = None
-    L.flimo_loc_get_pass.argtypes = [vp, C.c_int, C.POINTER(C.c_int), f64p, f64p, f64p, f64p]
-    L.flimo_loc_get_pc2match.restype = C.c_size_t
-    L.flimo_loc_get_pc2match.argtypes = [vp, C.c_void_p, C.c_size_t]
-    L.flimo_loc_get_final_scan.restype = C.c_size_t
-    L.flimo_loc_get_final_scan.argtypes = [vp, C.c_void_p, C.c_size_t]
-    L.flimo_loc_get_debug_cloud.restype = C.c_size_t
-    L.flimo_loc_get_debug_cloud.argtypes = [vp, C.c_int, C.c_void_p, C.c_size_t]
-    L.flimo_loc_get_stage_times.restype = None
-    L.flimo_loc_get_stage_times.argtypes = [vp, f64p]
-    L.flimo_loc_get_pose_cov.restype = None
-    L.flimo_loc_get_pose_cov.argtypes = [vp, f64p]
-    L.flimo_loc_register_resident.argtypes = [vp, f64p, f64p]
-    L.flimo_loc_host_profile.restype = None
-    L.flimo_loc_host_profile.argtypes = [vp, f64p, C.c_int]
-    L.flimo_eskf_update_fixed.argtypes = [f64p, f64p, f64p, f64p, C.c_int, C.c_int, f64p, C.c_double, C.c_double,
-                                          C.POINTER(C.c_int)]
-    L.flimo_eskf_predict.argtypes = [f64p, f64p, C.c_double, f64p, f64p, f64p]
+    _abi.declare(L, 1)
     _host = L
     return L
 
@@ -246,7 +99,7 @@ class _MapperCtxView(_lib.HipCtx):
         return C.c_void_p(self._loc._L.flimo_loc_ctx(self._loc._h))
 
 
-class Localizer:
+class Localizer(_lib._SharedEntries):
     """fast_limo::Localizer (one instance per GPU)."""
 
     def __init__(self, cfg: LocCfg):
@@ -374,277 +227,29 @@ class Localizer:
         k = _lib.carve_cfg(**cfg)
         self._L.flimo_loc_set_map_carving(self._h, int(every_n_sweeps), C.byref(k))
 
-    def map_seen_through(self, x26, sensor, **cfg):
-        """The stored points the scan of the last sweep looks through at ``x26`` from ``sensor`` (flimo_loc_map_seen_through):
-        ``(mask, count)`` as ``HipCtx.map_seen_through``.  Waits for an insert, a crop or a carve still running; changes nothing."""
-        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
-        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
-        k = _lib.carve_cfg(**cfg)
-        n = self.map_size()
-        mask = np.zeros(max(n, 1), np.uint8)
-        count = C.c_size_t(0)
-        rc = self._L.flimo_loc_map_seen_through(self._h, x.ctypes.data, s.ctypes.data, C.byref(k), mask.ctypes.data, n, C.byref(count))
-        if rc != 0:
-            raise FlimoError(f"flimo_loc_map_seen_through failed ({rc})")
-        return mask[:n].astype(bool), int(count.value)
+    # ---- the entries shared with HipCtx (_lib._SharedEntries), on the flimo_loc_* symbols ----
+    map_knn, map_radius_search = _lib._SharedEntries._knn_k, _lib._SharedEntries._radius_search
+    map_normals, map_normals_range = _lib._SharedEntries._normals, _lib._SharedEntries._normals_range
 
-    def map_carve(self, x26, sensor, box=None, **cfg) -> int:
-        """Forget the stored points the scan of the last sweep looks through and, with ``box`` = (lo, hi), those outside it
-        (flimo_loc_map_carve), as ``HipCtx.map_carve``.  Returns the number of points removed."""
-        x = np.ascontiguousarray(x26, dtype=np.float64).reshape(26)
-        s = np.ascontiguousarray(sensor, dtype=np.float32).reshape(3)
-        k = _lib.carve_cfg(**cfg)
-        lo = hi = None
-        if box is not None:
-            lo = np.ascontiguousarray(box[0], dtype=np.float32).reshape(3)
-            hi = np.ascontiguousarray(box[1], dtype=np.float32).reshape(3)
-        removed = C.c_size_t(0)
-        rc = self._L.flimo_loc_map_carve(self._h, x.ctypes.data, s.ctypes.data, C.byref(k), None if lo is None else lo.ctypes.data,
-                                         None if hi is None else hi.ctypes.data, C.byref(removed))
-        if rc != 0:
-            raise FlimoError(f"flimo_loc_map_carve failed ({rc})")
-        return int(removed.value)
+    def _symbol(self, entry):
+        return _abi.LOC_OF[entry]
+
+    def _fail(self, entry, rc):
+        raise FlimoError(f"{self._symbol(entry)} failed ({rc})")
+
+    def _scan_size(self):
+        return self.hip.scan_size()      # (the scan resident in the map's context; 0 when there is no map yet)
 
     def last_carve_removed(self) -> int:
         return int(self._L.flimo_loc_last_carve_removed(self._h))
-
-    @staticmethod
-    def _entry_chk(rc, what):
-        if rc != 0:
-            raise FlimoError(f"{what} failed ({rc})")
-
-    def _range(self, first, n):
-        """(first, n) of a range entry; ``n`` None: up to the map's end."""
-        first = int(first)
-        return first, max(self.map_size() - first, 0) if n is None else int(n)
-
-    def map_outliers(self, first=0, n=None, want=("mask", "mean_dist", "cnt"), **cfg):
-        """The map's outliers by neighbour statistics (flimo_loc_map_outliers), as ``HipCtx.map_outliers``.  Waits for an insert, a
-        crop or a carve still running; changes nothing.  No policy calls it: when to clean is the caller's schedule."""
-        first, n = self._range(first, n)
-        return _lib.outliers_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_outliers(self._h, first, n, *a), "flimo_loc_map_outliers"),
-                                  n, want, cfg)
-
-    def map_remove_outliers(self, first=0, n=None, **cfg):
-        """Forget them (flimo_loc_map_remove_outliers), as ``HipCtx.map_remove_outliers``: (points removed, stats)."""
-        first, n = self._range(first, n)
-        k = _lib.outlier_cfg(**cfg)
-        removed = C.c_size_t(0)
-        st = _lib.OutlierStats()
-        self._entry_chk(self._L.flimo_loc_map_remove_outliers(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
-                        "flimo_loc_map_remove_outliers")
-        return int(removed.value), st.as_dict()
-
-    def map_fpfh(self, first=0, n=None, want=("spfh", "cnt"), **cfg):
-        """FPFH descriptors of the map's stored points (flimo_loc_map_fpfh), as ``HipCtx.map_fpfh``.  Waits for an insert, a crop or
-        a carve still running; changes nothing.  The Localizer's own update does not use it."""
-        first, n = self._range(first, n)
-        return _lib.fpfh_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_fpfh(self._h, first, n, *a), "flimo_loc_map_fpfh"), n, want, cfg)
-
-    def map_keypoints(self, first=0, n=None, want=("saliency", "cnt"), **cfg):
-        """ISS keypoints of the map's stored points (flimo_loc_map_keypoints), as ``HipCtx.map_keypoints``.  Waits for an insert, a
-        crop or a carve still running; changes nothing.  The Localizer's own update does not use it."""
-        first, n = self._range(first, n)
-        return _lib.keypoints_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_keypoints(self._h, first, n, *a), "flimo_loc_map_keypoints"),
-                                   n, want, cfg)
-
-    def map_clusters(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
-        """Euclidean clusters of the map's stored points (flimo_loc_map_clusters), as ``HipCtx.map_clusters``.  Waits for an insert, a
-        crop or a carve still running; changes nothing.  No policy calls it: when to clean is the caller's schedule."""
-        first, n = self._range(first, n)
-        return _lib.clusters_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_clusters(self._h, first, n, *a), "flimo_loc_map_clusters"),
-                                  n, want, cfg)
-
-    def map_remove_clusters(self, first=0, n=None, **cfg):
-        """Forget the selected clusters' points of the range (flimo_loc_map_remove_clusters), as ``HipCtx.map_remove_clusters``:
-        (points removed, stats)."""
-        first, n = self._range(first, n)
-        k = _lib.cluster_cfg(**cfg)
-        removed = C.c_size_t(0)
-        st = _lib.ClusterStats()
-        self._entry_chk(self._L.flimo_loc_map_remove_clusters(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
-                        "flimo_loc_map_remove_clusters")
-        return int(removed.value), st.as_dict()
-
-    def map_planes(self, tri, want=("plane",), **cfg):
-        """RANSAC plane hypotheses over the map's stored points (flimo_loc_map_planes), as ``HipCtx.map_planes``.  Waits for an
-        insert, a crop or a carve still running; changes nothing.  No policy calls it."""
-        return _lib.planes_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_planes(self._h, *a), "flimo_loc_map_planes"), tri, want, cfg)
-
-    def map_plane_mask(self, sel=None, first=0, n=None, want_mask=True, **kw):
-        """The stored points of a range against one plane (flimo_loc_map_plane_mask), as ``HipCtx.map_plane_mask``: (mask, count)."""
-        first, n = self._range(first, n)
-        sel = _lib._as_plane_sel(sel, kw)
-        return _lib.plane_mask_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_plane_mask(self._h, first, n, *a), "flimo_loc_map_plane_mask"),
-                                    n, sel, want_mask)
-
-    def map_remove_plane(self, sel=None, first=0, n=None, **kw):
-        """Forget the points of the range inside one plane's gate (flimo_loc_map_remove_plane), as ``HipCtx.map_remove_plane``: the
-        number of points removed."""
-        first, n = self._range(first, n)
-        sel = _lib._as_plane_sel(sel, kw)
-        removed = C.c_size_t(0)
-        self._entry_chk(self._L.flimo_loc_map_remove_plane(self._h, first, n, C.byref(sel), C.byref(removed)), "flimo_loc_map_remove_plane")
-        return int(removed.value)
-
-    def map_voxels(self, want=("ijk", "count", "centroid"), **cfg):
-        """The voxels of the map's stored points (flimo_loc_map_voxels), as ``HipCtx.map_voxels``.  Waits for an insert, a crop or a
-        carve still running; changes nothing.  No policy calls it."""
-        return _lib.voxels_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_voxels(self._h, *a), "flimo_loc_map_voxels"),
-                                self.map_size(), want, cfg)
-
-    def map_voxel_mask(self, first=0, n=None, want=("voxel", "mask"), **cfg):
-        """The voxel and the thinning mask of a range of stored points (flimo_loc_map_voxel_mask), as ``HipCtx.map_voxel_mask``."""
-        first, n = self._range(first, n)
-        return _lib.voxel_mask_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_voxel_mask(self._h, first, n, *a), "flimo_loc_map_voxel_mask"),
-                                    n, want, cfg)
-
-    def map_thin(self, first=0, n=None, **cfg):
-        """Forget the points of the range that crowd their voxel (flimo_loc_map_thin), as ``HipCtx.map_thin``: (removed, stats)."""
-        first, n = self._range(first, n)
-        k = _lib.voxel_cfg(**cfg)
-        removed = C.c_size_t(0)
-        st = _lib.VoxelStats()
-        self._entry_chk(self._L.flimo_loc_map_thin(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)), "flimo_loc_map_thin")
-        return int(removed.value), st.as_dict()
 
     def voxel_cloud(self, res):
         """The decimated map one publishes or saves: the centroids of the voxels of edge ``res`` as float32 [nv, 3], in ascending
         (cz, cy, cx) -- ``map_voxels`` with only the centroid asked for."""
         return self.map_voxels(want=("centroid",), leaf=res)["centroid"].astype(np.float32)
 
-    def map_regions(self, first=0, n=None, want=("label", "size", "mask"), **cfg):
-        """Smooth-surface regions of the map's stored points (flimo_loc_map_regions), as ``HipCtx.map_regions``.  Waits for an insert,
-        a crop or a carve still running; changes nothing.  No policy calls it."""
-        first, n = self._range(first, n)
-        return _lib.regions_call(lambda *a: self._entry_chk(self._L.flimo_loc_map_regions(self._h, first, n, *a), "flimo_loc_map_regions"),
-                                 n, want, cfg)
-
-    def map_region_list(self, want=("label", "count", "centroid", "cov"), **cfg):
-        """The selected regions of the map's stored points (flimo_loc_map_region_list), as ``HipCtx.map_region_list``."""
-        return _lib.region_list_call(lambda *a: self._L.flimo_loc_map_region_list(self._h, *a),
-                                     lambda rc: self._entry_chk(rc, "flimo_loc_map_region_list"), want, cfg)
-
-    def map_remove_regions(self, first=0, n=None, **cfg):
-        """Forget the selected regions' points of the range (flimo_loc_map_remove_regions), as ``HipCtx.map_remove_regions``:
-        (points removed, stats)."""
-        first, n = self._range(first, n)
-        k = _lib.region_cfg(**cfg)
-        removed = C.c_size_t(0)
-        st = _lib.RegionStats()
-        self._entry_chk(self._L.flimo_loc_map_remove_regions(self._h, first, n, C.byref(k), C.byref(removed), C.byref(st)),
-                        "flimo_loc_map_remove_regions")
-        return int(removed.value), st.as_dict()
-
-    def map_radius_search(self, q, radius, sorted=False, want_xyz=False):
-        """Octree::radiusSearch over the Localizer's map (flimo_loc_map_radius_search): ``(offsets, idx, sqd[, xyz])`` in CSR form,
-        as ``HipCtx.radius_search``.  Waits for an insert or a crop still running behind the last sweep; changes nothing."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
-        nq = q.shape[0]
-        off = np.zeros(nq + 1, np.uint64)
-        total = C.c_uint64(0)
-        fn = self._L.flimo_loc_map_radius_search
-        rc = fn(self._h, q.ctypes.data, nq, float(radius), 0, off.ctypes.data, None, None, None, 0, C.byref(total))
-        if rc != 0:
-            raise FlimoError(f"flimo_loc_map_radius_search failed ({rc})")
-        n = int(total.value)
-        idx = np.empty(n, np.int32)
-        sqd = np.empty(n, np.float32)
-        xyz = np.empty((n, 3), np.float32) if want_xyz else None
-        if n > 0:
-            rc = fn(self._h, q.ctypes.data, nq, float(radius), 1 if sorted else 0, off.ctypes.data, idx.ctypes.data, sqd.ctypes.data,
-                    xyz.ctypes.data if want_xyz else None, n, C.byref(total))
-            if rc != 0:
-                raise FlimoError(f"flimo_loc_map_radius_search failed ({rc})")
-        return (off, idx, sqd, xyz) if want_xyz else (off, idx, sqd)
-
-    def map_knn(self, q, k, max_dist=float("inf"), want_xyz=False):
-        """Octree::knn for any k up to 64, with a distance gate, over the Localizer's map (flimo_loc_map_knn): ``(idx, sqd, cnt[, xyz])``
-        as ``HipCtx.knn_k``.  Waits for an insert or a crop still running behind the last sweep; changes nothing."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
-        nq, kk = q.shape[0], max(int(k), 1)
-        idx = np.empty((nq, kk), np.int32)
-        sqd = np.empty((nq, kk), np.float32)
-        cnt = np.empty((nq,), np.int32)
-        xyz = np.empty((nq, kk, 3), np.float32) if want_xyz else None
-        ptr = lambda a: a.ctypes.data if a.size else C.addressof(C.c_double())
-        rc = self._L.flimo_loc_map_knn(self._h, q.ctypes.data if nq else None, nq, int(k), float(max_dist), ptr(idx), ptr(sqd),
-                                       ptr(xyz) if want_xyz else None, ptr(cnt))
-        if rc != 0:
-            raise FlimoError(f"flimo_loc_map_knn failed ({rc})")
-        return (idx, sqd, cnt, xyz) if want_xyz else (idx, sqd, cnt)
-
-    def _normals_chk(self, rc):
-        if rc != 0:
-            raise FlimoError(f"flimo_loc_map_normals failed ({rc})")
-
-    def map_normals(self, q, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
-        """Plane normals, curvature and covariances of the map's k-NN neighbourhoods (flimo_loc_map_normals): the dict of
-        ``HipCtx.normals``.  Waits for an insert or a crop still running behind the last sweep; changes nothing."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
-        return _lib.normals_call(lambda *a: self._normals_chk(self._L.flimo_loc_map_normals(self._h, q.ctypes.data if q.shape[0] else None,
-                                                                                            q.shape[0], *a)),
-                                 q.shape[0], k, max_dist, min_pts, viewpoint, want)
-
-    def map_normals_range(self, first, n, k, max_dist=float("inf"), min_pts=3, viewpoint=None, want=("centroid", "cov", "eig")):
-        """... of the stored points first .. first + n - 1 themselves (flimo_loc_map_normals_range), as ``HipCtx.normals_range``."""
-        return _lib.normals_call(lambda *a: self._normals_chk(self._L.flimo_loc_map_normals_range(self._h, int(first), int(n), *a)),
-                                 int(n), k, max_dist, min_pts, viewpoint, want)
-
-    def _fitness_chk(self, rc):
-        if rc != 0:
-            raise FlimoError(f"flimo_loc_scan_fitness failed ({rc})")
-
-    def scan_fitness(self, x26s, max_dist=float("inf"), want_nn=False):
-        """How well the scan of the last sweep (``pc2match()``, resident on the GPU) fits the map at each pose of ``x26s`` [np, 26]
-        (flimo_loc_scan_fitness): ``(inliers, sum_sqd[, nn_sqd, nn_idx])`` as ``HipCtx.scan_fitness``.  Waits for an insert or a crop
-        still running behind the last sweep; changes nothing."""
-        n = self.hip.scan_size()      # (the scan resident in the map's context; 0 when there is no map yet)
-        return _lib.fitness_call(lambda *a: self._fitness_chk(self._L.flimo_loc_scan_fitness(self._h, *a)), x26s, n, max_dist, want_nn)
-
-    def _linearize_chk(self, rc):
-        if rc != 0:
-            raise FlimoError(f"flimo_loc_scan_linearize failed ({rc})")
-
-    def scan_linearize(self, x26s, k, max_dist, min_pts=3, max_curv=float("inf"), want_rows=False):
-        """The point-to-plane normal equations of the scan of the last sweep against the map at each pose of ``x26s`` [np, 26]
-        (flimo_loc_scan_linearize): the dict of ``HipCtx.scan_linearize``.  Waits for an insert or a crop still running behind the
-        last sweep; changes nothing."""
-        n = self.hip.scan_size()      # (the scan resident in the map's context; 0 when there is no map yet)
-        return _lib.linearize_call(lambda *a: self._linearize_chk(self._L.flimo_loc_scan_linearize(self._h, *a)), x26s, n, k, max_dist, min_pts,
-                                   max_curv, want_rows)
-
-    def _corr_chk(self, rc):
-        if rc != 0:
-            raise FlimoError(f"flimo_loc_corr_poses failed ({rc})")
-
-    def corr_poses(self, src, dst, tri, want=("pose",), **cfg):
-        """Pose hypotheses from point correspondences on the map's context (flimo_loc_corr_poses): the dict of
-        ``HipCtx.corr_poses``.  Waits for an insert, a crop or a carve still running behind the last sweep; reads neither the map nor
-        the resident scan.  The Localizer's own update does not use it."""
-        return _lib.corr_call(lambda *a: self._corr_chk(self._L.flimo_loc_corr_poses(self._h, *a)), src, dst, tri, want, cfg)
-
-    def corr_graph(self, src, dst, want=(), **cfg):
-        """The consistency graph of point correspondences and its core numbers on the map's context (flimo_loc_corr_graph): the dict
-        of ``HipCtx.corr_graph``.  Waits for an insert, a crop or a carve still running behind the last sweep; reads neither the map
-        nor the resident scan.  The Localizer's own update does not use it."""
-        return _lib.corr_graph_call(lambda *a: self._entry_chk(self._L.flimo_loc_corr_graph(self._h, *a), "flimo_loc_corr_graph"), src, dst,
-                                    want, cfg)
-
-    def desc_ref_set(self, desc):
-        """``desc`` [nr, dim] becomes the resident reference set of ``desc_match`` on the map's context (flimo_loc_desc_ref_set), as
-        ``HipCtx.desc_ref_set``.  Waits for an insert, a crop or a carve still running; reads neither the map nor the scan."""
-        d = _lib.desc_rows(desc)
-        self._entry_chk(self._L.flimo_loc_desc_ref_set(self._h, d.ctypes.data if d.size else None, d.shape[0], d.shape[1] if d.shape[0] else 0),
-                        "flimo_loc_desc_ref_set")
-
     def desc_ref_size(self) -> int:
         return self.hip.desc_ref_size()
-
-    def desc_match(self, q, k=2):
-        """Nearest rows of the resident reference set (flimo_loc_desc_match): the dict of ``HipCtx.desc_match``.  The Localizer's own
-        update does not use it."""
-        return _lib.desc_match_call(lambda *a: self._entry_chk(self._L.flimo_loc_desc_match(self._h, *a), "flimo_loc_desc_match"), q, k)
 
     def last_sweep_tied(self) -> bool:
         return bool(self._L.flimo_loc_last_sweep_tied(self._h))
@@ -1160,7 +765,6 @@ def ieskf_gj12_host(op, items):
     """The host filter's own elimination (flimo_host::inverse_gj / solve_gj, n = 12) on a batch: ``op`` _lib.IK_GJ12_INVERSE
     (items [n, 144] -> [n, 145]) or _lib.IK_GJ12_SOLVE ([n, 156] -> [n, 13]); the last column is ``ok``."""
     L = load_host()
-    L.flimo_ieskf_gj12_host.argtypes = [C.c_int, f64p, C.c_size_t, f64p]
     a, no = _lib.ik_items(op, items)
     out = np.zeros((a.shape[0], no))
     if a.shape[0]:
@@ -1175,8 +779,6 @@ def ieskf_run_fixed_host(x26, P, limits, partials, R=0.001, D=5.0, max_iter=3):
     Returns a dict: log (per completed pass a dict M, HTH, HTh, dx, x_after, t: the filter's own count so far), x, P, it (the iteration the loop ended in), t,
     passes."""
     L = load_host()
-    L.flimo_ieskf_run_fixed_host.argtypes = [f64p, f64p, f64p, C.c_double, C.c_double, C.c_int, C.c_int, f64p, f64p, C.POINTER(C.c_int),
-                                             f64p, f64p, C.POINTER(C.c_int)]
     x, Pm, lim, part = _lib.ik_fixed_args(x26, P, limits, partials)
     lg = np.zeros((int(max_iter) + 1, _lib.IK_HLOG_N))
     n = C.c_int(0)
@@ -1194,8 +796,6 @@ def ieskf_run_fixed_host(x26, P, limits, partials, R=0.001, D=5.0, max_iter=3):
 def eigen_solver6(A):
     """The host filter's restatement of Eigen::EigenSolver<Matrix6d>: (eigenvalues real, imag, eigenvector real parts as columns)."""
     L = load_host()
-    L.flimo_host_eigen_solver6.restype = None
-    L.flimo_host_eigen_solver6.argtypes = [f64p, f64p, f64p, f64p]
     A = np.ascontiguousarray(A, dtype=np.float64).reshape(36)
     wr = np.zeros(6); wi = np.zeros(6); V = np.zeros(36)
     L.flimo_host_eigen_solver6(A, wr, wi, V)

@@ -64,7 +64,7 @@ def test_corr_graph_entry_points_are_exported_declared_and_listed(built):
         assert callable(getattr(cls, "corr_graph"))
     for name in ("corr_prune", "corr_compatible_host"):
         assert callable(getattr(api, name)), name
-    assert callable(_lib.corr_graph_cfg) and callable(_lib.corr_graph_call)
+    assert callable(_lib.corr_graph_cfg) and _lib.HipCtx.corr_graph is api.Localizer.corr_graph      # (one method, two symbols)
     assert C.sizeof(_lib.CorrGraphCfg) == 12 and _lib.CORR_GRAPH_MAX_M == cg.MAX_M == 32768
     k = _lib.corr_graph_cfg()
     assert (k.tol, k.min_edge, k.edge_sim) == (F(0.05), 0.0, 0.0)

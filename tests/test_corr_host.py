@@ -62,7 +62,7 @@ def test_corr_entry_points_are_exported_declared_and_listed(built):
             assert callable(getattr(cls, name)), name
     for name in ("corr_triplets", "corr_pose_host", "corr_consensus"):
         assert callable(getattr(api, name)), name
-    assert callable(_lib.corr_cfg) and callable(_lib.corr_call)
+    assert callable(_lib.corr_cfg) and _lib.HipCtx.corr_poses is api.Localizer.corr_poses      # (one method, two symbols)
     assert C.sizeof(_lib.CorrCfg) == 12
     assert (_lib.CORR_OK, _lib.CORR_DEGENERATE, _lib.CORR_REJECTED) == (cc.OK, cc.DEGENERATE, cc.REJECTED) == (0, 1, 2)
 

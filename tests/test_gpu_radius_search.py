@@ -24,7 +24,7 @@ def _raw(ctx, q, radius, flags, off, idx, sqd, xyz, cap, total):
     """The C entry itself (arrays or None)."""
     q = np.ascontiguousarray(q, np.float32).reshape(-1)
     p = lambda a: None if a is None else a.ctypes.data
-    return ctx._L.flimo_radius_search(ctx._h, q, q.size // 3, float(radius), int(flags), p(off), p(idx), p(sqd), p(xyz), int(cap),
+    return ctx._L.flimo_radius_search(ctx._h, q.ctypes.data, q.size // 3, float(radius), int(flags), p(off), p(idx), p(sqd), p(xyz), int(cap),
                                       None if total is None else C.byref(total))
 
 
@@ -205,7 +205,7 @@ def test_edges(hip, scene):
         assert _raw(hip, q3, bad, 0, off, None, None, None, 0, total) == ERR_INVALID, bad
     assert _raw(hip, q3, 1.0, 2, off, None, None, None, 0, total) == ERR_INVALID               # unknown flag bits
     assert _raw(hip, q3, 1.0, 0, None, None, None, None, 0, total) == ERR_INVALID              # offsets are required
-    assert hip._L.flimo_radius_search(hip._h, np.zeros(0, np.float32), 0, 1.0, 0, off.ctypes.data, None, None, None, 0, C.byref(total)) == 0
+    assert hip._L.flimo_radius_search(hip._h, np.zeros(0, np.float32).ctypes.data, 0, 1.0, 0, off.ctypes.data, None, None, None, 0, C.byref(total)) == 0
     assert off[0] == 0 and total.value == 0                                                    # nq == 0
     # a NaN query among valid ones is empty; the others are not disturbed
     o, idx, sqd = hip.radius_search(q3, 2.0)

@@ -34,7 +34,7 @@ def test_radius_search_rejects_a_null_context(built):
     q = np.zeros(3, np.float32)
     off = np.full(2, 7, np.uint64)
     total = C.c_uint64(9)
-    assert L.flimo_radius_search(None, q, 1, 1.0, 0, off.ctypes.data, None, None, None, 0, C.byref(total)) == -2      # FLIMO_ERR_INVALID
+    assert L.flimo_radius_search(None, q.ctypes.data, 1, 1.0, 0, off.ctypes.data, None, None, None, 0, C.byref(total)) == -2      # FLIMO_ERR_INVALID
     H = api.load_host()
     assert H.flimo_loc_map_radius_search(None, q.ctypes.data, 1, 1.0, 0, off.ctypes.data, None, None, None, 0, C.byref(total)) == -2
 

@@ -48,7 +48,7 @@ def csr_once(ctx, pts, tol, cap):
     off = np.zeros(len(pts) + 1, np.uint64)
     idx = np.empty(max(cap, 1), np.int32)
     total = C.c_uint64(0)
-    ctx._chk(ctx._L.flimo_radius_search(ctx._h, pts.reshape(-1), len(pts), float(tol), 0, off.ctypes.data, idx.ctypes.data, None, None, cap,
+    ctx._chk(ctx._L.flimo_radius_search(ctx._h, pts.ctypes.data, len(pts), float(tol), 0, off.ctypes.data, idx.ctypes.data, None, None, cap,
                                         C.byref(total)))
     return off, idx[:int(total.value)]
 

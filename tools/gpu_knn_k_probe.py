@@ -78,7 +78,7 @@ def probe_map(name, reps, with_ref, trace):
         if not trace or k == 16:
             off = np.zeros(NQ + 1, np.uint64)
             total = C.c_uint64(0)
-            rc = ctx._L.flimo_radius_search(ctx._h, q.reshape(-1), NQ, radius, 0, off.ctypes.data, None, None, None, 0, C.byref(total))
+            rc = ctx._L.flimo_radius_search(ctx._h, q.ctypes.data, NQ, radius, 0, off.ctypes.data, None, None, None, 0, C.byref(total))
             assert rc == 0 and np.all(np.diff(off).astype(np.int64) >= k), "the radius gives every query its k"
             tot = int(total.value)
             r["route_c"] = dict(radius=radius, results_per_query=tot / NQ)
@@ -87,8 +87,8 @@ def probe_map(name, reps, with_ref, trace):
 
                 def route_c():
                     t = C.c_uint64(0)
-                    assert ctx._L.flimo_radius_search(ctx._h, q.reshape(-1), NQ, radius, 0, off.ctypes.data, None, None, None, 0, C.byref(t)) == 0
-                    assert ctx._L.flimo_radius_search(ctx._h, q.reshape(-1), NQ, radius, 1, off.ctypes.data, ridx.ctypes.data, rsqd.ctypes.data, None,
+                    assert ctx._L.flimo_radius_search(ctx._h, q.ctypes.data, NQ, radius, 0, off.ctypes.data, None, None, None, 0, C.byref(t)) == 0
+                    assert ctx._L.flimo_radius_search(ctx._h, q.ctypes.data, NQ, radius, 1, off.ctypes.data, ridx.ctypes.data, rsqd.ctypes.data, None,
                                                       tot, C.byref(t)) == 0
                 r["route_c"]["ms"] = timed(route_c, max(3, reps // 4), warm=1)
                 r["route_c"]["knn_k_over_route_c"] = r["gate_off"]["ms"]["median"] / r["route_c"]["ms"]["median"]

@@ -36,7 +36,7 @@ def stats(v):
 def call(ctx, q, radius, flags, off, idx, sqd, cap):
     total = C.c_uint64(0)
     t0 = time.perf_counter()
-    rc = ctx._L.flimo_radius_search(ctx._h, q, q.size // 3, float(radius), flags, off.ctypes.data, None if idx is None else idx.ctypes.data,
+    rc = ctx._L.flimo_radius_search(ctx._h, q.ctypes.data, q.size // 3, float(radius), flags, off.ctypes.data, None if idx is None else idx.ctypes.data,
                                     None if sqd is None else sqd.ctypes.data, None, cap, C.byref(total))
     ms = 1e3 * (time.perf_counter() - t0)
     assert rc == 0, (rc, ctx._L.flimo_last_error(ctx._h))

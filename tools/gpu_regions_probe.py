@@ -139,7 +139,7 @@ def step_composed(a):
             off = np.zeros(n + 1, np.uint64)
             idx = np.empty(max(cap, 1), np.int32)
             total = C.c_uint64(0)
-            ctx._chk(ctx._L.flimo_radius_search(ctx._h, pts.reshape(-1), n, float(tol), 0, off.ctypes.data, idx.ctypes.data, None, None, cap,
+            ctx._chk(ctx._L.flimo_radius_search(ctx._h, pts.ctypes.data, n, float(tol), 0, off.ctypes.data, idx.ctypes.data, None, None, cap,
                                                 C.byref(total)))
             idx = idx[:int(total.value)]
             t2 = time.perf_counter()
