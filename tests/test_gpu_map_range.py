@@ -1,7 +1,7 @@
 """GPU suite: the range rule of the map entries.  Every entry that takes a range [first, first + n) of the stored points refuses one
 that ends beyond the map with FLIMO_ERR_INVALID and a message that names the entry, the range and the map's size, before it looks at
 anything else of the range and without touching the map; first == the map's size with n == 0 is the empty range at the end and
-succeeds.  The rule is written once (check_range in flimo_capi.hip): this file holds that one copy to what each entry did when it
+succeeds.  The rule is written once (check_range in flimo_capi_query.hip): this file holds that one copy to what each entry did when it
 had its own.  Every case is a call that launches nothing."""
 import ctypes as C
 
