@@ -177,8 +177,8 @@ extern "C" int flimo_radius_candidates(flimo_ctx* c, const float* q, size_t nq, 
 }
 
 // ---- k-NN for k up to FLIMO_KNN_MAX_K with a distance gate (Octree::knn, Objects/Octree.hpp:526-555) -------------
-// kernels and the meaning of the call: flimo_knn_k.hip.  One block-search launch, one launch that finishes what it could not prove
-// over the directory's tiles, the copies back, one wait.  cand (developer counter, flimo_dev.h): the result arrays may then be NULL.
+// kernels and the meaning of the call: flimo_knn_k.hip.  One block-search launch, one launch that finishes the worklist of what it
+// could not prove over the directory's tiles, the copies back, one wait.  cand (developer counter, flimo_dev.h): the result arrays may then be NULL.
 static int knn_k_run(flimo_ctx* c, const float* q, size_t nq, int k, float max_dist, int32_t* idx, float* sqd, float* xyz, int32_t* cnt,
                      uint64_t* cand) {
   static_assert(FLIMO_KNN_MAX_K == KNNK_MAX_K, "the header's limit is the kernels'");
@@ -202,9 +202,11 @@ static int knn_k_run(flimo_ctx* c, const float* q, size_t nq, int k, float max_d
   float* d_xyz = xyz ? d.get<float>(nq * k * 3) : nullptr;
   int32_t* d_cnt = d.get<int32_t>(nq);
   unsigned long long* d_cand = cand ? d.get<unsigned long long>(nq) : nullptr;
+  uint2* d_work = d.get<uint2>(nq + 1);      // the worklist and, behind it, its counter: one allocation, this call is short
   { const int rc = d.ok(c); if (rc) return rc; }
+  unsigned* d_nwork = reinterpret_cast<unsigned*>(d_work + nq);
   HIPCHK(c, hipMemcpyAsync(d_q, q, nq * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, launch_knn_k(c->stream, c->grid, c->d_map_raw, d_q, (int)nq, k, max_dist, d_idx, d_sqd, d_xyz, d_cnt, d_cand));
+  HIPCHK(c, launch_knn_k(c->stream, c->grid, c->d_map_raw, d_q, (int)nq, k, max_dist, d_idx, d_sqd, d_xyz, d_cnt, d_cand, d_work, d_nwork));
   if (idx) HIPCHK(c, hipMemcpyAsync(idx, d_idx, nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (sqd) HIPCHK(c, hipMemcpyAsync(sqd, d_sqd, nq * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, d_xyz, nq * k * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -316,11 +316,11 @@ hipError_t launch_region_list_labels(hipStream_t st, const unsigned long long* k
 // gate).  The running k-best is a list distributed over the lanes that serve the query (knnk_plan lanes, chosen from k); a block
 // search near the map, then a best-first walk over the directory's tiles for what it could not prove.  idx / sqd: [nq][k], padded
 // with -1 / 0; xyz (optional): [nq][k][3], gathered from map_raw (the map in insertion order); cnt: [nq]; cand (optional): stored
-// points each query's walk loaded and tested.
+// points each query's walk loaded and tested.  Scratch: work ([nq]) and nwork (one counter): the queries left to the walk over the tiles.
 constexpr int KNNK_MAX_K = 64;
 int knnk_plan(int k);
 hipError_t launch_knn_k(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, int nq, int k, float max_dist, int32_t* idx,
-                        float* sqd, float* xyz, int32_t* cnt, unsigned long long* cand);
+                        float* sqd, float* xyz, int32_t* cnt, unsigned long long* cand, uint2* work, unsigned* nwork);
 // The same search, every query finished on the device into the plane normal of its neighbourhood (flimo_map_normals, flimo_c.h):
 // mean and covariance of r = p - q in float64, a Jacobi eigen-decomposition, the orientation rule.  q == nullptr: query i is the
 // stored point first + i.  normal / cnt: [nq]; centroid [nq][3], cov [nq][6], eig [nq][6]: optional.  Scratch: mom ([nq][9], the

@@ -14,14 +14,17 @@
 // is FILTERED against the k-th key (a broadcast, a compare, a ballot): once the list is warm most batches have no survivor.  A
 // survivor is broadcast to its group, every lane compares it with its own key and the tail moves up by one lane (rank-and-shift).
 //
-// The search.  knnk_kernel<L> (L = 16 lanes per query for k <= 16, a wave beyond): blocks of rows around the query's cell as
+// The search has ONE text, two device functions, and one pair of kernels over a JOB that says where a query comes from and how its
+// list ends (kk_search_kernel<L, Job> / kk_walk_kernel<Job>, below): flimo_knn_k is the job that ends in knnk_store (KnnJob); the
+// normals, the outliers, FPFH, the keypoints, the scan's fitness and its normal equations are the others.
+// knnk_block_search<L> (L = 16 lanes per query for k <= 16, a wave beyond): blocks of rows around the query's cell as
 // knn_search does -- ring 1, then straight to the ring that proves exactness once k candidates (or the gate) bound the distance;
 // of a later block only the shell beyond the block already walked is read, so no point is met twice.  Rows and the cells of a row
 // are pruned by the smaller of the k-th distance and the gate.  A query is PROVEN when that bound is <= the distance to the nearest
-// cell face not visited (knn_search's margins), or the block covers the grid.  What would need more than KK_FAR_RING rings is left
-// to knnk_far_kernel: one wave per query, best-first over the directory's existing tiles, nearest first, until the next tile is
-// farther than the bound (knn_far_kernel's scheme with the distributed list): a query kilometres from every point costs a look at
-// the directory and the nearest tiles.  All pruning is conservative; the float32 key compare alone decides membership and order.
+// cell face not visited (knn_search's margins), or the block covers the grid.  What would need more than KK_FAR_RING rings goes to
+// a worklist and knnk_tile_walk: one wave per query, best-first over the directory's existing tiles, nearest first, until the next
+// tile is farther than the bound (knn_far_kernel's scheme with the distributed list): a query kilometres from every point costs a
+// look at the directory and the nearest tiles.  All pruning is conservative; the float32 key compare alone decides membership and order.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <string.h>
@@ -160,7 +163,7 @@ __device__ __forceinline__ void knnk_row(const GridView& G, const KnnkGeo& g, fl
 
 // lane sub < k writes slot sub of its query: entries below the gate's key are results, the rest padding
 template <int L>
-__device__ __forceinline__ void knnk_store(int lane, int q, int k, kk_u64 mine, kk_u64 gate_key, bool proven, bool live,
+__device__ __forceinline__ void knnk_store(int lane, int q, int k, kk_u64 mine, kk_u64 gate_key, bool live,
                                            const float4* __restrict__ map_raw, int32_t* __restrict__ idx, float* __restrict__ sqd,
                                            float* __restrict__ xyz, int32_t* __restrict__ cnt) {
   const int sub = lane & (L - 1);
@@ -174,164 +177,16 @@ __device__ __forceinline__ void knnk_store(int lane, int q, int k, kk_u64 mine, 
     sqd[at] = has ? kk_key_dist(mine) : 0.f;
     if (xyz) {
       float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (has && proven) p = map_raw[ins];
+      if (has) p = map_raw[ins];
       xyz[3 * at] = p.x; xyz[3 * at + 1] = p.y; xyz[3 * at + 2] = p.z;
     }
   }
-  if (live && sub == 0) cnt[q] = proven ? c : -c - 1;      // (negative: knnk_far_kernel finishes the query)
+  if (live && sub == 0) cnt[q] = c;
 }
 
-template <int L>
-__global__ __launch_bounds__(KK_BLOCK) void knnk_kernel(GridView G, const float* __restrict__ qxyz, int nq, int k, float r2, kk_u64 gate_key,
-                                                        const float4* __restrict__ map_raw, int32_t* __restrict__ idx, float* __restrict__ sqd,
-                                                        float* __restrict__ xyz, int32_t* __restrict__ cnt, unsigned long long* __restrict__ cand_out) {
-  const int lane = threadIdx.x & 63;
-  const int sub = lane & (L - 1);
-  const size_t gq = ((size_t)blockIdx.x * KK_BLOCK + threadIdx.x) / (unsigned)L;
-  const bool live = gq < (size_t)nq;
-  const int q = live ? (int)gq : 0;
-  const int maxdim = grid_maxdim(G);
-  float gx = 0.f, gy = 0.f, gz = 0.f;
-  if (live) { gx = qxyz[3 * q]; gy = qxyz[3 * q + 1]; gz = qxyz[3 * q + 2]; }
-  KnnkGeo g;
-  const bool valid = knnk_geo(G, maxdim, live ? gx : NAN, gy, gz, g);
-  const float edge = fminf(fminf(fminf(g.rx, 1.f - g.rx), fminf(g.ry, 1.f - g.ry)), fminf(g.rz, 1.f - g.rz));
-  kk_u64 mine = gate_key;
-  unsigned long long cand = 0;
-  bool done = !valid || gate_key == 0ull, proven = true;      // NaN query / a gate of 0: empty, and that is exact
-  // first ring that can reach the grid at all
-  int r_prev = -1, r = 1;
-  if (!done) {
-    const int ox_ = g.cx < 0 ? -g.cx : (g.cx >= G.nx ? g.cx - G.nx + 1 : 0);
-    const int oy_ = g.cy < 0 ? -g.cy : (g.cy >= G.ny ? g.cy - G.ny + 1 : 0);
-    const int oz_ = g.cz < 0 ? -g.cz : (g.cz >= G.nz ? g.cz - G.nz + 1 : 0);
-    r = max(1, max(ox_, max(oy_, oz_)));
-    if (r > KK_FAR_RING) { done = true; proven = false; }
-  }
-  float bound = r2;                          // min(gate, k-th distance so far) [m^2]: no point farther than it can enter the list
-  while (__any(!done)) {
-    // ---- the block of ring r, of which the block of ring r_prev has been walked: rows clipped to the grid; an inner row has a
-    //      part on either side of the old block (two jobs), an outer row is one job ----
-    const int y0 = max(g.cy - r, 0), y1 = min(g.cy + r, G.ny - 1), z0 = max(g.cz - r, 0), z1 = min(g.cz + r, G.nz - 1);
-    const int nyb = max(y1 - y0 + 1, 0), nzb = max(z1 - z0 + 1, 0);
-    const int sides = r_prev >= 0 ? 2 : 1;
-    const int njobs = done ? 0 : nyb * nzb * sides;
-    float bnd2 = kk_ball(G, bound);
-    for (int jb = 0; __any(jb < njobs); jb += L) {
-      const int j = jb + sub;
-      uint32_t lo = 0, len = 0;
-      if (j < njobs) {
-        const int row = sides == 2 ? j >> 1 : j, side = sides == 2 ? j & 1 : 0;
-        const int yy = y0 + row % nyb, zz = z0 + row / nyb;
-        const bool inner = r_prev >= 0 && abs(yy - g.cy) <= r_prev && abs(zz - g.cz) <= r_prev;
-        int x0 = g.cx - r, x1 = g.cx + r;
-        if (inner) { if (side == 0) x1 = g.cx - r_prev - 1; else x0 = g.cx + r_prev + 1; }
-        else if (side == 1) x1 = x0 - 1;
-        x0 = max(x0, 0); x1 = min(x1, G.nx - 1);
-        if (x0 <= x1) knnk_row(G, g, bnd2, yy, zz, x0, x1, lo, len);
-      }
-      knnk_round<L>(G, gx, gy, gz, lane, k, lo, len, mine, cand);
-      // the ball shrinks with the k-th best
-      const float dk = kk_key_dist(__shfl(mine, k - 1, L));
-      if (dk < bound) { bound = dk; bnd2 = kk_ball(G, bound); }
-    }
-    if (!done) {
-      // ---- exactness: every point not visited is at least rg away (knn_search) ----
-      const float rg = ((float)r + edge - g.margin) * G.cell;
-      const bool covers = (g.cx - r <= 0) && (g.cx + r >= G.nx - 1) && (g.cy - r <= 0) && (g.cy + r >= G.ny - 1) && (g.cz - r <= 0) &&
-                          (g.cz + r >= G.nz - 1);
-      if (covers || (rg > 0.f && bound <= rg * rg * (1.f - 1.0e-6f))) {
-        done = true;
-      } else {
-        // next ring: straight to the one that proves exactness once a bound is known, else double
-        int rn = 2 * r;
-        if (bound < 3.0e38f) {
-          const float need = fl_sqrt(bound) * G.inv_cell * (1.f + 4.0e-6f) - edge + g.margin;
-          rn = max(r + 1, (int)ceilf(fminf(need, 1.0e9f)));
-        }
-        if (rn > KK_FAR_RING) { done = true; proven = false; }
-        r_prev = r;
-        r = rn;
-      }
-    }
-  }
-  knnk_store<L>(lane, q, k, mine, gate_key, proven, live, map_raw, idx, sqd, xyz, cnt);
-  if (cand_out && live && sub == 0) cand_out[q] = cand;
-}
-
-// What knnk_kernel could not prove within KK_FAR_RING rings, ONE WAVE PER QUERY over the directory of tiles that exist: tiles in
-// ascending order of their box's distance to the query (a lower bound of the distance of every point inside) until the next tile
-// is farther than the bound -- the smaller of the gate and the k-th best -- or none is left.  The list starts afresh; when the
-// block search left k candidates, its k-th distance (an upper bound of the true one) is the first bound.
-__global__ __launch_bounds__(KK_BLOCK) void knnk_far_kernel(GridView G, const float* __restrict__ qxyz, int nq, int k, float r2, kk_u64 gate_key,
-                                                            const float4* __restrict__ map_raw, int32_t* __restrict__ idx, float* __restrict__ sqd,
-                                                            float* __restrict__ xyz, int32_t* __restrict__ cnt, unsigned long long* __restrict__ cand_out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int maxdim = grid_maxdim(G);
-  const int ndir = G.ntx * G.nty * G.ntz;
-  const int cells_per_xtile = max(1, (8 << G.ts) / G.xs);
-  for (int q = blockIdx.x * (KK_BLOCK / 64) + wave; q < nq; q += gridDim.x * (KK_BLOCK / 64)) {
-    const int c0 = cnt[q];
-    if (c0 >= 0) continue;                                       // proven by the block search (wave-uniform)
-    const float gx = qxyz[3 * q], gy = qxyz[3 * q + 1], gz = qxyz[3 * q + 2];
-    KnnkGeo g;
-    (void)knnk_geo(G, maxdim, gx, gy, gz, g);                    // (a NaN query never comes here)
-    float bound = r2;
-    if (-c0 - 1 == k) bound = fminf(bound, sqd[(size_t)q * k + (k - 1)]);
-    float bnd2 = kk_ball(G, bound);
-    kk_u64 mine = gate_key;
-    unsigned long long cand = 0;
-    float last_d = -1.f;
-    int last_i = -1;
-    for (;;) {
-      // ---- the nearest tile not visited yet: (distance, directory index) in ascending order ----
-      float best_d = INFINITY;
-      int best_i = INT_MAX;
-      for (int i = lane; i < ndir; i += 64) {
-        if (G.dir[i] == 0) continue;
-        const int tx = i % G.ntx, tyz = i / G.ntx, ty_ = tyz % G.nty, tz_ = tyz / G.nty;
-        const float x0 = (float)(tx * cells_per_xtile), x1 = (float)((tx + 1) * cells_per_xtile);
-        const float y0 = (float)((ty_ << G.ty) - GRID_PAD), y1 = (float)(((ty_ + 1) << G.ty) - GRID_PAD);
-        const float z0 = (float)((tz_ << G.tz) - GRID_PAD), z1 = (float)(((tz_ + 1) << G.tz) - GRID_PAD);
-        const float ax = fmaxf(fmaxf(x0 - g.qcx, g.qcx - x1) - g.margin, 0.f), ay = fmaxf(fmaxf(y0 - g.qcy, g.qcy - y1) - g.margin, 0.f),
-                    az = fmaxf(fmaxf(z0 - g.qcz, g.qcz - z1) - g.margin, 0.f);
-        const float d = (ax * ax + ay * ay + az * az) * (1.f - 1.0e-6f);
-        const bool after = d > last_d || (d == last_d && i > last_i);
-        if (after && (d < best_d || (d == best_d && i < best_i))) { best_d = d; best_i = i; }
-      }
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const float od = __shfl_xor(best_d, o, 64);
-        const int oi = __shfl_xor(best_i, o, 64);
-        if (od < best_d || (od == best_d && oi < best_i)) { best_d = od; best_i = oi; }
-      }
-      if (best_i == INT_MAX) break;                              // every tile has been visited
-      if (best_d > bnd2) break;                                  // no point of it -- or of any later one -- lies within the bound
-      last_d = best_d; last_i = best_i;
-      // ---- its rows, one per lane and round ----
-      const int tx = best_i % G.ntx, tyz = best_i / G.ntx, ty_ = tyz % G.nty, tz_ = tyz / G.nty;
-      const int xt0 = tx * cells_per_xtile, xt1 = min((tx + 1) * cells_per_xtile, G.nx) - 1;
-      const int nrows = 1 << (G.ty + G.tz);
-      for (int jb = 0; jb < nrows; jb += 64) {
-        const int j = jb + lane;
-        const int yy = (ty_ << G.ty) + (j & ((1 << G.ty) - 1)) - GRID_PAD, zz = (tz_ << G.tz) + (j >> G.ty) - GRID_PAD;
-        uint32_t lo = 0, len = 0;
-        if (j < nrows && yy >= 0 && yy < G.ny && zz >= 0 && zz < G.nz && xt0 <= xt1) knnk_row(G, g, bnd2, yy, zz, xt0, xt1, lo, len);
-        if (!__any(len != 0u)) continue;
-        knnk_round<64>(G, gx, gy, gz, lane, k, lo, len, mine, cand);
-        const float dk = kk_key_dist(__shfl(mine, k - 1, 64));
-        if (dk < bound) { bound = dk; bnd2 = kk_ball(G, bound); }
-      }
-    }
-    knnk_store<64>(lane, q, k, mine, gate_key, true, true, map_raw, idx, sqd, xyz, cnt);
-    if (cand_out && lane == 0) cand_out[q] += cand;
-  }
-}
-
-// ---- the two searches once more as device functions, for kk_search_kernel / kk_walk_kernel, which end a query as their job says
-//      (below).  knnk_kernel and knnk_far_kernel above stay as they are; the text is the same, statement for statement.  Calling
-//      these from them gives knnk_kernel<16> and knnk_far_kernel 100 VGPRs each (92 and 91 now): four waves per SIMD instead of
-//      five.  __launch_bounds__(KK_BLOCK, 5) on top brings both to 96 VGPRs, with 16 and 12 bytes of scratch per lane. ----
+// ---- the search: the only copy of its text, run by kk_search_kernel / kk_walk_kernel (below), which end a query as their job
+//      says -- flimo_knn_k's in knnk_store.  `cand` counts the points met, for the developer's flimo_knn_k_candidates; every
+//      other job lets it die. ----
 // The block search of one query by the L lanes of its group (every lane of the wave calls it; a group without a query passes
 // live = false): `mine` ends as this lane's entry of the k-best list.  Returns whether the list is proven exact; if not, the tiles'
 // walk (knnk_tile_walk) has to finish the query.
@@ -455,7 +310,7 @@ __device__ __forceinline__ void knnk_tile_walk(const GridView& G, int maxdim, in
   }
 }
 
-// ---- the search for kernels that end a query otherwise than knnk_store: one pair of kernels over a JOB, passed by value ----------
+// ---- one pair of kernels over a JOB, passed by value ---------------------------------------------------------------------------
 // A job numbers its queries by SLOTS and says where they come from and how they end:
 //   slot<L>(at, x, y, z)   the slot of this lane's group and its query; returns whether there is one (if not: slot 0, no query)
 //   total()          the number of slots: the walk clamps a worklist entry by it
@@ -464,9 +319,15 @@ __device__ __forceinline__ void knnk_tile_walk(const GridView& G, int maxdim, in
 //   finish<L>(lane, at, live, mine, gx, gy, gz)      the end of a query whose list is exact, by the L lanes that hold it; every lane
 //                    of the wave calls it, live = false for a group without a query or with one the walk has yet to finish
 //   LANES            lanes per query, 0: knnk_plan(k);  PAIRS: the slots are (pose, scan point) pairs (KkPairs below)
-// kk_search_kernel is knnk_kernel's search with that end.  A query the block search cannot prove goes to the worklist (its slot,
-// its first bound: the list's k-th distance, when there is one, bounds the true one) by one atomicAdd of its leading lane on
-// `nwork`; kk_walk_kernel, one wave per entry, runs knnk_far_kernel's walk and the same end.
+//   COUNT, cand      optional (KkCounts): the job keeps the number of points its queries met, cand[slot]
+// kk_search_kernel is the block search with that end.  A query it cannot prove goes to the worklist (its slot, its first bound:
+// the list's k-th distance, when there is one, bounds the true one) by one atomicAdd of its leading lane on `nwork`, and nothing
+// of it is written yet; kk_walk_kernel, one wave per entry, runs the walk over the tiles and the same end.
+template <class Job, class = void>
+struct KkCounts { static constexpr bool value = false; };
+template <class Job>
+struct KkCounts<Job, std::void_t<decltype(Job::COUNT)>> { static constexpr bool value = Job::COUNT; };
+
 template <int L>
 __device__ __forceinline__ bool kk_flat_slot(int nq, size_t& at) {      // slots 0 .. nq - 1, KK_BLOCK / L of them per workgroup
   const size_t gq = ((size_t)blockIdx.x * KK_BLOCK + threadIdx.x) / (unsigned)L;
@@ -493,6 +354,9 @@ __global__ __launch_bounds__(KK_BLOCK) void kk_search_kernel(GridView G, Job J, 
     }
   }
   J.template finish<L>(lane, at, live && proven, mine, gx, gy, gz);
+  if constexpr (KkCounts<Job>::value) {
+    if (live && sub == 0) J.cand[at] = cand;      // (proven or not: the walk adds its part)
+  }
 }
 
 // (waves per SIMD the walk's register budget is cut for: 5 unless a job whose end needs more registers than that leaves asks for fewer)
@@ -518,8 +382,60 @@ __global__ __launch_bounds__(KK_BLOCK, KkWalkWaves<Job>::value) void kk_walk_ker
     unsigned long long cand = 0;
     knnk_tile_walk(G, maxdim, ndir, cells_per_xtile, gx, gy, gz, lane, J.k, __uint_as_float(e.y), J.gate_key, mine, cand);
     J.template finish<64>(lane, at, true, mine, gx, gy, gz);
+    if constexpr (KkCounts<Job>::value) {
+      if (lane == 0) J.cand[at] += cand;
+    }
   }
 }
+
+// ---- flimo_knn_k: packed queries, the list ended in the caller's arrays (knnk_store) -------------------------------------------
+// COUNT: the developer's counter of the points met (flimo_knn_k_candidates).  It is live through the whole search and costs the
+// 16-lane search a wave of occupancy (profiles/knn_k/README.md), so the production call does not instantiate it.
+template <bool COUNT_>
+struct KnnJob {
+  static constexpr int LANES = 0;
+  static constexpr bool PAIRS = false;
+  static constexpr bool COUNT = COUNT_;
+  const float* qxyz;     // [nq][3]
+  int nq, k;
+  float r2;
+  kk_u64 gate_key;
+  const float4* map_raw;
+  int32_t* idx;          // [nq][k]
+  float* sqd;            // [nq][k]
+  float* xyz;            // [nq][k][3] or null
+  int32_t* cnt;          // [nq]
+  unsigned long long* cand;      // [nq] (COUNT)
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
+    const bool live = kk_flat_slot<L>(nq, at);
+    if (live) query(at, x, y, z);
+    return live;
+  }
+  __host__ __device__ size_t total() const { return (size_t)nq; }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { x = qxyz[3 * at]; y = qxyz[3 * at + 1]; z = qxyz[3 * at + 2]; }
+  template <int L>
+  __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float, float, float) const {
+    knnk_store<L>(lane, (int)at, k, mine, gate_key, live, map_raw, idx, sqd, xyz, cnt);
+  }
+};
+
+// the stored points of a chunk as slots: query i is stored point first + i (the base of the jobs over stored points)
+struct KkStored {
+  unsigned first;
+  int nq, k;             // queries of the chunk; the list's length
+  float r2;
+  kk_u64 gate_key;
+  const float4* map_raw;
+  template <int L>
+  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
+    const bool live = kk_flat_slot<L>(nq, at);
+    if (live) query(at, x, y, z);
+    return live;
+  }
+  __host__ __device__ size_t total() const { return (size_t)nq; }
+  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
+};
 
 // ---- normals and covariances of the k-NN neighbourhoods (flimo_map_normals) ---------------------------------------------------
 // The same search; instead of knnk_store the group finishes its query in registers.  Lane `sub` holds slot sub of the list; it
@@ -973,24 +889,11 @@ __device__ __forceinline__ void knnk_mean_dist(unsigned first, int k1, kk_u64 ga
 }
 
 // the stored points of a chunk, ended in their mean neighbour distance
-struct OutlierJob {
+struct OutlierJob : KkStored {      // (k: the neighbours asked for + 1)
   static constexpr int LANES = 0;
   static constexpr bool PAIRS = false;
-  unsigned first;        // query i is stored point first + i
-  int nq, k;             // queries of the chunk; the list's length: the neighbours asked for + 1
-  float r2;
-  kk_u64 gate_key;
-  const float4* map_raw;
   double* mean;
   int32_t* cnt;
-  template <int L>
-  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
-    const bool live = kk_flat_slot<L>(nq, at);
-    if (live) query(at, x, y, z);
-    return live;
-  }
-  __host__ __device__ size_t total() const { return (size_t)nq; }
-  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
   template <int L>
   __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float, float, float) const {
     knnk_mean_dist<L>(first, k, gate_key, lane, (int)at, live, mine, mean, cnt);
@@ -1131,26 +1034,13 @@ __device__ __forceinline__ void knnk_spfh(unsigned first, int k, kk_u64 gate_key
 }
 
 // the stored points of a chunk, ended in their SPFH row and the length of their list (both arrays are the whole map's)
-struct SpfhJob {
+struct SpfhJob : KkStored {
   static constexpr int LANES = 0;
   static constexpr bool PAIRS = false;
   static constexpr int WALK_WAVES = 4;      // (the pair's float64 frame and atan2: 132 B a lane spilled at 5)
-  unsigned first;        // query i is stored point first + i
-  int nq, k;
-  float r2;
-  kk_u64 gate_key;
-  const float4* map_raw;
   const float4* normals; // [map size]: nx ny nz curvature, NaN where there is no plane
   unsigned char* spfh;   // [map size][FPFH_DIM]
   unsigned char* len;    // [map size]
-  template <int L>
-  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
-    const bool live = kk_flat_slot<L>(nq, at);
-    if (live) query(at, x, y, z);
-    return live;
-  }
-  __host__ __device__ size_t total() const { return (size_t)nq; }
-  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
   template <int L>
   __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float gx, float gy, float gz) const {
     knnk_spfh<L>(first, k, gate_key, lane, at, live, mine, gx, gy, gz, map_raw, normals, spfh, len);
@@ -1192,26 +1082,13 @@ __device__ __forceinline__ void knnk_fpfh(int k, kk_u64 gate_key, int lane, size
 }
 
 // the stored points of a chunk of the range, ended in their FPFH row (the chunk's) from the rows of SpfhJob (the whole map's)
-struct FpfhJob {
+struct FpfhJob : KkStored {
   static constexpr int LANES = 0;
   static constexpr bool PAIRS = false;
-  unsigned first;
-  int nq, k;
-  float r2;
-  kk_u64 gate_key;
-  const float4* map_raw;
   const unsigned char* spfh;
   const unsigned char* len;
   float* fpfh;           // [nq][FPFH_DIM]
   int32_t* cnt;          // [nq]
-  template <int L>
-  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
-    const bool live = kk_flat_slot<L>(nq, at);
-    if (live) query(at, x, y, z);
-    return live;
-  }
-  __host__ __device__ size_t total() const { return (size_t)nq; }
-  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
   template <int L>
   __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float, float, float) const {
     knnk_fpfh<L>(k, gate_key, lane, at, live, mine, spfh, len, fpfh, cnt);
@@ -1271,25 +1148,12 @@ __device__ __forceinline__ void knnk_iss(unsigned first, int k, kk_u64 gate_key,
 }
 
 // the stored points of a chunk of the range, ended in their mask byte (the chunk's) from the saliency of the whole map
-struct IssJob {
+struct IssJob : KkStored {
   static constexpr int LANES = 0;
   static constexpr bool PAIRS = false;
-  unsigned first;        // query i is stored point first + i
-  int nq, k;
-  float r2;
-  kk_u64 gate_key;
-  const float4* map_raw;
   const double* sal;     // [map size]
   unsigned char* mask;   // [nq]
   unsigned* count;       // the keypoints so far
-  template <int L>
-  __device__ bool slot(size_t& at, float& x, float& y, float& z) const {
-    const bool live = kk_flat_slot<L>(nq, at);
-    if (live) query(at, x, y, z);
-    return live;
-  }
-  __host__ __device__ size_t total() const { return (size_t)nq; }
-  __device__ void query(size_t at, float& x, float& y, float& z) const { const float4 p = map_raw[(size_t)first + at]; x = p.x; y = p.y; z = p.z; }
   template <int L>
   __device__ void finish(int lane, size_t at, bool live, kk_u64 mine, float, float, float) const {
     knnk_iss<L>(first, k, gate_key, lane, at, live, mine, sal, mask, count);
@@ -1330,23 +1194,31 @@ static hipError_t kk_launch(hipStream_t st, const GridView& G, const Job& J, uin
   else kk_launch_search<64>(st, G, J, work, nwork);
   const unsigned walk_blocks = (unsigned)std::min<size_t>(4096, (J.total() + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
   hipLaunchKernelGGL(kk_walk_kernel<Job>, dim3(walk_blocks), dim3(KK_BLOCK), 0, st, G, J, work, nwork);
-  return hipSuccess;
+  return hipGetLastError();
+}
+// the fields every job over a chunk of flat slots has: the chunk, the list's length, the gate, the stored points
+template <class Job>
+static void kk_fill(Job& J, unsigned first, int nq, int k, float max_dist, const float4* map_raw) {
+  J.first = first; J.nq = nq; J.k = k;
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.map_raw = map_raw;
 }
 
+template <bool COUNT>
+static hipError_t knn_k_launch(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, int nq, int k, float max_dist, int32_t* idx,
+                               float* sqd, float* xyz, int32_t* cnt, unsigned long long* cand, uint2* work, unsigned* nwork) {
+  KnnJob<COUNT> J;
+  J.qxyz = q; J.nq = nq; J.k = k;
+  kk_gate(max_dist, J.r2, J.gate_key);
+  J.map_raw = map_raw; J.idx = idx; J.sqd = sqd; J.xyz = xyz; J.cnt = cnt; J.cand = cand;
+  return kk_launch(st, G, J, work, nwork);
+}
 hipError_t launch_knn_k(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, int nq, int k, float max_dist, int32_t* idx,
-                        float* sqd, float* xyz, int32_t* cnt, unsigned long long* cand) {
+                        float* sqd, float* xyz, int32_t* cnt, unsigned long long* cand, uint2* work, unsigned* nwork) {
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
-  float r2;
-  kk_u64 gate_key;
-  kk_gate(max_dist, r2, gate_key);
-  const int L = knnk_plan(k);
-  const unsigned blocks = (unsigned)(((size_t)nq * L + KK_BLOCK - 1) / KK_BLOCK);
-  if (L == 16) hipLaunchKernelGGL((knnk_kernel<16>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, q, nq, k, r2, gate_key, map_raw, idx, sqd, xyz, cnt, cand);
-  else hipLaunchKernelGGL((knnk_kernel<64>), dim3(blocks), dim3(KK_BLOCK), 0, st, G, q, nq, k, r2, gate_key, map_raw, idx, sqd, xyz, cnt, cand);
-  const unsigned far_blocks = (unsigned)std::min<size_t>(4096, ((size_t)nq + KK_BLOCK / 64 - 1) / (KK_BLOCK / 64));
-  hipLaunchKernelGGL(knnk_far_kernel, dim3(far_blocks), dim3(KK_BLOCK), 0, st, G, q, nq, k, r2, gate_key, map_raw, idx, sqd, xyz, cnt, cand);
-  return hipGetLastError();
+  return cand ? knn_k_launch<true>(st, G, map_raw, q, nq, k, max_dist, idx, sqd, xyz, cnt, cand, work, nwork)
+              : knn_k_launch<false>(st, G, map_raw, q, nq, k, max_dist, idx, sqd, xyz, cnt, cand, work, nwork);
 }
 
 hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4* map_raw, const float* q, unsigned first, int nq, int k,
@@ -1355,11 +1227,11 @@ hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4*
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
   NormalsJob J;
-  J.qxyz = q; J.first = first; J.nq = nq; J.k = k; J.need = std::max(3, min_pts);
-  kk_gate(max_dist, J.r2, J.gate_key);
+  kk_fill(J, first, nq, k, max_dist, map_raw);
+  J.qxyz = q; J.need = std::max(3, min_pts);
   J.has_vp = viewpoint != nullptr;
   J.vx = viewpoint ? viewpoint[0] : 0.f; J.vy = viewpoint ? viewpoint[1] : 0.f; J.vz = viewpoint ? viewpoint[2] : 0.f;
-  J.map_raw = map_raw; J.cnt = cnt; J.mom = mom;
+  J.cnt = cnt; J.mom = mom;
   const NormalsOut O{normal, cnt, centroid, cov, eig};
   const hipError_t e = kk_launch(st, G, J, work, nwork);
   if (e != hipSuccess) return e;
@@ -1372,11 +1244,9 @@ hipError_t launch_outlier_search(hipStream_t st, const GridView& G, const float4
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k + 1 > KNNK_MAX_K) return hipErrorInvalidValue;
   OutlierJob J;
-  J.first = first; J.nq = nq; J.k = k + 1;
-  kk_gate(max_dist, J.r2, J.gate_key);
-  J.map_raw = map_raw; J.mean = mean; J.cnt = cnt;
-  const hipError_t e = kk_launch(st, G, J, work, nwork);
-  return e != hipSuccess ? e : hipGetLastError();
+  kk_fill(J, first, nq, k + 1, max_dist, map_raw);
+  J.mean = mean; J.cnt = cnt;
+  return kk_launch(st, G, J, work, nwork);
 }
 
 hipError_t launch_fpfh_spfh(hipStream_t st, const GridView& G, const float4* map_raw, const float4* normals, unsigned first, int nq, int k,
@@ -1384,11 +1254,9 @@ hipError_t launch_fpfh_spfh(hipStream_t st, const GridView& G, const float4* map
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
   SpfhJob J;
-  J.first = first; J.nq = nq; J.k = k;
-  kk_gate(max_dist, J.r2, J.gate_key);
-  J.map_raw = map_raw; J.normals = normals; J.spfh = spfh; J.len = len;
-  const hipError_t e = kk_launch(st, G, J, work, nwork);
-  return e != hipSuccess ? e : hipGetLastError();
+  kk_fill(J, first, nq, k, max_dist, map_raw);
+  J.normals = normals; J.spfh = spfh; J.len = len;
+  return kk_launch(st, G, J, work, nwork);
 }
 
 hipError_t launch_fpfh_sum(hipStream_t st, const GridView& G, const float4* map_raw, const unsigned char* spfh, const unsigned char* len,
@@ -1396,11 +1264,9 @@ hipError_t launch_fpfh_sum(hipStream_t st, const GridView& G, const float4* map_
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
   FpfhJob J;
-  J.first = first; J.nq = nq; J.k = k;
-  kk_gate(max_dist, J.r2, J.gate_key);
-  J.map_raw = map_raw; J.spfh = spfh; J.len = len; J.fpfh = fpfh; J.cnt = cnt;
-  const hipError_t e = kk_launch(st, G, J, work, nwork);
-  return e != hipSuccess ? e : hipGetLastError();
+  kk_fill(J, first, nq, k, max_dist, map_raw);
+  J.spfh = spfh; J.len = len; J.fpfh = fpfh; J.cnt = cnt;
+  return kk_launch(st, G, J, work, nwork);
 }
 
 hipError_t launch_iss_saliency(hipStream_t st, const GridView& G, const float4* map_raw, unsigned first, int nq, int k, float max_dist, int min_pts,
@@ -1409,10 +1275,10 @@ hipError_t launch_iss_saliency(hipStream_t st, const GridView& G, const float4* 
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
   NormalsJob J;
-  J.qxyz = nullptr; J.first = first; J.nq = nq; J.k = k; J.need = std::max(3, min_pts);
-  kk_gate(max_dist, J.r2, J.gate_key);
+  kk_fill(J, first, nq, k, max_dist, map_raw);
+  J.qxyz = nullptr; J.need = std::max(3, min_pts);
   J.has_vp = 0; J.vx = J.vy = J.vz = 0.f;
-  J.map_raw = map_raw; J.cnt = cnt; J.mom = mom;
+  J.cnt = cnt; J.mom = mom;
   const hipError_t e = kk_launch(st, G, J, work, nwork);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(iss_saliency_kernel, dim3((unsigned)(((size_t)nq + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, first, nq, J.need,
@@ -1425,11 +1291,9 @@ hipError_t launch_iss_suppress(hipStream_t st, const GridView& G, const float4* 
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
   IssJob J;
-  J.first = first; J.nq = nq; J.k = k;
-  kk_gate(max_dist, J.r2, J.gate_key);
-  J.map_raw = map_raw; J.sal = sal; J.mask = mask; J.count = count;
-  const hipError_t e = kk_launch(st, G, J, work, nwork);
-  return e != hipSuccess ? e : hipGetLastError();
+  kk_fill(J, first, nq, k, max_dist, map_raw);
+  J.sal = sal; J.mask = mask; J.count = count;
+  return kk_launch(st, G, J, work, nwork);
 }
 
 unsigned outlier_segments(size_t n) { return (unsigned)((n + OUT_SEG - 1) / OUT_SEG); }

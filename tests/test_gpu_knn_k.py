@@ -434,3 +434,59 @@ def test_through_the_localizer_and_invisible_to_registration(built):
     for j, (a, b) in enumerate(zip(plain, with_search)):
         assert a[2] == b[2] and a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes(), j
     assert plain[0][2] > 1000
+
+
+# 11
+def test_a_worklist_longer_than_the_walks_grid(built):
+    """20 001 queries of which 18 000 lie 50 - 500 m outside a 2 m box of about 300 points: every one of those is left to the walk
+    over the tiles, more entries than its 4096 x 4 waves, so its grid stride runs; near queries and a NaN one lie between them,
+    and 20 001 is a multiple of neither 4 nor 16.  Every query is compared; the candidate counter is a function of the query alone."""
+    from fast_limo_amd import _lib
+    rs = np.random.RandomState(21)
+    centre = np.float32([10.0, -5.0, 3.0])
+    ctx = _lib.HipCtx(0)
+    try:
+        ctx.map_config(downsample=False)
+        ctx.map_add((rs.uniform(-1.0, 1.0, (300, 3)) + centre).astype(np.float32))
+        mp = ctx.map_points()
+        assert mp.shape[0] == 300
+        nq = 20001
+        d = rs.normal(0, 1, (nq, 3))
+        d /= np.linalg.norm(d, axis=1)[:, None]
+        q = (centre + d * rs.uniform(50.0, 500.0, (nq, 1))).astype(np.float32)
+        near = np.arange(0, nq, 10)                                               # every tenth query lies inside the box
+        q[near] = (rs.uniform(-1.0, 1.0, (near.size, 3)) + centre).astype(np.float32)
+        nan_at = int(near[near.size // 2])
+        q[nan_at] = np.float32([np.nan, 0.0, 0.0])
+        far = np.setdiff1d(np.arange(nq), near)
+        assert far.size == 18000 > 4096 * 4 and nq % 4 and nq % 16
+        dist = np.linalg.norm(q.astype(np.float64) - centre, axis=1)
+        assert dist[far].min() > 49.0 and np.nanmax(dist[near]) < 1.8
+        chosen = np.concatenate([far[:21], far[-21:], near[:10], near[-11:], [nan_at]])
+        assert chosen.size == 64
+        for max_dist in (INF, 0.6, 120.0):                                        # 0.6 m cuts near lists short, 120 m the far ones
+            bidx, bsqd, bcnt = brute_knn(q, mp, 64, max_dist, chunk=2048)         # the k-list is the first k of the 64-list
+            if max_dist == 0.6:
+                assert np.any((bcnt[near] > 0) & (bcnt[near] < 16)) and 17 < bcnt[near].max() < 64 and np.all(bcnt[far] == 0)
+            elif max_dist == 120.0:
+                assert np.any(bcnt[far] == 0) and np.any((bcnt[far] > 0) & (bcnt[far] < 64)) and np.any(bcnt[far] == 64)
+            else:
+                assert np.all(np.delete(bcnt, nan_at) == 64)
+            assert bcnt[nan_at] == 0
+            for k in (3, 16, 17, 64):
+                msg = f"worklist: k = {k}, max_dist = {max_dist}"
+                idx, sqd, cnt, xyz = ctx.knn_k(q, k, max_dist, want_xyz=True)
+                np.testing.assert_array_equal(cnt, np.minimum(bcnt, k), err_msg=msg + " (cnt)")
+                np.testing.assert_array_equal(bits(sqd), bits(bsqd[:, :k]), err_msg=msg + " (distance bits)")
+                np.testing.assert_array_equal(idx, bidx[:, :k], err_msg=msg + " (idx)")
+                pad = idx < 0
+                assert np.all(pad == (np.arange(k)[None, :] >= cnt[:, None])), msg
+                np.testing.assert_array_equal(xyz[~pad], mp[idx[~pad]], err_msg=msg + " (xyz)")
+                assert np.all(xyz[pad] == 0) and np.all(sqd[pad] == 0), msg
+                cand = ctx.knn_k_candidates(q, k, max_dist)
+                np.testing.assert_array_equal(ctx.knn_k_candidates(q, k, max_dist), cand, err_msg=msg + " (cand, second call)")
+                alone = np.concatenate([ctx.knn_k_candidates(q[i:i + 1], k, max_dist) for i in chosen])
+                np.testing.assert_array_equal(cand[chosen], alone, err_msg=msg + " (cand, each query alone)")
+                assert np.all(cand >= cnt.astype(np.uint64)), msg
+    finally:
+        ctx.close()
