@@ -677,10 +677,60 @@ static int map_append_host(flimo_ctx* c, const float4* pts, size_t n) {
   return FLIMO_OK;
 }
 
+// Octree::clear() as the removal entries and the zero-size root need it: stored points, book (with the nodes of what is
+// forgotten) and index tables go; the time of the last insert and the second level's centre stay (nothing was inserted, the
+// sensor is where it was).  Everything a pass kept that names map positions goes with them.
+static int map_forget_all(flimo_ctx* c) {
+  HIPCHK(c, c->gbook.finish(c->stream, c->scratch));
+  const double last_time = c->map_last_time;
+  const bool had_center = c->have_fine_center;
+  (void)flimo_map_clear(c);
+  c->map_last_time = last_time;
+  c->have_fine_center = had_center;
+  c->gbook.release();
+  index_free(c->idx);
+  index_free(c->fine_idx);
+  (void)hipFree(c->d_crowd_bits);
+  c->d_crowd_bits = nullptr; c->crowd_bits_cap = 0;
+  c->crowd_cells.clear(); c->crowd_listed = 0;
+  c->last_nq = 0; c->recs_valid = c->dbg_valid = false;      // the last pass's records name positions of the old arrays
+  return FLIMO_OK;
+}
+
+static int map_add_device(flimo_ctx* c, const float4* d_pts, size_t m, double stamp, const float* known_bb = nullptr);
+
+// The zero-size root: every stored point lies at one location, so the root cube has half edge 0 and doubling never
+// makes it hold a batch that lies elsewhere (the reference never returns from that loop).  This project takes such a batch as
+// initialize(stored points followed by the batch's finite points): clear(), then the first batch's path over both.
+// (bb: box of the batch's finite points)
+static int map_add_to_zero_root(flimo_ctx* c, const float4* d_pts, size_t m, double stamp, const float bb[6]) {
+  const size_t n_old = c->map_n;
+  float ubb[6];
+  for (int a = 0; a < 3; a++) {
+    const float at = c->gbook.root_c[a];
+    ubb[a] = bb[a] < at ? bb[a] : at;
+    ubb[3 + a] = bb[3 + a] > at ? bb[3 + a] : at;
+  }
+  GBook fresh;                                          // what an empty book says to the union's box, before anything goes
+  if (fresh.admit(ubb, c->map_cfg.min_extent) != GBook::ADMIT_OK)
+    return fail(c, FLIMO_ERR_UNSUPPORTED, "octree too deep: the root cube this batch needs is more than %d halvings above 2 * min_extent (%g)",
+                GB_MAX_DEPTH, (double)c->map_cfg.min_extent);
+  struct Tmp { float4* p = nullptr; ~Tmp() { (void)hipFree(p); } } both;
+  HIPCHK(c, hipMalloc(&both.p, (n_old + m) * sizeof(float4)));
+  HIPCHK(c, hipMemcpyAsync(both.p, c->d_map_raw, n_old * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(both.p + n_old, d_pts, m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc = map_forget_all(c);
+  if (rc) return rc;
+  rc = map_add_device(c, both.p, n_old + m, stamp, ubb);
+  c->gbook.release_batch_scratch();
+  return rc;
+}
+
 // Octree::update for a batch that already lives on the device (m points, NaNs allowed): the device
 // book decides keep / drop, the kept points are appended in batch order, the grid is rebuilt.
 // (known_bb: the exact box of the batch's finite points when the caller has it already -- a crop's compaction leaves it)
-static int map_add_device(flimo_ctx* c, const float4* d_pts, size_t m, double stamp, const float* known_bb = nullptr) {
+static int map_add_device(flimo_ctx* c, const float4* d_pts, size_t m, double stamp, const float* known_bb) {
   if (m == 0) return FLIMO_OK;
   if (c->map_n + m > 0x7fff0000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "map would exceed 2^31 points");
   static const bool prof = getenv("FLIMO_PROF_INSERT") != nullptr;     // developer timing of the insert stages
@@ -693,6 +743,16 @@ static int map_add_device(flimo_ctx* c, const float4* d_pts, size_t m, double st
   const double t1 = prof ? now() : 0.0;
   double t2 = t1, t3 = t1;
   if (any) {
+    // the book's answer from its host mirror, before map, index or book change
+    switch (c->gbook.admit(bb, c->map_cfg.min_extent)) {
+      case GBook::ADMIT_OK: break;
+      case GBook::ADMIT_ZERO_ROOT: return map_add_to_zero_root(c, d_pts, m, stamp, bb);
+      case GBook::ADMIT_TOO_DEEP:
+        return fail(c, FLIMO_ERR_UNSUPPORTED, "octree too deep: the root cube this batch needs is more than %d halvings above 2 * min_extent (%g)",
+                    GB_MAX_DEPTH, (double)c->map_cfg.min_extent);
+      case GBook::ADMIT_GROWTH:
+        return fail(c, FLIMO_ERR_UNSUPPORTED, "octree root would have to double more than %d times to hold this batch", kMaxRootDoublings);
+    }
     const size_t old_cap = c->map_cap;
     int rc = ensure_dev(c, c->d_map_raw, c->map_cap, c->map_n + m, true, c->map_n);
     if (rc) return rc;
@@ -783,25 +843,18 @@ static int map_keep_only(flimo_ctx* c, const float4* kept_pts, size_t kept, size
   if (kept > n_old) return fail(c, FLIMO_ERR_HIP, "%s: compaction reported %zu of %zu points", what, kept, n_old);
   if (kept == n_old) return FLIMO_OK;
   // ---- clear() ... ----
-  HIPCHK(c, c->gbook.finish(c->stream, c->scratch));
-  const double last_time = c->map_last_time;
+  const double last_time = c->map_last_time;         // (a crop is no insert)
   const bool had_center = c->have_fine_center;
-  (void)flimo_map_clear(c);
-  c->map_last_time = last_time;                      // (a crop is no insert)
-  c->gbook.release();                                // the nodes of the forgotten regions go with the rest
-  index_free(c->idx);
-  index_free(c->fine_idx);
-  (void)hipFree(c->d_crowd_bits);
-  c->d_crowd_bits = nullptr; c->crowd_bits_cap = 0;
-  c->crowd_cells.clear(); c->crowd_listed = 0;
-  c->last_nq = 0; c->recs_valid = c->dbg_valid = false;      // the last pass's records name positions of the old arrays
+  int rc = map_forget_all(c);
+  if (rc) return rc;
+  c->have_fine_center = false;
   (*calls)++;
   *points += n_old - kept;
   if (removed) *removed = n_old - kept;
   if (kept == 0) return FLIMO_OK;
   // ---- ... + initialize(kept) ----
   c->have_fine_center = had_center;                  // (the sensor is where it was: the second level stays around it)
-  const int rc = map_add_device(c, kept_pts, kept, last_time, bb);
+  rc = map_add_device(c, kept_pts, kept, last_time, bb);
   c->gbook.release_batch_scratch();
   if (rc) return rc;
   if (c->map_n != kept) return fail(c, FLIMO_ERR_HIP, "%s: %zu of the %zu kept points were stored", what, c->map_n, kept);
@@ -2735,7 +2788,10 @@ extern "C" int flimo_insert_rule_replay(float min_extent, int downsample, const 
   insert_book_config(b, min_extent, downsample != 0);
   size_t off = 0;
   for (size_t k = 0; k < n_batches; k++) {
-    insert_book_update(b, xyz + 3 * off, batch_sizes[k], keep + off);
+    if (!insert_book_update(b, xyz + 3 * off, batch_sizes[k], keep + off)) {
+      insert_book_destroy(b);
+      return FLIMO_ERR_TOO_LARGE;          // the root would have to double more than kMaxRootDoublings times
+    }
     off += batch_sizes[k];
   }
   if (stored) *stored = insert_book_size(b);

@@ -5,10 +5,15 @@
 #include <stdint.h>
 #include <vector>
 #include "flimo_kernels.h"
+#include "flimo_insert.h"
 
 namespace flimo {
 
 struct GbItem;
+
+// Deepest chain of splits the subtree builds are sized for (the stack of gb_build_kernel, flimo_gbook.hip): a batch whose root
+// cube would take more halvings than this to reach 2 * min_extent is refused by GBook::admit before anything changes.
+constexpr int GB_MAX_DEPTH = 48;
 
 struct GBook {
   bool active = false;
@@ -47,6 +52,16 @@ struct GBook {
   bool counters_dirty = false;   // an update() that did not reach its trailing mail (an error return) left them non-zero: the next one clears them
   int last_items = 0;
 
+  // Before a batch changes anything: what would it meet?  (bb: box of its finite points; min_half_next: the minimum extent a
+  // first batch would be built with)
+  enum Admit {
+    ADMIT_OK,
+    ADMIT_ZERO_ROOT,   // the root has size zero (every stored point at one location) and the batch leaves that location: the caller
+                       // takes it as initialize(stored points followed by the batch), DESIGN.md "The zero-size root"
+    ADMIT_TOO_DEEP,    // the root as the batch leaves it is more than GB_MAX_DEPTH halvings above 2 * min_extent
+    ADMIT_GROWTH       // the root would have to double more than kMaxRootDoublings times (flimo_insert.h)
+  };
+  Admit admit(const float bb[6], float min_half_next) const;
   // take over a tree built on the host for the first batch
   hipError_t import_host(hipStream_t st, const std::vector<float>& c4, const std::vector<int>& child, const std::vector<int>& cnt,
                          int root_id, const float4* map_raw, int map_n, float min_half, bool downsample);

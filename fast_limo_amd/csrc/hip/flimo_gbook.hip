@@ -217,7 +217,14 @@ __global__ __launch_bounds__(256) void gb_gather_kernel(const int* __restrict__ 
 // The wave walks the item's subtree with an explicit stack (LDS); at every node that splits, the lanes load
 // the node's points in parallel, octant counts and stable ranks come from ballots, the index list is
 // partitioned through `tmp`, and lane 0 allocates the children with one atomic.
-constexpr int GB_STACK = 128;      // >= 7 * max depth + 1
+// Size of the stack.  A node that splits is popped and its (at most 8) children are pushed, so every split on the path from the
+// item's node down to the node in hand leaves at most 7 siblings waiting: after s splits in a row the stack holds at most
+// 7 s + 1 entries.  A node splits only while its half edge is > 2 * min_half, and a child's half edge is exactly half its
+// parent's, so s never exceeds the number of halvings that take the ROOT's half edge to <= 2 * min_half (gb_levels).  The host
+// admits a batch only when that number, for the root as the batch leaves it, is <= GB_MAX_DEPTH (GBook::admit): with
+// min_extent 0.01 that is a root cube of 0.02 * 2^48 m, about 5.6e12 m, a side.  The whole-block kernel pushes only the children
+// it keeps (those above kBigItem), which the same count bounds.
+constexpr int GB_STACK = 7 * GB_MAX_DEPTH + 1;
 
 __global__ __launch_bounds__(256) void gb_build_kernel(const GbItem* __restrict__ items, const int* __restrict__ n_items_dev, const float4* __restrict__ map_raw,
                                                        int* __restrict__ lists, int* __restrict__ tmp, float4* __restrict__ node_c,
@@ -455,6 +462,72 @@ __global__ __launch_bounds__(1024) void gb_build_big_kernel(GbItem* __restrict__
 // ---- host side ----------------------------------------------------------------------------------
 #define GBCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 
+// splits in a row that a cube of this half edge can see: halvings until the half edge is <= 2 * min_half (float32, exact: a
+// subnormal ends at 0).  Saturates above GB_MAX_DEPTH.
+static int gb_levels(float half, float min_half) {
+  int s = 0;
+  while (half > 2 * min_half && s <= GB_MAX_DEPTH) { half *= 0.5f; s++; }
+  return s;
+}
+
+// root cube of a first batch (Octree.hpp:287-296), float32 like the reference
+static void gb_root_of_box(const float bb[6], float c[3], float* half) {
+  const float ex = 0.5f * (bb[3] - bb[0]), ey = 0.5f * (bb[4] - bb[1]), ez = 0.5f * (bb[5] - bb[2]);
+  c[0] = bb[0] + ex; c[1] = bb[1] + ey; c[2] = bb[2] + ez;
+  *half = ex;
+  if (ey > *half) *half = ey;
+  if (ez > *half) *half = ez;
+}
+
+// Root growth (Octree.hpp:354-374) on copies of the host mirror: the root doubles towards the batch's max corner, then towards
+// its min corner, until it holds both.  New root nodes (c4, child links) oldest first when the vectors are given; their ids
+// start at first_id.  false: more than kMaxRootDoublings doublings -- no float32 cube gets there (flimo_insert.h).
+static bool gb_grow_root(const float bb[6], float c[3], float* half, int* root, int first_id, std::vector<float>* nc,
+                         std::vector<int>* nchild) {
+  const float corners[2][3] = {{bb[3], bb[4], bb[5]}, {bb[0], bb[1], bb[2]}};
+  int added = 0;
+  for (int ci = 0; ci < 2; ci++) {
+    const float* b = corners[ci];
+    for (;;) {
+      float mm = fabsf(b[0] - c[0]);
+      const float my = fabsf(b[1] - c[1]), mz = fabsf(b[2] - c[2]);
+      if (my > mm) mm = my;
+      if (mz > mm) mm = mz;
+      if (!(mm > *half)) break;
+      if (added >= kMaxRootDoublings) return false;
+      const float ph = 2 * *half;
+      const float px = c[0] + (b[0] > c[0] ? 0.5f : -0.5f) * ph;
+      const float py = c[1] + (b[1] > c[1] ? 0.5f : -0.5f) * ph;
+      const float pz = c[2] + (b[2] > c[2] ? 0.5f : -0.5f) * ph;
+      const int slot = (c[0] > px ? 1 : 0) | (c[1] > py ? 2 : 0) | (c[2] > pz ? 4 : 0);
+      if (nc) { nc->push_back(px); nc->push_back(py); nc->push_back(pz); nc->push_back(ph); }
+      if (nchild) for (int k = 0; k < 8; k++) nchild->push_back(k == slot ? *root : -1);
+      *root = first_id + added;
+      added++;
+      c[0] = px; c[1] = py; c[2] = pz; *half = ph;
+    }
+  }
+  return true;
+}
+
+// What the next batch (box of its finite points: bb) would meet, from the host mirror alone -- nothing is changed.
+GBook::Admit GBook::admit(const float bb[6], float min_half_next) const {
+  float c[3], half;
+  if (!active) {
+    gb_root_of_box(bb, c, &half);
+    return gb_levels(half, min_half_next) > GB_MAX_DEPTH ? ADMIT_TOO_DEEP : ADMIT_OK;
+  }
+  if (root_half == 0.f) {                                       // all stored points at root_c
+    const bool same = bb[0] == root_c[0] && bb[1] == root_c[1] && bb[2] == root_c[2] && bb[3] == root_c[0] && bb[4] == root_c[1] &&
+                      bb[5] == root_c[2];
+    return same ? ADMIT_OK : ADMIT_ZERO_ROOT;
+  }
+  c[0] = root_c[0]; c[1] = root_c[1]; c[2] = root_c[2]; half = root_half;
+  int r = root;
+  if (!gb_grow_root(bb, c, &half, &r, node_n, nullptr, nullptr)) return ADMIT_GROWTH;
+  return gb_levels(half, min_half) > GB_MAX_DEPTH ? ADMIT_TOO_DEEP : ADMIT_OK;
+}
+
 template <typename T>
 static hipError_t grow(T*& p, size_t& cap, size_t need, size_t keep_n, hipStream_t st) {
   if (need <= cap) return hipSuccess;
@@ -549,6 +622,11 @@ hipError_t GBook::init(hipStream_t st, const float4* batch, int m, const float b
   *kept_out = 0;
   active = false;
   if (m <= 0) return hipSuccess;
+  {
+    float c0[3], h0;
+    gb_root_of_box(bb, c0, &h0);
+    if (gb_levels(h0, min_half_) > GB_MAX_DEPTH) return hipErrorInvalidValue;      // (admit() names it; nothing touched)
+  }
   min_half = min_half_;
   downsample = downsample_;
   node_n = 0;
@@ -586,12 +664,7 @@ hipError_t GBook::init(hipStream_t st, const float4* batch, int m, const float b
   GBCHK(hipStreamSynchronize(st));
   const int kept = (int)(last_rank + last_flag);
   if (kept == 0) return hipSuccess;
-  // root cube (Octree.hpp:287-296), float32 like the reference
-  const float ex = 0.5f * (bb[3] - bb[0]), ey = 0.5f * (bb[4] - bb[1]), ez = 0.5f * (bb[5] - bb[2]);
-  root_c[0] = bb[0] + ex; root_c[1] = bb[1] + ey; root_c[2] = bb[2] + ez;
-  root_half = ex;
-  if (ey > root_half) root_half = ey;
-  if (ez > root_half) root_half = ez;
+  gb_root_of_box(bb, root_c, &root_half);
   root = 0;
   const float4 rc = make_float4(root_c[0], root_c[1], root_c[2], root_half);
   int child8[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
@@ -637,29 +710,18 @@ hipError_t GBook::update(hipStream_t st, const float4* batch, int m, const float
   *kept_out = 0;
   if (m <= 0) return hipSuccess;
   GBCHK(finish(st, S));
-  // ---- root growth on the host mirror (Octree.hpp:354-374): max corner first, then min ----
+  // ---- root growth on the host mirror (Octree.hpp:354-374): worked out on copies, refused before anything changes ----
   {
     std::vector<float> nc;   // new root nodes (c4) oldest first
     std::vector<int> nchild;
-    const float corners[2][3] = {{bb[3], bb[4], bb[5]}, {bb[0], bb[1], bb[2]}};
-    for (int ci = 0; ci < 2; ci++) {
-      const float* b = corners[ci];
-      for (;;) {
-        float mm = fabsf(b[0] - root_c[0]);
-        const float my = fabsf(b[1] - root_c[1]), mz = fabsf(b[2] - root_c[2]);
-        if (my > mm) mm = my;
-        if (mz > mm) mm = mz;
-        if (!(mm > root_half)) break;
-        const float ph = 2 * root_half;
-        const float px = root_c[0] + (b[0] > root_c[0] ? 0.5f : -0.5f) * ph;
-        const float py = root_c[1] + (b[1] > root_c[1] ? 0.5f : -0.5f) * ph;
-        const float pz = root_c[2] + (b[2] > root_c[2] ? 0.5f : -0.5f) * ph;
-        const int slot = (root_c[0] > px ? 1 : 0) | (root_c[1] > py ? 2 : 0) | (root_c[2] > pz ? 4 : 0);
-        nc.push_back(px); nc.push_back(py); nc.push_back(pz); nc.push_back(ph);
-        for (int k = 0; k < 8; k++) nchild.push_back(k == slot ? root : -1);
-        root = node_n + (int)(nc.size() / 4) - 1;
-        root_c[0] = px; root_c[1] = py; root_c[2] = pz; root_half = ph;
-      }
+    {
+      float c[3] = {root_c[0], root_c[1], root_c[2]}, half = root_half;
+      int r = root;
+      if (root_half == 0.f && admit(bb, min_half) != ADMIT_OK) return hipErrorInvalidValue;     // the caller re-initialises (ADMIT_ZERO_ROOT)
+      if (!gb_grow_root(bb, c, &half, &r, node_n, &nc, &nchild)) return hipErrorInvalidValue;
+      if (gb_levels(half, min_half) > GB_MAX_DEPTH) return hipErrorInvalidValue;
+      root = r;
+      root_c[0] = c[0]; root_c[1] = c[1]; root_c[2] = c[2]; root_half = half;
     }
     const int add = (int)(nc.size() / 4);
     if (add > 0) {

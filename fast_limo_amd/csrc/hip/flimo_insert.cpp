@@ -118,53 +118,98 @@ struct InsertBook {
     }
   }
 
-  void update(const float* xyz, size_t n, unsigned char* keep) {
-    for (size_t i = 0; i < n; i++) keep[i] = 1;
-    if (n == 0) return;
+  // Every leaf's points in no particular order (the zero-size root: they all lie at one location).
+  void collect(int32_t id, std::vector<P3>& out) const {
+    if (id < 0) return;
+    const Cell& c = pool[id];
+    if (!c.split) { out.insert(out.end(), c.pts.begin(), c.pts.end()); return; }
+    for (int k = 0; k < 8; k++) collect(c.kid[k], out);
+  }
+
+  // initialize (Octree.hpp:282-298): root cube from the bounding box, no down-sampling
+  void initialize(std::vector<P3>& pts, const P3& mn, const P3& mx) {
+    const float ex = 0.5f * (mx.x - mn.x), ey = 0.5f * (mx.y - mn.y), ez = 0.5f * (mx.z - mn.z);
+    const float cx = mn.x + ex, cy = mn.y + ey, cz = mn.z + ez;
+    float half = ex;
+    if (ey > half) half = ey;
+    if (ez > half) half = ez;
+    root = grow(cx, cy, cz, half, pts);
+  }
+
+  // false: the root would have to double more often than a float32 half edge can (kMaxRootDoublings); nothing was changed
+  bool update(const float* xyz, size_t n, unsigned char* keep) {
+    // processPoints (Octree.hpp:235-267): non-finite points are never stored and do not count for the box
+    std::vector<Item> items;
+    items.reserve(n);
     P3 mn{FLT_MAX, FLT_MAX, FLT_MAX}, mx{-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (size_t i = 0; i < n; i++) {
       const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+      keep[i] = std::isfinite(x) && std::isfinite(y) && std::isfinite(z) ? 1 : 0;
+      if (!keep[i]) continue;
+      items.push_back(Item{P3{x, y, z}, (uint32_t)i});
       mn.x = x < mn.x ? x : mn.x; mn.y = y < mn.y ? y : mn.y; mn.z = z < mn.z ? z : mn.z;
       mx.x = x > mx.x ? x : mx.x; mx.y = y > mx.y ? y : mx.y; mx.z = z > mx.z ? z : mx.z;
     }
+    if (items.empty()) return true;                      // a batch without a finite point changes nothing
     if (root < 0) {
-      // initialize (Octree.hpp:282-298): root cube from the bounding box, no down-sampling
-      const float ex = 0.5f * (mx.x - mn.x), ey = 0.5f * (mx.y - mn.y), ez = 0.5f * (mx.z - mn.z);
-      const float cx = mn.x + ex, cy = mn.y + ey, cz = mn.z + ez;
-      float half = ex;
-      if (ey > half) half = ey;
-      if (ez > half) half = ez;
-      std::vector<P3> pts(n);
-      for (size_t i = 0; i < n; i++) pts[i] = P3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-      root = grow(cx, cy, cz, half, pts);
-      return;
+      std::vector<P3> pts(items.size());
+      for (size_t i = 0; i < items.size(); i++) pts[i] = items[i].p;
+      initialize(pts, mn, mx);
+      return true;
     }
-    // root growth by doubling towards out-of-bounds corners (Octree.hpp:354-374): max first, then min
-    static const float f[2] = {-0.5f, 0.5f};
-    const P3 corners[2] = {mx, mn};
-    for (int ci = 0; ci < 2; ci++) {
-      const P3 b = corners[ci];
-      for (;;) {
-        const Cell& r = pool[root];
-        float m = std::fabs(b.x - r.cx);
-        const float my = std::fabs(b.y - r.cy), mz = std::fabs(b.z - r.cz);
-        if (my > m) m = my;
-        if (mz > m) m = mz;
-        if (!(m > r.half)) break;
-        const float ph = 2 * r.half;
-        const float px = r.cx + f[b.x > r.cx ? 1 : 0] * ph, py = r.cy + f[b.y > r.cy ? 1 : 0] * ph,
-                    pz = r.cz + f[b.z > r.cz ? 1 : 0] * ph;
-        const P3 old_c{r.cx, r.cy, r.cz};
-        const int32_t nr = alloc();
-        pool[nr].cx = px; pool[nr].cy = py; pool[nr].cz = pz; pool[nr].half = ph;
-        pool[nr].split = true;
-        pool[nr].kid[octant_of(old_c, px, py, pz)] = root;
-        root = nr;
+    // A root of size zero (all stored points at one location) cannot grow by doubling.  A batch that leaves that location
+    // is taken as initialize(stored points followed by the batch's finite points): DESIGN.md, "The zero-size root".
+    if (pool[root].half == 0.f && !pool[root].split) {
+      const Cell& r = pool[root];
+      if (mn.x != r.cx || mn.y != r.cy || mn.z != r.cz || mx.x != r.cx || mx.y != r.cy || mx.z != r.cz) {
+        std::vector<P3> pts;
+        collect(root, pts);
+        for (const P3& p : pts) {
+          mn.x = p.x < mn.x ? p.x : mn.x; mn.y = p.y < mn.y ? p.y : mn.y; mn.z = p.z < mn.z ? p.z : mn.z;
+          mx.x = p.x > mx.x ? p.x : mx.x; mx.y = p.y > mx.y ? p.y : mx.y; mx.z = p.z > mx.z ? p.z : mx.z;
+        }
+        for (const Item& it : items) pts.push_back(it.p);
+        pool.clear(); free_list.clear(); root = -1; stored = 0;
+        initialize(pts, mn, mx);
+        return true;
       }
     }
-    std::vector<Item> items(n);
-    for (size_t i = 0; i < n; i++) items[i] = Item{P3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]}, (uint32_t)i};
+    // root growth by doubling towards out-of-bounds corners (Octree.hpp:354-374): max first, then min.  The new chain of
+    // roots is worked out first and attached only when it ends within kMaxRootDoublings.
+    static const float f[2] = {-0.5f, 0.5f};
+    const P3 corners[2] = {mx, mn};
+    std::vector<Cell> chain;
+    {
+      const Cell& r0 = pool[root];
+      float cx = r0.cx, cy = r0.cy, cz = r0.cz, half = r0.half;
+      for (int ci = 0; ci < 2; ci++) {
+        const P3 b = corners[ci];
+        for (;;) {
+          float m = std::fabs(b.x - cx);
+          const float my = std::fabs(b.y - cy), mz = std::fabs(b.z - cz);
+          if (my > m) m = my;
+          if (mz > m) m = mz;
+          if (!(m > half)) break;
+          if ((int)chain.size() >= kMaxRootDoublings) return false;
+          const float ph = 2 * half;
+          const float px = cx + f[b.x > cx ? 1 : 0] * ph, py = cy + f[b.y > cy ? 1 : 0] * ph, pz = cz + f[b.z > cz ? 1 : 0] * ph;
+          Cell nr;
+          nr.cx = px; nr.cy = py; nr.cz = pz; nr.half = ph;
+          nr.split = true;
+          nr.kid[octant_of(P3{cx, cy, cz}, px, py, pz)] = -2;     // (the root below it: linked when the chain is attached)
+          chain.push_back(nr);
+          cx = px; cy = py; cz = pz; half = ph;
+        }
+      }
+    }
+    for (const Cell& nr : chain) {
+      const int32_t id = alloc();
+      pool[id] = nr;
+      for (int k = 0; k < 8; k++) if (pool[id].kid[k] == -2) pool[id].kid[k] = root;
+      root = id;
+    }
     route(root, items, keep);
+    return true;
   }
 };
 
@@ -199,6 +244,6 @@ void insert_book_clear(InsertBook* b) {
   b->pool.clear(); b->free_list.clear(); b->root = -1; b->stored = 0;
 }
 size_t insert_book_size(const InsertBook* b) { return b->stored; }
-void insert_book_update(InsertBook* b, const float* xyz, size_t n, unsigned char* keep) { b->update(xyz, n, keep); }
+bool insert_book_update(InsertBook* b, const float* xyz, size_t n, unsigned char* keep) { return b->update(xyz, n, keep); }
 
 }  // namespace flimo

@@ -25,8 +25,14 @@ void insert_book_destroy(InsertBook* b);
 void insert_book_config(InsertBook* b, float min_extent, bool downsample);
 void insert_book_clear(InsertBook* b);
 size_t insert_book_size(const InsertBook* b);
-// xyz: n packed NaN-free points.  keep[i] := 1 if point i is stored, 0 if dropped.
-void insert_book_update(InsertBook* b, const float* xyz, size_t n, unsigned char* keep);
+// A float32 half edge can double fewer than 300 times before it is infinite (from the smallest subnormal, 2^-149, to
+// 2^128: 277 times): the root-growth loop of Octree::update never legitimately runs longer.  A batch that would need more
+// is refused before anything changes.
+constexpr int kMaxRootDoublings = 300;
+
+// xyz: n packed points.  keep[i] := 1 if point i is stored, 0 if dropped (non-finite points are never stored).
+// false: the batch was refused (kMaxRootDoublings), book and keep[] flags of no meaning.
+bool insert_book_update(InsertBook* b, const float* xyz, size_t n, unsigned char* keep);
 
 // flattened copy of the live tree: c4 = (cx, cy, cz, half) per node, child = 8 links per node (-1 absent),
 // cnt = leaf point count or -1 for internal nodes

@@ -1610,6 +1610,8 @@ hipError_t batch_bbox(hipStream_t st, const float4* pts, size_t n, MapBuildScrat
   if ((e = fetch_bbox(st, S, ob)) != hipSuccess) return e;
   if (ob[0] == 0xffffffffu) return hipSuccess;
   for (int i = 0; i < 6; i++) bb[i] = o2f_host(ob[i]);
+  // a batch without a finite point: every block still sends its starting values, FLT_MAX below -FLT_MAX
+  if (!(bb[0] <= bb[3])) return hipSuccess;
   *any = true;
   return hipSuccess;
 }

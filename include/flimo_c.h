@@ -83,7 +83,11 @@ const char* flimo_version(void);
  *      and octree::Octree::{initialize,update} (Objects/Octree.hpp:282-432) ---- */
 int flimo_map_config(flimo_ctx* ctx, const flimo_map_cfg* cfg);
 /* xyz: n points, stride_bytes between consecutive points (>= 12), host memory.  NaN points are
- * dropped (Octree::processPoints, Objects/Octree.hpp:243-244). */
+ * dropped (Octree::processPoints, Objects/Octree.hpp:243-244); a batch without a finite point changes nothing.
+ * Where the reference has no answer: a map whose stored points all lie at one location (octree root of size zero) takes a batch
+ * that leaves that location as initialize(stored points followed by the batch), everything stored, in order.
+ * FLIMO_ERR_UNSUPPORTED, map untouched: the octree root the batch needs lies more than 48 halvings above 2 * min_extent
+ * ("octree too deep").  Both hold for every call that adds to the map. */
 int flimo_map_add(flimo_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes, double stamp);
 int flimo_map_clear(flimo_ctx* ctx);
 /* A local map (no counterpart in the reference, whose octree has no erase): keeps the stored points inside [lo, hi] (inclusive,

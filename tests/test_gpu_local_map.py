@@ -11,6 +11,7 @@ import pytest
 
 from common import CAPS, sort_rows
 from fast_limo_amd import synth
+from insert_rule_common import _stored_of_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -192,27 +193,6 @@ def test_after_a_crop_the_map_is_a_fresh_octree_of_the_kept_points(built, oracle
 
 # ---- 3. a moving box over many batches, against the oracle alone ----------------------------------------------------------------
 MOVING_BOX_SIZES = [(35000, 32307), (69027, 56595), (90703, 70085), (102924, 76431), (101780, 70385), (103596, 72704)]
-
-
-def _rows_view(a):
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    return a.view(np.dtype((np.void, 12))).reshape(-1)
-
-
-def _stored_of_batch(batch, pts_before, pts_after):
-    """The batch's stored points in insertion (= batch) order: the multiset difference of the octree's points after and before it
-    (the octree never drops a stored point), picked out of the batch in its order."""
-    from collections import Counter
-    need = Counter(_rows_view(pts_after).tolist())
-    need.subtract(Counter(_rows_view(pts_before).tolist()))
-    assert min(need.values(), default=0) >= 0
-    out = []
-    for i, key in enumerate(_rows_view(batch).tolist()):
-        if need.get(key, 0) > 0:
-            need[key] -= 1
-            out.append(i)
-    assert sum(need.values()) == 0
-    return batch[np.array(out, np.int64)] if out else np.zeros((0, 3), np.float32)
 
 
 def test_moving_box_over_twelve_batches_against_the_oracle(built, oracle):
