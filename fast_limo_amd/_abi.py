@@ -3,7 +3,8 @@ per exported function.  ``_lib.load_hip()`` and ``api.load_host()`` declare thei
 symbols the tests compare with the headers are read off them.
 
 A new entry that both a ``flimo_ctx`` and a ``flimo_loc`` offer is one row of ``PAIRED`` -- the two symbols and the arguments after
-the handle -- and one method of ``_lib._SharedEntries``; ``HipCtx`` and ``Localizer`` then both have it."""
+the handle -- and one method of ``_lib._SharedEntries``; ``HipCtx`` and ``Localizer`` then both have it.  ``PAIRED_NDT`` holds the
+rows of the NDT entries in the same form."""
 from __future__ import annotations
 
 import ctypes as C
@@ -48,7 +49,7 @@ class _Stats(C.Structure):
     """The statistics an entry returns: counters and, in float64, moments."""
 
     def as_dict(self):
-        return {name: (float if kind is C.c_double else int)(getattr(self, name)) for name, kind in self._fields_}
+        return {name: (float if kind in (C.c_double, C.c_float) else int)(getattr(self, name)) for name, kind in self._fields_}
 
 
 class OutlierCfg(C.Structure):
@@ -120,6 +121,17 @@ class RegionStats(_Stats):
     """flimo_region_stats (include/flimo_c.h)."""
     _fields_ = [("n", C.c_uint64), ("smooth", C.c_uint64), ("regions", C.c_uint64), ("largest", C.c_uint64), ("sel_regions", C.c_uint64),
                 ("unassigned", C.c_uint64), ("sel_points", C.c_uint64)]
+
+
+class NdtCfg(C.Structure):
+    """flimo_ndt_cfg (include/flimo_c.h)."""
+    _fields_ = [("leaf", C.c_float), ("min_pts", C.c_int), ("eig_ratio", C.c_double)]
+
+
+class NdtInfo(_Stats):
+    """flimo_ndt_model_info (include/flimo_c.h)."""
+    _fields_ = [("cells", C.c_uint64), ("map_size_at_build", C.c_uint64), ("eig_ratio", C.c_double), ("leaf", C.c_float),
+                ("min_pts", C.c_int), ("stale", C.c_int)]
 
 
 class CorrGraphCfg(C.Structure):
@@ -202,7 +214,15 @@ PAIRED = (
     ("flimo_desc_ref_set", "flimo_loc_desc_ref_set", [vp, sz, i]),
     ("flimo_desc_match", "flimo_loc_desc_match", [vp, sz, i, i, vp, vp, vp]),
 )
-LOC_OF = {hip: loc for hip, loc, _ in PAIRED}
+# The resident NDT models and the passes against them: paired rows like the ones above, in a table of their own.
+PAIRED_NDT = (
+    ("flimo_ndt_build", "flimo_loc_ndt_build", [i, P(NdtCfg), P(sz)]),
+    ("flimo_ndt_cells", "flimo_loc_ndt_cells", [i, sz, P(sz), vp, vp, vp, vp, vp, vp]),
+    ("flimo_ndt_info", "flimo_loc_ndt_info", [i, P(NdtInfo)]),
+    ("flimo_ndt_clear", "flimo_loc_ndt_clear", [i]),
+    ("flimo_scan_ndt", "flimo_loc_scan_ndt", [i, vp, sz, i, d, vp, vp, vp, vp, vp, vp, vp]),
+)
+LOC_OF = {hip: loc for hip, loc, _ in PAIRED + PAIRED_NDT}
 
 # Everything else: (result, symbol, every argument -- the handle, where there is one, included).
 HIP_ONLY = (
@@ -235,6 +255,7 @@ HIP_ONLY = (
     (i, "flimo_set_normals_chunk", [vp, sz]),
     (i, "flimo_set_fitness_chunk", [vp, sz]),
     (i, "flimo_set_linearize_chunk", [vp, sz]),
+    (i, "flimo_set_ndt_chunk", [vp, sz]),
     (i, "flimo_set_corr_chunk", [vp, sz]),
     (i, "flimo_set_desc_chunk", [vp, sz, sz]),
     (sz, "flimo_desc_ref_size", [vp]),
@@ -247,6 +268,7 @@ HIP_ONLY = (
     (i, "flimo_corr_pose_host", [vp, vp, P(CorrCfg), vp, vp]),
     (i, "flimo_corr_compatible_host", [vp, vp, vp, vp, P(CorrGraphCfg)]),
     (i, "flimo_desc_dist_host", [vp, vp, i, vp]),
+    (i, "flimo_ndt_term_host", [vp, vp, vp, vp, vp, vp, d, vp]),
     (None, "flimo_plane_fit5_host", [f32p, f32p]),
     (i, "flimo_plane_eval5_host", [f32p, f32p, f]),
     (i, "flimo_calculate_H_host", [f64p, f32p, f32p, f32p, sz, i, f64p, f64p]),
@@ -360,13 +382,13 @@ HOST_ONLY = (
     (None, "flimo_host_eigen_solver6", [f64p, f64p, f64p, f64p]),
 )
 
-HIP_SYMBOLS = [hip for hip, _, _ in PAIRED] + [name for _, name, _ in HIP_ONLY]
-HOST_SYMBOLS = [loc for _, loc, _ in PAIRED] + [name for _, name, _ in HOST_ONLY]
+HIP_SYMBOLS = [hip for hip, _, _ in PAIRED + PAIRED_NDT] + [name for _, name, _ in HIP_ONLY]
+HOST_SYMBOLS = [loc for _, loc, _ in PAIRED + PAIRED_NDT] + [name for _, name, _ in HOST_ONLY]
 
 
 def declare(lib, side):
     """Give every function of ``lib`` its result and argument types; ``side`` 0: libflimo_hip.so, 1: libfast_limo.so."""
-    for row in PAIRED:
+    for row in PAIRED + PAIRED_NDT:
         fn = getattr(lib, row[side])
         fn.restype, fn.argtypes = C.c_int, [vp] + row[2]
     for restype, name, args in (HIP_ONLY, HOST_ONLY)[side]:

@@ -15,7 +15,7 @@ import numpy as np
 from . import _abi
 # (every structure stays a name of this module: callers and tests say _lib.MatchCfg, _lib.Frame, ...)
 from ._abi import (CHAIN_MAX_PASSES, CarveCfg, ChainIO, ChainPass, ClusterCfg, ClusterStats, CorrCfg, CorrGraphCfg, FilterCfg, FpfhCfg, Frame,
-                   KeypointCfg, MapCfg, MatchCfg, OutlierCfg, OutlierStats, PlaneCfg, PlaneSel, RegionCfg, RegionStats, VoxelCfg, VoxelStats,
+                   KeypointCfg, MapCfg, MatchCfg, NdtCfg, NdtInfo, OutlierCfg, OutlierStats, PlaneCfg, PlaneSel, RegionCfg, RegionStats, VoxelCfg, VoxelStats,
                    f32p, f64p, i32p)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -176,6 +176,10 @@ _KEYPOINT_OUTPUTS = (("mask", np.uint8, 1), ("saliency", np.float64, 1), ("cnt",
 _COMPONENT_OUTPUTS = (("label", np.int32, 1), ("size", np.int32, 1), ("mask", np.uint8, 1))      # clusters and regions
 _VOXEL_MASK_OUTPUTS = (("voxel", np.int32, 1), ("mask", np.uint8, 1))
 _NORMAL_OUTPUTS = (("normal", np.float32, 4), ("cnt", np.int32, 1), ("centroid", np.float64, 3), ("cov", np.float64, 6), ("eig", np.float64, 6))
+
+NDT_CELL_OUTPUTS = (("ijk", np.int32, 3), ("count", np.int32, 1), ("mean", np.float64, 3), ("evec", np.float64, 9), ("wgt", np.float64, 3),
+                    ("eval", np.float64, 3))
+NDT_SLOTS = 4          # FLIMO_NDT_SLOTS
 
 _NONE = C.create_string_buffer(8)
 
@@ -541,6 +545,61 @@ class _SharedEntries:
                     *(_ptr(out.get(name)) for name in ("valid", "H", "g", "cost", "rows", "pair_cnt")))
         return out
 
+    def ndt_build(self, slot, leaf, min_pts=6, eig_ratio=0.01):
+        """flimo_ndt_build: the NDT cell model of slot ``slot`` (0 .. NDT_SLOTS - 1) from the voxels of the whole map at ``leaf``
+        -- the voxels of ``map_voxels`` with at least ``min_pts`` points and a covariance that is not zero, their principal axes and
+        the weights 1 / max(l, eig_ratio * l2).  A snapshot: later inserts and removals leave it alone (``ndt_info``: stale).
+        Returns the number of cells.  A ``Localizer`` first waits for an insert, a crop or a carve still running behind the last
+        sweep."""
+        k, nc = NdtCfg(float(leaf), int(min_pts), float(eig_ratio)), C.c_size_t(0)
+        self._entry("flimo_ndt_build", int(slot), C.byref(k), C.byref(nc))
+        return int(nc.value)
+
+    def ndt_info(self, slot):
+        """flimo_ndt_info: a dict of the model in ``slot``: cells, map_size_at_build, eig_ratio, leaf, min_pts, stale."""
+        info = NdtInfo()
+        self._entry("flimo_ndt_info", int(slot), C.byref(info))
+        return info.as_dict()
+
+    def ndt_cells(self, slot, want=("ijk", "count", "mean", "evec", "wgt", "eval")):
+        """flimo_ndt_cells: the model in ``slot`` as a dict of the arrays named in ``want`` -- ijk [nc, 3] = (cx, cy, cz), count
+        [nc], mean [nc, 3], evec [nc, 3, 3] (row k: the unit vector of eigenvalue k), wgt [nc, 3], eval [nc, 3] (ascending, before
+        the clamp) -- and ``nc``; the cells in ascending (cz, cy, cx)."""
+        nc = C.c_size_t(0)
+        self._entry("flimo_ndt_cells", int(slot), 0, C.byref(nc), None, None, None, None, None, None)
+        n = int(nc.value)
+        arr = _outputs("ndt_cells", NDT_CELL_OUTPUTS, want, n)
+        if arr and n:
+            self._entry("flimo_ndt_cells", int(slot), n, C.byref(nc), *_ptrs(arr, NDT_CELL_OUTPUTS))
+        if "evec" in arr:
+            arr["evec"] = arr["evec"].reshape(n, 3, 3)
+        out = dict(arr)
+        out["nc"] = n
+        return out
+
+    def ndt_clear(self, slot=-1):
+        """flimo_ndt_clear: free the model in ``slot``; -1: all of them."""
+        self._entry("flimo_ndt_clear", int(slot))
+
+    def scan_ndt(self, slot, x26s, d2, hood=7, want_terms=False):
+        """flimo_scan_ndt: the NDT score and Gauss-Newton normal equations of the resident scan against the model in ``slot`` at
+        each pose of ``x26s`` [np, 26] (only pos and rot are read).  ``hood``: 1 (the point's own cell) or 7 (and its six face
+        neighbours); ``d2``: the Gaussian's scale (``api.ndt_params``).  Returns a dict: valid [np] int32 (pairs with a live term),
+        cells [np] int64 (live terms), H [np, 21] (upper triangle, row-major), g [np, 6], score [np] (the sum of e)[, terms
+        [np, n, 7, 2]: (m, e) per neighbour slot, NaN when absent; term_cell [np, n, 7]: the cell's row in ``ndt_cells``, -1].
+        The step solves H xi = -g (``api.ndt_align`` iterates it).  A ``Localizer`` first waits for an insert, a crop or a carve
+        still running behind the last sweep; its resident scan is that sweep's (``pc2match()``)."""
+        x = _poses(x26s)
+        m, n = x.shape[0], self._scan_size()
+        out = {"valid": np.zeros(m, np.int32), "cells": np.zeros(m, np.int64), "H": np.zeros((m, 21)), "g": np.zeros((m, 6)),
+               "score": np.zeros(m)}
+        if want_terms:
+            out["terms"] = np.full((m, n, 7, 2), np.nan)
+            out["term_cell"] = np.full((m, n, 7), -1, np.int32)
+        self._entry("flimo_scan_ndt", int(slot), x.ctypes.data if m else None, m, int(hood), float(d2),
+                    *(_ptr(out.get(name)) for name in ("valid", "cells", "H", "g", "score", "terms", "term_cell")))
+        return out
+
     def corr_poses(self, src, dst, tri, want=("pose",), **cfg):
         """flimo_corr_poses: pose hypotheses from point correspondences.  ``src`` [m, 3] (body frame) and ``dst`` [m, 3] (map frame)
         are the putative pairs, ``tri`` [nh, 3] the caller's samples of three of them (``api.corr_triplets``); ``cfg``: the fields
@@ -775,6 +834,10 @@ class HipCtx(_SharedEntries):
     def set_linearize_chunk(self, pairs):
         """(pose, point) pairs per chunk of ``scan_linearize`` (flimo_set_linearize_chunk; 0: the default of 2^20)."""
         self._chk(self._L.flimo_set_linearize_chunk(self._h, int(pairs)))
+
+    def set_ndt_chunk(self, pairs):
+        """(pose, point) pairs per chunk of ``scan_ndt`` (flimo_set_ndt_chunk; 0: the default of 2^20)."""
+        self._chk(self._L.flimo_set_ndt_chunk(self._h, int(pairs)))
 
     def set_corr_chunk(self, n):
         """Hypotheses per chunk of ``corr_poses`` (flimo_set_corr_chunk; 0: the default of 2^16)."""

@@ -620,7 +620,7 @@ def desc_pairs(ref_obj, qry_obj, q_desc, r_desc, ratio=0.9, mutual=True):
 
 
 def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=True, nh=4096, seed=0, top=8, corr=None, fitness_max_dist=1.0, align=None,
-               x26_like=None, prune=None, keypoints=None, scan_keypoints=None):
+               x26_like=None, prune=None, keypoints=None, scan_keypoints=None, refine="plane", ndt=None):
     """A pose of a scan in a map from nothing but the two clouds -- plumbing over six calls, every parameter the caller's.
     ``map_obj`` (a ``HipCtx`` or a ``Localizer``) holds the map, and the scan (body frame) as its resident scan; ``scan_obj`` is a
     context whose MAP is that scan.  FPFH of both sides (``fpfh``: the fields of ``_lib.fpfh_cfg``; ``scan_fpfh``: the scan side's
@@ -637,7 +637,11 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
     ``keypoints``: None, or a dict of the fields of ``_lib.keypoint_cfg`` (``scan_keypoints``: the scan side's where they differ) --
     both sides then run ``map_keypoints``, and ``desc_ref_set`` and ``desc_pairs`` see the keypoints' FPFH rows alone; FPFH itself is
     still formed for every point.  The returned pairs, src and dst are in the ORIGINAL indices; ``keypoints`` is added to the result:
-    (the scan's ascending indices, the map's)."""
+    (the scan's ascending indices, the map's).
+    ``refine``: "plane" (the default: ``scan_align``) or "ndt" -- the best row is then refined by ``ndt_align`` (``ndt``: its keyword
+    arguments; ``slots`` is required and names models already built on ``map_obj`` with ``ndt_build``, coarse to fine)."""
+    if refine not in ("plane", "ndt"):
+        raise ValueError(f"relocalize: refine must be 'plane' or 'ndt', not {refine!r}")
     fpfh, corr, align = dict(fpfh or {}), dict(corr or {}), dict(align or {})
     m_hip, s_hip = getattr(map_obj, "hip", map_obj), getattr(scan_obj, "hip", scan_obj)
     f_map = map_obj.map_fpfh(want=(), **fpfh)["fpfh"]
@@ -664,7 +668,7 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
     cost = fitness_cost(inliers, sum_sqd, m_hip.scan_size(), fitness_max_dist)
     order = np.lexsort((np.arange(cost.size), cost))
     ranked = cons["x26"][order]
-    aligned = scan_align(map_obj, ranked[:1], **align)
+    aligned = scan_align(map_obj, ranked[:1], **align) if refine == "plane" else ndt_align(map_obj, ranked[:1], **dict(ndt or {}))
     out = dict(pairs=(qi, rj), fpfh=(f_scan, f_map), src=src, dst=dst, consensus=cons,
                fitness=dict(inliers=inliers[order], sum_sqd=sum_sqd[order], cost=cost[order], x26=ranked), align=aligned,
                x26=aligned["x26"][0] if ranked.shape[0] else None)
@@ -746,6 +750,53 @@ def scan_align(obj, x26s, k=5, max_dist=1.0, min_pts=3, max_curv=0.05, iters=10,
             x[j] = pose_retract(x[j], xi)
             steps[j] += 1
     return dict(x26=x, valid=valid, cost=cost, iters=steps, status=status)
+
+
+def ndt_params(outlier_ratio, leaf):
+    """PCL's Gaussian fit of the NDT likelihood (pcl::NormalDistributionsTransform::init / computeTransformation) for an outlier
+    ratio and a leaf size: returns (d1, d2) -- a term scores -d1 * exp(-d2 / 2 * m).  c1 = 10 (1 - o), c2 = o / leaf^3,
+    d3 = -log c2, d1 = -log(c1 + c2) - d3, d2 = -2 log((-log(c1 e^(-1/2) + c2) - d3) / d1)."""
+    o, leaf = float(outlier_ratio), float(leaf)
+    c1, c2 = 10.0 * (1.0 - o), o / (leaf * leaf * leaf)
+    d3 = -math.log(c2)
+    d1 = -math.log(c1 + c2) - d3
+    d2 = -2.0 * math.log((-math.log(c1 * math.exp(-0.5) + c2) - d3) / d1)
+    return d1, d2
+
+
+def ndt_term_host(w, p, R, mean, evec, wgt, d2):
+    """One NDT term on the host (flimo_ndt_term_host: the function the kernels of ``scan_ndt`` call, with libm's exp): ``w`` the
+    float32 world point, ``p`` the float32 scan point, ``R`` [3, 3] the float32 rotation, (``mean``, ``evec`` [3, 3], ``wgt``) a
+    cell of ``ndt_cells``.  Returns (live, m, e, sums [28]: H's 21, g's 6, the score).  Needs no device."""
+    L = _lib.load_hip()
+    a = [np.ascontiguousarray(v, dtype=np.float32).reshape(n) for v, n in ((w, 3), (p, 3), (R, 9))]
+    b = [np.ascontiguousarray(v, dtype=np.float64).reshape(n) for v, n in ((mean, 3), (evec, 9), (wgt, 3))]
+    out = np.zeros(30)
+    rc = L.flimo_ndt_term_host(*(v.ctypes.data for v in a + b), float(d2), out.ctypes.data)
+    if rc < 0:
+        raise FlimoError(f"flimo_ndt_term_host failed ({rc})")
+    return rc == 1, float(out[0]), float(out[1]), out[2:].copy()
+
+
+def ndt_align(obj, x26s, slots, hood=7, outlier_ratio=0.55, iters=30, min_valid=30):
+    """Refine pose hypotheses of the resident scan by NDT, coarse to fine: for each slot of ``slots`` in the given order (models
+    built with ``ndt_build``, largest leaf first) ``scan_align`` runs ``iters`` Gauss-Newton steps on ``scan_ndt``'s normal
+    equations at that model's ``d2`` (``ndt_params(outlier_ratio, leaf)``), starting where the previous slot ended.  Returns
+    ``scan_align``'s dict of the LAST slot -- cost is -score, the sum of e negated --, and ``stages``: the dict of every slot."""
+    x = np.array(np.asarray(x26s, np.float64).reshape(-1, 26))
+    stages = []
+    for slot in slots:
+        d2 = ndt_params(outlier_ratio, obj.ndt_info(slot)["leaf"])[1]
+
+        def linearize(xs, _slot=slot, _d2=d2):
+            lin = obj.scan_ndt(_slot, xs, _d2, hood=hood)
+            lin["cost"] = -lin["score"]
+            return lin
+        stages.append(scan_align(obj, x, iters=iters, min_valid=min_valid, linearize=linearize))
+        x = stages[-1]["x26"]
+    if not stages:
+        raise ValueError("ndt_align: no slots")
+    return dict(stages[-1], stages=stages)
 
 
 def eskf_update_fixed(x26, P, H, h, max_iters=3, limits=None, R=0.001, D=5.0):

@@ -253,6 +253,7 @@ extern "C" void flimo_ctx_destroy(flimo_ctx* c) {
   c->gbook.release();
   (void)hipFree(c->d_batch);
   (void)hipFree(c->d_desc_rt); (void)hipFree(c->d_desc_norm);
+  for (flimo_ctx::NdtModel& m : c->ndt) m.release();
   delete c;
 }
 
@@ -270,6 +271,7 @@ extern "C" int flimo_map_config(flimo_ctx* c, const flimo_map_cfg* cfg) {
 
 extern "C" int flimo_map_clear(flimo_ctx* c) {
   if (!c) return FLIMO_ERR_INVALID;
+  if (c->map_n > 0) c->map_epoch++;      // (the resident NDT models stay: flimo_ndt_info reports them stale)
   c->map_n = 0;
   c->grid_valid = false;
   c->fine_valid = false;
@@ -674,6 +676,7 @@ static int map_append_host(flimo_ctx* c, const float4* pts, size_t n) {
   HIPCHK(c, hipMemcpyAsync(c->d_map_raw + c->map_n, pts, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->map_n += n;
+  c->map_epoch++;
   return FLIMO_OK;
 }
 
@@ -766,6 +769,7 @@ static int map_add_device(flimo_ctx* c, const float4* d_pts, size_t m, double st
     t2 = prof ? now() : 0.0;
     c->map_n += (size_t)kept;
     if (kept > 0) {
+      c->map_epoch++;
       // the kept points lie inside the batch box: a superset box only makes the dense grid a little larger
       for (int a = 0; a < 3; a++) { if (bb[a] < c->bb[a]) c->bb[a] = bb[a]; if (bb[3 + a] > c->bb[3 + a]) c->bb[3 + a] = bb[3 + a]; }
     }
@@ -842,6 +846,7 @@ static int map_keep_only(flimo_ctx* c, const float4* kept_pts, size_t kept, size
                          size_t* removed, const char* what) {
   if (kept > n_old) return fail(c, FLIMO_ERR_HIP, "%s: compaction reported %zu of %zu points", what, kept, n_old);
   if (kept == n_old) return FLIMO_OK;
+  c->map_epoch++;
   // ---- clear() ... ----
   const double last_time = c->map_last_time;         // (a crop is no insert)
   const bool had_center = c->have_fine_center;

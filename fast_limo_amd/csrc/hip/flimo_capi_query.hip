@@ -1,7 +1,7 @@
 // fast_limo_amd/csrc/hip/flimo_capi_query.hip -- C ABI (include/flimo_c.h) over the gfx950 kernels: the analysis entries.
 //
 // The call-at-a-time entries over the stored map (k-NN, radius search, normals, outliers, FPFH, keypoints, clusters, planes, voxels,
-// regions) and over the resident scan, correspondences and descriptors (scan fitness / linearize, flimo_corr_*, flimo_desc_*).  Each
+// regions) and over the resident scan, correspondences and descriptors (scan fitness / linearize / NDT, flimo_corr_*, flimo_desc_*).  Each
 // is glue of one shape: check the arguments, take a DevScratch, launch in chunks, copy back, wait once.  The registration path --
 // context, map index, sweep front end, the passes and the chain -- is flimo_capi.hip, which also defines the three functions these
 // entries call into it (ensure_index, flush_deskew, map_remove_masked); struct flimo_ctx and the shared helpers are flimo_ctx.h.
@@ -17,6 +17,7 @@
 #include "flimo_voxel.h"
 #include "flimo_region.h"
 #include "flimo_desc.h"
+#include "flimo_ndt.h"
 
 #pragma clang fp contract(off)
 
@@ -1522,3 +1523,209 @@ extern "C" int flimo_scan_linearize(flimo_ctx* c, const double* x26, size_t np, 
   return FLIMO_OK;
 }
 extern "C" int flimo_set_linearize_chunk(flimo_ctx* c, size_t pairs) { return set_chunk(c, &flimo_ctx::linearize_chunk, pairs, (size_t)1 << 20); }
+
+// ---- NDT: the resident cell model and the per-pose score and normal equations against it (pcl::NormalDistributionsTransform) ------
+// kernels: flimo_ndt.hip.  The build is voxels_device's launches (flimo_map_voxels with cov: the same keys, sort and moments, so the
+// same bits), then the eigen-solve per voxel, a scan of the cell flags and the pack into the slot's own buffers -- 8 + 4 + 24 + 128 B
+// a cell, kept until the slot is rebuilt or cleared; the new model replaces the old one only when everything has succeeded.  A pass
+// runs in chunks of whole poses as flimo_scan_linearize, three launches a chunk (lookup, reduce, final); reads d_scan only.
+static int ndt_slot_check(flimo_ctx* c, const char* what, int slot) {
+  if (slot < 0 || slot >= FLIMO_NDT_SLOTS) return fail(c, FLIMO_ERR_INVALID, "%s: slot must be in 0..%d", what, FLIMO_NDT_SLOTS - 1);
+  return FLIMO_OK;
+}
+extern "C" int flimo_ndt_build(flimo_ctx* c, int slot, const flimo_ndt_cfg* cfg, size_t* nc) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "ndt build: null cfg");
+  { const int rc = ndt_slot_check(c, "ndt build", slot); if (rc) return rc; }
+  const flimo_voxel_cfg vk{cfg->leaf, FLIMO_VOXEL_KEEP_FIRST, 1};
+  { const int rc = voxel_check(c, 0, 0, &vk, "ndt build"); if (rc) return rc; }
+  if (cfg->min_pts < 3 || !(cfg->eig_ratio > 0.0 && cfg->eig_ratio <= 1.0))      // (a NaN fails the test)
+    return fail(c, FLIMO_ERR_INVALID, "ndt build: min_pts must be >= 3 and eig_ratio in (0, 1]");
+  struct Fresh {      // the model under construction: released unless it is handed to the slot
+    flimo_ctx::NdtModel m;
+    bool keep = false;
+    ~Fresh() { if (!keep) m.release(); }
+  } f;
+  f.m.built = true; f.m.leaf = cfg->leaf; f.m.min_pts = cfg->min_pts; f.m.eig_ratio = cfg->eig_ratio;
+  f.m.map_n = c->map_n; f.m.epoch = c->map_epoch;
+  if (c->map_n > 0) {
+    VoxelDev d;
+    flimo_voxel_stats st;
+    { const int rc = voxels_device(c, 0, 0, vk, 2, (size_t)-1, false, false, d, &st); if (rc) return rc; }
+    const size_t nv = d.nv;
+    if (nv > 0) {
+      size_t tmp_bytes = 0;
+      HIPCHK(c, ndt_tmp_bytes(nv, &tmp_bytes));
+      double* d_eig = d.mem.get<double>(12 * nv);
+      uint32_t* d_flag = d.mem.get<uint32_t>(nv + 1);
+      uint32_t* d_pos = d.mem.get<uint32_t>(nv + 1);
+      void* d_tmp = d.mem.get<unsigned char>(tmp_bytes);
+      { const int rc = d.mem.ok(c); if (rc) return rc; }
+      HIPCHK(c, launch_ndt_cells(c->stream, d.count, d.cov, (unsigned)nv, cfg->min_pts, d_eig, d_flag, d_pos, d_tmp, tmp_bytes));
+      uint32_t cells = 0;
+      HIPCHK(c, hipMemcpyAsync(&cells, d_pos + nv, sizeof cells, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      if ((size_t)cells > nv) return fail(c, FLIMO_ERR_HIP, "ndt build: counted %u cells of %zu voxels", cells, nv);
+      if (cells > 0) {
+        HIPCHK(c, hipMalloc(&f.m.d_keys, (size_t)cells * sizeof(unsigned long long)));
+        HIPCHK(c, hipMalloc(&f.m.d_count, (size_t)cells * sizeof(int32_t)));
+        HIPCHK(c, hipMalloc(&f.m.d_eval, (size_t)cells * 3 * sizeof(double)));
+        HIPCHK(c, hipMalloc(&f.m.d_cells, (size_t)cells * sizeof(NdtCell)));
+        HIPCHK(c, launch_ndt_pack(c->stream, d_flag, d_pos, d.ijk, d.count, d.centroid, d_eig, (unsigned)nv, cfg->eig_ratio, f.m.d_keys, f.m.d_count,
+                                  f.m.d_eval, f.m.d_cells));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+      }
+      f.m.nc = cells;
+    }
+  }
+  c->ndt[slot].release();
+  c->ndt[slot] = f.m;
+  f.keep = true;
+  if (nc) *nc = f.m.nc;
+  return FLIMO_OK;
+}
+static int ndt_model_of(flimo_ctx* c, const char* what, int slot, const flimo_ctx::NdtModel** m) {
+  { const int rc = ndt_slot_check(c, what, slot); if (rc) return rc; }
+  if (!c->ndt[slot].built) return fail(c, FLIMO_ERR_NOMAP, "%s: slot %d holds no model (flimo_ndt_build)", what, slot);
+  *m = &c->ndt[slot];
+  return FLIMO_OK;
+}
+extern "C" int flimo_ndt_cells(flimo_ctx* c, int slot, size_t cap, size_t* nc, int32_t* ijk, int32_t* count, double* mean, double* evec, double* wgt,
+                               double* eval) {
+  if (!c) return FLIMO_ERR_INVALID;
+  const flimo_ctx::NdtModel* m = nullptr;
+  { const int rc = ndt_model_of(c, "ndt cells", slot, &m); if (rc) return rc; }
+  const size_t n = m->nc;
+  const bool arrays = ijk || count || mean || evec || wgt || eval;
+  if (nc) *nc = n;
+  if (arrays && n > cap) return fail(c, FLIMO_ERR_TOO_LARGE, "ndt cells: the model has %zu cells, the arrays hold %zu", n, cap);
+  if (!arrays || n == 0) return FLIMO_OK;
+  ctx_enter(c);
+  // (through vectors of the call: the caller's arrays stay untouched if a copy fails)
+  std::vector<unsigned long long> keys(ijk ? n : 0);
+  std::vector<int32_t> cnt(count ? n : 0);
+  std::vector<double> ev(eval ? 3 * n : 0);
+  std::vector<NdtCell> rec((mean || evec || wgt) ? n : 0);
+  if (ijk) HIPCHK(c, hipMemcpyAsync(keys.data(), m->d_keys, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  if (count) HIPCHK(c, hipMemcpyAsync(cnt.data(), m->d_count, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (eval) HIPCHK(c, hipMemcpyAsync(ev.data(), m->d_eval, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (!rec.empty()) HIPCHK(c, hipMemcpyAsync(rec.data(), m->d_cells, n * sizeof(NdtCell), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (ijk) for (size_t v = 0; v < n; v++) voxel_cell_of_key(keys[v], ijk + 3 * v);
+  if (count) memcpy(count, cnt.data(), n * sizeof(int32_t));
+  if (eval) memcpy(eval, ev.data(), 3 * n * sizeof(double));
+  for (size_t v = 0; v < rec.size(); v++) {
+    if (mean) memcpy(mean + 3 * v, rec[v].mean, 3 * sizeof(double));
+    if (evec) memcpy(evec + 9 * v, rec[v].v, 9 * sizeof(double));
+    if (wgt) memcpy(wgt + 3 * v, rec[v].w, 3 * sizeof(double));
+  }
+  return FLIMO_OK;
+}
+extern "C" int flimo_ndt_info(flimo_ctx* c, int slot, flimo_ndt_model_info* info) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!info) return fail(c, FLIMO_ERR_INVALID, "ndt info: null info");
+  const flimo_ctx::NdtModel* m = nullptr;
+  { const int rc = ndt_model_of(c, "ndt info", slot, &m); if (rc) return rc; }
+  info->cells = m->nc; info->map_size_at_build = m->map_n; info->eig_ratio = m->eig_ratio; info->leaf = m->leaf; info->min_pts = m->min_pts;
+  info->stale = m->epoch != c->map_epoch ? 1 : 0;
+  return FLIMO_OK;
+}
+extern "C" int flimo_ndt_clear(flimo_ctx* c, int slot) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (slot != -1) { const int rc = ndt_slot_check(c, "ndt clear", slot); if (rc) return rc; }
+  ctx_enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int s = 0; s < FLIMO_NDT_SLOTS; s++)
+    if (slot == -1 || slot == s) c->ndt[s].release();
+  return FLIMO_OK;
+}
+extern "C" int flimo_scan_ndt(flimo_ctx* c, int slot, const double* x26, size_t np, int hood, double d2, int32_t* valid, int64_t* cells, double* H,
+                              double* g, double* score, double* terms, int32_t* term_cell) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if ((np > 0 && !x26) || !valid || !cells || !H || !g || !score)
+    return fail(c, FLIMO_ERR_INVALID, "scan ndt: null poses / valid / cells / H / g / score");
+  if (hood != 1 && hood != NDT_HOOD_MAX) return fail(c, FLIMO_ERR_INVALID, "scan ndt: hood must be 1 or 7");
+  if (!(d2 > 0.0) || std::isinf(d2)) return fail(c, FLIMO_ERR_INVALID, "scan ndt: d2 must be finite and > 0");
+  const flimo_ctx::NdtModel* m = nullptr;
+  { const int rc = ndt_model_of(c, "scan ndt", slot, &m); if (rc) return rc; }
+  if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan ndt: the number of poses must be below 2^31");
+  { const int rc = check_poses_finite(c, "scan ndt", x26, np); if (rc) return rc; }
+  if (np == 0) return FLIMO_OK;
+  const size_t n = c->scan_n;
+  if (n > ((size_t)1 << 28)) return fail(c, FLIMO_ERR_TOO_LARGE, "scan ndt: a scan of more than 2^28 points");
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  if (terms) for (size_t i = 0; i < np * n * 14; i++) terms[i] = nan;      // (the slots a pass has no cell for stay so)
+  if (term_cell) for (size_t i = 0; i < np * n * 7; i++) term_cell[i] = -1;
+  if (n == 0 || m->nc == 0) {      // an empty scan or model: no pair has a term
+    for (size_t j = 0; j < np; j++) { valid[j] = 0; cells[j] = 0; score[j] = 0.0; }
+    for (size_t i = 0; i < np * 21; i++) H[i] = 0.0;
+    for (size_t i = 0; i < np * 6; i++) g[i] = 0.0;
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  { const int rcf = flush_deskew(c); if (rcf) return rcf; }
+  // scratch of this call, released on every exit path
+  DevScratch d;
+  const size_t k = pose_chunk(c->ndt_chunk, n, np);
+  const size_t nseg = scan_ndt_segments((unsigned)n), slots = k * n * (size_t)hood;
+  float* d_poses = d.get<float>(k * 12);
+  int32_t* d_cell = d.get<int32_t>(slots);
+  double* d_e = d.get<double>(slots);
+  double* d_m = terms ? d.get<double>(slots) : nullptr;
+  double* d_part = d.get<double>(k * nseg * NDT_NUM);
+  int32_t* d_part_cnt = d.get<int32_t>(k * nseg * 2);
+  double* d_sums = d.get<double>(k * NDT_NUM);
+  long long* d_counts = d.get<long long>(k * 2);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  std::vector<float> rt(k * 12);
+  std::vector<double> sums(k * NDT_NUM), he, hm;
+  std::vector<long long> counts(k * 2);
+  std::vector<int32_t> hc;
+  if (terms) { he.resize(slots); hm.resize(slots); }
+  if (terms || term_cell) hc.resize(slots);
+  for (size_t a = 0; a < np; a += k) {
+    const size_t kk = std::min(k, np - a), used = kk * n * (size_t)hood;
+    { const int rc = upload_poses(c, x26 + 26 * a, kk, rt, d_poses); if (rc) return rc; }
+    HIPCHK(c, launch_scan_ndt(c->stream, c->d_scan, (unsigned)n, d_poses, (unsigned)kk, hood, 1.0f / m->leaf, d2, m->d_keys, m->d_cells, (unsigned)m->nc,
+                              d_cell, d_e, d_m, d_part, d_part_cnt, d_sums, d_counts));
+    HIPCHK(c, hipMemcpyAsync(sums.data(), d_sums, kk * NDT_NUM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(counts.data(), d_counts, kk * 2 * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    if (terms) {
+      HIPCHK(c, hipMemcpyAsync(he.data(), d_e, used * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(hm.data(), d_m, used * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!hc.empty()) HIPCHK(c, hipMemcpyAsync(hc.data(), d_cell, used * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    // (the next chunk's poses overwrite rt and d_poses: one wait per chunk)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t j = 0; j < kk; j++) {
+      memcpy(H + 21 * (a + j), &sums[NDT_NUM * j], 21 * sizeof(double));
+      memcpy(g + 6 * (a + j), &sums[NDT_NUM * j + 21], 6 * sizeof(double));
+      score[a + j] = sums[NDT_NUM * j + 27];
+      valid[a + j] = (int32_t)counts[2 * j];
+      cells[a + j] = (int64_t)counts[2 * j + 1];
+    }
+    if (!hc.empty())
+      for (size_t pr = 0; pr < kk * n; pr++)
+        for (int s = 0; s < hood; s++) {
+          const size_t from = pr * (size_t)hood + (size_t)s, to = (a * n + pr) * 7 + (size_t)s;
+          const bool present = hc[from] >= 0;
+          if (term_cell) term_cell[to] = hc[from];
+          if (terms && present) { terms[2 * to] = hm[from]; terms[2 * to + 1] = he[from]; }
+        }
+  }
+  return FLIMO_OK;
+}
+extern "C" int flimo_set_ndt_chunk(flimo_ctx* c, size_t pairs) { return set_chunk(c, &flimo_ctx::ndt_chunk, pairs, (size_t)1 << 20); }
+extern "C" int flimo_ndt_term_host(const float w3[3], const float p3[3], const float R9[9], const double mean3[3], const double evec9[9],
+                                   const double wgt3[3], double d2, double out30[30]) {
+  if (!w3 || !p3 || !R9 || !mean3 || !evec9 || !wgt3 || !out30) return FLIMO_ERR_INVALID;
+  NdtCell r;
+  memcpy(r.mean, mean3, sizeof r.mean);
+  memcpy(r.v, evec9, sizeof r.v);
+  memcpy(r.w, wgt3, sizeof r.w);
+  r.pad = 0.0;
+  double acc[NDT_NUM] = {0.0};
+  const bool live = ndt_term(w3, p3, R9, r, -0.5 * d2, d2, [](double x) { return ::exp(x); }, &out30[0], &out30[1], acc);
+  memcpy(out30 + 2, acc, sizeof acc);
+  return live ? 1 : 0;
+}

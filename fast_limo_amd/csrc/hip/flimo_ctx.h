@@ -67,6 +67,26 @@ struct flimo_ctx {
   size_t desc_chunk = (size_t)1 << 16;      // queries per chunk of flimo_desc_match (flimo_set_desc_chunk)
   size_t desc_split = 0;                    // reference rows per split of its grid; 0: chosen per chunk, to fill the device
   float desc_last_ms = 0.f;                 // GPU time of the last call's launches (timing level >= 1)
+  // the resident NDT cell models (flimo_ndt_build): each a SNAPSHOT of the map's voxels at its build -- inserts, removals and
+  // flimo_map_clear leave it alone and only move map_epoch on, which is how flimo_ndt_info knows a model stale
+  struct NdtModel {
+    bool built = false;
+    size_t nc = 0, map_n = 0;               // cells; stored points at the build
+    float leaf = 0.f;
+    int min_pts = 0;
+    double eig_ratio = 0.0;
+    uint64_t epoch = 0;                     // map_epoch at the build
+    unsigned long long* d_keys = nullptr;   // [nc] ascending
+    int32_t* d_count = nullptr;             // [nc]
+    double* d_eval = nullptr;               // [nc][3] l0 <= l1 <= l2, before the clamp
+    void* d_cells = nullptr;                // [nc] NdtCell (flimo_ndt.h)
+    void release() {
+      (void)hipFree(d_keys); (void)hipFree(d_count); (void)hipFree(d_eval); (void)hipFree(d_cells);
+      *this = NdtModel{};
+    }
+  } ndt[FLIMO_NDT_SLOTS];
+  uint64_t map_epoch = 0;                   // bumped whenever the stored points change: the insert, the clear, the removals' shared tail
+  size_t ndt_chunk = (size_t)1 << 20;       // (pose, point) pairs per chunk of flimo_scan_ndt (flimo_set_ndt_chunk)
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
   IndexTables idx;                 // the index of the main grid (GridView, flimo_types.h): tiles, directory, escapes, xstart
   GridView grid{};

@@ -460,4 +460,22 @@ hipError_t launch_desc_pack(hipStream_t st, const float* x, unsigned n, int dim,
 hipError_t launch_desc_match(hipStream_t st, const float* rt, const float* rnorm, unsigned nr, unsigned tiles_per_split, const float* q,
                              float* qnorm, unsigned nq, int dim, int k, unsigned long long* part, int32_t* idx, float* dist, int32_t* cnt);
 
+// flimo_ndt.hip -- the NDT cell model and the per-pose sums against it (flimo_ndt_build, flimo_scan_ndt; flimo_c.h).
+//  launch_ndt_cells   behind launch_voxel_moments: eig [nv][12] (l0 l1 l2, v0, v1, v2 of every voxel of at least min_pts points),
+//                     flag [nv + 1] (1: a cell; flag[nv] = 0) and its exclusive scan pos [nv + 1]: pos[nv] is the number of cells.
+//                     tmp holds ndt_tmp_bytes(nv).
+//  launch_ndt_pack    keys / cnt / eval [nc][3] / cells [nc] (128-byte records, flimo_ndt.h) of the cells, ascending key.
+//  launch_scan_ndt    a chunk of np poses (np <= FIT_MAX_POSES, n * np <= 2^28): cell / e [np * n * hood] and m (may be null) per
+//                     (pair, neighbour slot); part [np * segments][28], part_cnt [np * segments][2]; sums [np][28], counts [np][2]
+//                     (pairs with a live term, live terms).  nc >= 1.
+hipError_t ndt_tmp_bytes(size_t nv, size_t* bytes);
+hipError_t launch_ndt_cells(hipStream_t st, const int32_t* count, const double* cov, unsigned nv, int min_pts, double* eig, uint32_t* flag,
+                            uint32_t* pos, void* tmp, size_t tmp_bytes);
+hipError_t launch_ndt_pack(hipStream_t st, const uint32_t* flag, const uint32_t* pos, const int32_t* ijk, const int32_t* count, const double* centroid,
+                           const double* eig, unsigned nv, double eig_ratio, unsigned long long* keys, int32_t* cnt, double* eval, void* cells);
+unsigned scan_ndt_segments(unsigned n);
+hipError_t launch_scan_ndt(hipStream_t st, const float4* scan, unsigned n, const float* poses, unsigned np, int hood, float inv, double d2,
+                           const unsigned long long* keys, const void* cells, unsigned nc, int32_t* cell, double* e, double* m, double* part,
+                           int32_t* part_cnt, double* sums, long long* counts);
+
 }  // namespace flimo

@@ -354,6 +354,28 @@ int flimo_loc_scan_linearize(flimo_loc* L, const double* x26, size_t np, int k, 
   if (!L) return FLIMO_ERR_INVALID;
   return flimo_scan_linearize(ctx_of(L), x26, np, k, max_dist, min_pts, max_curv, valid, H, g, cost, rows, pair_cnt);
 }
+int flimo_loc_ndt_build(flimo_loc* L, int slot, const flimo_ndt_cfg* cfg, size_t* nc) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return L->map->ndt_build(slot, cfg, nc);
+}
+int flimo_loc_ndt_cells(flimo_loc* L, int slot, size_t cap, size_t* nc, int32_t* ijk, int32_t* count, double* mean, double* evec, double* wgt,
+                        double* eval) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_ndt_cells(ctx_of(L), slot, cap, nc, ijk, count, mean, evec, wgt, eval);
+}
+int flimo_loc_ndt_info(flimo_loc* L, int slot, flimo_ndt_model_info* info) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_ndt_info(ctx_of(L), slot, info);
+}
+int flimo_loc_ndt_clear(flimo_loc* L, int slot) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_ndt_clear(ctx_of(L), slot);
+}
+int flimo_loc_scan_ndt(flimo_loc* L, int slot, const double* x26, size_t np, int hood, double d2, int32_t* valid, int64_t* cells, double* H, double* g,
+                       double* score, double* terms, int32_t* term_cell) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return L->map->ndt(slot, x26, np, hood, d2, valid, cells, H, g, score, terms, term_cell);
+}
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
 // the map insert that ends a scan runs on the Mapper's worker thread (Mapper::add_scan): wait for it / switch it off

@@ -713,6 +713,19 @@ int Mapper::linearize(const double* x26, size_t np, int k, float max_dist, int m
                               (pair_cnt && np && n) ? pair_cnt->data() : nullptr);
 }
 
+// NDT: the resident cell model and one linearisation against it (an insert, a crop or a carve on the worker thread ends first)
+int Mapper::ndt_build(int slot, const flimo_ndt_cfg* cfg, size_t* nc) {
+  sync();
+  if (!ctx_ && !attach(device_, cell_size_)) return FLIMO_ERR_NO_DEVICE;
+  return flimo_ndt_build(ctx_, slot, cfg, nc);
+}
+int Mapper::ndt(int slot, const double* x26, size_t np, int hood, double d2, int32_t* valid, int64_t* cells, double* H, double* g, double* score,
+                double* terms, int32_t* term_cell) {
+  sync();
+  if (!ctx_) return FLIMO_ERR_NOMAP;
+  return flimo_scan_ndt(ctx_, slot, x26, np, hood, d2, valid, cells, H, g, score, terms, term_cell);
+}
+
 // pose hypotheses from point correspondences (an insert, a crop or a carve on the worker thread ends first)
 int Mapper::corr_poses(const float* src_xyz, const float* dst_xyz, size_t m, const int32_t* tri, size_t nh, const flimo_corr_cfg* cfg,
                        int32_t* status, int32_t* inliers, double* sum_sqd, double* pose, float* pair_sqd) {

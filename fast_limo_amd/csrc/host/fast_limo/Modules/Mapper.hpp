@@ -152,6 +152,13 @@ class fast_limo::Mapper {
   int linearize(const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, std::vector<int32_t>& valid,
                 std::vector<double>& H, std::vector<double>& g, std::vector<double>& cost, std::vector<double>* rows = nullptr,
                 std::vector<int32_t>* pair_cnt = nullptr);
+  // NDT (flimo_ndt_build / flimo_scan_ndt, same arguments and results): a resident cell model of the map's voxels at cfg->leaf in one
+  // of FLIMO_NDT_SLOTS slots -- a snapshot that later inserts and crops leave alone --, and per pose hypothesis the score and the 6 x 6
+  // Gauss-Newton normal equations of the resident scan against it.  Both run after an insert, a crop or a carve on the worker thread
+  // has ended.  Return a FLIMO_* code.
+  int ndt_build(int slot, const flimo_ndt_cfg* cfg, size_t* nc = nullptr);
+  int ndt(int slot, const double* x26, size_t np, int hood, double d2, int32_t* valid, int64_t* cells, double* H, double* g, double* score,
+          double* terms = nullptr, int32_t* term_cell = nullptr);
   // Pose hypotheses from point correspondences (flimo_corr_poses, same arguments and results): src[i] in the body frame is dst[i] in
   // the map's; per triplet of tri the pre-rejection, the closed-form pose and the correspondences it explains.  Reads neither the map
   // nor the resident scan: it only runs on this Mapper's context (created here if there is none yet), after an insert, a crop or a

@@ -885,6 +885,94 @@ int flimo_scan_fitness(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t 
 int flimo_scan_linearize(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t np, int k, float max_dist, int min_pts, float max_curv,
                          int32_t* valid /* [np] */, double* H /* [np][21] */, double* g /* [np][6] */, double* cost /* [np] */,
                          double* rows /* [np][n][7], may be NULL */, int32_t* pair_cnt /* [np][n], may be NULL */);
+/* ---- NDT, the normal distributions transform (what pcl::NormalDistributionsTransform computes; the reference has no counterpart):
+ *      the consumer of flimo_map_voxels' covariances.  A resident CELL MODEL is built from the map's voxels once; flimo_scan_ndt then
+ *      gives, for each of np pose hypotheses, the score and the 6 x 6 Gauss-Newton normal equations of the resident scan against it.
+ *      A pair costs a cell lookup instead of a neighbour search, and the basin grows with the leaf: a context holds FLIMO_NDT_SLOTS
+ *      models, one per leaf of a coarse-to-fine schedule (fast_limo_amd.api.ndt_align runs one). ----
+ * flimo_ndt_build(ctx, slot, cfg, &nc): the model of slot `slot` from the voxels of the WHOLE map at cfg->leaf.
+ *  - key, count, centroid and cov of a voxel are exactly flimo_map_voxels' (leaf), bit for bit: its key, sort and moments launches run
+ *    on the device and nothing is downloaded.
+ *  - the eigen-solve of cov is the cyclic Jacobi of flimo_map_normals' plane (the same rotations; ascending eigenvalues
+ *    l0 <= l1 <= l2, on a tie the lower column first); all three unit vectors v0 v1 v2 are kept with whatever sign the rotations leave.
+ *  - a voxel is a CELL iff count >= min_pts and l2 > 0.0.  Its record: floor = eig_ratio * l2 (one float64 product),
+ *    lk' = lk < floor ? floor : lk, wk = 1.0 / lk'; mean[3] (the centroid), v[3][3], w[3], padded to 128 bytes.  Cells are listed in
+ *    ascending key, that is ascending (cz, cy, cx).
+ *  - the model is a SNAPSHOT: inserts, crops, removals and flimo_map_clear do not touch it (a saved map's model survives a local-map
+ *    crop); flimo_ndt_info's `stale` is 1 once the stored points have changed since the build.  A build on an empty map gives an
+ *    empty model: FLIMO_OK, *nc = 0.  A build into a slot that holds a model replaces it.
+ *  FLIMO_ERR_INVALID: NULL ctx / cfg, a leaf flimo_map_voxels rejects, min_pts < 3, eig_ratio NaN or outside (0, 1], slot outside
+ *  0 .. FLIMO_NDT_SLOTS - 1; FLIMO_ERR_TOO_LARGE as flimo_map_voxels.  On an error *nc and the slot's old model are untouched.
+ *  Calling rules of flimo_map_voxels (no pass in flight); the map, the scan and the bits of a later pass are unchanged.  nc may be NULL.
+ * flimo_ndt_cells(ctx, slot, cap, &nc, ...): downloads the model, any subset of the arrays (NULL skips one): ijk [nc][3] = (cx, cy, cz),
+ *  count [nc], mean [nc][3], evec [nc][9] = v0 v1 v2, wgt [nc][3], eval [nc][3] = l0 l1 l2 before the clamp.  The cap rule is
+ *  flimo_map_voxels': cap < nc with an array asked for gives FLIMO_ERR_TOO_LARGE, *nc is set and the arrays are untouched.
+ *  FLIMO_ERR_NOMAP: no model in the slot.
+ * flimo_ndt_info(ctx, slot, &info): FLIMO_ERR_NOMAP for an empty slot.  flimo_ndt_clear(ctx, slot): frees a slot, slot = -1 all. */
+#define FLIMO_NDT_SLOTS 4
+typedef struct flimo_ndt_cfg {
+  float leaf;
+  int min_pts;       /* >= 3 */
+  double eig_ratio;  /* in (0, 1]: no eigenvalue of a cell counts as smaller than eig_ratio * l2 (PCL: 0.01) */
+} flimo_ndt_cfg;
+typedef struct flimo_ndt_model_info {
+  uint64_t cells;              /* nc */
+  uint64_t map_size_at_build;  /* stored points the build saw */
+  double eig_ratio;
+  float leaf;
+  int min_pts;
+  int stale;                   /* 1: the stored points have changed since the build */
+} flimo_ndt_model_info;
+int flimo_ndt_build(flimo_ctx* ctx, int slot, const flimo_ndt_cfg* cfg, size_t* nc);
+int flimo_ndt_cells(flimo_ctx* ctx, int slot, size_t cap, size_t* nc, int32_t* ijk /* [nc][3] */, int32_t* count /* [nc] */,
+                    double* mean /* [nc][3] */, double* evec /* [nc][9] */, double* wgt /* [nc][3] */, double* eval /* [nc][3] */);
+int flimo_ndt_info(flimo_ctx* ctx, int slot, flimo_ndt_model_info* info);
+int flimo_ndt_clear(flimo_ctx* ctx, int slot);
+/* ---- the NDT score and normal equations of the resident scan against the model of `slot`, for each of np pose hypotheses ----
+ * x26 [np][26]: the poses; only pos and rot are read.  n = flimo_scan_size(ctx).  Every quantity is float64 and uncontracted unless
+ * stated otherwise.
+ *  - w(j, i): the float32 world point of resident scan point i under pose j, exactly as in flimo_scan_fitness.
+ *  - its cell is voxel_key(w, 1.0f / leaf) -- flimo_voxel_key_host's function; an outside point or a NaN coordinate gives no cell.
+ *    Neighbour slots: s = 0 is the own cell (cx, cy, cz); with hood == 7, s = 1..6 are -x, +x, -y, +y, -z, +z (PCL's DIRECT1 and
+ *    DIRECT7).  A neighbour whose coordinate leaves the lattice is absent, and so is a key that is no CELL of the model.
+ *  - the term of a present cell (p: the float32 scan point widened; R: the nine float32 rotation entries of the pose's matrix widened;
+ *    k = 0, 1, 2):
+ *      r   = (double)w - mean                               (three subtractions)
+ *      d_k = v_k.x*r.x + (v_k.y*r.y + v_k.z*r.z)
+ *      m   = w0*(d_0*d_0) + (w1*(d_1*d_1) + w2*(d_2*d_2))
+ *      x   = c * m,  c = -0.5 * d2 formed once, on the host;   e = exp(x), the device's float64 exp
+ *    The term is LIVE iff e > 0.0 (underflow and NaN alike are excluded: no 0 * inf ever enters a sum).  For a live term
+ *      a_k = R^T v_k, b_k = p x a_k, J_k = (a_k, b_k) in the associations flimo_scan_linearize states for a, b and J
+ *      s_k = (e * d2) * w_k
+ *    and, for k ascending: H_ab += (s_k * J_k[a]) * J_k[b] for the 21 upper-triangle entries, g_a += (s_k * d_k) * J_k[a];
+ *    score += e once per term.
+ *  g is the gradient of F = -sum e under flimo_scan_linearize's body-frame perturbation, H its positive-semidefinite Gauss-Newton
+ *  part sum e*d2*B^T Sigma'^-1 B: H xi = -g is the step fast_limo_amd.api.scan_align already solves.  The overall factor d1 of PCL's
+ *  score is the caller's (fast_limo_amd.api.ndt_params gives PCL's (d1, d2) for an outlier ratio and a leaf).
+ * Outputs, host memory, per pose:
+ *  - H [np][21], g [np][6], score [np]; valid [np]: the pairs with at least one live term; cells [np]: the live terms.
+ *    The 28 sums are taken in the shape of flimo_scan_linearize: segments of 4096 slots, thread t of 256
+ *    takes slots t, t + 256, .. in ascending order -- inside a slot the neighbour slots s ascend, inside a term k ascends, every
+ *    contribution ONE add onto the thread's accumulator, which starts at +0.0 --, a butterfly over 64 lanes,
+ *    ((w0 + w1) + (w2 + w3)), then the segments in ascending order.  No floating-point atomics: the bits depend on the scan, the
+ *    model, the pose, hood and d2 alone -- not on np, the other poses, the chunking or the lookup method.
+ *  - terms [np][n][7][2] (may be NULL): (m, e) per neighbour slot, NaN for an absent cell (with hood == 1 the slots 1..6 are absent);
+ *    term_cell [np][n][7] (may be NULL): the cell's position in flimo_ndt_cells' listing, or -1.
+ * FLIMO_ERR_NOMAP: no model in `slot`.  FLIMO_ERR_INVALID: NULL ctx / x26 (np > 0) / valid / cells / H / g / score, hood not 1 or
+ * 7, d2 NaN, <= 0 or infinite, a non-finite value among x26[j][0..6], a slot outside 0 .. FLIMO_NDT_SLOTS - 1.  FLIMO_ERR_TOO_LARGE:
+ * np >= 2^31.  The outputs are untouched on any error.  FLIMO_OK with all sums and counts 0 (terms NaN, term_cell -1) for an empty
+ * model and an empty scan; np == 0 returns FLIMO_OK and touches nothing.  A pending deskew runs first; the scan, the map, the model
+ * and the bits of a later pass are unchanged.  Device memory is taken per chunk of 2^20 (pose, point) pairs -- whole poses --, 12 B a
+ * neighbour slot (84 B a pair at hood 7; 20 B a slot when terms are asked for). */
+int flimo_scan_ndt(flimo_ctx* ctx, int slot, const double* x26 /* [np][26] */, size_t np, int hood /* 1 or 7 */, double d2,
+                   int32_t* valid /* [np] */, int64_t* cells /* [np] */, double* H /* [np][21] */, double* g /* [np][6] */,
+                   double* score /* [np] */, double* terms /* [np][n][7][2], may be NULL */, int32_t* term_cell /* [np][n][7], may be NULL */);
+/* One term on the host: the function the kernels call (flimo_ndt.h), with libm's exp.  w3: the float32 world point, p3: the float32
+ * scan point, R9: the rotation, row-major; mean3 / evec9 / wgt3: a cell as flimo_ndt_cells lists it.  out30 = m, e, then the 28
+ * contributions (H's 21, g's 6, the score) summed over k from +0.0 -- all 0 when the term is not live.  Returns 1 for a live term,
+ * 0 otherwise, FLIMO_ERR_INVALID for a NULL pointer.  Needs no device. */
+int flimo_ndt_term_host(const float w3[3], const float p3[3], const float R9[9], const double mean3[3], const double evec9[9],
+                        const double wgt3[3], double d2, double out30[30]);
 /* ---- pose hypotheses from point correspondences: what pcl::SampleConsensusPrerejective does per sample (the reference's
  *      relocation branch gets the same from KISS-Matcher's pruning and solver) -- minimal samples of three correspondences, a cheap
  *      polygon test, a closed-form rigid pose for each of the rest, and the count of the correspondences each pose explains, for

@@ -199,6 +199,18 @@ int    flimo_loc_scan_fitness(flimo_loc* L, const double* x26, size_t np, float 
  * valid 0; rows / pair_cnt have no element).  The Localizer's own update does not use it. */
 int    flimo_loc_scan_linearize(flimo_loc* L, const double* x26, size_t np, int k, float max_dist, int min_pts, float max_curv, int32_t* valid,
                                 double* H, double* g, double* cost, double* rows, int32_t* pair_cnt);
+/* NDT against the Localizer's map (the reference has no counterpart): flimo_ndt_build / flimo_ndt_cells / flimo_ndt_info /
+ * flimo_ndt_clear / flimo_scan_ndt (include/flimo_c.h: same arguments, same results, same error codes) on the map's context, after an
+ * insert, a crop or a carve still running behind the last sweep has ended.  The models are snapshots: the sweeps' inserts and the
+ * local map's crops leave them alone and flimo_ndt_info reports them stale.  A Localizer that has no map yet builds an empty model.
+ * The Localizer's own update does not use them. */
+int    flimo_loc_ndt_build(flimo_loc* L, int slot, const flimo_ndt_cfg* cfg, size_t* nc);
+int    flimo_loc_ndt_cells(flimo_loc* L, int slot, size_t cap, size_t* nc, int32_t* ijk, int32_t* count, double* mean, double* evec, double* wgt,
+                           double* eval);
+int    flimo_loc_ndt_info(flimo_loc* L, int slot, flimo_ndt_model_info* info);
+int    flimo_loc_ndt_clear(flimo_loc* L, int slot);
+int    flimo_loc_scan_ndt(flimo_loc* L, int slot, const double* x26, size_t np, int hood, double d2, int32_t* valid, int64_t* cells, double* H,
+                          double* g, double* score, double* terms, int32_t* term_cell);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
