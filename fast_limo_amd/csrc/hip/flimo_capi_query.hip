@@ -18,6 +18,7 @@
 #include "flimo_region.h"
 #include "flimo_desc.h"
 #include "flimo_ndt.h"
+#include "flimo_sums.h"
 
 #pragma clang fp contract(off)
 
@@ -324,14 +325,14 @@ static int outliers_device(flimo_ctx* c, size_t first, size_t n, const flimo_out
   { const int rc = need_index(c, "map outliers"); if (rc) return rc; }
   ctx_enter(c);
   const size_t m = std::min(std::min(n, std::max<size_t>(c->outlier_chunk, 1)), (size_t)1 << 24);
-  const unsigned nseg = outlier_segments(n);
+  const unsigned nseg = sum_segments(n);
   d.mean = d.mem.get<double>(n);
   d.cnt = d.mem.get<int32_t>(n);
   d.mask = d.mem.get<unsigned char>(n);
   uint2* d_work = d.mem.get<uint2>(m);
   unsigned* d_nwork = d.mem.get<unsigned>(1);
   double* d_part = d.mem.get<double>(nseg);
-  unsigned* d_part_cnt = d.mem.get<unsigned>(nseg);
+  int32_t* d_part_cnt = d.mem.get<int32_t>(nseg);
   unsigned long long* d_words = d.mem.get<unsigned long long>(3);      // {sum bits, |T|, few | far << 32}
   { const int rc = d.mem.ok(c); if (rc) return rc; }
   // (a chunk's worklist is read by its own second launch only: the stream orders the chunks, nothing waits in between)
@@ -1169,8 +1170,10 @@ extern "C" int flimo_set_voxel_plan(flimo_ctx* c, int plan) {
 // per chunk the poses' matrices go up (pose_from_x26 on the host, as flimo_scan_to_world forms them), three launches (block search,
 // walk over the tiles, the reduction per pose), two numbers per pose -- and the slots, where asked for -- come back; device scratch
 // is the chunk's, whatever np.  Reads d_scan only: d_scan_world and the pass's buffers are left alone.
-// what the two entries over pose hypotheses share: the poses' check (what: the caller's name in the message) ...
-static int check_poses_finite(flimo_ctx* c, const char* what, const double* x26, size_t np) {
+// what the entries over pose hypotheses (this one, flimo_scan_linearize, flimo_scan_ndt) share: the poses' check (what: the
+// caller's name in the message) ...
+static int check_poses(flimo_ctx* c, const char* what, const double* x26, size_t np) {
+  if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the number of poses must be below 2^31", what);
   for (size_t j = 0; j < np; j++)
     for (int t = 0; t < 7; t++)
       if (!std::isfinite(x26[26 * j + t])) return fail(c, FLIMO_ERR_INVALID, "%s: pose %zu has a non-finite position or rotation", what, j);
@@ -1182,23 +1185,50 @@ static size_t pose_chunk(size_t chunk_pairs, size_t n, size_t np) {
   const size_t pairs_max = std::min<size_t>(std::max<size_t>(chunk_pairs, 1), (size_t)1 << 28);
   return std::min(np, std::min<size_t>(std::max<size_t>(pairs_max / n, 1), FIT_MAX_POSES));
 }
-// ... and the RT rows of k poses, formed in rt and sent to d_poses
-static int upload_poses(flimo_ctx* c, const double* x26, size_t k, std::vector<float>& rt, float* d_poses) {
-  for (size_t j = 0; j < k; j++) {
-    PoseMats P;
-    pose_from_x26(x26 + 26 * j, P);
-    memcpy(&rt[12 * j], P.RT, 12 * sizeof(float));
+// ... the entry into the stream: a pending deskew of the resident scan runs first ...
+static int enter_flushed(flimo_ctx* c) { ctx_enter(c); return flush_deskew(c); }
+// ... the loop over the chunks.  m: the poses of a chunk; d_poses is the first buffer of the entry's scratch d (the entry checks
+// d.ok() after its own).  run, per chunk of k poses from pose a on: the RT rows are formed in rt and go up, launch(a, k) queues the
+// entry's kernels, copy_back(a, k) its hipMemcpyAsyncs (each returns a FLIMO code), one wait, then after(a, k) on the host ...
+struct PoseChunks {
+  size_t m;
+  float* d_poses;
+  std::vector<float> rt;
+  PoseChunks(DevScratch& d, size_t chunk_pairs, size_t n, size_t np) : m(pose_chunk(chunk_pairs, n, np)), d_poses(d.get<float>(m * 12)), rt(m * 12) {}
+  template <class Launch, class CopyBack, class After>
+  int run(flimo_ctx* c, const double* x26, size_t np, Launch launch, CopyBack copy_back, After after) {
+    for (size_t a = 0; a < np; a += m) {
+      const size_t k = std::min(m, np - a);
+      for (size_t j = 0; j < k; j++) {
+        PoseMats P;
+        pose_from_x26(x26 + 26 * (a + j), P);
+        memcpy(&rt[12 * j], P.RT, 12 * sizeof(float));
+      }
+      HIPCHK(c, hipMemcpyAsync(d_poses, rt.data(), k * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      { const int rc = launch(a, k); if (rc) return rc; }
+      { const int rc = copy_back(a, k); if (rc) return rc; }
+      // (the next chunk's poses overwrite rt and d_poses: one wait per chunk)
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      after(a, k);
+    }
+    return FLIMO_OK;
   }
-  HIPCHK(c, hipMemcpyAsync(d_poses, rt.data(), k * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  return FLIMO_OK;
+};
+// ... a chunk's sums [k][28] taken apart into H, g and the cost or score of the poses from a on, and H and g of np poses without a term
+static void unpack_sums(const double* sums, size_t a, size_t k, double* H, double* g, double* last) {
+  for (size_t j = 0; j < k; j++) {
+    memcpy(H + 21 * (a + j), sums + 28 * j, 21 * sizeof(double));
+    memcpy(g + 6 * (a + j), sums + 28 * j + 21, 6 * sizeof(double));
+    last[a + j] = sums[28 * j + 27];
+  }
 }
+static void zero_H_g(double* H, double* g, size_t np) { std::fill_n(H, np * 21, 0.0); std::fill_n(g, np * 6, 0.0); }
 extern "C" int flimo_scan_fitness(flimo_ctx* c, const double* x26, size_t np, float max_dist, int32_t* inliers, double* sum_sqd, float* nn_sqd,
                                   int32_t* nn_idx) {
   if (!c) return FLIMO_ERR_INVALID;
   if ((np > 0 && !x26) || !inliers || !sum_sqd) return fail(c, FLIMO_ERR_INVALID, "scan fitness: null poses / inliers / sum_sqd");
   { const int rc = check_gate(c, "scan fitness", max_dist); if (rc) return rc; }
-  if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan fitness: the number of poses must be below 2^31");
-  { const int rc = check_poses_finite(c, "scan fitness", x26, np); if (rc) return rc; }
+  { const int rc = check_poses(c, "scan fitness", x26, np); if (rc) return rc; }
   if (np == 0) return FLIMO_OK;
   const size_t n = c->scan_n;
   { const int rc0 = ensure_index(c); if (rc0) return rc0; }
@@ -1208,12 +1238,12 @@ extern "C" int flimo_scan_fitness(flimo_ctx* c, const double* x26, size_t np, fl
     if (nn_idx) for (size_t i = 0; i < np * n; i++) nn_idx[i] = -1;
     return FLIMO_OK;
   }
-  ctx_enter(c);
-  { const int rcf = flush_deskew(c); if (rcf) return rcf; }
+  { const int rcf = enter_flushed(c); if (rcf) return rcf; }
   // scratch of this call, released on every exit path
   DevScratch d;
-  const size_t m = pose_chunk(c->fitness_chunk, n, np);
-  float* d_poses = d.get<float>(m * 12);
+  PoseChunks P(d, c->fitness_chunk, n, np);
+  const size_t m = P.m;
+  float* d_poses = P.d_poses;
   float* d_sqd = d.get<float>(m * n);
   int32_t* d_idx = nn_idx ? d.get<int32_t>(m * n) : nullptr;
   uint2* d_work = d.get<uint2>(m * n);
@@ -1221,20 +1251,20 @@ extern "C" int flimo_scan_fitness(flimo_ctx* c, const double* x26, size_t np, fl
   int32_t* d_inliers = d.get<int32_t>(m);
   double* d_sum = d.get<double>(m);
   { const int rc = d.ok(c); if (rc) return rc; }
-  std::vector<float> rt(m * 12);
-  for (size_t a = 0; a < np; a += m) {
-    const size_t k = std::min(m, np - a);
-    { const int rc = upload_poses(c, x26 + 26 * a, k, rt, d_poses); if (rc) return rc; }
-    HIPCHK(c, launch_scan_fitness(c->stream, c->grid, c->d_scan, (unsigned)n, d_poses, (unsigned)k, max_dist, d_sqd, d_idx, d_work, d_nwork,
-                                  d_inliers, d_sum));
-    HIPCHK(c, hipMemcpyAsync(inliers + a, d_inliers, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sum_sqd + a, d_sum, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (nn_sqd) HIPCHK(c, hipMemcpyAsync(nn_sqd + a * n, d_sqd, k * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (nn_idx) HIPCHK(c, hipMemcpyAsync(nn_idx + a * n, d_idx, k * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    // (the next chunk's poses overwrite rt and d_poses: one wait per chunk)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return FLIMO_OK;
+  return P.run(c, x26, np,
+    [&](size_t, size_t k) -> int {
+      HIPCHK(c, launch_scan_fitness(c->stream, c->grid, c->d_scan, (unsigned)n, d_poses, (unsigned)k, max_dist, d_sqd, d_idx, d_work, d_nwork,
+                                    d_inliers, d_sum));
+      return FLIMO_OK;
+    },
+    [&](size_t a, size_t k) -> int {
+      HIPCHK(c, hipMemcpyAsync(inliers + a, d_inliers, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(sum_sqd + a, d_sum, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      if (nn_sqd) HIPCHK(c, hipMemcpyAsync(nn_sqd + a * n, d_sqd, k * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      if (nn_idx) HIPCHK(c, hipMemcpyAsync(nn_idx + a * n, d_idx, k * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      return FLIMO_OK;
+    },
+    [](size_t, size_t) {});
 }
 extern "C" int flimo_set_fitness_chunk(flimo_ctx* c, size_t pairs) { return set_chunk(c, &flimo_ctx::fitness_chunk, pairs, (size_t)1 << 22); }
 
@@ -1469,27 +1499,24 @@ extern "C" int flimo_scan_linearize(flimo_ctx* c, const double* x26, size_t np, 
   { const int rc = check_gate(c, "scan linearize", max_dist); if (rc) return rc; }
   if (std::isnan(max_curv) || max_curv < 0.f) return fail(c, FLIMO_ERR_INVALID, "scan linearize: max_curv must be >= 0 or INFINITY");
   if (k < 3 || k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "scan linearize: k must be in 3..%d", FLIMO_KNN_MAX_K);
-  if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan linearize: the number of poses must be below 2^31");
-  { const int rc = check_poses_finite(c, "scan linearize", x26, np); if (rc) return rc; }
+  { const int rc = check_poses(c, "scan linearize", x26, np); if (rc) return rc; }
   if (np == 0) return FLIMO_OK;
   const size_t n = c->scan_n;
   { const int rc0 = ensure_index(c); if (rc0) return rc0; }
   if (n > ((size_t)1 << 28)) return fail(c, FLIMO_ERR_TOO_LARGE, "scan linearize: a scan of more than 2^28 points");
   if (n == 0 || !c->grid_valid || max_dist == 0.f) {      // an empty scan or map, a gate that admits nothing: no pair has a plane
     for (size_t j = 0; j < np; j++) { valid[j] = 0; cost[j] = 0.0; }
-    for (size_t i = 0; i < np * 21; i++) H[i] = 0.0;
-    for (size_t i = 0; i < np * 6; i++) g[i] = 0.0;
+    zero_H_g(H, g, np);
     if (rows) for (size_t i = 0; i < np * n * 7; i++) rows[i] = std::numeric_limits<double>::quiet_NaN();
     if (pair_cnt) for (size_t i = 0; i < np * n; i++) pair_cnt[i] = 0;
     return FLIMO_OK;
   }
-  ctx_enter(c);
-  { const int rcf = flush_deskew(c); if (rcf) return rcf; }
+  { const int rcf = enter_flushed(c); if (rcf) return rcf; }
   // scratch of this call, released on every exit path
   DevScratch d;
-  const size_t m = pose_chunk(c->linearize_chunk, n, np);
-  const size_t nseg = scan_linearize_segments((unsigned)n);
-  float* d_poses = d.get<float>(m * 12);
+  PoseChunks P(d, c->linearize_chunk, n, np);
+  const size_t m = P.m, nseg = sum_segments(n);
+  float* d_poses = P.d_poses;
   int32_t* d_cnt = d.get<int32_t>(m * n);
   double* d_mom = d.get<double>(m * n * 9);
   uint2* d_work = d.get<uint2>(m * n);
@@ -1499,28 +1526,27 @@ extern "C" int flimo_scan_linearize(flimo_ctx* c, const double* x26, size_t np, 
   double* d_part = d.get<double>(m * nseg * 28);
   int32_t* d_part_cnt = d.get<int32_t>(m * nseg);
   double* d_sums = d.get<double>(m * 28);
-  int32_t* d_valid = d.get<int32_t>(m);
+  long long* d_valid = d.get<long long>(m);
   { const int rc = d.ok(c); if (rc) return rc; }
-  std::vector<float> rt(m * 12);
   std::vector<double> sums(m * 28);
-  for (size_t a = 0; a < np; a += m) {
-    const size_t kk = std::min(m, np - a);
-    { const int rc = upload_poses(c, x26 + 26 * a, kk, rt, d_poses); if (rc) return rc; }
-    HIPCHK(c, launch_scan_linearize(c->stream, c->grid, c->d_map_raw, c->d_scan, (unsigned)n, d_poses, (unsigned)kk, k, max_dist, min_pts, max_curv,
-                                    d_cnt, d_mom, d_work, d_nwork, d_rows, d_ok, d_part, d_part_cnt, d_sums, d_valid));
-    HIPCHK(c, hipMemcpyAsync(valid + a, d_valid, kk * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sums.data(), d_sums, kk * 28 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (rows) HIPCHK(c, hipMemcpyAsync(rows + a * n * 7, d_rows, kk * n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (pair_cnt) HIPCHK(c, hipMemcpyAsync(pair_cnt + a * n, d_cnt, kk * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    // (the next chunk's poses overwrite rt and d_poses: one wait per chunk)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t j = 0; j < kk; j++) {
-      memcpy(H + 21 * (a + j), &sums[28 * j], 21 * sizeof(double));
-      memcpy(g + 6 * (a + j), &sums[28 * j + 21], 6 * sizeof(double));
-      cost[a + j] = sums[28 * j + 27];
-    }
-  }
-  return FLIMO_OK;
+  std::vector<long long> counts(m);
+  return P.run(c, x26, np,
+    [&](size_t, size_t kk) -> int {
+      HIPCHK(c, launch_scan_linearize(c->stream, c->grid, c->d_map_raw, c->d_scan, (unsigned)n, d_poses, (unsigned)kk, k, max_dist, min_pts, max_curv,
+                                      d_cnt, d_mom, d_work, d_nwork, d_rows, d_ok, d_part, d_part_cnt, d_sums, d_valid));
+      return FLIMO_OK;
+    },
+    [&](size_t a, size_t kk) -> int {
+      HIPCHK(c, hipMemcpyAsync(counts.data(), d_valid, kk * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(sums.data(), d_sums, kk * 28 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      if (rows) HIPCHK(c, hipMemcpyAsync(rows + a * n * 7, d_rows, kk * n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      if (pair_cnt) HIPCHK(c, hipMemcpyAsync(pair_cnt + a * n, d_cnt, kk * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      return FLIMO_OK;
+    },
+    [&](size_t a, size_t kk) {
+      unpack_sums(sums.data(), a, kk, H, g, cost);
+      for (size_t j = 0; j < kk; j++) valid[a + j] = (int32_t)counts[j];
+    });
 }
 extern "C" int flimo_set_linearize_chunk(flimo_ctx* c, size_t pairs) { return set_chunk(c, &flimo_ctx::linearize_chunk, pairs, (size_t)1 << 20); }
 
@@ -1648,8 +1674,7 @@ extern "C" int flimo_scan_ndt(flimo_ctx* c, int slot, const double* x26, size_t 
   if (!(d2 > 0.0) || std::isinf(d2)) return fail(c, FLIMO_ERR_INVALID, "scan ndt: d2 must be finite and > 0");
   const flimo_ctx::NdtModel* m = nullptr;
   { const int rc = ndt_model_of(c, "scan ndt", slot, &m); if (rc) return rc; }
-  if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan ndt: the number of poses must be below 2^31");
-  { const int rc = check_poses_finite(c, "scan ndt", x26, np); if (rc) return rc; }
+  { const int rc = check_poses(c, "scan ndt", x26, np); if (rc) return rc; }
   if (np == 0) return FLIMO_OK;
   const size_t n = c->scan_n;
   if (n > ((size_t)1 << 28)) return fail(c, FLIMO_ERR_TOO_LARGE, "scan ndt: a scan of more than 2^28 points");
@@ -1658,17 +1683,15 @@ extern "C" int flimo_scan_ndt(flimo_ctx* c, int slot, const double* x26, size_t 
   if (term_cell) for (size_t i = 0; i < np * n * 7; i++) term_cell[i] = -1;
   if (n == 0 || m->nc == 0) {      // an empty scan or model: no pair has a term
     for (size_t j = 0; j < np; j++) { valid[j] = 0; cells[j] = 0; score[j] = 0.0; }
-    for (size_t i = 0; i < np * 21; i++) H[i] = 0.0;
-    for (size_t i = 0; i < np * 6; i++) g[i] = 0.0;
+    zero_H_g(H, g, np);
     return FLIMO_OK;
   }
-  ctx_enter(c);
-  { const int rcf = flush_deskew(c); if (rcf) return rcf; }
+  { const int rcf = enter_flushed(c); if (rcf) return rcf; }
   // scratch of this call, released on every exit path
   DevScratch d;
-  const size_t k = pose_chunk(c->ndt_chunk, n, np);
-  const size_t nseg = scan_ndt_segments((unsigned)n), slots = k * n * (size_t)hood;
-  float* d_poses = d.get<float>(k * 12);
+  PoseChunks P(d, c->ndt_chunk, n, np);
+  const size_t k = P.m, nseg = sum_segments(n), slots = k * n * (size_t)hood;
+  float* d_poses = P.d_poses;
   int32_t* d_cell = d.get<int32_t>(slots);
   double* d_e = d.get<double>(slots);
   double* d_m = terms ? d.get<double>(slots) : nullptr;
@@ -1677,43 +1700,44 @@ extern "C" int flimo_scan_ndt(flimo_ctx* c, int slot, const double* x26, size_t 
   double* d_sums = d.get<double>(k * NDT_NUM);
   long long* d_counts = d.get<long long>(k * 2);
   { const int rc = d.ok(c); if (rc) return rc; }
-  std::vector<float> rt(k * 12);
+  static_assert(NDT_NUM == 28, "unpack_sums takes 28 numbers a pose");
   std::vector<double> sums(k * NDT_NUM), he, hm;
   std::vector<long long> counts(k * 2);
   std::vector<int32_t> hc;
   if (terms) { he.resize(slots); hm.resize(slots); }
   if (terms || term_cell) hc.resize(slots);
-  for (size_t a = 0; a < np; a += k) {
-    const size_t kk = std::min(k, np - a), used = kk * n * (size_t)hood;
-    { const int rc = upload_poses(c, x26 + 26 * a, kk, rt, d_poses); if (rc) return rc; }
-    HIPCHK(c, launch_scan_ndt(c->stream, c->d_scan, (unsigned)n, d_poses, (unsigned)kk, hood, 1.0f / m->leaf, d2, m->d_keys, m->d_cells, (unsigned)m->nc,
-                              d_cell, d_e, d_m, d_part, d_part_cnt, d_sums, d_counts));
-    HIPCHK(c, hipMemcpyAsync(sums.data(), d_sums, kk * NDT_NUM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(counts.data(), d_counts, kk * 2 * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    if (terms) {
-      HIPCHK(c, hipMemcpyAsync(he.data(), d_e, used * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(hm.data(), d_m, used * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (!hc.empty()) HIPCHK(c, hipMemcpyAsync(hc.data(), d_cell, used * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    // (the next chunk's poses overwrite rt and d_poses: one wait per chunk)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t j = 0; j < kk; j++) {
-      memcpy(H + 21 * (a + j), &sums[NDT_NUM * j], 21 * sizeof(double));
-      memcpy(g + 6 * (a + j), &sums[NDT_NUM * j + 21], 6 * sizeof(double));
-      score[a + j] = sums[NDT_NUM * j + 27];
-      valid[a + j] = (int32_t)counts[2 * j];
-      cells[a + j] = (int64_t)counts[2 * j + 1];
-    }
-    if (!hc.empty())
-      for (size_t pr = 0; pr < kk * n; pr++)
-        for (int s = 0; s < hood; s++) {
-          const size_t from = pr * (size_t)hood + (size_t)s, to = (a * n + pr) * 7 + (size_t)s;
-          const bool present = hc[from] >= 0;
-          if (term_cell) term_cell[to] = hc[from];
-          if (terms && present) { terms[2 * to] = hm[from]; terms[2 * to + 1] = he[from]; }
-        }
-  }
-  return FLIMO_OK;
+  return P.run(c, x26, np,
+    [&](size_t, size_t kk) -> int {
+      HIPCHK(c, launch_scan_ndt(c->stream, c->d_scan, (unsigned)n, d_poses, (unsigned)kk, hood, 1.0f / m->leaf, d2, m->d_keys, m->d_cells,
+                                (unsigned)m->nc, d_cell, d_e, d_m, d_part, d_part_cnt, d_sums, d_counts));
+      return FLIMO_OK;
+    },
+    [&](size_t, size_t kk) -> int {
+      const size_t used = kk * n * (size_t)hood;
+      HIPCHK(c, hipMemcpyAsync(sums.data(), d_sums, kk * NDT_NUM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(counts.data(), d_counts, kk * 2 * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+      if (terms) {
+        HIPCHK(c, hipMemcpyAsync(he.data(), d_e, used * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hm.data(), d_m, used * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      }
+      if (!hc.empty()) HIPCHK(c, hipMemcpyAsync(hc.data(), d_cell, used * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      return FLIMO_OK;
+    },
+    [&](size_t a, size_t kk) {
+      unpack_sums(sums.data(), a, kk, H, g, score);
+      for (size_t j = 0; j < kk; j++) {
+        valid[a + j] = (int32_t)counts[2 * j];
+        cells[a + j] = (int64_t)counts[2 * j + 1];
+      }
+      if (!hc.empty())
+        for (size_t pr = 0; pr < kk * n; pr++)
+          for (int s = 0; s < hood; s++) {
+            const size_t from = pr * (size_t)hood + (size_t)s, to = (a * n + pr) * 7 + (size_t)s;
+            const bool present = hc[from] >= 0;
+            if (term_cell) term_cell[to] = hc[from];
+            if (terms && present) { terms[2 * to] = hm[from]; terms[2 * to + 1] = he[from]; }
+          }
+    });
 }
 extern "C" int flimo_set_ndt_chunk(flimo_ctx* c, size_t pairs) { return set_chunk(c, &flimo_ctx::ndt_chunk, pairs, (size_t)1 << 20); }
 extern "C" int flimo_ndt_term_host(const float w3[3], const float p3[3], const float R9[9], const double mean3[3], const double evec9[9],

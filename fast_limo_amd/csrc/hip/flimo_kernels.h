@@ -334,12 +334,11 @@ hipError_t launch_knn_k_normals(hipStream_t st, const GridView& G, const float4*
 // kk_slot_sum of the float64 widenings of fl_sqrt(sqd) over them / cnt, NaN for cnt 0.  Scratch: work ([nq]), nwork.
 hipError_t launch_outlier_search(hipStream_t st, const GridView& G, const float4* map_raw, unsigned first, int nq, int k, float max_dist,
                                  double* mean, int32_t* cnt, uint2* work, unsigned* nwork);
-// The statistics over a range's n slots, T = {i : cnt[i] >= need}, in two levels of one fixed shape (flimo_knn_k.hip).  pass 0:
-// out[0] = the bits of the float64 sum of mean over T, out[1] = |T|; pass 1: out[0] = the bits of the sum of (mean - mu)^2 over T.
-// part / part_cnt: outlier_segments(n) words each; out: two device words.
-unsigned outlier_segments(size_t n);
+// The statistics over a range's n slots, T = {i : cnt[i] >= need}, as sums of the shape of flimo_sums.h.  pass 0: out[0] = the bits
+// of the float64 sum of mean over T, out[1] = |T|; pass 1: out[0] = the bits of the sum of (mean - mu)^2 over T (out[1] = |T| again).
+// part / part_cnt: sum_segments(n) words each; out: two device words.
 hipError_t launch_outlier_sum(hipStream_t st, const double* mean, const int32_t* cnt, unsigned n, int need, int pass, double mu, double* part,
-                              unsigned* part_cnt, unsigned long long* out);
+                              int32_t* part_cnt, unsigned long long* out);
 // mask[i] = cnt[i] < min_pts, or (stat_on and cnt[i] >= need and mean[i] > threshold); counts[0] / counts[1] (device): how many by
 // the first / the second rule
 hipError_t launch_outlier_mask(hipStream_t st, const double* mean, const int32_t* cnt, unsigned n, int min_pts, int need, bool stat_on,
@@ -381,11 +380,10 @@ hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* 
 // point-to-plane row {J0..J5, d} and the per-pose sums of the normal equations (flimo_scan_linearize, flimo_c.h).  sums [np][28]:
 // the 21 upper-triangle sums of H, the 6 of g, the cost; valid [np].  n * np <= 2^28, np <= FIT_MAX_POSES.
 // Scratch per pair: cnt (4 B), mom (72 B), work (8 B), rows (56 B), ok (1 B); per pose and segment of the scan
-// (scan_linearize_segments(n) of them): part (28 doubles), part_cnt; nwork (one counter).
-unsigned scan_linearize_segments(unsigned n);
+// (sum_segments(n) of them, flimo_sums.h): part (28 doubles), part_cnt; nwork (one counter).
 hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4* map_raw, const float4* scan, unsigned n, const float* poses,
                                  unsigned np, int k, float max_dist, int min_pts, float max_curv, int32_t* cnt, double* mom, uint2* work,
-                                 unsigned* nwork, double* rows, unsigned char* ok, double* part, int32_t* part_cnt, double* sums, int32_t* valid);
+                                 unsigned* nwork, double* rows, unsigned char* ok, double* part, int32_t* part_cnt, double* sums, long long* valid);
 
 // flimo_corr.hip -- pose hypotheses from point correspondences (flimo_corr_poses, flimo_c.h) for a chunk of nh triplets tri [nh][3]
 // (every index already checked to lie in [0, m)) over the clouds src / dst [m][3], packed xyz: the solve per hypothesis (status
@@ -473,7 +471,6 @@ hipError_t launch_ndt_cells(hipStream_t st, const int32_t* count, const double* 
                             uint32_t* pos, void* tmp, size_t tmp_bytes);
 hipError_t launch_ndt_pack(hipStream_t st, const uint32_t* flag, const uint32_t* pos, const int32_t* ijk, const int32_t* count, const double* centroid,
                            const double* eig, unsigned nv, double eig_ratio, unsigned long long* keys, int32_t* cnt, double* eval, void* cells);
-unsigned scan_ndt_segments(unsigned n);
 hipError_t launch_scan_ndt(hipStream_t st, const float4* scan, unsigned n, const float* poses, unsigned np, int hood, float inv, double d2,
                            const unsigned long long* keys, const void* cells, unsigned nc, int32_t* cell, double* e, double* m, double* part,
                            int32_t* part_cnt, double* sums, long long* counts);

@@ -35,6 +35,7 @@
 #include "flimo_math.h"
 #include "flimo_kernels.h"
 #include "flimo_jacobi.h"
+#include "flimo_sums.h"
 
 #pragma clang fp contract(off)
 
@@ -676,15 +677,8 @@ __global__ __launch_bounds__(FIT_RED) void fit_reduce_kernel(const float* __rest
 // KK_BLOCK / L consecutive scan points of ONE pose as the fitness' does (LinJob); the pair's moments (72 B) and count go to the
 // chunk's scratch, a pair the block search cannot prove to the worklist and the walk over the tiles.  A third launch, one THREAD per
 // pair, runs kk_plane on the moments -- flimo_map_normals' plane of the query w, bit for bit -- and writes the pair's row
-// {J0..J5, d} and its validity; every term is float64 in the association flimo_c.h states.  The sums have two levels, both of one
-// fixed shape that depends on n alone:
-//   level 1  the scan's slots are cut into segments of LIN_SEG; one workgroup of LIN_RED threads per (segment, pose): thread t adds
-//            the 28 products of slots t, t + LIN_RED, ... of its segment in ascending order (an invalid slot adds +0.0), a butterfly
-//            over the 64 lanes of each wave, then ((wave 0 + wave 1) + (wave 2 + wave 3))
-//   level 2  one thread per (pose, number) adds the pose's segment partials in ascending order of the segment
-// No atomics on floating-point values.
-constexpr int LIN_RED = 256;                    // threads of a level-1 workgroup
-constexpr int LIN_SEG = 4096;                   // slots of a segment: 16 per thread
+// {J0..J5, d} and its validity; every term is float64 in the association flimo_c.h states.  The sums have the shape of flimo_sums.h,
+// a row being a pose and a slot a scan point: a slot adds its 28 products, an invalid one +0.0.
 constexpr int LIN_NUM = 28;                     // 21 of H, 6 of g, the cost
 
 // the pairs, each ended in its moments; need and max_curv are lin_finish_kernel's
@@ -748,19 +742,17 @@ __global__ __launch_bounds__(KK_BLOCK) void lin_finish_kernel(LinJob A, const in
   ok[at] = valid ? 1 : 0;
 }
 
-// level 1: workgroup (segment, pose) over the slots [seg * LIN_SEG, min(n, (seg + 1) * LIN_SEG)) of its pose
-__global__ __launch_bounds__(LIN_RED) void lin_reduce_kernel(const double* __restrict__ rows, const unsigned char* __restrict__ ok, unsigned n,
+// level 1: workgroup (segment, pose) over the slots [seg * SUM_SEG, min(n, (seg + 1) * SUM_SEG)) of its pose
+__global__ __launch_bounds__(SUM_RED) void lin_reduce_kernel(const double* __restrict__ rows, const unsigned char* __restrict__ ok, unsigned n,
                                                              unsigned nseg, double* __restrict__ part, int32_t* __restrict__ part_cnt) {
-  __shared__ double s_sum[LIN_RED / 64][LIN_NUM];
-  __shared__ int s_cnt[LIN_RED / 64];
   const unsigned seg = blockIdx.x, pose = blockIdx.y;
   const size_t base = (size_t)pose * (size_t)n;
-  const unsigned end = min(n, (seg + 1u) * (unsigned)LIN_SEG);
+  const unsigned end = min(n, (seg + 1u) * (unsigned)SUM_SEG);
   double acc[LIN_NUM];
 #pragma unroll
   for (int t = 0; t < LIN_NUM; t++) acc[t] = 0.0;
-  int c = 0;
-  for (unsigned i = seg * (unsigned)LIN_SEG + threadIdx.x; i < end; i += LIN_RED) {
+  int c[1] = {0};
+  for (unsigned i = seg * (unsigned)SUM_SEG + threadIdx.x; i < end; i += SUM_RED) {
     const bool v = ok[base + i] != 0;
     const double* Rw = rows + (size_t)7 * (base + i);
     double J[7];
@@ -774,45 +766,9 @@ __global__ __launch_bounds__(LIN_RED) void lin_reduce_kernel(const double* __res
 #pragma unroll
     for (int a = 0; a < 6; a++) acc[21 + a] = acc[21 + a] + (v ? J[a] * J[6] : 0.0);
     acc[27] = acc[27] + (v ? J[6] * J[6] : 0.0);
-    c += v ? 1 : 0;
+    c[0] += v ? 1 : 0;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < LIN_NUM; t++) {
-    double v = acc[t];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
-    acc[t] = v;
-  }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) c += __shfl_xor(c, o, 64);
-  if (lane == 0) {
-#pragma unroll
-    for (int t = 0; t < LIN_NUM; t++) s_sum[wave][t] = acc[t];
-    s_cnt[wave] = c;
-  }
-  __syncthreads();
-  const size_t slot = (size_t)pose * (size_t)nseg + seg;
-  if (threadIdx.x < LIN_NUM) part[slot * LIN_NUM + threadIdx.x] = (s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x]) + (s_sum[2][threadIdx.x] + s_sum[3][threadIdx.x]);
-  if (threadIdx.x == 0) part_cnt[slot] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-}
-
-// level 2: thread (pose, number) adds the pose's segment partials in ascending order; sums: [np][LIN_NUM]
-__global__ __launch_bounds__(KK_BLOCK) void lin_final_kernel(const double* __restrict__ part, const int32_t* __restrict__ part_cnt, unsigned np,
-                                                             unsigned nseg, double* __restrict__ sums, int32_t* __restrict__ valid) {
-  const size_t g = (size_t)blockIdx.x * KK_BLOCK + threadIdx.x;
-  if (g >= (size_t)np * (LIN_NUM + 1)) return;
-  const size_t pose = g / (LIN_NUM + 1);
-  const int t = (int)(g % (LIN_NUM + 1));
-  if (t == LIN_NUM) {
-    int c = 0;
-    for (unsigned s = 0; s < nseg; s++) c += part_cnt[pose * nseg + s];
-    valid[pose] = c;
-  } else {
-    double v = 0.0;
-    for (unsigned s = 0; s < nseg; s++) v = v + part[(pose * nseg + s) * LIN_NUM + t];
-    sums[pose * LIN_NUM + t] = v;
-  }
+  sum_tail(acc, c, pose, nseg, seg, part, part_cnt);
 }
 
 // ---- mean neighbour distances of stored points (flimo_map_outliers) -------------------------------------------------------------
@@ -820,16 +776,8 @@ __global__ __launch_bounds__(KK_BLOCK) void lin_final_kernel(const double* __res
 // at distance 0.  The group ends the query in registers: the slot whose insertion index is the point's own is dropped -- when no
 // slot holds it and the list is full (more than k exact duplicates of lower index come first), the last one is --, c = the slots
 // left, S = kk_slot_sum over the float64 widenings of fl_sqrt(sqd) with the dropped and the empty slots at +0.0: 8 B + 4 B per
-// point, the list goes nowhere.  The statistics over a range's mean[] / cnt[] have two levels of one fixed shape that depends on n
-// alone (lin_reduce_kernel's):
-//   level 1  the range's slots are cut into segments of OUT_SEG; one workgroup of OUT_RED threads per segment: thread t adds the
-//            terms of slots t, t + OUT_RED, ... of its segment in ascending order (a slot outside T adds +0.0), a butterfly over
-//            the 64 lanes of each wave, then ((wave 0 + wave 1) + (wave 2 + wave 3))
-//   level 2  one thread adds the segment partials in ascending order of the segment
-// The term is m (pass 0, which also counts T) or (m - mu) * (m - mu) (pass 1).  No atomics on floating-point values.
-constexpr int OUT_RED = 256;                    // threads of a level-1 workgroup
-constexpr int OUT_SEG = 4096;                   // slots of a segment: 16 per thread
-
+// point, the list goes nowhere.  The statistics over a range's mean[] / cnt[] are sums of the shape of flimo_sums.h with one row and
+// one number: a slot's term is m (pass 0, which also counts T) or (m - mu) * (m - mu) (pass 1), a slot outside T adds +0.0.
 template <int L>
 __device__ __forceinline__ void knnk_mean_dist(unsigned first, int k1, kk_u64 gate_key, int lane, int q, bool live, kk_u64 mine,
                                                double* __restrict__ mean, int32_t* __restrict__ cnt) {
@@ -860,44 +808,22 @@ struct OutlierJob : KkStored {      // (k: the neighbours asked for + 1)
   }
 };
 
-// level 1 of the statistics: workgroup `seg` over the slots [seg * OUT_SEG, min(n, (seg + 1) * OUT_SEG)) of the range; T: cnt >= need
+// level 1 of the statistics: workgroup `seg` over the slots [seg * SUM_SEG, min(n, (seg + 1) * SUM_SEG)) of the range; T: cnt >= need
 template <int PASS>
-__global__ __launch_bounds__(OUT_RED) void outlier_sum_kernel(const double* __restrict__ mean, const int32_t* __restrict__ cnt, unsigned n, int need,
-                                                              double mu, double* __restrict__ part, unsigned* __restrict__ part_cnt) {
-  __shared__ double s_sum[OUT_RED / 64];
-  __shared__ unsigned s_cnt[OUT_RED / 64];
+__global__ __launch_bounds__(SUM_RED) void outlier_sum_kernel(const double* __restrict__ mean, const int32_t* __restrict__ cnt, unsigned n, int need,
+                                                              double mu, double* __restrict__ part, int32_t* __restrict__ part_cnt) {
   const unsigned seg = blockIdx.x;
-  const unsigned end = min(n, (seg + 1u) * (unsigned)OUT_SEG);
-  double acc = 0.0;
-  unsigned c = 0;
-  for (unsigned i = seg * (unsigned)OUT_SEG + threadIdx.x; i < end; i += OUT_RED) {
+  const unsigned end = min(n, (seg + 1u) * (unsigned)SUM_SEG);
+  double acc[1] = {0.0};
+  int c[1] = {0};
+  for (unsigned i = seg * (unsigned)SUM_SEG + threadIdx.x; i < end; i += SUM_RED) {
     const bool in = cnt[i] >= need;
     const double m = mean[i];
     const double d = m - mu;
-    acc = acc + (in ? (PASS == 0 ? m : d * d) : 0.0);
-    c += in ? 1u : 0u;
+    acc[0] = acc[0] + (in ? (PASS == 0 ? m : d * d) : 0.0);
+    c[0] += in ? 1 : 0;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) acc = acc + __shfl_xor(acc, o, 64);
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) c += __shfl_xor(c, o, 64);
-  if (lane == 0) { s_sum[wave] = acc; s_cnt[wave] = c; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[seg] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-    part_cnt[seg] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-  }
-}
-// level 2: one thread adds the partials in ascending order; out: {the sum's bits, the count}
-__global__ void outlier_final_kernel(const double* __restrict__ part, const unsigned* __restrict__ part_cnt, unsigned nseg,
-                                     unsigned long long* __restrict__ out) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double v = 0.0;
-  unsigned long long c = 0;
-  for (unsigned s = 0; s < nseg; s++) { v = v + part[s]; c += part_cnt[s]; }
-  out[0] = (unsigned long long)__double_as_longlong(v);
-  out[1] = c;
+  sum_tail(acc, c, 0u, 0u, seg, part, part_cnt);      // (one row: its partials are part[seg])
 }
 // the predicate: few = cnt < min_pts; far = the statistical rule is on, the point is of T and its mean is beyond the threshold
 __global__ __launch_bounds__(KK_BLOCK) void outlier_mask_kernel(const double* __restrict__ mean, const int32_t* __restrict__ cnt, unsigned n, int min_pts,
@@ -1256,15 +1182,14 @@ hipError_t launch_iss_suppress(hipStream_t st, const GridView& G, const float4* 
   return kk_launch(st, G, J, work, nwork);
 }
 
-unsigned outlier_segments(size_t n) { return (unsigned)((n + OUT_SEG - 1) / OUT_SEG); }
-
 hipError_t launch_outlier_sum(hipStream_t st, const double* mean, const int32_t* cnt, unsigned n, int need, int pass, double mu, double* part,
-                              unsigned* part_cnt, unsigned long long* out) {
+                              int32_t* part_cnt, unsigned long long* out) {
   if (n == 0) return hipErrorInvalidValue;
-  const unsigned nseg = outlier_segments(n);
-  if (pass == 0) hipLaunchKernelGGL((outlier_sum_kernel<0>), dim3(nseg), dim3(OUT_RED), 0, st, mean, cnt, n, need, mu, part, part_cnt);
-  else hipLaunchKernelGGL((outlier_sum_kernel<1>), dim3(nseg), dim3(OUT_RED), 0, st, mean, cnt, n, need, mu, part, part_cnt);
-  hipLaunchKernelGGL(outlier_final_kernel, dim3(1), dim3(64), 0, st, part, part_cnt, nseg, out);
+  const unsigned nseg = sum_segments(n);
+  if (pass == 0) hipLaunchKernelGGL((outlier_sum_kernel<0>), dim3(nseg), dim3(SUM_RED), 0, st, mean, cnt, n, need, mu, part, part_cnt);
+  else hipLaunchKernelGGL((outlier_sum_kernel<1>), dim3(nseg), dim3(SUM_RED), 0, st, mean, cnt, n, need, mu, part, part_cnt);
+  // (out[0] takes the sum as a float64 -- its bits --, out[1] the count as a 64-bit integer)
+  launch_sum_final<1, 1>(st, part, part_cnt, 1u, nseg, reinterpret_cast<double*>(out), reinterpret_cast<long long*>(out + 1));
   return hipGetLastError();
 }
 
@@ -1292,11 +1217,9 @@ hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* 
   return hipGetLastError();
 }
 
-unsigned scan_linearize_segments(unsigned n) { return (unsigned)(((size_t)n + LIN_SEG - 1) / LIN_SEG); }
-
 hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4* map_raw, const float4* scan, unsigned n, const float* poses,
                                  unsigned np, int k, float max_dist, int min_pts, float max_curv, int32_t* cnt, double* mom, uint2* work,
-                                 unsigned* nwork, double* rows, unsigned char* ok, double* part, int32_t* part_cnt, double* sums, int32_t* valid) {
+                                 unsigned* nwork, double* rows, unsigned char* ok, double* part, int32_t* part_cnt, double* sums, long long* valid) {
   if (n == 0 || np == 0) return hipSuccess;
   if ((unsigned long long)n * np > 0x10000000ull || np > FIT_MAX_POSES || k < 1 || k > KNNK_MAX_K) return hipErrorInvalidValue;
   LinJob J;
@@ -1310,10 +1233,9 @@ hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4
   if (e != hipSuccess) return e;
   const size_t pairs = (size_t)n * np;
   hipLaunchKernelGGL(lin_finish_kernel, dim3((unsigned)((pairs + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, J, cnt, mom, rows, ok);
-  const unsigned nseg = scan_linearize_segments(n);
-  hipLaunchKernelGGL(lin_reduce_kernel, dim3(nseg, np), dim3(LIN_RED), 0, st, rows, ok, n, nseg, part, part_cnt);
-  hipLaunchKernelGGL(lin_final_kernel, dim3((unsigned)(((size_t)np * (LIN_NUM + 1) + KK_BLOCK - 1) / KK_BLOCK)), dim3(KK_BLOCK), 0, st, part, part_cnt,
-                     np, nseg, sums, valid);
+  const unsigned nseg = sum_segments(n);
+  hipLaunchKernelGGL(lin_reduce_kernel, dim3(nseg, np), dim3(SUM_RED), 0, st, rows, ok, n, nseg, part, part_cnt);
+  launch_sum_final<LIN_NUM, 1>(st, part, part_cnt, np, nseg, sums, valid);
   return hipGetLastError();
 }
 

@@ -10,24 +10,22 @@
 // The passes (per chunk of whole poses):
 //   ndt_lookup_kernel   stage 1, one THREAD per (pair, neighbour slot): the float32 world point, its voxel (voxel_key), the slot's
 //                       key, a binary search of the model's keys, m (ndt_m) and e = exp(-0.5 * d2 * m): 12 B a slot (20 B with m).
-//   ndt_reduce_kernel   stage 2 and level 1 of the sums, the shape of lin_reduce_kernel (flimo_knn_k.hip): workgroup (segment, pose),
-//                       thread t takes slots t, t + NDT_RED, .. of its segment in ascending order, inside a slot the neighbour slots
-//                       ascend; a live term reloads its record (L2-resident: stage 1 just read it) and ndt_term adds the 28
-//                       contributions onto the thread's accumulators, its exp being stage 1's stored e; a butterfly over the 64
-//                       lanes, then ((wave 0 + wave 1) + (wave 2 + wave 3)).
-//   ndt_final_kernel    level 2: one thread per (pose, number) adds the segment partials in ascending order.
+//   ndt_reduce_kernel   stage 2 and level 1 of the sums in the shape of flimo_sums.h, a row being a pose and a slot a scan point:
+//                       inside a slot the neighbour slots ascend; a live term reloads its record (L2-resident: stage 1 just read
+//                       it) and ndt_term adds the 28 contributions onto the thread's accumulators, its exp being stage 1's stored
+//                       e.  Two counts travel with the sums: the pairs with a live term and the live terms.
+//   sum_final_kernel    level 2 (flimo_sums.h).
 // No atomics on floating-point values: the bits depend on the scan, the model, the pose, hood and d2 alone.
 #include "flimo_ndt.h"
 #include "flimo_jacobi.h"
 #include "flimo_prims.h"
 #include "flimo_kernels.h"
+#include "flimo_sums.h"
 
 #pragma clang fp contract(off)
 
 namespace flimo {
 
-constexpr int NDT_RED = 256;       // threads of a level-1 workgroup (LIN_RED)
-constexpr int NDT_SEG = 4096;      // slots of a segment (LIN_SEG)
 constexpr int NDT_BLOCK = 256;
 
 __global__ __launch_bounds__(NDT_BLOCK) void ndt_cell_kernel(const int32_t* __restrict__ count, const double* __restrict__ cov, unsigned nv,
@@ -139,21 +137,19 @@ struct NdtStoredExp {      // stage 2's exp: the value stage 1 stored for this t
   __device__ double operator()(double) const { return e; }
 };
 
-// stage 2 + level 1: workgroup (segment, pose) over the slots [seg * NDT_SEG, min(n, (seg + 1) * NDT_SEG)) of its pose
-__global__ __launch_bounds__(NDT_RED) void ndt_reduce_kernel(NdtPass A, const int32_t* __restrict__ cell, const double* __restrict__ e_in,
+// stage 2 + level 1: workgroup (segment, pose) over the slots [seg * SUM_SEG, min(n, (seg + 1) * SUM_SEG)) of its pose
+__global__ __launch_bounds__(SUM_RED) void ndt_reduce_kernel(NdtPass A, const int32_t* __restrict__ cell, const double* __restrict__ e_in,
                                                              unsigned nseg, double* __restrict__ part, int32_t* __restrict__ part_cnt) {
-  __shared__ double s_sum[NDT_RED / 64][NDT_NUM];
-  __shared__ int s_cnt[NDT_RED / 64][2];
   const unsigned seg = blockIdx.x, pose = blockIdx.y;
   const size_t base = (size_t)pose * (size_t)A.n;
-  const unsigned end = min(A.n, (seg + 1u) * (unsigned)NDT_SEG);
+  const unsigned end = min(A.n, (seg + 1u) * (unsigned)SUM_SEG);
   const float* M = A.poses + 12 * (size_t)pose;
   const float R[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
   double acc[NDT_NUM];
 #pragma unroll
   for (int t = 0; t < NDT_NUM; t++) acc[t] = 0.0;
-  int pairs = 0, terms = 0;
-  for (unsigned i = seg * (unsigned)NDT_SEG + threadIdx.x; i < end; i += NDT_RED) {
+  int c[2] = {0, 0};      // pairs with a live term, live terms
+  for (unsigned i = seg * (unsigned)SUM_SEG + threadIdx.x; i < end; i += SUM_RED) {
     const float4 p4 = A.scan[i];
     const float p[3] = {p4.x, p4.y, p4.z};
     float w[3];
@@ -169,48 +165,10 @@ __global__ __launch_bounds__(NDT_RED) void ndt_reduce_kernel(NdtPass A, const in
       double m, e2;
       live += ndt_term(w, p, R, r, A.cc, A.d2, NdtStoredExp{e}, &m, &e2, acc) ? 1 : 0;
     }
-    terms += live;
-    pairs += live > 0 ? 1 : 0;
+    c[1] += live;
+    c[0] += live > 0 ? 1 : 0;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < NDT_NUM; t++) {
-    double v = acc[t];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
-    acc[t] = v;
-  }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { pairs += __shfl_xor(pairs, o, 64); terms += __shfl_xor(terms, o, 64); }
-  if (lane == 0) {
-#pragma unroll
-    for (int t = 0; t < NDT_NUM; t++) s_sum[wave][t] = acc[t];
-    s_cnt[wave][0] = pairs;
-    s_cnt[wave][1] = terms;
-  }
-  __syncthreads();
-  const size_t slot = (size_t)pose * (size_t)nseg + seg;
-  if (threadIdx.x < NDT_NUM)
-    part[slot * NDT_NUM + threadIdx.x] = (s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x]) + (s_sum[2][threadIdx.x] + s_sum[3][threadIdx.x]);
-  if (threadIdx.x < 2u) part_cnt[2 * slot + threadIdx.x] = (s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x]) + (s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x]);
-}
-
-// level 2: thread (pose, number) adds the pose's segment partials in ascending order; sums [np][NDT_NUM], counts [np][2] = pairs, terms
-__global__ __launch_bounds__(NDT_BLOCK) void ndt_final_kernel(const double* __restrict__ part, const int32_t* __restrict__ part_cnt, unsigned np,
-                                                              unsigned nseg, double* __restrict__ sums, long long* __restrict__ counts) {
-  const size_t g = (size_t)blockIdx.x * NDT_BLOCK + threadIdx.x;
-  if (g >= (size_t)np * (NDT_NUM + 2)) return;
-  const size_t pose = g / (NDT_NUM + 2);
-  const int t = (int)(g % (NDT_NUM + 2));
-  if (t >= NDT_NUM) {
-    long long c = 0;
-    for (unsigned s = 0; s < nseg; s++) c += part_cnt[2 * (pose * nseg + s) + (t - NDT_NUM)];
-    counts[2 * pose + (t - NDT_NUM)] = c;
-  } else {
-    double v = 0.0;
-    for (unsigned s = 0; s < nseg; s++) v = v + part[(pose * nseg + s) * NDT_NUM + t];
-    sums[pose * NDT_NUM + t] = v;
-  }
+  sum_tail(acc, c, pose, nseg, seg, part, part_cnt);
 }
 
 static inline dim3 ndt_grid(size_t threads) { return dim3((unsigned)((threads + NDT_BLOCK - 1) / NDT_BLOCK)); }
@@ -238,17 +196,15 @@ hipError_t launch_ndt_pack(hipStream_t st, const uint32_t* flag, const uint32_t*
   return hipGetLastError();
 }
 
-unsigned scan_ndt_segments(unsigned n) { return (unsigned)(((size_t)n + NDT_SEG - 1) / NDT_SEG); }
-
 hipError_t launch_scan_ndt(hipStream_t st, const float4* scan, unsigned n, const float* poses, unsigned np, int hood, float inv, double d2,
                            const unsigned long long* keys, const void* cells, unsigned nc, int32_t* cell, double* e, double* m, double* part,
                            int32_t* part_cnt, double* sums, long long* counts) {
   if (n == 0 || np == 0) return hipSuccess;
   const NdtPass A{scan, poses, n, np, hood, inv, -0.5 * d2, d2, keys, static_cast<const NdtCell*>(cells), nc};
   hipLaunchKernelGGL(ndt_lookup_kernel, ndt_grid((size_t)n * np * (size_t)hood), dim3(NDT_BLOCK), 0, st, A, cell, e, m);
-  const unsigned nseg = scan_ndt_segments(n);
-  hipLaunchKernelGGL(ndt_reduce_kernel, dim3(nseg, np), dim3(NDT_RED), 0, st, A, cell, e, nseg, part, part_cnt);
-  hipLaunchKernelGGL(ndt_final_kernel, ndt_grid((size_t)np * (NDT_NUM + 2)), dim3(NDT_BLOCK), 0, st, part, part_cnt, np, nseg, sums, counts);
+  const unsigned nseg = sum_segments(n);
+  hipLaunchKernelGGL(ndt_reduce_kernel, dim3(nseg, np), dim3(SUM_RED), 0, st, A, cell, e, nseg, part, part_cnt);
+  launch_sum_final<NDT_NUM, 2>(st, part, part_cnt, np, nseg, sums, counts);
   return hipGetLastError();
 }
 

@@ -159,7 +159,7 @@ int flimo_map_carve(flimo_ctx* ctx, const double x26[26], const float sensor_xyz
  *    and the empty slots holding +0.0; mean_dist[i] = m_i = S_i / c_i, NaN for c_i = 0.  The bits depend on the list alone.
  *  - statistics set T = { i : c_i >= max(1, min_pts) }, N = |T| = n_stat; mu = (sum over T of m_i) / N; sigma = sqrt((sum over T of
  *    (m_i - mu)^2) / (N - 1)), two passes, 0 for N = 1; threshold = mu + (double)std_mul * sigma.  The two sums are float64, taken
- *    on the device in one fixed shape over the range's n slots (a slot outside T adds +0.0), no floating-point
+ *    on the device in one fixed shape over the range's n slots (a slot outside T adds +0.0; flimo_sums.h), no floating-point
  *    atomics: their bits depend on the stored points, first, n and the cfg only -- not on the chunking, the cell size or the path
  *    of the search.  The divisions, the square root and the threshold are the host's.  N = 0: mu, sigma and threshold are NaN and
  *    the statistical rule selects nothing.
@@ -871,7 +871,7 @@ int flimo_scan_fitness(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t 
  *  - H [np][21]: the upper-triangle sums of J_a*J_b, row-major 00, 01 .. 05, 11 .. 55;  g [np][6]: the sums of J_a*d;
  *    cost [np]: the sum of d*d;  valid [np]: the exact count.  The Gauss-Newton step solves H xi = -g, xi = (drho, dphi).
  *    Every sum is taken in ONE fixed shape over the scan's n slots, an invalid slot adding +0.0, without floating-point atomics
- *    (DESIGN.md section 8 states the shape; it is a function of n alone): the bits of a pose's 28 numbers depend on the scan, the
+ *    (flimo_sums.h and DESIGN.md section 8 state the shape; it is a function of n alone): the bits of a pose's 28 numbers depend on the scan, the
  *    map's stored points, the pose and the four parameters -- not on np, the other poses, how the call is cut into chunks, the map's
  *    cell size or which path of the search finished a pair.
  *  - rows [np][n][7] (may be NULL): J0..J5, d per pair, NaN for an invalid pair.
@@ -951,10 +951,10 @@ int flimo_ndt_clear(flimo_ctx* ctx, int slot);
  *  score is the caller's (fast_limo_amd.api.ndt_params gives PCL's (d1, d2) for an outlier ratio and a leaf).
  * Outputs, host memory, per pose:
  *  - H [np][21], g [np][6], score [np]; valid [np]: the pairs with at least one live term; cells [np]: the live terms.
- *    The 28 sums are taken in the shape of flimo_scan_linearize: segments of 4096 slots, thread t of 256
- *    takes slots t, t + 256, .. in ascending order -- inside a slot the neighbour slots s ascend, inside a term k ascends, every
- *    contribution ONE add onto the thread's accumulator, which starts at +0.0 --, a butterfly over 64 lanes,
- *    ((w0 + w1) + (w2 + w3)), then the segments in ascending order.  No floating-point atomics: the bits depend on the scan, the
+ *    The 28 sums are taken in the one shape of flimo_scan_linearize's and flimo_map_outliers' sums, stated in
+ *    fast_limo_amd/csrc/hip/flimo_sums.h (and DESIGN.md section 8), a slot being a scan point: inside a slot the neighbour slots
+ *    s ascend, inside a term k ascends, every contribution ONE add onto the thread's accumulator, which starts at +0.0.
+ *    No floating-point atomics: the bits depend on the scan, the
  *    model, the pose, hood and d2 alone -- not on np, the other poses, the chunking or the lookup method.
  *  - terms [np][n][7][2] (may be NULL): (m, e) per neighbour slot, NaN for an absent cell (with hood == 1 the slots 1..6 are absent);
  *    term_cell [np][n][7] (may be NULL): the cell's position in flimo_ndt_cells' listing, or -1.

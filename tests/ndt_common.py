@@ -7,7 +7,7 @@ between the vectors is not covered by that derivation and has its own bar (test_
 
 The terms.  ``lookup`` restates the cell lookup (voxels_common.keys is voxel_key; the neighbour slots -x +x -y +y -z +z; a binary
 search of the model's keys), ``terms`` m and x = c * m in the stated association, ``contributions`` the 28 numbers of every
-(point, neighbour slot, k) given an e, ``shape_sums`` the two-level shape of the sums in numpy, ``shape_sums_plain`` the same
+(point, neighbour slot, k) given an e, ``shape_sums`` the two-level shape of the sums in numpy (sums_common), ``shape_sums_plain`` the same
 in plain Python floats, ``fsum_sums`` the independent math.fsum value with the sums of absolute values for
 scan_linearize_common.sum_bound.
 
@@ -18,11 +18,12 @@ import math
 import numpy as np
 
 import scan_fitness_common as sf
+import sums_common
 import voxels_common as vc
+from sums_common import RED, SEG          # SUM_RED, SUM_SEG of flimo_sums.h
 
 D = np.float64
 EXP_ULPS = 4
-SEG, RED = 4096, 256          # LIN_SEG, LIN_RED
 PAIRS21 = [(a, b) for a in range(6) for b in range(a, 6)]
 HALF = vc.HALF
 
@@ -138,25 +139,7 @@ def contributions(x26, scan, model, cell, d, e, d2):
 
 def shape_sums(C):
     """The 28 sums of one pose in the shape of the call: C [n, 7, 3, 28] -> [28]."""
-    n = C.shape[0]
-    total = np.zeros(28)
-    for s0 in range(0, n, SEG):
-        blk = np.zeros((SEG, 7, 3, 28))
-        m = min(SEG, n - s0)
-        blk[:m] = C[s0:s0 + m]
-        seq = blk.reshape(SEG // RED, RED, 21, 28).transpose(1, 0, 2, 3).reshape(RED, -1, 28)      # thread t: slots t, t + 256, ..
-        acc = np.zeros((RED, 28))
-        for j in range(seq.shape[1]):
-            acc = acc + seq[:, j]
-        lanes = acc.reshape(4, 64, 28)
-        idx = np.arange(64)
-        o = 1
-        while o < 64:
-            lanes = lanes + lanes[:, idx ^ o]
-            o <<= 1
-        wv = lanes[:, 0]
-        total = total + ((wv[0] + wv[1]) + (wv[2] + wv[3]))
-    return total
+    return sums_common.shape_sums(np.asarray(C).reshape(C.shape[0], 21, 28))
 
 
 def shape_sums_plain(C):

@@ -14,6 +14,7 @@ import numpy as np
 from fast_limo_amd import synth
 from knn_k_common import brute_knn
 from radius_common import sqdist_f32
+from sums_common import shape_sums
 
 INF = float("inf")
 F = np.float32
@@ -111,6 +112,34 @@ def statistics(m, c, min_pts, std_mul):
     assert not np.any(few & far)
     return dict(n=len(c), n_stat=n_stat, mu=mu, sigma=sigma, threshold=thr, few=int(few.sum()), far=int(far.sum()),
                 outliers=int(few.sum() + far.sum()), mask=few | far, in_t=t, sum_m=sum_m, sum_d2=sum_d2)
+
+
+def device_stats(m, c, min_pts, std_mul):
+    """dict(n_stat, mu, sigma, threshold) as the call forms them, bit for bit, from the mean_dist and cnt it returned: the device's two
+    sums in their one shape (sums_common.shape_sums, one number a slot; a slot outside T adds +0.0), the host's arithmetic around them
+    (mu = S / N; sigma = sqrt(S / (N - 1)), 0.0 for N = 1; threshold = mu + float64(float32(std_mul)) * sigma, two roundings)."""
+    m = np.asarray(m, np.float64)
+    t = np.asarray(c) >= max(1, int(min_pts))
+    n_stat = int(t.sum())
+    mu = sigma = thr = np.float64("nan")
+    if n_stat:
+        mu = shape_sums(np.where(t, m, 0.0)[:, None, None])[0] / np.float64(n_stat)
+        sigma = np.float64(0.0)
+        if n_stat > 1:
+            with np.errstate(invalid="ignore"):
+                d2 = np.where(t, (m - mu) * (m - mu), 0.0)
+            sigma = np.sqrt(shape_sums(d2[:, None, None])[0] / np.float64(n_stat - 1))
+        with np.errstate(invalid="ignore"):
+            thr = mu + np.float64(F(std_mul)) * sigma
+    return dict(n_stat=n_stat, mu=float(mu), sigma=float(sigma), threshold=float(thr))
+
+
+def same_bits(got, want, what=""):
+    """n_stat equal; mu, sigma and threshold of the same bits (a NaN on both sides is the same: its sign is the host's choice)."""
+    assert got["n_stat"] == want["n_stat"], (what, got["n_stat"], want["n_stat"])
+    for key in ("mu", "sigma", "threshold"):
+        g, w = np.float64(got[key]), np.float64(want[key])
+        assert (np.isnan(g) and np.isnan(w)) or g.tobytes() == w.tobytes(), (what, key, repr(got[key]), repr(want[key]))
 
 
 def rel_gap(m, st):

@@ -18,6 +18,7 @@ import numpy as np
 
 import normals_common as nc
 import scan_fitness_common as sf
+import sums_common
 from fast_limo_amd import synth
 
 INF = float("inf")
@@ -170,6 +171,22 @@ def check(got, ref, n, tag="", want_rows=True):
             with np.errstate(invalid="ignore", divide="ignore"):
                 worst = max(worst, float(np.nanmax(np.where(np.asarray(b) > 0, e / b, 0.0))))
     return worst
+
+
+def pinned(got, tag=""):
+    """H, g and cost of every pose are, byte for byte, sums_common.shape_sums of the 28 products formed in numpy float64 from the
+    returned rows (21 of H: J[a] * J[b], a <= b, row-major; 6 of g: J[a] * J[6]; the cost: J[6] * J[6]; a NaN row adds +0.0), and
+    valid is the number of rows that are not NaN."""
+    for j, rows in enumerate(got["rows"]):
+        dead = np.isnan(rows[:, 6])
+        np.testing.assert_array_equal(np.isnan(rows), np.broadcast_to(dead[:, None], rows.shape), err_msg=f"{tag}: a row is NaN as a whole")
+        with np.errstate(invalid="ignore"):
+            T = np.stack([rows[:, a] * rows[:, b] for a, b in PAIRS21] + [rows[:, a] * rows[:, 6] for a in range(6)] + [rows[:, 6] * rows[:, 6]], axis=1)
+        T[dead] = 0.0
+        want = sums_common.shape_sums(T[:, None, :])
+        mine = np.concatenate([got["H"][j], got["g"][j], got["cost"][j:j + 1]])
+        assert mine.tobytes() == want.tobytes(), f"{tag}: the sums of pose {j} are not the shape's: {np.nonzero(mine != want)[0]}"
+        assert got["valid"][j] == int((~dead).sum()), f"{tag}: valid of pose {j}"
 
 
 def same_bytes(a, b, tag="", names=("valid", "H", "g", "cost", "rows", "pair_cnt")):

@@ -1,7 +1,8 @@
 """GPU suite: outliers by neighbour statistics -- flimo_map_outliers marks the stored points whose k nearest neighbours are too few
 inside the gate or too far away on average, flimo_map_remove_outliers forgets them in the crop's one ordered pass.  The yardstick is the
 definition restated in numpy (tests/outliers_common.py): the neighbour counts and the bits of every mean distance are compared
-exactly; mu, sigma and the threshold within the bound derived there (4 * N * 2^-52 relative); and because no mean distance of any
+exactly; mu, sigma and the threshold within the bound derived there (4 * N * 2^-52 relative) and bit for bit against the sums' one
+shape (tests/sums_common.py) over the returned means and counts; and because no mean distance of any
 configuration run here lies within 1e-9 relative of its threshold (tests/test_outliers_host.py asserts that), the masks and their
 counts exactly.  After a removal the map is clear() + initialize(kept), as after a crop: that part is checked against a twin context."""
 import ctypes as C
@@ -56,9 +57,10 @@ def _dbits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def _same_as_yardstick(out, m, c, st, what):
-    """cnt and the bits of mean_dist exact (every NaN is the quiet NaN 0x7ff8...), the stats within the bound, the mask and its
-    counts exact.  Each figure is printed before it is asserted."""
+def _same_as_yardstick(out, m, c, st, what, cfg):
+    """cnt and the bits of mean_dist exact (every NaN is the quiet NaN 0x7ff8...), the stats within the bound of the yardstick and bit
+    for bit what the returned mean_dist and cnt give through the sums' one shape (oc.device_stats), the mask and its counts exact.
+    Each figure is printed before it is asserted."""
     got = out["stats"]
     print(what, "n_stat", got["n_stat"], "mu", repr(got["mu"]), repr(st["mu"]), "sigma", repr(got["sigma"]), repr(st["sigma"]), "threshold",
           repr(got["threshold"]), repr(st["threshold"]), "few", got["few"], st["few"], "far", got["far"], st["far"], "bound", oc.bound(st["n_stat"]),
@@ -68,6 +70,9 @@ def _same_as_yardstick(out, m, c, st, what):
     bad = np.where(_dbits(out["mean_dist"]) != _dbits(want))[0]
     assert len(bad) == 0, (what, len(bad), bad[:5], out["mean_dist"][bad[:5]], want[bad[:5]])
     oc.same_stats(got, st, what)
+    pin = oc.device_stats(out["mean_dist"], out["cnt"], cfg["min_pts"], cfg["std_mul"])
+    print(what, "the shape's", pin)
+    oc.same_bits(got, pin, what)
     np.testing.assert_array_equal(out["mask"], st["mask"], err_msg=what)
 
 
@@ -75,7 +80,7 @@ def _same_as_yardstick(out, m, c, st, what):
 @pytest.mark.parametrize("cfg", oc.CONFIGS, ids=CFG_IDS)
 def test_counts_means_stats_and_mask_equal_the_yardstick(scene_ctx, cfg):
     m, c, st = oc.yardstick("scene", **cfg)
-    _same_as_yardstick(scene_ctx.map_outliers(**cfg), m, c, st, CFG_IDS(cfg))
+    _same_as_yardstick(scene_ctx.map_outliers(**cfg), m, c, st, CFG_IDS(cfg), cfg)
 
 
 # ---- 2. the pure forms ----------------------------------------------------------------------------------------------------------------
@@ -91,7 +96,7 @@ def test_the_pure_forms_are_the_radius_filter_and_the_statistical_filter(scene_c
     np.testing.assert_array_equal(out["mask"], cnt < need)       # (need <= k: a count beyond k is never below need)
     assert out["stats"]["far"] == 0 and out["stats"]["few"] == int((cnt < need).sum()) == out["stats"]["outliers"]
     m, c, st = oc.yardstick("scene", k=k, max_dist=r, min_pts=need, std_mul=INF)
-    _same_as_yardstick(out, m, c, st, "radius form")
+    _same_as_yardstick(out, m, c, st, "radius form", dict(min_pts=need, std_mul=INF))
     # the plain statistical filter: no gate, no count rule
     out = scene_ctx.map_outliers(k=8, max_dist=INF, min_pts=0, std_mul=1.0)
     s = out["stats"]
@@ -108,7 +113,7 @@ def test_far_points_take_the_walk_and_are_exact(built, cfg):
     try:
         m, c, st = oc.yardstick("far", **cfg)
         out = ctx.map_outliers(**cfg)
-        _same_as_yardstick(out, m, c, st, "far " + CFG_IDS(cfg))
+        _same_as_yardstick(out, m, c, st, "far " + CFG_IDS(cfg), cfg)
         if math.isinf(cfg["max_dist"]) and cfg["std_mul"] == 1.0:
             np.testing.assert_array_equal(np.where(out["mask"])[0], oc.N_SCENE + np.arange(3))      # ungated: the three, and only they
             assert np.all(out["mean_dist"][oc.N_SCENE:] > 400.0)
@@ -153,7 +158,7 @@ def test_a_range_has_the_whole_maps_neighbours_and_its_own_statistics(scene_ctx)
             m, cc, st = oc.yardstick("scene", first, n, **c)
             out = scene_ctx.map_outliers(first, n, **c)
             assert len(out["mask"]) == n and out["stats"]["n"] == n
-            _same_as_yardstick(out, m, cc, st, "range %d+%d %s" % (first, n, CFG_IDS(c)))
+            _same_as_yardstick(out, m, cc, st, "range %d+%d %s" % (first, n, CFG_IDS(c)), c)
             assert _dbits(out["mean_dist"]).tobytes() == _dbits(scene_ctx.map_outliers(**c)["mean_dist"][first:first + n]).tobytes()
     assert abs(scene_ctx.map_outliers(8000, 300, **cfg)["stats"]["mu"] - whole["stats"]["mu"]) > 0.1      # the specks' own mean
     empty = scene_ctx.map_outliers(oc.N_SCENE, 0, **cfg)
@@ -165,6 +170,16 @@ def test_a_range_has_the_whole_maps_neighbours_and_its_own_statistics(scene_ctx)
         with pytest.raises(_lib.FlimoError, match="invalid"):
             scene_ctx.map_remove_outliers(first, n, **cfg)
     assert scene_ctx.map_size() == oc.N_SCENE
+
+
+@pytest.mark.parametrize("first,n", [(8000, 1), (4095, 2), (100, 256), (8099, 257), (0, 4096), (4000, 4097)])
+def test_range_sizes_at_the_borders_of_the_sums_shape(scene_ctx, first, n):
+    """One slot, two, a workgroup's threads and one more, a segment and one more: ranges of the scene at k = 8 with no gate."""
+    cfg = dict(k=8, max_dist=INF, min_pts=0, std_mul=1.0)
+    m, c, st = oc.yardstick("scene", first, n, **cfg)
+    out = scene_ctx.map_outliers(first, n, **cfg)
+    assert out["stats"]["n"] == n == out["stats"]["n_stat"]
+    _same_as_yardstick(out, m, c, st, "range %d+%d" % (first, n), cfg)
 
 
 # ---- 6. removal -----------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,8 @@ the C ABI, and api.scan_align over it.
 The yardstick (tests/scan_linearize_common.py) is the route the call replaces: per pose the existing ``ctx.scan_to_world``, the
 existing ``ctx.normals(w, k, gate, min_pts)`` with centroid and eig, the terms of flimo_c.h in numpy float64, math.fsum.  pair_cnt,
 valid and every bit of rows (the NaN pattern included) are compared with no tolerance; H, g and cost within n * 2^-52 * sum|term|
-of fsum (the bound of any summation order of n terms).  Wherever two calls must give the same result the arrays are compared byte
+of fsum (the bound of any summation order of n terms) and, in the first test and the test of the scan sizes, byte for byte against
+the sums' one shape over the returned rows (``sl.pinned``, tests/sums_common.py).  Wherever two calls must give the same result the arrays are compared byte
 for byte, the sums included."""
 import numpy as np
 import pytest
@@ -65,6 +66,7 @@ def test_against_the_composed_route(hip, scene, k, gate, min_pts, max_curv):
     ref = sl.composed(hip, poses, k, gate, min_pts, max_curv)
     got = hip.scan_linearize(poses, k, gate, min_pts, max_curv, want_rows=True)
     worst = sl.check(got, ref, n, f"k {k}, gate {gate}")
+    sl.pinned(got, f"k {k}, gate {gate}")
     only = hip.scan_linearize(poses, k, gate, min_pts, max_curv)
     assert sorted(only) == ["H", "cost", "g", "valid"]
     sl.same_bytes(only, got, "without rows", names=("valid", "H", "g", "cost"))
@@ -150,6 +152,7 @@ def test_scan_sizes_off_the_lane_block_and_reduction_borders(scene, n):
             ref = sl.composed(ctx, poses, k, 1.0, 3, 0.05)
             whole = ctx.scan_linearize(poses, k, 1.0, 3, 0.05, want_rows=True)
             sl.check(whole, ref, n, f"n = {n}, k = {k}")
+            sl.pinned(whole, f"n = {n}, k = {k}")
             ctx.set_linearize_chunk(2 * n)
             sl.same_bytes(whole, ctx.scan_linearize(poses, k, 1.0, 3, 0.05, want_rows=True), f"n = {n}, k = {k}, chunks of two poses")
             ctx.set_linearize_chunk(0)
