@@ -3,8 +3,8 @@ per exported function.  ``_lib.load_hip()`` and ``api.load_host()`` declare thei
 symbols the tests compare with the headers are read off them.
 
 A new entry that both a ``flimo_ctx`` and a ``flimo_loc`` offer is one row of ``PAIRED`` -- the two symbols and the arguments after
-the handle -- and one method of ``_lib._SharedEntries``; ``HipCtx`` and ``Localizer`` then both have it.  ``PAIRED_NDT`` holds the
-rows of the NDT entries in the same form."""
+the handle -- and one method of ``_lib._SharedEntries``; ``HipCtx`` and ``Localizer`` then both have it.  ``PAIRED_NDT`` and
+``PAIRED_GICP`` hold the rows of the NDT and the GICP entries in the same form."""
 from __future__ import annotations
 
 import ctypes as C
@@ -134,6 +134,17 @@ class NdtInfo(_Stats):
                 ("min_pts", C.c_int), ("stale", C.c_int)]
 
 
+class GicpCfg(C.Structure):
+    """flimo_gicp_cfg (include/flimo_c.h)."""
+    _fields_ = [("k", C.c_int), ("max_dist", C.c_float), ("min_pts", C.c_int), ("rule", C.c_int), ("eps", C.c_double)]
+
+
+class GicpInfo(_Stats):
+    """flimo_gicp_model_info (include/flimo_c.h)."""
+    _fields_ = [("points", C.c_uint64), ("n_cov", C.c_uint64), ("eps", C.c_double), ("k", C.c_int), ("max_dist", C.c_float),
+                ("min_pts", C.c_int), ("rule", C.c_int), ("stale", C.c_int)]
+
+
 class CorrGraphCfg(C.Structure):
     """flimo_corr_graph_cfg (include/flimo_c.h)."""
     _fields_ = [("tol", C.c_float), ("min_edge", C.c_float), ("edge_sim", C.c_float)]
@@ -222,7 +233,17 @@ PAIRED_NDT = (
     ("flimo_ndt_clear", "flimo_loc_ndt_clear", [i]),
     ("flimo_scan_ndt", "flimo_loc_scan_ndt", [i, vp, sz, i, d, vp, vp, vp, vp, vp, vp, vp]),
 )
-LOC_OF = {hip: loc for hip, loc, _ in PAIRED + PAIRED_NDT}
+# The resident GICP model, the scan's covariances and the pass against both.
+PAIRED_GICP = (
+    ("flimo_gicp_build", "flimo_loc_gicp_build", [P(GicpCfg), P(sz)]),
+    ("flimo_gicp_model", "flimo_loc_gicp_model", [sz, sz, vp]),
+    ("flimo_gicp_info", "flimo_loc_gicp_info", [P(GicpInfo)]),
+    ("flimo_gicp_clear", "flimo_loc_gicp_clear", []),
+    ("flimo_scan_cov_set", "flimo_loc_scan_cov_set", [vp, sz]),
+    ("flimo_scan_gicp", "flimo_loc_scan_gicp", [vp, sz, f, vp, vp, vp, vp, vp, vp]),
+)
+PAIRED_ALL = PAIRED + PAIRED_NDT + PAIRED_GICP
+LOC_OF = {hip: loc for hip, loc, _ in PAIRED_ALL}
 
 # Everything else: (result, symbol, every argument -- the handle, where there is one, included).
 HIP_ONLY = (
@@ -256,6 +277,7 @@ HIP_ONLY = (
     (i, "flimo_set_fitness_chunk", [vp, sz]),
     (i, "flimo_set_linearize_chunk", [vp, sz]),
     (i, "flimo_set_ndt_chunk", [vp, sz]),
+    (i, "flimo_set_gicp_chunk", [vp, sz]),
     (i, "flimo_set_corr_chunk", [vp, sz]),
     (i, "flimo_set_desc_chunk", [vp, sz, sz]),
     (sz, "flimo_desc_ref_size", [vp]),
@@ -269,6 +291,9 @@ HIP_ONLY = (
     (i, "flimo_corr_compatible_host", [vp, vp, vp, vp, P(CorrGraphCfg)]),
     (i, "flimo_desc_dist_host", [vp, vp, i, vp]),
     (i, "flimo_ndt_term_host", [vp, vp, vp, vp, vp, vp, d, vp]),
+    (i, "flimo_gicp_eigen_host", [vp, vp]),
+    (i, "flimo_gicp_regularize_host", [vp, i, d, vp]),
+    (i, "flimo_gicp_term_host", [vp, vp, vp, vp, vp, vp, vp]),
     (None, "flimo_plane_fit5_host", [f32p, f32p]),
     (i, "flimo_plane_eval5_host", [f32p, f32p, f]),
     (i, "flimo_calculate_H_host", [f64p, f32p, f32p, f32p, sz, i, f64p, f64p]),
@@ -276,6 +301,7 @@ HIP_ONLY = (
     # scan
     (i, "flimo_scan_set", [vp, f32p, sz, sz]),
     (sz, "flimo_scan_size", [vp]),
+    (sz, "flimo_scan_cov_size", [vp]),
     (i, "flimo_scan_get", [vp, vp, sz, P(sz)]),
     (i, "flimo_scan_voxel_filter", [vp, f, P(sz)]),
     (i, "flimo_raw_scan_set", [vp, f32p, sz, sz, f64p]),
@@ -382,13 +408,13 @@ HOST_ONLY = (
     (None, "flimo_host_eigen_solver6", [f64p, f64p, f64p, f64p]),
 )
 
-HIP_SYMBOLS = [hip for hip, _, _ in PAIRED + PAIRED_NDT] + [name for _, name, _ in HIP_ONLY]
-HOST_SYMBOLS = [loc for _, loc, _ in PAIRED + PAIRED_NDT] + [name for _, name, _ in HOST_ONLY]
+HIP_SYMBOLS = [hip for hip, _, _ in PAIRED_ALL] + [name for _, name, _ in HIP_ONLY]
+HOST_SYMBOLS = [loc for _, loc, _ in PAIRED_ALL] + [name for _, name, _ in HOST_ONLY]
 
 
 def declare(lib, side):
     """Give every function of ``lib`` its result and argument types; ``side`` 0: libflimo_hip.so, 1: libfast_limo.so."""
-    for row in PAIRED + PAIRED_NDT:
+    for row in PAIRED_ALL:
         fn = getattr(lib, row[side])
         fn.restype, fn.argtypes = C.c_int, [vp] + row[2]
     for restype, name, args in (HIP_ONLY, HOST_ONLY)[side]:

@@ -15,7 +15,7 @@ import numpy as np
 from . import _abi
 # (every structure stays a name of this module: callers and tests say _lib.MatchCfg, _lib.Frame, ...)
 from ._abi import (CHAIN_MAX_PASSES, CarveCfg, ChainIO, ChainPass, ClusterCfg, ClusterStats, CorrCfg, CorrGraphCfg, FilterCfg, FpfhCfg, Frame,
-                   KeypointCfg, MapCfg, MatchCfg, NdtCfg, NdtInfo, OutlierCfg, OutlierStats, PlaneCfg, PlaneSel, RegionCfg, RegionStats, VoxelCfg, VoxelStats,
+                   GicpCfg, GicpInfo, KeypointCfg, MapCfg, MatchCfg, NdtCfg, NdtInfo, OutlierCfg, OutlierStats, PlaneCfg, PlaneSel, RegionCfg, RegionStats, VoxelCfg, VoxelStats,
                    f32p, f64p, i32p)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -180,6 +180,7 @@ _NORMAL_OUTPUTS = (("normal", np.float32, 4), ("cnt", np.int32, 1), ("centroid",
 NDT_CELL_OUTPUTS = (("ijk", np.int32, 3), ("count", np.int32, 1), ("mean", np.float64, 3), ("evec", np.float64, 9), ("wgt", np.float64, 3),
                     ("eval", np.float64, 3))
 NDT_SLOTS = 4          # FLIMO_NDT_SLOTS
+GICP_PLANE, GICP_CLAMP = 0, 1      # FLIMO_GICP_PLANE, FLIMO_GICP_CLAMP: the rules of gicp_build / api.gicp_regularize_host
 
 _NONE = C.create_string_buffer(8)
 
@@ -599,6 +600,73 @@ class _SharedEntries:
         self._entry("flimo_scan_ndt", int(slot), x.ctypes.data if m else None, m, int(hood), float(d2),
                     *(_ptr(out.get(name)) for name in ("valid", "cells", "H", "g", "score", "terms", "term_cell")))
         return out
+
+    def gicp_build(self, k=20, max_dist=float("inf"), min_pts=3, rule=GICP_PLANE, eps=1e-3):
+        """flimo_gicp_build: the GICP model of the context -- per stored point the covariance of ``normals_range(0, map_size(), k,
+        max_dist, min_pts)`` (bit for bit, left on the device), regularised by ``rule``: GICP_PLANE (eigenvalues eps, 1, 1: PCL's)
+        or GICP_CLAMP (none below eps * l2: the NDT model's).  A snapshot by insertion index: once the stored points change it is
+        stale and ``scan_gicp`` refuses it.  Returns the number of points that got a covariance.  A ``Localizer`` first waits for
+        an insert, a crop or a carve still running behind the last sweep."""
+        cfg, n_cov = GicpCfg(int(k), float(max_dist), int(min_pts), int(rule), float(eps)), C.c_size_t(0)
+        self._entry("flimo_gicp_build", C.byref(cfg), C.byref(n_cov))
+        return int(n_cov.value)
+
+    def gicp_info(self):
+        """flimo_gicp_info: a dict of the model: points, n_cov, eps, k, max_dist, min_pts, rule, stale."""
+        info = GicpInfo()
+        self._entry("flimo_gicp_info", C.byref(info))
+        return info.as_dict()
+
+    def gicp_model(self, first=0, n=None):
+        """flimo_gicp_model: rows first .. first + n - 1 of the model (``n`` None: to its end) as float64 [n, 6] = xx xy xz yy yz
+        zz; six NaN for a point without a covariance."""
+        first = int(first)
+        if n is None:
+            n = max(self.gicp_info()["points"] - first, 0)
+        cov = np.zeros((int(n), 6))
+        self._entry("flimo_gicp_model", first, int(n), _ptr(cov))
+        return cov
+
+    def gicp_clear(self):
+        """flimo_gicp_clear: free the model."""
+        self._entry("flimo_gicp_clear")
+
+    def scan_cov_set(self, cov6):
+        """flimo_scan_cov_set: one regularised covariance per point of the resident scan, float64 [n, 6], body frame, the scan's
+        order (``api.gicp_covs`` computes them); a row with a NaN: that point has none.  None or no row drops them, and so does
+        every call that replaces the resident scan."""
+        if cov6 is None:
+            self._entry("flimo_scan_cov_set", None, 0)
+            return
+        cov = np.ascontiguousarray(cov6, dtype=np.float64).reshape(-1, 6)
+        self._entry("flimo_scan_cov_set", cov.ctypes.data if cov.shape[0] else None, cov.shape[0])
+
+    def scan_gicp(self, x26s, max_dist=1.0, want_pairs=False):
+        """flimo_scan_gicp: the GICP (plane-to-plane) normal equations of the resident scan against the map at each pose of
+        ``x26s`` [np, 26] (only pos and rot are read): per pair the nearest stored point of ``scan_fitness(max_dist)``, weighed by
+        (CB + R CA R^T)^-1 from the model's row (``gicp_build``) and the scan's (``scan_cov_set``).  Returns a dict: valid [np]
+        int32, H [np, 21] (upper triangle, row-major), g [np, 6], cost [np] (the sum of m)[, pair_idx [np, n]: the neighbour or -1;
+        pair_m [np, n]: m, NaN for an invalid pair].  The step solves H xi = -g (``api.gicp_align`` iterates it).  A ``Localizer``
+        first waits for an insert, a crop or a carve still running behind the last sweep."""
+        x = _poses(x26s)
+        m, n = x.shape[0], self._scan_size()
+        out = {"valid": np.zeros(m, np.int32), "H": np.zeros((m, 21)), "g": np.zeros((m, 6)), "cost": np.zeros(m)}
+        if want_pairs:
+            out["pair_idx"] = np.full((m, n), -1, np.int32)
+            out["pair_m"] = np.full((m, n), np.nan)
+        self._entry("flimo_scan_gicp", x.ctypes.data if m else None, m, float(max_dist),
+                    *(_ptr(out.get(name)) for name in ("valid", "H", "g", "cost", "pair_idx", "pair_m")))
+        return out
+
+    def set_gicp_chunk(self, pairs):
+        """(pose, point) pairs per chunk of ``scan_gicp`` (flimo_set_gicp_chunk; 0: the default of 2^20), on the map's context."""
+        hip = getattr(self, "hip", self)
+        hip._chk(hip._L.flimo_set_gicp_chunk(hip._h, int(pairs)))
+
+    def scan_cov_size(self) -> int:
+        """flimo_scan_cov_size: the covariances ``scan_cov_set`` left with the resident scan, 0 when there are none."""
+        hip = getattr(self, "hip", self)
+        return int(hip._L.flimo_scan_cov_size(hip._h))
 
     def corr_poses(self, src, dst, tri, want=("pose",), **cfg):
         """flimo_corr_poses: pose hypotheses from point correspondences.  ``src`` [m, 3] (body frame) and ``dst`` [m, 3] (map frame)

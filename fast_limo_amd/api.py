@@ -620,7 +620,7 @@ def desc_pairs(ref_obj, qry_obj, q_desc, r_desc, ratio=0.9, mutual=True):
 
 
 def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=True, nh=4096, seed=0, top=8, corr=None, fitness_max_dist=1.0, align=None,
-               x26_like=None, prune=None, keypoints=None, scan_keypoints=None, refine="plane", ndt=None):
+               x26_like=None, prune=None, keypoints=None, scan_keypoints=None, refine="plane", ndt=None, gicp=None):
     """A pose of a scan in a map from nothing but the two clouds -- plumbing over six calls, every parameter the caller's.
     ``map_obj`` (a ``HipCtx`` or a ``Localizer``) holds the map, and the scan (body frame) as its resident scan; ``scan_obj`` is a
     context whose MAP is that scan.  FPFH of both sides (``fpfh``: the fields of ``_lib.fpfh_cfg``; ``scan_fpfh``: the scan side's
@@ -639,9 +639,11 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
     still formed for every point.  The returned pairs, src and dst are in the ORIGINAL indices; ``keypoints`` is added to the result:
     (the scan's ascending indices, the map's).
     ``refine``: "plane" (the default: ``scan_align``) or "ndt" -- the best row is then refined by ``ndt_align`` (``ndt``: its keyword
-    arguments; ``slots`` is required and names models already built on ``map_obj`` with ``ndt_build``, coarse to fine)."""
-    if refine not in ("plane", "ndt"):
-        raise ValueError(f"relocalize: refine must be 'plane' or 'ndt', not {refine!r}")
+    arguments; ``slots`` is required and names models already built on ``map_obj`` with ``ndt_build``, coarse to fine) -- or "gicp":
+    by ``gicp_align`` (``gicp``: its keyword arguments; ``map_obj`` already holds the model of ``gicp_build`` and the scan's
+    covariances of ``scan_cov_set``)."""
+    if refine not in ("plane", "ndt", "gicp"):
+        raise ValueError(f"relocalize: refine must be 'plane', 'ndt' or 'gicp', not {refine!r}")
     fpfh, corr, align = dict(fpfh or {}), dict(corr or {}), dict(align or {})
     m_hip, s_hip = getattr(map_obj, "hip", map_obj), getattr(scan_obj, "hip", scan_obj)
     f_map = map_obj.map_fpfh(want=(), **fpfh)["fpfh"]
@@ -668,7 +670,12 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
     cost = fitness_cost(inliers, sum_sqd, m_hip.scan_size(), fitness_max_dist)
     order = np.lexsort((np.arange(cost.size), cost))
     ranked = cons["x26"][order]
-    aligned = scan_align(map_obj, ranked[:1], **align) if refine == "plane" else ndt_align(map_obj, ranked[:1], **dict(ndt or {}))
+    if refine == "plane":
+        aligned = scan_align(map_obj, ranked[:1], **align)
+    elif refine == "ndt":
+        aligned = ndt_align(map_obj, ranked[:1], **dict(ndt or {}))
+    else:
+        aligned = gicp_align(map_obj, ranked[:1], **dict(gicp or {}))
     out = dict(pairs=(qi, rj), fpfh=(f_scan, f_map), src=src, dst=dst, consensus=cons,
                fitness=dict(inliers=inliers[order], sum_sqd=sum_sqd[order], cost=cost[order], x26=ranked), align=aligned,
                x26=aligned["x26"][0] if ranked.shape[0] else None)
@@ -797,6 +804,68 @@ def ndt_align(obj, x26s, slots, hood=7, outlier_ratio=0.55, iters=30, min_valid=
     if not stages:
         raise ValueError("ndt_align: no slots")
     return dict(stages[-1], stages=stages)
+
+
+def gicp_eigen_host(cov6):
+    """The eigen-pairs ``gicp_regularize_host`` works from (flimo_gicp_eigen_host: the Jacobi of the kernels, on the host): returns
+    (l [3] ascending, v [3, 3]: row k the unit vector of l[k]).  Needs no device."""
+    L = _lib.load_hip()
+    c = np.ascontiguousarray(cov6, dtype=np.float64).reshape(6)
+    out = np.zeros(12)
+    rc = L.flimo_gicp_eigen_host(c.ctypes.data, out.ctypes.data)
+    if rc < 0:
+        raise FlimoError(f"flimo_gicp_eigen_host failed ({rc})")
+    return out[:3].copy(), out[3:].reshape(3, 3).copy()
+
+
+def gicp_regularize_host(cov6, rule=_lib.GICP_PLANE, eps=1e-3):
+    """One regularised covariance on the host (flimo_gicp_regularize_host: the function ``gicp_build``'s kernel calls): ``cov6`` =
+    xx xy xz yy yz zz of a neighbourhood.  Returns (has, out [6]); six NaN and False where there is no covariance (a non-finite
+    number, or no positive eigenvalue).  Needs no device."""
+    L = _lib.load_hip()
+    c = np.ascontiguousarray(cov6, dtype=np.float64).reshape(6)
+    out = np.zeros(6)
+    rc = L.flimo_gicp_regularize_host(c.ctypes.data, int(rule), float(eps), out.ctypes.data)
+    if rc < 0:
+        raise FlimoError(f"flimo_gicp_regularize_host failed ({rc})")
+    return rc == 1, out
+
+
+def gicp_term_host(w, b, p, R, CA, CB):
+    """One GICP term on the host (flimo_gicp_term_host: the function the kernel of ``scan_gicp`` calls): ``w`` the float32 world
+    point, ``b`` the float32 stored point, ``p`` the float32 scan point, ``R`` [3, 3] the float32 rotation, ``CA`` / ``CB`` [6] the
+    scan point's and the stored point's covariance.  Returns (live, m, det, sums [28]: H's 21, g's 6, the cost).  Needs no device."""
+    L = _lib.load_hip()
+    a = [np.ascontiguousarray(v, dtype=np.float32).reshape(n) for v, n in ((w, 3), (b, 3), (p, 3), (R, 9))]
+    c = [np.ascontiguousarray(v, dtype=np.float64).reshape(6) for v in (CA, CB)]
+    out = np.zeros(30)
+    rc = L.flimo_gicp_term_host(*(v.ctypes.data for v in a + c), out.ctypes.data)
+    if rc < 0:
+        raise FlimoError(f"flimo_gicp_term_host failed ({rc})")
+    return rc == 1, float(out[0]), float(out[1]), out[2:].copy()
+
+
+def gicp_covs(scan_obj, xyz=None, k=20, max_dist=float("inf"), min_pts=3, rule=_lib.GICP_PLANE, eps=1e-3):
+    """The covariances ``scan_cov_set`` takes, for the points ``xyz`` [n, 3] of a scan (body frame): ``scan_obj`` is a context whose
+    MAP is that scan (``map_config(downsample=False)``, as for the scan's FPFH rows); per point the covariance of its ``k`` nearest
+    there (``normals``; ``xyz`` None: the stored points themselves, ``normals_range``), then ``gicp_regularize_host`` of every row.
+    Returns float64 [n, 6]; a point with fewer than max(3, min_pts) neighbours keeps its NaN row."""
+    if xyz is None:
+        cov = getattr(scan_obj, "normals_range", None) or scan_obj.map_normals_range
+        cov = cov(0, scan_obj.map_size(), k, max_dist, min_pts, want=("cov",))["cov"]
+    else:
+        cov = (getattr(scan_obj, "normals", None) or scan_obj.map_normals)(xyz, k, max_dist, min_pts, want=("cov",))["cov"]
+    out = np.full(cov.shape, np.nan)
+    for i in np.nonzero(np.all(np.isfinite(cov), axis=1))[0]:
+        out[i] = gicp_regularize_host(cov[i], rule, eps)[1]
+    return out
+
+
+def gicp_align(obj, x26s, max_dist=1.0, iters=10, min_valid=30):
+    """Refine pose hypotheses of the resident scan by GICP: ``scan_align`` on ``scan_gicp``'s normal equations -- ``iters``
+    Gauss-Newton steps, each with the nearest stored points and the weights (CB + R CA R^T)^-1 of its own pose.  ``obj`` holds the
+    model (``gicp_build``) and the scan's covariances (``scan_cov_set``).  Returns ``scan_align``'s dict; cost is the sum of m."""
+    return scan_align(obj, x26s, iters=iters, min_valid=min_valid, linearize=lambda xs: obj.scan_gicp(xs, max_dist))
 
 
 def eskf_update_fixed(x26, P, H, h, max_iters=3, limits=None, R=0.001, D=5.0):

@@ -254,6 +254,8 @@ extern "C" void flimo_ctx_destroy(flimo_ctx* c) {
   (void)hipFree(c->d_batch);
   (void)hipFree(c->d_desc_rt); (void)hipFree(c->d_desc_norm);
   for (flimo_ctx::NdtModel& m : c->ndt) m.release();
+  c->gicp.release();
+  (void)hipFree(c->d_scan_cov);
   delete c;
 }
 
@@ -1067,7 +1069,7 @@ static int ensure_scan(flimo_ctx* c, size_t n) {
   (void)hipFree(c->d_scan); (void)hipFree(c->d_scan_raw); (void)hipFree(c->d_scan_world); (void)hipFree(c->d_scan_t);
   c->d_scan = a; c->d_scan_raw = b; c->d_scan_world = w; c->d_scan_t = t;
   c->scan_cap = cap;
-  c->scan_n = 0; c->sorted_n = 0; c->raw_n = 0; c->prev.valid = 0;
+  scan_replaced(c, 0); c->raw_n = 0;
   c->deskew_kept = false;
   return FLIMO_OK;
 }
@@ -1122,7 +1124,7 @@ extern "C" int flimo_scan_set(flimo_ctx* c, const float* xyz, size_t n, size_t s
     HIPCHK(c, sort_scan(c->stream, c->d_scan, n, c->d_scan_sorted, c->scratch));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  c->scan_n = n; c->sorted_n = n; c->prev.valid = 0;
+  scan_replaced(c, n);
   return FLIMO_OK;
 }
 
@@ -1160,7 +1162,7 @@ extern "C" int flimo_scan_voxel_filter(flimo_ctx* c, float leaf, size_t* n_out) 
   HIPCHK(c, voxel_grid(c->stream, c->d_scan, c->scan_n, leaf, c->d_scan_world, &m, &pass, c->scratch));
   if (!pass) {
     std::swap(c->d_scan, c->d_scan_world);
-    c->scan_n = m; c->sorted_n = m; c->prev.valid = 0;
+    scan_replaced(c, m);
   }
   if (c->scan_n) HIPCHK(c, sort_scan(c->stream, c->d_scan, c->scan_n, c->d_scan_sorted, c->scratch));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1415,7 +1417,7 @@ extern "C" int flimo_deskew_resident_offset(flimo_ctx* c, const flimo_frame* fra
   if (dev_frame_size() != sizeof(flimo_frame)) return fail(c, FLIMO_ERR_INVALID, "frame layout mismatch");
   const size_t n = c->raw_n;
   c->deskew_kept = false;
-  if (n == 0) { c->scan_n = 0; c->sorted_n = 0; c->prev.valid = 0; return FLIMO_OK; }
+  if (n == 0) { scan_replaced(c, 0); return FLIMO_OK; }
   const size_t fbytes = nf * sizeof(flimo_frame);
   const size_t total = fbytes + 32 * sizeof(float);
   if (c->d_frames_fg && total <= FRAMES_FG_SLOT) {
@@ -1439,7 +1441,7 @@ extern "C" int flimo_deskew_resident_offset(flimo_ctx* c, const flimo_frame* fra
     c->deskew_n = n;
     c->deskew_pending = true;
     c->deskew_kept = true;
-    c->scan_n = n; c->sorted_n = n; c->prev.valid = 0;
+    scan_replaced(c, n);
     return FLIMO_OK;
   }
   // frames + the two 4x4 matrices go through one pinned staging copy
@@ -1479,7 +1481,7 @@ extern "C" int flimo_deskew_resident_offset(flimo_ctx* c, const flimo_frame* fra
   c->deskew_pending = true;
   c->deskew_kept = true;
   c->async_deskews++;
-  c->scan_n = n; c->sorted_n = n; c->prev.valid = 0;
+  scan_replaced(c, n);
   return FLIMO_OK;
 }
 

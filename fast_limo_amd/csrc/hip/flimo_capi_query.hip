@@ -1,7 +1,7 @@
 // fast_limo_amd/csrc/hip/flimo_capi_query.hip -- C ABI (include/flimo_c.h) over the gfx950 kernels: the analysis entries.
 //
 // The call-at-a-time entries over the stored map (k-NN, radius search, normals, outliers, FPFH, keypoints, clusters, planes, voxels,
-// regions) and over the resident scan, correspondences and descriptors (scan fitness / linearize / NDT, flimo_corr_*, flimo_desc_*).  Each
+// regions) and over the resident scan, correspondences and descriptors (scan fitness / linearize / NDT / GICP, flimo_corr_*, flimo_desc_*).  Each
 // is glue of one shape: check the arguments, take a DevScratch, launch in chunks, copy back, wait once.  The registration path --
 // context, map index, sweep front end, the passes and the chain -- is flimo_capi.hip, which also defines the three functions these
 // entries call into it (ensure_index, flush_deskew, map_remove_masked); struct flimo_ctx and the shared helpers are flimo_ctx.h.
@@ -18,6 +18,7 @@
 #include "flimo_region.h"
 #include "flimo_desc.h"
 #include "flimo_ndt.h"
+#include "flimo_gicp.h"
 #include "flimo_sums.h"
 
 #pragma clang fp contract(off)
@@ -1170,7 +1171,7 @@ extern "C" int flimo_set_voxel_plan(flimo_ctx* c, int plan) {
 // per chunk the poses' matrices go up (pose_from_x26 on the host, as flimo_scan_to_world forms them), three launches (block search,
 // walk over the tiles, the reduction per pose), two numbers per pose -- and the slots, where asked for -- come back; device scratch
 // is the chunk's, whatever np.  Reads d_scan only: d_scan_world and the pass's buffers are left alone.
-// what the entries over pose hypotheses (this one, flimo_scan_linearize, flimo_scan_ndt) share: the poses' check (what: the
+// what the entries over pose hypotheses (this one, flimo_scan_linearize, flimo_scan_ndt, flimo_scan_gicp) share: the poses' check (what: the
 // caller's name in the message) ...
 static int check_poses(flimo_ctx* c, const char* what, const double* x26, size_t np) {
   if (np >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the number of poses must be below 2^31", what);
@@ -1752,4 +1753,198 @@ extern "C" int flimo_ndt_term_host(const float w3[3], const float p3[3], const f
   const bool live = ndt_term(w3, p3, R9, r, -0.5 * d2, d2, [](double x) { return ::exp(x); }, &out30[0], &out30[1], acc);
   memcpy(out30 + 2, acc, sizeof acc);
   return live ? 1 : 0;
+}
+
+// ---- GICP: the resident covariance model and the per-pose normal equations against it (pcl::GeneralizedIterativeClosestPoint) -----
+// kernels: flimo_gicp.hip.  The build is flimo_map_fpfh's first loop -- flimo_map_normals_range's launches over the WHOLE map in
+// chunks of c->normals_chunk points, the covariances left on the device (so the same bits) -- and per chunk the pack into the
+// model's own buffer, 48 B a stored point, kept until the model is rebuilt or cleared; the new model replaces the old one only when
+// everything has succeeded.  Per chunk the scratch is the normals' (normal, count, cov, moments: 140 B a point) and the worklist
+// (8 B); nothing of points x k entries exists and nothing is downloaded.  A pass runs in chunks of whole poses as
+// flimo_scan_linearize, four launches a chunk (flimo_scan_fitness' two searches, reduce, final); reads d_scan only.
+static bool gicp_cfg_ok(const flimo_gicp_cfg* k) {      // (a NaN eps fails the test)
+  return k->min_pts >= 0 && (k->rule == FLIMO_GICP_PLANE || k->rule == FLIMO_GICP_CLAMP) && k->eps > 0.0 && k->eps <= 1.0;
+}
+extern "C" int flimo_gicp_build(flimo_ctx* c, const flimo_gicp_cfg* cfg, size_t* n_cov) {
+  static_assert(FLIMO_GICP_PLANE == GICP_PLANE && FLIMO_GICP_CLAMP == GICP_CLAMP, "the header's rules are the kernels'");
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "gicp build: null cfg");
+  { const int rc = check_gate(c, "gicp build", cfg->max_dist); if (rc) return rc; }
+  if (!gicp_cfg_ok(cfg)) return fail(c, FLIMO_ERR_INVALID, "gicp build: min_pts must be >= 0, rule FLIMO_GICP_PLANE or _CLAMP and eps in (0, 1]");
+  if (cfg->k < 3 || cfg->k > FLIMO_KNN_MAX_K) return fail(c, FLIMO_ERR_UNSUPPORTED, "gicp build: k must be in 3..%d", FLIMO_KNN_MAX_K);
+  { const int rc = check_map_size(c, "gicp build"); if (rc) return rc; }
+  struct Fresh {      // the model under construction: released unless it is handed to the context
+    flimo_ctx::GicpModel m;
+    bool keep = false;
+    ~Fresh() { if (!keep) m.release(); }
+  } f;
+  const size_t N = c->map_n;
+  f.m.built = true; f.m.n = N; f.m.cfg = *cfg; f.m.epoch = c->map_epoch;
+  if (N > 0) {
+    { const int rc = need_index(c, "gicp build"); if (rc) return rc; }
+    ctx_enter(c);
+    DevScratch d;
+    const size_t m = std::min(N, std::max<size_t>(c->normals_chunk, 1));
+    float4* d_normal = d.get<float4>(m);
+    int32_t* d_cnt = d.get<int32_t>(m);
+    double* d_cov = d.get<double>(m * 6);
+    double* d_mom = d.get<double>(m * 9);
+    uint2* d_work = d.get<uint2>(m);
+    unsigned* d_nwork = d.get<unsigned>(1);
+    unsigned* d_count = d.get<unsigned>(1);
+    { const int rc = d.ok(c); if (rc) return rc; }
+    HIPCHK(c, hipMalloc(&f.m.d_cov, N * 6 * sizeof(double)));
+    HIPCHK(c, hipMemsetAsync(d_count, 0, sizeof(unsigned), c->stream));
+    // (a chunk's scratch is read by its own launches only: the stream orders the chunks, nothing waits in between)
+    for (size_t a = 0; a < N; a += m) {
+      const size_t na = std::min(m, N - a);
+      HIPCHK(c, launch_knn_k_normals(c->stream, c->grid, c->d_map_raw, nullptr, (unsigned)a, (int)na, cfg->k, cfg->max_dist, cfg->min_pts, nullptr,
+                                     d_normal, d_cnt, nullptr, d_cov, nullptr, d_mom, d_work, d_nwork));
+      HIPCHK(c, launch_gicp_pack(c->stream, d_cov, (unsigned)na, cfg->rule, cfg->eps, f.m.d_cov + 6 * a, d_count));
+    }
+    unsigned h_count = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_count, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((size_t)h_count > N) return fail(c, FLIMO_ERR_HIP, "gicp build: counted %u covariances of %zu points", h_count, N);
+    f.m.n_cov = h_count;
+  }
+  c->gicp.release();
+  c->gicp = f.m;
+  f.keep = true;
+  if (n_cov) *n_cov = f.m.n_cov;
+  return FLIMO_OK;
+}
+static int gicp_model_of(flimo_ctx* c, const char* what) {
+  if (!c->gicp.built) return fail(c, FLIMO_ERR_NOMAP, "%s: the context holds no model (flimo_gicp_build)", what);
+  return FLIMO_OK;
+}
+extern "C" int flimo_gicp_model(flimo_ctx* c, size_t first, size_t n, double* cov) {
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = gicp_model_of(c, "gicp model"); if (rc) return rc; }
+  const flimo_ctx::GicpModel& m = c->gicp;
+  if (first > m.n || n > m.n - first)
+    return fail(c, FLIMO_ERR_INVALID, "gicp model: the range [%zu, %zu + %zu) ends beyond the model's %zu points", first, first, n, m.n);
+  if (n == 0) return FLIMO_OK;
+  if (!cov) return fail(c, FLIMO_ERR_INVALID, "gicp model: null cov");
+  ctx_enter(c);
+  HIPCHK(c, hipMemcpyAsync(cov, m.d_cov + 6 * first, n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return FLIMO_OK;
+}
+extern "C" int flimo_gicp_info(flimo_ctx* c, flimo_gicp_model_info* info) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!info) return fail(c, FLIMO_ERR_INVALID, "gicp info: null info");
+  { const int rc = gicp_model_of(c, "gicp info"); if (rc) return rc; }
+  const flimo_ctx::GicpModel& m = c->gicp;
+  info->points = m.n; info->n_cov = m.n_cov; info->eps = m.cfg.eps; info->k = m.cfg.k; info->max_dist = m.cfg.max_dist;
+  info->min_pts = m.cfg.min_pts; info->rule = m.cfg.rule;
+  info->stale = m.epoch != c->map_epoch ? 1 : 0;
+  return FLIMO_OK;
+}
+extern "C" int flimo_gicp_clear(flimo_ctx* c) {
+  if (!c) return FLIMO_ERR_INVALID;
+  ctx_enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->gicp.release();
+  return FLIMO_OK;
+}
+extern "C" int flimo_scan_cov_set(flimo_ctx* c, const double* cov6, size_t n) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!cov6 || n == 0) { c->scan_cov_n = 0; return FLIMO_OK; }
+  if (n != c->scan_n) return fail(c, FLIMO_ERR_INVALID, "scan cov set: %zu covariances for a resident scan of %zu points", n, c->scan_n);
+  ctx_enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (a pass still reading the old rows ends first)
+  c->scan_cov_n = 0;
+  { const int rc = ensure_dev(c, c->d_scan_cov, c->scan_cov_cap, n * 6, false, 0); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(c->d_scan_cov, cov6, n * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->scan_cov_n = n;
+  return FLIMO_OK;
+}
+extern "C" size_t flimo_scan_cov_size(const flimo_ctx* c) { return c ? c->scan_cov_n : 0; }
+extern "C" int flimo_scan_gicp(flimo_ctx* c, const double* x26, size_t np, float max_dist, int32_t* valid, double* H, double* g, double* cost,
+                               int32_t* pair_idx, double* pair_m) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if ((np > 0 && !x26) || !valid || !H || !g || !cost) return fail(c, FLIMO_ERR_INVALID, "scan gicp: null poses / valid / H / g / cost");
+  { const int rc = check_gate(c, "scan gicp", max_dist); if (rc) return rc; }
+  { const int rc = check_poses(c, "scan gicp", x26, np); if (rc) return rc; }
+  { const int rc = gicp_model_of(c, "scan gicp"); if (rc) return rc; }
+  if (c->gicp.epoch != c->map_epoch || c->gicp.n != c->map_n)
+    return fail(c, FLIMO_ERR_NOMAP, "scan gicp: the model is stale: the stored points have changed since flimo_gicp_build");
+  const size_t n = c->scan_n;
+  if (c->scan_cov_n != n || (n > 0 && !c->d_scan_cov))
+    return fail(c, FLIMO_ERR_NOMAP, "scan gicp: the resident scan of %zu points has no covariances (flimo_scan_cov_set)", n);
+  if (np == 0) return FLIMO_OK;
+  { const int rc0 = ensure_index(c); if (rc0) return rc0; }
+  if (n > ((size_t)1 << 28)) return fail(c, FLIMO_ERR_TOO_LARGE, "scan gicp: a scan of more than 2^28 points");
+  if (n == 0 || !c->grid_valid || max_dist == 0.f) {      // an empty scan or map, a gate that admits nothing: no pair has a neighbour
+    for (size_t j = 0; j < np; j++) { valid[j] = 0; cost[j] = 0.0; }
+    zero_H_g(H, g, np);
+    if (pair_idx) for (size_t i = 0; i < np * n; i++) pair_idx[i] = -1;
+    if (pair_m) for (size_t i = 0; i < np * n; i++) pair_m[i] = std::numeric_limits<double>::quiet_NaN();
+    return FLIMO_OK;
+  }
+  { const int rcf = enter_flushed(c); if (rcf) return rcf; }
+  // scratch of this call, released on every exit path
+  DevScratch d;
+  PoseChunks P(d, c->gicp_chunk, n, np);
+  const size_t m = P.m, nseg = sum_segments(n);
+  float* d_poses = P.d_poses;
+  float* d_sqd = d.get<float>(m * n);
+  int32_t* d_idx = d.get<int32_t>(m * n);
+  uint2* d_work = d.get<uint2>(m * n);
+  unsigned* d_nwork = d.get<unsigned>(1);
+  double* d_m = pair_m ? d.get<double>(m * n) : nullptr;
+  double* d_part = d.get<double>(m * nseg * GICP_NUM);
+  int32_t* d_part_cnt = d.get<int32_t>(m * nseg);
+  double* d_sums = d.get<double>(m * GICP_NUM);
+  long long* d_valid = d.get<long long>(m);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  static_assert(GICP_NUM == 28, "unpack_sums takes 28 numbers a pose");
+  // (the results of every chunk are gathered on the host first: the caller's arrays stay untouched if a later chunk fails)
+  std::vector<double> sums(m * GICP_NUM), all_sums(np * GICP_NUM), hm(pair_m ? np * n : 0);
+  std::vector<long long> counts(m), all_counts(np);
+  std::vector<int32_t> hi(pair_idx ? np * n : 0);
+  const int rc = P.run(c, x26, np,
+    [&](size_t, size_t kk) -> int {
+      HIPCHK(c, launch_scan_gicp(c->stream, c->grid, c->d_map_raw, c->d_scan, (unsigned)n, d_poses, (unsigned)kk, max_dist, c->gicp.d_cov, c->d_scan_cov,
+                                 d_sqd, d_idx, d_work, d_nwork, d_m, d_part, d_part_cnt, d_sums, d_valid));
+      return FLIMO_OK;
+    },
+    [&](size_t a, size_t kk) -> int {
+      HIPCHK(c, hipMemcpyAsync(counts.data(), d_valid, kk * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(sums.data(), d_sums, kk * GICP_NUM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      if (pair_idx) HIPCHK(c, hipMemcpyAsync(hi.data() + a * n, d_idx, kk * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      if (pair_m) HIPCHK(c, hipMemcpyAsync(hm.data() + a * n, d_m, kk * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      return FLIMO_OK;
+    },
+    [&](size_t a, size_t kk) {
+      memcpy(all_sums.data() + a * GICP_NUM, sums.data(), kk * GICP_NUM * sizeof(double));
+      memcpy(all_counts.data() + a, counts.data(), kk * sizeof(long long));
+    });
+  if (rc) return rc;
+  unpack_sums(all_sums.data(), 0, np, H, g, cost);
+  for (size_t j = 0; j < np; j++) valid[j] = (int32_t)all_counts[j];
+  if (pair_idx) memcpy(pair_idx, hi.data(), hi.size() * sizeof(int32_t));
+  if (pair_m) memcpy(pair_m, hm.data(), hm.size() * sizeof(double));
+  return FLIMO_OK;
+}
+extern "C" int flimo_set_gicp_chunk(flimo_ctx* c, size_t pairs) { return set_chunk(c, &flimo_ctx::gicp_chunk, pairs, (size_t)1 << 20); }
+extern "C" int flimo_gicp_eigen_host(const double cov6[6], double eig12[12]) {
+  if (!cov6 || !eig12) return FLIMO_ERR_INVALID;
+  double l[3], v[3][3];
+  gicp_eigen(cov6, l, v);
+  memcpy(eig12, l, sizeof l);
+  memcpy(eig12 + 3, v, sizeof v);
+  return FLIMO_OK;
+}
+extern "C" int flimo_gicp_regularize_host(const double cov6[6], int rule, double eps, double out6[6]) {
+  if (!cov6 || !out6) return FLIMO_ERR_INVALID;
+  if ((rule != FLIMO_GICP_PLANE && rule != FLIMO_GICP_CLAMP) || !(eps > 0.0 && eps <= 1.0)) return FLIMO_ERR_INVALID;
+  return gicp_regularize(cov6, rule, eps, out6) ? 1 : 0;
+}
+extern "C" int flimo_gicp_term_host(const float w3[3], const float b3[3], const float p3[3], const float R9[9], const double CA6[6], const double CB6[6],
+                                    double out30[30]) {
+  if (!w3 || !b3 || !p3 || !R9 || !CA6 || !CB6 || !out30) return FLIMO_ERR_INVALID;
+  return gicp_term(w3, b3, p3, R9, CA6, CB6, out30) ? 1 : 0;
 }

@@ -87,6 +87,24 @@ struct flimo_ctx {
   } ndt[FLIMO_NDT_SLOTS];
   uint64_t map_epoch = 0;                   // bumped whenever the stored points change: the insert, the clear, the removals' shared tail
   size_t ndt_chunk = (size_t)1 << 20;       // (pose, point) pairs per chunk of flimo_scan_ndt (flimo_set_ndt_chunk)
+  // the resident GICP model (flimo_gicp_build): one regularised covariance per stored point, by INSERTION INDEX -- a snapshot like an
+  // NDT model, but usable only for the map it was built from (a removal renumbers the points): flimo_scan_gicp refuses it once
+  // map_epoch has moved
+  struct GicpModel {
+    bool built = false;
+    size_t n = 0, n_cov = 0;                // stored points at the build; those that got a covariance
+    flimo_gicp_cfg cfg{};
+    uint64_t epoch = 0;                     // map_epoch at the build
+    double* d_cov = nullptr;                // [n][6] xx xy xz yy yz zz, six NaN where there is none
+    void release() {
+      (void)hipFree(d_cov);
+      *this = GicpModel{};
+    }
+  } gicp;
+  // the covariances of the resident scan's points (flimo_scan_cov_set): the caller's, dropped whenever the scan is replaced
+  double* d_scan_cov = nullptr;             // [scan_cov_n][6], body frame, the scan's order
+  size_t scan_cov_n = 0, scan_cov_cap = 0;
+  size_t gicp_chunk = (size_t)1 << 20;      // (pose, point) pairs per chunk of flimo_scan_gicp (flimo_set_gicp_chunk)
   bool sorted_follows = false;     // the raw buffer grew: the cell-sorted copy (3x its capacity) and the escape pool have to follow
   IndexTables idx;                 // the index of the main grid (GridView, flimo_types.h): tiles, directory, escapes, xstart
   GridView grid{};
@@ -378,6 +396,13 @@ static inline void cancel_prelaunch(flimo_ctx* c) {
 static inline void ctx_enter(flimo_ctx* c) {
   (void)hipSetDevice(c->device);
   cancel_prelaunch(c);
+}
+
+// every call that replaces the resident scan ends here: n points, no cell-sorted prefix yet to trust beyond them, no previous pass,
+// and none of what the caller uploaded per point of the old scan (flimo_scan_cov_set)
+static inline void scan_replaced(flimo_ctx* c, size_t n) {
+  c->scan_n = n; c->sorted_n = n; c->prev.valid = 0;
+  c->scan_cov_n = 0;
 }
 
 // defined in flimo_capi.hip, called from flimo_capi_query.hip too (hidden: the library exports nothing for them)

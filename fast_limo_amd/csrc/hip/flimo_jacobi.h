@@ -2,6 +2,7 @@
 // or a voxel in its principal axes shares: a cyclic Jacobi until the off-diagonal is exactly 0, the eigenvalues in ascending order
 // (on a tie the lower column first), the unit vectors as the rotations leave them.  kk_plane (flimo_knn_k.hip) keeps the smallest
 // one's vector and orients it; the NDT cell kernel (flimo_ndt.hip) keeps all three.  One text: their bits are the same by construction.
+// Host AND device: gicp_regularize (flimo_gicp.h) runs it on both; every operation is an IEEE float64 +, -, *, / or sqrt.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +12,7 @@ namespace flimo {
 
 // one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3: app, aqq, apq its 2 x 2; arp, arq the third row's entries of those
 // columns; v*p, v*q columns p and q of the accumulated eigenvectors (Rutishauser's update: apq becomes exactly 0)
-__device__ __forceinline__ void kk_jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
+__host__ __device__ __forceinline__ void kk_jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
                                               double& v1p, double& v1q, double& v2p, double& v2q) {
   if (apq == 0.0) return;
   const double g = fabs(apq);
@@ -36,11 +37,11 @@ __device__ __forceinline__ void kk_jacobi_rot(double& app, double& aqq, double& 
 }
 
 constexpr int KK_JACOBI_SWEEPS = 12;
-__device__ __forceinline__ void kk_swap_if(bool c, double& a, double& b) { const double x = c ? b : a, y = c ? a : b; a = x; b = y; }
+__host__ __device__ __forceinline__ void kk_swap_if(bool c, double& a, double& b) { const double x = c ? b : a, y = c ? a : b; a = x; b = y; }
 
 // The principal axes of a symmetric 3 x 3 covariance: l0 <= l1 <= l2 and the unit vectors as COLUMNS of v (vRC: row R, column C;
 // column k belongs to lk), with whatever sign the rotations leave.
-__device__ __forceinline__ void kk_eigen3(double a00, double a01, double a02, double a11, double a12, double a22, double& l0, double& l1, double& l2,
+__host__ __device__ __forceinline__ void kk_eigen3(double a00, double a01, double a02, double a11, double a12, double a22, double& l0, double& l1, double& l2,
                                           double& v00, double& v01, double& v02, double& v10, double& v11, double& v12, double& v20, double& v21,
                                           double& v22) {
   v00 = 1.0; v01 = 0.0; v02 = 0.0; v10 = 0.0; v11 = 1.0; v12 = 0.0; v20 = 0.0; v21 = 0.0; v22 = 1.0;

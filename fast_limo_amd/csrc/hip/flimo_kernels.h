@@ -371,8 +371,12 @@ hipError_t launch_iss_suppress(hipStream_t st, const GridView& G, const float4* 
 // the world point is transform_kernel's, from poses [np][12] (the upper three rows of PoseMats::RT).  sqd [np][n]: the nearest
 // stored point's squared distance, -1 for an empty query; idx [np][n] (optional): its insertion index, -1; inliers / sum_sqd [np]:
 // the slots that hold a distance and their float64 sum in one fixed shape.  n * np <= 2^31, np <= FIT_MAX_POSES.  Scratch: work
-// ([np * n]), nwork.
+// ([np * n]), nwork.  launch_scan_fitness is its two halves: the two search launches that fill sqd / idx (launch_scan_fit_search, which
+// flimo_scan_gicp runs on its own) and the launch that counts and sums them per pose (launch_scan_fit_reduce).
 constexpr unsigned FIT_MAX_POSES = 65535;
+hipError_t launch_scan_fit_search(hipStream_t st, const GridView& G, const float4* scan, unsigned n, const float* poses, unsigned np, float max_dist,
+                                  float* sqd, int32_t* idx, uint2* work, unsigned* nwork);
+hipError_t launch_scan_fit_reduce(hipStream_t st, const float* sqd, unsigned n, unsigned np, int32_t* inliers, double* sum_sqd);
 hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* scan, unsigned n, const float* poses, unsigned np, float max_dist,
                                float* sqd, int32_t* idx, uint2* work, unsigned* nwork, int32_t* inliers, double* sum_sqd);
 
@@ -474,5 +478,16 @@ hipError_t launch_ndt_pack(hipStream_t st, const uint32_t* flag, const uint32_t*
 hipError_t launch_scan_ndt(hipStream_t st, const float4* scan, unsigned n, const float* poses, unsigned np, int hood, float inv, double d2,
                            const unsigned long long* keys, const void* cells, unsigned nc, int32_t* cell, double* e, double* m, double* part,
                            int32_t* part_cnt, double* sums, long long* counts);
+
+// flimo_gicp.hip -- the GICP covariance model and the per-pose sums against it (flimo_gicp_build, flimo_scan_gicp; flimo_c.h).
+//  launch_gicp_pack   behind launch_knn_k_normals: out [n][6] = gicp_regularize (flimo_gicp.h) of cov [n][6], six NaN where there
+//                     is none; *count (device) grows by the rows that got one.
+//  launch_scan_gicp   a chunk of np poses (np <= FIT_MAX_POSES, n * np <= 2^28): launch_scan_fit_search into sqd / idx [np * n] (idx
+//                     is required), then the terms against model [map size][6] and scan_cov [n][6]: pair_m [np * n] (may be null;
+//                     NaN for an invalid pair), part [np * segments][28], part_cnt [np * segments]; sums [np][28], valid [np].
+hipError_t launch_gicp_pack(hipStream_t st, const double* cov, unsigned n, int rule, double eps, double* out, unsigned* count);
+hipError_t launch_scan_gicp(hipStream_t st, const GridView& G, const float4* map_raw, const float4* scan, unsigned n, const float* poses, unsigned np,
+                            float max_dist, const double* model, const double* scan_cov, float* sqd, int32_t* idx, uint2* work, unsigned* nwork,
+                            double* pair_m, double* part, int32_t* part_cnt, double* sums, long long* valid);
 
 }  // namespace flimo

@@ -1203,18 +1203,26 @@ hipError_t launch_outlier_mask(hipStream_t st, const double* mean, const int32_t
   return hipGetLastError();
 }
 
-hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* scan, unsigned n, const float* poses, unsigned np, float max_dist,
-                               float* sqd, int32_t* idx, uint2* work, unsigned* nwork, int32_t* inliers, double* sum_sqd) {
+hipError_t launch_scan_fit_search(hipStream_t st, const GridView& G, const float4* scan, unsigned n, const float* poses, unsigned np, float max_dist,
+                                  float* sqd, int32_t* idx, uint2* work, unsigned* nwork) {
   if (n == 0 || np == 0) return hipSuccess;
   if ((unsigned long long)n * np > 0x80000000ull || np > FIT_MAX_POSES) return hipErrorInvalidValue;
   FitJob J;
   J.P = KkPairs{scan, poses, n, np, 0};
   kk_gate(max_dist, J.r2, J.gate_key);
   J.sqd = sqd; J.idx = idx;
-  const hipError_t e = kk_launch(st, G, J, work, nwork);
-  if (e != hipSuccess) return e;
+  return kk_launch(st, G, J, work, nwork);
+}
+hipError_t launch_scan_fit_reduce(hipStream_t st, const float* sqd, unsigned n, unsigned np, int32_t* inliers, double* sum_sqd) {
+  if (n == 0 || np == 0) return hipSuccess;
   hipLaunchKernelGGL(fit_reduce_kernel, dim3(np), dim3(FIT_RED), 0, st, sqd, n, inliers, sum_sqd);
   return hipGetLastError();
+}
+hipError_t launch_scan_fitness(hipStream_t st, const GridView& G, const float4* scan, unsigned n, const float* poses, unsigned np, float max_dist,
+                               float* sqd, int32_t* idx, uint2* work, unsigned* nwork, int32_t* inliers, double* sum_sqd) {
+  const hipError_t e = launch_scan_fit_search(st, G, scan, n, poses, np, max_dist, sqd, idx, work, nwork);
+  if (e != hipSuccess) return e;
+  return launch_scan_fit_reduce(st, sqd, n, np, inliers, sum_sqd);
 }
 
 hipError_t launch_scan_linearize(hipStream_t st, const GridView& G, const float4* map_raw, const float4* scan, unsigned n, const float* poses,

@@ -376,6 +376,31 @@ int flimo_loc_scan_ndt(flimo_loc* L, int slot, const double* x26, size_t np, int
   if (!L) return FLIMO_ERR_INVALID;
   return L->map->ndt(slot, x26, np, hood, d2, valid, cells, H, g, score, terms, term_cell);
 }
+int flimo_loc_gicp_build(flimo_loc* L, const flimo_gicp_cfg* cfg, size_t* n_cov) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_gicp_build(ctx_of(L), cfg, n_cov);
+}
+int flimo_loc_gicp_model(flimo_loc* L, size_t first, size_t n, double* cov) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_gicp_model(ctx_of(L), first, n, cov);
+}
+int flimo_loc_gicp_info(flimo_loc* L, flimo_gicp_model_info* info) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_gicp_info(ctx_of(L), info);
+}
+int flimo_loc_gicp_clear(flimo_loc* L) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_gicp_clear(ctx_of(L));
+}
+int flimo_loc_scan_cov_set(flimo_loc* L, const double* cov6, size_t n) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_scan_cov_set(ctx_of(L), cov6, n);
+}
+int flimo_loc_scan_gicp(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* valid, double* H, double* g, double* cost,
+                        int32_t* pair_idx, double* pair_m) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_scan_gicp(ctx_of(L), x26, np, max_dist, valid, H, g, cost, pair_idx, pair_m);
+}
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
 // the map insert that ends a scan runs on the Mapper's worker thread (Mapper::add_scan): wait for it / switch it off

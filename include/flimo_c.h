@@ -973,6 +973,116 @@ int flimo_scan_ndt(flimo_ctx* ctx, int slot, const double* x26 /* [np][26] */, s
  * 0 otherwise, FLIMO_ERR_INVALID for a NULL pointer.  Needs no device. */
 int flimo_ndt_term_host(const float w3[3], const float p3[3], const float R9[9], const double mean3[3], const double evec9[9],
                         const double wgt3[3], double d2, double out30[30]);
+/* ---- GICP, generalized ICP or plane-to-plane (what pcl::GeneralizedIterativeClosestPoint and fast_gicp linearise; the reference
+ *      has no counterpart): the consumer of flimo_map_normals' covariances.  Every residual -- the scan point at the pose minus its
+ *      nearest stored point -- is weighed by the shape of BOTH surfaces, M = (CB + R CA R^T)^-1.  The map's covariances are a
+ *      resident MODEL built once (flimo_gicp_build); the scan's are the caller's, uploaded once per scan (flimo_scan_cov_set: the
+ *      library does not index the scan; a second context whose map is the scan computes them, fast_limo_amd.api.gicp_covs);
+ *      flimo_scan_gicp then gives, for each of np pose hypotheses, the 6 x 6 Gauss-Newton normal equations.  Every quantity below is
+ *      float64 on float32 inputs widened, uncontracted, in exactly the written association; a covariance is its six numbers
+ *      xx xy xz yy yz zz; a three-term sum is written x0 + (x1 + x2). ----
+ * The regularised covariance C' of a neighbourhood covariance C (gicp_regularize, fast_limo_amd/csrc/hip/flimo_gicp.h):
+ *  - the eigen-solve of C is the cyclic Jacobi of flimo_map_normals' plane and of the NDT cells (ascending l0 <= l1 <= l2, on a tie the
+ *    lower column first; unit vectors v0 v1 v2 with whatever sign the rotations leave).
+ *  - NO covariance: any of the six numbers non-finite, or not l2 > 0.0.  C' is then six NaN.
+ *  - FLIMO_GICP_PLANE (PCL's rule; eps in (0, 1], PCL: 1e-3): l0' = eps, l1' = l2' = 1.0.
+ *    FLIMO_GICP_CLAMP (the NDT model's rule; eps plays eig_ratio): floor = eps * l2 (one product), lk' = lk < floor ? floor : lk.
+ *  - C'_ab = ((0.0 + (l0' * v0[a]) * v0[b]) + (l1' * v1[a]) * v1[b]) + (l2' * v2[a]) * v2[b] for the six ab.
+ * flimo_gicp_build(ctx, cfg, &n_cov): ONE model per context, a row of six numbers per stored point in insertion order.
+ *  - C of stored point i is exactly flimo_map_normals_range(0, map size, k, max_dist, min_pts)'s cov[i], bit for bit (six NaN below
+ *    max(3, min_pts) neighbours): its launches run over the whole map in chunks of flimo_set_normals_chunk points, the covariances
+ *    stay on the device, nothing of points x k entries exists and nothing is downloaded.  Row i is C' of that; *n_cov counts the rows
+ *    that got one.
+ *  - the model is a SNAPSHOT indexed by insertion index, and a removal renumbers the stored points: it is usable only for the map
+ *    it was built from.  flimo_gicp_info's `stale` is 1, and flimo_scan_gicp refuses the model, once the stored points have changed
+ *    (an insert, a crop or another removal, flimo_map_clear).  A build on an empty map gives an empty model: FLIMO_OK, *n_cov = 0.
+ *    A build replaces the context's model -- only when everything has succeeded.
+ *  FLIMO_ERR_UNSUPPORTED: k outside 3 .. FLIMO_KNN_MAX_K.  FLIMO_ERR_INVALID: NULL ctx / cfg, max_dist NaN or < 0 (INFINITY: no
+ *  gate), min_pts < 0, an unknown rule, eps NaN or outside (0, 1].  FLIMO_ERR_TOO_LARGE: a map of 2^31 points or more.  On an error
+ *  *n_cov and the old model are untouched.  Calling rules of flimo_map_normals (no pass in flight); the map, the scan and the bits of
+ *  a later pass are unchanged.  n_cov may be NULL.
+ * flimo_gicp_model(ctx, first, n, cov): downloads rows first .. first + n - 1, cov [n][6].  FLIMO_ERR_INVALID for a range beyond the
+ *  model's points or a NULL cov with n > 0.  flimo_gicp_info(ctx, &info).  Both: FLIMO_ERR_NOMAP without a model.
+ *  flimo_gicp_clear(ctx): frees the model. */
+#define FLIMO_GICP_PLANE 0
+#define FLIMO_GICP_CLAMP 1
+typedef struct flimo_gicp_cfg {
+  int k;            /* neighbours of a stored point's covariance, 3 .. FLIMO_KNN_MAX_K (PCL: 20) */
+  float max_dist;   /* their gate [m]; INFINITY: none */
+  int min_pts;      /* a point with fewer than max(3, min_pts) neighbours has no covariance */
+  int rule;         /* FLIMO_GICP_PLANE or FLIMO_GICP_CLAMP */
+  double eps;       /* in (0, 1] */
+} flimo_gicp_cfg;
+typedef struct flimo_gicp_model_info {
+  uint64_t points;  /* stored points the build saw: the model's rows */
+  uint64_t n_cov;   /* rows that hold a covariance */
+  double eps;       /* the cfg of the build: eps, k, max_dist, min_pts, rule */
+  int k;
+  float max_dist;
+  int min_pts;
+  int rule;
+  int stale;        /* 1: the stored points have changed since the build; flimo_scan_gicp refuses the model */
+} flimo_gicp_model_info;
+int flimo_gicp_build(flimo_ctx* ctx, const flimo_gicp_cfg* cfg, size_t* n_cov);
+int flimo_gicp_model(flimo_ctx* ctx, size_t first, size_t n, double* cov /* [n][6] */);
+int flimo_gicp_info(flimo_ctx* ctx, flimo_gicp_model_info* info);
+int flimo_gicp_clear(flimo_ctx* ctx);
+/* The covariances of the resident scan's points: cov6 [n][6], one REGULARISED covariance per point, in the body frame, in
+ * flimo_scan_to_world's order; a row with a NaN means "this point has none".  n must be flimo_scan_size(ctx) (FLIMO_ERR_INVALID
+ * otherwise); n == 0 or a NULL cov6 drops the covariances.  Every call that replaces the resident scan drops them too
+ * (flimo_scan_set, flimo_scan_voxel_filter, the raw-scan and deskew entries); a deskew still pending does not: it is the same
+ * points in the same order.  flimo_scan_cov_size: n, or 0 when there are none. */
+int    flimo_scan_cov_set(flimo_ctx* ctx, const double* cov6 /* [n][6] */, size_t n);
+size_t flimo_scan_cov_size(const flimo_ctx* ctx);
+/* ---- the GICP normal equations of the resident scan against the stored points, for each of np pose hypotheses ----
+ * x26 [np][26]: the poses; only pos and rot are read.  n = flimo_scan_size(ctx).  Per (pose j, scan point i):
+ *  - w: the float32 world point and b: its nearest stored point are exactly flimo_scan_fitness(max_dist)'s -- nn_idx under the same
+ *    gate and the same order (distance bits, insertion index); b's coordinates are the stored point's float32.
+ *  - CB = the model's row of b, CA = the scan's row i; p: the float32 scan point, R: the nine float32 rotation entries of the pose's
+ *    matrix, row-major.  The term (gicp_term, flimo_gicp.h):
+ *      r      = (double)w - (double)b                                  (three subtractions)
+ *      T_ij   = R_i0*CA_0j + (R_i1*CA_1j + R_i2*CA_2j)                 (T = R CA)
+ *      S_ij   = CB_ij + (T_i0*R_j0 + (T_i1*R_j1 + T_i2*R_j2))          for the six i <= j (S = CB + R CA R^T)
+ *      c00 = S11*S22 - S12*S12, c01 = S02*S12 - S01*S22, c02 = S01*S12 - S02*S11,
+ *      c11 = S00*S22 - S02*S02, c12 = S01*S02 - S00*S12, c22 = S00*S11 - S01*S01   (the cofactors)
+ *      det    = S00*c00 + (S01*c01 + S02*c02);   M_ij = c_ij / det     (six divisions; M symmetric)
+ *    The pair is LIVE iff all twelve covariance numbers are finite and det > 0.0 and 1.0 / det is finite.  For a live pair
+ *      y_i    = M_i0*r_0 + (M_i1*r_1 + M_i2*r_2);   m = r_0*y_0 + (r_1*y_1 + r_2*y_2)
+ *      J_c    = column c of R for c = 0, 1, 2;  J_3 = p.y*J_2 - p.z*J_1,  J_4 = p.z*J_0 - p.x*J_2,  J_5 = p.x*J_1 - p.y*J_0
+ *               (componentwise: the columns of [R | -R [p]x], the derivative of r under flimo_scan_linearize's body-frame
+ *               perturbation t <- t + R drho, R <- R Exp(dphi), with M held fixed)
+ *      U_c[i] = M_i0*J_c[0] + (M_i1*J_c[1] + M_i2*J_c[2])
+ *      H_ab   = J_a[0]*U_b[0] + (J_a[1]*U_b[1] + J_a[2]*U_b[2])  for the 21 upper-triangle entries, row-major 00, 01 .. 55
+ *      g_a    = J_a[0]*y_0 + (J_a[1]*y_1 + J_a[2]*y_2);   cost = m
+ *    J is built from R and scan coordinates and r is a difference: a map kilometres from the origin costs no conditioning.  g is the
+ *    gradient of (1/2) sum m at fixed M, H is positive semidefinite whenever S is positive definite: H xi = -g is the step
+ *    fast_limo_amd.api.scan_align already solves (api.gicp_align iterates it).
+ *  - the pair is VALID iff it has a neighbour inside the gate and its term is live.
+ * Outputs, host memory, per pose: H [np][21], g [np][6], cost [np] (the sum of m); valid [np].  The 28 sums are taken in the one
+ * shape of fast_limo_amd/csrc/hip/flimo_sums.h, a slot being a scan point: every contribution ONE add onto
+ * the thread's accumulator, which starts at +0.0; an invalid slot adds +0.0.  No floating-point atomics: the bits depend on the
+ * scan, its covariances, the stored points, the model, the pose and max_dist alone -- not on np, the other poses, the chunking, the
+ * cell size or the search path.  pair_idx [np][n] (may be NULL): the neighbour's insertion index or -1, for an invalid pair with a
+ * neighbour as well; pair_m [np][n] (may be NULL): m, NaN for an invalid pair.
+ * FLIMO_ERR_NOMAP: no model, a stale model (the message says so), or no covariances of the resident scan.  FLIMO_ERR_INVALID: NULL
+ * ctx / x26 (np > 0) / valid / H / g / cost, max_dist NaN or < 0, a non-finite value among x26[j][0..6].  FLIMO_ERR_TOO_LARGE:
+ * np >= 2^31.  The outputs are untouched on any error.  FLIMO_OK with all sums 0, pair_idx -1 and pair_m NaN for an empty scan, an
+ * empty map and max_dist == 0; np == 0 returns FLIMO_OK and touches nothing.  A pending deskew runs first; the scan, the map, the
+ * model and the bits of a later pass are unchanged.  Device memory is taken per chunk of 2^20 (pose, point) pairs -- whole poses
+ * (flimo_set_gicp_chunk, flimo_dev.h) --, 16 B a pair (24 B with pair_m). */
+int flimo_scan_gicp(flimo_ctx* ctx, const double* x26 /* [np][26] */, size_t np, float max_dist, int32_t* valid /* [np] */,
+                    double* H /* [np][21] */, double* g /* [np][6] */, double* cost /* [np] */, int32_t* pair_idx /* [np][n], may be NULL */,
+                    double* pair_m /* [np][n], may be NULL */);
+/* The functions the kernels call (flimo_gicp.h), on the host; none needs a device.  flimo_gicp_eigen_host: eig12 = l0 l1 l2, v0, v1,
+ * v2 of cov6 by the Jacobi above.  flimo_gicp_regularize_host: out6 = C'; returns 1, or 0 (six NaN) where there is no covariance;
+ * FLIMO_ERR_INVALID for a NULL pointer, an unknown rule, eps NaN or outside (0, 1].  flimo_gicp_term_host: w3 the float32 world point,
+ * b3 the float32 stored point, p3 the float32 scan point, R9 the rotation, row-major; out30 = m, det, then the 28 contributions (H's
+ * 21, g's 6, the cost) -- all 0 when the term is not live.  Returns 1 for a live term, 0 otherwise, FLIMO_ERR_INVALID for a NULL
+ * pointer. */
+int flimo_gicp_eigen_host(const double cov6[6], double eig12[12]);
+int flimo_gicp_regularize_host(const double cov6[6], int rule, double eps, double out6[6]);
+int flimo_gicp_term_host(const float w3[3], const float b3[3], const float p3[3], const float R9[9], const double CA6[6], const double CB6[6],
+                         double out30[30]);
 /* ---- pose hypotheses from point correspondences: what pcl::SampleConsensusPrerejective does per sample (the reference's
  *      relocation branch gets the same from KISS-Matcher's pruning and solver) -- minimal samples of three correspondences, a cheap
  *      polygon test, a closed-form rigid pose for each of the rest, and the count of the correspondences each pose explains, for

@@ -124,6 +124,10 @@ int flimo_set_linearize_chunk(flimo_ctx* ctx, size_t pairs);
  * pose with more points than that runs alone.  The chunk bounds the call's device scratch (84 B a pair at hood 7).  The results do
  * not depend on it (tests, A/B). */
 int flimo_set_ndt_chunk(flimo_ctx* ctx, size_t pairs);
+/* flimo_scan_gicp works in chunks of whole poses, at most `pairs` (pose, point) pairs each (default 2^20; 0 restores it); a single
+ * pose with more points than that runs alone.  The chunk bounds the call's device scratch (16 B a pair, 24 B with pair_m).  The
+ * results do not depend on it (tests, A/B). */
+int flimo_set_gicp_chunk(flimo_ctx* ctx, size_t pairs);
 
 /* out[0] = GPU ms of the algebra launches timed so far (timing level 1), out[1] = their number,
  * out[2] = chains run, out[3] = chains that came back before the final iteration, out[4] = chains declined */

@@ -211,6 +211,19 @@ int    flimo_loc_ndt_info(flimo_loc* L, int slot, flimo_ndt_model_info* info);
 int    flimo_loc_ndt_clear(flimo_loc* L, int slot);
 int    flimo_loc_scan_ndt(flimo_loc* L, int slot, const double* x26, size_t np, int hood, double d2, int32_t* valid, int64_t* cells, double* H,
                           double* g, double* score, double* terms, int32_t* term_cell);
+/* GICP against the Localizer's map (the reference has no counterpart): flimo_gicp_build / flimo_gicp_model / flimo_gicp_info /
+ * flimo_gicp_clear / flimo_scan_cov_set / flimo_scan_gicp (include/flimo_c.h: same arguments, same results, same error codes) on the
+ * map's context, after an insert, a crop or a carve still running behind the last sweep has ended.  The model is a snapshot of the
+ * stored points by insertion index: a sweep's insert or a local map's crop makes it stale, and flimo_scan_gicp then answers
+ * FLIMO_ERR_NOMAP until it is rebuilt; every sweep replaces the resident scan and so drops its covariances
+ * (flimo_scan_cov_size(flimo_loc_ctx(L)) tells how many there are).  The Localizer's own update does not use them. */
+int    flimo_loc_gicp_build(flimo_loc* L, const flimo_gicp_cfg* cfg, size_t* n_cov);
+int    flimo_loc_gicp_model(flimo_loc* L, size_t first, size_t n, double* cov);
+int    flimo_loc_gicp_info(flimo_loc* L, flimo_gicp_model_info* info);
+int    flimo_loc_gicp_clear(flimo_loc* L);
+int    flimo_loc_scan_cov_set(flimo_loc* L, const double* cov6, size_t n);
+int    flimo_loc_scan_gicp(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* valid, double* H, double* g, double* cost,
+                           int32_t* pair_idx, double* pair_m);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
