@@ -4,7 +4,7 @@ symbols the tests compare with the headers are read off them.
 
 A new entry that both a ``flimo_ctx`` and a ``flimo_loc`` offer is one row of ``PAIRED`` -- the two symbols and the arguments after
 the handle -- and one method of ``_lib._SharedEntries``; ``HipCtx`` and ``Localizer`` then both have it.  ``PAIRED_NDT`` and
-``PAIRED_GICP`` hold the rows of the NDT and the GICP entries in the same form."""
+``PAIRED_GICP`` hold the rows of the NDT and the GICP entries in the same form, ``PAIRED_SC`` those of Scan Context."""
 from __future__ import annotations
 
 import ctypes as C
@@ -145,6 +145,16 @@ class GicpInfo(_Stats):
                 ("min_pts", C.c_int), ("rule", C.c_int), ("stale", C.c_int)]
 
 
+class ScCfg(C.Structure):
+    """flimo_sc_cfg (include/flimo_c.h)."""
+    _fields_ = [("rings", C.c_int), ("sectors", C.c_int), ("min_range", C.c_float), ("max_range", C.c_float), ("z_offset", C.c_float)]
+
+
+class ScMatchCfg(C.Structure):
+    """flimo_sc_match_cfg (include/flimo_c.h)."""
+    _fields_ = [("k", C.c_int), ("min_cols", C.c_int), ("max_dist", C.c_float)]
+
+
 class CorrGraphCfg(C.Structure):
     """flimo_corr_graph_cfg (include/flimo_c.h)."""
     _fields_ = [("tol", C.c_float), ("min_edge", C.c_float), ("edge_sim", C.c_float)]
@@ -242,7 +252,16 @@ PAIRED_GICP = (
     ("flimo_scan_cov_set", "flimo_loc_scan_cov_set", [vp, sz]),
     ("flimo_scan_gicp", "flimo_loc_scan_gicp", [vp, sz, f, vp, vp, vp, vp, vp, vp]),
 )
-PAIRED_ALL = PAIRED + PAIRED_NDT + PAIRED_GICP
+# Scan Context: the descriptor of the resident scan, the resident database and the match.
+PAIRED_SC = (
+    ("flimo_scan_context", "flimo_loc_scan_context", [P(ScCfg), vp, vp, vp]),
+    ("flimo_sc_db_add", "flimo_loc_sc_db_add", [vp, sz, i, i, P(sz)]),
+    ("flimo_sc_db_add_scan", "flimo_loc_sc_db_add_scan", [P(ScCfg), vp, P(sz)]),
+    ("flimo_sc_db_get", "flimo_loc_sc_db_get", [sz, sz, vp]),
+    ("flimo_sc_db_clear", "flimo_loc_sc_db_clear", []),
+    ("flimo_sc_match", "flimo_loc_sc_match", [vp, sz, i, i, sz, sz, P(ScMatchCfg), vp, vp, vp, vp, vp]),
+)
+PAIRED_ALL = PAIRED + PAIRED_NDT + PAIRED_GICP + PAIRED_SC
 LOC_OF = {hip: loc for hip, loc, _ in PAIRED_ALL}
 
 # Everything else: (result, symbol, every argument -- the handle, where there is one, included).
@@ -283,6 +302,10 @@ HIP_ONLY = (
     (sz, "flimo_desc_ref_size", [vp]),
     (i, "flimo_desc_ref_dim", [vp]),
     (f, "flimo_desc_last_ms", [vp]),
+    (i, "flimo_set_sc_chunk", [vp, sz, sz]),
+    (sz, "flimo_sc_db_size", [vp]),
+    (i, "flimo_sc_db_shape", [vp, P(i), P(i)]),
+    (f, "flimo_sc_last_ms", [vp]),
     # the functions the kernels call, on the host
     (i, "flimo_plane_solve_host", [vp, P(PlaneCfg), vp, vp]),
     (i, "flimo_voxel_key_host", [vp, f, vp, P(u64)]),
@@ -290,6 +313,8 @@ HIP_ONLY = (
     (i, "flimo_corr_pose_host", [vp, vp, P(CorrCfg), vp, vp]),
     (i, "flimo_corr_compatible_host", [vp, vp, vp, vp, P(CorrGraphCfg)]),
     (i, "flimo_desc_dist_host", [vp, vp, i, vp]),
+    (i, "flimo_sc_bin_host", [vp, P(ScCfg), vp, P(i), P(i), P(f)]),
+    (i, "flimo_sc_dist_host", [vp, vp, i, i, i, P(f), P(i), vp]),
     (i, "flimo_ndt_term_host", [vp, vp, vp, vp, vp, vp, d, vp]),
     (i, "flimo_gicp_eigen_host", [vp, vp]),
     (i, "flimo_gicp_regularize_host", [vp, i, d, vp]),

@@ -15,7 +15,7 @@ import numpy as np
 from . import _abi
 # (every structure stays a name of this module: callers and tests say _lib.MatchCfg, _lib.Frame, ...)
 from ._abi import (CHAIN_MAX_PASSES, CarveCfg, ChainIO, ChainPass, ClusterCfg, ClusterStats, CorrCfg, CorrGraphCfg, FilterCfg, FpfhCfg, Frame,
-                   GicpCfg, GicpInfo, KeypointCfg, MapCfg, MatchCfg, NdtCfg, NdtInfo, OutlierCfg, OutlierStats, PlaneCfg, PlaneSel, RegionCfg, RegionStats, VoxelCfg, VoxelStats,
+                   GicpCfg, GicpInfo, KeypointCfg, MapCfg, MatchCfg, NdtCfg, NdtInfo, OutlierCfg, OutlierStats, PlaneCfg, PlaneSel, RegionCfg, RegionStats, ScCfg, ScMatchCfg, VoxelCfg, VoxelStats,
                    f32p, f64p, i32p)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -130,6 +130,39 @@ def desc_rows(desc):
     """A descriptor array as the calls take it: C-contiguous float32 [n, dim] (a 1-D array is one column)."""
     d = np.ascontiguousarray(desc, dtype=np.float32)
     return d.reshape(-1, 1) if d.ndim == 1 else d.reshape(d.shape[0], int(np.prod(d.shape[1:])))
+
+
+SC_MAX_RINGS, SC_MAX_SECTORS, SC_MAX_K = 32, 64, 8      # FLIMO_SC_MAX_*
+
+
+def sc_cfg(rings=20, sectors=60, min_range=0.0, max_range=80.0, z_offset=2.0) -> ScCfg:
+    """Scan Context's published shape unless told otherwise: 20 rings x 60 sectors out to 80 m, the sensor 2 m above the ground."""
+    return ScCfg(int(rings), int(sectors), float(min_range), float(max_range), float(z_offset))
+
+
+def _as_sc_cfg(cfg, kw):
+    if isinstance(cfg, ScCfg):
+        if kw:
+            raise ValueError("scan context: give a ScCfg or the fields of sc_cfg, not both")
+        return cfg
+    if cfg is not None:
+        raise ValueError("scan context: cfg must be a ScCfg")
+    return sc_cfg(**kw)
+
+
+def _frame12(frame12):
+    """A row-major 3 x 4 transform as the calls take it: float32 [12], None for none."""
+    return None if frame12 is None else np.ascontiguousarray(frame12, dtype=np.float32).reshape(12)
+
+
+def sc_rows(desc):
+    """Descriptors as the calls take them: C-contiguous float32 [n, rings, sectors] (a 2-D array is one descriptor)."""
+    d = np.ascontiguousarray(desc, dtype=np.float32)
+    if d.ndim == 2:
+        d = d.reshape(1, *d.shape)
+    if d.ndim != 3:
+        raise ValueError("scan context: descriptors are [n, rings, sectors]")
+    return d
 
 
 MATCH_REC_DTYPE = np.dtype([
@@ -732,6 +765,65 @@ class _SharedEntries:
         self._entry("flimo_desc_match", _ptr(q), nq, q.shape[1], int(k), _ptr(out["idx"]), _ptr(out["dist"]), _ptr(out["cnt"]))
         return out
 
+    def scan_context(self, cfg=None, frame12=None, **kw):
+        """flimo_scan_context: the Scan Context descriptor of the resident scan -- per (ring, sector) bin of the sensor's polar
+        grid the largest height of a point in it.  ``cfg``: a ``ScCfg`` or None with the fields of ``sc_cfg`` as keywords;
+        ``frame12``: None or a row-major 3 x 4 transform applied to every point first (lidar to base, gravity alignment).  Returns
+        (desc [rings, sectors] float32, used: the points that have a bin).  A pending deskew runs first; changes nothing.  A
+        ``Localizer`` first waits for an insert, a crop or a carve still running behind the last sweep."""
+        k, f = _as_sc_cfg(cfg, kw), _frame12(frame12)
+        desc, used = np.zeros((max(k.rings, 0), max(k.sectors, 0)), np.float32), C.c_int32(0)
+        self._entry("flimo_scan_context", C.byref(k), _ptr(f), _ptr(desc), C.byref(used))
+        return desc, int(used.value)
+
+    def sc_db_add(self, desc):
+        """flimo_sc_db_add: append ``desc`` [n, rings, sectors] (or one [rings, sectors]) to the context's resident Scan Context
+        database; returns the id of the first (ids count up from 0 in the order added).  The database's shape is that of its first
+        entry after a clear; it is independent of the map and of the scan."""
+        d = sc_rows(desc)
+        first = C.c_size_t(0)
+        self._entry("flimo_sc_db_add", _ptr(d), d.shape[0], d.shape[1], d.shape[2], C.byref(first))
+        return int(first.value)
+
+    def sc_db_add_scan(self, cfg=None, frame12=None, **kw):
+        """flimo_sc_db_add_scan: append ``scan_context``'s descriptor of the resident scan without a round trip; returns its id."""
+        k, f, at = _as_sc_cfg(cfg, kw), _frame12(frame12), C.c_size_t(0)
+        self._entry("flimo_sc_db_add_scan", C.byref(k), _ptr(f), C.byref(at))
+        return int(at.value)
+
+    def sc_db_get(self, first=0, n=None):
+        """flimo_sc_db_get: the raw rows of the entries first .. first + n - 1 (``n`` None: to the end) as float32 [n, rings,
+        sectors]."""
+        hip = getattr(self, "hip", self)
+        first, size = int(first), hip.sc_db_size()
+        n = max(size - first, 0) if n is None else int(n)
+        rings, sectors = hip.sc_db_shape()
+        out = np.zeros((n, rings, sectors), np.float32)
+        self._entry("flimo_sc_db_get", first, n, _ptr(out))
+        return out
+
+    def sc_db_clear(self):
+        """flimo_sc_db_clear: forget every entry; the next add sets the shape."""
+        self._entry("flimo_sc_db_clear")
+
+    def sc_match(self, q, k=1, min_cols=1, max_dist=float("inf"), first=0, n=None, want_profile=False):
+        """flimo_sc_match: per descriptor of ``q`` [nq, rings, sectors] (or one [rings, sectors]) the first ``k`` entries with ids
+        in [first, first + n) (``n`` None: to the end) by (bits of the float32 distance, id), the distance the smallest over every
+        column shift of 1 - mean cosine of the columns valid in both (at least ``min_cols`` of them), below ``max_dist``.  Returns a
+        dict: idx [nq, k] int32 (-1 beyond cnt), dist [nq, k] float32, shift [nq, k] int32 (yaw_query = yaw_entry - shift * 2 pi /
+        sectors), cnt [nq][, profile [nq, k, sectors]: the distance at every shift, NaN where excluded].  Exact and reproducible.
+        A ``Localizer`` first waits for an insert, a crop or a carve still running behind the last sweep."""
+        q = sc_rows(q)
+        nq, kk = q.shape[0], max(int(k), 1)
+        cfg = ScMatchCfg(int(k), int(min_cols), float(max_dist))
+        out = {"idx": np.full((nq, kk), -1, np.int32), "dist": np.zeros((nq, kk), np.float32), "shift": np.full((nq, kk), -1, np.int32),
+               "cnt": np.zeros(nq, np.int32)}
+        if want_profile:
+            out["profile"] = np.full((nq, kk, q.shape[2]), np.nan, np.float32)
+        self._entry("flimo_sc_match", _ptr(q), nq, q.shape[1], q.shape[2], int(first), (1 << 62) if n is None else int(n), C.byref(cfg),
+                    *(_ptr(out.get(name)) for name in ("idx", "dist", "shift", "cnt", "profile")))
+        return out
+
 
 class HipCtx(_SharedEntries):
     """Thin OO wrapper over one ``flimo_ctx`` (one GPU, one map, one stream)."""
@@ -924,6 +1016,23 @@ class HipCtx(_SharedEntries):
     def desc_last_ms(self) -> float:
         """GPU ms of the last ``desc_match``'s launches (flimo_desc_last_ms; 0 unless ``set_timing`` is on)."""
         return float(self._L.flimo_desc_last_ms(self._h))
+
+    def sc_db_size(self) -> int:
+        return int(self._L.flimo_sc_db_size(self._h))
+
+    def sc_db_shape(self):
+        """(rings, sectors) of the resident Scan Context database, (0, 0) when it is empty (flimo_sc_db_shape)."""
+        r, s = C.c_int(0), C.c_int(0)
+        self._chk(self._L.flimo_sc_db_shape(self._h, C.byref(r), C.byref(s)))
+        return int(r.value), int(s.value)
+
+    def set_sc_chunk(self, queries_per_chunk=0, entries_per_split=0):
+        """Queries per chunk of ``sc_match`` and entries per split of its grid (flimo_set_sc_chunk; 0: the defaults)."""
+        self._chk(self._L.flimo_set_sc_chunk(self._h, int(queries_per_chunk), int(entries_per_split)))
+
+    def sc_last_ms(self) -> float:
+        """GPU ms of the last ``sc_match``'s launches (flimo_sc_last_ms; 0 unless ``set_timing`` is on)."""
+        return float(self._L.flimo_sc_last_ms(self._h))
 
     def scan_voxel_filter(self, leaf: float) -> int:
         n = C.c_size_t(0)

@@ -686,7 +686,83 @@ def relocalize(map_obj, scan_obj, fpfh=None, scan_fpfh=None, ratio=0.9, mutual=T
     return out
 
 
-ALIGN_RUNNING, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2      # scan_align's status per pose: ran every iteration / too few valid pairs / H not positive definite
+def sc_bin_host(p, cfg=None, frame12=None, **kw):
+    """The Scan Context bin of ONE point on the host (flimo_sc_bin_host: the function the descriptor kernel calls): ``cfg`` a
+    ``_lib.ScCfg`` or None with the fields of ``_lib.sc_cfg`` as keywords.  Returns (has, ring, sector, h); ring = sector = -1 and
+    h = 0 for a point without a bin.  Needs no device."""
+    L = _lib.load_hip()
+    k, f = _lib._as_sc_cfg(cfg, kw), _lib._frame12(frame12)
+    q = np.ascontiguousarray(p, dtype=np.float32).reshape(3)
+    ring, sector, h = C.c_int(-1), C.c_int(-1), C.c_float(0.0)
+    rc = L.flimo_sc_bin_host(q.ctypes.data, C.byref(k), None if f is None else f.ctypes.data, C.byref(ring), C.byref(sector), C.byref(h))
+    if rc < 0:
+        raise FlimoError(f"flimo_sc_bin_host failed ({rc})")
+    return rc == 1, int(ring.value), int(sector.value), np.float32(h.value)
+
+
+def sc_dist_host(a, b, min_cols=1, want_profile=False):
+    """The Scan Context distance of ONE pair of descriptors [rings, sectors] on the host (flimo_sc_dist_host: the functions the
+    kernels call).  Returns (have, dist float32, shift[, profile [sectors] float32: NaN for an excluded shift]); have is False, dist
+    0 and shift -1 when every shift is excluded.  Needs no device."""
+    L = _lib.load_hip()
+    x, y = (np.ascontiguousarray(v, dtype=np.float32) for v in (a, b))
+    if x.ndim != 2 or x.shape != y.shape:
+        raise ValueError("sc_dist_host: two descriptors [rings, sectors] of one shape")
+    dist, shift = C.c_float(0.0), C.c_int(-1)
+    prof = np.full(x.shape[1], np.nan, np.float32) if want_profile else None
+    rc = L.flimo_sc_dist_host(x.ctypes.data, y.ctypes.data, x.shape[0], x.shape[1], int(min_cols), C.byref(dist), C.byref(shift),
+                              None if prof is None else prof.ctypes.data)
+    if rc < 0:
+        raise FlimoError(f"flimo_sc_dist_host failed ({rc})")
+    out = (rc == 1, np.float32(dist.value), int(shift.value))
+    return out + (prof,) if want_profile else out
+
+
+def sc_guesses(x26_keyframes, idx, shift, sectors):
+    """Pose guesses from ``sc_match``'s answer: one x26 row per (idx, shift) pair -- the keyframe's row ``x26_keyframes[idx]`` with
+    its position, roll and pitch, and the yaw of the match: yaw_query = yaw_keyframe - shift * 2 pi / sectors, i.e. the keyframe's
+    rotation with Rz(-shift * 2 pi / sectors) in front of it (float64; q = x26[3:7] as x y z w).  The descriptor carries no
+    translation: the position is the keyframe's.  ``idx`` and ``shift`` of any one shape, every idx >= 0; returns [idx.size, 26]."""
+    kf = np.asarray(x26_keyframes, np.float64).reshape(-1, 26)
+    idx, shift = np.asarray(idx, np.int64).reshape(-1), np.asarray(shift, np.int64).reshape(-1)
+    if idx.shape != shift.shape or np.any(idx < 0) or np.any(idx >= kf.shape[0]):
+        raise ValueError("sc_guesses: idx and shift must pair up and name keyframes")
+    x = np.array(kf[idx])
+    half = -0.5 * shift.astype(np.float64) * (2.0 * math.pi / float(sectors))
+    sz, cw = np.sin(half), np.cos(half)
+    bx, by, bz, bw = x[:, 3], x[:, 4], x[:, 5], x[:, 6]
+    q = np.stack([cw * bx - sz * by, cw * by + sz * bx, cw * bz + sz * bw, cw * bw - sz * bz], axis=1)
+    x[:, 3:7] = q / np.linalg.norm(q, axis=1, keepdims=True)
+    return x
+
+
+def place_relocalize(obj, x26_keyframes, cfg, frame12=None, k=4, first=0, n=None, match=None, fitness_max_dist=1.0, align=None):
+    """A pose of the resident scan in the map by place recognition -- plumbing over five calls.  ``obj`` (a ``HipCtx`` or a
+    ``Localizer``) holds the map, the scan (body frame) as its resident scan, and a Scan Context database whose entry i was taken at
+    ``x26_keyframes[i]``.  ``scan_context(cfg, frame12)`` of the scan, ``sc_match`` of it against the entries [first, first + n) for
+    the best ``k`` (``match``: further keyword arguments of ``sc_match``), ``sc_guesses``, ``scan_fitness`` of the guesses ranked by
+    ``fitness_cost`` at ``fitness_max_dist``, ``scan_align`` (``align``: its keyword arguments) of the best.  Returns the dict of
+    each stage: desc, used, match, guesses (x26 rows in the match's order), fitness (inliers, sum_sqd, cost, x26, order: ranked),
+    align, and x26: the refined best row, None when nothing matched."""
+    hip = getattr(obj, "hip", obj)
+    desc, used = obj.scan_context(cfg, frame12)
+    m = obj.sc_match(desc, k=k, first=first, n=n, **dict(match or {}))
+    cnt = int(m["cnt"][0])
+    guesses = sc_guesses(x26_keyframes, m["idx"][0, :cnt], m["shift"][0, :cnt], desc.shape[1])
+    out = dict(desc=desc, used=used, match=m, guesses=guesses, fitness=None, align=None, x26=None)
+    if cnt == 0:
+        return out
+    inliers, sum_sqd = obj.scan_fitness(guesses, max_dist=fitness_max_dist)
+    cost = fitness_cost(inliers, sum_sqd, hip.scan_size(), fitness_max_dist)
+    order = np.lexsort((np.arange(cost.size), cost))
+    ranked = guesses[order]
+    aligned = scan_align(obj, ranked[:1], **dict(align or {}))
+    out.update(fitness=dict(inliers=inliers[order], sum_sqd=sum_sqd[order], cost=cost[order], x26=ranked, order=order), align=aligned,
+               x26=aligned["x26"][0])
+    return out
+
+
+ALIGN_RUNNING, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2     # scan_align's status per pose: ran every iteration / too few valid pairs / H not positive definite
 
 
 def sym6(H21):

@@ -253,6 +253,7 @@ extern "C" void flimo_ctx_destroy(flimo_ctx* c) {
   c->gbook.release();
   (void)hipFree(c->d_batch);
   (void)hipFree(c->d_desc_rt); (void)hipFree(c->d_desc_norm);
+  (void)hipFree(c->d_sc_raw); (void)hipFree(c->d_sc_un); (void)hipFree(c->d_sc_valid);
   for (flimo_ctx::NdtModel& m : c->ndt) m.release();
   c->gicp.release();
   (void)hipFree(c->d_scan_cov);

@@ -1,7 +1,7 @@
 // fast_limo_amd/csrc/hip/flimo_capi_query.hip -- C ABI (include/flimo_c.h) over the gfx950 kernels: the analysis entries.
 //
 // The call-at-a-time entries over the stored map (k-NN, radius search, normals, outliers, FPFH, keypoints, clusters, planes, voxels,
-// regions) and over the resident scan, correspondences and descriptors (scan fitness / linearize / NDT / GICP, flimo_corr_*, flimo_desc_*).  Each
+// regions) and over the resident scan, correspondences and descriptors (scan fitness / linearize / NDT / GICP, flimo_corr_*, flimo_desc_*, Scan Context).  Each
 // is glue of one shape: check the arguments, take a DevScratch, launch in chunks, copy back, wait once.  The registration path --
 // context, map index, sweep front end, the passes and the chain -- is flimo_capi.hip, which also defines the three functions these
 // entries call into it (ensure_index, flush_deskew, map_remove_masked); struct flimo_ctx and the shared helpers are flimo_ctx.h.
@@ -17,6 +17,7 @@
 #include "flimo_voxel.h"
 #include "flimo_region.h"
 #include "flimo_desc.h"
+#include "flimo_sc.h"
 #include "flimo_ndt.h"
 #include "flimo_gicp.h"
 #include "flimo_sums.h"
@@ -1488,6 +1489,259 @@ extern "C" int flimo_set_desc_chunk(flimo_ctx* c, size_t queries_per_chunk, size
   return FLIMO_OK;
 }
 extern "C" float flimo_desc_last_ms(const flimo_ctx* c) { return c ? c->desc_last_ms : 0.f; }
+
+// ---- Scan Context: the descriptor of the resident scan, the resident database of descriptors and the match over every shift -------
+// kernels: flimo_sc.hip; the definition: flimo_sc.h.  flimo_scan_context is a zeroing and one launch over the scan.  The database
+// is three arrays that grow geometrically by device-to-device copy (raw rows, normalised rows, valid-column bits); an add uploads
+// (or, flimo_sc_db_add_scan, forms in place) the raw rows and one launch normalises them.  flimo_sc_match runs the queries in chunks
+// of c->sc_chunk: per chunk the rows go up, the launches (the queries' normalised form, the match over (query tiles) x (splits of
+// the range), the merge of the splits, the profiles of the returned pairs), the results come back.  Reads neither the map nor --
+// the two scan entries apart -- the scan.
+static int sc_check_shape(flimo_ctx* c, const char* what, int rings, int sectors) {
+  if (rings < 1 || rings > FLIMO_SC_MAX_RINGS) return fail(c, FLIMO_ERR_INVALID, "%s: rings must be in 1..%d", what, FLIMO_SC_MAX_RINGS);
+  if (sectors < 2 || sectors > FLIMO_SC_MAX_SECTORS) return fail(c, FLIMO_ERR_INVALID, "%s: sectors must be in 2..%d", what, FLIMO_SC_MAX_SECTORS);
+  return FLIMO_OK;
+}
+static int sc_check_cfg(flimo_ctx* c, const char* what, const flimo_sc_cfg* cfg, const float* frame12, ScBinCfg* K) {
+  if (!cfg) return fail(c, FLIMO_ERR_INVALID, "%s: null cfg", what);
+  { const int rc = sc_check_shape(c, what, cfg->rings, cfg->sectors); if (rc) return rc; }
+  if (!(cfg->min_range >= 0.f) || !std::isfinite(cfg->max_range) || !(cfg->max_range > cfg->min_range))
+    return fail(c, FLIMO_ERR_INVALID, "%s: 0 <= min_range < max_range, max_range finite, must hold", what);
+  if (!std::isfinite(cfg->z_offset)) return fail(c, FLIMO_ERR_INVALID, "%s: non-finite z_offset", what);
+  K->rings = cfg->rings; K->sectors = cfg->sectors;
+  K->min_range = cfg->min_range; K->max_range = cfg->max_range; K->z_offset = cfg->z_offset;
+  sc_scales(*K);
+  K->has_frame = frame12 ? 1 : 0;
+  for (int a = 0; a < 12; a++) {
+    if (frame12 && !std::isfinite(frame12[a])) return fail(c, FLIMO_ERR_INVALID, "%s: non-finite frame12 entry", what);
+    K->frame[a] = frame12 ? frame12[a] : 0.f;
+  }
+  return FLIMO_OK;
+}
+extern "C" int flimo_sc_bin_host(const float p[3], const flimo_sc_cfg* cfg, const float frame12[12], int* ring, int* sector, float* h) {
+  if (!p || !ring || !sector || !h) return FLIMO_ERR_INVALID;
+  ScBinCfg K;
+  { const int rc = sc_check_cfg(nullptr, "sc bin", cfg, frame12, &K); if (rc) return rc; }
+  return sc_bin(K, p[0], p[1], p[2], ring, sector, h) ? 1 : 0;
+}
+extern "C" int flimo_scan_context(flimo_ctx* c, const flimo_sc_cfg* cfg, const float frame12[12], float* desc, int32_t* used) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (!desc) return fail(c, FLIMO_ERR_INVALID, "scan context: null desc");
+  ScBinCfg K;
+  { const int rc = sc_check_cfg(c, "scan context", cfg, frame12, &K); if (rc) return rc; }
+  if (c->scan_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "scan context: the scan must hold fewer than 2^31 points");
+  const size_t nb = (size_t)K.rings * K.sectors;
+  if (c->scan_n == 0) {
+    memset(desc, 0, nb * sizeof(float));
+    if (used) *used = 0;
+    return FLIMO_OK;
+  }
+  { const int rc = enter_flushed(c); if (rc) return rc; }
+  DevScratch d;
+  float* d_desc = d.get<float>(nb);
+  int* d_used = d.get<int>(1);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  float h_desc[FLIMO_SC_MAX_RINGS * FLIMO_SC_MAX_SECTORS];
+  int h_used = 0;
+  HIPCHK(c, launch_sc_descriptor(c->stream, c->d_scan, (unsigned)c->scan_n, K, d_desc, d_used));
+  HIPCHK(c, hipMemcpyAsync(h_desc, d_desc, nb * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&h_used, d_used, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(desc, h_desc, nb * sizeof(float));
+  if (used) *used = h_used;
+  return FLIMO_OK;
+}
+static void sc_db_free(flimo_ctx* c) {
+  (void)hipFree(c->d_sc_raw); (void)hipFree(c->d_sc_un); (void)hipFree(c->d_sc_valid);
+  c->d_sc_raw = c->d_sc_un = nullptr;
+  c->d_sc_valid = nullptr;
+  c->sc_n = c->sc_cap = 0;
+  c->sc_rings = c->sc_sectors = 0;
+}
+// room for `more` entries of this shape behind the sc_n there are: the shape must be the database's, the three arrays grow to at
+// least twice their capacity, the entries move by device-to-device copy.  Nothing changes when it fails.
+static int sc_db_reserve(flimo_ctx* c, const char* what, size_t more, int rings, int sectors) {
+  if (c->sc_n > 0 && (rings != c->sc_rings || sectors != c->sc_sectors))
+    return fail(c, FLIMO_ERR_INVALID, "%s: a %d x %d descriptor for a database of %d x %d", what, rings, sectors, c->sc_rings, c->sc_sectors);
+  if (c->sc_n + more >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "%s: the database must hold fewer than 2^31 entries", what);
+  if (c->sc_n == 0 && c->sc_cap > 0 && (rings != c->sc_rings || sectors != c->sc_sectors)) sc_db_free(c);      // (an empty one of another shape)
+  const size_t need = c->sc_n + more;
+  if (need > c->sc_cap) {
+    const size_t ncap = std::max<size_t>(std::max(need, 2 * c->sc_cap), 64);
+    const size_t nb = (size_t)rings * sectors, nu = (size_t)rings * 64;
+    struct New { float *raw = nullptr, *un = nullptr; unsigned long long* valid = nullptr;
+                 ~New() { (void)hipFree(raw); (void)hipFree(un); (void)hipFree(valid); } } nw;
+    HIPCHK(c, hipMalloc(&nw.raw, ncap * nb * sizeof(float)));
+    HIPCHK(c, hipMalloc(&nw.un, ncap * nu * sizeof(float)));
+    HIPCHK(c, hipMalloc(&nw.valid, ncap * sizeof(unsigned long long)));
+    if (c->sc_n) {
+      HIPCHK(c, hipMemcpyAsync(nw.raw, c->d_sc_raw, c->sc_n * nb * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(nw.un, c->d_sc_un, c->sc_n * nu * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(nw.valid, c->d_sc_valid, c->sc_n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::swap(nw.raw, c->d_sc_raw); std::swap(nw.un, c->d_sc_un); std::swap(nw.valid, c->d_sc_valid);
+    c->sc_cap = ncap;
+  }
+  c->sc_rings = rings; c->sc_sectors = sectors;
+  return FLIMO_OK;
+}
+// the normalised form of the `more` raw rows behind the sc_n entries; they then count
+static int sc_db_commit(flimo_ctx* c, size_t more) {
+  const size_t nb = (size_t)c->sc_rings * c->sc_sectors, nu = (size_t)c->sc_rings * 64;
+  HIPCHK(c, launch_sc_norms(c->stream, c->d_sc_raw + c->sc_n * nb, (unsigned)more, c->sc_rings, c->sc_sectors, c->d_sc_un + c->sc_n * nu,
+                            c->d_sc_valid + c->sc_n));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->sc_n += more;
+  return FLIMO_OK;
+}
+extern "C" int flimo_sc_db_add(flimo_ctx* c, const float* desc, size_t n, int rings, int sectors, size_t* first_id) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (n > 0 && !desc) return fail(c, FLIMO_ERR_INVALID, "sc db add: null desc");
+  { const int rc = sc_check_shape(c, "sc db add", rings, sectors); if (rc) return rc; }
+  if (n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "sc db add: the database must hold fewer than 2^31 entries");
+  if (n == 0) {
+    if (c->sc_n > 0 && (rings != c->sc_rings || sectors != c->sc_sectors)) return fail(c, FLIMO_ERR_INVALID, "sc db add: not the database's shape");
+    if (first_id) *first_id = c->sc_n;
+    return FLIMO_OK;
+  }
+  ctx_enter(c);
+  { const int rc = sc_db_reserve(c, "sc db add", n, rings, sectors); if (rc) return rc; }
+  const size_t nb = (size_t)rings * sectors, id = c->sc_n;
+  HIPCHK(c, hipMemcpyAsync(c->d_sc_raw + id * nb, desc, n * nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  { const int rc = sc_db_commit(c, n); if (rc) return rc; }
+  if (first_id) *first_id = id;
+  return FLIMO_OK;
+}
+extern "C" int flimo_sc_db_add_scan(flimo_ctx* c, const flimo_sc_cfg* cfg, const float frame12[12], size_t* id) {
+  if (!c) return FLIMO_ERR_INVALID;
+  ScBinCfg K;
+  { const int rc = sc_check_cfg(c, "sc db add scan", cfg, frame12, &K); if (rc) return rc; }
+  if (c->scan_n >= 0x80000000ull) return fail(c, FLIMO_ERR_TOO_LARGE, "sc db add scan: the scan must hold fewer than 2^31 points");
+  { const int rc = enter_flushed(c); if (rc) return rc; }
+  { const int rc = sc_db_reserve(c, "sc db add scan", 1, K.rings, K.sectors); if (rc) return rc; }
+  DevScratch d;
+  int* d_used = d.get<int>(1);
+  { const int rc = d.ok(c); if (rc) return rc; }
+  const size_t at = c->sc_n;
+  HIPCHK(c, launch_sc_descriptor(c->stream, c->d_scan, (unsigned)c->scan_n, K, c->d_sc_raw + at * K.rings * K.sectors, d_used));
+  { const int rc = sc_db_commit(c, 1); if (rc) return rc; }
+  if (id) *id = at;
+  return FLIMO_OK;
+}
+extern "C" size_t flimo_sc_db_size(const flimo_ctx* c) { return c ? c->sc_n : 0; }
+extern "C" int flimo_sc_db_shape(const flimo_ctx* c, int* rings, int* sectors) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (rings) *rings = c->sc_n ? c->sc_rings : 0;
+  if (sectors) *sectors = c->sc_n ? c->sc_sectors : 0;
+  return FLIMO_OK;
+}
+extern "C" int flimo_sc_db_get(flimo_ctx* c, size_t first, size_t n, float* desc) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (first > c->sc_n || n > c->sc_n - first) return fail(c, FLIMO_ERR_INVALID, "sc db get: [%zu, %zu + %zu) ends beyond the %zu entries", first, first, n, c->sc_n);
+  if (n == 0) return FLIMO_OK;
+  if (!desc) return fail(c, FLIMO_ERR_INVALID, "sc db get: null desc");
+  ctx_enter(c);
+  const size_t nb = (size_t)c->sc_rings * c->sc_sectors;
+  HIPCHK(c, hipMemcpyAsync(desc, c->d_sc_raw + first * nb, n * nb * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return FLIMO_OK;
+}
+extern "C" int flimo_sc_db_clear(flimo_ctx* c) {
+  if (!c) return FLIMO_ERR_INVALID;
+  ctx_enter(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  sc_db_free(c);
+  return FLIMO_OK;
+}
+extern "C" int flimo_sc_match(flimo_ctx* c, const float* q, size_t nq, int rings, int sectors, size_t first, size_t n, const flimo_sc_match_cfg* cfg,
+                              int32_t* idx, float* dist, int32_t* shift, int32_t* cnt, float* profile) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if ((nq > 0 && !q) || !cfg || !idx || !dist || !shift || !cnt) return fail(c, FLIMO_ERR_INVALID, "sc match: null q / cfg / idx / dist / shift / cnt");
+  { const int rc = sc_check_shape(c, "sc match", rings, sectors); if (rc) return rc; }
+  if (cfg->k < 1 || cfg->k > FLIMO_SC_MAX_K) return fail(c, FLIMO_ERR_INVALID, "sc match: k must be in 1..%d", FLIMO_SC_MAX_K);
+  if (cfg->min_cols < 1 || cfg->min_cols > sectors) return fail(c, FLIMO_ERR_INVALID, "sc match: min_cols must be in 1..sectors");
+  if (!(cfg->max_dist > 0.f)) return fail(c, FLIMO_ERR_INVALID, "sc match: max_dist must be > 0 or INFINITY");
+  const int k = cfg->k;
+  if (nq >= 0x80000000ull || (unsigned long long)nq * (unsigned long long)k >= 0x80000000ull)
+    return fail(c, FLIMO_ERR_TOO_LARGE, "sc match: nq * k must be below 2^31");
+  if (c->sc_n > 0 && (rings != c->sc_rings || sectors != c->sc_sectors))
+    return fail(c, FLIMO_ERR_INVALID, "sc match: %d x %d queries for a database of %d x %d", rings, sectors, c->sc_rings, c->sc_sectors);
+  if (nq == 0) return FLIMO_OK;
+  c->sc_last_ms = 0.f;
+  if (first >= c->sc_n || n == 0) {      // nobody to be near
+    for (size_t i = 0; i < nq; i++) cnt[i] = 0;
+    for (size_t i = 0; i < nq * (size_t)k; i++) { idx[i] = -1; dist[i] = 0.f; shift[i] = -1; }
+    if (profile) for (size_t i = 0; i < nq * (size_t)k * sectors; i++) profile[i] = std::numeric_limits<float>::quiet_NaN();
+    return FLIMO_OK;
+  }
+  n = std::min(n, c->sc_n - first);
+  ctx_enter(c);
+  const size_t m = std::min(nq, std::max<size_t>(c->sc_chunk, 1));      // queries of a chunk
+  // entries per split: the caller's, or as many splits as bring the grid to about four workgroups a compute unit, none below eight
+  // entries (a workgroup's waves take two at a time); never more than 32768 splits
+  size_t eps;
+  if (c->sc_split) eps = std::min(c->sc_split, n);
+  else {
+    const size_t groups = (m + (size_t)sc_query_tile() - 1) / (size_t)sc_query_tile();
+    const size_t want = std::max<size_t>(1024 / groups, 1);
+    eps = std::max<size_t>((n + want - 1) / want, 8);
+  }
+  eps = std::max(eps, (n + 32767) / 32768);
+  const size_t nsplit = (n + eps - 1) / eps;
+  const size_t nb = (size_t)rings * sectors, nu = (size_t)rings * 64, kl = (size_t)sc_list_len();
+  DevScratch d;
+  float* d_q = d.get<float>(m * nb);
+  float* d_qun = d.get<float>(m * nu);
+  unsigned long long* d_qvalid = d.get<unsigned long long>(m);
+  unsigned long long* d_part = d.get<unsigned long long>(nsplit * m * kl);
+  int* d_part_shift = d.get<int>(nsplit * m * kl);
+  int32_t* d_idx = d.get<int32_t>(m * (size_t)k);
+  float* d_dist = d.get<float>(m * (size_t)k);
+  int32_t* d_shift = d.get<int32_t>(m * (size_t)k);
+  int32_t* d_cnt = d.get<int32_t>(m);
+  float* d_profile = profile ? d.get<float>(m * (size_t)k * sectors) : nullptr;
+  { const int rc = d.ok(c); if (rc) return rc; }
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (c->timing) { HIPCHK(c, hipEventCreate(&ev[0])); HIPCHK(c, hipEventCreate(&ev[1])); }
+  for (size_t a = 0; a < nq; a += m) {
+    const size_t na = std::min(m, nq - a), nk = na * (size_t)k;
+    HIPCHK(c, hipMemcpyAsync(d_q, q + a * nb, na * nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (ev[0]) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    HIPCHK(c, launch_sc_norms(c->stream, d_q, (unsigned)na, rings, sectors, d_qun, d_qvalid));
+    HIPCHK(c, launch_sc_match(c->stream, c->d_sc_un, c->d_sc_valid, (unsigned)first, (unsigned)(first + n), (unsigned)eps, d_qun, d_qvalid,
+                              (unsigned)na, rings, sectors, k, cfg->min_cols, cfg->max_dist, d_part, d_part_shift, d_idx, d_dist, d_shift, d_cnt,
+                              d_profile));
+    if (ev[1]) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    HIPCHK(c, hipMemcpyAsync(idx + a * (size_t)k, d_idx, nk * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dist + a * (size_t)k, d_dist, nk * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(shift + a * (size_t)k, d_shift, nk * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt + a, d_cnt, na * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (profile) HIPCHK(c, hipMemcpyAsync(profile + a * (size_t)k * sectors, d_profile, nk * sectors * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the next chunk overwrites the chunk's buffers)
+    if (ev[0]) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->sc_last_ms += ms; }
+  }
+  if (ev[0]) { (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); }
+  return FLIMO_OK;
+}
+extern "C" int flimo_sc_dist_host(const float* a, const float* b, int rings, int sectors, int min_cols, float* dist, int* shift, float* profile) {
+  if (!a || !b || !dist || !shift) return FLIMO_ERR_INVALID;
+  if (rings < 1 || rings > FLIMO_SC_MAX_RINGS || sectors < 2 || sectors > FLIMO_SC_MAX_SECTORS || min_cols < 1 || min_cols > sectors)
+    return FLIMO_ERR_INVALID;
+  float d = 0.f;
+  int s = -1;
+  const bool have = sc_dist(a, b, rings, sectors, min_cols, &d, &s, profile);
+  *dist = d;
+  *shift = s;
+  return have ? 1 : 0;
+}
+extern "C" int flimo_set_sc_chunk(flimo_ctx* c, size_t queries_per_chunk, size_t entries_per_split) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->sc_chunk = queries_per_chunk ? queries_per_chunk : (size_t)1 << 12;
+  c->sc_split = entries_per_split;
+  return FLIMO_OK;
+}
+extern "C" float flimo_sc_last_ms(const flimo_ctx* c) { return c ? c->sc_last_ms : 0.f; }
 
 // ---- point-to-plane normal equations of the resident scan under pose hypotheses: one linearisation of a registration ----------
 // kernels: flimo_knn_k.hip.  Chunks of whole poses as flimo_scan_fitness, c->linearize_chunk pairs at most unless one pose alone

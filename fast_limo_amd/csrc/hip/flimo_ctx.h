@@ -67,6 +67,16 @@ struct flimo_ctx {
   size_t desc_chunk = (size_t)1 << 16;      // queries per chunk of flimo_desc_match (flimo_set_desc_chunk)
   size_t desc_split = 0;                    // reference rows per split of its grid; 0: chosen per chunk, to fill the device
   float desc_last_ms = 0.f;                 // GPU time of the last call's launches (timing level >= 1)
+  // the resident Scan Context database (flimo_sc_db_add): the raw rows, their normalised form (flimo_sc.h) and the bits of the
+  // valid columns; independent of the map and of the scan
+  float* d_sc_raw = nullptr;                // [sc_cap][sc_rings][sc_sectors]
+  float* d_sc_un = nullptr;                 // [sc_cap][sc_rings][64]
+  unsigned long long* d_sc_valid = nullptr; // [sc_cap]
+  size_t sc_n = 0, sc_cap = 0;
+  int sc_rings = 0, sc_sectors = 0;
+  size_t sc_chunk = (size_t)1 << 12;        // queries per chunk of flimo_sc_match (flimo_set_sc_chunk)
+  size_t sc_split = 0;                      // entries per split of its grid; 0: chosen per chunk, to fill the device
+  float sc_last_ms = 0.f;                   // GPU time of the last call's launches (timing level >= 1)
   // the resident NDT cell models (flimo_ndt_build): each a SNAPSHOT of the map's voxels at its build -- inserts, removals and
   // flimo_map_clear leave it alone and only move map_epoch on, which is how flimo_ndt_info knows a model stale
   struct NdtModel {

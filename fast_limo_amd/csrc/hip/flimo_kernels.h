@@ -462,6 +462,24 @@ hipError_t launch_desc_pack(hipStream_t st, const float* x, unsigned n, int dim,
 hipError_t launch_desc_match(hipStream_t st, const float* rt, const float* rnorm, unsigned nr, unsigned tiles_per_split, const float* q,
                              float* qnorm, unsigned nq, int dim, int k, unsigned long long* part, int32_t* idx, float* dist, int32_t* cnt);
 
+// flimo_sc.hip -- Scan Context (flimo_scan_context, flimo_sc_db_*, flimo_sc_match; flimo_c.h, flimo_sc.h).
+//  launch_sc_descriptor  desc [rings][sectors] and *used (both device) of the scan's n points: the zeroing and one launch.
+//  launch_sc_norms       the normalised form of n descriptors raw [n][rings][sectors]: un [n][rings][64], valid [n] (the bits of
+//                        the valid columns; 0 for an excluded descriptor).
+//  launch_sc_match       a chunk of nq queries in that form against the entries [e_first, e_end) of the database, in splits of
+//                        per_split entries (splits <= 65535): part / part_shift [splits][nq][sc_list_len()] scratch, then idx /
+//                        dist / shift [nq][k], cnt [nq] and, unless null, profile [nq][k][sectors].  A workgroup takes
+//                        sc_query_tile() queries.
+struct ScBinCfg;
+int sc_query_tile();
+int sc_list_len();
+hipError_t launch_sc_descriptor(hipStream_t st, const float4* scan, unsigned n, const ScBinCfg& K, float* desc, int* used);
+hipError_t launch_sc_norms(hipStream_t st, const float* raw, unsigned n, int rings, int sectors, float* un, unsigned long long* valid);
+hipError_t launch_sc_match(hipStream_t st, const float* un, const unsigned long long* valid, unsigned e_first, unsigned e_end, unsigned per_split,
+                           const float* qun, const unsigned long long* qvalid, unsigned nq, int rings, int sectors, int k, int min_cols,
+                           float max_dist, unsigned long long* part, int* part_shift, int32_t* idx, float* dist, int32_t* shift, int32_t* cnt,
+                           float* profile);
+
 // flimo_ndt.hip -- the NDT cell model and the per-pose sums against it (flimo_ndt_build, flimo_scan_ndt; flimo_c.h).
 //  launch_ndt_cells   behind launch_voxel_moments: eig [nv][12] (l0 l1 l2, v0, v1, v2 of every voxel of at least min_pts points),
 //                     flag [nv + 1] (1: a cell; flag[nv] = 0) and its exclusive scan pos [nv + 1]: pos[nv] is the number of cells.

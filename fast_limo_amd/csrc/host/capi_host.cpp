@@ -401,6 +401,31 @@ int flimo_loc_scan_gicp(flimo_loc* L, const double* x26, size_t np, float max_di
   if (!L) return FLIMO_ERR_INVALID;
   return flimo_scan_gicp(ctx_of(L), x26, np, max_dist, valid, H, g, cost, pair_idx, pair_m);
 }
+int flimo_loc_scan_context(flimo_loc* L, const flimo_sc_cfg* cfg, const float* frame12, float* desc, int32_t* used) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_scan_context(ctx_of(L), cfg, frame12, desc, used);
+}
+int flimo_loc_sc_db_add(flimo_loc* L, const float* desc, size_t n, int rings, int sectors, size_t* first_id) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_sc_db_add(ctx_of(L), desc, n, rings, sectors, first_id);
+}
+int flimo_loc_sc_db_add_scan(flimo_loc* L, const flimo_sc_cfg* cfg, const float* frame12, size_t* id) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_sc_db_add_scan(ctx_of(L), cfg, frame12, id);
+}
+int flimo_loc_sc_db_get(flimo_loc* L, size_t first, size_t n, float* desc) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_sc_db_get(ctx_of(L), first, n, desc);
+}
+int flimo_loc_sc_db_clear(flimo_loc* L) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_sc_db_clear(ctx_of(L));
+}
+int flimo_loc_sc_match(flimo_loc* L, const float* q, size_t nq, int rings, int sectors, size_t first, size_t n, const flimo_sc_match_cfg* cfg,
+                       int32_t* idx, float* dist, int32_t* shift, int32_t* cnt, float* profile) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_sc_match(ctx_of(L), q, nq, rings, sectors, first, n, cfg, idx, dist, shift, cnt, profile);
+}
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
 // the map insert that ends a scan runs on the Mapper's worker thread (Mapper::add_scan): wait for it / switch it off

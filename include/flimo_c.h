@@ -1230,6 +1230,88 @@ int flimo_desc_ref_dim(const flimo_ctx* ctx);
 int flimo_desc_match(flimo_ctx* ctx, const float* q /* [nq][dim] */, size_t nq, int dim, int k, int32_t* idx /* [nq][k] */,
                      float* dist /* [nq][k] */, int32_t* cnt /* [nq] */);
 int flimo_desc_dist_host(const float* a, const float* b, int dim, float* d);
+/* ---- Scan Context place recognition (Kim & Kim, IROS 2018): which earlier sweep was taken where this sweep was taken, and how is
+ *      it turned relative to it -- a global descriptor per keyframe, a resident database of them, and the exact match of a batch of
+ *      queries against every entry at every column shift.  The definition is ONE host / device header (csrc/hip/flimo_sc.h);
+ *      tests/sc_common.py restates everything below in numpy; the tests compare every bit.  Everything is float32 with ONE rounding
+ *      per written operation, nothing contracted; fmaf is the correctly rounded fused multiply-add. ----
+ * 1. The descriptor of the resident scan: flimo_scan_context fills desc [rings][sectors] (host memory) and, unless NULL, *used.
+ *  Per point (sc_bin):
+ *  - Frame: with frame12 NULL, v is the point; otherwise v is the row-major 3 x 4 transform, c0*x + (c1*y + (c2*z + c3)) per row
+ *    (a lidar-to-base or gravity alignment).  A point with a non-finite component of v has no bin.
+ *  - Ring: r = sqrt(vx*vx + vy*vy), correctly rounded.  No bin unless r > 0, r >= min_range and r < max_range.
+ *    ring = min(rings - 1, (int)(r * rscale)), rscale = (float)((double)rings / (double)max_range).
+ *  - Sector: a = atan2f(vy, vx) as csrc/hip/flimo_math.h restates glibc's; if a < 0 then a = a + 0x1.921fb6p+2f.
+ *    sector = min(sectors - 1, (int)(a * sscale)), sscale = (float)((double)sectors / 6.283185307179586).
+ *  - Height: h = vz + z_offset.  No bin unless h > 0.
+ *  desc[ring][sector] is the maximum h over the points that have that bin, +0.0f where none has; used is how many points have a
+ *  bin.  h > 0, so the maximum is an integer maximum over the floats' bits: the scan's order and the launch shape move no bit.
+ *  A pending deskew runs first, as for flimo_map_seen_through.  An empty scan: FLIMO_OK, an all-zero descriptor, used = 0.
+ *  FLIMO_ERR_INVALID, outputs untouched: a NULL ctx, cfg or desc, a cfg value outside its range, a non-finite frame12 entry.  The
+ *  map, the scan and the bits of a later pass are not touched.  The descriptor assumes a roughly level sensor (frame12 is where a
+ *  gravity alignment goes) and carries no translation: two places that look alike from above are alike to it.
+ *  flimo_sc_bin_host: sc_bin for ONE point on the host; returns 1 when the point has a bin (ring, sector, h are then set), 0 when
+ *  it has none, FLIMO_ERR_INVALID as above.
+ * 2. The resident database: entries get ids 0, 1, 2, .. in the order added; its shape is that of the first entry after a clear,
+ *  any other shape is FLIMO_ERR_INVALID.  flimo_sc_db_add appends n descriptors from host memory (*first_id, unless NULL: the id of
+ *  the first); flimo_sc_db_add_scan appends flimo_scan_context's result without a round trip -- its entry is bit-equal to
+ *  flimo_sc_db_add of the downloaded descriptor.  At add time a launch forms each entry's normalised form (3.), kept on the device
+ *  beside the raw rows; flimo_sc_db_get returns the raw rows of the entries [first, first + n) (FLIMO_ERR_INVALID when the range
+ *  ends beyond the size).  flimo_sc_db_size / flimo_sc_db_shape: entries and shape (0 x 0: none).  flimo_sc_db_clear frees it.
+ *  The capacity grows geometrically by device-to-device copy.  The database is independent of the map and of the scan -- inserts,
+ *  crops and clears of the map leave it alone -- and is freed with the context.  FLIMO_ERR_TOO_LARGE at 2^31 entries; a failed
+ *  add leaves the database as it was.  Device memory: 4 B * rings * (sectors + 64) + 8 B an entry.
+ * 3. The match: flimo_sc_match answers, per query descriptor q[i], with the first k of the entries [first, first + n).
+ *  Columns: for column j of a descriptor D, n_j = sqrt(c_R) with c_0 = +0, c_{t+1} = fmaf(D[t][j], D[t][j], c_t), rings ascending.
+ *  The column is VALID iff n_j > 0; its normalised form is u[t][j] = D[t][j] / n_j (one correctly rounded division per entry),
+ *  +0 for an invalid column.  A descriptor with a non-finite entry is EXCLUDED: as a query it has cnt 0, as an entry it is never
+ *  returned.
+ *  Per shift s in 0 .. sectors - 1, query column (j + s) mod sectors meets candidate column j: term_j is the ascending fmaf chain
+ *  over the rings of uq[t][(j + s) % sectors] * uc[t][j] from +0 when both columns are valid, +0 otherwise; m(s) is the number of
+ *  valid pairs; sum(s) is the pairwise tree ((t0 + t1) + (t2 + t3)) + .. over 64 slots indexed by j (+0 at and beyond sectors);
+ *  d(s) = 1.0f - sum(s) / (float)m(s), a negative result +0.0f.  A shift with m(s) < min_cols is excluded (profile: NaN).
+ *  The pair's distance is the first d(s) in the order (bits of d, s), shift is that s; a pair with every shift excluded is not
+ *  returned.  Per query the answer is the first k candidates in the order (bits of dist, id) among those with dist < max_dist
+ *  (strict); cnt is how many; the slots beyond cnt hold idx = -1, dist = 0, shift = -1 and a NaN profile.  The order is total: it
+ *  does not depend on tiling, splits, chunks or the other queries.
+ *  The meaning of the shift: the sector index grows with the angle in the sensor frame, so
+ *  psi_query = psi_candidate - shift * 2 pi / sectors.  The descriptor carries no translation.
+ *  Outputs, host memory: idx / dist / shift [nq][k], cnt [nq], profile [nq][k][sectors] (may be NULL: d(s) of each returned pair).
+ *  FLIMO_OK with every cnt 0: no database, n == 0, a range wholly beyond the size (a range reaching past the size is cut to it).
+ *  FLIMO_OK with nothing touched: nq == 0.  FLIMO_ERR_INVALID: a NULL pointer, a shape outside its range or other than the
+ *  database's, a cfg value outside its range.  FLIMO_ERR_TOO_LARGE: nq * k >= 2^31.  Outputs are untouched on an error.  Calling
+ *  rules as flimo_desc_match; neither the map nor the scan is read.  Brute force, exact: sectors^2 * rings multiply-adds a pair.
+ *  flimo_sc_dist_host: ONE pair on the host by the same functions; returns 1 and sets dist and shift (profile [sectors] unless
+ *  NULL), 0 when every shift is excluded (dist 0, shift -1), FLIMO_ERR_INVALID for a NULL pointer or a value out of range. */
+#define FLIMO_SC_MAX_RINGS 32
+#define FLIMO_SC_MAX_SECTORS 64
+#define FLIMO_SC_MAX_K 8
+typedef struct flimo_sc_cfg {
+  int rings;        /* 1..32 */
+  int sectors;      /* 2..64 */
+  float min_range;  /* >= 0 */
+  float max_range;  /* finite, > min_range */
+  float z_offset;   /* finite; sensor height */
+} flimo_sc_cfg;
+typedef struct flimo_sc_match_cfg {
+  int k;           /* 1..8 */
+  int min_cols;    /* 1..sectors */
+  float max_dist;  /* > 0 or INFINITY */
+} flimo_sc_match_cfg;
+int flimo_scan_context(flimo_ctx* ctx, const flimo_sc_cfg* cfg, const float frame12[12] /* may be NULL */,
+                       float* desc /* [rings][sectors] */, int32_t* used /* may be NULL */);
+int flimo_sc_bin_host(const float p[3], const flimo_sc_cfg* cfg, const float frame12[12], int* ring, int* sector, float* h);
+int flimo_sc_db_add(flimo_ctx* ctx, const float* desc /* [n][rings][sectors] */, size_t n, int rings, int sectors, size_t* first_id);
+int flimo_sc_db_add_scan(flimo_ctx* ctx, const flimo_sc_cfg* cfg, const float frame12[12], size_t* id);
+size_t flimo_sc_db_size(const flimo_ctx* ctx);
+int flimo_sc_db_shape(const flimo_ctx* ctx, int* rings, int* sectors);
+int flimo_sc_db_get(flimo_ctx* ctx, size_t first, size_t n, float* desc);
+int flimo_sc_db_clear(flimo_ctx* ctx);
+int flimo_sc_match(flimo_ctx* ctx, const float* q /* [nq][rings][sectors] */, size_t nq, int rings, int sectors, size_t first, size_t n,
+                   const flimo_sc_match_cfg* cfg, int32_t* idx /* [nq][k] */, float* dist /* [nq][k] */, int32_t* shift /* [nq][k] */,
+                   int32_t* cnt /* [nq] */, float* profile /* [nq][k][sectors], may be NULL */);
+int flimo_sc_dist_host(const float* a, const float* b, int rings, int sectors, int min_cols, float* dist, int* shift,
+                       float* profile /* [sectors], may be NULL */);
 /* Both clouds the caller of Localizer::updatePointCloud may ask for (pc2match: body frame; final_scan: world frame of pose x26,
  * Localizer.cpp:361-371) in ONE round trip: packed float4 records (x, y, z, unused) in pinned memory owned by the context, valid
  * until the next flimo_scan_clouds on it.  *n = points in each. */

@@ -112,6 +112,12 @@ int flimo_set_corr_chunk(flimo_ctx* ctx, size_t n);
 int flimo_set_desc_chunk(flimo_ctx* ctx, size_t queries_per_chunk, size_t refs_per_split);
 /* GPU milliseconds of the launches of the last flimo_desc_match on the context, all chunks together (0 unless flimo_set_timing is on) */
 float flimo_desc_last_ms(const flimo_ctx* ctx);
+/* flimo_sc_match works in chunks of queries_per_chunk queries (default 2^12; 0 restores it), and its grid splits the candidate
+ * range into runs of entries_per_split entries (0, the default: chosen per call so that the grid fills the device); the two bound
+ * the call's device scratch: per query of a chunk its rows, its results and 96 B a split.  Equal results whatever the two. */
+int flimo_set_sc_chunk(flimo_ctx* ctx, size_t queries_per_chunk, size_t entries_per_split);
+/* GPU milliseconds of the launches of the last flimo_sc_match on the context, all chunks together (0 unless flimo_set_timing is on) */
+float flimo_sc_last_ms(const flimo_ctx* ctx);
 /* flimo_scan_fitness works in chunks of whole poses, at most `pairs` (pose, point) pairs each (default 2^22; 0 restores it); a
  * single pose with more points than that runs alone.  The chunk bounds the call's device scratch.  The results do not depend on it
  * (tests, A/B). */

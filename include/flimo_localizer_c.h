@@ -224,6 +224,19 @@ int    flimo_loc_gicp_clear(flimo_loc* L);
 int    flimo_loc_scan_cov_set(flimo_loc* L, const double* cov6, size_t n);
 int    flimo_loc_scan_gicp(flimo_loc* L, const double* x26, size_t np, float max_dist, int32_t* valid, double* H, double* g, double* cost,
                            int32_t* pair_idx, double* pair_m);
+/* Scan Context on the Localizer's map context (the reference's loop/scancontext branch has it beside the Localizer, not in it):
+ * flimo_scan_context / flimo_sc_db_add / flimo_sc_db_add_scan / flimo_sc_db_get / flimo_sc_db_clear / flimo_sc_match
+ * (include/flimo_c.h: same arguments, same results, same error codes), after an insert, a crop or a carve still running behind
+ * the last sweep has ended.  The resident scan is the last sweep's; the database stays on the map's context
+ * (flimo_sc_db_size(flimo_loc_ctx(L)) tells its size) and no insert, crop or clear of the map touches it.  The Localizer's own
+ * update does not use it. */
+int    flimo_loc_scan_context(flimo_loc* L, const flimo_sc_cfg* cfg, const float* frame12, float* desc, int32_t* used);
+int    flimo_loc_sc_db_add(flimo_loc* L, const float* desc, size_t n, int rings, int sectors, size_t* first_id);
+int    flimo_loc_sc_db_add_scan(flimo_loc* L, const flimo_sc_cfg* cfg, const float* frame12, size_t* id);
+int    flimo_loc_sc_db_get(flimo_loc* L, size_t first, size_t n, float* desc);
+int    flimo_loc_sc_db_clear(flimo_loc* L);
+int    flimo_loc_sc_match(flimo_loc* L, const float* q, size_t nq, int rings, int sectors, size_t first, size_t n,
+                          const flimo_sc_match_cfg* cfg, int32_t* idx, float* dist, int32_t* shift, int32_t* cnt, float* profile);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
