@@ -4,7 +4,8 @@ symbols the tests compare with the headers are read off them.
 
 A new entry that both a ``flimo_ctx`` and a ``flimo_loc`` offer is one row of ``PAIRED`` -- the two symbols and the arguments after
 the handle -- and one method of ``_lib._SharedEntries``; ``HipCtx`` and ``Localizer`` then both have it.  ``PAIRED_NDT`` and
-``PAIRED_GICP`` hold the rows of the NDT and the GICP entries in the same form, ``PAIRED_SC`` those of Scan Context."""
+``PAIRED_GICP`` hold the rows of the NDT and the GICP entries in the same form, ``PAIRED_SC`` those of Scan Context,
+``PAIRED_SEG`` those of the map segments."""
 from __future__ import annotations
 
 import ctypes as C
@@ -261,7 +262,17 @@ PAIRED_SC = (
     ("flimo_sc_db_clear", "flimo_loc_sc_db_clear", []),
     ("flimo_sc_match", "flimo_loc_sc_match", [vp, sz, i, i, sz, sz, P(ScMatchCfg), vp, vp, vp, vp, vp]),
 )
-PAIRED_ALL = PAIRED + PAIRED_NDT + PAIRED_GICP + PAIRED_SC
+# Map segments: the table, the move of the map by segment, forgetting by age.
+PAIRED_SEG = (
+    ("flimo_map_segment_mark", "flimo_loc_map_segment_mark", [P(sz)]),
+    ("flimo_map_segments", "flimo_loc_map_segments", [vp, sz, P(sz), P(i)]),
+    ("flimo_map_segments_reset", "flimo_loc_map_segments_reset", []),
+    ("flimo_map_corrected", "flimo_loc_map_corrected", [vp, sz, sz, sz, vp, P(sz)]),
+    ("flimo_map_correct", "flimo_loc_map_correct", [vp, sz, P(sz)]),
+    ("flimo_map_transform", "flimo_loc_map_transform", [vp, P(sz)]),
+    ("flimo_map_remove_range", "flimo_loc_map_remove_range", [sz, sz, P(sz)]),
+)
+PAIRED_ALL = PAIRED + PAIRED_NDT + PAIRED_GICP + PAIRED_SC + PAIRED_SEG
 LOC_OF = {hip: loc for hip, loc, _ in PAIRED_ALL}
 
 # Everything else: (result, symbol, every argument -- the handle, where there is one, included).
@@ -306,6 +317,7 @@ HIP_ONLY = (
     (sz, "flimo_sc_db_size", [vp]),
     (i, "flimo_sc_db_shape", [vp, P(i), P(i)]),
     (f, "flimo_sc_last_ms", [vp]),
+    (i, "flimo_set_segment_plan", [vp, sz, i]),
     # the functions the kernels call, on the host
     (i, "flimo_plane_solve_host", [vp, P(PlaneCfg), vp, vp]),
     (i, "flimo_voxel_key_host", [vp, f, vp, P(u64)]),
@@ -319,6 +331,7 @@ HIP_ONLY = (
     (i, "flimo_gicp_eigen_host", [vp, vp]),
     (i, "flimo_gicp_regularize_host", [vp, i, d, vp]),
     (i, "flimo_gicp_term_host", [vp, vp, vp, vp, vp, vp, vp]),
+    (i, "flimo_seg_move_host", [vp, vp, vp]),
     (None, "flimo_plane_fit5_host", [f32p, f32p]),
     (i, "flimo_plane_eval5_host", [f32p, f32p, f]),
     (i, "flimo_calculate_H_host", [f64p, f32p, f32p, f32p, sz, i, f64p, f64p]),

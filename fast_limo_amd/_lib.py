@@ -260,6 +260,16 @@ def _pairs(what, src, dst):
     return s, d
 
 
+def seg_mats(T):
+    """Matrices of ``map_correct`` as float64 [S, 12]: from [S, 12], [S, 3, 4], [S, 4, 4] (the last row is dropped) or one such."""
+    m = np.asarray(T, dtype=np.float64)
+    if m.ndim >= 2 and m.shape[-2:] == (4, 4):
+        m = m[..., :3, :]
+    if m.size == 0 or m.size % 12:
+        raise ValueError("segment matrices: 12 entries each, at least one")
+    return np.ascontiguousarray(m.reshape(-1, 12))
+
+
 class _SharedEntries:
     """The methods ``HipCtx`` and ``api.Localizer`` share, once; an entry is named by its symbol in libflimo_hip.so (a row of
     ``_abi.PAIRED``).  A class supplies ``_L`` and ``_h`` (library and handle), ``_symbol(entry)`` (the symbol it calls for the
@@ -823,6 +833,71 @@ class _SharedEntries:
         self._entry("flimo_sc_match", _ptr(q), nq, q.shape[1], q.shape[2], int(first), (1 << 62) if n is None else int(n), C.byref(cfg),
                     *(_ptr(out.get(name)) for name in ("idx", "dist", "shift", "cnt", "profile")))
         return out
+
+    def map_segment_mark(self) -> int:
+        """flimo_map_segment_mark: close the open segment of the stored points at the current size and open a new one; returns the
+        new segment's number.  A segment is a run of insertion indices -- a stretch of the drive; the caller marks segment s right
+        before keyframe s's first insert.  FlimoError while the table is stale (``map_segments``).  A ``Localizer`` first waits for
+        an insert, a crop or a carve still running behind the last sweep, so the mark lands behind that sweep's points."""
+        at = C.c_size_t(0)
+        self._entry("flimo_map_segment_mark", C.byref(at))
+        return int(at.value)
+
+    def map_segments(self):
+        """flimo_map_segments: (begin [S + 1] uint64, stale) -- segment s is the insertion indices [begin[s], begin[s + 1]),
+        begin[S] the map's size.  Stale after a removal other than ``map_remove_range`` that removed a point, until
+        ``map_segments_reset`` or ``map_clear``."""
+        n_seg, stale = C.c_size_t(0), C.c_int(0)
+        self._entry("flimo_map_segments", None, 0, C.byref(n_seg), C.byref(stale))
+        begin = np.zeros(int(n_seg.value) + 1, np.uint64)
+        self._entry("flimo_map_segments", _ptr(begin), begin.size, C.byref(n_seg), C.byref(stale))
+        return begin, bool(stale.value)
+
+    def map_segments_reset(self):
+        """flimo_map_segments_reset: one segment over every stored point, not stale."""
+        self._entry("flimo_map_segments_reset")
+
+    def map_corrected(self, T, first=0, n=None, want_xyz=True):
+        """flimo_map_corrected: where the stored points first .. first + n - 1 (``n`` None: up to the map's end) would go under
+        ``map_correct(T)``; ``T`` [S, 12] (or [S, 3, 4]) float64.  Returns (xyz [n, 3] float32 or None, changed: how many have
+        different bits afterwards); changes nothing."""
+        m = seg_mats(T)
+        first, n = self._range(first, n)
+        xyz, changed = (np.zeros((n, 3), np.float32) if want_xyz else None), C.c_size_t(0)
+        self._entry("flimo_map_corrected", _ptr(m), m.shape[0], first, n, _ptr(xyz), C.byref(changed))
+        return xyz, int(changed.value)
+
+    def map_correct(self, T) -> int:
+        """flimo_map_correct: move every stored point by its segment's matrix -- ``T`` [S, 12] (or [S, 3, 4]) float64, row-major
+        3 x 4, new world <- old world (``api.segment_corrections``) -- and rebuild the index once; returns how many points changed
+        bits (0: nothing happened at all).  Size, insertion indices, the segment table and the time of the last insert stay; models
+        built from the old positions are stale afterwards.  A ``Localizer``'s filter pose is the caller's to set (``set_x``)."""
+        m, changed = seg_mats(T), C.c_size_t(0)
+        self._entry("flimo_map_correct", _ptr(m), m.shape[0], C.byref(changed))
+        return int(changed.value)
+
+    def map_transform(self, T) -> int:
+        """flimo_map_transform: ``map_correct`` with the one matrix ``T`` (12 entries, row-major 3 x 4) for every stored point; does
+        not read the segment table.  Returns how many points changed bits."""
+        m, changed = seg_mats(T), C.c_size_t(0)
+        if m.shape[0] != 1:
+            raise ValueError("map_transform: one 3 x 4 matrix")
+        self._entry("flimo_map_transform", _ptr(m), C.byref(changed))
+        return int(changed.value)
+
+    def map_remove_range(self, first, n=None) -> int:
+        """flimo_map_remove_range: forget the stored points first .. first + n - 1 (``n`` None: up to the map's end; cut to the
+        size) -- forgetting by age; afterwards the map is as after ``map_crop_box`` and the segment table has followed exactly.
+        Returns the number of points removed."""
+        removed = C.c_size_t(0)
+        self._entry("flimo_map_remove_range", int(first), (1 << 62) if n is None else int(n), C.byref(removed))
+        return int(removed.value)
+
+    def set_segment_plan(self, slab=0, blocks=0):
+        """The launch of ``map_correct`` / ``map_transform`` / ``map_corrected`` (flimo_set_segment_plan, include/flimo_dev.h), on
+        the map's context; no result depends on it."""
+        hip = getattr(self, "hip", self)
+        hip._chk(hip._L.flimo_set_segment_plan(hip._h, int(slab), int(blocks)))
 
 
 class HipCtx(_SharedEntries):

@@ -762,7 +762,185 @@ def place_relocalize(obj, x26_keyframes, cfg, frame12=None, k=4, first=0, n=None
     return out
 
 
-ALIGN_RUNNING, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2     # scan_align's status per pose: ran every iteration / too few valid pairs / H not positive definite
+def seg_move_host(T, p):
+    """ONE stored point moved by ONE matrix on the host (flimo_seg_move_host: the function the move's kernel calls).  ``T``: 12
+    float64, row-major 3 x 4; ``p``: 3 float32.  Returns float32 [3].  Needs no device."""
+    L = _lib.load_hip()
+    m = np.ascontiguousarray(T, dtype=np.float64).reshape(12)
+    q, out = np.ascontiguousarray(p, dtype=np.float32).reshape(3), np.zeros(3, np.float32)
+    rc = L.flimo_seg_move_host(m.ctypes.data, q.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise FlimoError(f"flimo_seg_move_host failed ({rc})")
+    return out
+
+
+def _pose_mats(x26):
+    """[n, 26] state rows -> [n, 4, 4] float64: R of the normalised quaternion x26[3:7] (x y z w), t = x26[0:3]."""
+    x = np.asarray(x26, np.float64).reshape(-1, 26)
+    q = x[:, 3:7] / np.linalg.norm(x[:, 3:7], axis=1, keepdims=True)
+    qx, qy, qz, qw = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    M = np.zeros((x.shape[0], 4, 4))
+    M[:, 0, 0], M[:, 0, 1], M[:, 0, 2] = 1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw)
+    M[:, 1, 0], M[:, 1, 1], M[:, 1, 2] = 2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw)
+    M[:, 2, 0], M[:, 2, 1], M[:, 2, 2] = 2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)
+    M[:, :3, 3] = x[:, 0:3]
+    M[:, 3, 3] = 1.0
+    return M
+
+
+def segment_corrections(x26_old, x26_new):
+    """The matrices of ``map_correct`` from keyframe poses before and after an optimisation: row s = T_new[s] . T_old[s]^-1 as
+    [n, 12] float64 (row-major 3 x 4, new world <- old world), from ``pos`` and the normalised ``rot`` of each row, all in float64:
+    R = R_new R_old^T, t = t_new - R t_old."""
+    A, B = _pose_mats(x26_old), _pose_mats(x26_new)
+    if A.shape != B.shape:
+        raise ValueError("segment_corrections: as many new poses as old ones")
+    R = B[:, :3, :3] @ np.transpose(A[:, :3, :3], (0, 2, 1))
+    t = B[:, :3, 3] - np.einsum("nij,nj->ni", R, A[:, :3, 3])
+    return np.ascontiguousarray(np.concatenate([R, t[:, :, None]], axis=2).reshape(-1, 12))
+
+
+def _hat(v):
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def _so3_log(R):
+    """The rotation vector of R (float64), angle in [0, pi]."""
+    c = min(1.0, max(-1.0, 0.5 * (R[0, 0] + R[1, 1] + R[2, 2] - 1.0)))
+    w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = 0.5 * float(np.linalg.norm(w))      # sin(angle)
+    th = math.atan2(s, c)
+    if s > 1e-9:
+        return w * (0.5 * th / s)
+    if c > 0.0:
+        return 0.5 * w                       # angle -> 0
+    ax = np.sqrt(np.maximum(0.5 * (np.diag(R) + 1.0), 0.0))      # angle -> pi: the axis from the diagonal, signs from the largest entry's row
+    k = int(np.argmax(ax))
+    for j in range(3):
+        if j != k and R[k, j] + R[j, k] < 0.0:
+            ax[j] = -ax[j]
+    return ax / np.linalg.norm(ax) * th
+
+
+def _so3_jr_inv(phi):
+    """Inverse of SO(3)'s right Jacobian at rotation vector phi: Log(Exp(phi) Exp(d)) = phi + Jr^-1 d + o(d)."""
+    th = float(np.linalg.norm(phi))
+    K = _hat(phi)
+    a = 1.0 / 12.0 if th < 1e-4 else 1.0 / (th * th) - (1.0 + math.cos(th)) / (2.0 * th * math.sin(th))
+    return np.eye(3) + 0.5 * K + a * (K @ K)
+
+
+def _pg_edges(edges, n):
+    out = []
+    for e in edges:
+        a, b, Z = int(e[0]), int(e[1]), np.asarray(e[2], np.float64).reshape(4, 4)
+        w = np.ones(6) if len(e) < 4 or e[3] is None else np.asarray(e[3], np.float64).reshape(6)
+        if not (0 <= a < n and 0 <= b < n) or a == b:
+            raise ValueError("pose_graph_solve: an edge joins two different nodes of the graph")
+        out.append((a, b, Z, w))
+    return out
+
+
+def pose_graph_residuals(M, edges):
+    """Per edge (i, j, Z, w) of ``_pg_edges`` the residual of E = Z^-1 T_i^-1 T_j as (translation of E, rotation vector of E), with
+    the pieces the Jacobians need: (r [6], R_E, R_a, t_a) where (R_a, t_a) = T_i^-1 T_j."""
+    out = []
+    for a, b, Z, _ in edges:
+        Ri, Rj = M[a, :3, :3], M[b, :3, :3]
+        Ra, ta = Ri.T @ Rj, Ri.T @ (M[b, :3, 3] - M[a, :3, 3])
+        Rz = Z[:3, :3]
+        Re, te = Rz.T @ Ra, Rz.T @ (ta - Z[:3, 3])
+        out.append((np.concatenate([te, _so3_log(Re)]), Re, Ra, ta))
+    return out
+
+
+def pose_graph_solve(x26, edges, fixed=0, iters=50, tol=1e-10):
+    """Pose-graph optimisation on the host, in float64 -- a helper like ``scan_align``'s Cholesky, nothing on the GPU.  ``x26``
+    [n, 26]: the nodes (pos and rot are read and written, the rest is copied through); ``edges``: (i, j, Z) or (i, j, Z, w) with Z
+    the measured T_i^-1 T_j as a 4 x 4 matrix and w six weights (translation then rotation; default 1).  Gauss-Newton on SE(3) with
+    the body-frame perturbation of ``pose_retract`` (t += R drho, R <- R Exp(dphi)), dense normal equations, node ``fixed`` held.
+    The cost is sum_e sum_k w_k r_k^2 with r = (translation, rotation vector) of Z^-1 T_i^-1 T_j; a step that would raise it is
+    halved (at most 30 times), so the cost never rises.  Ends after ``iters`` steps, when a step's norm falls below ``tol``, or when
+    no shorter step lowers the cost.  Returns a dict: x26 [n, 26], cost and grad (the cost and the gradient's norm at the start and
+    after every step), iters (steps taken)."""
+    x = np.array(np.asarray(x26, np.float64).reshape(-1, 26))
+    n = x.shape[0]
+    E = _pg_edges(edges, n)
+    fixed = int(fixed)
+    if not 0 <= fixed < n:
+        raise ValueError("pose_graph_solve: `fixed` names no node")
+    free = [k for k in range(n) if k != fixed]
+    col = {k: 6 * c for c, k in enumerate(free)}
+
+    def linearise(x):
+        M = _pose_mats(x)
+        H, g, cost = np.zeros((6 * len(free), 6 * len(free))), np.zeros(6 * len(free)), 0.0
+        for (a, b, Z, w), (r, Re, Ra, ta) in zip(E, pose_graph_residuals(M, E)):
+            cost += float(np.dot(w, r * r))
+            Ji, Jj, Jri = np.zeros((6, 6)), np.zeros((6, 6)), _so3_jr_inv(r[3:6])
+            RzT = Re @ Ra.T
+            Ji[0:3, 0:3], Ji[0:3, 3:6], Ji[3:6, 3:6] = -RzT, RzT @ _hat(ta), -Jri @ Ra.T
+            Jj[0:3, 0:3], Jj[3:6, 3:6] = Re, Jri
+            for (p, Jp) in ((a, Ji), (b, Jj)):
+                if p == fixed:
+                    continue
+                g[col[p]:col[p] + 6] += Jp.T @ (w * r)
+                for (q, Jq) in ((a, Ji), (b, Jj)):
+                    if q != fixed:
+                        H[col[p]:col[p] + 6, col[q]:col[q] + 6] += Jp.T @ (w[:, None] * Jq)
+        return H, g, cost
+
+    def cost_of(x):
+        return sum(float(np.dot(w, r * r)) for (_, _, _, w), (r, _, _, _) in zip(E, pose_graph_residuals(_pose_mats(x), E)))
+
+    H, g, cost = linearise(x)
+    costs, grads, steps = [cost], [float(np.linalg.norm(g))], 0
+    for _ in range(int(iters)):
+        if not free or not E:
+            break
+        try:
+            dx = -np.linalg.solve(H, g)
+        except np.linalg.LinAlgError:
+            dx = -np.linalg.lstsq(H, g, rcond=None)[0]
+        if not np.all(np.isfinite(dx)):
+            break
+        scale, trial = 1.0, None
+        for _ in range(31):
+            trial = np.array(x)
+            for k in free:
+                trial[k] = pose_retract(x[k], scale * dx[col[k]:col[k] + 6])
+            if cost_of(trial) <= cost:
+                break
+            scale, trial = 0.5 * scale, None
+        if trial is None:
+            break
+        x = trial
+        H, g, cost = linearise(x)
+        steps += 1
+        costs.append(cost)
+        grads.append(float(np.linalg.norm(g)))
+        if scale * float(np.linalg.norm(dx)) < tol:
+            break
+    return dict(x26=x, cost=np.array(costs), grad=np.array(grads), iters=steps)
+
+
+def loop_close(obj, x26_keyframes, edges, **solve):
+    """Close a loop: ``pose_graph_solve(x26_keyframes, edges, **solve)``, then ``obj.map_correct(segment_corrections(old, new))``
+    -- every stored point of segment s moves with keyframe s.  Convention: segment 0 is open from the start and holds keyframe 0's
+    points; the caller calls ``map_segment_mark`` right before the first insert of each later keyframe, so segment ids, rows of
+    ``x26_keyframes`` and ``sc_db_add_scan`` ids coincide.  ``obj``: a ``HipCtx`` or a ``Localizer`` (whose filter pose is then the
+    caller's to set, ``set_x``).  Returns a dict: x26 (the new keyframe poses), changed (stored points whose bits changed), T (the
+    matrices), solve (``pose_graph_solve``'s dict)."""
+    old = np.asarray(x26_keyframes, np.float64).reshape(-1, 26)
+    begin, stale = obj.map_segments()
+    if not stale and begin.size - 1 != old.shape[0]:
+        raise ValueError(f"loop_close: {old.shape[0]} keyframes for {begin.size - 1} segments")
+    sol = pose_graph_solve(old, edges, **solve)
+    T = segment_corrections(old, sol["x26"])
+    return dict(x26=sol["x26"], changed=obj.map_correct(T), T=T, solve=sol)
+
+
+ALIGN_RUNNING, ALIGN_FEW, ALIGN_SINGULAR = 0, 1, 2    # scan_align's status per pose: ran every iteration / too few valid pairs / H not positive definite
 
 
 def sym6(H21):

@@ -16,6 +16,7 @@
 #include "flimo_math.h"
 #include "flimo_pose.h"
 #include "flimo_ieskf.h"
+#include "flimo_segment.h"
 
 #pragma clang fp contract(off)
 
@@ -287,6 +288,8 @@ extern "C" int flimo_map_clear(flimo_ctx* c) {
   insert_book_clear(c->book);
   c->gbook.active = false;
   c->prev.valid = 0;               // the pruning bound only survives map ADDITIONS (distances can only shrink)
+  c->seg_begin.assign(1, 0);       // one open segment
+  c->seg_stale = false;
   return FLIMO_OK;
 }
 
@@ -690,9 +693,14 @@ static int map_forget_all(flimo_ctx* c) {
   HIPCHK(c, c->gbook.finish(c->stream, c->scratch));
   const double last_time = c->map_last_time;
   const bool had_center = c->have_fine_center;
+  std::vector<uint64_t> seg_begin;
+  seg_begin.swap(c->seg_begin);                      // (the segment table too: whether it still holds is the caller's to say)
+  const bool seg_stale = c->seg_stale;
   (void)flimo_map_clear(c);
   c->map_last_time = last_time;
   c->have_fine_center = had_center;
+  c->seg_begin.swap(seg_begin);
+  c->seg_stale = seg_stale;
   c->gbook.release();
   index_free(c->idx);
   index_free(c->fine_idx);
@@ -849,6 +857,7 @@ static int map_keep_only(flimo_ctx* c, const float4* kept_pts, size_t kept, size
                          size_t* removed, const char* what) {
   if (kept > n_old) return fail(c, FLIMO_ERR_HIP, "%s: compaction reported %zu of %zu points", what, kept, n_old);
   if (kept == n_old) return FLIMO_OK;
+  c->seg_stale = true;                               // (insertion indices are renumbered; flimo_map_remove_range puts the table right itself)
   c->map_epoch++;
   // ---- clear() ... ----
   const double last_time = c->map_last_time;         // (a crop is no insert)
@@ -916,6 +925,158 @@ extern "C" int flimo_map_crop_box(flimo_ctx* c, const float lo[3], const float h
 extern "C" int flimo_map_crop_stats(const flimo_ctx* c, uint64_t out[2]) {
   if (!c || !out) return FLIMO_ERR_INVALID;
   out[0] = c->crops; out[1] = c->crop_removed;
+  return FLIMO_OK;
+}
+
+// ---- map segments: moving the map after a loop closure, forgetting by age (include/flimo_c.h, "Map segments") -------------------
+// kernel: flimo_segment.hip.  The table is host bookkeeping (flimo_ctx::seg_begin): stored points lie in insertion order, an append
+// and a rebuild from the map's own points both keep that order, so a run of indices is a stretch of the drive at no cost per point.
+extern "C" int flimo_map_segment_mark(flimo_ctx* c, size_t* id) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (c->seg_stale) return fail(c, FLIMO_ERR_NOMAP, "segment mark: the segment table is stale (a removal renumbered the stored points); flimo_map_segments_reset starts it anew");
+  if (c->seg_begin.size() >= FLIMO_SEG_MAX) return fail(c, FLIMO_ERR_TOO_LARGE, "segment mark: %zu segments already", c->seg_begin.size());
+  c->seg_begin.push_back((uint64_t)c->map_n);
+  if (id) *id = c->seg_begin.size() - 1;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_segments(const flimo_ctx* c, uint64_t* begin, size_t cap, size_t* n_seg, int* stale) {
+  if (!c) return FLIMO_ERR_INVALID;
+  const size_t S = c->seg_begin.size();
+  if (n_seg) *n_seg = S;
+  if (stale) *stale = c->seg_stale ? 1 : 0;
+  if (!begin) return FLIMO_OK;
+  if (cap < S + 1) return FLIMO_ERR_INVALID;
+  for (size_t s = 0; s < S; s++) begin[s] = std::min<uint64_t>(c->seg_begin[s], c->map_n);      // (beyond the size only when stale)
+  begin[S] = (uint64_t)c->map_n;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_segments_reset(flimo_ctx* c) {
+  if (!c) return FLIMO_ERR_INVALID;
+  c->seg_begin.assign(1, 0);
+  c->seg_stale = false;
+  return FLIMO_OK;
+}
+extern "C" int flimo_set_segment_plan(flimo_ctx* c, size_t slab, int blocks) {
+  if (!c) return FLIMO_ERR_INVALID;
+  if (blocks < 0 || (slab != 0 && (slab < 256 || slab > SEG_SLAB_MAX || slab % 256 != 0)))
+    return fail(c, FLIMO_ERR_INVALID, "segment plan: slab must be 0 or a multiple of 256 up to %zu, blocks >= 0", SEG_SLAB_MAX);
+  c->seg_slab = slab; c->seg_blocks = blocks;
+  return FLIMO_OK;
+}
+static int seg_check_T(flimo_ctx* c, const double* T, size_t n_seg, const char* what) {
+  if (!T || n_seg == 0) return fail(c, FLIMO_ERR_INVALID, "%s: null matrices", what);
+  for (size_t k = 0; k < n_seg * 12; k++)
+    if (!std::isfinite(T[k])) return fail(c, FLIMO_ERR_INVALID, "%s: entry %zu of matrix %zu is not finite", what, k % 12, k / 12);
+  return FLIMO_OK;
+}
+// the table the calls that read it insist on: not stale, n_seg its length
+static int seg_check_table(flimo_ctx* c, size_t n_seg, const char* what) {
+  if (c->seg_stale) return fail(c, FLIMO_ERR_NOMAP, "%s: the segment table is stale (a removal renumbered the stored points); flimo_map_segments_reset starts it anew", what);
+  if (n_seg != c->seg_begin.size()) return fail(c, FLIMO_ERR_INVALID, "%s: %zu matrices for %zu segments", what, n_seg, c->seg_begin.size());
+  return FLIMO_OK;
+}
+// the stored points [first, first + n) moved by their segments' matrices (begin [S], T [S][12]: host) into d_out (device, may be null);
+// ends synchronised
+static int seg_run(flimo_ctx* c, const uint64_t* begin, const double* T, size_t S, size_t first, size_t n, float4* d_out, size_t* changed,
+                   size_t* bad, float bb[6]) {
+  DevScratch mem;
+  uint64_t* d_begin = mem.get<uint64_t>(S * 13);      // [S] starts, then [S][12] float64
+  { const int rc = mem.ok(c); if (rc) return rc; }
+  double* d_T = reinterpret_cast<double*>(d_begin + S);
+  HIPCHK(c, hipMemcpyAsync(d_begin, begin, S * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_T, T, S * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, seg_move_launch(c->stream, c->d_map_raw, first, n, d_begin, d_T, (uint32_t)S, d_out, c->seg_slab ? c->seg_slab : SEG_SLAB_DEFAULT,
+                            c->seg_blocks ? c->seg_blocks : compact_blocks(c), c->scratch, changed, bad, bb));
+  if (*changed > n || *bad > n) return fail(c, FLIMO_ERR_HIP, "segment move: counted %zu changed and %zu non-finite of %zu points", *changed, *bad, n);
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_corrected(flimo_ctx* c, const double* T, size_t n_seg, size_t first, size_t n, float* xyz, size_t* changed) {
+  if (changed) *changed = 0;
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = seg_check_T(c, T, n_seg, "map corrected"); if (rc) return rc; }
+  { const int rc = seg_check_table(c, n_seg, "map corrected"); if (rc) return rc; }
+  if (first > c->map_n || n > c->map_n - first) return fail(c, FLIMO_ERR_INVALID, "map corrected: [%zu, %zu + %zu) lies beyond the %zu stored points", first, first, n, c->map_n);
+  if (n == 0) return FLIMO_OK;
+  ctx_enter(c);
+  KeptPts moved;
+  if (xyz) HIPCHK(c, hipMalloc(&moved.p, n * sizeof(float4)));
+  size_t chg = 0, bad = 0;
+  float bb[6];
+  { const int rc = seg_run(c, c->seg_begin.data(), T, n_seg, first, n, moved.p, &chg, &bad, bb); if (rc) return rc; }
+  if (xyz) {
+    const int rc = ensure_stage(c, n * sizeof(float4));
+    if (rc) return rc;
+    const float4* st = (const float4*)c->h_stage;
+    HIPCHK(c, hipMemcpyAsync(c->h_stage, moved.p, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; i++) { xyz[3 * i] = st[i].x; xyz[3 * i + 1] = st[i].y; xyz[3 * i + 2] = st[i].z; }
+  }
+  if (changed) *changed = chg;
+  return FLIMO_OK;
+}
+// What flimo_map_correct and flimo_map_transform share: every stored point moved (table and matrices on the host), then -- unless
+// no bit changed -- the map is clear() + initialize(moved points, insertion order, one batch), the removal entries' tail
+// (map_keep_only) with nothing removed.  Whatever can refuse is asked before anything is forgotten.
+static int map_move(flimo_ctx* c, const uint64_t* begin, const double* T, size_t S, size_t* changed, const char* what) {
+  const size_t n = c->map_n;
+  if (n == 0) return FLIMO_OK;
+  ctx_enter(c);
+  KeptPts moved;
+  HIPCHK(c, hipMalloc(&moved.p, n * sizeof(float4)));
+  size_t chg = 0, bad = 0;
+  float bb[6];
+  { const int rc = seg_run(c, begin, T, S, 0, n, moved.p, &chg, &bad, bb); if (rc) return rc; }
+  if (bad) return fail(c, FLIMO_ERR_UNSUPPORTED, "%s: %zu moved points have a component that is not finite in float32", what, bad);
+  if (chg == 0) return FLIMO_OK;
+  GBook fresh;                                          // what an empty book says to the moved points' box, before anything goes
+  if (fresh.admit(bb, c->map_cfg.min_extent) != GBook::ADMIT_OK)
+    return fail(c, FLIMO_ERR_UNSUPPORTED, "%s: octree too deep: the root cube the moved points need is more than %d halvings above 2 * min_extent (%g)",
+                what, GB_MAX_DEPTH, (double)c->map_cfg.min_extent);
+  c->map_epoch++;
+  const double last_time = c->map_last_time;         // (a correction is no insert)
+  int rc = map_forget_all(c);                        // (segment table and second-level centre are carried across)
+  if (rc) return rc;
+  rc = map_add_device(c, moved.p, n, last_time, bb);
+  c->gbook.release_batch_scratch();
+  if (rc) return rc;
+  if (c->map_n != n) return fail(c, FLIMO_ERR_HIP, "%s: %zu of the %zu moved points were stored", what, c->map_n, n);
+  if (changed) *changed = chg;
+  return FLIMO_OK;
+}
+extern "C" int flimo_map_correct(flimo_ctx* c, const double* T, size_t n_seg, size_t* changed) {
+  if (changed) *changed = 0;
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = seg_check_T(c, T, n_seg, "map correct"); if (rc) return rc; }
+  { const int rc = seg_check_table(c, n_seg, "map correct"); if (rc) return rc; }
+  return map_move(c, c->seg_begin.data(), T, n_seg, changed, "map correct");
+}
+extern "C" int flimo_map_transform(flimo_ctx* c, const double T[12], size_t* changed) {
+  if (changed) *changed = 0;
+  if (!c) return FLIMO_ERR_INVALID;
+  { const int rc = seg_check_T(c, T, 1, "map transform"); if (rc) return rc; }
+  const uint64_t whole = 0;
+  return map_move(c, &whole, T, 1, changed, "map transform");
+}
+extern "C" int flimo_map_remove_range(flimo_ctx* c, size_t first, size_t n, size_t* removed) {
+  if (removed) *removed = 0;
+  if (!c) return FLIMO_ERR_INVALID;
+  const size_t n_old = c->map_n;
+  if (first >= n_old || n == 0) return FLIMO_OK;
+  const size_t cnt = std::min(n, n_old - first), kept = n_old - cnt;
+  ctx_enter(c);
+  KeptPts kept_pts;
+  HIPCHK(c, hipMalloc(&kept_pts.p, std::max<size_t>(kept, 1) * sizeof(float4)));
+  if (first) HIPCHK(c, hipMemcpyAsync(kept_pts.p, c->d_map_raw, first * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  if (kept > first)
+    HIPCHK(c, hipMemcpyAsync(kept_pts.p + first, c->d_map_raw + first + cnt, (kept - first) * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const bool was_stale = c->seg_stale;
+  // (no box: the insert measures the two runs' own)
+  const int rc = map_keep_only(c, kept_pts.p, kept, n_old, nullptr, &c->range_removals, &c->range_removed, removed, "remove range");
+  if (rc) return rc;
+  // begin'[s] = begin[s] - |[first, first + cnt) with [0, begin[s])|: exact, so the table is as valid as it was
+  for (uint64_t& b : c->seg_begin) b -= std::min<uint64_t>(b > first ? b - first : 0, cnt);
+  c->seg_stale = was_stale;
   return FLIMO_OK;
 }
 

@@ -46,6 +46,13 @@ struct flimo_ctx {
   uint64_t plane_removals = 0, plane_removed = 0;       // flimo_map_remove_plane: the same
   uint64_t thin_removals = 0, thin_removed = 0;         // flimo_map_thin: the same
   uint64_t region_removals = 0, region_removed = 0;     // flimo_map_remove_regions: the same
+  uint64_t range_removals = 0, range_removed = 0;       // flimo_map_remove_range: the same
+  // map segments (include/flimo_c.h): segment s is the insertion indices [seg_begin[s], seg_begin[s + 1]), the last one open up to
+  // map_n; host bookkeeping only.  seg_stale: a removal renumbered the points and the table no longer says where a stretch lies
+  std::vector<uint64_t> seg_begin{0};
+  bool seg_stale = false;
+  size_t seg_slab = 0;             // flimo_set_segment_plan: points per workgroup and step of the move (0: SEG_SLAB_DEFAULT) ...
+  int seg_blocks = 0;              // ... and its grid (0: two workgroups a compute unit); neither changes a result
   bool have_origin = false;        // the origin of the map's cells is set (GridView: it stays; a grid that grows moves its corner by whole cells)
   size_t map_n = 0, map_cap = 0, sorted_cap = 0;
   size_t normals_chunk = (size_t)1 << 20;   // queries per launch of flimo_map_normals (flimo_set_normals_chunk): bounds its device scratch

@@ -135,9 +135,11 @@ struct MapBuildScratch {
   // the range image of a carve (carve_image): [6][res][res] depth bits, then the count word of carve_mask; grown on demand
   unsigned int* carve_img = nullptr;
   size_t carve_img_words = 0;
+  // the two counts of a move (seg_move_launch, flimo_segment.hip): points changed, points not finite; zero whenever none is running
+  uint32_t* seg_cnt = nullptr;
 };
 // slots of the mail words
-enum MailSlot { MAIL_BOOK = 0 /* 6 */, MAIL_BOOK_END = 8 /* 2 */, MAIL_CROWD = 12, MAIL_BOXCOUNT = 13, MAIL_BBOX = 16 /* 6 */, MAIL_VOXEL = 24 /* 4 */, MAIL_TILES = 28 /* build: tiles, overflow; merge: tiles, overflow */, MAIL_ROWS = 32 /* an insert found the point array or the escape pool full */, MAIL_ESCAPES = 33 /* escape slots a full layout asked for */, MAIL_CROP = 36 /* kept count of a crop */, MAIL_CARVE = 37 /* points a scan sees through */,
+enum MailSlot { MAIL_BOOK = 0 /* 6 */, MAIL_BOOK_END = 8 /* 2 */, MAIL_CROWD = 12, MAIL_BOXCOUNT = 13, MAIL_BBOX = 16 /* 6 */, MAIL_VOXEL = 24 /* 4 */, MAIL_TILES = 28 /* build: tiles, overflow; merge: tiles, overflow */, MAIL_ROWS = 32 /* an insert found the point array or the escape pool full */, MAIL_ESCAPES = 33 /* escape slots a full layout asked for */, MAIL_CROP = 36 /* kept count of a crop */, MAIL_CARVE = 37 /* points a scan sees through */, MAIL_SEG = 38 /* 2: points a move changes, points it leaves not finite */,
                 MAIL_TAG = 62 /* number of the last mail_words, written behind its words */, MAIL_WORDS = 64 };
 struct MailPart { const void* src; int n; int dst; };
 // queues ONE small kernel that copies up to 6 runs of words into the mail slots; `rearm_bbox`: S.bbox is reset to the empty box

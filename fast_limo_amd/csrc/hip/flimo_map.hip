@@ -1995,6 +1995,7 @@ void map_scratch_free(MapBuildScratch& S) {
   if (S.filt_desc) hipFree(S.filt_desc);
   if (S.crop_desc) (void)hipFree(S.crop_desc);
   if (S.carve_img) (void)hipFree(S.carve_img);
+  if (S.seg_cnt) (void)hipFree(S.seg_cnt);
   if (S.filt_mail_host) hipHostFree(S.filt_mail_host);
   if (S.mail_host) hipHostFree(S.mail_host);
   S = MapBuildScratch();

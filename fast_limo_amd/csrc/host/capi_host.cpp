@@ -426,6 +426,34 @@ int flimo_loc_sc_match(flimo_loc* L, const float* q, size_t nq, int rings, int s
   if (!L) return FLIMO_ERR_INVALID;
   return flimo_sc_match(ctx_of(L), q, nq, rings, sectors, first, n, cfg, idx, dist, shift, cnt, profile);
 }
+int flimo_loc_map_segment_mark(flimo_loc* L, size_t* id) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_segment_mark(ctx_of(L), id);
+}
+int flimo_loc_map_segments(flimo_loc* L, uint64_t* begin, size_t cap, size_t* n_seg, int* stale) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_segments(ctx_of(L), begin, cap, n_seg, stale);
+}
+int flimo_loc_map_segments_reset(flimo_loc* L) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_segments_reset(ctx_of(L));
+}
+int flimo_loc_map_corrected(flimo_loc* L, const double* T, size_t n_seg, size_t first, size_t n, float* xyz, size_t* changed) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_corrected(ctx_of(L), T, n_seg, first, n, xyz, changed);
+}
+int flimo_loc_map_correct(flimo_loc* L, const double* T, size_t n_seg, size_t* changed) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_correct(ctx_of(L), T, n_seg, changed);
+}
+int flimo_loc_map_transform(flimo_loc* L, const double T[12], size_t* changed) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_transform(ctx_of(L), T, changed);
+}
+int flimo_loc_map_remove_range(flimo_loc* L, size_t first, size_t n, size_t* removed) {
+  if (!L) return FLIMO_ERR_INVALID;
+  return flimo_map_remove_range(ctx_of(L), first, n, removed);
+}
 int flimo_loc_last_sweep_tied(const flimo_loc* L) { return (L && L->loc->last_sweep_tied()) ? 1 : 0; }
 void flimo_loc_set_propagation_wait(flimo_loc* L, double seconds) { if (L) L->loc->propagation_wait_s = seconds; }
 // the map insert that ends a scan runs on the Mapper's worker thread (Mapper::add_scan): wait for it / switch it off

@@ -1326,6 +1326,62 @@ int flimo_scan_debug_clouds(flimo_ctx* ctx, const double x26_final[26], const fl
                             const float** final_raw_xyzw, size_t* n);
 int flimo_map_add_scan(flimo_ctx* ctx, const double x26[26], double stamp);
 
+/* ---- Map segments: moving the map after a loop closure, forgetting by age (no counterpart in the reference) ----
+ * Stored points lie in insertion order, and that order survives both an append and a rebuild of the map from its own points.  So a
+ * run of insertion indices is a stretch of the drive, at zero bytes per point.  A context keeps a table begin[0 .. S], S >= 1,
+ * begin[0] = 0: segment s is the stored points with insertion index in [begin[s], begin[s + 1]); begin[S] is flimo_map_size, so
+ * the last segment is open and grows with every add.  A fresh context and one after flimo_map_clear have S = 1.  The table is host
+ * bookkeeping; no device memory, no change to the insert.
+ *
+ * The table stays valid through every call that adds (also a batch that meets the zero-size root, which stores all points again in
+ * order), through flimo_map_correct / flimo_map_transform (same points, same indices) and through flimo_map_remove_range (which
+ * shifts the boundaries exactly).  It goes STALE with every other removal that removed at least one point -- crop, carve,
+ * remove_outliers / _clusters / _plane / _regions, thin: they renumber the points and report no count per boundary.  With a stale
+ * table flimo_map_segment_mark, flimo_map_correct and flimo_map_corrected answer FLIMO_ERR_NOMAP ("... stale ...") until
+ * flimo_map_segments_reset or flimo_map_clear.
+ *
+ * flimo_map_segment_mark: closes the open segment at the current size and opens a new one; *id (may be NULL) = its number.  Empty
+ *   segments are allowed.  FLIMO_ERR_TOO_LARGE at FLIMO_SEG_MAX segments.
+ * flimo_map_segments: *n_seg = S, *stale = 0 / 1, begin[0 .. S] (all three may be NULL: ask with begin = NULL for the count);
+ *   FLIMO_ERR_INVALID for cap < S + 1 with a non-NULL begin.
+ * flimo_map_segments_reset: one segment over everything, not stale.
+ *
+ * The move.  T is a row-major 3 x 4 float64 matrix, new world <- old world, applied as given (rigidity is the caller's business).
+ * With X = (double)x and so on, r_k = T[4k] * X + (T[4k+1] * Y + (T[4k+2] * Z + T[4k+3])), every operation float64 with one
+ * rounding and nothing contracted; the moved component is (float)r_k.  flimo_seg_move_host runs the device's function on the host;
+ * tests/segments_common.py restates it in numpy, bit for bit.  The result depends on nothing else: not the launch shape, not the
+ * table's length.
+ *
+ * flimo_map_corrected: the predicate alone.  xyz [n][3] (may be NULL) = where the stored points [first, first + n) would go, each
+ *   by its segment's matrix T[s]; *changed (may be NULL) = how many of them have different bits afterwards.  n_seg must equal S.
+ *   Changes nothing: not the map, not the scan, not the bits of a later pass.
+ * flimo_map_correct: every stored point moves by its segment's matrix; n_seg must equal S.  If no point's bits change, nothing
+ *   happens at all (index and epoch stay, as after a crop that removes nothing).  Otherwise the map is clear() + initialize(moved
+ *   points, insertion order, one batch): same size, same insertion indices (the table stays valid), flimo_map_last_time untouched
+ *   (a correction is no insert), the second level stays around the sensor; everything that names old positions goes as after a
+ *   crop (the last pass's records, the pruning bound, a queued pass), a GICP model is stale afterwards (flimo_scan_gicp refuses it)
+ *   and flimo_ndt_info reports stale.  The Scan Context database and the resident scan are untouched.  The FILTER'S POSE IS THE
+ *   CALLER'S TO SET after a correction (flimo_loc_set_x): the map moved under it.
+ *   A failed call leaves the map exactly as it was: FLIMO_ERR_UNSUPPORTED when a moved component is not finite in float32, or when
+ *   a fresh octree would refuse the moved points' box ("octree too deep", flimo_map_add) -- both known before anything is forgotten.
+ *   FLIMO_ERR_INVALID for a NULL T, a non-finite entry of T, n_seg != S.  An empty map: FLIMO_OK, *changed = 0.
+ * flimo_map_transform: the same with ONE matrix for every point (a second session registered into this one's frame).  It does not
+ *   read the table: it works on a stale one and leaves table and flag alone.
+ * flimo_map_remove_range: forgetting by age.  The stored points [first, first + n) go (the range is cut to the size); afterwards
+ *   everything is as flimo_map_crop_box documents.  The table follows exactly -- begin'[s] = begin[s] - |[first, first + n) with
+ *   [0, begin[s])| -- and is not marked stale.
+ * Calling rules of the four: those of flimo_map_crop_box, no pass of this context in flight. */
+#define FLIMO_SEG_MAX ((size_t)1 << 20)
+int flimo_map_segment_mark(flimo_ctx* ctx, size_t* id);
+int flimo_map_segments(const flimo_ctx* ctx, uint64_t* begin, size_t cap, size_t* n_seg, int* stale);
+int flimo_map_segments_reset(flimo_ctx* ctx);
+int flimo_seg_move_host(const double T[12], const float p[3], float out[3]);
+int flimo_map_corrected(flimo_ctx* ctx, const double* T /* [n_seg][12] */, size_t n_seg, size_t first, size_t n, float* xyz /* [n][3] */,
+                        size_t* changed);
+int flimo_map_correct(flimo_ctx* ctx, const double* T /* [n_seg][12] */, size_t n_seg, size_t* changed);
+int flimo_map_transform(flimo_ctx* ctx, const double T[12], size_t* changed);
+int flimo_map_remove_range(flimo_ctx* ctx, size_t first, size_t n, size_t* removed);
+
 /* Wall-clock bound (milliseconds, default 2000) of the wait for a pass's result inside flimo_match_reduce: the reference's
  * Mapper::match (Modules/Mapper.cpp:59-86) cannot hang, a GPU launch can -- when the bound expires the call returns
  * FLIMO_ERR_TIMEOUT (kernel still running) or FLIMO_ERR_HIP (stream idle, nothing published) instead of blocking its caller,

@@ -66,6 +66,10 @@ int flimo_map_crop_stats(const flimo_ctx* ctx, uint64_t out[2]);
 /* flimo_map_carve so far: out[0] = calls that removed points (each one full layout), out[1] = points removed.  (flimo_map_crop_stats
  * counts crops only: a carve with a box is a carve.) */
 int flimo_map_carve_stats(const flimo_ctx* ctx, uint64_t out[2]);
+/* The launch of flimo_map_correct / flimo_map_transform / flimo_map_corrected: slab = stored points a workgroup takes per step (a
+ * multiple of 256 up to 16384; 0: the default, 2048), blocks = workgroups (0: two a compute unit).  Neither changes a result
+ * (tests, A/B). */
+int flimo_set_segment_plan(flimo_ctx* ctx, size_t slab, int blocks);
 /* flimo_radius_search's walk, counted: cand[i] = stored points query i's walk loads and tests at this radius (what the count and
  * the fill launch each read, 16 bytes apiece); cand: host, [nq].  Arguments as flimo_radius_search. */
 int flimo_radius_candidates(flimo_ctx* ctx, const float* q_xyz, size_t nq, float radius, uint64_t* cand);

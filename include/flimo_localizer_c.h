@@ -237,6 +237,19 @@ int    flimo_loc_sc_db_get(flimo_loc* L, size_t first, size_t n, float* desc);
 int    flimo_loc_sc_db_clear(flimo_loc* L);
 int    flimo_loc_sc_match(flimo_loc* L, const float* q, size_t nq, int rings, int sectors, size_t first, size_t n,
                           const flimo_sc_match_cfg* cfg, int32_t* idx, float* dist, int32_t* shift, int32_t* cnt, float* profile);
+/* Map segments on the Localizer's map (the reference has no loop closure): flimo_map_segment_mark / flimo_map_segments /
+ * flimo_map_segments_reset / flimo_map_corrected / flimo_map_correct / flimo_map_transform / flimo_map_remove_range
+ * (include/flimo_c.h: same arguments, same results, same error codes) on the map's context, after an insert, a crop or a carve
+ * still running behind the last sweep has ended -- so a mark lands behind the last sweep's points.  The local map's crops and the
+ * carving policy make the table stale like any removal.  THE FILTER'S POSE IS THE CALLER'S TO SET after a correction
+ * (flimo_loc_set_x): the map moved, the state did not.  There is no policy that calls them. */
+int    flimo_loc_map_segment_mark(flimo_loc* L, size_t* id);
+int    flimo_loc_map_segments(flimo_loc* L, uint64_t* begin, size_t cap, size_t* n_seg, int* stale);
+int    flimo_loc_map_segments_reset(flimo_loc* L);
+int    flimo_loc_map_corrected(flimo_loc* L, const double* T, size_t n_seg, size_t first, size_t n, float* xyz, size_t* changed);
+int    flimo_loc_map_correct(flimo_loc* L, const double* T, size_t n_seg, size_t* changed);
+int    flimo_loc_map_transform(flimo_loc* L, const double T[12], size_t* changed);
+int    flimo_loc_map_remove_range(flimo_loc* L, size_t first, size_t n, size_t* removed);
 int    flimo_loc_last_sweep_tied(const flimo_loc* L);      /* 1: the last sweep of the device front end had equal stamps */
 /* how long updatePointCloud waits for the IMU stream to reach the end of the sweep (Localizer::propagatedFromTimeRange,
  * Localizer.cpp:855-871).  The reference waits on its condition variable without bound, and so does fast_limo::Localizer used
